@@ -2,7 +2,7 @@
 """Benchmark of the hot path: clips/sec of one full harness step.  Default = BASELINE config 2
 ([B=8 per GPU, T=16, 3, 224, 224], 4-stage CNN 32-64-128-256 + 2-layer transformer d=512 h=8, bf16).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,4,5}] [--dtype {bf16,fp32}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,4,5}] [--dtype {bf16,fp32}] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no launcher environment starts the N ranks ITSELF (a child `python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` of this same file, before this process touches the GPU), forwards
@@ -11,11 +11,15 @@ one rank of that job.
 
 A step = zero_grad -> forward -> cross-entropy -> backward -> (RCCL gradient all-reduce when N>1) -> AdamW.step, i.e. the
 reference harness inner loop (Model.py:55-59 / FCT.py:328-338) with nothing skipped; synthetic clips are resident in HBM
-before the timed region.  Rank 0 prints ONE JSON line (see the task contract) including
+before the timed region.  Rank 0 prints ONE JSON line (see the task contract).  A plain run sets up, warms up, times the K steps
+and prints the headline; `--dump-outputs DIR` also writes what the last timed step computed (loss, logits, gradients, updated
+parameters and BatchNorm statistics) as DIR/<name>.npy in float32.  `--full` adds everything else to the line:
 
   "fwd_bwd_only": the same K steps without zero_grad/AdamW (the metric's literal "fwd+bwd"), timed right after the headline
   "roofline":     the dominant HIP kernel, timed live with events on the launch stream, against the MI355X peak
   "cpu_baseline": the CPU oracle (oracle/hybrid_ref.py, kind "port") timed on the host cores on a bounded sample
+  and the PCIe-inclusive leg, the kernel table and the extra legs (configs 4 / 5, the other precision modes, FCT, Encoder_32K, the
+  in-run logits check); the --no-* options trim a --full run.
 
 Configs (BASELINE.json `configs`; config 2 is the one the metric is quoted on, the others are labelled in config.workload):
   2  [8,16,3,224,224]  d=512 h=8 hid=2048      4  [8,64,3,224,224]  d=768 h=8 hid=3072      5  [4,16,3,448,448]  d=512 h=8 hid=2048
@@ -71,7 +75,13 @@ def parse(argv=None):
                                                                  "modes, FCT, Encoder_32K, config-1 CPU baseline, the in-run bf16 logits check)")
     ap.add_argument("--eager", action="store_true", help="issue every launch from Python each step instead of replaying the captured hipGraphs "
                                                          "(graph.GraphedTrainStep); same kernels and arithmetic, more host time")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: fwd+bwd-only, PCIe-inclusive leg, roofline and "
+                                                        "kernel table, CPU baseline, the extra legs (trimmed by the --no-* options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args(argv)
+    if not args.full:           # a plain run: the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_fwd_bwd_only = args.no_pipeline = args.no_live_traffic = args.no_extra_legs = True
     c = CONFIGS[args.config]
     for flag, key in (("batch", "batch"), ("frames", "frames"), ("size", "size"), ("d_model", "d_model"), ("heads", "num_heads"), ("hidden", "hidden_dim")):
         if getattr(args, flag) is None:
@@ -707,6 +717,32 @@ def live_traffic(kernel_name, timeout_s=150):
         "passes); FETCH_SIZE x 2 (gfx950 correction) + WRITE_SIZE, KiB units, average over this kernel's launches")
 
 
+DUMP_LIMIT_BYTES = 60 << 20         # --dump-outputs: the arrays together (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: tensor} as outdir/<name>.npy in float32.  If the arrays together exceed DUMP_LIMIT_BYTES, every tensor of more than
+    4096 elements keeps the same fraction of its (flattened) elements, at positions drawn by a generator seeded with 0 and kept in index
+    order: the same positions in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    small = sum(t.numel() for t in host.values() if t.numel() <= 4096) * 4
+    large = sum(t.numel() for t in host.values() if t.numel() > 4096) * 4
+    frac = min(1.0, (DUMP_LIMIT_BYTES - small) / large) if large else 1.0
+    total = 0
+    for name, t in host.items():
+        if frac < 1.0 and t.numel() > 4096:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:int(t.numel() * frac)].sort().values
+            t = t.reshape(-1)[idx]
+        a = t.numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": outdir, "arrays": len(host), "bytes": total, "sampled": frac < 1.0,
+            "what": "the last timed step: loss, logits, gradients, updated parameters, BatchNorm running statistics (float32)"
+                    + (f"; tensors of more than 4096 elements sampled to {frac:.3f} of their elements, seeded" if frac < 1.0 else "")}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -787,12 +823,15 @@ def main():
                 p_.grad = None
             trainer, graphed = None, False
             reducer = GradAllReducer(model) if world > 1 else None
+    eager_logits = [None]                            # the eager step's last logits (graphed: trainer.logits, a static tensor)
     if graphed:
         step, fwd_bwd = trainer.step, trainer.fwd_bwd
     else:
         def step():
             opt.zero_grad(set_to_none=True)
-            loss = crit(model(x), y)
+            logits = model(x)
+            eager_logits[0] = logits.detach()
+            loss = crit(logits, y)
             loss.backward()
             if reducer is not None:
                 reducer.finalize()
@@ -837,6 +876,13 @@ def main():
     gc.freeze()
     dt, loss = timed(step, args.steps)
     final_loss = float(loss.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:              # before anything else runs a step: what the last timed step left
+        arrays = {"loss": loss, "logits": trainer.logits if graphed else eager_logits[0]}
+        arrays.update((f"grad.{n}", p.grad) for n, p in model.named_parameters() if p.grad is not None)
+        arrays.update((f"param.{n}", p) for n, p in model.named_parameters())
+        arrays.update((f"buffer.{n}", b) for n, b in model.named_buffers() if b.is_floating_point())
+        dumped = dump_outputs(args.dump_outputs, arrays)
     fb = None
     if not args.no_fwd_bwd_only:
         fwd_bwd()
@@ -898,10 +944,12 @@ def main():
                        "train_mode": "BatchNorm batch stats, attention dropout 0.1 (reference semantics)",
                        "logits_parity": "north_star's 1e-3 rel vs the CPU oracle is met by compute_dtype fp32 (exact fp32 MFMA), bf16x3 (split-bf16 "
                                         "products) and mixed (bf16 conv stages + bf16x3 temporal part); bf16 mode is at bf16 rounding level -- all four "
-                                        "measured in this run: key logits_check"},
+                                        "measured by a --full run: key logits_check"},
             "final_loss": final_loss,
             "graph_fallback": bool(graph_fallback),
         }
+        if dumped is not None:
+            out["outputs"] = dumped
         if fb is not None:
             out["fwd_bwd_only"] = fb
         if fed is not None:
@@ -934,7 +982,7 @@ def main():
                                     "GBps": round(r["bytes"] / (r["ms"] * 1e-3) / 1e9, 1)} for r in rows]
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args)
-        # the extra legs belong to the plain command (what the driver runs); the trimmed forms the profiling scripts use skip them
+        # the extra legs belong to the untrimmed --full command; the trimmed forms the profiling scripts use skip them
         if not (args.no_extra_legs or args.no_roofline or args.no_cpu_baseline or args.eager) and world == 1 and is_cfg and args.config == 2 and args.dtype == "bf16":
             # free the headline's model and graphs first: config 4 wants the memory
             if graphed:
