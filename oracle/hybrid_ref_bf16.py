@@ -23,7 +23,8 @@ an L2 discrepancy eps << u = 2^-8 becomes sqrt(eps * u) after the next rounding 
 flips by a whole ulp), so any two implementations with identical rounding points but different summation order drift to
 bf16-noise-level differences after a handful of stages (measured: logits 5-7e-3 apart at full size, the same order as
 either one's distance from the fp32 oracle).  The full-size tests report both distances (tests/test_gpu_fullsize.py).
-Dropout is not modelled: parity runs use p = 0 (decision 4).  The functions follow the dtype of the
+Dropout is not drawn here: parity runs use p = 0 (decision 4), and the train-mode tests pass the kernels' own
+masks in (``mha`` / ``encoder``'s mask arguments, replayed by oracle/dropout_masks.py).  The functions follow the dtype of the
 model they are given: on a ``.double()`` copy of the oracle the accumulation is fp64 (rounding points unchanged), which takes
 the host's own fp32 summation error out of the comparison (tests/test_gpu_fullsize.py).
 """
@@ -81,8 +82,14 @@ def _linear(x, lin, relu=False):
     return rb(torch.relu(y) if relu else y)
 
 
-def _mha(att, x, mask, k_in=None, v_in=None):
-    """MultiheadAttention.forward(q, k, v, mask) (k = v = q unless given), src L67-89 (attention core L49-62, head split L22-45)."""
+def _mask(m, like):
+    return torch.as_tensor(m).to(dtype=like.dtype, device=like.device)
+
+
+def _mha(att, x, mask, k_in=None, v_in=None, drop=None):
+    """MultiheadAttention.forward(q, k, v, mask) (k = v = q unless given), src L67-89 (attention core L49-62, head split L22-45).
+    drop: attention-weight dropout multipliers [B*H, S, S] (oracle/dropout_masks.py) or None.  The short kernels multiply the fp32
+    probability and round the product once, as the P.V operand."""
     B, S, D = x.shape
     H = att.num_heads
     dh = D // H
@@ -96,23 +103,31 @@ def _mha(att, x, mask, k_in=None, v_in=None):
     dot = rg(torch.matmul(q, k.transpose(-2, -1))) / math.sqrt(att.input_dim)
     if mask is not None:
         dot = dot.masked_fill(mask.repeat(H, 1, 1) == 0, -1e9)
-    w = rv(torch.softmax(dot, dim=-1))                  # the probabilities are kept in fp32; the P.V operand is bf16
+    w = torch.softmax(dot, dim=-1)
+    if drop is not None:
+        w = w * _mask(drop, w)
+    w = rv(w)                                           # the probabilities are kept in fp32; the P.V operand is bf16
     a = rb(torch.matmul(w, v))
     a = a.reshape(B, H, S, dh).permute(0, 2, 1, 3).reshape(B, S, D)
     return _linear(a, att.output_layer)
 
 
-def _encoder(enc, x, mask):
-    """TransformerEncoder.forward, src L110-126 (dropout p must be 0)."""
-    assert enc.dropout == 0.0
+def _encoder(enc, x, mask, attn_masks=None, layer_masks=None):
+    """TransformerEncoder.forward, src L110-126.  Without masks dropout p must be 0; attn_masks / layer_masks (one entry per layer,
+    oracle/dropout_masks.py) inject the kernels' dropout: the LayerNorm-row kernels multiply the fp32 value and store the product in bf16."""
+    masked = attn_masks is not None or layer_masks is not None
+    assert masked or enc.dropout == 0.0
     for i in range(enc.num_layers):
         att, ff, ln = enc.attention_layers[i], enc.feedforward_layers[i], enc.layer_norm[i]
-        assert not (att.training and att.dropoutLayer.p > 0.0)
+        assert masked or not (att.training and att.dropoutLayer.p > 0.0)
         skip1 = x
-        x = rb(ln(_mha(att, x, mask)) + skip1)
+        x = rb(ln(_mha(att, x, mask, drop=attn_masks[i] if attn_masks else None)) + skip1)
         skip2 = x
         f = _linear(_linear(x, ff[0], True), ff[2])
-        x = rb((ln(f) + skip2) * math.sqrt(0.5))
+        x = (ln(f) + skip2) * math.sqrt(0.5)
+        if layer_masks and layer_masks[i] is not None:
+            x = x * _mask(layer_masks[i], x)
+        x = rb(x)
     return x
 
 
@@ -134,9 +149,9 @@ def conv_stage(seq, name, x, first, training):
     return _conv_stage(seq, name, x, first, training)
 
 
-def encoder(enc, x, mask):
-    return _encoder(enc, rb(x), mask)
+def encoder(enc, x, mask, attn_masks=None, layer_masks=None):
+    return _encoder(enc, rb(x), mask, attn_masks, layer_masks)
 
 
-def mha(att, q, k, v, mask):
-    return _mha(att, rb(q), mask, rb(k), rb(v))
+def mha(att, q, k, v, mask, drop=None):
+    return _mha(att, rb(q), mask, rb(k), rb(v), drop)

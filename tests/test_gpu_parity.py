@@ -298,7 +298,11 @@ def test_multihead_attention_matches_oracle(mode, B, S, D, H, use_mask):
 @pytest.mark.parametrize("B,S,D,Hid,L,H,use_mask", [(2, 16, 64, 128, 2, 4, False), (1, 7, 32, 40, 1, 2, True), (8, 16, 512, 2048, 2, 8, False),
                                                     (2, 96, 64, 128, 2, 4, False), (2, 128, 128, 256, 1, 4, True),           # T = 96, 128 tokens
                                                     # deeper stacks: the weight gradients go layer by layer (one launch each) instead of one launch for all
-                                                    (2, 16, 64, 128, 3, 4, False), (1, 8, 32, 64, 4, 2, True)])
+                                                    (2, 16, 64, 128, 3, 4, False), (1, 8, 32, 64, 4, 2, True),
+                                                    # bf16: the LayerNorm fused into the next GEMM's prologue with the wide row image (gemm_nt_ln<2>,
+                                                    # 513 <= D <= 1008; M = 27 a ragged row tile, D = 520 a ragged column tile), and D = 1024 just past it
+                                                    (2, 16, 768, 1024, 2, 8, False), (3, 9, 768, 1024, 2, 8, False), (2, 20, 1008, 1024, 2, 9, False),
+                                                    (2, 20, 1024, 1024, 2, 8, False), (2, 8, 520, 512, 2, 5, False)])
 def test_transformer_encoder_matches_oracle(mode, B, S, D, Hid, L, H, use_mask):
     ftol, gtol = TOL[mode]
     torch.manual_seed(3)

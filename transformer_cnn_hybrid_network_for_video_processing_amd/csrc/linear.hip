@@ -918,7 +918,7 @@ int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* 
 
 // Internal: hyb_gemm_nt with LayerNorm + residual as the prologue (gemm_nt_ln_kernel): A = dropout((LN(x) * gamma + beta + skip) * out_scale),
 // also written to y (+ stats [2][Mo]) by the column-0 workgroups.  Returns -100 when the shape is not taken (the caller then runs the two
-// launches): bf16 only, few-tile grids (every column tile re-forms its rows), R = D a multiple of 8 up to 1024 with the image in 64 KB of LDS.
+// launches): bf16 only, few-tile grids (every column tile re-forms its rows), R = D a multiple of 8, 256 .. 1008 (the 32 x (R + 16) bf16 row image must fit in 64 KB of LDS; R = 1024 does not).
 int hyb_gemm_nt_ln(int dtype, int groups, const void* x, const void* skip, const float* gamma, const float* beta, void* y, float* stats, float eps,
                    float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const void* const* B, void* const* C,
                    const float* const* bias, int Mo, int No, int R, int ldb, int ldc, int relu, hipStream_t st) {
