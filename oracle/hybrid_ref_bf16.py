@@ -139,8 +139,14 @@ def forward(ref, x, mask=None):
     f = x.reshape(B * T, *x.shape[2:])
     for i in range(ref.num_stages):
         f = _conv_stage(getattr(ref, f"encoder{i + 1}"), f"enc{i + 1}", f, i == 0, ref.training)
+    return temporal(ref, f, B, mask)
+
+
+def temporal(ref, f, B, mask=None):
+    """The temporal half of ``forward``: last pooled map f [B*T, C, Hh, Ww] (values the bf16 path stores: already bf16-representable)
+    -> logits [B, classes].  Global average pool -> token projection -> encoder -> mean over frames -> head."""
     feat = rb(f.mean(dim=(2, 3)))
-    tok = _linear(feat, ref.token_proj).reshape(B, T, -1)
+    tok = _linear(feat, ref.token_proj).reshape(B, f.shape[0] // B, -1)
     enc = _encoder(ref.encoder, tok, mask)
     return F.linear(enc.mean(dim=1), ref.head.weight, ref.head.bias)       # the head runs in fp32 on the stored bf16 tokens
 

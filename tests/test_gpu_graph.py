@@ -1,5 +1,7 @@
 """GraphedTrainStep: the training step as replayed hipGraphs must be the eager step, bit for bit, and must advance what eager
 advances per step (dropout masks, AdamW's step number, BatchNorm running statistics)."""
+import math
+
 import pytest
 import torch
 
@@ -141,5 +143,69 @@ def test_graphed_long_clip_steps_equal_eager_and_redraw_masks():
     try:
         losses = [tr.step().item() for _ in range(4)]
         assert len(set(losses)) == len(losses) and all(l == l for l in losses)
+    finally:
+        tr.close()
+
+
+def _spy_on_ce_scratch(monkeypatch):
+    """Fresh scratch cache + a wrapper of ops._ce_scratch that records (cache miss, stream is capturing) per call."""
+    from transformer_cnn_hybrid_network_for_video_processing_amd import ops
+    monkeypatch.setattr(ops, "_CE_SCRATCH", {})
+    calls, orig = [], ops._ce_scratch
+
+    def spy(B, device):
+        miss = (device.index, ops._stream(), B) not in ops._CE_SCRATCH
+        calls.append((miss, torch.cuda.is_current_stream_capturing()))
+        return orig(B, device)
+    monkeypatch.setattr(ops, "_ce_scratch", spy)
+    return ops, calls
+
+
+def test_fused_loss_scratch_is_never_created_under_capture(monkeypatch):
+    """The ticket word behind the fused loss's per-clip terms has to be zero before the first hyb_temporal_ce_fwd call on it, and no captured
+    launch zeroes it.  A buffer first created while its stream captures gets its zero-fill as a node of that one graph: the graph step()
+    replays would reuse it with the fill never executed.  So: every call made while capturing must find its buffer in the cache."""
+    ops, calls = _spy_on_ce_scratch(monkeypatch)
+    m, x, y = _setup(0.0, 0.0)
+    opt = P().HybridAdamW(m.parameters(), lr=1e-3)
+    tr = P().GraphedTrainStep(m, P().HybridCrossEntropyLoss(), opt, x, y, warmup=2)
+    try:
+        for _ in range(4):
+            tr.step()
+        torch.cuda.synchronize()
+    finally:
+        tr.close()
+    capturing = [c for c in calls if c[1]]
+    assert len(capturing) >= 2, calls                  # graph A and the one-graph step both hold the fused loss
+    assert len(calls) - len(capturing) == 2, calls     # the two eager warm-up steps; replays make no Python call
+    assert not any(miss for miss, cap in calls if cap), calls
+    assert ops._CE_SCRATCH and all(int(t[-1].view(torch.int32).item()) == 0 for t in ops._CE_SCRATCH.values())
+
+
+@pytest.mark.parametrize("mode", ["bf16", "mixed"])
+def test_step_alone_returns_the_eager_loss_and_leaves_the_ticket_zero(monkeypatch, mode):
+    """step() with no fwd_bwd() before it (the benchmarked use): graph A, whose capture used to hold the scratch buffer's only zero-fill, is never
+    replayed.  The first replayed step's loss must be the eager loss of the same step, and the ticket word must read 0 after every step."""
+    ops, _ = _spy_on_ce_scratch(monkeypatch)
+    WARM, K = 1, 3
+    m1, x, y = _setup(0.0, 0.0, mode=mode)
+    m2, _, _ = _setup(0.0, 0.0, mode=mode)
+    crit = P().HybridCrossEntropyLoss()
+    o1, o2 = P().HybridAdamW(m1.parameters(), lr=1e-3), P().HybridAdamW(m2.parameters(), lr=1e-3)
+    eager = []
+    for _ in range(WARM + K):
+        o1.zero_grad(set_to_none=True)
+        loss = crit(m1(x), y)
+        loss.backward()
+        o1.step()
+        eager.append(loss.item())
+    tr = P().GraphedTrainStep(m2, crit, o2, x, y, warmup=WARM)
+    try:
+        assert tr.gs is not None                       # one rank: step() replays the one-graph form
+        for k in range(K):
+            got = tr.step().item()
+            assert math.isfinite(got) and got == eager[WARM + k], (k, got, eager)
+            tickets = [int(t[-1].view(torch.int32).item()) for t in ops._CE_SCRATCH.values()]
+            assert tickets and all(t == 0 for t in tickets), tickets
     finally:
         tr.close()

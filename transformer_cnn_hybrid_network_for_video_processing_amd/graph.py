@@ -76,6 +76,13 @@ class GraphedTrainStep:
                 p.grad = v                                     # AdamW reads the (all-reduced) buckets in place
         # warm-up on a side stream (lazy initialisation, allocator steady state), then capture
         side = torch.cuda.Stream(device=dev)
+        cap = torch.cuda.Stream(device=dev)                    # every capture below runs on this stream
+        if self._fused_loss:
+            # the fused loss keeps a ticket word between its workgroups that must be zero before the first call and that no graph zeroes:
+            # the buffers of both streams are created and zeroed here, eagerly, and kept (ops._ce_scratch refuses to create one under capture)
+            nclips = x.shape[0]
+            self._ce_scratch = [ops.prepare_ce_scratch(nclips, dev, st) for st in (side, cap)]
+            cap.wait_stream(torch.cuda.current_stream(dev))
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
@@ -85,9 +92,9 @@ class GraphedTrainStep:
         torch.cuda.synchronize(dev)
         self._warm_steps = max(1, warmup)
         self.ga, self.gb, self.gc_ = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.ga):
+        with torch.cuda.graph(self.ga, stream=cap):
             self._piece_a()
-        with torch.cuda.graph(self.gb, pool=self.ga.pool()):
+        with torch.cuda.graph(self.gb, pool=self.ga.pool(), stream=cap):
             self._piece_b()
         self.gs = None
         params = self.t_params + self.b_params
@@ -99,12 +106,12 @@ class GraphedTrainStep:
             self.gs = torch.cuda.CUDAGraph()
             # (its own memory pool: in A/B's pool the loss and gradient tensors step() returns could sit in blocks that A/B use as scratch,
             # and a later fwd_bwd() would overwrite them -- ADVICE r3)
-            with torch.cuda.graph(self.gs):
+            with torch.cuda.graph(self.gs, stream=cap):
                 self._piece_a(); self._piece_b(); self._piece_c()
             self._grads_step, self._loss_step = [p.grad for p in params], self.loss
             self._bound = "step"
         else:
-            with torch.cuda.graph(self.gc_, pool=self.ga.pool()):
+            with torch.cuda.graph(self.gc_, pool=self.ga.pool(), stream=cap):
                 self._piece_c()
         # the captures above did not execute: the state is still "after the warm-up steps"
 

@@ -875,8 +875,27 @@ _CE_SCRATCH = {}
 
 def _ce_scratch(B, device):
     """The B + 1 floats hyb_temporal_ce_fwd keeps between its workgroups (per-clip loss terms + a ticket word that every call leaves zero):
-    one zero-initialised buffer per (device, stream, B), so calls that share it are stream-ordered."""
+    one zero-initialised buffer per (device, stream, B), so calls that share it are stream-ordered.  A buffer is never first created on a
+    capturing stream: its zero-fill would be a node of that one graph only, and every other graph captured on the stream would reuse the
+    buffer with nothing that zeroes the ticket (a non-zero ticket leaves the loss unwritten, silently).  Whoever captures calls
+    prepare_ce_scratch() first, eagerly."""
     key = (device.index, _stream(), B)
+    t = _CE_SCRATCH.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("hybrid::temporal_ce under stream capture needs its scratch buffer created and zeroed beforehand: call "
+                               "ops.prepare_ce_scratch(B, device, capture_stream) eagerly before capturing")
+        t = _CE_SCRATCH[key] = torch.zeros(B + 1, dtype=torch.float32, device=device)
+    return t
+
+
+def prepare_ce_scratch(B, device, stream):
+    """Create and zero, now (eagerly, on the current stream), the scratch buffer hybrid::temporal_ce will use when it is called with B clips on
+    ``stream`` (a torch.cuda.Stream); returns it.  The caller orders ``stream`` after the current stream before the first such call."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("prepare_ce_scratch must run outside stream capture")
+    device = torch.device(device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), stream.cuda_stream, B)
     t = _CE_SCRATCH.get(key)
     if t is None:
         t = _CE_SCRATCH[key] = torch.zeros(B + 1, dtype=torch.float32, device=device)
