@@ -456,6 +456,34 @@ int hyb_adamw_step(int count, float* const* params, const float* const* grads, f
                    const long long* numel, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,
                    long long* step_inc, unsigned int* advance_ticket, void* stream);
 
+/* ---- hyper-parameters in device memory: gradient-norm clipping and learning-rate schedules under hipGraph replay -------------------
+ * (New symbols only: hyb_adamw_step above is unchanged and hyb_abi_version() stays 9.)
+ * hyb_adamw_step takes its hyper-parameters by value, so a captured launch keeps the values of the capture for ever.  The three calls
+ * below keep them in a DEVICE block `double hyper[6]` = {lr, beta1, beta2, eps, weight_decay, max_grad_norm}, owned by the caller.
+ *
+ * hyb_adamw_hyper_set: writes the six values from a one-workgroup kernel that received them as kernel arguments: no staging memory, the
+ * host never waits, and calling it before every step with a new lr is safe.  NOT meant to be captured into a replayed graph: a captured
+ * call would rewrite the block with its capture-time values at every replay.  max_grad_norm <= 0 or +inf = no clipping. */
+int hyb_adamw_hyper_set(double* hyper, double lr, double beta1, double beta2, double eps, double weight_decay, double max_grad_norm,
+                        void* stream);
+/* hyb_grad_norm: ONE global L2 norm over `count` fp32 gradient tensors (host array of device pointers, as hyb_adamw_step) and the clip
+ * coefficient of torch.nn.utils.clip_grad_norm_(norm_type = 2): norm_out[0] = sqrt(sum g^2), norm_out[1] = min(1, max_grad_norm /
+ * (norm_out[0] + 1e-6)) (1 when clipping is off; a NaN norm gives a NaN coefficient, as torch with error_if_nonfinite = False).
+ * 4096-element chunks, one workgroup each, fp32 within a chunk in a fixed order (independent of the tensor's alignment), then the chunks'
+ * partial sums in double in a fixed order by a one-workgroup launch: no floating-point atomics, bit-identical from run to run.
+ * partials: hyb_grad_norm_workspace(count, numel) floats (= sum of ceil(numel[i] / 4096); 0 for bad arguments); no state is kept in it
+ * between calls, calls sharing partials / norm_out must be stream-ordered.  More than 80 tensors = more launches, still one norm. */
+size_t hyb_grad_norm_workspace(int count, const long long* numel);
+int hyb_grad_norm(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
+                  float* norm_out /* [2]: total L2 norm, clip coefficient */, void* stream);
+/* hyb_adamw_step_dev: the update of hyb_adamw_step with every scalar formed ON THE DEVICE from hyper[0..4] and step + (step_inc ?
+ * *step_inc : 0), in double, rounded to fp32 once -- the expressions hyb_adamw_step evaluates on the host.  clip: NULL, or the norm_out
+ * of hyb_grad_norm: every gradient element is multiplied by clip[1] before use (g * 1.0f is exact, so an unclipped step equals a step
+ * without clipping bit for bit).  step_inc / advance_ticket as in hyb_adamw_step. */
+int hyb_adamw_step_dev(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                       const long long* numel, const double* hyper, long long step, long long* step_inc, unsigned int* advance_ticket,
+                       const float* clip /* norm_out of hyb_grad_norm, or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

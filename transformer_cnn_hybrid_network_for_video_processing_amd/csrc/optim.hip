@@ -100,7 +100,282 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
     }
 }
 
+// ---- hyper-parameters on the device (hyb_adamw_hyper_set / hyb_grad_norm / hyb_adamw_step_dev) ------------------------------------------
+// A captured launch freezes its by-value arguments, so a learning-rate schedule under hipGraph replay needs the hyper-parameters in device
+// memory: double hyper[6] = {lr, beta1, beta2, eps, weight_decay, max_grad_norm}, rewritten between replays by the one-workgroup kernel below
+// (the values travel as ITS kernel arguments: no staging buffer to reuse too early, nothing for the host to wait on).
+constexpr int HYPER_N = 6;
+struct HyperVals { double v[HYPER_N]; };
+
+__global__ __launch_bounds__(64) void hyper_set_kernel(double* hyper, HyperVals h) {
+    double x = h.v[0];                                             // (selects, not an indexed read: the arguments stay in registers)
+#pragma unroll
+    for (int i = 1; i < HYPER_N; ++i) x = (int)threadIdx.x == i ? h.v[i] : x;
+    if (threadIdx.x < HYPER_N) hyper[threadIdx.x] = x;
+}
+
+// Global L2 norm of all gradient tensors + torch's clip coefficient, bit-reproducible: no floating-point atomics, every order fixed.
+//   grad_norm_kernel, one workgroup per 4096-element chunk: a thread squares-and-adds its 16 elements in index order (fmaf; the same
+//   element -> thread -> order mapping as adamw_kernel whether the tensor is 16-byte aligned or not), wave_sum, the four wave totals pairwise
+//   in index order -> partials[chunk];
+//   grad_norm_final_kernel, ONE workgroup in a launch of its own: partials[0 .. total) in double -- thread t takes t, t + 256, ... ascending,
+//   thread 0 adds the 256 thread sums in ascending order -- then the norm and the coefficient.
+// The second launch IS the cross-workgroup hand-off.  The in-launch form (partial store, release fetch_add on a ticket at agent scope, acquire
+// fence and final sum in the workgroup that finishes last) was built and measured first: 38.6 us per call against 11.7 us for these two launches
+// on the model's 27.3 MB of gradients (scripts/micro/grad_norm_handoff.hip) -- every workgroup's release is an L2 write-back, the cost adamw_kernel's
+// note below its ticket records too -- so it costs far more than the 4.6 us of one dependent launch and was dropped.
+struct GradNormArgs {
+    const float* g[ADAM_MAX];
+    long long n[ADAM_MAX];
+    int chunk_begin[ADAM_MAX + 1];
+    int count;
+    int chunk_offset;                     // index of this launch's first chunk among all chunks of the call (more than 80 tensors = several launches)
+    float* partials;
+};
+
+// one chunk's sum of squares; every thread of the workgroup must call it, thread 0 gets the result
+__device__ __forceinline__ float grad_chunk_sumsq(const GradNormArgs& a, float* s_wave /* [4] */) {
+    int ti = 0;
+    for (int i = 1; i < a.count; ++i)
+        if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
+    const float* __restrict__ g = a.g[ti];
+    const long long n = a.n[ti];
+    const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
+    constexpr int NK = ADAM_CHUNK / (256 * 4);
+    float s = 0.f;
+    if ((((uintptr_t)g & 15) == 0) && base + ADAM_CHUNK <= n) {
+        f32x4 v[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) v[k] = *reinterpret_cast<const f32x4*>(g + base + ((long long)k * 256 + threadIdx.x) * 4);
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s = __builtin_fmaf(v[k][j], v[k][j], s);
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            for (long long e = i; e < i + 4 && e < n; ++e) s = __builtin_fmaf(g[e], g[e], s);
+        }
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+}
+
+// partials[0 .. total) -> norm_out; every thread of the (one) workgroup must call it.  LOAD(i) reads partials[i].
+template <typename Load> __device__ __forceinline__ void grad_norm_finish(Load load, int total, const double* hyper, float* norm_out, double* s_sum /* [256] */) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < total; i += 8 * 256) {          // eight loads in flight (one workgroup: pure latency), added in index order
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = i + j * 256 < total ? load(i + j * 256) : 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += (double)v[j];
+    }
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        for (int i = 0; i < 256; ++i) sum += s_sum[i];
+        const float norm = (float)sqrt(sum);
+        const double mx = hyper[5];
+        // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1); a NaN norm stays a NaN coefficient
+        double coef = 1.0;
+        if (mx > 0.0 && mx < (double)INFINITY) { coef = mx / ((double)norm + 1e-6); coef = coef > 1.0 ? 1.0 : coef; }
+        norm_out[0] = norm;
+        norm_out[1] = (float)coef;
+    }
+}
+
+__global__ __launch_bounds__(256) void grad_norm_kernel(GradNormArgs a) {
+    __shared__ float s_wave[4];
+    const float s = grad_chunk_sumsq(a, s_wave);
+    if (threadIdx.x == 0) a.partials[a.chunk_offset + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* partials, int total, const double* hyper, float* norm_out) {
+    __shared__ double s_sum[256];
+    grad_norm_finish([partials](int i) { return partials[i]; }, total, hyper, norm_out, s_sum);
+}
+
+// adamw_kernel with every scalar formed on the device: from hyper[] and step + *step_inc by thread 0, in double, rounded once -- the same
+// expressions, in the same precision, as hyb_adamw_step forms on the host (and as adamw_kernel's own step_inc branch).  clip: NULL, or the
+// norm_out of grad_norm_kernel: every gradient element is multiplied by clip[1] first (g * 1.0f is exact: an unclipped step is the plain step).
+struct AdamScalars { float decay, omb1, beta2, omb2, eps, step_size, inv_sqrt_bc2, clip; };
+struct AdamDevArgs {
+    AdamTensor t[ADAM_MAX];
+    int chunk_begin[ADAM_MAX + 1];
+    int count;
+    const double* hyper;
+    const long long* step_inc;
+    long long* advance;
+    unsigned int* ticket;
+    long long step;
+    const float* clip;
+};
+
+// adam_one with every fused multiply-add written out, so that the device path computes what adamw_kernel computes as the compiler contracts
+// it (test_unclipped_equals_no_clipping: bit-equal to the plain launch).  adamw_kernel's 16-byte groups end in p = fma(p, decay, -(step * q)),
+// its element-wise remainder -- which stores p * decay first -- in p = fma(-step, q, p * decay); VEC says which of the two this element takes.
+template <bool VEC> __device__ __forceinline__ void adam_dev_one(float& p, float g, float& m, float& v, const AdamScalars& a) {
+#pragma clang fp contract(off)
+    g = g * a.clip;
+    m = __builtin_fmaf(a.omb1, g - m, m);
+    v = __builtin_fmaf(a.beta2, v, (a.omb2 * g) * g);
+    const float q = m / __builtin_fmaf(sqrtf(v), a.inv_sqrt_bc2, a.eps);
+    p = VEC ? __builtin_fmaf(p, a.decay, -(a.step_size * q)) : __builtin_fmaf(-a.step_size, q, p * a.decay);
+}
+
+__device__ __forceinline__ void adam_dev_scalars(const AdamDevArgs& a, float* out /* [8] */) {
+#pragma clang fp contract(off)                                    // 1.0 - lr * wd: a product rounded, then a difference, as on the host (no fma)
+    const double lr = a.hyper[0], b1 = a.hyper[1], b2 = a.hyper[2], eps = a.hyper[3], wd = a.hyper[4];
+    const double tt = (double)(a.step + (a.step_inc ? *a.step_inc : 0ll));
+    const double prod = lr * wd;
+    out[0] = (float)(1.0 - prod);
+    out[1] = (float)(1.0 - b1);
+    out[2] = (float)b2;
+    out[3] = (float)(1.0 - b2);
+    out[4] = (float)eps;
+    out[5] = (float)(lr / (1.0 - pow(b1, tt)));
+    out[6] = (float)(1.0 / sqrt(1.0 - pow(b2, tt)));
+    out[7] = a.clip ? a.clip[1] : 1.0f;
+}
+
+__global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevArgs a) {
+    __shared__ float s_sc[8];
+    int ti = 0;
+    for (int i = 1; i < a.count; ++i)
+        if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
+    const AdamTensor t = a.t[ti];
+    const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
+    const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0);
+    constexpr int NK = ADAM_CHUNK / (256 * 4);
+    const bool full = vec && base + ADAM_CHUNK <= t.n;            // as in adamw_kernel: a full chunk's 16 loads go out before the scalar work
+    f32x4 p[NK], m[NK], v[NK], g[NK];
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            p[k] = *reinterpret_cast<const f32x4*>(t.p + i); m[k] = *reinterpret_cast<const f32x4*>(t.m + i);
+            v[k] = *reinterpret_cast<const f32x4*>(t.v + i); g[k] = *reinterpret_cast<const f32x4*>(t.g + i);
+        }
+    }
+    if (threadIdx.x == 0) adam_dev_scalars(a, s_sc);
+    __syncthreads();
+    const AdamScalars sc{s_sc[0], s_sc[1], s_sc[2], s_sc[3], s_sc[4], s_sc[5], s_sc[6], s_sc[7]};
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { float pj = p[k][j], mj = m[k][j], vj = v[k][j]; adam_dev_one<true>(pj, g[k][j], mj, vj, sc); p[k][j] = pj; m[k][j] = mj; v[k][j] = vj; }
+            *reinterpret_cast<f32x4*>(t.p + i) = p[k]; *reinterpret_cast<f32x4*>(t.m + i) = m[k]; *reinterpret_cast<f32x4*>(t.v + i) = v[k];
+        }
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            if (i >= t.n) break;
+            if (vec && i + 4 <= t.n) {
+                f32x4 pp = *reinterpret_cast<f32x4*>(t.p + i), mm = *reinterpret_cast<f32x4*>(t.m + i), vv = *reinterpret_cast<f32x4*>(t.v + i);
+                const f32x4 gg = *reinterpret_cast<const f32x4*>(t.g + i);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { float pj = pp[j], mj = mm[j], vj = vv[j]; adam_dev_one<true>(pj, gg[j], mj, vj, sc); pp[j] = pj; mm[j] = mj; vv[j] = vj; }
+                *reinterpret_cast<f32x4*>(t.p + i) = pp; *reinterpret_cast<f32x4*>(t.m + i) = mm; *reinterpret_cast<f32x4*>(t.v + i) = vv;
+            } else {
+                for (long long e = i; e < i + 4 && e < t.n; ++e) adam_dev_one<false>(t.p[e], t.g[e], t.m[e], t.v[e], sc);
+            }
+        }
+    }
+    // the counter's one read (thread 0, in front of the barrier) is complete in every workgroup that has taken a ticket: see adamw_kernel
+    if (a.advance && threadIdx.x == 0) {
+        if (__hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+            __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            *a.advance += 1;
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int hyb_adamw_hyper_set(double* hyper, double lr, double beta1, double beta2, double eps, double weight_decay, double max_grad_norm,
+                                   void* stream) {
+    HYB_CHECK_ARG(hyper && lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0 &&
+                  max_grad_norm == max_grad_norm);
+    const HyperVals h{{lr, beta1, beta2, eps, weight_decay, max_grad_norm}};
+    hipLaunchKernelGGL(hyper_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, h);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t hyb_grad_norm_workspace(int count, const long long* numel) {
+    if (count <= 0 || !numel) return 0;
+    size_t chunks = 0;
+    for (int i = 0; i < count; ++i) {
+        if (numel[i] <= 0) return 0;
+        chunks += (size_t)hyb_cdiv(numel[i], ADAM_CHUNK);
+    }
+    return chunks;
+}
+
+extern "C" int hyb_grad_norm(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
+                             float* norm_out, void* stream) {
+    HYB_CHECK_ARG(count > 0 && grads && numel && partials && hyper && norm_out);
+    long long total = 0;
+    for (int i = 0; i < count; ++i) {
+        HYB_CHECK_ARG(grads[i] && numel[i] > 0);
+        total += hyb_cdiv(numel[i], ADAM_CHUNK);
+    }
+    HYB_CHECK_ARG(total < (1ll << 31));
+    int offset = 0;
+    for (int first = 0; first < count; first += ADAM_MAX) {
+        GradNormArgs a{};
+        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
+        int chunks = 0;
+        for (int i = 0; i < n; ++i) {
+            a.g[i] = grads[first + i]; a.n[i] = numel[first + i];
+            a.chunk_begin[i] = chunks;
+            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
+        }
+        a.chunk_begin[n] = chunks;
+        a.count = n;
+        a.chunk_offset = offset;
+        a.partials = partials;
+        hipLaunchKernelGGL(grad_norm_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        HYB_LAUNCH_CHECK();
+        offset += chunks;
+    }
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partials, (int)total, hyper, norm_out);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int hyb_adamw_step_dev(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                  const long long* numel, const double* hyper, long long step, long long* step_inc,
+                                  unsigned int* advance_ticket, const float* clip, void* stream) {
+    HYB_CHECK_ARG(count > 0 && params && grads && exp_avg && exp_avg_sq && numel && hyper && step >= 1 && (!advance_ticket || step_inc));
+    for (int i = 0; i < count; ++i) HYB_CHECK_ARG(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && numel[i] > 0);
+    for (int first = 0; first < count; first += ADAM_MAX) {
+        AdamDevArgs a{};
+        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
+        int chunks = 0;
+        for (int i = 0; i < n; ++i) {
+            a.t[i] = AdamTensor{params[first + i], grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
+            a.chunk_begin[i] = chunks;
+            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
+        }
+        a.chunk_begin[n] = chunks;
+        a.count = n;
+        a.hyper = hyper; a.step_inc = step_inc; a.step = step; a.clip = clip;
+        a.advance = (advance_ticket && first + ADAM_MAX >= count) ? step_inc : nullptr;       // the last launch of the call advances the counter
+        a.ticket = advance_ticket;
+        hipLaunchKernelGGL(adamw_dev_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        HYB_LAUNCH_CHECK();
+    }
+    return 0;
+}
 
 extern "C" int hyb_adamw_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                               const long long* numel, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,

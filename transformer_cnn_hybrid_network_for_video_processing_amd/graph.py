@@ -13,7 +13,10 @@ What makes capture legal here
     freed by the library, and no call synchronises;
   * step-dependent scalars live on the device: the kernels add a device counter to their by-value dropout seed, and AdamW forms
     its bias corrections from state['step'] + counter on the device (hyb_*'s seed_inc / step_inc arguments).  The counter is
-    advanced inside the last graph, so every replay is a new step with new masks;
+    advanced inside the last graph, so every replay is a new step with new masks.  With dynamic_hyper=True (or max_grad_norm set on the
+    optimizer) AdamW's hyper-parameters live on the device too: step() uploads what changed (optimizer.sync_hyper(), never captured)
+    before it replays, so a torch.optim.lr_scheduler works across replays, and the gradient norm is taken and applied inside piece C --
+    with data parallelism over the averaged gradients in the buckets, as DistributedDataParallel + clip_grad_norm_ would;
   * BatchNorm running statistics are updated in place by the captured statistics kernels (hybrid::backbone_).
 
 Data parallelism (world > 1): the backward pass is captured in two pieces so that the gradient all-reduce of the temporal part
@@ -39,12 +42,19 @@ from . import ops
 
 
 class GraphedTrainStep:
-    def __init__(self, model, criterion, optimizer, x, y, mask=None, process_group=None, warmup=3):
+    def __init__(self, model, criterion, optimizer, x, y, mask=None, process_group=None, warmup=3, dynamic_hyper=False):
         if not (hasattr(model, "forward_backbone") and hasattr(model, "forward_temporal")):
             raise TypeError("GraphedTrainStep drives a TransformerCNNHybrid")
         if not hasattr(optimizer, "set_step_counter"):
             raise TypeError("GraphedTrainStep needs HybridAdamW (its step number lives on the device)")
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
+        if dynamic_hyper:
+            optimizer.set_dynamic_hyper(True)
+        # what the captured AdamW launch is bound to: the device path reads its hyper-parameters when it runs; the plain launch carries
+        # them by value, so a later change would be lost silently -- step() refuses it instead
+        self._dev_hyper = optimizer.uses_device_hyper()
+        self._clipping = any(g.get("max_grad_norm") is not None for g in optimizer.param_groups)
+        self._captured_hyper = self._hyper_now()
         from .modules import HybridCrossEntropyLoss
         self._fused_loss = (type(criterion) is HybridCrossEntropyLoss and hasattr(model, "forward_temporal_loss")
                             and os.environ.get("HYB_FUSED_LOSS", "1") != "0")       # (=0: A/B, the criterion as its own two launches)
@@ -114,6 +124,29 @@ class GraphedTrainStep:
             with torch.cuda.graph(self.gc_, pool=self.ga.pool(), stream=cap):
                 self._piece_c()
         # the captures above did not execute: the state is still "after the warm-up steps"
+
+    def _hyper_now(self):
+        return [(g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"], g.get("max_grad_norm") is not None) for g in self.optimizer.param_groups]
+
+    def _check_hyper(self):
+        """In front of every replay.  Device path: upload what changed.  Plain path: a few comparisons per group (the host is the step's pacemaker
+        between graph launches, so this stays allocation-free) -- a changed value must not be lost silently."""
+        if self._dev_hyper:
+            if any((g.get("max_grad_norm") is not None) != self._clipping for g in self.optimizer.param_groups):
+                raise RuntimeError("GraphedTrainStep: max_grad_norm was switched on or off after capture; the norm launch is (not) part of the "
+                                   "captured step -- set it on the optimizer before constructing GraphedTrainStep")
+            self.optimizer.sync_hyper()                        # on the current stream, in front of the replay; uploads only what changed
+            return
+        for g, c in zip(self.optimizer.param_groups, self._captured_hyper):
+            if g["lr"] != c[0] or tuple(g["betas"]) != c[1] or g["eps"] != c[2] or g["weight_decay"] != c[3] or (g.get("max_grad_norm") is not None) != c[4]:
+                raise RuntimeError("GraphedTrainStep: an optimizer hyper-parameter (lr, betas, eps, weight_decay, max_grad_norm) changed after "
+                                   "capture, but the captured AdamW launch carries the old value -- construct with dynamic_hyper=True to use "
+                                   "schedulers (and set max_grad_norm before constructing)")
+
+    @property
+    def grad_norm(self):
+        """optimizer.grad_norm: the device scalar holding the last step's unclipped total gradient norm (max_grad_norm set)."""
+        return self.optimizer.grad_norm
 
     def _bind(self, which):
         if self.gs is not None and self._bound != which:
@@ -187,6 +220,7 @@ class GraphedTrainStep:
 
     def step(self):
         """One training step; returns the (device) loss tensor of this step -- reading it synchronises."""
+        self._check_hyper()
         if self.gs is not None:
             self._bind("step")
             self.gs.replay()

@@ -2,7 +2,14 @@
 (`optim.AdamW(model.parameters(), lr)`, Model.py:153 / FCT.py:305), as ONE HIP launch over all parameter tensors
 (`hyb_adamw_step`).  Same constructor defaults and update rule as `torch.optim.AdamW` (betas (0.9, 0.999), eps 1e-8,
 weight_decay 1e-2, amsgrad/maximize off); state-dict keys (`step`, `exp_avg`, `exp_avg_sq`) follow torch's so checkpoints
-interchange.  CUDA fp32 parameters only -- there is no CPU fallback."""
+interchange.  CUDA fp32 parameters only -- there is no CPU fallback.
+
+Two things a training run needs on top of that, both built on hyper-parameters that live in DEVICE memory (`double hyper[6]` per group):
+  * `max_grad_norm=c`: `torch.nn.utils.clip_grad_norm_(params, c)` fused into the step -- one launch forms the global L2 norm of all
+    gradients and the clip coefficient (`hyb_grad_norm`, bit-reproducible), the AdamW launch scales every gradient element by it;
+  * `set_dynamic_hyper(True)`: the AdamW launch reads lr / betas / eps / weight_decay from the device block (`hyb_adamw_step_dev`), so a
+    launch captured into a hipGraph follows `param_groups[i]["lr"] = ...` -- i.e. any `torch.optim.lr_scheduler` -- after a
+    `sync_hyper()`, which `step()` (eager) and `GraphedTrainStep.step()` (before the replay) call."""
 import ctypes
 
 import torch
@@ -12,14 +19,22 @@ from .ops import _stream
 
 
 class HybridAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be None (no clipping) or > 0")
+        # max_grad_norm sits in the groups only so that it travels in the state dict: clipping is global, every group carries the same value
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm))
         self._tables = {}            # per group: cached pointer tables of the tensors whose addresses never change
         self._step_counter = None    # device int64 [1]: the kernel uses step + counter (captured launches, graph.GraphedTrainStep)
         self._advance = False
         self._ticket = None          # device uint32 [1], this optimizer's own: the advancing launch counts its finished workgroups there
+        self._dynamic = False        # set_dynamic_hyper(): take the device path even without clipping
+        self._hyper = None           # device double [groups, 6]: lr, beta1, beta2, eps, weight_decay, max_grad_norm (0 = off) per group
+        self._hyper_sent = {}        # per group: the values last uploaded (sync_hyper uploads on change only)
+        self._norm_out = None        # device fp32 [2]: the last step's unclipped total gradient norm, its clip coefficient
+        self._partials = None        # (numels, device fp32 [chunks], host numel array): hyb_grad_norm's per-chunk sums of squares
 
     def set_step_counter(self, counter, advance=False):
         """With a device counter the step number used by the kernel is state['step'] + counter, read on the device: one captured
@@ -30,6 +45,70 @@ class HybridAdamW(torch.optim.Optimizer):
         self._advance = bool(advance) and counter is not None
         if self._advance and (self._ticket is None or self._ticket.device != counter.device):
             self._ticket = torch.zeros(1, dtype=torch.int32, device=counter.device)
+
+    def set_dynamic_hyper(self, flag=True):
+        """True: step() launches hyb_adamw_step_dev, which reads the hyper-parameters from device memory when it runs -- needed for a
+        captured step that must follow a learning-rate schedule.  (With max_grad_norm set the device path is taken anyway.)"""
+        self._dynamic = bool(flag)
+
+    def uses_device_hyper(self):
+        return self._dynamic or any(g.get("max_grad_norm") is not None for g in self.param_groups)
+
+    def _clip_value(self):
+        vals = {None if g.get("max_grad_norm") is None else float(g["max_grad_norm"]) for g in self.param_groups}
+        if len(vals) != 1:
+            raise RuntimeError("HybridAdamW: clipping is global over all groups -- every param group must carry the same max_grad_norm")
+        c = vals.pop()
+        if c is not None and not c > 0.0:
+            raise ValueError("max_grad_norm must be None (no clipping) or > 0")
+        return c
+
+    def _device_buffers(self):
+        """The hyper blocks and norm_out: created and zeroed EAGERLY.  A buffer born while its stream captures is
+        zeroed only by that one graph (a replay of another graph would meet whatever the block held before), so that is refused."""
+        if self._hyper is None or self._hyper.shape[0] != len(self.param_groups):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("HybridAdamW: the device hyper-parameter block does not exist yet and cannot be created under stream "
+                                   "capture -- call sync_hyper() (or take one eager step()) before capturing")
+            dev = self.param_groups[0]["params"][0].device
+            if dev.type != "cuda":
+                raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
+            self._hyper = torch.zeros(len(self.param_groups), 6, dtype=torch.float64, device=dev)
+            self._hyper_sent = {}
+            if self._norm_out is None or self._norm_out.device != dev:
+                self._norm_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        return self._hyper
+
+    def _group_hyper(self, group):
+        b1, b2 = group["betas"]
+        c = group.get("max_grad_norm")             # (groups loaded from a torch.optim.AdamW state dict lack the key)
+        return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), 0.0 if c is None else float(c))
+
+    def sync_hyper(self):
+        """Upload every group's (lr, betas, eps, weight_decay, max_grad_norm) that differs from what the device holds (one tiny launch per
+        changed group on the current stream; the host never waits).  Must NOT be captured: the values travel as kernel arguments, a captured
+        upload would put the capture-time values back at every replay."""
+        hyper = self._device_buffers()
+        for gi, group in enumerate(self.param_groups):
+            vals = self._group_hyper(group)
+            if self._hyper_sent.get(gi) != vals:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
+                lib.call("hyb_adamw_hyper_set", hyper[gi].data_ptr(), *vals, _stream())
+                self._hyper_sent[gi] = vals
+
+    @property
+    def grad_norm(self):
+        """Device fp32 scalar: the unclipped total L2 norm of the last clipped step's gradients (what clip_grad_norm_ returns).  Reading it
+        synchronises; holding it does not."""
+        self._device_buffers()
+        return self._norm_out[0]
+
+    @property
+    def clip_coef(self):
+        """Device fp32 scalar: the coefficient the last clipped step multiplied its gradients by (1 = not clipped)."""
+        self._device_buffers()
+        return self._norm_out[1]
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
@@ -55,6 +134,8 @@ class HybridAdamW(torch.optim.Optimizer):
         live = [gi for gi, group in enumerate(self.param_groups) if any(p.grad is not None for p in group["params"])]
         if self._advance and len(live) != 1:
             raise RuntimeError("HybridAdamW: an advancing step counter needs exactly one parameter group with gradients")
+        dev_path = self.uses_device_hyper()
+        work = []                                   # per live group: (group index, tensor count, tables, gradients, step number)
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -87,9 +168,43 @@ class HybridAdamW(torch.optim.Optimizer):
                 if g.dtype != torch.float32 or not g.is_contiguous():
                     g = g.float().contiguous()
                 grads.append(g)
-            b1, b2 = group["betas"]
-            lib.call("hyb_adamw_step", len(ps), tab[2], ptr_array([g.data_ptr() for g in grads]), tab[3], tab[4], tab[5],
-                     float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), steps.pop(),
-                     self._step_counter.data_ptr() if self._step_counter is not None else None,
-                     self._ticket.data_ptr() if self._advance else None, _stream())
+            work.append((gi, len(ps), tab, grads, steps.pop()))
+        counter = self._step_counter.data_ptr() if self._step_counter is not None else None
+        ticket = self._ticket.data_ptr() if self._advance else None
+        if not dev_path:
+            for gi, n, tab, grads, step in work:
+                group = self.param_groups[gi]
+                b1, b2 = group["betas"]
+                lib.call("hyb_adamw_step", n, tab[2], ptr_array([g.data_ptr() for g in grads]), tab[3], tab[4], tab[5],
+                         float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), step, counter, ticket,
+                         _stream())
+            return loss
+        # ---- device path: hyper-parameters (and the clip coefficient) are read from device memory by the launches themselves ----
+        clip = self._clip_value()
+        hyper = self._device_buffers()
+        if torch.cuda.is_current_stream_capturing():
+            # only hyb_grad_norm and hyb_adamw_step_dev are recorded; the upload is the replaying caller's (GraphedTrainStep.step)
+            if len(self._hyper_sent) != len(self.param_groups):
+                raise RuntimeError("HybridAdamW: hyper-parameters were never uploaded -- call sync_hyper() before capturing step()")
+        else:
+            self.sync_hyper()
+        if not work:
+            return loss
+        clip_ptr = None
+        if clip is not None:                        # ONE norm over the gradients of all groups, as clip_grad_norm_(model.parameters())
+            all_grads = [g for w in work for g in w[3]]
+            numels = tuple(g.numel() for g in all_grads)
+            if self._partials is None or self._partials[0] != numels:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("HybridAdamW: the gradient-norm workspace cannot be created under stream capture -- take one eager "
+                                       "step() with the same gradients first")
+                arr = (ctypes.c_longlong * len(numels))(*numels)
+                chunks = lib.query("hyb_grad_norm_workspace", len(numels), arr)
+                self._partials = (numels, torch.zeros(chunks, dtype=torch.float32, device=hyper.device), arr)
+            lib.call("hyb_grad_norm", len(all_grads), ptr_array([g.data_ptr() for g in all_grads]), self._partials[2],
+                     self._partials[1].data_ptr(), hyper[work[0][0]].data_ptr(), self._norm_out.data_ptr(), _stream())
+            clip_ptr = self._norm_out.data_ptr()
+        for gi, n, tab, grads, step in work:
+            lib.call("hyb_adamw_step_dev", n, tab[2], ptr_array([g.data_ptr() for g in grads]), tab[3], tab[4], tab[5], hyper[gi].data_ptr(),
+                     step, counter, ticket, clip_ptr, _stream())
         return loss
