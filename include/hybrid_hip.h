@@ -185,6 +185,21 @@ int hyb_convstage_bwd(int dtype, int first, const void* dpooled, const void* x, 
                       const void* packed_bwd /* from hyb_convstage_fwd, or NULL to repack */,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- whole conv stage, INFERENCE (eval-mode BatchNorm; new symbols only, hyb_abi_version() stays 9) ---------------------------------
+ * pooled = maxpool2x2(relu(conv3x3(x, weight) * scale + shift)) with scale = gamma * rsqrt(running_var + eps), shift = beta -
+ * running_mean * scale (fp32; padded channels exact zeros).  The running statistics are only read, nothing is saved for a backward.
+ * bf16 storage, shapes the asynchronous conv kernels take (hyb_conv3x3_pool_fused() == 1): ONE kernel -- the affine, the ReLU and the 2x2
+ * maximum are applied to the fp32 accumulators in the conv's epilogue, the raw conv output is never stored and the pooled value is
+ * rounded to bf16 once.  Everything else (fp32 storage, other shapes): the conv -> hyb_bn_relu_pool_fwd pair of hyb_convstage_fwd's eval
+ * mode with the raw output in the workspace: the same results as hyb_convstage_fwd(training = 0), bit for bit.
+ * x / Ci / Cip / first as in hyb_convstage_fwd.  hyb_conv3x3_pool_fused is a pure host query (W = the stage's input width). */
+int hyb_conv3x3_pool_fused(int dtype, int W, int Cip, int Cop);
+size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop);
+int hyb_convstage_infer(int dtype, int first, const void* x, const float* weight, const float* gamma, const float* beta,
+                        const float* running_mean, const float* running_var, float eps,
+                        int N, int H, int W, int Ci, int Cip, int Co, int Cop,
+                        void* pooled /* [N,H/2,W/2,Cop] T */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- frame token: global average pool over H*W (the composite's own glue) ----------- */
 int hyb_gap_fwd(int dtype, const void* x /* [N,HW,Cp] */, void* feat /* [N,Cp] */, int N, int HW, int Cp, void* stream);
 int hyb_gap_bwd(int dtype, const void* dfeat /* [N,Cp] */, void* dx /* [N,HW,Cp] */, int N, int HW, int Cp, void* stream);
@@ -300,6 +315,16 @@ int hyb_backbone_bwd(int dtype, int stages, const int* channels, const void* dpo
                      const void* pooled_last /* NULL, or the last stage's forward output */, const float* x, const float* const* params,
                      const void* const* saved, int training, int N, int H, int W, float* const* grads, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* hyb_backbone_infer: the stages of hyb_backbone_fwd for INFERENCE, chained on the caller's stream as hyb_convstage_infer would run them:
+ *   one launch forms every stage's scale/shift from the running statistics, one packs every stage's forward weights, then one launch
+ *   per stage (two where hyb_conv3x3_pool_fused() == 0).  channels as above; params: HOST array of stages*5 device pointers {weight, gamma,
+ *   beta, running_mean, running_var}, all read-only; pooled_last [N, H/2^stages, W/2^stages, pad(C_stages)] T is the only output.
+ *   The workspace holds the packed weights, the scale/shift rows, the intermediate pooled maps (two buffers, ping-pong) and, only
+ *   for stages without the fused epilogue, one raw conv output. */
+size_t hyb_backbone_infer_workspace(int dtype, int stages, const int* channels, int N, int H, int W);
+int hyb_backbone_infer(int dtype, int stages, const int* channels, const float* x, const float* const* params, float eps,
+                       int N, int H, int W, void* pooled_last, void* workspace, size_t workspace_bytes, void* stream);
 
 /* hyb_temporal_*: frame tokens (global average pool over HW + Linear(C, D); composite's own) -> hyb_encoder_* (TransformerEncoder.pyc
  *   src L110-126) -> head (mean over S + Linear(D, classes); composite's own).  h [B*S, HW, Cp] T is the last pooled map.

@@ -40,6 +40,25 @@ __global__ void bn_finalize_kernel(const float* __restrict__ stats, const float*
     mean_invstd[Cop + c] = invstd;
 }
 
+// inference: the scale/shift rows of SEVERAL BatchNorms from their running statistics in one launch (blockIdx.y = which); the fp32
+// expressions of bn_finalize_kernel's eval branch, padded channels zero.  Nothing but scale_shift is written.
+struct BnInferMany { const float* gamma[16]; const float* beta[16]; const float* mean[16]; const float* var[16]; float* ss[16]; int Co[16], Cop[16]; };
+__global__ void bn_infer_affine_kernel(BnInferMany a, float eps) {
+    const int s = blockIdx.y, c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int Co = a.Co[s], Cop = a.Cop[s];
+    if (c >= Cop) return;
+    float mean = 0.f, invstd = 0.f, g = 0.f, b = 0.f;
+    if (c < Co) {
+        g = a.gamma[s][c];
+        b = a.beta[s][c];
+        mean = a.mean[s][c];
+        invstd = rsqrtf(a.var[s][c] + eps);
+    }
+    const float scale = g * invstd;
+    a.ss[s][c] = scale;
+    a.ss[s][Cop + c] = b - mean * scale;
+}
+
 // partial rows [G][2][Cop] -> statistics -> finalize, one launch (1024 threads: 32 channels x 32 row groups per block)
 __global__ __launch_bounds__(1024) void bn_stats_finalize_kernel(const float* __restrict__ part, int G, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, float* running_mean,
@@ -505,6 +524,22 @@ extern "C" int hyb_bn_finalize(const float* stats, const float* gamma, const flo
     HYB_CHECK_ARG(!training || stats);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(hyb_cdiv(Cop, 256)), dim3(256), 0, (hipStream_t)stream, stats, gamma, beta, running_mean,
                        running_var, nbt, training, momentum, eps, count, Co, Cop, scale_shift, mean_invstd, running_out);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// Internal (hyb_convstage_infer / hyb_backbone_infer): scale_shift[i] [2][Cop[i]] of n <= 16 eval-mode BatchNorms, one launch
+int hyb_bn_infer_affine_many(int n, const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* var,
+                             float* const* scale_shift, const int* Co, const int* Cop, float eps, hipStream_t st) {
+    if (n < 1 || n > 16) return HYB_E_ARG;
+    BnInferMany a{};
+    int maxc = 0;
+    for (int i = 0; i < n; ++i) {
+        HYB_CHECK_ARG(gamma[i] && beta[i] && mean[i] && var[i] && scale_shift[i] && Co[i] > 0 && Cop[i] >= Co[i]);
+        a.gamma[i] = gamma[i]; a.beta[i] = beta[i]; a.mean[i] = mean[i]; a.var[i] = var[i]; a.ss[i] = scale_shift[i]; a.Co[i] = Co[i]; a.Cop[i] = Cop[i];
+        if (Cop[i] > maxc) maxc = Cop[i];
+    }
+    hipLaunchKernelGGL(bn_infer_affine_kernel, dim3(hyb_cdiv(maxc, 256), n), dim3(256), 0, st, a, eps);
     HYB_LAUNCH_CHECK();
     return 0;
 }

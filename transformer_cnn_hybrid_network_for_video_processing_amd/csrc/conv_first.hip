@@ -579,6 +579,9 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
                         int prepacked, void* route, hipStream_t st) {
     const size_t es = sizeof(T);
     char* ws = (char*)workspace;
+    // inference (hyb_stage1_infer): eval mode without a mean_invstd buffer -- the caller has filled scale_shift already (one launch for all of
+    // a backbone's stages) and packed_out, when given, is just [2][Cop][64] of prepacked weights: nothing is kept for a backward
+    const bool infer = !training && !mean_invstd;
     // packed weights in both K orders; kept for backward when asked (packed_out = [2][Cop][64])
     T* wp = packed_out ? (T*)packed_out : (T*)ws;                       ws += al256((size_t)Cop * 64 * es);
     T* wp2 = packed_out ? (T*)packed_out + (size_t)Cop * 64 : (T*)ws;   ws += al256((size_t)Cop * 64 * es);
@@ -625,7 +628,7 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
     const int gx = s1_grid(numTiles);
     int rc;
     int gx_rows = gx;                                      // partial statistics rows actually written
-    if (packed_out) {
+    if (packed_out && !infer) {
         // defined contents for the whole saved buffer (its size is counted in 2-byte elements: twice the need with fp32 storage): the
         // Gram slot's padding always, the slot itself when this path does not produce it
         // (when it is produced -- 16-bit storage -- the statistics kernel below zeroes the 16 bytes of padding itself: no extra launch)
@@ -648,6 +651,8 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
         if (rc) return rc;
         rc = hyb_bn_stats_finalize(part, gx_rows, gamma, beta, running_mean, running_var, nbt, momentum, eps, (long long)N * H * W, Co, Cop,
                                    scale_shift, mean_invstd, running_out, (void*)st);
+    } else if (infer) {
+        rc = 0;
     } else {
         rc = hyb_bn_finalize(stats, gamma, beta, running_mean, running_var, nbt, 0, momentum, eps, (long long)N * H * W, Co, Cop,
                              scale_shift, mean_invstd, nullptr, (void*)st);
@@ -738,4 +743,12 @@ int hyb_stage1_bwd(int dtype, const void* dpooled, const float* x, const float* 
     if (dtype == HYB_F32) return stage1_bwd_t<float>(dpooled, x, weight, gamma, scale_shift, mean_invstd, training, N, H, W, Ci, Co, Cop, dweight, dgamma, dbeta, packed_in, workspace, route, st);
     if (dtype == HYB_BF16) return stage1_bwd_t<bf16>(dpooled, x, weight, gamma, scale_shift, mean_invstd, training, N, H, W, Ci, Co, Cop, dweight, dgamma, dbeta, packed_in, workspace, route, st);
     return HYB_E_ARG;
+}
+
+// Inference: the apply + pool pass alone, with scale_shift [2][Cop] given.  prepacked = NULL, or [2][Cop][64] packed weights (both K orders)
+// the caller has written; otherwise the weights are packed into the workspace (hyb_stage1_fwd_workspace bytes either way).
+int hyb_stage1_infer(int dtype, const float* x, const float* weight, const float* scale_shift, int N, int H, int W, int Ci, int Co, int Cop, void* pooled,
+                     void* prepacked, void* workspace, hipStream_t st) {
+    return hyb_stage1_fwd(dtype, x, weight, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.f, 0.f, N, H, W, Ci, Co, Cop, pooled,
+                          const_cast<float*>(scale_shift), nullptr, prepacked, workspace, nullptr, prepacked != nullptr, nullptr, st);
 }

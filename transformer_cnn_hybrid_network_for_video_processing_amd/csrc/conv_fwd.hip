@@ -682,6 +682,46 @@ int hyb_conv_pack_weight_many(int dtype, int n, const float* const* w, void* con
     return 0;
 }
 
+// Forward layouts only (inference, hyb_backbone_infer): wp0[i] of n stages plus the first stage's [2][s1_Cop][64], one launch
+template <typename T>
+__global__ void pack_weight_fwd_many_kernel(PackMany a) {
+    const int s = blockIdx.y;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s == a.n) {
+        const long long total = (long long)a.s1_Cop * 64;
+        if (i >= 2 * total) return;
+        const bool second = i >= total;
+        ((T*)a.s1_wp)[i] = from_f32<T>(s1w_pack_value(a.s1_w, second ? i - total : i, second, a.s1_Co, a.s1_Ci));
+        return;
+    }
+    const int Co = a.Co[s], Ci = a.Ci[s], Cip = a.Cip[s];
+    if (i >= (long long)a.Cop[s] * 9 * Cip) return;
+    const int c32 = (int)(i % 32), tap = (int)((i / 32) % 9), chunk = (int)((i / 288) % (Cip / 32)), co = (int)(i / ((long long)9 * Cip));
+    const int ci = chunk * 32 + c32;
+    float v = 0.f;
+    if (co < Co && ci < Ci) v = a.w[s][((long long)co * Ci + ci) * 9 + tap];
+    pack_store((T*)a.wp0[s], i, v, true);
+}
+int hyb_conv_pack_weight_fwd_many(int dtype, int n, const float* const* w, void* const* wp0, const int* Co, const int* Ci, const int* Cop, const int* Cip,
+                                  const float* s1_w, void* s1_wp, int s1_Co, int s1_Ci, int s1_Cop, hipStream_t st) {
+    if (n < 0 || n > 16 || (n == 0 && !s1_wp)) return HYB_E_ARG;
+    PackMany a{};
+    long long maxc = 0;
+    for (int i = 0; i < n; ++i) {
+        a.w[i] = w[i]; a.wp0[i] = wp0[i]; a.Co[i] = Co[i]; a.Ci[i] = Ci[i]; a.Cop[i] = Cop[i]; a.Cip[i] = Cip[i];
+        const long long c = (long long)Cop[i] * 9 * Cip[i];
+        if (c > maxc) maxc = c;
+    }
+    a.n = n; a.s1_w = s1_w; a.s1_wp = s1_wp; a.s1_Co = s1_Co; a.s1_Ci = s1_Ci; a.s1_Cop = s1_Cop;
+    if (s1_wp && (long long)s1_Cop * 128 > maxc) maxc = (long long)s1_Cop * 128;
+    const dim3 grid(hyb_cdiv(maxc, 256), n + (s1_wp ? 1 : 0));
+    if (dtype == HYB_F32) hipLaunchKernelGGL(pack_weight_fwd_many_kernel<float>, grid, dim3(256), 0, st, a);
+    else if (dtype == HYB_BF16) hipLaunchKernelGGL(pack_weight_fwd_many_kernel<bf16>, grid, dim3(256), 0, st, a);
+    else return HYB_E_ARG;
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int hyb_conv_pack_weight(int dtype, int mode, const float* w, void* wp, int Co, int Ci, int Cop, int Cip, void* stream) {
     HYB_CHECK_ARG(w && wp && Co > 0 && Ci > 0 && Cop % 32 == 0 && Cop >= Co && mode >= 0 && mode <= 2);
     if (mode == 2) HYB_CHECK_ARG(Ci <= 3);

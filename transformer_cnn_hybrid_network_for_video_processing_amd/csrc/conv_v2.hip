@@ -17,7 +17,9 @@
 //   * output channels are permuted inside the MFMA tiles so that a lane ends up with 8 consecutive channels per 32-channel
 //     half: an epilogue store instruction writes 64 contiguous bytes per pixel;
 //   * the BatchNorm batch statistics (UNet.py:59) are folded into the epilogue from the fp32 accumulators, reduced in a fixed
-//     order (bit-reproducible).
+//     order (bit-reproducible);
+//   * POOL instantiations (inference, hyb_conv_v2_pool) never store the raw convolution: the epilogue applies the BatchNorm affine to the
+//     fp32 accumulators, takes the 2 x 2 maximum across lanes, applies the ReLU and stores the pooled map (pool_affine_max below).
 #include <stdlib.h>
 #include <type_traits>
 #include "hyb_common.h"
@@ -38,6 +40,25 @@ constexpr unsigned V2_OOB = 0xfffffff0u;        // beyond every descriptor below
 constexpr unsigned V2_RECORDS = 0x80000000u;
 
 template <int S> using step_c = std::integral_constant<int, S>;
+
+// ---- POOL epilogue: BatchNorm affine + MaxPool2d(2, 2) + ReLU on the accumulators ---------------------------------------------------------
+// A lane holds pixel (py, px) = (p >> 2, p & 3) of a 4 x 4 patch, p = lane & 15; the other three pixels of its 2 x 2 window are lanes p ^ 1,
+// p ^ 4 and p ^ 5 of the same 16-lane DPP row.  Two DPP exchanges per value, no LDS: quad_perm [1,0,3,2] brings lane p ^ 1, a row rotation by
+// four brings the lane one patch row away.  Whichever way the rotation turns, the lanes on ONE side of it (py even or py odd) read the other
+// row of their own window and end up with the whole window's maximum; pool_store_lane finds that side by rotating the lane index itself, so
+// nothing here depends on the rotation's direction.  Affine before the maximum (the scale may be negative), ReLU after it (monotone), like
+// bn_relu_pool_fwd_kernel -- but on fp32 accumulators, so the pooled value is rounded to bf16 once.
+__device__ __forceinline__ float pool_affine_max(float acc, float scale, float shift) {
+    float a = fmaf(acc, scale, shift);
+    a = fmaxf(a, hyb_dpp_mov<0xB1>(a));          // quad_perm [1,0,3,2]: lane p ^ 1
+    a = fmaxf(a, hyb_dpp_mov<0x124>(a));         // row_ror:4: lane p ^ 4 on the storing side
+    return fmaxf(a, 0.f);
+}
+// the lanes that store a window: px even, and the patch row whose rotation partner is the window's other row
+__device__ __forceinline__ bool pool_store_lane(int p) {
+    const int partner = __builtin_amdgcn_update_dpp(0, p, 0x124, 0xf, 0xf, false);
+    return partner == (p ^ 4) && !(p & 1);
+}
 
 template <int NT, int CB, int PGR, int PGC, int R>
 struct V2Geom {
@@ -69,7 +90,8 @@ struct V2Geom {
     }
 };
 
-template <int NT, int CB, int PGR, int PGC, int R, bool STATS>
+// POOL: y is the pooled map [N][H/2][W/2][Cop] and `stats` carries the BatchNorm scale/shift rows [2][Cop] (read only)
+template <int NT, int CB, int PGR, int PGC, int R, bool STATS, bool POOL = false>
 __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) void conv3x3_v2_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wp,
                                                             bf16* __restrict__ y, float* __restrict__ stats,
                                                             int N, int H, int W, int Cip, int Cop,
@@ -82,7 +104,9 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16* const hbuf = reinterpret_cast<bf16*>(smem_raw);                       // [2][HBUF]
     bf16* const wring = hbuf + 2 * G::HBUF;                                     // [R][WSLOT]
-    float* const wgstat = reinterpret_cast<float*>(wring + R * WSLOT);          // [NW waves][2][NT*16]
+    float* const wgstat = reinterpret_cast<float*>(wring + R * WSLOT);          // [NW waves][2][NT*16]; POOL: scale/shift [2][CBW]
+    static_assert(!(STATS && POOL), "the pooled epilogue keeps no batch statistics");
+    static_assert(!POOL || NT >= 2, "the pooled epilogue stores whole 32-channel halves");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -98,6 +122,11 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
     if (STATS) {
         for (int i = tid; i < G::STAT_FLOATS; i += NTHR) wgstat[i] = 0.f;
     }
+    if (POOL) {      // this workgroup's scale/shift: up to 32 values per lane at NT = 4, kept in LDS (2 CBW <= STAT_FLOATS) and read per tile
+        for (int i = tid; i < 2 * CBW; i += NTHR) wgstat[i] = stats[(long long)(i / CBW) * Cop + co_wg + (i % CBW)];
+        __syncthreads();
+    }
+    const bool pool_lane = POOL && pool_store_lane(p);
 
     // ---- halo DMA pieces of this lane: byte offset from the halo origin pixel, and (hy, hx) for the bounds test
     constexpr bool HOFF_REG = true;              // large halos: recompute the offset per piece instead of holding it (registers)
@@ -276,7 +305,36 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
                     for (int r = 0; r < 4; ++r) { s1[t][r] = 0.f; s2[t][r] = 0.f; }
             }
             const int gy = ty0 + prow * 4 + py;
-            auto emit = [&](auto FULL_) __attribute__((always_inline)) {
+            auto emit_pool = [&](auto FULL_) __attribute__((always_inline)) {
+                constexpr bool FULL = decltype(FULL_)::value;
+                f32x4 sc[NT], sh[NT];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const float* sp = wgstat + cb * (NT * 16) + (t >> 1) * 32 + q * 8 + (t & 1) * 4;
+                    sc[t] = *reinterpret_cast<const f32x4*>(sp);
+                    sh[t] = *reinterpret_cast<const f32x4*>(sp + CBW);
+                }
+                const int Ho = H >> 1, Wo = W >> 1;
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    const int gx = tx0 + pstrip * 28 + m * 4 + px;
+                    Vec8<bf16> v[(NT + 1) / 2];
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[t >> 1].set((t & 1) * 4 + r, pool_affine_max(acc[m][t][r], sc[t][r], sh[t][r]));
+                    // floor semantics (bn_relu_pool_fwd_kernel): a window exists when both of its rows and columns are inside the image;
+                    // a full tile issues exactly NS lane-masked store instructions per wave
+                    if (pool_lane && (FULL || (((gy | 1) < H) && ((gx | 1) < W)))) {
+                        bf16* dst = y + ((long long)(n * Ho + (gy >> 1)) * Wo + (gx >> 1)) * Cop + co_base + q * 8;
+#pragma unroll
+                        for (int h = 0; h < (NT + 1) / 2; ++h) v[h].store(dst + h * 32);
+                    }
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+            };
+            auto emit_raw = [&](auto FULL_) __attribute__((always_inline)) {
                 constexpr bool FULL = decltype(FULL_)::value;
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
@@ -305,6 +363,9 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
 #pragma unroll
                     for (int t = 0; t < NT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
+            };
+            auto emit = [&](auto FULL_) __attribute__((always_inline)) {
+                if constexpr (POOL) emit_pool(FULL_); else emit_raw(FULL_);
             };
             if (full) {
                 emit(std::true_type{});          // exactly NS store instructions per wave: the next waits step over them by count
@@ -358,7 +419,8 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
 // nine taps' fragments of its 32 output channels (72 registers) for the whole kernel, the halo images are a ring of THREE filled two tiles
 // ahead by LDS-DMA, and a tile costs ONE counted wait + ONE barrier.  Same tiles, fragment layout, swizzle, epilogue and statistics order
 // per tile as conv3x3_v2_kernel<2, CB, PGR, PGC, .>; the per-lane statistics are folded across lanes once, at the end.
-template <int CB, int PGR, int PGC, bool STATS>
+// POOL: as conv3x3_v2_kernel; the 16 scale/shift values of a lane live in the registers the statistics of the STATS sibling use.
+template <int CB, int PGR, int PGC, bool STATS, bool POOL = false>
 __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wp, bf16* __restrict__ y,
                                                                             float* __restrict__ stats, int N, int H, int W, int Cip, int Cop, int tilesX,
                                                                             int tilesY, int numTiles, int stat_rows, int xpix, long long xblk) {
@@ -379,6 +441,17 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
     const int co_base = co_wg + cb * (NT * 16);
     const long long wrow = (long long)9 * Cip;
     (void)xblk;
+    static_assert(!(STATS && POOL), "the pooled epilogue keeps no batch statistics");
+    f32x4 sc[NT], sh[NT];
+    if (POOL) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const float* sp = stats + co_base + (t >> 1) * 32 + q * 8 + (t & 1) * 4;
+            sc[t] = *reinterpret_cast<const f32x4*>(sp);
+            sh[t] = *reinterpret_cast<const f32x4*>(sp + Cop);
+        }
+    }
+    const bool pool_lane = POOL && pool_store_lane(p);
 
     // the wave's weights: row (t, p) of the MFMA tile holds channel (t >> 1) * 32 + (p >> 2) * 8 + (t & 1) * 4 + (p & 3) (conv3x3_v2_kernel)
     Frag<bf16> aw[9][NT];
@@ -485,7 +558,22 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
         const int n = cur.n, ty0 = cur.ty0, tx0 = cur.tx0;
         const bool full = (ty0 + TH <= H) && (tx0 + TW <= W);
         const int gy = ty0 + prow * 4 + py;
-        auto emit = [&](auto FULL_) __attribute__((always_inline)) {
+        auto emit_pool = [&](auto FULL_) __attribute__((always_inline)) {
+            constexpr bool FULL = decltype(FULL_)::value;
+            const int Ho = H >> 1, Wo = W >> 1;
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                const int gx = tx0 + pstrip * 28 + m * 4 + px;
+                Vec8<bf16> v;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v.set(j, pool_affine_max(acc[m][j >> 2][j & 3], sc[j >> 2][j & 3], sh[j >> 2][j & 3]));
+                if (pool_lane && (FULL || (((gy | 1) < H) && ((gx | 1) < W))))       // full tile: exactly NS lane-masked stores per wave
+                    v.store(y + ((long long)(n * Ho + (gy >> 1)) * Wo + (gx >> 1)) * Cop + co_base + q * 8);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        };
+        auto emit_raw = [&](auto FULL_) __attribute__((always_inline)) {
             constexpr bool FULL = decltype(FULL_)::value;
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
@@ -511,6 +599,9 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
 #pragma unroll
                 for (int t = 0; t < NT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
+        };
+        auto emit = [&](auto FULL_) __attribute__((always_inline)) {
+            if constexpr (POOL) emit_pool(FULL_); else emit_raw(FULL_);
         };
         // the next tile's halo (issued one iteration ago) must have landed: in issue order the outstanding operations are [this wave's DMA pieces of
         // iteration it - 1] [its NS stores, if that tile was full] [HT pieces of this iteration] [NS stores]: leave the last three groups in flight
@@ -551,9 +642,10 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
     }
 }
 
+// ss != NULL (with part == NULL): the POOL instantiation, y = the pooled map
 template <int CB, int PGR, int PGC>
-int launch_k32(const bf16* x, const bf16* wp, bf16* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st, int xpix,
-               long long xblk) {
+int launch_k32(const bf16* x, const bf16* wp, bf16* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st,
+               int xpix, long long xblk) {
     using G = V2Geom<2, CB, PGR, PGC, 3>;
     constexpr size_t LDS = (size_t)3 * G::HBUF * 2 + G::STAT_FLOATS * 4;
     static_assert(LDS <= 80 * 1024, "two workgroups per CU");
@@ -564,7 +656,14 @@ int launch_k32(const bf16* x, const bf16* wp, bf16* y, float* part, int N, int H
     if (gx < 1) gx = 1;
     gx = hyb_cdiv(numTiles, hyb_cdiv(numTiles, gx));
     const dim3 grid(gx, Cop / G::CBW);
-    static HybAttrOnce once_stats, once_plain;
+    static HybAttrOnce once_stats, once_plain, once_pool;
+    if (ss) {
+        if (int e = hyb_set_lds_attr(once_pool, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, false, true>, (int)LDS)) return e;
+        hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, false, true>), grid, dim3(256), LDS, st, x, wp, y, const_cast<float*>(ss), N, H, W, Cip, Cop,
+                           tilesX, tilesY, (int)numTiles, 0, xpix, xblk);
+        HYB_LAUNCH_CHECK();
+        return 0;
+    }
     if (int e = hyb_set_lds_attr(once_stats, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, true>, (int)LDS)) return e;
     if (int e = hyb_set_lds_attr(once_plain, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, false>, (int)LDS)) return e;
     if (part)
@@ -578,8 +677,8 @@ int launch_k32(const bf16* x, const bf16* wp, bf16* y, float* part, int N, int H
 }
 
 template <int NT, int CB, int PGR, int PGC, int R>
-int launch_v2(const bf16* x, const bf16* wp, bf16* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st, int xpix,
-              long long xblk) {
+int launch_v2(const bf16* x, const bf16* wp, bf16* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st,
+              int xpix, long long xblk) {
     using G = V2Geom<NT, CB, PGR, PGC, R>;
     const int tilesX = hyb_cdiv(W, G::TW), tilesY = hyb_cdiv(H, G::TH);
     const long long numTiles = (long long)N * tilesX * tilesY;
@@ -589,7 +688,14 @@ int launch_v2(const bf16* x, const bf16* wp, bf16* y, float* part, int N, int H,
     if (gx < 1) gx = 1;
     gx = hyb_cdiv(numTiles, hyb_cdiv(numTiles, gx));          // contiguous runs of ceil(numTiles / gx) tiles: drop the empty ones
     const dim3 grid(gx, Cop / G::CBW);
-    static HybAttrOnce once_stats, once_plain;                 // per template instantiation, per device
+    static HybAttrOnce once_stats, once_plain, once_pool;      // per template instantiation, per device
+    if (ss) {
+        if (int e = hyb_set_lds_attr(once_pool, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false, true>, (int)G::LDS_BYTES)) return e;
+        hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false, true>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, const_cast<float*>(ss),
+                           N, H, W, Cip, Cop, tilesX, tilesY, (int)numTiles, 0, xpix, xblk);
+        HYB_LAUNCH_CHECK();
+        return 0;
+    }
     if (int e = hyb_set_lds_attr(once_stats, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true>, (int)G::LDS_BYTES)) return e;
     if (int e = hyb_set_lds_attr(once_plain, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false>, (int)G::LDS_BYTES)) return e;
     if (part)
@@ -619,12 +725,14 @@ int hyb_conv_v2_supported(int W, int Cip, int Cop) {
 }
 
 // xblk = 0: NHWC input; else the block-planar input's block stride in elements (see conv3x3_v2_kernel)
-int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st, long long xblk) {
+// ss != NULL: the POOL instantiation of the same variant (y = the pooled map, no statistics)
+static int conv_v2_dispatch(const void* x, const void* wp, void* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows,
+                            hipStream_t st, long long xblk) {
     const int xpix = xblk ? 32 : Cip;
     if (!xblk) xblk = 32;
     if (Cip % 32 != 0 || (long long)40 * W * Cip >= (1ll << 29) || (long long)256 * 9 * Cip >= (1ll << 29)) return -100;   // 32-bit buffer offsets
     const bf16* xb = (const bf16*)x; const bf16* wb = (const bf16*)wp; bf16* yb = (bf16*)y;
-#define V2(NT_, CB_, PGR_, PGC_, R_) launch_v2<NT_, CB_, PGR_, PGC_, R_>(xb, wb, yb, part, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk)
+#define V2(NT_, CB_, PGR_, PGC_, R_) launch_v2<NT_, CB_, PGR_, PGC_, R_>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk)
     // Measured on the 224 x 224 clip stages: two four-wave workgroups per CU (their epilogues and MFMA phases interleave) win for
     // Cop <= 128; 256-channel blocks need the whole CU's LDS for a deep weight ring.  HYB_V2_NW=4|8 forces one family.
     static const int nw_env = getenv("HYB_V2_NW") ? atoi(getenv("HYB_V2_NW")) : 0;
@@ -633,8 +741,8 @@ int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int 
     if (k32_env && nw == 4 && Cip == 32 && Cop % 64 == 0) {
         // one channel block per tile: weights in registers, one barrier per tile (conv3x3_k32_kernel)
         return v2_cost(N, H, W, 8, 28, Cop / 64) <= v2_cost(N, H, W, 4, 56, Cop / 64)
-                   ? launch_k32<2, 2, 1>(xb, wb, yb, part, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk)
-                   : launch_k32<2, 1, 2>(xb, wb, yb, part, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk);
+                   ? launch_k32<2, 2, 1>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk)
+                   : launch_k32<2, 1, 2>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk);
     }
     if (nw == 4) {
         if (Cop % 256 == 0) return V2(4, 4, 1, 1, 3);
@@ -653,4 +761,15 @@ int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int 
     if (Cop % 32 == 0) return V2(2, 1, 4, 2, 6);
 #undef V2
     return -100;
+}
+
+int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st, long long xblk) {
+    return conv_v2_dispatch(x, wp, y, part, nullptr, N, H, W, Cip, Cop, stat_rows, st, xblk);
+}
+
+// Internal (hyb_convstage_infer): pooled[N][H/2][W/2][Cop] = maxpool2x2(relu(conv3x3(x, wp) * scale + shift)), ss = [2][Cop] scale | shift, the raw
+// convolution never stored.  -100 for the shapes hyb_conv_v2 does not take.
+int hyb_conv_v2_pool(const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
+    if (!ss || H < 2 || W < 2 || !hyb_conv_v2_supported(W, Cip, Cop)) return -100;
+    return conv_v2_dispatch(x, wp, pooled, nullptr, ss, N, H, W, Cip, Cop, 0, st, 0);
 }

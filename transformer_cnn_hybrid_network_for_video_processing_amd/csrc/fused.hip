@@ -36,6 +36,13 @@ int hyb_convstage_bwd_impl(int dtype, int first, const void* dpooled, const void
                            int Ci, int Cip, int Co, int Cop, void* dx, float* dweight, float* dgamma, float* dbeta,
                            const void* packed_bwd, void* workspace, size_t workspace_bytes, void* stream, void* slab_ws, HybSlabInfo* defer);
 int hyb_wgrad_reduce_multi(int n, const HybSlabInfo* infos, hipStream_t st);
+size_t hyb_stage1_fwd_workspace(int dtype, int Cop);
+int hyb_bn_infer_affine_many(int n, const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* var,
+                             float* const* scale_shift, const int* Co, const int* Cop, float eps, hipStream_t st);
+int hyb_conv_pack_weight_fwd_many(int dtype, int n, const float* const* w, void* const* wp0, const int* Co, const int* Ci, const int* Cop, const int* Cip,
+                                  const float* s1_w, void* s1_wp, int s1_Co, int s1_Ci, int s1_Cop, hipStream_t st);
+int hyb_convstage_infer_core(int dtype, int first, const void* x, const float* weight, const float* scale_shift, int N, int H, int W, int Ci, int Cip, int Co,
+                             int Cop, void* pooled, const void* prepacked, void* pack_ws, void* y_raw, void* s1_ws, void* stream);
 int hyb_conv_pack_weight_many(int dtype, int n, const float* const* w, void* const* wp0, void* const* wp1, const int* Co, const int* Ci, const int* Cop,
                               const int* Cip, const float* s1_w, void* s1_wp, int s1_Co, int s1_Ci, int s1_Cop, hipStream_t st);
 
@@ -106,6 +113,86 @@ extern "C" int hyb_backbone_fwd(int dtype, int stages, const int* channels, cons
                                        s == 0 ? 0 : padc(Ci), Co, padc(Co), O[0], O[1], (float*)O[2], (float*)O[3], O[4], training ? (float*)O[5] : nullptr,
                                        workspace, stage_ws, stream, prepacked[s]));
         in = O[1];
+        h /= 2; w /= 2;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Inference backbone: all stages chained on the caller's stream; one launch for every stage's scale/shift, one for every weight pack, then one
+// launch per stage (stage 1: apply + pool; stages 2..: conv with the affine + ReLU + pool epilogue, or the conv -> bn_relu_pool pair where
+// hyb_conv3x3_pool_fused says 0).  Workspace: scale/shift rows | weight packs | stage-1 scratch | two pooled maps (ping-pong) | one y_raw (pair only)
+namespace {
+struct InferLayout { size_t ss[16], pack[16], s1_ws, buf[2], y_raw, total; };
+inline bool infer_layout(int dtype, int stages, const int* channels, int N, int H, int W, InferLayout& L) {
+    if ((dtype != HYB_F32 && dtype != HYB_BF16) || stages < 1 || stages > 16 || !channels || N <= 0 || channels[0] < 1 || channels[0] > 4) return false;
+    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    for (int s = 0; s < stages; ++s) {
+        if (channels[s + 1] < 1) return false;
+        L.ss[s] = take(2 * (size_t)padc(channels[s + 1]) * 4);
+    }
+    L.pack[0] = take((size_t)padc(channels[1]) * 128 * es);
+    for (int s = 1; s < stages; ++s) L.pack[s] = take((size_t)hyb_conv_packed_elems(0, padc(channels[s]), padc(channels[s + 1])) * es);
+    L.s1_ws = take(hyb_stage1_fwd_workspace(dtype, padc(channels[1])));
+    size_t bufb[2] = {0, 0}, yraw = 0;
+    int h = H, w = W;
+    for (int s = 0; s < stages; ++s) {
+        if (h < 2 || w < 2) return false;
+        const int Cop = padc(channels[s + 1]);
+        if (Cop / 8 > 256) return false;
+        if (s > 0 && !hyb_conv3x3_pool_fused(dtype, w, padc(channels[s]), Cop)) yraw = smax(yraw, (size_t)N * h * w * Cop * es);
+        if (s < stages - 1) bufb[s & 1] = smax(bufb[s & 1], (size_t)N * (h / 2) * (w / 2) * Cop * es);
+        h /= 2; w /= 2;
+    }
+    L.buf[0] = take(bufb[0]);
+    L.buf[1] = take(bufb[1]);
+    L.y_raw = take(yraw);
+    L.total = off;
+    return true;
+}
+}  // namespace
+
+extern "C" size_t hyb_backbone_infer_workspace(int dtype, int stages, const int* channels, int N, int H, int W) {
+    InferLayout L;
+    return infer_layout(dtype, stages, channels, N, H, W, L) ? L.total : 0;
+}
+
+extern "C" int hyb_backbone_infer(int dtype, int stages, const int* channels, const float* x, const float* const* params, float eps, int N, int H, int W,
+                                  void* pooled_last, void* workspace, size_t workspace_bytes, void* stream) {
+    HYB_CHECK_ARG(stages >= 1 && stages <= 16 && channels && x && params && pooled_last && workspace && N > 0);
+    InferLayout L;
+    HYB_CHECK_ARG(infer_layout(dtype, stages, channels, N, H, W, L));
+    for (int s = 0; s < stages * 5; ++s) HYB_CHECK_ARG(params[s]);
+    if (workspace_bytes < L.total) return HYB_E_WORKSPACE;
+    char* ws = (char*)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    {   // every stage's scale/shift from the running statistics: one launch
+        const float* g[16]; const float* b[16]; const float* m[16]; const float* v[16]; float* ss[16]; int co[16], cop[16];
+        for (int s = 0; s < stages; ++s) {
+            const float* const* P = params + (size_t)s * 5;
+            g[s] = P[1]; b[s] = P[2]; m[s] = P[3]; v[s] = P[4]; ss[s] = (float*)(ws + L.ss[s]); co[s] = channels[s + 1]; cop[s] = padc(channels[s + 1]);
+        }
+        HYB_TRY(hyb_bn_infer_affine_many(stages, g, b, m, v, ss, co, cop, eps, st));
+    }
+    {   // every stage's forward weight pack: one launch
+        const float* pw[16]; void* p0[16]; int co[16], ci[16], cop[16], cip[16];
+        for (int s = 1; s < stages; ++s) {
+            pw[s - 1] = params[(size_t)s * 5]; p0[s - 1] = ws + L.pack[s];
+            co[s - 1] = channels[s + 1]; ci[s - 1] = channels[s]; cop[s - 1] = padc(channels[s + 1]); cip[s - 1] = padc(channels[s]);
+        }
+        HYB_TRY(hyb_conv_pack_weight_fwd_many(dtype, stages - 1, pw, p0, co, ci, cop, cip, params[0], ws + L.pack[0], channels[1], channels[0],
+                                              padc(channels[1]), st));
+    }
+    const void* in = x;
+    int h = H, w = W;
+    for (int s = 0; s < stages; ++s) {
+        const int Ci = channels[s], Co = channels[s + 1];
+        void* out = s == stages - 1 ? pooled_last : (void*)(ws + L.buf[s & 1]);
+        HYB_TRY(hyb_convstage_infer_core(dtype, s == 0, in, params[(size_t)s * 5], (const float*)(ws + L.ss[s]), N, h, w, Ci, s == 0 ? 0 : padc(Ci), Co,
+                                         padc(Co), out, ws + L.pack[s], nullptr, ws + L.y_raw, ws + L.s1_ws, stream));
+        in = out;
         h /= 2; w /= 2;
     }
     return 0;

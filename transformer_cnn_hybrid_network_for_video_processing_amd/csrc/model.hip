@@ -160,6 +160,74 @@ extern "C" int hyb_convstage_fwd(int dtype, int first, const void* x, const floa
                                   Cop, y_raw, pooled, scale_shift, mean_invstd, packed_bwd, running_out, workspace, workspace_bytes, stream, nullptr);
 }
 
+// ----------------------------------------------------------------------------------------------------------
+// conv stage, inference: running statistics read-only, nothing saved, no full-resolution conv output where the fused epilogue applies
+// ----------------------------------------------------------------------------------------------------------
+int hyb_conv_v2_pool(const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st);   // conv_v2.hip
+int hyb_conv_v2_supported(int W, int Cip, int Cop);
+int hyb_bn_infer_affine_many(int n, const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* var,
+                             float* const* scale_shift, const int* Co, const int* Cop, float eps, hipStream_t st);                           // bn_pool.hip
+int hyb_stage1_infer(int dtype, const float* x, const float* weight, const float* scale_shift, int N, int H, int W, int Ci, int Co, int Cop, void* pooled,
+                     void* prepacked, void* workspace, hipStream_t st);                                                                       // conv_first.hip
+
+// 1 when conv3x3 + BatchNorm affine + ReLU + MaxPool2d run as ONE kernel for this shape (bf16 storage, a shape the asynchronous kernels take);
+// 0: hyb_convstage_infer runs the conv -> bn_relu_pool pair with the raw output in its workspace.  HYB_POOL_FUSED=0 forces the pair (A/B).
+extern "C" int hyb_conv3x3_pool_fused(int dtype, int W, int Cip, int Cop) {
+    static const int fused_env = getenv("HYB_POOL_FUSED") ? atoi(getenv("HYB_POOL_FUSED")) : 1;
+    static const int v2_env = getenv("HYB_CONV_V2") ? atoi(getenv("HYB_CONV_V2")) : 1;
+    if (dtype != HYB_BF16 || W < 2 || Cip <= 0 || Cop <= 0 || Cip % 32 != 0 || Cop % 32 != 0) return 0;
+    return fused_env && v2_env && hyb_conv_v2_supported(W, Cip, Cop) ? 1 : 0;
+}
+
+// workspace of one inference stage: scale/shift row, then (first) the first stage's scratch, (else) the packed forward weights and -- only when
+// the fused epilogue does not serve the shape -- the raw conv output
+extern "C" size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop) {
+    if ((dtype != HYB_F32 && dtype != HYB_BF16) || N <= 0 || H < 2 || W < 2 || Cop <= 0 || Cop % 32 != 0 || (!first && (Cip <= 0 || Cip % 32 != 0))) return 0;
+    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    size_t b = align256(2 * (size_t)Cop * 4);
+    if (first) return b + align256(hyb_stage1_fwd_workspace(dtype, Cop));
+    b += align256((size_t)hyb_conv_packed_elems(0, Cip, Cop) * es);
+    if (!hyb_conv3x3_pool_fused(dtype, W, Cip, Cop)) b += align256((size_t)N * H * W * Cop * es);
+    return b;
+}
+
+// one stage with scale_shift and (optionally) the packed weights ready: the conv with the fused epilogue, else conv -> bn_relu_pool through y_raw
+int hyb_convstage_infer_core(int dtype, int first, const void* x, const float* weight, const float* scale_shift, int N, int H, int W, int Ci, int Cip, int Co,
+                             int Cop, void* pooled, const void* prepacked, void* pack_ws, void* y_raw, void* s1_ws, void* stream) {
+    if (first)
+        return hyb_stage1_infer(dtype, (const float*)x, weight, scale_shift, N, H, W, Ci, Co, Cop, pooled, const_cast<void*>(prepacked), s1_ws, (hipStream_t)stream);
+    const void* wp = prepacked;
+    if (!wp) { HYB_TRY(hyb_conv_pack_weight(dtype, 0, weight, pack_ws, Co, Ci, Cop, Cip, stream)); wp = pack_ws; }
+    if (hyb_conv3x3_pool_fused(dtype, W, Cip, Cop)) {
+        const int rc = hyb_conv_v2_pool(x, wp, pooled, scale_shift, N, H, W, Cip, Cop, (hipStream_t)stream);
+        if (rc != -100) return rc;
+        return HYB_E_ARG;          // (the query and the dispatcher apply the same shape test: not reached)
+    }
+    HYB_CHECK_ARG(y_raw);
+    HYB_TRY(hyb_conv3x3_fwd(dtype, 0, x, wp, y_raw, nullptr, nullptr, N, H, W, Ci, Cip, Cop, stream));
+    return hyb_bn_relu_pool_fwd(dtype, y_raw, scale_shift, pooled, N, H, W, Cop, stream);
+}
+
+extern "C" int hyb_convstage_infer(int dtype, int first, const void* x, const float* weight, const float* gamma, const float* beta,
+                                   const float* running_mean, const float* running_var, float eps, int N, int H, int W, int Ci, int Cip, int Co,
+                                   int Cop, void* pooled, void* workspace, size_t workspace_bytes, void* stream) {
+    HYB_CHECK_ARG(x && weight && gamma && beta && running_mean && running_var && pooled && workspace);
+    HYB_CHECK_ARG(dtype == HYB_F32 || dtype == HYB_BF16);
+    HYB_CHECK_ARG(H >= 2 && W >= 2 && Cop % 32 == 0 && Cop >= Co && Co > 0 && N > 0 && Ci > 0);
+    HYB_CHECK_ARG(first ? Ci <= 4 : (Cip % 32 == 0 && Cip >= Ci));
+    HYB_CHECK_ARG(Cop / 8 <= 256);
+    const size_t need = hyb_convstage_infer_workspace(dtype, first, N, H, W, Cip, Cop);
+    if (need == 0) return HYB_E_ARG;
+    if (workspace_bytes < need) return HYB_E_WORKSPACE;
+    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    char* ws = (char*)workspace;
+    float* ss = (float*)ws;                      ws += align256(2 * (size_t)Cop * 4);
+    HYB_TRY(hyb_bn_infer_affine_many(1, &gamma, &beta, &running_mean, &running_var, &ss, &Co, &Cop, eps, (hipStream_t)stream));
+    void* pack_ws = ws;
+    void* y_raw = first ? nullptr : (void*)(ws + align256((size_t)hyb_conv_packed_elems(0, Cip, Cop) * es));
+    return hyb_convstage_infer_core(dtype, first, x, weight, ss, N, H, W, Ci, Cip, Co, Cop, pooled, nullptr, pack_ws, y_raw, ws, stream);
+}
+
 extern "C" size_t hyb_convstage_bwd_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop) {
     if (first) return hyb_stage1_bwd_workspace(dtype, Cop);
     const size_t es = dtype == HYB_F32 ? 4 : 2;

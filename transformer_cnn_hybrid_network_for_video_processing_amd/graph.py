@@ -269,3 +269,55 @@ class GraphedTrainStep:
     def close(self):
         ops.set_step_counter(None)
         self.optimizer.set_step_counter(None)
+
+
+class GraphedPredict:
+    """``model.predict(x, mask)`` captured once as a hipGraph on static buffers: ``__call__(x)`` copies the clip batch in and replays.
+
+    Inference at small batch is launch-bound like the training step (about twenty launches and four operator calls of host work per
+    forward); replayed, it is one graph launch.  Same kernels, same order, same arithmetic as eager ``predict``: bit-identical results.
+    The graph is a single chain on one stream.  Capture discipline as GraphedTrainStep: warm up first on a side stream (lazy
+    initialisation, allocator steady state), every buffer is a torch allocation (the static inputs outside the capture, the operators'
+    workspaces in the graph's private pool), nothing under capture relies on a zero-filled buffer.  The returned logits tensor is the
+    graph's static output: the next call overwrites it (clone to keep).  The weights are read at replay time, so a later
+    ``load_state_dict`` into the same parameters is picked up; changing shapes, dtype or structure needs a new GraphedPredict."""
+
+    def __init__(self, model, x, mask=None, warmup=3):
+        if not hasattr(model, "predict"):
+            raise TypeError("GraphedPredict drives a TransformerCNNHybrid")
+        if not x.is_cuda:
+            raise RuntimeError("GraphedPredict needs the model and the clip batch on a cuda (ROCm) device; there is no CPU fallback")
+        self.model = model
+        dev = x.device
+        self.x = x.detach().float().clone()                   # static inputs
+        self.mask = mask.detach().clone() if mask is not None else None
+        side = torch.cuda.Stream(device=dev)
+        cap = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                model.predict(self.x, self.mask)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cap):
+            self.logits = model.predict(self.x, self.mask)
+
+    def __call__(self, x, mask=None):
+        if self.graph is None:
+            raise RuntimeError("GraphedPredict is closed")
+        if x.shape != self.x.shape:
+            raise ValueError(f"GraphedPredict was captured for clips of shape {tuple(self.x.shape)}, got {tuple(x.shape)}")
+        self.x.copy_(x, non_blocking=True)
+        if mask is not None:
+            if self.mask is None:
+                raise ValueError("GraphedPredict was captured without a mask")
+            self.mask.copy_(mask, non_blocking=True)
+        self.graph.replay()
+        return self.logits
+
+    def close(self):
+        """Release the graph and its private memory pool."""
+        if self.graph is not None:
+            self.graph.reset()
+        self.graph = self.logits = None

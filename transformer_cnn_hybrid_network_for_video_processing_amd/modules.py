@@ -81,6 +81,27 @@ class ConvBNReLUPool(nn.Sequential, _ComputeDtypeMixin):
             h = self.forward_nhwc(ops.nchw_to_nhwc(x, self._dt, ops.pad_channels(self.in_channels)), False)
         return ops.nhwc_to_nchw(h, self._dt, self.features)
 
+    def infer_nhwc(self, x, first):
+        """forward_nhwc for inference: BatchNorm from the running statistics whatever ``self.training`` says, nothing saved, and (bf16) the
+        conv's epilogue applies BatchNorm + ReLU + MaxPool, so no full-resolution conv output exists.  Call under ``torch.no_grad()``."""
+        conv, bn = getattr(self, self._conv), getattr(self, self._norm)
+        if not bn.track_running_stats or bn.running_mean is None:
+            raise RuntimeError("inference needs BatchNorm running statistics (track_running_stats=True)")
+        return ops.convstage_infer(x, conv.weight, bn, self._dt, first)
+
+    @torch.no_grad()
+    def infer(self, x):
+        """Standalone inference: [N,C,H,W] fp32 in, [N,features,H/2,W/2] fp32 out; eval semantics, ``self.training`` untouched."""
+        if x.dim() != 4:
+            raise ValueError("expected [N,C,H,W]")
+        if not x.is_cuda:
+            raise RuntimeError("ConvBNReLUPool runs on the MI355X HIP path only: move the module and input to 'cuda' (there is no CPU fallback)")
+        if self.in_channels <= 4:
+            h = self.infer_nhwc(x.float(), True)
+        else:
+            h = self.infer_nhwc(ops.nchw_to_nhwc(x, self._dt, ops.pad_channels(self.in_channels)), False)
+        return ops.nhwc_to_nchw(h, self._dt, self.features)
+
 
 class MultiheadAttention(nn.Module, _ComputeDtypeMixin):
     def __init__(self, input_dim, num_heads, compute_dtype="bf16"):                 # src L7-19
@@ -262,6 +283,63 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
         return ops.temporal_ce(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias, enc._flat_params(),
                                self.head.weight, self.head.bias, mask, target, B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout),
                                ops.next_seed())
+
+    # ---- inference ------------------------------------------------------------------------------------------------------------------
+    def _infer_fused(self):
+        """hybrid::backbone_infer + hybrid::temporal serve the plain reference structure (what ``_fused()`` asks, minus the train/eval flags:
+        inference never looks at them)."""
+        stages = [getattr(self, f"encoder{i + 1}") for i in range(self.num_stages)]
+        bn0 = getattr(stages[0], stages[0]._norm)
+        return (self.fuse_model_ops and self.in_channels <= 4 and self.encoder.num_layers > 0 and self.token_proj.bias is not None
+                and self.head.bias is not None
+                and all(getattr(s, s._norm).track_running_stats and getattr(s, s._norm).running_mean is not None
+                        and getattr(s, s._norm).eps == bn0.eps for s in stages))
+
+    def _frames(self, x):
+        if x.dim() == 4:
+            x = x.unsqueeze(1)
+        if x.dim() != 5:
+            raise ValueError("expected a clip tensor [B,T,C,H,W] or a frame batch [B,C,H,W]")
+        if not x.is_cuda:
+            raise RuntimeError("TransformerCNNHybrid runs on the MI355X HIP path only: move the model and input to 'cuda' "
+                               "(there is no CPU fallback)")
+        B, T = x.shape[:2]
+        return x.reshape(B * T, *x.shape[2:]).float(), B
+
+    def _eval_forward(self, fn, *args):
+        """fn(*args) with every submodule in eval mode; the flags are put back afterwards."""
+        flags = [(m, m.training) for m in self.modules()]
+        try:
+            self.eval()
+            return fn(*args)
+        finally:
+            for m, t in flags:
+                m.training = t
+
+    @torch.no_grad()
+    def forward_backbone_infer(self, x):
+        """forward_backbone for inference -> (last pooled map, B): BatchNorm from the running statistics whatever ``self.training`` says,
+        nothing kept for a backward, one workspace instead of per-stage buffers, and in bf16 no full-resolution conv output (the conv
+        kernels of stages 2.. apply BatchNorm + ReLU + MaxPool in their epilogue).  Models ``_infer_fused()`` rejects take forward_backbone."""
+        if not self._infer_fused():
+            return self._eval_forward(self.forward_backbone, x)
+        f, B = self._frames(x)
+        stages = [getattr(self, f"encoder{i + 1}") for i in range(self.num_stages)]
+        return ops.backbone_infer(f, [(getattr(s, s._conv).weight, getattr(s, s._norm)) for s in stages], self._dt), B
+
+    @torch.no_grad()
+    def predict(self, x, mask=None):
+        """Logits [B, num_classes] for inference: what ``model.eval()(x, mask)`` returns under ``torch.no_grad()`` (bf16 conv stages: up to one
+        rounding fewer per stage), without looking at or changing ``self.training``: BatchNorm running statistics, attention-weight dropout
+        off (quirk Q5), the per-layer dropout as the eval forward applies it (quirk Q6)."""
+        if not self._infer_fused():
+            return self._eval_forward(self.forward, x, mask)
+        h, B = self.forward_backbone_infer(x)
+        enc = self.encoder
+        tdt = self._temporal_dt()
+        return ops.temporal(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias, enc._flat_params(),
+                            self.head.weight, self.head.bias, mask, B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads, 0.0, float(enc.dropout),
+                            ops.next_seed())
 
     def backbone_parameters(self):
         return [p for i in range(self.num_stages) for p in getattr(self, f"encoder{i + 1}").parameters()]

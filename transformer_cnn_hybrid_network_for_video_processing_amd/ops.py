@@ -21,6 +21,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::head             mean over T + Linear(d, classes)                    (composite's own)
     hybrid::cross_entropy    mean cross-entropy                                  (composite's own)
     hybrid::cast, hybrid::nchw_to_nhwc, hybrid::nhwc_to_nchw                     layout / dtype glue for standalone module use
+    hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
 """
 import functools
 import os
@@ -790,6 +791,99 @@ def backbone(x, stages, training, dt):
     return res[0]
 
 
+# ---------------------------------------------------------------------------------------------
+# inference operators: eval-mode BatchNorm (running statistics read-only), nothing saved for a backward, no autograd formula.
+# bf16 storage: conv3x3 + affine + ReLU + MaxPool as ONE kernel per stage (no full-resolution conv output); other dtypes / shapes run
+# today's conv -> bn_relu_pool pair inside the same entry point (hyb_conv3x3_pool_fused tells which).
+# ---------------------------------------------------------------------------------------------
+def _inference_only(opname):
+    """Autograd-key kernel of an inference operator: refuse to be recorded, else run the backend kernel."""
+    op = getattr(torch.ops.hybrid, opname)
+
+    def kernel(*args):
+        if torch.is_grad_enabled():
+            for a in args:
+                for t in (a if isinstance(a, (list, tuple)) else (a,)):
+                    if isinstance(t, torch.Tensor) and t.requires_grad:
+                        raise RuntimeError(f"hybrid::{opname} is an inference operator and has no autograd formula: call it under torch.no_grad() "
+                                           "(TransformerCNNHybrid.predict does), or use the training forward")
+        with _below_autograd():
+            return op(*args)
+    return kernel
+
+
+def conv3x3_pool_fused(dt, W, Cip, Cop):
+    """True when hybrid::convstage_infer runs this stage shape as one kernel (W = the stage's input width, padded channel counts)."""
+    return bool(_query("hyb_conv3x3_pool_fused", int(dt), int(W), int(Cip), int(Cop)))
+
+
+def convstage_infer_op(x: Tensor, weight: Tensor, gamma: Tensor, beta: Tensor, running_mean: Tensor, running_var: Tensor, eps: float, dt: int,
+                       first: bool) -> Tensor:
+    """-> pooled [N, H/2, W/2, Cop] of the compute dtype.  x as in hybrid::convstage."""
+    _require_cuda(x, weight, gamma, beta, running_mean, running_var)
+    x = x.contiguous()
+    N, H, W, Ci, Cip, Co, Cop = _convstage_dims(x, weight, first)
+    if first and Ci > 4:
+        raise RuntimeError("first-stage kernel supports in_channels <= 4")
+    if H < 2 or W < 2:
+        raise RuntimeError(f"conv stage needs H, W >= 2 (got {H}x{W})")
+    dev = x.device
+    pooled = torch.empty(N, H // 2, W // 2, Cop, dtype=_TORCH_DTYPE[dt], device=dev)
+    ws = _ws(_query("hyb_convstage_infer_workspace", dt, int(first), N, H, W, Cip, Cop), dev)
+    lib.call("hyb_convstage_infer", dt, int(first), x.data_ptr(), weight.contiguous().data_ptr(), gamma.contiguous().data_ptr(),
+             beta.contiguous().data_ptr(), running_mean.contiguous().data_ptr(), running_var.contiguous().data_ptr(), float(eps), N, H, W, Ci, Cip,
+             Co, Cop, pooled.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return pooled
+
+
+def convstage_infer_fake(x, weight, gamma, beta, running_mean, running_var, eps, dt, first):
+    N, H, W, Ci, Cip, Co, Cop = _convstage_dims(x, weight, first)
+    return x.new_empty((N, H // 2, W // 2, Cop), dtype=_TORCH_DTYPE[dt])
+
+
+def backbone_infer_op(x: Tensor, weights: Sequence[Tensor], gammas: Sequence[Tensor], betas: Sequence[Tensor], running_means: Sequence[Tensor],
+                      running_vars: Sequence[Tensor], eps: float, dt: int) -> Tensor:
+    """All conv stages on NCHW fp32 frames x [N, C_in <= 4, H, W] -> the last pooled map.  One allocation besides the output: the workspace
+    (packed weights, scale/shift rows, two ping-pong pooled maps; a raw conv output only for stages without the fused epilogue)."""
+    _require_cuda(x, *weights, *gammas, *betas, *running_means, *running_vars)
+    x = x.contiguous()
+    S = len(weights)
+    N, H, W, chans, dims = _backbone_geometry(x, weights)
+    if chans[0] > 4:
+        raise RuntimeError("hybrid::backbone_infer reads NCHW frames with C_in <= 4")
+    if dims[-1][0] < 2 or dims[-1][1] < 2:
+        raise RuntimeError(f"frames of {H}x{W} are too small for {S} conv stages (each needs H, W >= 2)")
+    dev = x.device
+    h, w_, _, Cop = dims[-1]
+    pooled = torch.empty(N, h // 2, w_ // 2, Cop, dtype=_TORCH_DTYPE[dt], device=dev)
+    keep, params = [], []
+    for s in range(S):
+        ts = [t.contiguous() for t in (weights[s], gammas[s], betas[s], running_means[s], running_vars[s])]
+        keep += ts
+        params += [t.data_ptr() for t in ts]
+    ws = _ws(_query("hyb_backbone_infer_workspace", dt, S, tuple(chans), N, H, W), dev)
+    lib.call("hyb_backbone_infer", dt, S, _int_array(chans), x.data_ptr(), ptr_array(params), float(eps), N, H, W, pooled.data_ptr(), ws.data_ptr(),
+             ws.numel(), _stream())
+    return pooled
+
+
+def backbone_infer_fake(x, weights, gammas, betas, running_means, running_vars, eps, dt):
+    N, H, W, chans, dims = _backbone_geometry(x, weights)
+    h, w_, _, Cop = dims[-1]
+    return x.new_empty((N, h // 2, w_ // 2, Cop), dtype=_TORCH_DTYPE[dt])
+
+
+def convstage_infer(x, weight, bn, dt, first):
+    return torch.ops.hybrid.convstage_infer(x, weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), int(dt), bool(first))
+
+
+def backbone_infer(x, stages, dt):
+    """stages: list of (conv.weight, bn) pairs, as ops.backbone."""
+    bns = [bn for _, bn in stages]
+    return torch.ops.hybrid.backbone_infer(x, [w for w, _ in stages], [bn.weight for bn in bns], [bn.bias for bn in bns],
+                                           [bn.running_mean for bn in bns], [bn.running_var for bn in bns], float(bns[0].eps), int(dt))
+
+
 def _check_h_dtype(h, dt):
     """dt | HYB_H_BF16 (fp32 / bf16x3 temporal part behind bf16 conv stages): the pooled map is bf16, the global-average-pool kernels convert."""
     want = torch.bfloat16 if dt & HYB_H_BF16 else _TORCH_DTYPE[dt & 0xff]
@@ -1263,6 +1357,12 @@ _define("backbone_", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] bet
                                                                                                 *bs, *rms, *rvs, *nbts)))
 _define("backbone_bwd", "(Tensor dpooled, Tensor pooled, Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] saved, bool training, int dt) -> Tensor[]",
         backbone_bwd_op, backbone_bwd_fake)
+_define("convstage_infer", "(Tensor x, Tensor weight, Tensor gamma, Tensor beta, Tensor running_mean, Tensor running_var, float eps, int dt, bool first) "
+        "-> Tensor", convstage_infer_op, convstage_infer_fake)
+_LIB.impl("convstage_infer", _inference_only("convstage_infer"), "Autograd")
+_define("backbone_infer", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, float eps, "
+        "int dt) -> Tensor", backbone_infer_op, backbone_infer_fake)
+_LIB.impl("backbone_infer", _inference_only("backbone_infer"), "Autograd")
 _define("temporal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, int B, int dt, "
         "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor)", temporal_op,
         temporal_fake,
