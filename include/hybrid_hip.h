@@ -221,7 +221,9 @@ int hyb_linear_bwd(int dtype, const void* x, int ldx, const float* W, const void
  * b*H+h).  scores = q k^T / sqrt(D) (D = d_model, quirk Q1); mask: NULL or fp32 [B,S,S],
  * row b*H+h uses mask[(b*H+h) % B] (quirk Q4: mask.repeat(H,1,1)); masked_fill(mask==0,-1e9);
  * softmax; dropout(p_drop) on the weights (src L58, counter-based RNG keyed by seed);
- * out = weights v.  stats: fp32 [B*H,S,2] = (row max, row sum of exp) of the scaled, masked scores -- all the backward needs to
+ * out = weights v.  Masked scores follow masked_fill in both directions: the VALUE -1e9 enters the softmax (a query whose keys are all
+ * masked -- a padded frame under a valid x valid mask, a zero row of a [B,S,1] mask -- attends uniformly, 1/S per key), and NO gradient
+ * reaches a masked score: such a query adds nothing to dq or dk, and dv receives 1/S of its dout.  stats: fp32 [B*H,S,2] = (row max, row sum of exp) of the scaled, masked scores -- all the backward needs to
  * recompute the probabilities (the fp32 probability matrix of the first generation is gone); pass the SAME mask, p_drop and seed
  * to the backward call.
  * Limits: S <= 64 (longer sequences: hyb_attention_long_* below; hyb_encoder_* switch by themselves), D/H a multiple of 8, <= 128. */

@@ -20,6 +20,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import padding_masks  # noqa: E402
 from oracle import dropout_masks as DM  # noqa: E402
 from oracle import hybrid_ref as R  # noqa: E402
 from oracle import hybrid_ref_bf16 as RB  # noqa: E402
@@ -224,7 +225,10 @@ def _oracle(ref):
 @pytest.mark.parametrize("p", [0.1, 0.5])
 @pytest.mark.parametrize("B,S,D,H,use_mask", [(683, 7, 24, 3, False), (300, 16, 64, 8, True),     # packed: four problems per workgroup
                                               (3, 40, 96, 2, True), (2, 17, 32, 4, False),          # 3 and 2 token tiles, ragged
-                                              (2, 96, 64, 4, False), (2, 70, 32, 4, True)])         # > 64 tokens: online-softmax kernels
+                                              (2, 96, 64, 4, False), (2, 70, 32, 4, True),          # > 64 tokens: online-softmax kernels
+                                              # a padding mask (tests/padding_masks.py): dropout on the uniform weights of fully masked rows,
+                                              # and the backward's regenerated mask on them
+                                              (2, 16, 64, 4, "pad"), (2, 70, 32, 4, "pad")])
 def test_multihead_attention_train_mode_matches_masked_oracle(mode, p, B, S, D, H, use_mask, fixed_seed):
     ftol, gtol = TOL[mode]
     if mode == "bf16" and S > 64:
@@ -239,7 +243,10 @@ def test_multihead_attention_train_mode_matches_masked_oracle(mode, p, B, S, D, 
     hip.dropoutLayer.p = p
     q, k, v = (torch.randn(B, S, D) for _ in range(3))
     mask = None
-    if use_mask:
+    if use_mask == "pad":
+        mask = padding_masks.pad(B, S)
+        assert min(padding_masks.row_census(mask, B, S, H)) > 0         # fully masked rows and rows with a visible key
+    elif use_mask:
         mask = (torch.rand(B, S, S) > 0.3).float()
         mask[:, :, 0] = 1
     r = torch.randn(B, S, D)

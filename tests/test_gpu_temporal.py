@@ -15,7 +15,8 @@ tighter than the whole-model gates:
 
 What the fp32 CPU oracle itself measures against fp64 on these shapes: logits 1e-7 .. 4e-7, dh 3e-7 .. 7e-7, worst parameter gradient
 1e-6 .. 1e-5 -- 10 x to 100 x inside the fp32 gates.  bf16 rounding noise (rounded oracle against plain fp64): logits 2e-3 .. 8e-3, dh 3e-2 ..
-6e-2, i.e. the bf16 gates sit at the scale of the rounding itself.
+6e-2, i.e. the bf16 gates sit at the scale of the rounding itself.  (The padding cases L1P / LONGP / CFG2P: logits 2e-7 .. 4e-7, worst
+gradient 1e-6 .. 8e-6, asserted at 10 x inside the gates by tests/test_oracle.py.)
 
 Each case lands on a known side of the dispatch rules, re-read from the code:
 
@@ -42,6 +43,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import padding_masks  # noqa: E402
 from oracle import hybrid_ref as R  # noqa: E402
 from oracle import hybrid_ref_bf16 as RB  # noqa: E402
 from test_gpu_parity import TOL, check, check_param_grads, rel  # noqa: E402
@@ -80,6 +82,11 @@ CASES = {
     "CFG5": Case(4, 16, 512, 2048, 2, 8, 8, 256, 14, 14, False, "in"),
     # B > 32; 1280 output tiles: the many-tile side of every "at most 256 tiles" GEMM rule
     "WIDE": Case(40, 16, 512, 2048, 2, 8, 8, 256, 2, 2, False, "out"),
+    # mask = "pad": a valid (x) valid padding mask (tests/padding_masks.py) -- every padded frame is a fully masked query row, which the random
+    # masks above never contain (they keep key 0).  L1's and LONG's geometry, and the benchmarked temporal shape
+    "L1P": Case(3, 5, 64, 128, 1, 4, 5, 24, 3, 3, "pad", "in"),
+    "LONGP": Case(2, 70, 64, 128, 2, 4, 8, 32, 2, 2, "pad", "in"),
+    "CFG2P": Case(8, 16, 512, 2048, 2, 8, 8, 256, 7, 7, "pad", "in"),
 }
 C65 = Case(2, 18, 256, 512, 2, 2, 65, 96, 5, 3, False, "out")       # C64's geometry with one class too many for hyb_head_bwd
 MODES = ["fp32", "bf16x3", "bf16", "mixed", "bf16-fp32"]
@@ -145,7 +152,10 @@ def _inputs(c):
     h[..., :c.C] = torch.rand(c.B * c.S, c.Hh, c.Ww, c.C, generator=g) * 2.0          # a pooled map is what a ReLU and a max left: >= 0
     y = torch.randint(0, c.classes, (c.B,), generator=g)
     mask = None
-    if c.mask:
+    if c.mask == "pad":
+        mask = padding_masks.pad(c.B, c.S)
+        assert min(padding_masks.row_census(mask, c.B, c.S, c.heads)) > 0       # fully masked rows and rows with a visible key
+    elif c.mask:
         mask = (torch.rand(c.B, c.S, c.S, generator=g) > 0.3).float()
         mask[:, :, 0] = 1
     return ref, h, y, mask

@@ -293,3 +293,172 @@ def test_fp32_oracle_error_behind_the_relaxed_temporal_gates():
             assert r <= 0.25 * gtol or 0.8 * listed[n] <= r <= 1.05 * listed[n], (n, r)
         else:
             assert r <= 0.25 * gtol, (n, r)
+
+
+# ---------------------------------------------------------------------------
+# fully masked query rows (padding masks): the semantics tests/test_gpu_padding_mask.py relies on
+# ---------------------------------------------------------------------------
+def np_core_fwd_bwd(q, k, v, mask, H, dout):
+    """The attention core and its gradients by hand (loops, no torch, no autograd): q, k, v, dout [B,S,D]; mask [B,S,S] or broadcastable.
+    masked_fill: the VALUE -1e9 goes into the softmax, and the masked score gets NO gradient.  Returns out, dq, dk, dv, and the
+    probabilities [B*H,S,S]."""
+    B, S, D = q.shape
+    dh = D // H
+    mask = np.broadcast_to(mask, (B, S, S))
+    out, dq, dk, dv = (np.zeros((B, S, D)) for _ in range(4))
+    probs = np.zeros((B * H, S, S))
+    for bb in range(B):
+        for h in range(H):
+            sl = slice(h * dh, (h + 1) * dh)
+            masked = mask[(bb * H + h) % B] == 0                       # mask.repeat(H, 1, 1)[b * H + h]
+            s = np.where(masked, -1e9, q[bb, :, sl] @ k[bb, :, sl].T / math.sqrt(D))
+            p = np.exp(s - s.max(axis=-1, keepdims=True))
+            p /= p.sum(axis=-1, keepdims=True)
+            probs[bb * H + h] = p
+            out[bb, :, sl] = p @ v[bb, :, sl]
+            dp = dout[bb, :, sl] @ v[bb, :, sl].T
+            ds = p * (dp - (p * dp).sum(axis=-1, keepdims=True))
+            ds = np.where(masked, 0.0, ds) / math.sqrt(D)
+            dq[bb, :, sl] = ds @ k[bb, :, sl]
+            dk[bb, :, sl] = ds.T @ q[bb, :, sl]
+            dv[bb, :, sl] = p.T @ dout[bb, :, sl]
+    return out, dq, dk, dv, probs
+
+
+def _identity_mha(D, H):
+    m = R.MultiheadAttention(D, H).double().eval()
+    with torch.no_grad():
+        for lin in (m.query_layer, m.key_layer, m.value_layer, m.output_layer):
+            lin.weight.copy_(torch.eye(D))
+            lin.bias.zero_()
+    return m
+
+
+@pytest.mark.parametrize("B,S,D,H,mname", [(2, 6, 16, 2, "pad"), (3, 5, 24, 3, "pad"), (3, 5, 24, 3, "clip0"), (2, 6, 16, 2, "rows"), (2, 70, 16, 2, "late"),
+                                           (2, 6, 16, 2, "values")])
+def test_fully_masked_rows_are_uniform_and_pass_no_score_gradient_in_all_three_oracles(B, S, D, H, mname):
+    """With identity projections and positive inputs (every ReLU is the identity) the module IS its attention core.  On a mask with fully
+    masked (problem, query) rows: hybrid_ref equals the numpy restatement above (values and all three gradients); and in hybrid_ref,
+    hybrid_ref_masked and hybrid_ref_bf16 alike such a row's output is the mean of its problem's value rows, its dq is exactly zero, and dk
+    does not change by a bit when dO changes in those rows only while dv moves by 1/S of that change -- properties that survive the bf16
+    oracle's rounding points."""
+    import padding_masks as PM
+    from oracle import hybrid_ref_bf16 as RB
+    from oracle import hybrid_ref_masked as RM
+    m = _identity_mha(D, H)
+    g = torch.Generator().manual_seed(6)
+    q, k, v = ((torch.rand(B, S, D, generator=g, dtype=torch.float64) + 0.1).bfloat16().double() for _ in range(3))
+    d1 = torch.randn(B, S, D, generator=g, dtype=torch.float64).bfloat16().double()
+    mask = PM.build(mname, B, S)
+    full = PM.problem_rows_fully_masked(mask, B, S, H)
+    assert full.any() and not full.all()
+    sel = full.reshape(B, H, S).permute(0, 2, 1)[..., None].expand(B, S, H, D // H).reshape(B, S, D)
+    d2 = torch.where(sel, (d1 + torch.randn(B, S, D, generator=g, dtype=torch.float64)).bfloat16().double(), d1)
+    split = lambda t: t.reshape(B, S, H, D // H).permute(0, 2, 1, 3).reshape(B * H, S, D // H)      # noqa: E731
+    vmean = split(v).mean(dim=1, keepdim=True).expand(-1, S, -1)
+    want_dv = (split(d2 - d1) * full[..., None]).sum(dim=1, keepdim=True).expand(-1, S, -1) / S
+
+    def run(fn, dout):
+        a, b, c = (t.clone().requires_grad_(True) for t in (q, k, v))
+        y = fn(a, b, c)
+        (y * dout).sum().backward()
+        return y.detach(), a.grad, b.grad, c.grad
+    oracles = {"hybrid_ref": (lambda a, b, c: m(a, b, c, mask), 1e-12),
+               "hybrid_ref_masked": (lambda a, b, c: RM.mha(m, a, b, c, mask), 1e-12),
+               "hybrid_ref_bf16": (lambda a, b, c: RB.mha(m, a, b, c, mask), 2.0 ** -7)}      # bf16(1/S) weights, a bf16 output, a bf16 dv
+    res = {}
+    for name, (fn, tol) in oracles.items():
+        y1, dq1, dk1, dv1 = run(fn, d1)
+        y2, dq2, dk2, dv2 = run(fn, d2)
+        res[name] = (y1, dq1, dk1, dv1)
+        assert (split(y1)[full] - vmean[full]).abs().max() <= tol * vmean.abs().max(), name
+        assert not dq1[sel].any() and not dq2[sel].any(), name
+        assert torch.equal(dk1, dk2) and torch.equal(dq1, dq2) and torch.equal(y1, y2), name
+        assert (split(dv2 - dv1) - want_dv).abs().max() <= tol * max(want_dv.abs().max(), dv1.abs().max()), name
+    for a, b in zip(res["hybrid_ref"], res["hybrid_ref_masked"]):
+        assert torch.equal(a, b)
+    for a, b in zip(res["hybrid_ref"], res["hybrid_ref_bf16"]):                          # one algorithm, bf16 rounding points apart
+        assert (a - b).abs().max() <= 2e-2 * a.abs().max()
+    out, dq, dk, dv, probs = np_core_fwd_bwd(q.numpy(), k.numpy(), v.numpy(), mask.double().numpy(), H, d1.numpy())
+    assert np.allclose(probs[full.numpy()], 1.0 / S, rtol=0, atol=1e-15)                 # uniform rows
+    for got, want in zip(res["hybrid_ref"], (out, dq, dk, dv)):
+        assert np.allclose(got.numpy(), want, atol=1e-12)
+    # the score gradient itself, in the oracle's own graph: zero wherever the mask is zero
+    a, b, c = (split(t).clone().requires_grad_(True) for t in (q, k, v))
+    dot = torch.matmul(a, b.transpose(-2, -1)) / math.sqrt(D)
+    dot.retain_grad()
+    rep = mask.repeat(H, 1, 1)
+    filled = dot.masked_fill(rep == 0, -1e9)
+    (torch.matmul(torch.softmax(filled, dim=-1), c) * split(d1)).sum().backward()
+    assert not dot.grad[(rep == 0).expand_as(dot)].any() and dot.grad[(rep != 0).expand_as(dot)].any()
+
+
+def test_padding_mask_builders_give_every_case_its_rows():
+    """Every module-level case of tests/test_gpu_padding_mask.py has at least one fully masked (problem, query) row (the control `keys` has
+    none) and at least one row with a visible key, under the reference's head-replication rule -- checked here for every shape of the table."""
+    import padding_masks as PM
+    for B, S, D, H, mname in PM.MHA_CASES:
+        mask = PM.build(mname, B, S)
+        n_full, n_open = PM.row_census(mask, B, S, H)
+        assert n_open > 0 and (n_full == 0 if mname == "keys" else n_full > 0), (B, S, D, H, mname)
+        assert torch.equal(mask, PM.build(mname, B, S))                                  # deterministic
+    for B, S, D, Hid, L, H in PM.ENCODER_CASES:
+        assert min(PM.row_census(PM.pad(B, S), B, S, H)) > 0
+    v = PM.values(2, 6)
+    assert set(v.unique().tolist()) <= {0.0, 0.5, -1.0, 2.0, 1.0} and torch.signbit(v[v == 0]).any() and not torch.signbit(v[v == 0]).all()
+    assert torch.equal(PM.build("values:bool", 2, 6), PM.pad(2, 6) != 0) and PM.build("values:int64", 2, 6).dtype == torch.int64
+
+
+def _fp32_oracle_room(what, figs, ftol, gtol):
+    fwd, grad = figs
+    print(f"\n[fp32 CPU oracle vs fp64: {what}] forward {fwd:.2e} (gate {ftol:.1e}); worst gradient {grad:.2e} (gate {gtol:.1e})")
+    assert fwd <= 0.1 * ftol and grad <= 0.1 * gtol, (what, fwd, grad)
+
+
+def test_fp32_oracle_has_ten_times_room_under_the_fp32_gates_on_the_padding_mask_cases():
+    """tests/test_gpu_padding_mask.py gates fp32 (and bf16x3) against the fp32 CPU oracle at 1e-4 forward / 1e-3 gradients.  Measured
+    against fp64 on the same seeded inputs, with the same norm and floor, that oracle's own error has to sit at least 10 x inside both gates
+    on every module-level case; a case that lacks the room gets another seed or shape, never another gate."""
+    import copy
+    import test_gpu_padding_mask as G
+    from test_gpu_parity import TOL, rel
+    ftol, gtol = TOL["fp32"]
+    for B, S, D, H, mname in G.PM.MHA_CASES:
+        ref, orc, (q, k, v, r, mask), yr, grads = G._mha_reference(B, S, D, H, mname, False)
+        assert orc is ref and yr.dtype == torch.float32
+        m64 = copy.deepcopy(ref).double()
+        m64.zero_grad()
+        q64, k64, v64 = (t.double().requires_grad_(True) for t in (q, k, v))
+        y64 = m64(q64, k64, v64, mask)
+        (y64 * r.double()).sum().backward()
+        Gi = max(t.grad.abs().max().item() for t in (q64, k64, v64))
+        Gp = max(p.grad.abs().max().item() for p in m64.parameters())
+        p32 = dict(ref.named_parameters())
+        worst = max([rel(a, b.grad, 1e-4 * Gi) for a, b in zip(grads, (q64, k64, v64))]
+                    + [rel(p32[n].grad, p.grad, 1e-4 * Gp) for n, p in m64.named_parameters()])
+        _fp32_oracle_room(f"mha B{B} S{S} D{D} H{H} {mname}", (rel(yr, y64), worst), ftol, gtol)
+    for B, S, D, Hid, L, H in G.PM.ENCODER_CASES:
+        ref, orc, (x, r, mask), yr, dx = G._encoder_reference(B, S, D, Hid, L, H, False)
+        m64 = copy.deepcopy(ref).double()
+        m64.zero_grad()
+        x64 = x.double().requires_grad_(True)
+        y64 = m64(x64, mask)
+        (y64 * r.double()).sum().backward()
+        Gp = max(p.grad.abs().max().item() for p in m64.parameters())
+        p32 = dict(ref.named_parameters())
+        worst = max([rel(dx, x64.grad)] + [rel(p32[n].grad, p.grad, 1e-4 * Gp) for n, p in m64.named_parameters()])
+        _fp32_oracle_room(f"encoder B{B} S{S} D{D} L{L} H{H} pad", (rel(yr, y64), worst), ftol, gtol)
+    # the padding cases of tests/test_gpu_temporal.py (fp32 map), same measurement: logits, dh and every temporal parameter gradient
+    import test_gpu_temporal as T
+    for name in ("L1P", "LONGP", "CFG2P"):
+        c = T.CASES[name]
+        ref, h, y, mask = T._inputs(c)
+        o_logits, _, o_dh, o_grads = T._oracle(c, False, False)
+        m = copy.deepcopy(ref)
+        hd = h[..., :c.C].clone().requires_grad_(True)
+        logits = m.head(m.encoder(m.token_proj(hd.mean(dim=(1, 2))).reshape(c.B, c.S, -1), mask).mean(dim=1))
+        named = [(n, p) for n, p in m.named_parameters() if n.split(".")[0] in T._TEMPORAL]
+        grads = torch.autograd.grad(1.5 * F.cross_entropy(logits, y), [hd] + [p for _, p in named])
+        Gt = max(g.abs().max().item() for g in o_grads.values())
+        worst = max([rel(grads[0], o_dh)] + [rel(g, o_grads[n], 1e-4 * Gt) for (n, _), g in zip(named, grads[1:])])
+        _fp32_oracle_room(f"temporal {name}", (rel(logits, o_logits), worst), *T.gates("fp32", c))

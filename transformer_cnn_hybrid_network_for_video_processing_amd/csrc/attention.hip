@@ -325,6 +325,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_kernel(const T* __restri
         const float* mrow = mbase ? mbase + (long long)(qok ? query : 0) * d.S : nullptr;
         f32x4 pT[NTC], dpT[NTC];
         float dl = 0.f;
+        unsigned mz = 0;                                       // bit 4 kt + r: that key is masked for this query (masked_fill passes no gradient)
         if constexpr (!SINGLE && HOIST) {
 #pragma unroll
             for (int s = 0; s < 4; ++s)
@@ -386,7 +387,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_kernel(const T* __restri
                 for (int r = 0; r < 4; ++r) {
                     const int key = kt * 16 + 4 * g + r;
                     float sv = pT[kt][r] * scale;
-                    if (mrow && key < d.S && mrow[key] == 0.f) sv = -1e9f;
+                    if (mrow && key < d.S && mrow[key] == 0.f) { sv = -1e9f; mz |= 1u << (4 * kt + r); }
                     float pv = (qok && key < d.S) ? __expf(sv - mx) * inv : 0.f;
                     float dp = dpT[kt][r], mult = 1.f;
                     if (p_drop > 0.f && qok && key < d.S) {
@@ -412,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_kernel(const T* __restri
             if (kt < d.nt) {
                 float x[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) x[r] = pT[kt][r] * (dpT[kt][r] - dl) * scale;
+                for (int r = 0; r < 4; ++r) x[r] = (mz >> (4 * kt + r) & 1u) ? 0.f : pT[kt][r] * (dpT[kt][r] - dl) * scale;
                 acc_to_frag(dsT[kt], x);
                 if (!SINGLE) *reinterpret_cast<Frag16<T>*>(Simg + (qt * 16 + p) * d.ldp + kt * 16 + 4 * g) = dsT[kt];      // dS: for dK in phase B
             }
@@ -453,14 +454,15 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_kernel(const T* __restri
                 const int query = 4 * g + r;
                 const bool ok = kok && query < d.S;
                 float pv = 0.f, mult = 1.f;
+                bool mzero = false;                            // masked score: the weight keeps its value (1/S in a fully masked row), dS is zero
                 if (ok) {
                     const float* st = stats + ((long long)pidx * d.S + query) * 2;
                     float sv = sN[r] * scale;
-                    if (mbase && mbase[(long long)query * d.S + key] == 0.f) sv = -1e9f;
+                    if (mbase && mbase[(long long)query * d.S + key] == 0.f) { sv = -1e9f; mzero = true; }
                     pv = __expf(sv - st[0]) / st[1];
                     if (p_drop > 0.f) mult = dropout_mult(seed, ((unsigned long long)pidx * d.S + query) * d.S + key, p_drop, inv_keep);
                 }
-                ds[r] = pv * (dpN[r] * mult - delta[4 * g + r]) * scale;
+                ds[r] = mzero ? 0.f : pv * (dpN[r] * mult - delta[4 * g + r]) * scale;
                 pd[r] = pv * mult;
             }
             Frag16<T> dsF, pdF;
@@ -1249,10 +1251,11 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_dq_kernel(const T* __restric
                 const int key = kb + kt * 16 + 4 * g + r;
                 const bool ok = key < L;
                 float sv = sT[r] * scale, dpv = dpT[r];
-                if (ex.mask && ok && ex.mask[((long long)(blockIdx.y % ex.Bmask) * L + qrow) * L + key] == 0.f) sv = -1e9f;
+                const bool mzero = ex.mask && ok && ex.mask[((long long)(blockIdx.y % ex.Bmask) * L + qrow) * L + key] == 0.f;
+                if (mzero) sv = -1e9f;
                 if (ex.p_drop > 0.f) dpv *= dropout_mult(dseed, ((unsigned long long)blockIdx.y * L + qrow) * L + key, ex.p_drop, ex.inv_keep);
                 const float pv = ok ? __expf(sv - lse_q) : 0.f;
-                x[r] = pv * (dpv - dl) * scale;
+                x[r] = mzero ? 0.f : pv * (dpv - dl) * scale;              // masked_fill passes no gradient to a masked score
             }
             acc_to_frag(ds[kt], x);
         }
@@ -1308,6 +1311,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_dkv_kernel(const T* __restri
     f32x4 dkT[DTC], dvT[DTC];
 #pragma unroll
     for (int dt = 0; dt < DTC; ++dt) { dkT[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dvT[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    const float inv_L = 1.f / (float)L;
     for (int qb = 0; qb < L; qb += 64) {
         __syncthreads();
         for (int u = tid; u < 64 * segs; u += 256) {
@@ -1344,10 +1348,13 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_dkv_kernel(const T* __restri
                 const int ql = qt * 16 + 4 * g + r;
                 const bool ok = key < L && qb + ql < L;
                 float sv = sN[r] * scale, mult = 1.f;
-                if (ex.mask && ok && ex.mask[((long long)(blockIdx.y % ex.Bmask) * L + qb + ql) * L + key] == 0.f) sv = -1e9f;
+                const bool mzero = ex.mask && ok && ex.mask[((long long)(blockIdx.y % ex.Bmask) * L + qb + ql) * L + key] == 0.f;
+                if (mzero) sv = -1e9f;
                 if (ex.p_drop > 0.f && ok) mult = dropout_mult(dseed, ((unsigned long long)blockIdx.y * L + qb + ql) * L + key, ex.p_drop, ex.inv_keep);
-                const float pu = ok ? __expf(sv - lseL[ql]) : 0.f;                 // undropped softmax weight
-                ds[r] = pu * (dpN[r] * mult - delL[ql]) * scale;
+                // undropped softmax weight.  A saved log-sum-exp of exactly -1e9f is a row whose keys are all masked (fp32 cannot hold
+                // -1e9 + log L, and no sum of real scores gives that value): its weights are 1/L each
+                const float pu = !ok ? 0.f : (ex.mask && lseL[ql] == -1e9f) ? inv_L : __expf(sv - lseL[ql]);
+                ds[r] = mzero ? 0.f : pu * (dpN[r] * mult - delL[ql]) * scale;     // masked_fill passes no gradient to a masked score
                 pv[r] = pu * mult;                                                 // the weight that multiplied V
             }
             Frag16<T> dsF, pF;
