@@ -21,8 +21,8 @@
 // conflict-free (8 rows x 32 B of a 32-lane half tile the 64 banks exactly).
 // Reference quirks kept: scale 1/sqrt(d_model) (Q1), mask row b*H+h reads mask[(b*H+h) % B] (Q4), masked_fill(-1e9),
 // dropout on the weights (src L58).  fp32 mode runs the same structure on v_mfma_f32_16x16x4_f32.
-#include <stdlib.h>
 #include "hyb_common.h"
+#include "hyb_internal.h"
 
 namespace {
 
@@ -540,7 +540,7 @@ inline bool attn_dims(AttnDims& d, int B, int S, int D, int H, size_t es) {
     d.ld_o = D;
     d.relu_out = 0;
     // a grid of one-wave workgroups is dispatch-bound beyond a few thousand problems: pack four single-tile problems per workgroup then
-    static const int ppw_env = getenv("HYB_ATTN_PPW") ? atoi(getenv("HYB_ATTN_PPW")) : 4;      // waves (= problems) per workgroup at S <= 16
+    static const int ppw_env = hyb_env_int("HYB_ATTN_PPW", 4);      // waves (= problems) per workgroup at S <= 16
     d.ppw = (d.nt == 1 && (long long)B * H >= 2048) ? (ppw_env >= 1 && ppw_env <= 16 ? ppw_env : 4) : 1;
     return true;
 }
@@ -548,7 +548,7 @@ inline bool attn_dims(AttnDims& d, int B, int S, int D, int H, size_t es) {
 // waves per workgroup: default one per 16-token tile; HYB_ATTN_QROWS = 16 / 32 / 64 gives a wave that many query rows (the
 // tile-size sweep of BASELINE config 4, profiles/r02_attention_sweep.json)
 inline int attn_waves(const AttnDims& d) {
-    static const int qrows = getenv("HYB_ATTN_QROWS") ? atoi(getenv("HYB_ATTN_QROWS")) : 16;
+    static const int qrows = hyb_env_int("HYB_ATTN_QROWS", 16);
     const int per = qrows >= 64 ? 4 : qrows >= 32 ? 2 : 1;
     return (d.nt + per - 1) / per;
 }
@@ -1388,7 +1388,7 @@ __global__ __launch_bounds__(256, 2) void flash_bwd_dkv_kernel(const T* __restri
 static int flash_fwd_impl(int dtype, const void* q, const void* k, const void* v, void* out, float* lse, int N, int L, int H, int dhp, int ld,
                           float scale, hipStream_t st, int dh_true, const FlashExtra& ex) {
     if (!q || !k || !v || !out || N < 1 || L < 1 || H < 1 || dhp < 8 || dhp % 8 != 0 || dhp > 16 * MAXDT || ld % 8 != 0 || (long long)N * H > 65535) return HYB_E_ARG;
-    static const int f4_env = getenv("HYB_FLASH_FWD4") ? atoi(getenv("HYB_FLASH_FWD4")) : 1;
+    static const int f4_env = hyb_env_int("HYB_FLASH_FWD4", 1);
     if (dtype == HYB_F32 && f4_env && dhp == 8 && dh_true >= 1 && dh_true <= 8 && L >= 1024) {
         // heads of <= 8 features: the 4x4x1 matrix instruction, a query per lane (for <= 4 features the quad 4..7 of q, k, v is zero padding)
         if (dh_true <= 4) hipLaunchKernelGGL(flash_fwd4_kernel<1>, dim3(hyb_cdiv(L, 256), N * H), dim3(256), 0, st, (const float*)q, (const float*)k, (const float*)v,
@@ -1432,7 +1432,7 @@ static int flash_bwd_impl(int dtype, const void* q, const void* k, const void* v
     }
     const long long nq = (long long)N * H * L;
     hipLaunchKernelGGL(flash_delta_kernel<float>, dim3(hyb_cdiv(nq, 256)), dim3(256), 0, st, (const float*)o, (const float*)dout, delta_ws, N, L, H, dhp, ld);
-    static const int f4_env = getenv("HYB_FLASH_BWD4") ? atoi(getenv("HYB_FLASH_BWD4")) : 1;
+    static const int f4_env = hyb_env_int("HYB_FLASH_BWD4", 1);
     if (f4_env && dhp == 8 && dh_true >= 1 && dh_true <= 8 && L >= 1024) {      // heads of <= 8 features: the 4x4x1 matrix instruction
         const dim3 grid4(hyb_cdiv(L, 256), N * H);
         HybProfileHook* hook = hyb_find_hook(5, L, H);           // measurement hook (hyb_profile_set): kernel 5 = the dK / dV kernel of this path, keyed by (tokens, heads)
@@ -1496,7 +1496,6 @@ __global__ void cast_rows_kernel(const TS* __restrict__ src, long long lds, TD* 
     const long long r = i / D, c = i - r * D;
     dst[r * ldd + c] = from_f32<TD>(to_f32<TS>(src[r * lds + c]));
 }
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool long_dims_ok(int B, int S, int D, int H) {
     return B > 0 && S > 0 && D > 0 && H > 0 && D % H == 0 && (D / H) % 8 == 0 && D / H <= 16 * MAXDT && (long long)B * H <= 65535;
 }

@@ -9,10 +9,10 @@
 // A thread owns one channel quad for its whole run (the float4 stride is a multiple of C/4), so the partial sums need no index math.
 #include <math.h>
 #include "hyb_common.h"
+#include "hyb_internal.h"
 
 namespace {
 
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 constexpr int BN_MAX_BLOCKS = 1024;
 
 inline bool bn_shape_ok(long long P, int C) { return P > 0 && C >= 4 && C <= 1024 && C % 4 == 0 && 256 % (C / 4) == 0 && P * (C / 4) < (1ll << 40); }

@@ -1,8 +1,8 @@
 // BatchNorm2d (UNet.py:59) + ReLU (UNet.py:60) + MaxPool2d(2,2) (UNet.py:13) on NHWC activations,
 // forward and backward, plus the global-average-pool frame token and layout/cast helpers.
 // All of these are HBM-bound streaming kernels: 8 channels (16 B of bf16) per lane, channel-fastest.
-#include <stdlib.h>
 #include "hyb_common.h"
+#include "hyb_internal.h"
 
 namespace {
 
@@ -574,7 +574,7 @@ extern "C" int hyb_bn_relu_pool_bwd_reduce(int dtype, const void* dpooled, const
     HYB_CHECK_ARG(dpooled && y && ss && mi && sums && partials && N > 0 && H >= 2 && W >= 2 && Cop % 32 == 0 && Cop > 0 && Cop / 8 <= 256);
     // (the pooled form streams flat groups, not rows: one block per CU (measured 26 / 17.5 / 15.8 us at 1024 / 512 / 256 blocks) with 4 x 2 loads in flight per lane cover the memory latency, and
     // fewer blocks mean fewer partial rows for the second launch)
-    static const int pooled_grid = getenv("HYB_BN_REDUCE_WGS") ? atoi(getenv("HYB_BN_REDUCE_WGS")) : 256;
+    static const int pooled_grid = hyb_env_int("HYB_BN_REDUCE_WGS", 256);
     const int grid = (pooled && pooled_grid >= 1 && pooled_grid <= BN_MAX_ROWBLOCKS) ? (N * (H / 2) < pooled_grid ? N * (H / 2) : pooled_grid) : row_grid(N * (H / 2));
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = 256 * 16 * sizeof(float);

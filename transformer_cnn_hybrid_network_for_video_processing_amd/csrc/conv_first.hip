@@ -11,8 +11,8 @@
 // A workgroup walks 8x32-pixel tiles.  The fp32 halo (10x34 pixels, prefetched one tile ahead into registers) is converted
 // to T and expanded into an im2col matrix P[pixel][k = tap*4 + c] in LDS; P rows feed the conv MFMA (k contiguous) and
 // P columns feed the wgrad MFMA through transposed LDS reads, so no scalar gathers are needed.
-#include <stdlib.h>
 #include "conv_first.h"
+#include "hyb_internal.h"
 
 namespace {
 
@@ -533,40 +533,76 @@ int s1_dispatch(const S1Args& a, int grid_x, hipStream_t st) {
     return s1_launch<T, 2, MODE>(a, grid_x, st);
 }
 
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // ---- internal entry points used by hyb_convstage_{fwd,bwd} when first = 1 ----------------------------------------------
-size_t hyb_stage1_fwd_workspace(int dtype, int Cop) {
+// Forward workspace: the packed weights in both K orders ([Cop][64] each; ADJACENT, Cop*64*es being a multiple of 256: one pack launch writes
+// both), the eval-mode statistics row, the partial rows (statistics or Gram partial rows, whichever is larger), the Gram matrix in double
+struct S1FwdLayout { size_t wp, wp2, stats, part, gram, total; };
+static S1FwdLayout s1_fwd_layout(int dtype, int Cop) {
     const size_t es = dtype == HYB_F32 ? 4 : 2;
-    size_t part = (size_t)S1_MAXPART * 2 * Cop * 4;
-    if (part < (size_t)S1_BWD_PART * 2304 * 4) part = (size_t)S1_BWD_PART * 2304 * 4;            // Gram partial rows (statistics from G)
-    return 2 * al256((size_t)Cop * 64 * es) + al256(2 * (size_t)Cop * 4) + al256(part) + al256((size_t)S1_GRAM_DOUBLES * 8);
+    S1FwdLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    L.wp = take((size_t)Cop * 64 * es);
+    L.wp2 = take((size_t)Cop * 64 * es);
+    L.stats = take(2 * (size_t)Cop * 4);
+    const size_t stat_rows = (size_t)S1_MAXPART * 2 * Cop * 4, gram_rows = (size_t)S1_BWD_PART * 2304 * 4;
+    L.part = take(stat_rows > gram_rows ? stat_rows : gram_rows);
+    L.gram = take((size_t)S1_GRAM_DOUBLES * 8);
+    L.total = off;
+    return L;
 }
-size_t hyb_stage1_bwd_workspace(int dtype, int Cop) {
+// Backward workspace: the packed weights again, the reduced row [S1][G] in double, the per-workgroup partial rows
+struct S1BwdLayout { size_t wp, wp2, sums, part, total; };
+static S1BwdLayout s1_bwd_layout(int dtype, int Cop) {
     const size_t es = dtype == HYB_F32 ? 4 : 2;
-    return 2 * al256((size_t)Cop * 64 * es) + al256(((size_t)Cop * 48 + 2304) * 8) + al256((size_t)S1_BWD_PART * ((size_t)Cop * 48 + 2304) * 4);
+    S1BwdLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    L.wp = take((size_t)Cop * 64 * es);
+    L.wp2 = take((size_t)Cop * 64 * es);
+    L.sums = take(((size_t)Cop * 48 + 2304) * 8);
+    L.part = take((size_t)S1_BWD_PART * ((size_t)Cop * 48 + 2304) * 4);
+    L.total = off;
+    return L;
 }
+size_t hyb_stage1_fwd_workspace(int dtype, int Cop) { return s1_fwd_layout(dtype, Cop).total; }
+size_t hyb_stage1_bwd_workspace(int dtype, int Cop) { return s1_bwd_layout(dtype, Cop).total; }
 
-// Routing codes (S1Args::route): the forward's wave-private apply pass writes them, the backward's wave-private pass reads them instead of
-// recomputing the conv.  ONE rule for both sides (same frames pointer, same shape, same switches), so a backward never reads codes no
-// forward wrote: 16-bit storage, no ragged 8x16 blocks, aligned float4 rows, 32-bit buffer offsets, both wave-private generations enabled.
-static bool s1_route_ok(size_t es, const float* x, int N, int H, int W, int Ci, int Cop) {
-    static const int fwd_env = getenv("HYB_S1_WAVE") ? atoi(getenv("HYB_S1_WAVE")) : 1;
-    static const int bwd_env = getenv("HYB_S1_WAVE_BWD") ? atoi(getenv("HYB_S1_WAVE_BWD")) : 1;
-    static const int route_env = getenv("HYB_S1_ROUTE") ? atoi(getenv("HYB_S1_ROUTE")) : 1;          // (=0: A/B, the backward recomputes the conv)
-    return route_env && fwd_env && bwd_env && es == 2 && !HYB_X3 && (W % 16 == 0) && (H % 8 == 0) && (((uintptr_t)x & 15) == 0) && (Cop % 8 == 0) &&
-           (long long)N * Ci * H * W * 4 < (1ll << 32) && (long long)N * (H / 2) * (W / 2) * Cop * (long long)es < (1ll << 32);
+// Which kernels a first stage runs.  es = bytes per stored element; x16 / dp16 = the frames / dpooled pointer is 16-byte aligned;
+// blocks = W % 16 == 0 && H % 8 == 0 (no ragged 8x16 blocks); off32 = x and pooled fit 32-bit buffer offsets.
+//   fwd_wave   = HYB_S1_WAVE     && W % 4 == 0 && x16 && off32                                    wave-private forward passes (aligned float4 rows)
+//   bwd_wave   = HYB_S1_WAVE_BWD && (es == 2 || split-bf16 build) && blocks && x16 && dp16 && Cop % 4 == 0 && off32     wave-private backward pass
+//   gram_fwd   = HYB_S1_GRAM && fwd_wave && training && es == 2 && blocks                         forward: batch statistics from the Gram matrix
+//   gram_saved = HYB_S1_GRAM && bwd_wave && training && es == 2 && the forward's pack was saved   backward: reads that Gram matrix, sums S1 only
+//   route      = HYB_S1_ROUTE && HYB_S1_WAVE && HYB_S1_WAVE_BWD && s1_route_shape_ok && x16 && off32
+// route (S1Args::route): the forward's wave-private apply pass writes the routing codes (route implies fwd_wave), the backward's wave-private
+// pass reads them instead of recomputing the conv (route && bwd_wave).  Both sides get the verdict here from the same frames pointer, shape
+// and switches, so a backward never reads codes no forward wrote.  s1_route_shape_ok is its shape half (16-bit storage, not the split-bf16
+// build, no ragged blocks, whole 8-channel code words) and all that hyb_stage1_route_elems sizes the buffer by: an upper bound.
+static bool s1_route_shape_ok(size_t es, int H, int W, int Cop) { return es == 2 && !HYB_X3 && W % 16 == 0 && H % 8 == 0 && Cop % 8 == 0; }
+struct S1Paths { bool fwd_wave, bwd_wave, gram_fwd, gram_saved, route; };
+static S1Paths s1_paths(size_t es, const float* x, const void* dpooled, int N, int H, int W, int Ci, int Cop, int training, bool has_packed) {
+    static const int route_env = hyb_env_int("HYB_S1_ROUTE", 1);          // (=0: A/B, the backward recomputes the conv)
+    const bool x16 = ((uintptr_t)x & 15) == 0, dp16 = ((uintptr_t)dpooled & 15) == 0, blocks = W % 16 == 0 && H % 8 == 0;
+    const bool off32 = (long long)N * Ci * H * W * 4 < (1ll << 32) && (long long)N * (H / 2) * (W / 2) * Cop * (long long)es < (1ll << 32);
+    S1Paths p;
+    p.fwd_wave = hyb_sw_s1_wave() && W % 4 == 0 && x16 && off32;
+    p.bwd_wave = hyb_sw_s1_wave_bwd() && (es == 2 || HYB_X3) && blocks && x16 && dp16 && Cop % 4 == 0 && off32;
+    p.gram_fwd = hyb_sw_s1_gram() && p.fwd_wave && training && es == 2 && blocks;
+    p.gram_saved = hyb_sw_s1_gram() && p.bwd_wave && training && es == 2 && has_packed;
+    p.route = route_env && hyb_sw_s1_wave() && hyb_sw_s1_wave_bwd() && s1_route_shape_ok(es, H, W, Cop) && x16 && off32;
+    return p;
 }
 // elements of type T the caller provides for the codes: 4 bits per pooled element
 long long hyb_stage1_route_elems(int dtype, int N, int H, int W, int Cop) {
-    if (dtype != HYB_BF16 || HYB_X3 || W % 16 != 0 || H % 8 != 0 || Cop % 8 != 0 || N < 1) return 0;
+    if (dtype != HYB_BF16 || N < 1 || !s1_route_shape_ok(2, H, W, Cop)) return 0;
     return (long long)N * (H / 2) * (W / 2) * Cop / 4;          // bytes / 2
 }
 
 static int s1_grid(long long numTiles) {
-    static const int fwd_wgs = getenv("HYB_S1_FWD_WGS") ? atoi(getenv("HYB_S1_FWD_WGS")) : S1_FWD_WGS;
+    static const int fwd_wgs = hyb_env_int("HYB_S1_FWD_WGS", S1_FWD_WGS);
     long long g = numTiles < fwd_wgs ? numTiles : fwd_wgs;
     if (g > S1_MAXPART) g = S1_MAXPART;
     return (int)(g < 1 ? 1 : g);
@@ -579,30 +615,19 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
                         int prepacked, void* route, hipStream_t st) {
     const size_t es = sizeof(T);
     char* ws = (char*)workspace;
+    const S1FwdLayout lay = s1_fwd_layout(dtype, Cop);
     // inference (hyb_stage1_infer): eval mode without a mean_invstd buffer -- the caller has filled scale_shift already (one launch for all of
     // a backbone's stages) and packed_out, when given, is just [2][Cop][64] of prepacked weights: nothing is kept for a backward
     const bool infer = !training && !mean_invstd;
     // packed weights in both K orders; kept for backward when asked (packed_out = [2][Cop][64])
-    T* wp = packed_out ? (T*)packed_out : (T*)ws;                       ws += al256((size_t)Cop * 64 * es);
-    T* wp2 = packed_out ? (T*)packed_out + (size_t)Cop * 64 : (T*)ws;   ws += al256((size_t)Cop * 64 * es);
-    float* stats = (float*)ws;                   ws += al256(2 * (size_t)Cop * 4);
-    float* part = (float*)ws;
-    {
-        size_t pb = (size_t)S1_MAXPART * 2 * Cop * 4;
-        if (pb < (size_t)S1_BWD_PART * 2304 * 4) pb = (size_t)S1_BWD_PART * 2304 * 4;
-        ws += al256(pb);
-    }
+    T* wp = packed_out ? (T*)packed_out : (T*)(ws + lay.wp);
+    T* wp2 = packed_out ? (T*)packed_out + (size_t)Cop * 64 : (T*)(ws + lay.wp2);
+    float *stats = (float*)(ws + lay.stats), *part = (float*)(ws + lay.part);
     // Gram matrix (double): kept for backward behind the packed weights when asked, else scratch
-    double* gram = packed_out ? (double*)((T*)packed_out + (size_t)Cop * 128) : (double*)ws;
+    double* gram = packed_out ? (double*)((T*)packed_out + (size_t)Cop * 128) : (double*)(ws + lay.gram);
     const long long total = (long long)Cop * 64;
-    static const int wave_env = getenv("HYB_S1_WAVE") ? atoi(getenv("HYB_S1_WAVE")) : 1;          // second-generation forward passes (A/B)
-    // they address x and pooled with 32-bit buffer offsets and load aligned float4 row segments
-    const bool vec_ok = (W % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    const bool wave_private = wave_env && vec_ok && (long long)N * Ci * H * W * 4 < (1ll << 32) &&
-                              (long long)N * (H / 2) * (W / 2) * Cop * (long long)es < (1ll << 32);
-    // statistics from the Gram matrix: 16-bit storage, training mode, no ragged 8x16 blocks (same test as the backward's wave-private kernel)
-    static const int gram_env = getenv("HYB_S1_GRAM") ? atoi(getenv("HYB_S1_GRAM")) : 1;
-    const bool use_gram = gram_env && wave_private && training && sizeof(T) == 2 && (W % 16 == 0) && (H % 8 == 0);
+    const S1Paths paths = s1_paths(es, x, nullptr, N, H, W, Ci, Cop, training, packed_out != nullptr);
+    const bool wave_private = paths.fwd_wave, use_gram = paths.gram_fwd;
     const bool need_a = packed_out || !wave_private || use_gram;     // k = tap*4 + c: the block-level kernels, the Gram statistics, the backward pass
     const bool need_b = wave_private || packed_out;
     if (prepacked && packed_out) {
@@ -622,7 +647,7 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
     a.tilesX = hyb_cdiv(W, S1_TW); a.tilesY = hyb_cdiv(H, S1_TH);
     a.inv_tpi = 1.0f / (float)(a.tilesX * a.tilesY); a.inv_tx = 1.0f / (float)a.tilesX;
     a.vec_ok = (W % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    a.route = (route && wave_private && s1_route_ok(es, x, N, H, W, Ci, Cop)) ? (unsigned*)route : nullptr;
+    a.route = (route && wave_private && paths.route) ? (unsigned*)route : nullptr;
     const long long numTiles = (long long)N * a.tilesX * a.tilesY;
     a.numTiles = (int)numTiles;
     const int gx = s1_grid(numTiles);
@@ -636,7 +661,7 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
         if (!(training && use_gram)) { if (hipError_t e = hipMemsetAsync(gram, 0, tail, st)) return (int)e; }
     }
     if (training && use_gram) {
-        static const int gram_wgs = getenv("HYB_S1_GRAM_WGS") ? atoi(getenv("HYB_S1_GRAM_WGS")) : 512;          // 1024 measured 0.5 % slower
+        static const int gram_wgs = hyb_env_int("HYB_S1_GRAM_WGS", 512);          // 1024 measured 0.5 % slower
         int grows = gram_wgs < 1 ? 1 : (gram_wgs > S1_BWD_PART ? S1_BWD_PART : gram_wgs);
         rc = hyb_stage1w_gram(dtype, a, grows, st);
         if (rc) return rc;
@@ -660,7 +685,7 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
     if (rc) return rc;
     // the apply+pool pass keeps no partial rows, so its grid is free: 2048 workgroups (shorter tile runs, 166 VGPRs = 3 workgroups
     // per CU resident) measured +1 % of the step over 1024.  HYB_S1_APPLY_WGS overrides (A/B).
-    static const int apply_wgs = getenv("HYB_S1_APPLY_WGS") ? atoi(getenv("HYB_S1_APPLY_WGS")) : 2048;
+    static const int apply_wgs = hyb_env_int("HYB_S1_APPLY_WGS", 2048);
     int gx1 = apply_wgs > 0 ? apply_wgs : gx;
     if (gx1 > numTiles) gx1 = (int)numTiles;
     return wave_private ? hyb_stage1w_pass(dtype, 1, a, gx1, st) : s1_dispatch<T, 1>(a, gx1, st);
@@ -671,18 +696,15 @@ static int stage1_bwd_t(const void* dpooled, const float* x, const float* weight
                         const float* mean_invstd, int training, int N, int H, int W, int Ci, int Co, int Cop, float* dweight, float* dgamma,
                         float* dbeta, const void* packed_in, void* workspace, const void* route, hipStream_t st) {
     const size_t es = sizeof(T);
-    char* ws = (char*)workspace;
-    T* wp = (T*)ws;                              ws += al256((size_t)Cop * 64 * es);
-    T* wp2 = (T*)ws;                             ws += al256((size_t)Cop * 64 * es);
-    double* sums = (double*)ws;                  ws += al256(((size_t)Cop * 48 + 2304) * 8);      // reduced row [S1][G], double
-    float* part = (float*)ws;
-    // the wave-private kernel: 16-bit storage, aligned float4 row segments, no ragged 8x16 blocks, 32-bit buffer offsets
-    static const int wave_env = getenv("HYB_S1_WAVE_BWD") ? atoi(getenv("HYB_S1_WAVE_BWD")) : 1;
-    // (fp32 storage: only the split-bf16 build has a wave-private kernel, conv_first_wave.hip)
-    const bool wave_private = wave_env && (sizeof(T) == 2 || HYB_X3) && (W % 16 == 0) && (H % 8 == 0) && (((uintptr_t)x & 15) == 0) &&
-                              (((uintptr_t)dpooled & 15) == 0) && (Cop % 4 == 0) &&
-                              (long long)N * Ci * H * W * 4 < (1ll << 32) && (long long)N * (H / 2) * (W / 2) * Cop * (long long)es < (1ll << 32);
     const int dtype = sizeof(T) == 2 ? HYB_BF16 : HYB_F32;
+    char* ws = (char*)workspace;
+    const S1BwdLayout lay = s1_bwd_layout(dtype, Cop);
+    T *wp = (T*)(ws + lay.wp), *wp2 = (T*)(ws + lay.wp2);
+    double* sums = (double*)(ws + lay.sums);      // reduced row [S1][G], double
+    float* part = (float*)(ws + lay.part);
+    // (fp32 storage: only the split-bf16 build has a wave-private kernel, conv_first_wave.hip)
+    const S1Paths paths = s1_paths(es, x, dpooled, N, H, W, Ci, Cop, training, packed_in != nullptr);
+    const bool wave_private = paths.bwd_wave;
     if (packed_in) {
         wp = (T*)packed_in;                      // packed by the forward pass: [2][Cop][64]
         wp2 = (T*)packed_in + (size_t)Cop * 64;
@@ -699,21 +721,19 @@ static int stage1_bwd_t(const void* dpooled, const float* x, const float* weight
     a.tilesX = hyb_cdiv(W, S1_TW); a.tilesY = hyb_cdiv(H, S1_TH);
     a.inv_tpi = 1.0f / (float)(a.tilesX * a.tilesY); a.inv_tx = 1.0f / (float)a.tilesX;
     a.vec_ok = (W % 4 == 0) && (((uintptr_t)x & 15) == 0);
-    // (the forward's apply pass was wave-private under the same rule: s1_route_ok covers its conditions)
-    a.route = (route && wave_private && s1_route_ok(es, x, N, H, W, Ci, Cop)) ? (unsigned*)const_cast<void*>(route) : nullptr;
+    a.route = (route && wave_private && paths.route) ? (unsigned*)const_cast<void*>(route) : nullptr;
     const long long numTiles = (long long)N * a.tilesX * a.tilesY;
     a.numTiles = (int)numTiles;
     // one pass over x and dpooled (MODE 4), a fixed-order sum of the partial rows, and a finalize on tiny matrices
-    static const int bwd_wgs = getenv("HYB_S1_BWD_WGS") ? atoi(getenv("HYB_S1_BWD_WGS")) : 0;                // 0: 512 (768 = three workgroups per CU for the kernel without G measured 1 % slower)
+    static const int bwd_wgs = hyb_env_int("HYB_S1_BWD_WGS", 0);                // 0: 512 (768 = three workgroups per CU for the kernel without G measured 1 % slower)
     // (saved_g is decided below from the same inputs; the grid only needs the bound)
     int want = bwd_wgs > 0 ? bwd_wgs : S1_BWD_WGS;
     if (want > S1_BWD_PART) want = S1_BWD_PART;
     int gx = (int)(numTiles < want ? numTiles : want);
     if (gx < 1) gx = 1;
     const long long roww = (long long)Cop * 48 + 2304;
-    // the forward pass of a training step (same conditions) left the Gram matrix behind the packed weights: accumulate S1 only
-    static const int gram_env = getenv("HYB_S1_GRAM") ? atoi(getenv("HYB_S1_GRAM")) : 1;
-    const bool saved_g = gram_env && wave_private && training && packed_in != nullptr && sizeof(T) == 2;    // (the Gram pass is 16-bit only)
+    // the forward pass of a training step left the Gram matrix behind the packed weights: accumulate S1 only
+    const bool saved_g = paths.gram_saved;
     const long long rw = saved_g ? (long long)Cop * 48 : roww;
     int rc = wave_private ? hyb_stage1w_bwd(dtype, a, saved_g ? 0 : 1, gx, st) : s1_dispatch<T, 4>(a, gx, st);
     if (rc) return rc;

@@ -1,8 +1,8 @@
 // Stage 1, wave-private forward passes (see conv_first.hip for the stage's overall scheme and the block-level kernels).
 // This file is compiled with -mllvm -amdgpu-mfma-vgpr-form (build.py): every accumulator value is consumed by vector instructions,
 // which cannot read AGPRs, and the kernels are bound by VALU instruction issue -- one v_accvgpr_read per value otherwise.
-#include <stdlib.h>
 #include "conv_first.h"
+#include "hyb_internal.h"
 
 namespace {
 

@@ -9,8 +9,8 @@
 // Workgroup = 4 waves = CB channel blocks x PG pixel groups; the grid walks image tiles
 // (persistent, grid-stride) and folds the BatchNorm batch statistics (sum, sum of squares per
 // output channel, UNet.py:59) into the epilogue from the fp32 accumulators.
-#include <stdlib.h>
 #include "hyb_common.h"
+#include "hyb_internal.h"
 #include "conv_first.h"
 
 namespace {
@@ -417,6 +417,19 @@ __device__ __forceinline__ void pack_store(float* wp, long long i, float v, bool
     else wp[i] = v;
 }
 
+// Source value of element k of a packed 3x3 weight buffer (w fp32 [Co,Ci,3,3]; padded rows / columns are zero):
+//   forward: [Cop][Cip/32][9][32]                      rows = output channels
+//   dgrad:   [Cip][Cop/32][9][32], tap flipped         rows = input channels (the transposed convolution)
+__device__ __forceinline__ float pack_src_value(const float* __restrict__ w, long long k, bool dgrad, int Co, int Ci, int Cop, int Cip) {
+    const int rowc = dgrad ? Cop : Cip;                  // channels along a row of the packed matrix
+    const int c32 = (int)(k % 32);
+    const int tap = (int)((k / 32) % 9);
+    const int chunk = (int)((k / 288) % (rowc / 32));
+    const int row = (int)(k / ((long long)9 * rowc));
+    const int co = dgrad ? chunk * 32 + c32 : row, ci = dgrad ? row : chunk * 32 + c32;
+    return (co < Co && ci < Ci) ? w[((long long)co * Ci + ci) * 9 + (dgrad ? 8 - tap : tap)] : 0.f;
+}
+
 // w fp32 [Co,Ci,3,3] -> packed T (see hybrid_hip.h for the three modes); padded rows/cols are zero.
 template <typename T>
 __global__ void pack_weight_kernel(int mode, const float* __restrict__ w, T* __restrict__ wp, int Co, int Ci, int Cop, int Cip,
@@ -424,20 +437,8 @@ __global__ void pack_weight_kernel(int mode, const float* __restrict__ w, T* __r
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
     float v = 0.f;
-    if (mode == 0) {            // [Cop][Cip/32][9][32]
-        const int c32 = (int)(i % 32);
-        const int tap = (int)((i / 32) % 9);
-        const int chunk = (int)((i / 288) % (Cip / 32));
-        const int co = (int)(i / ((long long)9 * Cip));
-        const int ci = chunk * 32 + c32;
-        if (co < Co && ci < Ci) v = w[((long long)co * Ci + ci) * 9 + tap];
-    } else if (mode == 1) {     // dgrad: rows = input channels: [Cip][Cop/32][9][32], tap flipped
-        const int c32 = (int)(i % 32);
-        const int tap = (int)((i / 32) % 9);
-        const int chunk = (int)((i / 288) % (Cop / 32));
-        const int ci = (int)(i / ((long long)9 * Cop));
-        const int co = chunk * 32 + c32;
-        if (co < Co && ci < Ci) v = w[((long long)co * Ci + ci) * 9 + (8 - tap)];
+    if (mode != 2) {
+        v = pack_src_value(w, i, mode == 1, Co, Ci, Cop, Cip);
     } else {                    // first layer: [Cop][32], k = tap*Ci + ci
         const int k = (int)(i % 32);
         const int co = (int)(i / 32);
@@ -453,11 +454,6 @@ __global__ __launch_bounds__(1024) void stats_reduce_kernel(const float* __restr
 }
 
 constexpr int MAX_STAT_PARTIALS = 512;
-}  // namespace
-int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st,
-                long long xblk = 0);   // conv_v2.hip
-int hyb_conv_v2_supported(int W, int Cip, int Cop);
-namespace {
 
 template <typename T, int NT, int CB, int PG, int CK, bool WLDS = false>
 int launch_conv_ck(const T* x, const T* wp, T* y, float* stats, float* part, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
@@ -496,7 +492,7 @@ template <typename T, int NT, int CB, int PG>
 int launch_conv(const T* x, const T* wp, T* y, float* stats, float* part, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
     constexpr int ES = (int)sizeof(T);
     if constexpr (ES == 2) {
-        static const int wlds = getenv("HYB_CONV_WLDS") ? atoi(getenv("HYB_CONV_WLDS")) : 1;
+        static const int wlds = hyb_env_int("HYB_CONV_WLDS", 1);
         if (wlds) {     // default: weight fragments come from an LDS ring shared by the workgroup (HYB_CONV_WLDS=0: per-wave global loads)
             if constexpr (PG == 1) { if (Cip % 64 == 0) return launch_conv_ck<T, NT, CB, PG, 64, true>(x, wp, y, stats, part, N, H, W, Cip, Cop, st); }
             if constexpr (PG == 2) { if (Cip % 64 == 0) return launch_conv_ck<T, NT, CB, PG, 64, true>(x, wp, y, stats, part, N, H, W, Cip, Cop, st); }
@@ -541,13 +537,12 @@ int conv_fwd_t(int first, const void* x, const void* wp, void* y, float* stats, 
     HYB_CHECK_ARG(Cip % 32 == 0);
     if constexpr (sizeof(T) == 2) {
         // bf16: the asynchronous kernel (conv_v2.hip) takes every shape it has a variant for; HYB_CONV_V2=0 keeps the first-generation kernel
-        static const int v2 = getenv("HYB_CONV_V2") ? atoi(getenv("HYB_CONV_V2")) : 1;
-        if (v2) {
+        if (hyb_sw_conv_v2()) {
             const int rows = part ? hyb_conv_stats_rows(0, N, H, W, Cop) : 0;
             HybProfileHook* hook = hyb_find_hook(1, Cip, Cop);
             if (hook) hipEventRecord(hook->ev0, st);
             const int rc = hyb_conv_v2(x, wp, y, part, N, H, W, Cip, Cop, rows, st);
-            if (rc != -100) {
+            if (rc != HYB_NO_VARIANT) {
                 if (hook) hipEventRecord(hook->ev1, st);
                 if (rc) return rc;
                 if (part && stats) {
@@ -558,7 +553,7 @@ int conv_fwd_t(int first, const void* x, const void* wp, void* y, float* stats, 
             }
         }
     }
-    static const int cfg = getenv("HYB_CONV_CFG") ? atoi(getenv("HYB_CONV_CFG")) : 0;
+    static const int cfg = hyb_env_int("HYB_CONV_CFG", 0);
     if (cfg != 2 && Cop % 256 == 0) return launch_conv<T, 4, 4, 1>((const T*)x, (const T*)wp, (T*)y, stats, part, N, H, W, Cip, Cop, st);
     if (Cop % 128 == 0) return launch_conv<T, 4, 2, 2>((const T*)x, (const T*)wp, (T*)y, stats, part, N, H, W, Cip, Cop, st);
     if (Cop % 64 == 0) return launch_conv<T, 4, 1, 4>((const T*)x, (const T*)wp, (T*)y, stats, part, N, H, W, Cip, Cop, st);
@@ -569,8 +564,7 @@ int conv_fwd_t(int first, const void* x, const void* wp, void* y, float* stats, 
 
 // Internal (hyb_convstage_bwd): does the bf16 dgrad conv of this shape run on the asynchronous kernel (which can read a block-planar input)?
 int hyb_conv_dgrad_planar_ok(int dtype, int W, int Cin_p, int Cout_p) {
-    static const int v2 = getenv("HYB_CONV_V2") ? atoi(getenv("HYB_CONV_V2")) : 1;
-    return dtype == HYB_BF16 && v2 && hyb_conv_v2_supported(W, Cin_p, Cout_p);
+    return dtype == HYB_BF16 && hyb_sw_conv_v2() && hyb_conv_v2_supported(W, Cin_p, Cout_p);
 }
 // Internal: conv3x3 (dgrad weights) of a block-planar bf16 input [Cin_p/32][N][H][W][32] -> NHWC output
 int hyb_conv3x3_planar_in(const void* x, const void* wp, void* y, int N, int H, int W, int Cin_p, int Cout_p, hipStream_t st) {
@@ -593,22 +587,7 @@ __global__ void pack_weight_dual_kernel(const float* __restrict__ w, T* __restri
     if (i >= 2 * count) return;
     const bool second = i >= count;
     const long long k = second ? i - count : i;
-    const int c32 = (int)(k % 32);
-    const int tap = (int)((k / 32) % 9);
-    float v = 0.f;
-    if (!second) {
-        const int chunk = (int)((k / 288) % (Cip / 32));
-        const int co = (int)(k / ((long long)9 * Cip));
-        const int ci = chunk * 32 + c32;
-        if (co < Co && ci < Ci) v = w[((long long)co * Ci + ci) * 9 + tap];
-        pack_store(wp0, k, v, true);
-    } else {
-        const int chunk = (int)((k / 288) % (Cop / 32));
-        const int ci = (int)(k / ((long long)9 * Cop));
-        const int co = chunk * 32 + c32;
-        if (co < Co && ci < Ci) v = w[((long long)co * Ci + ci) * 9 + (8 - tap)];
-        pack_store(wp1, k, v, true);
-    }
+    pack_store(second ? wp1 : wp0, k, pack_src_value(w, k, second, Co, Ci, Cop, Cip), true);
 }
 int hyb_conv_pack_weight_dual(int dtype, const float* w, void* wp0, void* wp1, int Co, int Ci, int Cop, int Cip, hipStream_t st) {
     const long long count = (long long)Cop * 9 * Cip;
@@ -644,22 +623,7 @@ __global__ void pack_weight_many_kernel(PackMany a) {
     const int Co = a.Co[s], Ci = a.Ci[s], Cop = a.Cop[s], Cip = a.Cip[s];
     const bool second = i >= count;
     const long long k = second ? i - count : i;
-    const int c32 = (int)(k % 32);
-    const int tap = (int)((k / 32) % 9);
-    float v = 0.f;
-    if (!second) {
-        const int chunk = (int)((k / 288) % (Cip / 32));
-        const int co = (int)(k / ((long long)9 * Cip));
-        const int ci = chunk * 32 + c32;
-        if (co < Co && ci < Ci) v = w[((long long)co * Ci + ci) * 9 + tap];
-        pack_store((T*)a.wp0[s], k, v, true);
-    } else {
-        const int chunk = (int)((k / 288) % (Cop / 32));
-        const int ci = (int)(k / ((long long)9 * Cop));
-        const int co = chunk * 32 + c32;
-        if (co < Co && ci < Ci) v = w[((long long)co * Ci + ci) * 9 + (8 - tap)];
-        pack_store((T*)a.wp1[s], k, v, true);
-    }
+    pack_store((T*)(second ? a.wp1[s] : a.wp0[s]), k, pack_src_value(w, k, second, Co, Ci, Cop, Cip), true);
 }
 // s1_wp != NULL: also the first stage's two layouts (s1_w [s1_Co][s1_Ci][3][3] -> s1_wp [2][s1_Cop][64])
 int hyb_conv_pack_weight_many(int dtype, int n, const float* const* w, void* const* wp0, void* const* wp1, const int* Co, const int* Ci, const int* Cop,
@@ -694,13 +658,8 @@ __global__ void pack_weight_fwd_many_kernel(PackMany a) {
         ((T*)a.s1_wp)[i] = from_f32<T>(s1w_pack_value(a.s1_w, second ? i - total : i, second, a.s1_Co, a.s1_Ci));
         return;
     }
-    const int Co = a.Co[s], Ci = a.Ci[s], Cip = a.Cip[s];
-    if (i >= (long long)a.Cop[s] * 9 * Cip) return;
-    const int c32 = (int)(i % 32), tap = (int)((i / 32) % 9), chunk = (int)((i / 288) % (Cip / 32)), co = (int)(i / ((long long)9 * Cip));
-    const int ci = chunk * 32 + c32;
-    float v = 0.f;
-    if (co < Co && ci < Ci) v = a.w[s][((long long)co * Ci + ci) * 9 + tap];
-    pack_store((T*)a.wp0[s], i, v, true);
+    if (i >= (long long)a.Cop[s] * 9 * a.Cip[s]) return;
+    pack_store((T*)a.wp0[s], i, pack_src_value(a.w[s], i, false, a.Co[s], a.Ci[s], a.Cop[s], a.Cip[s]), true);
 }
 int hyb_conv_pack_weight_fwd_many(int dtype, int n, const float* const* w, void* const* wp0, const int* Co, const int* Ci, const int* Cop, const int* Cip,
                                   const float* s1_w, void* s1_wp, int s1_Co, int s1_Ci, int s1_Cop, hipStream_t st) {

@@ -20,9 +20,9 @@
 //     order (bit-reproducible);
 //   * POOL instantiations (inference, hyb_conv_v2_pool) never store the raw convolution: the epilogue applies the BatchNorm affine to the
 //     fp32 accumulators, takes the 2 x 2 maximum across lanes, applies the ReLU and stores the pooled map (pool_affine_max below).
-#include <stdlib.h>
 #include <type_traits>
 #include "hyb_common.h"
+#include "hyb_internal.h"
 
 namespace {
 
@@ -717,12 +717,14 @@ double v2_cost(int N, int H, int W, int TH, int TW, int gy) {
 
 }  // namespace
 
-// Internal (conv_fwd.hip): returns -100 when no asynchronous variant fits this shape.  part: partial-statistics rows
-// [stat_rows][2][Cop] (may be NULL), all of them written.
-// which shapes hyb_conv_v2 takes (the same tests as below)
+// Which shapes the asynchronous kernels take (conv_v2_dispatch asks this function: every channel count that is a multiple of 32 has a
+// variant; the bounds keep a halo row block and a weight block inside 32-bit buffer offsets)
 int hyb_conv_v2_supported(int W, int Cip, int Cop) {
-    return !(Cip % 32 != 0 || (long long)40 * W * Cip >= (1ll << 29) || (long long)256 * 9 * Cip >= (1ll << 29)) && Cop % 32 == 0;
+    return Cip % 32 == 0 && Cop % 32 == 0 && (long long)40 * W * Cip < (1ll << 29) && (long long)256 * 9 * Cip < (1ll << 29);
 }
+
+// Internal (conv_fwd.hip): returns HYB_NO_VARIANT when no asynchronous variant fits this shape.  part: partial-statistics rows
+// [stat_rows][2][Cop] (may be NULL), all of them written.
 
 // xblk = 0: NHWC input; else the block-planar input's block stride in elements (see conv3x3_v2_kernel)
 // ss != NULL: the POOL instantiation of the same variant (y = the pooled map, no statistics)
@@ -730,14 +732,14 @@ static int conv_v2_dispatch(const void* x, const void* wp, void* y, float* part,
                             hipStream_t st, long long xblk) {
     const int xpix = xblk ? 32 : Cip;
     if (!xblk) xblk = 32;
-    if (Cip % 32 != 0 || (long long)40 * W * Cip >= (1ll << 29) || (long long)256 * 9 * Cip >= (1ll << 29)) return -100;   // 32-bit buffer offsets
+    if (!hyb_conv_v2_supported(W, Cip, Cop)) return HYB_NO_VARIANT;
     const bf16* xb = (const bf16*)x; const bf16* wb = (const bf16*)wp; bf16* yb = (bf16*)y;
 #define V2(NT_, CB_, PGR_, PGC_, R_) launch_v2<NT_, CB_, PGR_, PGC_, R_>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk)
     // Measured on the 224 x 224 clip stages: two four-wave workgroups per CU (their epilogues and MFMA phases interleave) win for
     // Cop <= 128; 256-channel blocks need the whole CU's LDS for a deep weight ring.  HYB_V2_NW=4|8 forces one family.
-    static const int nw_env = getenv("HYB_V2_NW") ? atoi(getenv("HYB_V2_NW")) : 0;
+    static const int nw_env = hyb_env_int("HYB_V2_NW", 0);
     const int nw = nw_env ? nw_env : (Cop % 256 == 0 ? 8 : 4);
-    static const int k32_env = getenv("HYB_CONV_K32") ? atoi(getenv("HYB_CONV_K32")) : 1;      // (=0: A/B, the ring kernel for 32 input channels too)
+    static const int k32_env = hyb_env_int("HYB_CONV_K32", 1);      // (=0: A/B, the ring kernel for 32 input channels too)
     if (k32_env && nw == 4 && Cip == 32 && Cop % 64 == 0) {
         // one channel block per tile: weights in registers, one barrier per tile (conv3x3_k32_kernel)
         return v2_cost(N, H, W, 8, 28, Cop / 64) <= v2_cost(N, H, W, 4, 56, Cop / 64)
@@ -749,7 +751,7 @@ static int conv_v2_dispatch(const void* x, const void* wp, void* y, float* part,
         if (Cop % 128 == 0) return v2_cost(N, H, W, 8, 28, Cop / 128) <= v2_cost(N, H, W, 4, 56, Cop / 128) ? V2(4, 2, 2, 1, 4) : V2(4, 2, 1, 2, 4);
         if (Cop % 64 == 0) return v2_cost(N, H, W, 8, 28, Cop / 64) <= v2_cost(N, H, W, 4, 56, Cop / 64) ? V2(2, 2, 2, 1, 4) : V2(2, 2, 1, 2, 4);
         if (Cop % 32 == 0) return V2(2, 1, 4, 1, 4);
-        return -100;
+        return HYB_NO_VARIANT;
     }
     if (Cop % 256 == 0) {
         return v2_cost(N, H, W, 8, 28, Cop / 256) <= v2_cost(N, H, W, 4, 56, Cop / 256) ? V2(4, 4, 2, 1, 6) : V2(4, 4, 1, 2, 6);
@@ -760,7 +762,7 @@ static int conv_v2_dispatch(const void* x, const void* wp, void* y, float* part,
     if (Cop % 64 == 0) return V2(4, 1, 4, 2, 5);
     if (Cop % 32 == 0) return V2(2, 1, 4, 2, 6);
 #undef V2
-    return -100;
+    return HYB_NO_VARIANT;
 }
 
 int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st, long long xblk) {
@@ -768,8 +770,8 @@ int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int 
 }
 
 // Internal (hyb_convstage_infer): pooled[N][H/2][W/2][Cop] = maxpool2x2(relu(conv3x3(x, wp) * scale + shift)), ss = [2][Cop] scale | shift, the raw
-// convolution never stored.  -100 for the shapes hyb_conv_v2 does not take.
+// convolution never stored.  HYB_NO_VARIANT for the shapes hyb_conv_v2 does not take.
 int hyb_conv_v2_pool(const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
-    if (!ss || H < 2 || W < 2 || !hyb_conv_v2_supported(W, Cip, Cop)) return -100;
+    if (!ss || H < 2 || W < 2 || !hyb_conv_v2_supported(W, Cip, Cop)) return HYB_NO_VARIANT;
     return conv_v2_dispatch(x, wp, pooled, nullptr, ss, N, H, W, Cip, Cop, 0, st, 0);
 }

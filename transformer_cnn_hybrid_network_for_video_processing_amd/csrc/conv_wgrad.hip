@@ -9,11 +9,9 @@
 // A workgroup owns one output block (64 co x CIT*16 ci x 9 taps, fp32 accumulators in registers) and
 // walks a strided subset of 8x16-pixel tiles; partial blocks go to fp32 slabs [S][Cop][9][Cip] that a
 // second kernel sums in a fixed order (bitwise reproducible; no float atomics).
-#include <stdlib.h>
 #include <type_traits>
 #include "hyb_common.h"
-
-int hyb_wgrad_reduce_multi(int n, const HybSlabInfo* infos, hipStream_t st);
+#include "hyb_internal.h"
 
 namespace {
 
@@ -643,7 +641,7 @@ int w2_launch(dim3 grid, HybProfileHook* hook, hipStream_t st, const bf16* x, co
     // consumer x producer waves per workgroup: 4x4 (one of each per SIMD) or 8x8 (two of each per SIMD).  Measured in one call
     // (fused, config 2): the HBM-bound 32-channel-block stage gains from 8x8 (127 -> 110 us), the 64-channel-block stages lose
     // (94 -> 110 us: 128 VGPRs spill the 36-tile accumulators' helpers); 8 consumers + 4 producers is never best when fused.
-    static const int env = getenv("HYB_WGRAD_WAVES") ? atoi(getenv("HYB_WGRAD_WAVES")) : 0;
+    static const int env = hyb_env_int("HYB_WGRAD_WAVES", 0);
     const int cfg = env ? env : (CI == 32 ? 88 : 44);
     if (cfg == 88) return w2_launch_cw<FUSE, CI, 8, 8>(grid, hook, st, x, dy, slab, N, H, W, Cip, Cop, tX, tY, nT, fz);
     return w2_launch_cw<FUSE, CI, 4, 4>(grid, hook, st, x, dy, slab, N, H, W, Cip, Cop, tX, tY, nT, fz);
@@ -713,6 +711,12 @@ int hyb_wgrad_reduce_multi(int n, const HybSlabInfo* infos, hipStream_t st) {
     HYB_LAUNCH_CHECK();
     return 0;
 }
+// Which non-first shapes take the warp-specialised kernel (the only one that can write a block-planar dyraw): wgrad_t asks this function
+int hyb_wgrad_v2_supported(int dtype, int W, int Cip, int Cop) {
+    const int ci_blk = Cip % 64 == 0 ? 64 : 32;
+    return dtype == HYB_BF16 && hyb_sw_wgrad_v2() && Cip % 32 == 0 && Cop % 64 == 0 && (Cop / 64) * (Cip / ci_blk) <= 256 &&
+           (long long)12 * W * (Cip > Cop ? Cip : Cop) < (1ll << 29);
+}
 namespace {
 
 struct WgradPlan { int S, gy, cit; long long per_slab; };
@@ -722,7 +726,7 @@ inline WgradPlan wgrad_plan(int first, int N, int H, int W, int Cip, int Cop) {
     const long long numTiles = (long long)N * hyb_cdiv(H, WG_TH) * hyb_cdiv(W, WG_TW);
     if (first) { p.cit = 0; p.gy = Cop / 32; p.per_slab = (long long)Cop * 32; }
     else { p.cit = (Cip % 64 == 0) ? 4 : 2; p.gy = ((Cop + 63) / 64) * (Cip / (p.cit * 16)); p.per_slab = (long long)Cop * 9 * Cip; }
-    static const int wgs = getenv("HYB_WGRAD1_WGS") ? atoi(getenv("HYB_WGRAD1_WGS")) : 512;       // first-generation kernel: workgroups in total (A/B)
+    static const int wgs = hyb_env_int("HYB_WGRAD1_WGS", 512);       // first-generation kernel: workgroups in total (A/B)
     long long s = (wgs > 0 ? wgs : 512) / p.gy;
     if (s < 1) s = 1;
     if (s > numTiles) s = numTiles;
@@ -738,10 +742,9 @@ int wgrad_t(int first, const void* x, const void* dy, float* dw, int N, int H, i
     if (ws_bytes < (size_t)p.S * p.per_slab * sizeof(float)) return HYB_E_WORKSPACE;
     float* slab = (float*)ws;
     if constexpr (sizeof(T) == 2) {
-        static const int v2 = getenv("HYB_WGRAD_V2") ? atoi(getenv("HYB_WGRAD_V2")) : 1;
-        const int ci_blk = Cip % 64 == 0 ? 64 : 32;
-        const int blocks = (Cop / 64) * (Cip / ci_blk);
-        if (v2 && !first && Cip % 32 == 0 && Cop % 64 == 0 && blocks <= 256 && (long long)12 * W * (Cip > Cop ? Cip : Cop) < (1ll << 29)) {
+        if (!first && hyb_wgrad_v2_supported(HYB_BF16, W, Cip, Cop)) {
+            const int ci_blk = Cip % 64 == 0 ? 64 : 32;
+            const int blocks = (Cop / 64) * (Cip / ci_blk);
             // generation of the fused kernel for this shape: 0 second (below), 1 third (conv_wgrad_v3.h); 2 / 3 only in experiment builds
             const int gen3 = (fz && ci_blk == 64) ? w3_supported(H, W, Cip, Cop) : 0;
             const int tX = hyb_cdiv(W, W2_TW), tY = gen3 == 3 ? H / 4 : hyb_cdiv(H, W2_TH);
@@ -804,13 +807,6 @@ int wgrad_t(int first, const void* x, const void* dy, float* dw, int N, int H, i
 }  // namespace
 
 // Internal: weight gradient with the BatchNorm/ReLU/MaxPool backward fused into the tile staging (non-first stages)
-// which shapes take the warp-specialised kernel (the only one that can write a block-planar dyraw): the tests of wgrad_t
-int hyb_wgrad_v2_supported(int dtype, int W, int Cip, int Cop) {
-    static const int v2 = getenv("HYB_WGRAD_V2") ? atoi(getenv("HYB_WGRAD_V2")) : 1;
-    const int ci_blk = Cip % 64 == 0 ? 64 : 32;
-    return dtype == HYB_BF16 && v2 && Cip % 32 == 0 && Cop % 64 == 0 && (Cop / 64) * (Cip / ci_blk) <= 256 &&
-           (long long)12 * W * (Cip > Cop ? Cip : Cop) < (1ll << 29);
-}
 
 int hyb_conv3x3_wgrad_fused(int dtype, const void* x, const void* y, const void* dp, const float* ss, const float* mi, const float* gamma,
                             const float* sums, int training, long long count, void* dyraw_out, long long dyraw_blk, float* dw, int N, int H, int W,

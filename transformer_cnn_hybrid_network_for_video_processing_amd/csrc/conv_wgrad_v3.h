@@ -296,7 +296,7 @@ inline int w3_supported(int H, int W, int Cip, int Cop) {
 #ifdef HYB_NO_V3
     static const int v3 = 0;
 #else
-    static const int v3_env = getenv("HYB_WGRAD_V3") ? atoi(getenv("HYB_WGRAD_V3")) : W3_DEFAULT;
+    static const int v3_env = hyb_env_int("HYB_WGRAD_V3", W3_DEFAULT);
 #ifdef HYB_WGRAD_EXPERIMENTS
     static const int v3 = v3_env;                       // 2 / 3: the experiment kernels of scripts/micro/wgrad_variants
 #else

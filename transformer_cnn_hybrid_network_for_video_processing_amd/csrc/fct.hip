@@ -12,22 +12,12 @@
 //   MaxPool2d(2), AvgPool2d(2,2), Upsample(x2 nearest), cat, add   FCT.py:147,170,180,222,238-240
 //   DiceLoss                                                   Metrics.py:5-22
 #include <math.h>
-#include <stdlib.h>
 #include "hyb_common.h"
+#include "hyb_internal.h"
 #include "conv_geo.h"
-
-int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* B, void* const* C, const float* const* bias, int out_f32,
-                int Mo, int No, int R, int lda, int ldb, int ldc, int relu, int accumulate, hipStream_t st, const void* const* Amask = nullptr,
-                const void* const* Cmask = nullptr);
-bool hyb_conv_implicit_ok(int Ci, long long rows);
-int hyb_conv_implicit_gemm(const float* x, const float* wp, const float* bias, float* y, int n_img, int H, int W, int Ci, int Ho, int Wo, int Co,
-                           int Kp, int k, int stride, int pad, int dil, int ldy, int relu, hipStream_t st);
-int hyb_flash_attention_fwd(int dtype, const void* q, const void* k, const void* v, void* out, float* lse, int N, int L, int H, int dhp, int ld,
-                            float scale, hipStream_t st, int dh_true);
 
 namespace {
 
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int up8(int v) { return (v + 7) / 8 * 8; }
 #define FCT_TRY(call) do { int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
 
@@ -228,8 +218,7 @@ extern "C" int hyb_conv2d_fwd(const float* x, const float* w, const float* b, fl
     float* col = (float*)((char*)workspace + al256((size_t)Co * Kp * 4));
     hipLaunchKernelGGL(conv_pack_g_kernel, dim3(grid1((long long)Co * Kp)), dim3(256), 0, st, w, wp, Co, Ci, k * k, Kp);
     HYB_LAUNCH_CHECK();
-    static const int implicit_env = getenv("HYB_CONV_IMPLICIT") ? atoi(getenv("HYB_CONV_IMPLICIT")) : 1;
-    if (implicit_env && !ident && hyb_conv_implicit_ok(Ci, (long long)N * g.Ho * g.Wo) && (long long)N * g.Ho * g.Wo <= 0x7fffffff / 32 * 32 &&
+    if (hyb_sw_conv_implicit() && !ident && hyb_conv_implicit_ok(Ci, (long long)N * g.Ho * g.Wo) && (long long)N * g.Ho * g.Wo <= 0x7fffffff / 32 * 32 &&
         (long long)N * H * W <= 0x7fffffff / 32 * 32) {
         // no patch matrix: the GEMM gathers its A fragments from the image (all images in one launch)
         float* gemm_out = ((act == HYB_ACT_GELU || act == HYB_ACT_SIGMOID) && z_out) ? z_out : y;

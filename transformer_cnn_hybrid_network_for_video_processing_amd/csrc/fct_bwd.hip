@@ -9,23 +9,12 @@
 //   LayerNorm over C, MaxPool2d(2) (gradient to the first maximum in scan order, like torch), Upsample x2 (sum of the 2x2 block),
 //   cat (split), DiceLoss, dropout (counter-based mask regenerated from the seed).
 #include <math.h>
-#include <stdlib.h>
 #include "hyb_common.h"
+#include "hyb_internal.h"
 #include "conv_geo.h"
-
-int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* B, void* const* C, const float* const* bias, int out_f32,
-                int Mo, int No, int R, int lda, int ldb, int ldc, int relu, int accumulate, hipStream_t st, const void* const* Amask = nullptr,
-                const void* const* Cmask = nullptr);
-
-bool hyb_conv_implicit_ok(int Ci, long long rows);
-int hyb_conv_implicit_gemm(const float* x, const float* wp, const float* bias, float* y, int n_img, int H, int W, int Ci, int Ho, int Wo, int Co,
-                           int Kp, int k, int stride, int pad, int dil, int ldy, int relu, hipStream_t st);
-int hyb_flash_attention_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta_ws,
-                            void* dq, void* dk, void* dv, int N, int L, int H, int dhp, int ld, float scale, hipStream_t st, int dh_true);
 
 namespace {
 
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int up8(int v) { return (v + 7) / 8 * 8; }
 inline int grid1(long long n) { return hyb_cdiv(n, 256); }
 #define FCT_TRY(call) do { int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
@@ -604,7 +593,7 @@ static void launch_direct_wgrad(const float* dy, int lddy, const float* x, int l
 // geo != NULL: x is the NHWC image of the convolution `geo` (K = k*k*Ci, Ci % 16 == 0), gathered implicitly (direct_wgrad_kernel<.., true>)
 int hyb_sliced_wgrad_cs(const float* dy, int lddy, const float* x, int ldx, float* out, float* colsum, long long P, int Nn, int K, int accumulate,
                         void* ws, void* cws, hipStream_t st, const ConvGeo* geo = nullptr) {
-    static const int legacy = getenv("HYB_FCT_WGRAD_V1") ? atoi(getenv("HYB_FCT_WGRAD_V1")) : 0;      // first-generation kernel (A/B)
+    static const int legacy = hyb_env_int("HYB_FCT_WGRAD_V1", 0);      // first-generation kernel (A/B)
     int ntl, ktl, rows, S;
     direct_geometry(P, Nn, K, ntl, ktl, rows, S);
     float* cpart = colsum ? (float*)cws : nullptr;
@@ -692,10 +681,9 @@ extern "C" int hyb_conv2d_bwd(const float* dy, const float* x, const float* w, c
     void* ws_c = ws;
     // stride-1 input gradient = a convolution of dz with the flipped kernel (padding dil*(k-1) - pad): the same implicit GEMM as the
     // forward, no dcol matrix and no col2im pass
-    static const int implicit_env = getenv("HYB_CONV_IMPLICIT") ? atoi(getenv("HYB_CONV_IMPLICIT")) : 1;
-    const bool dgrad_implicit = implicit_env && dx && !ident && stride == 1 && dilation * (k - 1) >= pad && hyb_conv_implicit_ok(Co8, (long long)N * H * W);
+    const bool dgrad_implicit = hyb_sw_conv_implicit() && dx && !ident && stride == 1 && dilation * (k - 1) >= pad && hyb_conv_implicit_ok(Co8, (long long)N * H * W);
     // weight gradient straight from the image (no patch matrix) whenever a k tile of 16 columns stays inside one tap
-    static const int wgrad_implicit_env = getenv("HYB_WGRAD_IMPLICIT") ? atoi(getenv("HYB_WGRAD_IMPLICIT")) : 1;
+    static const int wgrad_implicit_env = hyb_env_int("HYB_WGRAD_IMPLICIT", 1);
     const bool wgrad_implicit = wgrad_implicit_env && !ident && Ci % 16 == 0 && Kp == kk * Ci;
     // unpadded shapes need no repacking of the results: the slab sums land in dw (1x1: [Co][Ci] is the packed layout) and db directly
     float* dw_dst = (k == 1 && Kp == Ci && Co8 == Co) ? dw : dwp;

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_lds_kernel(GemmArgs args, int 
 
 // Shapes the LDS kernel takes: 16-byte-aligned operands and row strides, at least 64 columns.  Returns false -> gemm_nt_tall_kernel.
 bool gt_lds_ok(const GemmArgs& a, bool implicit) {
-    static const int env = getenv("HYB_GEMM_LDS") ? atoi(getenv("HYB_GEMM_LDS")) : 1;
+    static const int env = hyb_env_int("HYB_GEMM_LDS", 1);
     if (!env || a.No < 64 || a.R % 4 != 0 || a.ldb % 4 != 0) return false;
     if (((uintptr_t)a.g[0].A | (uintptr_t)a.g[0].B) & 15) return false;
     if (!implicit && (a.lda % 4 != 0 || (long long)a.lda * 128 * 4 >= 0x7fffffffll)) return false;      // (32-bit byte offsets inside a 128-row block)
@@ -209,7 +209,7 @@ void gt_go(const GemmArgs& a, const ConvGather& cg, long long blocks, int tiles_
         (void)hipFuncSetAttribute((const void*)gemm_nt_lds_kernel<BN, S, IMPLICIT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         once = true;
     }
-    static const int order_env = getenv("HYB_GEMM_LDS_ORDER") ? atoi(getenv("HYB_GEMM_LDS_ORDER")) : 1;      // (=0: A/B, tap-major K walk)
+    static const int order_env = hyb_env_int("HYB_GEMM_LDS_ORDER", 1);      // (=0: A/B, tap-major K walk)
     const int ci = IMPLICIT ? (1 << cg.log2ci) : 0;
     const int korder = (IMPLICIT && order_env && ci % 32 == 0 && a.R == cg.k * cg.k * ci && cg.k > 1) ? 1 : 0;
     hipLaunchKernelGGL((gemm_nt_lds_kernel<BN, S, IMPLICIT>), dim3((unsigned)blocks), dim3(256), lds, st, a, tiles_n, row_blocks, cg, korder);
@@ -217,7 +217,7 @@ void gt_go(const GemmArgs& a, const ConvGather& cg, long long blocks, int tiles_
 
 template <bool IMPLICIT>
 int gt_launch(const GemmArgs& a, const ConvGather& cg, hipStream_t st) {
-    static const int s_env = getenv("HYB_GEMM_LDS_S") ? atoi(getenv("HYB_GEMM_LDS_S")) : 0;
+    static const int s_env = hyb_env_int("HYB_GEMM_LDS_S", 0);
     const int row_blocks = hyb_cdiv(a.Mo, 128);
     const bool wide = a.No > 64;
     const int tiles_n = hyb_cdiv(a.No, wide ? 128 : 64);

@@ -3,6 +3,7 @@
 // One wave per token row (D <= 2048), 8 features per lane per chunk, statistics by wave shuffles.
 // Also the classifier head (mean over T + Linear) and the cross-entropy loss: tiny, one kernel each.
 #include "hyb_common.h"
+#include "hyb_internal.h"
 
 namespace {
 
@@ -531,9 +532,6 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_kernel(const float* __r
 
 }  // namespace
 
-int hyb_ln_residual_fwd_inc(int dtype, const void* x, const void* skip, const float* gamma, const float* beta, void* y, float* stats,
-                            int M, int D, float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc,
-                            void* stream);
 extern "C" int hyb_ln_residual_fwd(int dtype, const void* x, const void* skip, const float* gamma, const float* beta, void* y, float* stats,
                                    int M, int D, float eps, float out_scale, float p_drop, unsigned long long seed, void* stream) {
     return hyb_ln_residual_fwd_inc(dtype, x, skip, gamma, beta, y, stats, M, D, eps, out_scale, p_drop, seed, nullptr, stream);

@@ -7,18 +7,9 @@
 //   transposed source : element (row, r) at p[r*ld + row]   (vector loads along row, scattered LDS writes)
 // fp32 sources (the master weights) are converted to T while staging.  Token counts (M = B*T = 128..512) are
 // small, so these GEMMs are latency-bound; tiles are 64x64 or 32x32 to spread them over more CUs.
-#include <stdlib.h>
 #include "hyb_common.h"
+#include "hyb_internal.h"
 #include "ln_rows.h"
-
-int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* B, void* const* C, const float* const* bias, int out_f32,
-                int Mo, int No, int R, int lda, int ldb, int ldc, int relu, int accumulate, hipStream_t st, const void* const* Amask = nullptr,
-                const void* const* Cmask = nullptr);
-int hyb_linear_dw_multi(int dtype, int groups, const void* const* dy, const void* const* mask, const void* const* x, float* const* dW,
-                        float* const* db, const int* N, const int* K, const int* lddy, const int* ldx, int M, hipStream_t st,
-                        int nriders, const HybDwRider* riders);
-int hyb_gemm_skinny_wf32(int dtype, const void* A, const float* Bf, void* C, const float* bias, int Mo, int No, int R, int lda, int ldb, int ldc, int relu,
-                         int accumulate, int transposed_b, hipStream_t st);
 
 namespace {
 
@@ -363,7 +354,7 @@ int launch_gemm(const GemmArgs& a, int groups, hipStream_t st) {
         hipLaunchKernelGGL((gemm_kernel<T, TA, TB, TC, TRANS_A, TRANS_B, 64>), grid, dim3(256), 0, st, a);
     } else {
         dim3 grid(hyb_cdiv(a.No, 32), hyb_cdiv(a.Mo, 32), groups);
-        static const int ks4 = getenv("HYB_GEMM_KS4") ? atoi(getenv("HYB_GEMM_KS4")) : 1;       // (=0: A/B, one k-step per round)
+        static const int ks4 = hyb_env_int("HYB_GEMM_KS4", 1);       // (=0: A/B, one k-step per round)
         if (ks4 && a.R >= 128) hipLaunchKernelGGL((gemm_kernel<T, TA, TB, TC, TRANS_A, TRANS_B, 32, 4>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((gemm_kernel<T, TA, TB, TC, TRANS_A, TRANS_B, 32>), grid, dim3(256), 0, st, a);
     }
@@ -808,7 +799,7 @@ template <typename T>
 int linear_fwd_t(const void* x, int ldx, const float* W, const float* b, void* y, int M, int N, int K, int relu, hipStream_t st) {
     {                                                       // few-tile products: eight waves split K, fragments straight from the master weights
         const int rc = hyb_gemm_skinny_wf32(sizeof(T) == 2 ? HYB_BF16 : HYB_F32, x, W, y, b, M, N, K, ldx, K, N, relu, 0, 0, st);
-        if (rc != -100) return rc;
+        if (rc != HYB_NO_VARIANT) return rc;
     }
     GemmArgs a{};
     a.g[0] = GemmGroup{x, W, y, b, nullptr, nullptr};
@@ -837,8 +828,8 @@ int linear_bwd_t(const void* x, int ldx, const float* W, const void* Wt, const v
         if (rc) return rc;
     } else if (dx) { // dx[m][k] = sum_n dym[m][n] * W[n][k]
         int rc = hyb_gemm_skinny_wf32(sizeof(T) == 2 ? HYB_BF16 : HYB_F32, dym, W, dx, nullptr, M, K, N, N, K, ldx, 0, accumulate_dx, 1, st);
-        if (rc != -100 && rc != 0) return rc;
-        if (rc == -100) {            // not a few-tile shape: the LDS-staged kernel
+        if (rc != HYB_NO_VARIANT && rc != 0) return rc;
+        if (rc == HYB_NO_VARIANT) {            // not a few-tile shape: the LDS-staged kernel
         GemmArgs a{};
         a.g[0] = GemmGroup{dym, W, dx, nullptr, nullptr, nullptr};
         a.Mo = M; a.No = K; a.R = N; a.lda = N; a.ldb = K; a.ldc = ldx; a.relu = 0; a.accumulate = accumulate_dx;
@@ -888,9 +879,9 @@ int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* 
     a.Mo = Mo; a.No = No; a.R = R; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.relu = relu; a.accumulate = accumulate;
     dim3 grid(hyb_cdiv(No, 32), hyb_cdiv(Mo, 32), groups);
     // few tiles (M = 128, N = 512: 64 workgroups on 256 CUs): eight waves split K to shorten the per-wave load/MFMA chain
-    static const int w8env = getenv("HYB_GEMM_W8") ? atoi(getenv("HYB_GEMM_W8")) : 1;
+    static const int w8env = hyb_env_int("HYB_GEMM_W8", 1);
     const bool w8 = w8env && (long long)grid.x * grid.y * grid.z <= 256 && R >= 256;
-    static const int tall_env = getenv("HYB_GEMM_TALL") ? atoi(getenv("HYB_GEMM_TALL")) : 1;
+    static const int tall_env = hyb_env_int("HYB_GEMM_TALL", 1);
     if (dtype == HYB_F32 && tall_env && groups == 1 && !Amask && !Cmask && Mo >= 2048) {
         // pixel-side GEMMs (M = N*H*W): one pass over A per column tile, four independent waves per workgroup
         const int row_blocks = hyb_cdiv(Mo, 128);
@@ -917,18 +908,18 @@ int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* 
 }
 
 // Internal: hyb_gemm_nt with LayerNorm + residual as the prologue (gemm_nt_ln_kernel): A = dropout((LN(x) * gamma + beta + skip) * out_scale),
-// also written to y (+ stats [2][Mo]) by the column-0 workgroups.  Returns -100 when the shape is not taken (the caller then runs the two
+// also written to y (+ stats [2][Mo]) by the column-0 workgroups.  Returns HYB_NO_VARIANT when the shape is not taken (the caller then runs the two
 // launches): bf16 only, few-tile grids (every column tile re-forms its rows), R = D a multiple of 8, 256 .. 1008 (the 32 x (R + 16) bf16 row image must fit in 64 KB of LDS; R = 1024 does not).
 int hyb_gemm_nt_ln(int dtype, int groups, const void* x, const void* skip, const float* gamma, const float* beta, void* y, float* stats, float eps,
                    float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const void* const* B, void* const* C,
                    const float* const* bias, int Mo, int No, int R, int ldb, int ldc, int relu, hipStream_t st) {
-    static const int env = getenv("HYB_GEMM_LN") ? atoi(getenv("HYB_GEMM_LN")) : 1;          // (=0: A/B, LayerNorm as its own launch)
+    static const int env = hyb_env_int("HYB_GEMM_LN", 1);          // (=0: A/B, LayerNorm as its own launch)
     const dim3 grid(hyb_cdiv(No, 32), hyb_cdiv(Mo, 32), groups);
     const size_t img = (size_t)32 * (R + LNG_PAD) * sizeof(bf16), red = (size_t)8 * 32 * 33 * sizeof(float);
     const size_t lds = img > red ? img : red;
     if (!env || dtype != HYB_BF16 || groups < 1 || groups > 3 || (long long)grid.x * grid.y * grid.z > 256 || R < 256 || R > 1024 || R % 8 != 0 ||
         ldb % 8 != 0 || lds > 64 * 1024)
-        return -100;
+        return HYB_NO_VARIANT;
     GemmArgs a{};
     for (int i = 0; i < groups; ++i) a.g[i] = GemmGroup{nullptr, B[i], C[i], bias ? bias[i] : nullptr, nullptr, nullptr, nullptr};
     a.Mo = Mo; a.No = No; a.R = R; a.lda = R; a.ldb = ldb; a.ldc = ldc; a.relu = relu; a.accumulate = 0;
@@ -939,14 +930,14 @@ int hyb_gemm_nt_ln(int dtype, int groups, const void* x, const void* skip, const
     return 0;
 }
 
-// Internal: skinny product on the fp32 master weights (BMODE 1 / 2 of gemm_nt_splitk_kernel), bf16 activations; returns -100 when the
+// Internal: skinny product on the fp32 master weights (BMODE 1 / 2 of gemm_nt_splitk_kernel), bf16 activations; returns HYB_NO_VARIANT when the
 // shape is not a few-tile one (the caller then takes the LDS-staged kernel)
 int hyb_gemm_skinny_wf32(int dtype, const void* A, const float* Bf, void* C, const float* bias, int Mo, int No, int R, int lda, int ldb, int ldc, int relu,
                          int accumulate, int transposed_b, hipStream_t st) {
-    static const int env = getenv("HYB_GEMM_WF32") ? atoi(getenv("HYB_GEMM_WF32")) : 1;
+    static const int env = hyb_env_int("HYB_GEMM_WF32", 1);
     const dim3 grid(hyb_cdiv(No, 32), hyb_cdiv(Mo, 32), 1);
-    if (!env || (long long)grid.x * grid.y > 256 || R < 256 || R % 32 != 0 || lda % 8 != 0 || ((uintptr_t)A % 16) != 0) return -100;
-    if (!transposed_b && (ldb % 4 != 0 || ((uintptr_t)Bf % 16) != 0)) return -100;
+    if (!env || (long long)grid.x * grid.y > 256 || R < 256 || R % 32 != 0 || lda % 8 != 0 || ((uintptr_t)A % 16) != 0) return HYB_NO_VARIANT;
+    if (!transposed_b && (ldb % 4 != 0 || ((uintptr_t)Bf % 16) != 0)) return HYB_NO_VARIANT;
     GemmArgs a{};
     a.g[0] = GemmGroup{A, Bf, C, bias, nullptr, nullptr};
     a.Mo = Mo; a.No = No; a.R = R; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.relu = relu; a.accumulate = accumulate;
@@ -1027,7 +1018,7 @@ int hyb_linear_dw_multi(int dtype, int groups, const void* const* dy, const void
     }
     a.nriders = nriders;
     a.rider_begin[nriders] = blocks;
-    static const int tr_env = getenv("HYB_DW_TR") ? atoi(getenv("HYB_DW_TR")) : 1;      // (=0: A/B, the transposing-store form)
+    static const int tr_env = hyb_env_int("HYB_DW_TR", 1);      // (=0: A/B, the transposing-store form)
     bool aligned = true;                                   // 16-byte rows and bases for the straight vector staging
     for (int i = 0; i < groups; ++i)
         aligned = aligned && lddy[i] % 8 == 0 && ldx[i] % 8 == 0 && ((uintptr_t)dy[i] % 16 == 0) && ((uintptr_t)x[i] % 16 == 0) &&

@@ -3,62 +3,12 @@
 //   hyb_convstage_{fwd,bwd} : Conv3x3 -> BatchNorm2d -> ReLU -> MaxPool2d      (UNet.py:58-60, UNet.py:13)
 //   hyb_encoder_{fwd,bwd}   : TransformerEncoder.forward, all layers             (TransformerEncoder.pyc src L110-126)
 #include <math.h>
-#include <stdlib.h>
 #include "hyb_common.h"
-
-int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* B, void* const* C, const float* const* bias, int out_f32,
-                int Mo, int No, int R, int lda, int ldb, int ldc, int relu, int accumulate, hipStream_t st, const void* const* Amask = nullptr,
-                const void* const* Cmask = nullptr);
-int hyb_convert_weights(int dtype, int count, const float* const* W, void* const* Wc, void* const* Wt, const int* N, const int* K,
-                        const int* ldt, hipStream_t st);
-int hyb_ln_bwd_rows(int M);
-int hyb_gemm_nt_ln(int dtype, int groups, const void* x, const void* skip, const float* gamma, const float* beta, void* y, float* stats, float eps,
-                   float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const void* const* B, void* const* C,
-                   const float* const* bias, int Mo, int No, int R, int ldb, int ldc, int relu, hipStream_t st);
-int hyb_ln_residual_bwd_rows(int dtype, const void* dy, const void* x, const float* gamma, const float* stats, void* dx, void* dskip,
-                             int accumulate_dskip, float* part, int M, int D, float out_scale, float p_drop, unsigned long long seed,
-                             const unsigned long long* seed_inc, hipStream_t st);
-int hyb_ln_residual_fwd_inc(int dtype, const void* x, const void* skip, const float* gamma, const float* beta, void* y, float* stats,
-                            int M, int D, float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc,
-                            void* stream);
-int hyb_ln_rows_reduce(const float* part, int rows, int D, float* dgamma, float* dbeta, hipStream_t st);
-int hyb_linear_dw_multi(int dtype, int groups, const void* const* dy, const void* const* mask, const void* const* x, float* const* dW,
-                        float* const* db, const int* N, const int* K, const int* lddy, const int* ldx, int M, hipStream_t st,
-                        int nriders, const HybDwRider* riders);
-int hyb_linear_dw_grouped(int dtype, int groups, const void* const* dy, const void* const* mask, const void* x, float* const* dW,
-                          float* const* db, int M, int N, int K, int lddy, int ldx, hipStream_t st);
-int hyb_attention_fwd_packed(int dtype, const void* qkv, const float* mask, void* out, float* stats, int B, int S, int D, int H, float p_drop,
-                             unsigned long long seed, const unsigned long long* seed_inc, hipStream_t st);
-int hyb_attention_bwd_packed(int dtype, const void* qkv, const float* mask, const float* stats, const void* dout, void* dqkv, int B, int S, int D,
-                             int H, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, hipStream_t st, int relu_out);
-extern "C" size_t hyb_attention_long_workspace(int dtype, int B, int S, int D, int H);
-int hyb_linear_bwd_wt(int dtype, const void* x, int ldx, const float* W, const void* Wt, const void* y, const void* dy, void* dx, int accumulate_dx,
-                      float* dW, float* db, int M, int N, int K, int relu, void* ws, size_t ws_bytes, hipStream_t st);
-
-size_t hyb_stage1_fwd_workspace(int dtype, int Cop);
-size_t hyb_stage1_bwd_workspace(int dtype, int Cop);
-int hyb_stage1_fwd(int dtype, const float* x, const float* weight, const float* gamma, const float* beta, float* running_mean,
-                   float* running_var, long long* nbt, int training, float momentum, float eps, int N, int H, int W, int Ci, int Co, int Cop,
-                   void* pooled, float* scale_shift, float* mean_invstd, void* packed_out, void* workspace, float* running_out, int prepacked,
-                   void* route, hipStream_t st);
-long long hyb_stage1_route_elems(int dtype, int N, int H, int W, int Cop);
-int hyb_stage1_bwd(int dtype, const void* dpooled, const float* x, const float* weight, const float* gamma, const float* scale_shift,
-                   const float* mean_invstd, int training, int N, int H, int W, int Ci, int Co, int Cop, float* dweight, float* dgamma,
-                   float* dbeta, const void* packed_in, void* workspace, const void* route, hipStream_t st);
-int hyb_conv3x3_wgrad_fused(int dtype, const void* x, const void* y, const void* dp, const float* ss, const float* mi, const float* gamma,
-                            const float* sums, int training, long long count, void* dyraw_out, long long dyraw_blk, float* dw, int N, int H, int W,
-                            int Ci, int Cip, int Co, int Cop, void* workspace, size_t workspace_bytes, hipStream_t st, HybSlabInfo* defer);
-int hyb_wgrad_v2_supported(int dtype, int W, int Cip, int Cop);
-int hyb_conv_dgrad_planar_ok(int dtype, int W, int Cin_p, int Cout_p);
-int hyb_conv3x3_planar_in(const void* x, const void* wp, void* y, int N, int H, int W, int Cin_p, int Cout_p, hipStream_t st);
-int hyb_conv_pack_weight_dual(int dtype, const float* w, void* wp0, void* wp1, int Co, int Ci, int Cop, int Cip, hipStream_t st);
+#include "hyb_internal.h"
 
 namespace {
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-#define HYB_TRY(call) do { int rc_ = (call); if (rc_ != 0) return rc_; } while (0)
-#define HYB_HIP_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return (int)e_; } while (0)
+// more than 64 tokens per clip: attention goes through hyb_attention_long_* (attention.hip), which need scratch
+inline bool enc_long_seq(int S) { return S > 64; }
 
 struct EncLayout {       // byte offsets inside `saved` for one layer, plus per-layer stride
     size_t x_in, qkv, probs, attn, o, st1, x1, hmid, f, st2, long_ws, long_ws_bytes, layer_bytes;
@@ -70,7 +20,7 @@ inline EncLayout enc_layout(int dtype, int B, int S, int D, int Hid, int H) {
     const size_t M = (size_t)B * S;
     EncLayout L;
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
     L.x_in = take(M * D * es);
     L.qkv = take(M * 3 * D * es);                  // post-ReLU q | k | v, token-major [M][3D]
     L.probs = take((size_t)B * H * S * 2 * 4);       // softmax row statistics (max, sum) per (clip, head, query): P is recomputed in backward
@@ -81,9 +31,9 @@ inline EncLayout enc_layout(int dtype, int B, int S, int D, int Hid, int H) {
     L.hmid = take(M * Hid * es);
     L.f = take(M * D * es);
     L.st2 = take(2 * M * 4);
-    // more than 64 tokens per clip: attention() goes through hyb_attention_long_* (attention.hip), whose scratch (dense fp32 copies of the
-    // packed q|k|v, delta) lives here, per layer, in the caller's saved blob: the forward entry point has no workspace argument
-    L.long_ws_bytes = S > 64 ? hyb_attention_long_workspace(dtype, B, S, D, H) : 0;
+    // the long-sequence attention's scratch (dense fp32 copies of the packed q|k|v, delta) lives here, per layer, in the caller's saved blob:
+    // the forward entry point has no workspace argument
+    L.long_ws_bytes = enc_long_seq(S) ? hyb_attention_long_workspace(dtype, B, S, D, H) : 0;
     L.long_ws = take(L.long_ws_bytes);
     const size_t wsz[6] = {(size_t)D * D, (size_t)D * D, (size_t)D * D, (size_t)D * D, (size_t)Hid * D, (size_t)D * Hid};
     // (fp32 storage: the forward reads the master weights in place, no plain copies -- only the transposed ones below)
@@ -93,6 +43,84 @@ inline EncLayout enc_layout(int dtype, int B, int S, int D, int Hid, int H) {
     L.wt[2] = L.wt[0] + 2 * (size_t)D * es;
     for (int i = 3; i < 6; ++i) L.wt[i] = take(wsz[i] * es);
     L.layer_bytes = off;
+    return L;
+}
+
+// Workspace of the encoder backward.  Shared by all layers (consumed inside a layer's dX chain): g2 = d(x1), g4 = d(attn), gin = ping-pong
+// d(layer input).  Per layer PARITY (what the layer's weight-gradient launch reads): g1 = d(LN2 input), dqkv = d(q|k|v) packed [M][3D] (three
+// M x D slots), dh = d(hmid), g1b = d(LN1 input), lnpart = LayerNorm partial rows of the layer's two calls.  long_ws: long-sequence attention.
+struct EncBwdLayout { size_t g2, g4, gin[2], g1[2], dqkv[2], dh[2], g1b[2], lnpart[2], long_ws, total; };
+inline EncBwdLayout enc_bwd_layout(int dtype, int B, int S, int D, int Hid, int H) {
+    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    const size_t M = (size_t)B * S;
+    const size_t md = al256(M * D * es), big = al256(M * (size_t)(Hid > D ? Hid : D) * es);
+    EncBwdLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    L.g2 = take(md);
+    L.g4 = take(md);
+    for (int j = 0; j < 2; ++j) L.gin[j] = take(md);
+    for (int j = 0; j < 2; ++j) {
+        L.g1[j] = take(md);
+        L.dqkv[j] = take(3 * md);
+        L.dh[j] = take(big);
+        L.g1b[j] = take(big);
+        L.lnpart[j] = take((size_t)2 * 32 * 2 * D * sizeof(float));
+    }
+    L.long_ws = take(enc_long_seq(S) ? hyb_attention_long_workspace(dtype, B, S, D, H) : 0);
+    L.total = off;
+    return L;
+}
+
+// Workspace of a non-first conv stage, forward: packed forward weights | eval-mode statistics row | per-workgroup partial statistics rows
+struct ConvFwdLayout { size_t wp, stats, part, total; };
+inline ConvFwdLayout conv_fwd_layout(int dtype, int Cip, int Cop) {
+    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    ConvFwdLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    L.wp = take((size_t)hyb_conv_packed_elems(0, Cip, Cop) * es);
+    L.stats = take(2 * (size_t)Cop * 4);
+    L.part = take(hyb_conv_stats_workspace(Cop));
+    L.total = off;
+    return L;
+}
+
+// Workspace of one inference stage: scale/shift row, then (first) the first stage's scratch, (else) the packed forward weights and -- only
+// when hyb_conv3x3_pool_fused says the fused epilogue does not serve the shape -- the raw conv output (y_raw_bytes = 0 otherwise)
+struct ConvInferLayout { size_t ss, s1_ws, pack, y_raw, y_raw_bytes, total; };
+inline ConvInferLayout conv_infer_layout(int dtype, int first, int N, int H, int W, int Cip, int Cop) {
+    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    ConvInferLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    L.ss = take(2 * (size_t)Cop * 4);
+    if (first) {
+        L.s1_ws = take(hyb_stage1_fwd_workspace(dtype, Cop));
+    } else {
+        L.pack = take((size_t)hyb_conv_packed_elems(0, Cip, Cop) * es);
+        L.y_raw_bytes = hyb_conv3x3_pool_fused(dtype, W, Cip, Cop) ? 0 : (size_t)N * H * W * Cop * es;
+        L.y_raw = take(L.y_raw_bytes);
+    }
+    L.total = off;
+    return L;
+}
+
+// Workspace of a non-first conv stage, backward: BatchNorm sums + their partial rows | dense gradient of the raw conv output | dgrad-packed
+// weights | weight-gradient slabs (slab_bytes of them)
+struct ConvBwdLayout { size_t sums, sum_part, dyraw, wpd, slabs, slab_bytes, total; };
+inline ConvBwdLayout conv_bwd_layout(int dtype, int N, int H, int W, int Cip, int Cop) {
+    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    ConvBwdLayout L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al256(bytes); return o; };
+    L.sums = take(2 * (size_t)Cop * 4);
+    L.sum_part = take(hyb_bn_bwd_reduce_workspace(Cop));
+    L.dyraw = take((size_t)N * H * W * Cop * es);
+    L.wpd = take((size_t)Cip * 9 * Cop * es);
+    L.slab_bytes = hyb_conv3x3_wgrad_workspace(0, N, H, W, Cip, Cop);
+    L.slabs = take(L.slab_bytes);
+    L.total = off;
     return L;
 }
 
@@ -111,9 +139,7 @@ extern "C" long long hyb_convstage_packed_bwd_elems(int first, int Cip, int Cop)
 extern "C" long long hyb_convstage_route_elems(int dtype, int N, int H, int W, int Cop) { return hyb_stage1_route_elems(dtype, N, H, W, Cop); }
 
 extern "C" size_t hyb_convstage_fwd_workspace(int dtype, int first, int Cip, int Cop) {
-    if (first) return hyb_stage1_fwd_workspace(dtype, Cop);
-    const size_t es = dtype == HYB_F32 ? 4 : 2;
-    return align256((size_t)hyb_conv_packed_elems(first, Cip, Cop) * es) + align256(2 * (size_t)Cop * 4) + align256(hyb_conv_stats_workspace(Cop));
+    return first ? hyb_stage1_fwd_workspace(dtype, Cop) : conv_fwd_layout(dtype, Cip, Cop).total;
 }
 
 // prepacked_fwd != NULL: the caller (hyb_backbone_fwd) has packed this stage's forward AND backward weights already (first stage: both
@@ -131,11 +157,10 @@ int hyb_convstage_fwd_impl(int dtype, int first, const void* x, const float* wei
         return hyb_stage1_fwd(dtype, (const float*)x, weight, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, N, H, W, Ci,
                               Co, Cop, pooled, scale_shift, mean_invstd, packed_bwd, workspace, running_out, prepacked_fwd != nullptr, y_raw,
                               (hipStream_t)stream);
-    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    const ConvFwdLayout lay = conv_fwd_layout(dtype, Cip, Cop);
     char* ws = (char*)workspace;
-    void* wp = ws;
-    float* stats = (float*)(ws + align256((size_t)hyb_conv_packed_elems(first, Cip, Cop) * es));
-    float* part = (float*)((char*)stats + align256(2 * (size_t)Cop * 4));
+    void* wp = ws + lay.wp;
+    float *stats = (float*)(ws + lay.stats), *part = (float*)(ws + lay.part);
     if (prepacked_fwd) wp = const_cast<void*>(prepacked_fwd);
     else if (packed_bwd) HYB_TRY(hyb_conv_pack_weight_dual(dtype, weight, wp, packed_bwd, Co, Ci, Cop, Cip, (hipStream_t)stream));
     else HYB_TRY(hyb_conv_pack_weight(dtype, 0, weight, wp, Co, Ci, Cop, Cip, stream));
@@ -163,32 +188,17 @@ extern "C" int hyb_convstage_fwd(int dtype, int first, const void* x, const floa
 // ----------------------------------------------------------------------------------------------------------
 // conv stage, inference: running statistics read-only, nothing saved, no full-resolution conv output where the fused epilogue applies
 // ----------------------------------------------------------------------------------------------------------
-int hyb_conv_v2_pool(const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st);   // conv_v2.hip
-int hyb_conv_v2_supported(int W, int Cip, int Cop);
-int hyb_bn_infer_affine_many(int n, const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* var,
-                             float* const* scale_shift, const int* Co, const int* Cop, float eps, hipStream_t st);                           // bn_pool.hip
-int hyb_stage1_infer(int dtype, const float* x, const float* weight, const float* scale_shift, int N, int H, int W, int Ci, int Co, int Cop, void* pooled,
-                     void* prepacked, void* workspace, hipStream_t st);                                                                       // conv_first.hip
-
 // 1 when conv3x3 + BatchNorm affine + ReLU + MaxPool2d run as ONE kernel for this shape (bf16 storage, a shape the asynchronous kernels take);
 // 0: hyb_convstage_infer runs the conv -> bn_relu_pool pair with the raw output in its workspace.  HYB_POOL_FUSED=0 forces the pair (A/B).
 extern "C" int hyb_conv3x3_pool_fused(int dtype, int W, int Cip, int Cop) {
-    static const int fused_env = getenv("HYB_POOL_FUSED") ? atoi(getenv("HYB_POOL_FUSED")) : 1;
-    static const int v2_env = getenv("HYB_CONV_V2") ? atoi(getenv("HYB_CONV_V2")) : 1;
+    static const int fused_env = hyb_env_int("HYB_POOL_FUSED", 1);
     if (dtype != HYB_BF16 || W < 2 || Cip <= 0 || Cop <= 0 || Cip % 32 != 0 || Cop % 32 != 0) return 0;
-    return fused_env && v2_env && hyb_conv_v2_supported(W, Cip, Cop) ? 1 : 0;
+    return fused_env && hyb_sw_conv_v2() && hyb_conv_v2_supported(W, Cip, Cop) ? 1 : 0;
 }
 
-// workspace of one inference stage: scale/shift row, then (first) the first stage's scratch, (else) the packed forward weights and -- only when
-// the fused epilogue does not serve the shape -- the raw conv output
 extern "C" size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop) {
     if ((dtype != HYB_F32 && dtype != HYB_BF16) || N <= 0 || H < 2 || W < 2 || Cop <= 0 || Cop % 32 != 0 || (!first && (Cip <= 0 || Cip % 32 != 0))) return 0;
-    const size_t es = dtype == HYB_F32 ? 4 : 2;
-    size_t b = align256(2 * (size_t)Cop * 4);
-    if (first) return b + align256(hyb_stage1_fwd_workspace(dtype, Cop));
-    b += align256((size_t)hyb_conv_packed_elems(0, Cip, Cop) * es);
-    if (!hyb_conv3x3_pool_fused(dtype, W, Cip, Cop)) b += align256((size_t)N * H * W * Cop * es);
-    return b;
+    return conv_infer_layout(dtype, first, N, H, W, Cip, Cop).total;
 }
 
 // one stage with scale_shift and (optionally) the packed weights ready: the conv with the fused epilogue, else conv -> bn_relu_pool through y_raw
@@ -200,8 +210,7 @@ int hyb_convstage_infer_core(int dtype, int first, const void* x, const float* w
     if (!wp) { HYB_TRY(hyb_conv_pack_weight(dtype, 0, weight, pack_ws, Co, Ci, Cop, Cip, stream)); wp = pack_ws; }
     if (hyb_conv3x3_pool_fused(dtype, W, Cip, Cop)) {
         const int rc = hyb_conv_v2_pool(x, wp, pooled, scale_shift, N, H, W, Cip, Cop, (hipStream_t)stream);
-        if (rc != -100) return rc;
-        return HYB_E_ARG;          // (the query and the dispatcher apply the same shape test: not reached)
+        return rc != HYB_NO_VARIANT ? rc : HYB_E_ARG;          // (hyb_conv3x3_pool_fused asked the dispatcher's own shape test: not reached)
     }
     HYB_CHECK_ARG(y_raw);
     HYB_TRY(hyb_conv3x3_fwd(dtype, 0, x, wp, y_raw, nullptr, nullptr, N, H, W, Ci, Cip, Cop, stream));
@@ -216,32 +225,21 @@ extern "C" int hyb_convstage_infer(int dtype, int first, const void* x, const fl
     HYB_CHECK_ARG(H >= 2 && W >= 2 && Cop % 32 == 0 && Cop >= Co && Co > 0 && N > 0 && Ci > 0);
     HYB_CHECK_ARG(first ? Ci <= 4 : (Cip % 32 == 0 && Cip >= Ci));
     HYB_CHECK_ARG(Cop / 8 <= 256);
-    const size_t need = hyb_convstage_infer_workspace(dtype, first, N, H, W, Cip, Cop);
-    if (need == 0) return HYB_E_ARG;
-    if (workspace_bytes < need) return HYB_E_WORKSPACE;
-    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    if (hyb_convstage_infer_workspace(dtype, first, N, H, W, Cip, Cop) == 0) return HYB_E_ARG;
+    const ConvInferLayout lay = conv_infer_layout(dtype, first, N, H, W, Cip, Cop);
+    if (workspace_bytes < lay.total) return HYB_E_WORKSPACE;
     char* ws = (char*)workspace;
-    float* ss = (float*)ws;                      ws += align256(2 * (size_t)Cop * 4);
+    float* ss = (float*)(ws + lay.ss);
     HYB_TRY(hyb_bn_infer_affine_many(1, &gamma, &beta, &running_mean, &running_var, &ss, &Co, &Cop, eps, (hipStream_t)stream));
-    void* pack_ws = ws;
-    void* y_raw = first ? nullptr : (void*)(ws + align256((size_t)hyb_conv_packed_elems(0, Cip, Cop) * es));
-    return hyb_convstage_infer_core(dtype, first, x, weight, ss, N, H, W, Ci, Cip, Co, Cop, pooled, nullptr, pack_ws, y_raw, ws, stream);
+    void* y_raw = lay.y_raw_bytes ? (void*)(ws + lay.y_raw) : nullptr;
+    return hyb_convstage_infer_core(dtype, first, x, weight, ss, N, H, W, Ci, Cip, Co, Cop, pooled, nullptr, first ? nullptr : ws + lay.pack, y_raw,
+                                    first ? ws + lay.s1_ws : nullptr, stream);
 }
 
 extern "C" size_t hyb_convstage_bwd_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop) {
-    if (first) return hyb_stage1_bwd_workspace(dtype, Cop);
-    const size_t es = dtype == HYB_F32 ? 4 : 2;
-    size_t b = align256(2 * (size_t)Cop * 4) + align256(hyb_bn_bwd_reduce_workspace(Cop));   // sums + partial rows
-    b += align256((size_t)N * H * W * Cop * es);                                  // dense grad of the raw conv output
-    if (!first) b += align256((size_t)Cip * 9 * Cop * es);                        // dgrad-packed weights
-    b += align256(hyb_conv3x3_wgrad_workspace(first, N, H, W, Cip, Cop));         // wgrad slabs
-    return b;
+    return first ? hyb_stage1_bwd_workspace(dtype, Cop) : conv_bwd_layout(dtype, N, H, W, Cip, Cop).total;
 }
 
-int hyb_convstage_bwd_impl(int dtype, int first, const void* dpooled, const void* x, const void* y_raw, const void* pooled, const float* weight,
-                           const float* gamma, const float* scale_shift, const float* mean_invstd, int training, int N, int H, int W,
-                           int Ci, int Cip, int Co, int Cop, void* dx, float* dweight, float* dgamma, float* dbeta,
-                           const void* packed_bwd, void* workspace, size_t workspace_bytes, void* stream, void* slab_ws, HybSlabInfo* defer);
 extern "C" int hyb_convstage_bwd(int dtype, int first, const void* dpooled, const void* x, const void* y_raw, const void* pooled, const float* weight,
                                  const float* gamma, const float* scale_shift, const float* mean_invstd, int training, int N, int H, int W,
                                  int Ci, int Cip, int Co, int Cop, void* dx, float* dweight, float* dgamma, float* dbeta,
@@ -264,33 +262,28 @@ int hyb_convstage_bwd_impl(int dtype, int first, const void* dpooled, const void
     if (first)
         return hyb_stage1_bwd(dtype, dpooled, (const float*)x, weight, gamma, scale_shift, mean_invstd, training, N, H, W, Ci, Co, Cop, dweight,
                               dgamma, dbeta, packed_bwd, workspace, y_raw, (hipStream_t)stream);
-    const size_t es = dtype == HYB_F32 ? 4 : 2;
+    const ConvBwdLayout lay = conv_bwd_layout(dtype, N, H, W, Cip, Cop);
     char* ws = (char*)workspace;
-    float* sums = (float*)ws;                    ws += align256(2 * (size_t)Cop * 4);
-    float* sum_part = (float*)ws;                ws += align256(hyb_bn_bwd_reduce_workspace(Cop));
-    void* dyraw = ws;                            ws += align256((size_t)N * H * W * Cop * es);
-    void* wpd = nullptr;
-    if (!first) { wpd = ws;                      ws += align256((size_t)Cip * 9 * Cop * es); }
-    void* slabs = (slab_ws && defer) ? slab_ws : (void*)ws;
-    const size_t slab_bytes = hyb_conv3x3_wgrad_workspace(first, N, H, W, Cip, Cop);
+    float *sums = (float*)(ws + lay.sums), *sum_part = (float*)(ws + lay.sum_part);
+    void *dyraw = ws + lay.dyraw, *wpd = ws + lay.wpd;
+    void* slabs = (slab_ws && defer) ? slab_ws : (void*)(ws + lay.slabs);
+    const size_t slab_bytes = lay.slab_bytes;
     const long long count = (long long)N * H * W;
     HYB_TRY(hyb_bn_relu_pool_bwd_reduce(dtype, dpooled, y_raw, pooled, scale_shift, mean_invstd, sums, sum_part, dgamma, dbeta, N, H, W, Co, Cop, stream));
     // dense BN/ReLU/pool backward is computed inside the wgrad tile staging; the tile is also written once (dyraw) for dgrad
     // Layout of the dense gradient between the two kernels.  NHWC makes the dgrad conv read each 128-byte line of a >= 64-channel
     // gradient once per 32-channel block (stage 2: 555 MB fetched for 308 MB, by PMC); when both kernels are the second-generation
     // ones the tensor is written block-planar, [Cop/32][N][H][W][32], and a block's halo uses whole lines.
-    static const int planar_env = getenv("HYB_DYRAW_PLANAR") ? atoi(getenv("HYB_DYRAW_PLANAR")) : 1;
-    const bool planar = planar_env && !first && Cop >= 64 && hyb_wgrad_v2_supported(dtype, W, Cip, Cop) && hyb_conv_dgrad_planar_ok(dtype, W, Cop, Cip);
+    static const int planar_env = hyb_env_int("HYB_DYRAW_PLANAR", 1);
+    const bool planar = planar_env && Cop >= 64 && hyb_wgrad_v2_supported(dtype, W, Cip, Cop) && hyb_conv_dgrad_planar_ok(dtype, W, Cop, Cip);
     const long long dyraw_blk = planar ? (long long)N * H * W * 32 : 0;
     HYB_TRY(hyb_conv3x3_wgrad_fused(dtype, x, y_raw, dpooled, scale_shift, mean_invstd, gamma, sums, training, count, dyraw, dyraw_blk, dweight, N, H,
                                     W, Ci, Cip, Co, Cop, slabs, slab_bytes, (hipStream_t)stream, (slab_ws && defer) ? defer : nullptr));
-    if (!first) {
-        // dgrad = conv3x3 of the dense output gradient with the transposed, tap-flipped weights
-        const void* wd = packed_bwd;
-        if (!wd) { HYB_TRY(hyb_conv_pack_weight(dtype, 1, weight, wpd, Co, Ci, Cop, Cip, stream)); wd = wpd; }
-        if (planar) HYB_TRY(hyb_conv3x3_planar_in(dyraw, wd, dx, N, H, W, Cop, Cip, (hipStream_t)stream));
-        else HYB_TRY(hyb_conv3x3_fwd(dtype, 0, dyraw, wd, dx, nullptr, nullptr, N, H, W, Co, Cop, Cip, stream));
-    }
+    // dgrad = conv3x3 of the dense output gradient with the transposed, tap-flipped weights
+    const void* wd = packed_bwd;
+    if (!wd) { HYB_TRY(hyb_conv_pack_weight(dtype, 1, weight, wpd, Co, Ci, Cop, Cip, stream)); wd = wpd; }
+    if (planar) HYB_TRY(hyb_conv3x3_planar_in(dyraw, wd, dx, N, H, W, Cop, Cip, (hipStream_t)stream));
+    else HYB_TRY(hyb_conv3x3_fwd(dtype, 0, dyraw, wd, dx, nullptr, nullptr, N, H, W, Co, Cop, Cip, stream));
     return 0;
 }
 
@@ -306,17 +299,9 @@ extern "C" size_t hyb_encoder_saved_bytes(int dtype, int B, int S, int D, int Hi
 }
 extern "C" size_t hyb_encoder_workspace_bytes(int dtype, int B, int S, int D, int Hid, int L, int H) {
     if (B <= 0 || S <= 0 || D <= 0 || Hid <= 0 || L <= 0 || H <= 0) return 0;
-    const size_t es = dtype == HYB_F32 ? 4 : 2;
-    const size_t M = (size_t)B * S;
-    const size_t big = (size_t)(Hid > D ? Hid : D);
-    // (the buffers a layer's weight gradients read -- g1, dqkv, dh, g1b, LayerNorm partial rows -- exist twice, one set per layer parity)
-    return 12 * align256(M * D * es) + 4 * align256(M * big * es) + 2 * align256((size_t)2 * 32 * 2 * D * sizeof(float)) +
-           (S > 64 ? align256(hyb_attention_long_workspace(dtype, B, S, D, H)) : 0);      // scratch of the long-sequence attention backward
+    return enc_bwd_layout(dtype, B, S, D, Hid, H).total;
 }
 
-int hyb_encoder_fwd_impl(int dtype, const void* x, const float* mask, const float* const* params, void* out, void* saved, int B, int S,
-                         int D, int Hid, int L, int H, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc, void* stream,
-                         HybEncTail* tail);
 extern "C" int hyb_encoder_fwd(int dtype, const void* x, const float* mask, const float* const* params, void* out, void* saved, int B, int S,
                                int D, int Hid, int L, int H, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc, void* stream) {
     return hyb_encoder_fwd_impl(dtype, x, mask, params, out, saved, B, S, D, Hid, L, H, attn_p, layer_p, seed, seed_inc, stream, nullptr);
@@ -380,7 +365,7 @@ int hyb_encoder_fwd_impl(int dtype, const void* x, const float* mask, const floa
             const int rc = hyb_gemm_nt_ln(dtype, 3, pb + lay.f, pb + lay.x1, PP[12], PP[13], x_in, (float*)(pb + lay.st2), 1e-5f, (float)sqrt(0.5), layer_p,
                                           drop_seed(seed, i - 1), seed_inc, Wq3, ys, bs, M, D, D, D, 3 * D, 1, st);
             if (rc == 0) projected = true;
-            else if (rc != -100) return rc;
+            else if (rc != HYB_NO_VARIANT) return rc;
             else HYB_TRY(hyb_ln_residual_fwd_inc(dtype, pb + lay.f, pb + lay.x1, PP[12], PP[13], x_in, (float*)(pb + lay.st2), M, D, 1e-5f,
                                                  (float)sqrt(0.5), layer_p, drop_seed(seed, i - 1), seed_inc, stream));
             ln2_pending = false;
@@ -389,7 +374,7 @@ int hyb_encoder_fwd_impl(int dtype, const void* x, const float* mask, const floa
             const void* xs[3] = {x_in, x_in, x_in};
             HYB_TRY(hyb_gemm_nt(dtype, 3, xs, Wq3, ys, bs, 0, M, D, D, D, D, 3 * D, 1, 0, st));
         }
-        if (S > 64)
+        if (enc_long_seq(S))
             HYB_TRY(hyb_attention_long_fwd(dtype, base + lay.qkv, base + lay.qkv + (size_t)D * es, base + lay.qkv + 2 * (size_t)D * es, 3 * D, mask,
                                            base + lay.attn, (float*)(base + lay.probs), B, S, D, H, attn_p, attn_seed(seed, i), seed_inc,
                                            base + lay.long_ws, lay.long_ws_bytes, st));
@@ -403,7 +388,7 @@ int hyb_encoder_fwd_impl(int dtype, const void* x, const float* mask, const floa
             const void* B_[1] = {WC(4)}; void* C_[1] = {base + lay.hmid}; const float* b_[1] = {P[9]};
             const int rc = hyb_gemm_nt_ln(dtype, 1, base + lay.o, x_in, P[12], P[13], base + lay.x1, (float*)(base + lay.st1), 1e-5f, 1.0f, 0.f, 0ull,
                                           nullptr, B_, C_, b_, M, Hid, D, D, Hid, 1, st);
-            if (rc == -100) {
+            if (rc == HYB_NO_VARIANT) {
                 HYB_TRY(hyb_ln_residual_fwd_inc(dtype, base + lay.o, x_in, P[12], P[13], base + lay.x1, (float*)(base + lay.st1), M, D, 1e-5f, 1.0f, 0.f,
                                                 0ull, nullptr, stream));
                 const void* A_[1] = {base + lay.x1};
@@ -423,28 +408,20 @@ int hyb_encoder_fwd_impl(int dtype, const void* x, const float* mask, const floa
     return 0;
 }
 
-int hyb_encoder_bwd_impl(int dtype, const void* dout, const float* mask, const float* const* params, float* const* grads,
-                         const void* saved, void* dx, int B, int S, int D, int Hid, int L, int H, float attn_p, float layer_p,
-                         unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes, void* stream,
-                         const HybDwExtra* extra, int tail_done, const HybDwRider* extra_rider);
 // Where the backward of the LAST layer's second LayerNorm reads and writes (hyb_temporal_bwd runs it inside its fused tail launch and then
 // calls hyb_encoder_bwd_impl with tail_done = 1): the same buffers hyb_ln_residual_bwd_rows is given below.
 HybEncBwdTail hyb_encoder_bwd_tail(int dtype, const float* const* params, const void* saved, void* workspace, int B, int S, int D, int Hid, int L, int H,
                                    float layer_p, unsigned long long seed) {
-    const size_t es = dtype == HYB_F32 ? 4 : 2;
     const int M = B * S, i = L - 1;
     const EncLayout lay = enc_layout(dtype, B, S, D, Hid, H);
+    const EncBwdLayout wl = enc_bwd_layout(dtype, B, S, D, Hid, H);
     const char* base = (const char*)saved + (size_t)i * lay.layer_bytes;
     char* ws = (char*)workspace;
-    const size_t md = align256((size_t)M * D * es);
-    const size_t big = align256((size_t)M * (Hid > D ? Hid : D) * es);
-    const size_t lnb = align256((size_t)2 * 32 * 2 * D * sizeof(float));
-    char* q = ws + 4 * md + (size_t)(i & 1) * (md + 3 * md + 2 * big + lnb);        // parity set of the last layer (see hyb_encoder_bwd_impl)
     HybEncBwdTail t;
     t.f = base + lay.f; t.stats = (const float*)(base + lay.st2); t.gamma = params[(size_t)i * 14 + 12];
-    t.dx = q;                                     // set.g1
-    t.dskip = ws;                                 // g2
-    t.ln_part = (float*)(q + md + 3 * md + 2 * big);
+    t.dx = ws + wl.g1[i & 1];                     // the last layer's parity set (see hyb_encoder_bwd_impl)
+    t.dskip = ws + wl.g2;
+    t.ln_part = (float*)(ws + wl.lnpart[i & 1]);
     t.ln_rows = hyb_ln_bwd_rows(M);
     t.out_scale = (float)sqrt(0.5); t.p_drop = layer_p; t.seed = drop_seed(seed, i);
     return t;
@@ -466,34 +443,20 @@ int hyb_encoder_bwd_impl(int dtype, const void* dout, const float* mask, const f
     // extra_rider: one more fixed-order row sum (the head's weight / bias gradient terms) for the final multi-matrix launch
     HYB_CHECK_ARG((dout || tail_done) && params && grads && saved && dx && workspace && B > 0 && S > 0 && D > 0 && Hid > 0 && L > 0 && H > 0 && D % H == 0);
     HYB_CHECK_ARG(dtype == HYB_F32 || dtype == HYB_BF16);
-    if (workspace_bytes < hyb_encoder_workspace_bytes(dtype, B, S, D, Hid, L, H)) return HYB_E_WORKSPACE;
+    const EncBwdLayout wl = enc_bwd_layout(dtype, B, S, D, Hid, H);
+    if (workspace_bytes < wl.total) return HYB_E_WORKSPACE;
     const size_t es = dtype == HYB_F32 ? 4 : 2;
     const int M = B * S;
     const EncLayout lay = enc_layout(dtype, B, S, D, Hid, H);
     hipStream_t st = (hipStream_t)stream;
     const char* sv = (const char*)saved;
     char* ws = (char*)workspace;
-    const size_t md = align256((size_t)M * D * es);
-    const size_t big = align256((size_t)M * (Hid > D ? Hid : D) * es);
-    const size_t lnb = align256((size_t)2 * 32 * 2 * D * sizeof(float));
     const int lnrows = hyb_ln_bwd_rows(M);
-    // shared by all layers (consumed inside a layer's dX chain)
-    void* g2 = ws;            // d(x1)
-    void* g4 = ws + md;       // d(attn)
-    void* gin[2] = {ws + 2 * md, ws + 3 * md};
-    // per layer parity: what the layer's weight-gradient launch reads
+    void *g2 = ws + wl.g2, *g4 = ws + wl.g4;
+    void* gin[2] = {ws + wl.gin[0], ws + wl.gin[1]};
     struct Set { void* g1; void* dqkv; void* dh; void* g1b; float* lnpart; } set[2];
-    {
-        char* q = ws + 4 * md;
-        for (int j = 0; j < 2; ++j) {
-            set[j].g1 = q; q += md;                 // d(LN2 input)
-            set[j].dqkv = q; q += 3 * md;           // d(q|k|v) packed [M][3D]
-            set[j].dh = q; q += big;                // d(hmid)
-            set[j].g1b = q; q += big;               // d(LN1 input)
-            set[j].lnpart = (float*)q; q += lnb;    // LayerNorm affine-gradient partial rows of the layer's two calls
-        }
-    }
-    void* const long_ws = ws + 12 * md + 4 * big + 2 * lnb;       // S > 64 only (hyb_encoder_workspace_bytes)
+    for (int j = 0; j < 2; ++j) set[j] = Set{ws + wl.g1[j], ws + wl.dqkv[j], ws + wl.dh[j], ws + wl.g1b[j], (float*)(ws + wl.lnpart[j])};
+    void* const long_ws = ws + wl.long_ws;
     // (The layer's weight-gradient launch is off the dX chain; issuing it as a parallel branch of the replayed graph was measured in
     // round 2 and lost 4.7 % of the step -- every fork / join edge costs more than the 5 us kernel it hides -- so it stays in line.)
 
@@ -526,7 +489,7 @@ int hyb_encoder_bwd_impl(int dtype, const void* dout, const float* mask, const f
         { const void* A_[1] = {b.g1b}; const void* B_[1] = {base + lay.wt[3]}; void* C_[1] = {g4};
           HYB_TRY(hyb_gemm_nt(dtype, 1, A_, B_, C_, nullptr, 0, M, D, D, D, D, D, 0, 0, st)); }
         // attention core: d(q|k|v) packed [M][3D]
-        if (S > 64)
+        if (enc_long_seq(S))
             HYB_TRY(hyb_attention_long_bwd(dtype, base + lay.qkv, base + lay.qkv + (size_t)D * es, base + lay.qkv + 2 * (size_t)D * es, 3 * D, mask,
                                            base + lay.attn, (const float*)(base + lay.probs), g4, b.dqkv, (char*)b.dqkv + (size_t)D * es,
                                            (char*)b.dqkv + 2 * (size_t)D * es, 3 * D, B, S, D, H, attn_p, attn_seed(seed, i), seed_inc,
@@ -537,13 +500,13 @@ int hyb_encoder_bwd_impl(int dtype, const void* dout, const float* mask, const f
                                          attn_seed(seed, i), seed_inc, st, 1));
         // Q, K, V projections (+ReLU) share the layer input: one K-concatenated dX GEMM
         { const void* A_[1] = {b.dqkv}; const void* B_[1] = {base + lay.wt[0]}; void* C_[1] = {gx}; const void* M_[1] = {base + lay.qkv};
-          HYB_TRY(hyb_gemm_nt(dtype, 1, A_, B_, C_, nullptr, 0, M, D, 3 * D, 3 * D, 3 * D, D, 0, 1, st, S > 64 ? M_ : nullptr)); }
+          HYB_TRY(hyb_gemm_nt(dtype, 1, A_, B_, C_, nullptr, 0, M, D, 3 * D, 3 * D, 3 * D, D, 0, 1, st, enc_long_seq(S) ? M_ : nullptr)); }
         // the six weight (+ bias) gradients of the layer in ONE launch (768 tiles at config 2 instead of four 64-256-tile launches); the
         // layer's one LayerNorm is applied twice (quirk Q3): both calls' partial rows -> its weight/bias gradients ride in the same launch
         {
             const char* dq_ = (const char*)b.dqkv; const char* qk_ = base + lay.qkv;
             const void* dy_[6] = {b.g1, b.dh, b.g1b, dq_, dq_ + (size_t)D * es, dq_ + 2 * (size_t)D * es};
-            const bool qm = S > 64;                        // (the long-sequence attention backward leaves d(q|k|v) unmasked)
+            const bool qm = enc_long_seq(S);                        // (the long-sequence attention backward leaves d(q|k|v) unmasked)
             const void* mk_[6] = {nullptr, nullptr, nullptr, qm ? qk_ : nullptr, qm ? qk_ + (size_t)D * es : nullptr, qm ? qk_ + 2 * (size_t)D * es : nullptr};
             const void* x_[6] = {base + lay.hmid, base + lay.x1, base + lay.attn, base + lay.x_in, base + lay.x_in, base + lay.x_in};
             float* dW_[6] = {G[10], G[8], G[6], G[0], G[2], G[4]};

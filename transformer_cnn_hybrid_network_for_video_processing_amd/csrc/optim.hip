@@ -6,6 +6,7 @@
 // The tensor table travels in the kernel arguments (up to 80 tensors per launch), a workgroup owns 4096 consecutive elements
 // of one tensor and finds it by scanning the table's chunk offsets; HBM-bound: 7 x 4 bytes per parameter.
 #include "hyb_common.h"
+#include "hyb_internal.h"
 
 namespace {
 

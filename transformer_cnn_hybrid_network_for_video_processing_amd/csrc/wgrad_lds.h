@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_lds_kernel(const float* __restri
 // 3 = 128 x 64 (2 x 2, NKT 2), 4 = 128 x 96 (2 x 2, NKT 3).
 struct WlPlan { int cfg, BN, BK, ntiles, ktiles, rows, S; };
 inline bool wl_plan(WlPlan& pl, long long P, int Nn, int K, int lddy, int ldx, const float* dy, const float* x, const ConvGeo* geo) {
-    static const int env = getenv("HYB_WGRAD_LDS") ? atoi(getenv("HYB_WGRAD_LDS")) : 1;
+    static const int env = hyb_env_int("HYB_WGRAD_LDS", 1);
     if (!env || Nn < 64 || K < 64 || P < 4096 || lddy % 4 != 0 || Nn % 4 != 0 || K % 4 != 0) return false;
     if (geo ? geo->Ci % 4 != 0 : ldx % 4 != 0) return false;
     if (dy && x && ((((uintptr_t)dy) | ((uintptr_t)x)) & 15)) return false;
