@@ -194,6 +194,10 @@ int hyb_convstage_bwd(int dtype, int first, const void* dpooled, const void* x, 
  * mode with the raw output in the workspace: the same results as hyb_convstage_fwd(training = 0), bit for bit.
  * x / Ci / Cip / first as in hyb_convstage_fwd.  hyb_conv3x3_pool_fused is a pure host query (W = the stage's input width). */
 int hyb_conv3x3_pool_fused(int dtype, int W, int Cip, int Cop);
+/* hyb_conv3x3_pool_ext: pure host query (new symbol, hyb_abi_version() stays 9).  1 when hyb_convstage_fwd(training = 1) runs a non-first stage
+ * of this shape with the 2x2 window extremes stored by the conv's epilogue (no full-resolution re-read for BatchNorm + ReLU + MaxPool);
+ * the outputs are the same bit for bit either way. */
+int hyb_conv3x3_pool_ext(int dtype, int W, int Cip, int Cop);
 size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop);
 int hyb_convstage_infer(int dtype, int first, const void* x, const float* weight, const float* gamma, const float* beta,
                         const float* running_mean, const float* running_var, float eps,

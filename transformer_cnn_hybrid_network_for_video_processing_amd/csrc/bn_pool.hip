@@ -134,6 +134,32 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const T* __restri
     }
 }
 
+// The training-time conv epilogue (conv_v2.hip, EXT) has left in `pooled` the raw extreme of every 2 x 2 window -- its maximum of y where
+// gamma >= 0, its minimum where gamma < 0 -- which is where bn_relu_pool_fwd_kernel's maximum of y * scale + shift is attained (the affine
+// is monotone, its direction the sign of gamma).  In place: pooled = relu(ext * scale + shift), the expression of the kernel above on the
+// one value that matters, so the result is the same bit for bit at a quarter of the reads.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_relu_apply_pooled_kernel(T* __restrict__ pooled, const float* __restrict__ ss, int N, int Ho, int Wo, int Cop) {
+    const int OCT = Cop >> 3;
+    const int nthr = row_threads(OCT);
+    if ((int)threadIdx.x >= nthr) return;
+    const int oc = threadIdx.x % OCT;
+    float sc[8], sh[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { sc[j] = ss[oc * 8 + j]; sh[j] = ss[Cop + oc * 8 + j]; }
+    const int rows = N * Ho, rowlen = Wo * OCT;
+    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+        T* prow = pooled + (long long)row * Wo * Cop;
+        for (int idx = threadIdx.x; idx < rowlen; idx += nthr) {
+            Vec8<T> a, o;
+            a.load(prow + (long long)idx * 8);                 // (wo, oc) = (idx / OCT, idx % OCT): idx * 8 elements into the row
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o.set(j, fmaxf(a.get(j) * sc[j] + sh[j], 0.f));
+            o.store(prow + (long long)idx * 8);
+        }
+    }
+}
+
 // pass 1 of the backward: per-channel sum(dy) and sum(dy * xhat), dy routed through argmax and relu.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_relu_pool_bwd_reduce_kernel(const T* __restrict__ dp, const T* __restrict__ y,
@@ -552,6 +578,17 @@ extern "C" int hyb_bn_relu_pool_fwd(int dtype, const void* y, const float* ss, v
     HYB_DISPATCH_T(dtype,
         hipLaunchKernelGGL(bn_relu_pool_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)y, ss, (float*)pooled, N, H, W, Cop),
         hipLaunchKernelGGL(bn_relu_pool_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)y, ss, (bf16*)pooled, N, H, W, Cop));
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// Internal (hyb_convstage_fwd_impl): pooled [N][Ho][Wo][Cop] holds the conv epilogue's raw window extremes; in place -> relu(ext * scale + shift)
+int hyb_bn_relu_apply_pooled(int dtype, void* pooled, const float* ss, int N, int Ho, int Wo, int Cop, hipStream_t st) {
+    HYB_CHECK_ARG(pooled && ss && N > 0 && Ho > 0 && Wo > 0 && Cop % 32 == 0 && Cop > 0 && Cop / 8 <= 256);
+    const int grid = row_grid(N * Ho);
+    HYB_DISPATCH_T(dtype,
+        hipLaunchKernelGGL(bn_relu_apply_pooled_kernel<float>, dim3(grid), dim3(256), 0, st, (float*)pooled, ss, N, Ho, Wo, Cop),
+        hipLaunchKernelGGL(bn_relu_apply_pooled_kernel<bf16>, dim3(grid), dim3(256), 0, st, (bf16*)pooled, ss, N, Ho, Wo, Cop));
     HYB_LAUNCH_CHECK();
     return 0;
 }

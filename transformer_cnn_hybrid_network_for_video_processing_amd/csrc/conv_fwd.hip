@@ -575,6 +575,20 @@ int hyb_conv3x3_planar_in(const void* x, const void* wp, void* y, int N, int H, 
     return rc;
 }
 
+// Internal (hyb_convstage_fwd_impl, training, shapes hyb_conv3x3_pool_ext takes): hyb_conv3x3_fwd(bf16, stats_partials = part) whose epilogue
+// also leaves the raw extreme of every 2 x 2 window in pooled (conv_v2.hip, EXT).  The measurement hook brackets the launch as in conv_fwd_t.
+int hyb_conv3x3_fwd_ext(const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
+                        hipStream_t st) {
+    HYB_CHECK_ARG(x && wp && y && part && pooled && gamma && N > 0 && H >= 2 && W >= 2 && Cop > 0 && Cop % 32 == 0 && Cip % 32 == 0);
+    HYB_CHECK_ARG((long long)N * H * W * (Cop > Cip ? Cop : Cip) < (1ll << 40));
+    const int rows = hyb_conv_stats_rows(0, N, H, W, Cop);
+    HybProfileHook* hook = hyb_find_hook(1, Cip, Cop);
+    if (hook) hipEventRecord(hook->ev0, st);
+    const int rc = hyb_conv_v2_ext(x, wp, y, part, pooled, gamma, Co, N, H, W, Cip, Cop, rows, st);
+    if (hook) hipEventRecord(hook->ev1, st);
+    return rc == HYB_NO_VARIANT ? HYB_E_ARG : rc;          // (the caller asked hyb_conv3x3_pool_ext first: not reached)
+}
+
 extern "C" long long hyb_conv_packed_elems(int first, int Cip, int Cop) {
     return first ? (long long)Cop * 32 : (long long)Cop * 9 * Cip;
 }

@@ -19,7 +19,9 @@
 //   * the BatchNorm batch statistics (UNet.py:59) are folded into the epilogue from the fp32 accumulators, reduced in a fixed
 //     order (bit-reproducible);
 //   * POOL instantiations (inference, hyb_conv_v2_pool) never store the raw convolution: the epilogue applies the BatchNorm affine to the
-//     fp32 accumulators, takes the 2 x 2 maximum across lanes, applies the ReLU and stores the pooled map (pool_affine_max below).
+//     fp32 accumulators, takes the 2 x 2 maximum across lanes, applies the ReLU and stores the pooled map (pool_affine_max below);
+//   * EXT instantiations (training, hyb_conv_v2_ext) do everything the STATS ones do and also store, at a quarter of the resolution, the
+//     raw extreme of every 2 x 2 window (pool_raw_extreme below): BatchNorm + ReLU + MaxPool2d then never re-read the raw output.
 #include <type_traits>
 #include "hyb_common.h"
 #include "hyb_internal.h"
@@ -60,6 +62,46 @@ __device__ __forceinline__ bool pool_store_lane(int p) {
     return partner == (p ^ 4) && !(p & 1);
 }
 
+// ---- EXT epilogue: the raw extreme of every 2 x 2 window, beside the raw output and its statistics (training) ---------------------------------
+// Per channel v -> v * scale + shift is monotone and its direction is the sign of scale = gamma * invstd, i.e. of gamma (invstd > 0), which is
+// known BEFORE the batch statistics are: max over the window of (y * scale + shift) = ext * scale + shift with ext the window's maximum of y
+// where gamma >= 0 and its minimum where gamma < 0.  Rounding to bf16 is monotone too, so the extreme of the fp32 accumulators, rounded once,
+// is the extreme of the bf16 values y_raw holds.  The minimum is the maximum between two flips of the sign bit (exact): `flip` is 0x80000000
+// for a lane's channels with gamma < 0, else 0.  Lane mapping, exchanges and storing lanes are pool_affine_max's / pool_store_lane's.
+// bn_relu_apply_pooled_kernel (bn_pool.hip) turns the stored extremes into relu(ext * scale + shift) in place once the statistics exist.
+// (fmaxf would quiet both operands first -- the compiler cannot see that accumulators hold no signalling NaN -- three v_max_f32 per exchange;
+// the instruction itself is all that is needed.)
+__device__ __forceinline__ float raw_max(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float pool_raw_extreme(float acc, unsigned flip) {
+    float a = __uint_as_float(__float_as_uint(acc) ^ flip);
+    a = raw_max(a, hyb_dpp_mov<0xB1>(a));          // quad_perm [1,0,3,2]: lane p ^ 1
+    a = raw_max(a, hyb_dpp_mov<0x124>(a));         // row_ror:4: lane p ^ 4 on the storing side
+    return __uint_as_float(__float_as_uint(a) ^ flip);
+}
+// bit t * 4 + r of the result: the lane's accumulator value (t, r) belongs to a channel with gamma < 0 (channels >= Co: padding, never read)
+template <int NT> __device__ __forceinline__ unsigned ext_negative_mask(const float* __restrict__ gamma, int Co, int co_base, int q) {
+    unsigned m = 0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int c = co_base + (t >> 1) * 32 + q * 8 + (t & 1) * 4 + r;
+            if (c < Co && gamma[c] < 0.f) m |= 1u << (t * 4 + r);
+        }
+    return m;
+}
+__device__ __forceinline__ unsigned ext_flip(unsigned mask, int bit) { return (mask << (31 - bit)) & 0x80000000u; }
+// Which variants have an EXT instantiation.  The eight-wave ones with 64 channels per wave (NT = 4) do not: their STATS siblings already use
+// all 256 registers and with the extremes each of them spills (88 - 124 bytes of scratch per lane).  A variant that spills is not built; its
+// shapes keep the conv -> bn_relu_pool pair (hyb_conv_v2_ext_supported below answers for a shape).
+constexpr bool v2_ext_built(int NT, int NW) { return NT == 2 || NW == 4; }
+// what the EXT instantiations get beside the STATS arguments: the pooled map [N][H/2][W/2][Cop] to fill with extremes, and gamma[Co]
+struct V2Ext { bf16* pooled; const float* gamma; int Co; };
+
 template <int NT, int CB, int PGR, int PGC, int R>
 struct V2Geom {
     static constexpr int PG = PGR * PGC, MT = 7;
@@ -88,14 +130,17 @@ struct V2Geom {
         for (int j = s - R + 4; j <= s; ++j) n += WI + hi(j);
         return n;
     }
+    // the largest wait_n of the steps that step over a full tile's stores (S < R - 3)
+    static constexpr int max_wait_after_store() { int n = 0; for (int s = 0; s < R - 3; ++s) n = wait_n(s) > n ? wait_n(s) : n; return n; }
 };
 
 // POOL: y is the pooled map [N][H/2][W/2][Cop] and `stats` carries the BatchNorm scale/shift rows [2][Cop] (read only)
-template <int NT, int CB, int PGR, int PGC, int R, bool STATS, bool POOL = false>
+// EXT (with STATS): also ext.pooled = the raw 2 x 2 extremes (pool_raw_extreme)
+template <int NT, int CB, int PGR, int PGC, int R, bool STATS, bool POOL = false, bool EXT = false>
 __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) void conv3x3_v2_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wp,
                                                             bf16* __restrict__ y, float* __restrict__ stats,
                                                             int N, int H, int W, int Cip, int Cop,
-                                                            int tilesX, int tilesY, int numTiles, int stat_rows, int xpix, long long xblk) {
+                                                            int tilesX, int tilesY, int numTiles, int stat_rows, int xpix, long long xblk, V2Ext ext) {
     // input addressing: element stride between pixels (Cip for NHWC) and between 32-channel blocks (32 for NHWC); a "block-planar"
     // input [Cip/32][N][H][W][32] has xpix = 32, xblk = N*H*W*32: a block's halo then uses whole 128-byte lines (see hyb_convstage_bwd)
     using G = V2Geom<NT, CB, PGR, PGC, R>;
@@ -107,6 +152,7 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
     float* const wgstat = reinterpret_cast<float*>(wring + R * WSLOT);          // [NW waves][2][NT*16]; POOL: scale/shift [2][CBW]
     static_assert(!(STATS && POOL), "the pooled epilogue keeps no batch statistics");
     static_assert(!POOL || NT >= 2, "the pooled epilogue stores whole 32-channel halves");
+    static_assert(!EXT || (STATS && NT >= 2), "the extremes ride on the training epilogue and are stored as whole 32-channel halves");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -126,7 +172,8 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
         for (int i = tid; i < 2 * CBW; i += NTHR) wgstat[i] = stats[(long long)(i / CBW) * Cop + co_wg + (i % CBW)];
         __syncthreads();
     }
-    const bool pool_lane = POOL && pool_store_lane(p);
+    const bool pool_lane = (POOL || EXT) && pool_store_lane(p);
+    const unsigned ext_neg = EXT ? ext_negative_mask<NT>(ext.gamma, ext.Co, co_base, q) : 0u;
 
     // ---- halo DMA pieces of this lane: byte offset from the halo origin pixel, and (hy, hx) for the bounds test
     constexpr bool HOFF_REG = true;              // large halos: recompute the offset per piece instead of holding it (registers)
@@ -204,7 +251,9 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
     Blk cur = decode(tile, 0);
     int hsel = 0, slot_cur = 0;
     bool after_store = false;                       // the previous block ended with a full-tile epilogue (NS stores per wave)
-    constexpr int NS = MT * ((NT + 1) / 2);
+    // store instructions per wave of a full tile: one per patch and 32-channel half, and as many again (lane-masked) for the extremes
+    constexpr int NS = (EXT ? 2 : 1) * MT * ((NT + 1) / 2);
+    static_assert(G::max_wait_after_store() + NS <= 63, "the counted waits must fit vmcnt's six bits");
 
     // ---- prologue: halo of the first block, weights of steps 0 .. R-2
     {
@@ -360,6 +409,21 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
                                 }
                         }
                     }
+                    if constexpr (EXT) {     // every lane takes part in the exchanges; windows follow emit_pool's floor rule and store count
+                        // One 32-channel half at a time, fenced: left to itself the scheduler starts both halves of several patches at once and
+                        // the 64-channel variants, whose STATS siblings already use all 256 registers, spill.
+                        const bool st_lane = pool_lane && (FULL || (((gy | 1) < H) && ((gx | 1) < W)));
+                        bf16* dst = ext.pooled + ((long long)(n * (H >> 1) + (gy >> 1)) * (W >> 1) + (gx >> 1)) * Cop + co_base + q * 8;
+#pragma unroll
+                        for (int h = 0; h < (NT + 1) / 2; ++h) {
+                            __builtin_amdgcn_sched_barrier(0);
+                            Vec8<bf16> e;
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) e.set(j, pool_raw_extreme(acc[m][h * 2 + (j >> 2)][j & 3], ext_flip(ext_neg, h * 8 + j)));
+                            if (st_lane) e.store(dst + h * 32);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
 #pragma unroll
                     for (int t = 0; t < NT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
@@ -420,10 +484,11 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, CB * PGR * PGC == 4 ? 2 : 1) v
 // ahead by LDS-DMA, and a tile costs ONE counted wait + ONE barrier.  Same tiles, fragment layout, swizzle, epilogue and statistics order
 // per tile as conv3x3_v2_kernel<2, CB, PGR, PGC, .>; the per-lane statistics are folded across lanes once, at the end.
 // POOL: as conv3x3_v2_kernel; the 16 scale/shift values of a lane live in the registers the statistics of the STATS sibling use.
-template <int CB, int PGR, int PGC, bool STATS, bool POOL = false>
+// EXT: as conv3x3_v2_kernel.
+template <int CB, int PGR, int PGC, bool STATS, bool POOL = false, bool EXT = false>
 __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wp, bf16* __restrict__ y,
                                                                             float* __restrict__ stats, int N, int H, int W, int Cip, int Cop, int tilesX,
-                                                                            int tilesY, int numTiles, int stat_rows, int xpix, long long xblk) {
+                                                                            int tilesY, int numTiles, int stat_rows, int xpix, long long xblk, V2Ext ext) {
     constexpr int NT = 2, HBN = 3;
     using G = V2Geom<NT, CB, PGR, PGC, 3>;
     constexpr int MT = G::MT, TH = G::TH, TW = G::TW, HW_ = G::HW_, HP = G::HP, HT = G::HT, NHW = G::NHW, CBW = G::CBW, PG = G::PG, NW = G::NW,
@@ -442,6 +507,7 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
     const long long wrow = (long long)9 * Cip;
     (void)xblk;
     static_assert(!(STATS && POOL), "the pooled epilogue keeps no batch statistics");
+    static_assert(!EXT || STATS, "the extremes ride on the training epilogue");
     f32x4 sc[NT], sh[NT];
     if (POOL) {
 #pragma unroll
@@ -451,7 +517,8 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
             sh[t] = *reinterpret_cast<const f32x4*>(sp + Cop);
         }
     }
-    const bool pool_lane = POOL && pool_store_lane(p);
+    const bool pool_lane = (POOL || EXT) && pool_store_lane(p);
+    const unsigned ext_neg = EXT ? ext_negative_mask<NT>(ext.gamma, ext.Co, co_base, q) : 0u;
 
     // the wave's weights: row (t, p) of the MFMA tile holds channel (t >> 1) * 32 + (p >> 2) * 8 + (t & 1) * 4 + (p & 3) (conv3x3_v2_kernel)
     Frag<bf16> aw[9][NT];
@@ -507,7 +574,8 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
     const int tile_end = tile0 + tchunk < numTiles ? tile0 + tchunk : numTiles;
     const int ntiles = tile_end - tile0;
     auto tl = [&](int i) { return decode(tile0 + (i < ntiles ? i : ntiles - 1)); };
-    constexpr int NS = MT * ((NT + 1) / 2);
+    constexpr int NS = (EXT ? 2 : 1) * MT * ((NT + 1) / 2);       // stores per wave of a full tile (conv3x3_v2_kernel)
+    static_assert(HT + 2 * NS <= 63, "the counted waits must fit vmcnt's six bits");
 
     halo_dma(tl(0), hbuf);
     halo_dma(tl(1), hbuf + G::HBUF);
@@ -596,6 +664,13 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
                             }
                     }
                 }
+                if constexpr (EXT) {         // every lane takes part in the exchanges; windows follow emit_pool's floor rule and store count
+                    Vec8<bf16> e;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) e.set(j, pool_raw_extreme(acc[m][j >> 2][j & 3], ext_flip(ext_neg, j)));
+                    if (pool_lane && (FULL || (((gy | 1) < H) && ((gx | 1) < W))))
+                        e.store(ext.pooled + ((long long)(n * (H >> 1) + (gy >> 1)) * (W >> 1) + (gx >> 1)) * Cop + co_base + q * 8);
+                }
 #pragma unroll
                 for (int t = 0; t < NT; ++t) acc[m][t] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
@@ -642,10 +717,10 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
     }
 }
 
-// ss != NULL (with part == NULL): the POOL instantiation, y = the pooled map
+// ss != NULL (with part == NULL): the POOL instantiation, y = the pooled map; ext.pooled != NULL (with part): the EXT instantiation
 template <int CB, int PGR, int PGC>
 int launch_k32(const bf16* x, const bf16* wp, bf16* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st,
-               int xpix, long long xblk) {
+               int xpix, long long xblk, V2Ext ext) {
     using G = V2Geom<2, CB, PGR, PGC, 3>;
     constexpr size_t LDS = (size_t)3 * G::HBUF * 2 + G::STAT_FLOATS * 4;
     static_assert(LDS <= 80 * 1024, "two workgroups per CU");
@@ -656,11 +731,19 @@ int launch_k32(const bf16* x, const bf16* wp, bf16* y, float* part, const float*
     if (gx < 1) gx = 1;
     gx = hyb_cdiv(numTiles, hyb_cdiv(numTiles, gx));
     const dim3 grid(gx, Cop / G::CBW);
-    static HybAttrOnce once_stats, once_plain, once_pool;
+    static HybAttrOnce once_stats, once_plain, once_pool, once_ext;
     if (ss) {
         if (int e = hyb_set_lds_attr(once_pool, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, false, true>, (int)LDS)) return e;
         hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, false, true>), grid, dim3(256), LDS, st, x, wp, y, const_cast<float*>(ss), N, H, W, Cip, Cop,
-                           tilesX, tilesY, (int)numTiles, 0, xpix, xblk);
+                           tilesX, tilesY, (int)numTiles, 0, xpix, xblk, V2Ext{});
+        HYB_LAUNCH_CHECK();
+        return 0;
+    }
+    if (ext.pooled) {
+        if (!part) return HYB_E_ARG;
+        if (int e = hyb_set_lds_attr(once_ext, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, true, false, true>, (int)LDS)) return e;
+        hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, true, false, true>), grid, dim3(256), LDS, st, x, wp, y, part, N, H, W, Cip, Cop, tilesX, tilesY,
+                           (int)numTiles, stat_rows, xpix, xblk, ext);
         HYB_LAUNCH_CHECK();
         return 0;
     }
@@ -668,17 +751,17 @@ int launch_k32(const bf16* x, const bf16* wp, bf16* y, float* part, const float*
     if (int e = hyb_set_lds_attr(once_plain, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, false>, (int)LDS)) return e;
     if (part)
         hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, true>), grid, dim3(256), LDS, st, x, wp, y, part, N, H, W, Cip, Cop, tilesX, tilesY, (int)numTiles,
-                           stat_rows, xpix, xblk);
+                           stat_rows, xpix, xblk, V2Ext{});
     else
         hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, false>), grid, dim3(256), LDS, st, x, wp, y, (float*)nullptr, N, H, W, Cip, Cop, tilesX, tilesY,
-                           (int)numTiles, 0, xpix, xblk);
+                           (int)numTiles, 0, xpix, xblk, V2Ext{});
     HYB_LAUNCH_CHECK();
     return 0;
 }
 
 template <int NT, int CB, int PGR, int PGC, int R>
 int launch_v2(const bf16* x, const bf16* wp, bf16* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st,
-              int xpix, long long xblk) {
+              int xpix, long long xblk, V2Ext ext) {
     using G = V2Geom<NT, CB, PGR, PGC, R>;
     const int tilesX = hyb_cdiv(W, G::TW), tilesY = hyb_cdiv(H, G::TH);
     const long long numTiles = (long long)N * tilesX * tilesY;
@@ -688,22 +771,34 @@ int launch_v2(const bf16* x, const bf16* wp, bf16* y, float* part, const float* 
     if (gx < 1) gx = 1;
     gx = hyb_cdiv(numTiles, hyb_cdiv(numTiles, gx));          // contiguous runs of ceil(numTiles / gx) tiles: drop the empty ones
     const dim3 grid(gx, Cop / G::CBW);
-    static HybAttrOnce once_stats, once_plain, once_pool;      // per template instantiation, per device
+    static HybAttrOnce once_stats, once_plain, once_pool, once_ext;      // per template instantiation, per device
     if (ss) {
         if (int e = hyb_set_lds_attr(once_pool, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false, true>, (int)G::LDS_BYTES)) return e;
         hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false, true>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, const_cast<float*>(ss),
-                           N, H, W, Cip, Cop, tilesX, tilesY, (int)numTiles, 0, xpix, xblk);
+                           N, H, W, Cip, Cop, tilesX, tilesY, (int)numTiles, 0, xpix, xblk, V2Ext{});
         HYB_LAUNCH_CHECK();
         return 0;
+    }
+    if (ext.pooled) {
+        if constexpr (v2_ext_built(NT, G::NW)) {
+            if (!part) return HYB_E_ARG;
+            if (int e = hyb_set_lds_attr(once_ext, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true, false, true>, (int)G::LDS_BYTES)) return e;
+            hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true, false, true>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, part, N, H, W,
+                               Cip, Cop, tilesX, tilesY, (int)numTiles, stat_rows, xpix, xblk, ext);
+            HYB_LAUNCH_CHECK();
+            return 0;
+        } else {
+            return HYB_NO_VARIANT;
+        }
     }
     if (int e = hyb_set_lds_attr(once_stats, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true>, (int)G::LDS_BYTES)) return e;
     if (int e = hyb_set_lds_attr(once_plain, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false>, (int)G::LDS_BYTES)) return e;
     if (part)
         hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, part, N, H, W, Cip, Cop,
-                           tilesX, tilesY, (int)numTiles, stat_rows, xpix, xblk);
+                           tilesX, tilesY, (int)numTiles, stat_rows, xpix, xblk, V2Ext{});
     else
         hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, (float*)nullptr, N, H, W,
-                           Cip, Cop, tilesX, tilesY, (int)numTiles, 0, xpix, xblk);
+                           Cip, Cop, tilesX, tilesY, (int)numTiles, 0, xpix, xblk, V2Ext{});
     HYB_LAUNCH_CHECK();
     return 0;
 }
@@ -723,28 +818,42 @@ int hyb_conv_v2_supported(int W, int Cip, int Cop) {
     return Cip % 32 == 0 && Cop % 32 == 0 && (long long)40 * W * Cip < (1ll << 29) && (long long)256 * 9 * Cip < (1ll << 29);
 }
 
+// Waves per workgroup of the family conv_v2_dispatch picks for Cop.  Measured on the 224 x 224 clip stages: two four-wave workgroups per CU
+// (their epilogues and MFMA phases interleave) win for Cop <= 128; 256-channel blocks need the whole CU's LDS for a deep weight ring.
+// HYB_V2_NW=4|8 forces one family.
+static int v2_waves(int Cop) {
+    static const int nw_env = hyb_env_int("HYB_V2_NW", 0);
+    return nw_env ? nw_env : (Cop % 256 == 0 ? 8 : 4);
+}
+// Does the variant hyb_conv_v2_ext would launch for this shape exist (v2_ext_built)?  The two tile shapes conv_v2_dispatch chooses between
+// by cost share NT and the wave count, so the answer does not depend on N and H.
+int hyb_conv_v2_ext_supported(int W, int Cip, int Cop) {
+    if (!hyb_conv_v2_supported(W, Cip, Cop) || W < 2) return 0;
+    const int nw = v2_waves(Cop);
+    const int nt = nw == 4 ? (Cop % 128 == 0 ? 4 : 2) : (Cop % 64 == 0 ? 4 : 2);       // conv3x3_k32_kernel: NT = 2, four waves
+    return v2_ext_built(nt, nw) ? 1 : 0;
+}
+
 // Internal (conv_fwd.hip): returns HYB_NO_VARIANT when no asynchronous variant fits this shape.  part: partial-statistics rows
 // [stat_rows][2][Cop] (may be NULL), all of them written.
 
 // xblk = 0: NHWC input; else the block-planar input's block stride in elements (see conv3x3_v2_kernel)
 // ss != NULL: the POOL instantiation of the same variant (y = the pooled map, no statistics)
+// ext.pooled != NULL: the EXT instantiation of the same variant (part required)
 static int conv_v2_dispatch(const void* x, const void* wp, void* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows,
-                            hipStream_t st, long long xblk) {
+                            hipStream_t st, long long xblk, V2Ext ext = V2Ext{}) {
     const int xpix = xblk ? 32 : Cip;
     if (!xblk) xblk = 32;
     if (!hyb_conv_v2_supported(W, Cip, Cop)) return HYB_NO_VARIANT;
     const bf16* xb = (const bf16*)x; const bf16* wb = (const bf16*)wp; bf16* yb = (bf16*)y;
-#define V2(NT_, CB_, PGR_, PGC_, R_) launch_v2<NT_, CB_, PGR_, PGC_, R_>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk)
-    // Measured on the 224 x 224 clip stages: two four-wave workgroups per CU (their epilogues and MFMA phases interleave) win for
-    // Cop <= 128; 256-channel blocks need the whole CU's LDS for a deep weight ring.  HYB_V2_NW=4|8 forces one family.
-    static const int nw_env = hyb_env_int("HYB_V2_NW", 0);
-    const int nw = nw_env ? nw_env : (Cop % 256 == 0 ? 8 : 4);
+#define V2(NT_, CB_, PGR_, PGC_, R_) launch_v2<NT_, CB_, PGR_, PGC_, R_>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk, ext)
+    const int nw = v2_waves(Cop);
     static const int k32_env = hyb_env_int("HYB_CONV_K32", 1);      // (=0: A/B, the ring kernel for 32 input channels too)
     if (k32_env && nw == 4 && Cip == 32 && Cop % 64 == 0) {
         // one channel block per tile: weights in registers, one barrier per tile (conv3x3_k32_kernel)
         return v2_cost(N, H, W, 8, 28, Cop / 64) <= v2_cost(N, H, W, 4, 56, Cop / 64)
-                   ? launch_k32<2, 2, 1>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk)
-                   : launch_k32<2, 1, 2>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk);
+                   ? launch_k32<2, 2, 1>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk, ext)
+                   : launch_k32<2, 1, 2>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk, ext);
     }
     if (nw == 4) {
         if (Cop % 256 == 0) return V2(4, 4, 1, 1, 3);
@@ -774,4 +883,12 @@ int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int 
 int hyb_conv_v2_pool(const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
     if (!ss || H < 2 || W < 2 || !hyb_conv_v2_supported(W, Cip, Cop)) return HYB_NO_VARIANT;
     return conv_v2_dispatch(x, wp, pooled, nullptr, ss, N, H, W, Cip, Cop, 0, st, 0);
+}
+
+// Internal (hyb_conv3x3_fwd_ext): hyb_conv_v2 with partial statistics, and pooled[N][H/2][W/2][Cop] = the raw extreme of every 2 x 2 window of y
+// (its maximum where gamma >= 0, its minimum where gamma < 0; channels >= Co count as non-negative).  HYB_NO_VARIANT as hyb_conv_v2.
+int hyb_conv_v2_ext(const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
+                    int stat_rows, hipStream_t st) {
+    if (!part || !pooled || !gamma || H < 2 || W < 2 || Co < 1 || Co > Cop) return HYB_E_ARG;
+    return conv_v2_dispatch(x, wp, y, part, nullptr, N, H, W, Cip, Cop, stat_rows, st, 0, V2Ext{(bf16*)pooled, gamma, Co});
 }

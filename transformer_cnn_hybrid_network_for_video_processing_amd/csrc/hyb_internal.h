@@ -39,6 +39,7 @@ int hyb_flash_attention_bwd(int dtype, const void* q, const void* k, const void*
 // bn_pool.hip
 int hyb_bn_infer_affine_many(int n, const float* const* gamma, const float* const* beta, const float* const* mean, const float* const* var,
                              float* const* scale_shift, const int* Co, const int* Cop, float eps, hipStream_t st);
+int hyb_bn_relu_apply_pooled(int dtype, void* pooled, const float* ss, int N, int Ho, int Wo, int Cop, hipStream_t st);
 int hyb_gap_fwd_h16(const void* x, float* feat, int N, int HW, int Cp, hipStream_t st);
 int hyb_gap_bwd_h16(const float* dfeat, void* dx, int N, int HW, int Cp, hipStream_t st);
 // conv_first.hip
@@ -55,6 +56,8 @@ int hyb_stage1_infer(int dtype, const float* x, const float* weight, const float
                      void* prepacked, void* workspace, hipStream_t st);
 // conv_fwd.hip
 int hyb_conv_dgrad_planar_ok(int dtype, int W, int Cin_p, int Cout_p);
+int hyb_conv3x3_fwd_ext(const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
+                        hipStream_t st);
 int hyb_conv3x3_planar_in(const void* x, const void* wp, void* y, int N, int H, int W, int Cin_p, int Cout_p, hipStream_t st);
 int hyb_conv_pack_weight_dual(int dtype, const float* w, void* wp0, void* wp1, int Co, int Ci, int Cop, int Cip, hipStream_t st);
 int hyb_conv_pack_weight_many(int dtype, int n, const float* const* w, void* const* wp0, void* const* wp1, const int* Co, const int* Ci, const int* Cop,
@@ -63,8 +66,11 @@ int hyb_conv_pack_weight_fwd_many(int dtype, int n, const float* const* w, void*
                                   const float* s1_w, void* s1_wp, int s1_Co, int s1_Ci, int s1_Cop, hipStream_t st);
 // conv_v2.hip
 int hyb_conv_v2_supported(int W, int Cip, int Cop);
+int hyb_conv_v2_ext_supported(int W, int Cip, int Cop);
 int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st, long long xblk = 0);
 int hyb_conv_v2_pool(const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st);
+int hyb_conv_v2_ext(const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
+                    int stat_rows, hipStream_t st);
 // conv_wgrad.hip
 int hyb_wgrad_reduce_multi(int n, const HybSlabInfo* infos, hipStream_t st);
 int hyb_wgrad_v2_supported(int dtype, int W, int Cip, int Cop);

@@ -165,9 +165,14 @@ int hyb_convstage_fwd_impl(int dtype, int first, const void* x, const float* wei
     else if (packed_bwd) HYB_TRY(hyb_conv_pack_weight_dual(dtype, weight, wp, packed_bwd, Co, Ci, Cop, Cip, (hipStream_t)stream));
     else HYB_TRY(hyb_conv_pack_weight(dtype, 0, weight, wp, Co, Ci, Cop, Cip, stream));
     if (training) {   // conv leaves per-workgroup partial sums; one launch sums them in a fixed order and finalises BN
-        HYB_TRY(hyb_conv3x3_fwd(dtype, 0, x, wp, y_raw, nullptr, part, N, H, W, Ci, Cip, Cop, stream));
+        // shapes hyb_conv3x3_pool_ext takes: the conv's epilogue also leaves every window's raw extreme in `pooled`, and BatchNorm + ReLU are
+        // applied to that quarter-resolution map in place -- the full-resolution re-read of y_raw by hyb_bn_relu_pool_fwd is gone
+        const bool ext = hyb_conv3x3_pool_ext(dtype, W, Cip, Cop) != 0;
+        if (ext) HYB_TRY(hyb_conv3x3_fwd_ext(x, wp, y_raw, part, pooled, gamma, Co, N, H, W, Cip, Cop, (hipStream_t)stream));
+        else HYB_TRY(hyb_conv3x3_fwd(dtype, 0, x, wp, y_raw, nullptr, part, N, H, W, Ci, Cip, Cop, stream));
         HYB_TRY(hyb_bn_stats_finalize(part, hyb_conv_stats_rows(0, N, H, W, Cop), gamma, beta, running_mean, running_var, nbt, momentum, eps,
                                       (long long)N * H * W, Co, Cop, scale_shift, mean_invstd, running_out, stream));
+        if (ext) return hyb_bn_relu_apply_pooled(dtype, pooled, scale_shift, N, H / 2, W / 2, Cop, (hipStream_t)stream);
     } else {
         HYB_TRY(hyb_conv3x3_fwd(dtype, 0, x, wp, y_raw, nullptr, nullptr, N, H, W, Ci, Cip, Cop, stream));
         HYB_TRY(hyb_bn_finalize(stats, gamma, beta, running_mean, running_var, nbt, 0, momentum, eps, (long long)N * H * W, Co, Cop,
@@ -194,6 +199,15 @@ extern "C" int hyb_conv3x3_pool_fused(int dtype, int W, int Cip, int Cop) {
     static const int fused_env = hyb_env_int("HYB_POOL_FUSED", 1);
     if (dtype != HYB_BF16 || W < 2 || Cip <= 0 || Cop <= 0 || Cip % 32 != 0 || Cop % 32 != 0) return 0;
     return fused_env && hyb_sw_conv_v2() && hyb_conv_v2_supported(W, Cip, Cop) ? 1 : 0;
+}
+
+// 1 when a TRAINING conv stage of this shape stores the raw 2 x 2 window extremes from the conv's epilogue and applies BatchNorm + ReLU to the
+// pooled map in place (bf16 storage, a shape the asynchronous kernels take with a variant that has the epilogue: hyb_conv_v2_ext_supported);
+// 0: the conv -> bn_relu_pool pair.  Same results bit for bit either way.  HYB_POOL_EXT=0 forces the pair (A/B).
+extern "C" int hyb_conv3x3_pool_ext(int dtype, int W, int Cip, int Cop) {
+    static const int ext_env = hyb_env_int("HYB_POOL_EXT", 1);
+    if (dtype != HYB_BF16 || W < 2 || Cip <= 0 || Cop <= 0 || Cip % 32 != 0 || Cop % 32 != 0) return 0;
+    return ext_env && hyb_sw_conv_v2() && hyb_conv_v2_ext_supported(W, Cip, Cop) ? 1 : 0;
 }
 
 extern "C" size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop) {

@@ -817,6 +817,11 @@ def conv3x3_pool_fused(dt, W, Cip, Cop):
     return bool(_query("hyb_conv3x3_pool_fused", int(dt), int(W), int(Cip), int(Cop)))
 
 
+def conv3x3_pool_ext(dt, W, Cip, Cop):
+    """True when a training-mode hybrid::convstage of this shape takes the window extremes from the conv's epilogue (same results either way)."""
+    return bool(_query("hyb_conv3x3_pool_ext", int(dt), int(W), int(Cip), int(Cop)))
+
+
 def convstage_infer_op(x: Tensor, weight: Tensor, gamma: Tensor, beta: Tensor, running_mean: Tensor, running_var: Tensor, eps: float, dt: int,
                        first: bool) -> Tensor:
     """-> pooled [N, H/2, W/2, Cop] of the compute dtype.  x as in hybrid::convstage."""
