@@ -282,6 +282,11 @@ int hyb_encoder_bwd(int dtype, const void* dout, const float* mask, const float*
                     float* const* grads, const void* saved, void* dx, int B, int S, int D, int Hid, int L,
                     int H, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* Pure host query (new symbol, hyb_abi_version() stays 9).  hyb_gemm_longk: 1 when the encoder's token product C[Mo][No] = A[Mo][R] .
+ * B[No][R]^T (bf16 in and out, `groups` products in one launch) runs on the long-K kernel: few-tile products with R >= 1024, i.e. the
+ * feed-forward's second Linear, the dX of its first Linear and the dX of the Q|K|V projection when Hid / 3 D reach 1024
+ * (HYB_GEMM_LONGK=0: never).  The results are the same bit for bit on either kernel. */
+int hyb_gemm_longk(int dtype, int groups, int Mo, int No, int R);
 
 /* ---- head: mean over T then Linear(d, classes) (composite's own) ---------------------- */
 int hyb_head_fwd(int dtype, const void* x /* [B,S,D] T */, const float* W /* [C,D] */, const float* b,

@@ -464,6 +464,79 @@ __global__ __launch_bounds__(NWV * 64) void gemm_nt_splitk_kernel(GemmArgs args)
     }
 }
 
+// The long-K form of gemm_nt_splitk_kernel<T, TC, 8, 0> (the FFN's second Linear, the dX of its first Linear and of the K-concatenated
+// Q|K|V projection: R = Hid or 3 D).  There a wave walks 6-12 k-steps; under the loop's `unroll 4` that is two or three dependent
+// load -> MFMA rounds, each a full trip to operands another XCD stored earlier in the step.  Here a wave requests the fragments of up to
+// LK_STEPS k-steps (Amask's included) before its first MFMA -- one round for R <= 2048 -- and the tile is 16 x 16, not 32 x 32: four times
+// the workgroups (256 at M = 128, N = 512) and half the fragment bytes through each CU's L1.
+// Same values bit for bit: wave w still accumulates k-steps w, w + 8, ... in that order into one accumulator per 16 x 16 block, the eight
+// partials are combined as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then bias, ReLU, accumulate, Cmask -- an output element
+// never sees the tile shape or the prefetch depth.
+constexpr int LK_STEPS = 8;
+template <typename T, typename TC>
+__global__ __launch_bounds__(512) void gemm_nt_longk_kernel(GemmArgs args) {
+    constexpr int NWV = 8;
+    __shared__ float red[NWV][16][17];
+    const GemmGroup grp = args.g[blockIdx.z];
+    const T* A = (const T*)grp.A;
+    const T* B = (const T*)grp.B;
+    const T* Mk = (const T*)grp.Amask;
+    TC* C = (TC*)grp.C;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int p = lane & 15, q = lane >> 4;
+    const int m0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
+    int r = m0 + p; if (r > args.Mo - 1) r = args.Mo - 1;
+    int c = n0 + p; if (c > args.No - 1) c = args.No - 1;
+    const T* arow = A + (long long)r * args.lda + 8 * q;
+    const T* mrow = (Mk ? Mk : A) + (long long)r * args.lda + 8 * q;
+    const T* brow = B + (long long)c * args.ldb + 8 * q;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int R = args.R;
+    for (int kb = wave * 32; kb < R; kb += LK_STEPS * NWV * 32) {
+        Frag<T> a[LK_STEPS], b[LK_STEPS], mk[LK_STEPS];
+        // every load of the round first (k0 < R is uniform over the wave; a lane past the end of a partial last k-step re-reads the
+        // start of its row and is zeroed below)
+#pragma unroll
+        for (int s = 0; s < LK_STEPS; ++s) {
+            const int k0 = kb + s * NWV * 32;
+            if (k0 < R) {
+                const int ko = (k0 + 8 * q + 8 <= R) ? k0 : 0;
+                frag_load(a[s], arow + ko);
+                frag_load(b[s], brow + ko);
+                if (Mk) frag_load(mk[s], mrow + ko);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < LK_STEPS; ++s) {
+            const int k0 = kb + s * NWV * 32;
+            if (k0 < R) {
+                if (Mk) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) if (!((float)mk[s].v[j] > 0.f)) a[s].v[j] = (T)0.0f;
+                }
+                if (k0 + 32 > R && k0 + 8 * q + 8 > R) { frag_zero(a[s]); frag_zero(b[s]); }
+                acc = mma32(a[s], b[s], acc);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[wave][4 * q + i][p] = acc[i];
+    __syncthreads();
+    if (tid >= 256) return;
+    const int row = tid >> 4, col = tid & 15;
+    const int mo = m0 + row, no = n0 + col;
+    if (mo >= args.Mo || no >= args.No) return;
+    float v = (red[0][row][col] + red[1][row][col]) + (red[2][row][col] + red[3][row][col]);
+    v += (red[4][row][col] + red[5][row][col]) + (red[6][row][col] + red[7][row][col]);
+    if (grp.bias) v += grp.bias[no];
+    if (args.relu) v = fmaxf(v, 0.f);
+    TC* dst = C + (long long)mo * args.ldc + no;
+    if (args.accumulate) v += to_f32<TC>(*dst);
+    if (grp.Cmask && !(to_f32<TC>(((const TC*)grp.Cmask)[(long long)mo * args.ldc + no]) > 0.f)) v = 0.f;
+    *dst = from_f32<TC>(v);
+}
+
 // The skinny product with LayerNorm + residual as its PROLOGUE:  C = act(LN(x + skip) . B^T + bias), the A operand formed by the workgroup
 // itself.  TransformerEncoder.forward normalises (src L116-117, L120-123) and immediately projects (the feed-forward's first Linear, the next
 // layer's Q / K / V projections); as launches of their own the two LayerNorms of a layer were 2 x 4.8 us for 128 rows (a dependent launch
@@ -857,7 +930,25 @@ int linear_bwd_t(const void* x, int ldx, const float* W, const void* Wt, const v
     return 0;
 }
 
+// few tiles (M = 128, N = 512: 64 workgroups of 32 x 32 on 256 CUs): eight waves split K to shorten the per-wave load/MFMA chain
+inline bool gemm_nt_w8(int groups, int Mo, int No, int R) {
+    static const int w8env = hyb_env_int("HYB_GEMM_W8", 1);
+    return w8env && (long long)hyb_cdiv(No, 32) * hyb_cdiv(Mo, 32) * groups <= 256 && R >= 256;
+}
+// ... and of those, the bf16 products with R >= 1024 take gemm_nt_longk_kernel: the step's long-K products have R = 1536 and 2048 (6 and 8
+// k-steps per wave, two rounds of the `unroll 4` loop); its K = 512 products (2 k-steps, one round) sit at the launch floor on the old kernel.
+// (The threshold is the smallest R the change was written for, not a measured crossover.)
+constexpr int LK_MIN_R = 1024;
+inline bool gemm_nt_longk(int dtype, int groups, int Mo, int No, int R, int out_f32) {
+    static const int env = hyb_env_int("HYB_GEMM_LONGK", 1);       // (=0: A/B, gemm_nt_splitk_kernel for every R)
+    return env && dtype == HYB_BF16 && !out_f32 && R >= LK_MIN_R && gemm_nt_w8(groups, Mo, No, R);
+}
+
 }  // namespace
+
+// Pure host query: 1 when hyb_gemm_nt runs a bf16 -> bf16 product of this shape on gemm_nt_longk_kernel (tests: the long-K comparison is
+// not one of the old kernel with itself)
+extern "C" int hyb_gemm_longk(int dtype, int groups, int Mo, int No, int R) { return gemm_nt_longk(dtype, groups, Mo, No, R, 0) ? 1 : 0; }
 
 // Internal: linear backward with pre-transposed T weights for the dx product
 int hyb_linear_bwd_wt(int dtype, const void* x, int ldx, const float* W, const void* Wt, const void* y, const void* dy, void* dx, int accumulate_dx,
@@ -878,9 +969,7 @@ int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* 
         a.g[i] = GemmGroup{A[i], B[i], C[i], bias ? bias[i] : nullptr, Amask ? Amask[i] : nullptr, nullptr, Cmask ? Cmask[i] : nullptr};
     a.Mo = Mo; a.No = No; a.R = R; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.relu = relu; a.accumulate = accumulate;
     dim3 grid(hyb_cdiv(No, 32), hyb_cdiv(Mo, 32), groups);
-    // few tiles (M = 128, N = 512: 64 workgroups on 256 CUs): eight waves split K to shorten the per-wave load/MFMA chain
-    static const int w8env = hyb_env_int("HYB_GEMM_W8", 1);
-    const bool w8 = w8env && (long long)grid.x * grid.y * grid.z <= 256 && R >= 256;
+    const bool w8 = gemm_nt_w8(groups, Mo, No, R);
     static const int tall_env = hyb_env_int("HYB_GEMM_TALL", 1);
     if (dtype == HYB_F32 && tall_env && groups == 1 && !Amask && !Cmask && Mo >= 2048) {
         // pixel-side GEMMs (M = N*H*W): one pass over A per column tile, four independent waves per workgroup
@@ -900,6 +989,8 @@ int hyb_gemm_nt(int dtype, int groups, const void* const* A, const void* const* 
     } else if (dtype == HYB_F32 && w8) hipLaunchKernelGGL((gemm_nt_splitk_kernel<float, float, 8>), grid, dim3(512), 0, st, a);      // (the temporal part of 'mixed' / 'bf16x3' / 'fp32')
     else if (dtype == HYB_F32) hipLaunchKernelGGL((gemm_nt_splitk_kernel<float, float, 4>), grid, dim3(256), 0, st, a);
     else if (dtype == HYB_BF16 && out_f32) hipLaunchKernelGGL((gemm_nt_splitk_kernel<bf16, float, 4>), grid, dim3(256), 0, st, a);
+    else if (gemm_nt_longk(dtype, groups, Mo, No, R, out_f32))
+        hipLaunchKernelGGL((gemm_nt_longk_kernel<bf16, bf16>), dim3(hyb_cdiv(No, 16), hyb_cdiv(Mo, 16), groups), dim3(512), 0, st, a);
     else if (dtype == HYB_BF16 && w8) hipLaunchKernelGGL((gemm_nt_splitk_kernel<bf16, bf16, 8>), grid, dim3(512), 0, st, a);
     else if (dtype == HYB_BF16) hipLaunchKernelGGL((gemm_nt_splitk_kernel<bf16, bf16, 4>), grid, dim3(256), 0, st, a);
     else return HYB_E_ARG;
