@@ -302,6 +302,22 @@ int hyb_cross_entropy_fwd(const float* logits, const long long* target, float* l
 int hyb_cross_entropy_bwd(const float* logits, const long long* target, const float* dloss /* [1] */,
                           float* dlogits, int B, int C, void* stream);
 
+/* hyb_cross_entropy_opts_*: the same loss with torch.nn.functional.cross_entropy's options, reduction "mean" (new symbols, hyb_abi_version()
+ *   stays 9).  weight [C] class weights >= 0, or NULL = all ones; has_ignore != 0: clips whose target equals ignore_index (inside or
+ *   outside [0, C)) are left out; label_smoothing e in [0, 1].  With keep_b = (target_b != ignore_index), lse_b = logsumexp(logits_b):
+ *     term_b = keep_b [ (1 - e) w[y_b] (lse_b - z_b[y_b]) + (e / C) sum_c w[c] (lse_b - z_b[c]) ],
+ *     den = sum_b keep_b w[y_b],   loss = (sum_b term_b) / den,
+ *     dlogits[b,c] = (dloss / den) keep_b [ (1 - e) w[y_b] (p_bc - [c == y_b]) + (e / C) (p_bc sum_k w[k] - w[c]) ].
+ *   den == 0 (every clip ignored, or zero-weight classes only): the loss is NaN and dlogits is all zero.  A kept target outside [0, C)
+ *   makes the loss and every kept row of dlogits NaN (rows of ignored clips stay 0); nothing is read out of bounds.  Numerator and den are summed in a fixed tree: results are
+ *   reproducible bit for bit.  HYB_E_ARG: a NULL pointer (other than weight), has_ignore not 0 / 1, label_smoothing outside [0, 1]. */
+int hyb_cross_entropy_opts_fwd(const float* logits, const long long* target, const float* weight /* [C] or NULL */,
+                               long long ignore_index, int has_ignore, float label_smoothing, float* loss /* [1] */, int B, int C,
+                               void* stream);
+int hyb_cross_entropy_opts_bwd(const float* logits, const long long* target, const float* weight /* [C] or NULL */,
+                               long long ignore_index, int has_ignore, float label_smoothing, const float* dloss /* [1] */,
+                               float* dlogits, int B, int C, void* stream);
+
 /* ---- model-level entry points: whole CNN backbone / whole temporal part in ONE call each way ---------------------------
  * They chain the stage-level entry points above on the caller's stream; their purpose is host time (a training step is three
  * operator calls each way), not different arithmetic: results are bit-identical to calling the stages one by one.
@@ -370,6 +386,24 @@ int hyb_temporal_ce_bwd(int dtype, const float* dloss, const float* logits, cons
                         void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p,
                         float layer_p, unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes,
                         void* stream);
+
+/* hyb_temporal_ce_opts_*: hyb_temporal_ce_* with the options of hyb_cross_entropy_opts_* (same meaning, same argument checks) behind the
+ *   target: the same launches, the same B + 1 floats of ce_scratch under the same rules (a buffer may serve both families), weight read
+ *   when the kernels run.  Results equal hyb_temporal_* followed by hyb_cross_entropy_opts_* bit for bit; shapes the fused tail does
+ *   not take run hyb_cross_entropy_opts_* as launches of their own.  (New symbols, hyb_abi_version() stays 9.) */
+int hyb_temporal_ce_opts_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                             const float* head_w, const float* head_b, const float* mask, const long long* target,
+                             const float* weight /* [classes] or NULL */, long long ignore_index, int has_ignore, float label_smoothing,
+                             void* feat, void* tok, void* enc_saved, void* enc_out, float* logits, float* loss, float* ce_scratch, int B,
+                             int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
+                             unsigned long long seed, const unsigned long long* seed_inc, void* stream);
+int hyb_temporal_ce_opts_bwd(int dtype, const float* dloss, const float* logits, const long long* target,
+                             const float* weight /* [classes] or NULL */, long long ignore_index, int has_ignore, float label_smoothing,
+                             const float* token_w, const float* const* enc_params, const float* head_w, const float* mask, const void* feat,
+                             const void* enc_saved, const void* enc_out, float* dtoken_w, float* dtoken_b, float* const* enc_grads,
+                             float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
+                             int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- FCT, the reference's "Fully Convolutional Transformer" (FCT.py:24-254; SURVEY.md section 8f-1, first "next" row) -----------
  * FORWARD entry points (the backward is the next step of this row).  Arrays are NHWC fp32 with the TRUE channel count

@@ -372,6 +372,94 @@ __global__ void ce_bwd_kernel(const float* __restrict__ logits, const long long*
     for (int c = 0; c < C; ++c) dlogits[b * C + c] = ce_clip_dlogit(logits + (long long)b * C, t, C, c, g);
 }
 
+// ---- cross entropy with options: class weights w (nullptr: all ones), an ignored class index, label smoothing e -------------------
+// torch.nn.functional.cross_entropy's "mean":  loss = (sum_b term_b) / den,  den = sum_b keep_b w[y_b],  keep_b = (y_b != ignore),
+//   term_b = keep_b [ (1 - e) w[y_b] (lse_b - z_b[y_b]) + (e / C) sum_c w[c] (lse_b - z_b[c]) ].
+// The plain loss above stays its own code (its kernels are the benchmarked path); these are the same per-clip / tree scheme: every
+// per-clip expression is one device function shared by the stand-alone kernels and the fused temporal tail, numerator and den each go
+// through the fixed 256-leaf tree, and den -- a function of target and weight alone -- is formed by whoever needs it, forward or backward,
+// with the same function: the backward divides by the forward's bits without a hand-off.
+__device__ __forceinline__ float ce_w(const float* w, int c) { return w ? w[c] : 1.f; }
+__device__ __forceinline__ bool ce_keep(long long t, const HybCeOpts& o) { return !(o.has_ignore && t == o.ignore_index); }
+// one clip's share of den; a kept target outside [0, C) poisons it (and with it the loss and every gradient) instead of reading out of bounds
+__device__ __forceinline__ float ce_clip_den(const float* w, long long t, int C, const HybCeOpts& o) {
+    if (!ce_keep(t, o)) return 0.f;
+    return (t >= 0 && t < C) ? ce_w(w, (int)t) : NAN;
+}
+__device__ __forceinline__ float ce_clip_loss_opts(const float* lg, const float* w, long long t, int C, const HybCeOpts& o) {
+    if (!ce_keep(t, o)) return 0.f;
+    if (!(t >= 0 && t < C)) return NAN;
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(lg[c] - mx);
+    const float lse = logf(s) + mx;
+    float r = (1.f - o.label_smoothing) * (ce_w(w, (int)t) * (lse - lg[(int)t]));
+    if (o.label_smoothing > 0.f) {
+        float sm = 0.f;
+        for (int c = 0; c < C; ++c) sm += ce_w(w, c) * (lse - lg[c]);
+        r += (o.label_smoothing / (float)C) * sm;
+    }
+    return r;
+}
+// one clip's d(loss)/d(logits[c]), g = dloss / den (0 when den == 0: nothing was kept, the gradient is zero)
+__device__ __forceinline__ float ce_clip_dlogit_opts(const float* lg, const float* w, long long t, int C, int c, float g, const HybCeOpts& o) {
+    if (!ce_keep(t, o)) return 0.f;
+    if (!(t >= 0 && t < C)) return NAN;
+    float mx = -INFINITY;
+    for (int k = 0; k < C; ++k) mx = fmaxf(mx, lg[k]);
+    float s = 0.f;
+    for (int k = 0; k < C; ++k) s += expf(lg[k] - mx);
+    const float p = expf(lg[c] - mx) / s;
+    float r = (1.f - o.label_smoothing) * (ce_w(w, (int)t) * (p - (c == (int)t ? 1.f : 0.f)));
+    if (o.label_smoothing > 0.f) {
+        float ws = 0.f;
+        for (int k = 0; k < C; ++k) ws += ce_w(w, k);
+        r += (o.label_smoothing / (float)C) * (p * ws - ce_w(w, c));
+    }
+    return g * r;
+}
+// sum of 256 leaves (thread t of the calling workgroup holds leaf t; every thread of it must call), ce_tree_mean's tree; returned to every thread
+__device__ __forceinline__ float ce_tree_sum(float acc, float* part /* LDS [256] */) {
+    if (threadIdx.x < 256) part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    const float r = part[0];
+    __syncthreads();                                          // (part is free again)
+    return r;
+}
+// den by the calling workgroup (>= 256 threads, all of them call): thread t owns clips t, t + 256, ..
+__device__ __forceinline__ float ce_den(const long long* __restrict__ target, const float* w, int B, int C, const HybCeOpts& o, float* part) {
+    float acc = 0.f;
+    if (threadIdx.x < 256)
+        for (int i = threadIdx.x; i < B; i += 256) acc += ce_clip_den(w, target[i], C, o);
+    return ce_tree_sum(acc, part);
+}
+__device__ __forceinline__ float ce_loss_opts(float num, float den) { return den == 0.f ? NAN : num / den; }
+__device__ __forceinline__ float ce_gscale_opts(float dloss, float den) { return den == 0.f ? 0.f : dloss / den; }
+
+__global__ __launch_bounds__(256) void ce_opts_fwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target, float* __restrict__ loss,
+                                                          int B, int C, HybCeOpts o) {
+    __shared__ float part[256];
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) acc += ce_clip_loss_opts(logits + (long long)b * C, o.weight, target[b], C, o);
+    const float num = ce_tree_sum(acc, part);
+    const float den = ce_den(target, o.weight, B, C, o, part);
+    if (threadIdx.x == 0) loss[0] = ce_loss_opts(num, den);
+}
+__global__ __launch_bounds__(256) void ce_opts_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                          const float* __restrict__ dloss, float* __restrict__ dlogits, int B, int C, HybCeOpts o) {
+    __shared__ float part[256];
+    const float g = ce_gscale_opts(dloss[0], ce_den(target, o.weight, B, C, o, part));      // every workgroup forms den for itself
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const long long t = target[b];
+    for (int c = 0; c < C; ++c) dlogits[(long long)b * C + c] = ce_clip_dlogit_opts(logits + (long long)b * C, o.weight, t, C, c, g, o);
+}
+
 // ---- the tail of the temporal part as ONE launch each way --------------------------------------------------------------------
 // forward: the last encoder layer's second LayerNorm (+ residual, scale, dropout: src L120-123) -> mean over the clip's tokens -> Linear
 // head -> (when a target is given) the clip's cross-entropy term, and the batch mean by the last workgroup to finish.  One workgroup per
@@ -384,21 +472,29 @@ __device__ __forceinline__ float head_logit(const float* pooled, const float* __
     return wave_sum(s);
 }
 
-template <typename T>
-__global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
-                                                                 const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
-                                                                 int B, int S, int D, float eps, float out_scale, float p_drop, unsigned long long seed,
-                                                                 const unsigned long long* __restrict__ seed_inc, const float* __restrict__ W,
-                                                                 const float* __restrict__ bias, float* __restrict__ logits, int C,
-                                                                 const long long* __restrict__ target, float* __restrict__ loss,
-                                                                 float* __restrict__ ce_scratch, int rows_in_lds) {
+// OPTS: the loss with options (ce_clip_loss_opts; `o`, and [64] class weights in LDS behind the loss tree).  The plain instantiation is the
+// code it always was: every OPTS line is compiled out of it.  nthreads / nclips are the kernel's blockDim.x / gridDim.x, read by the
+// __global__ wrappers: read in here, outside a kernel, blockDim.x compiles to the general form (a select on the grid's remainder and a
+// 16-bit global load of the implicit arguments) in front of the first row request instead of one scalar load of the kernel argument block.
+template <typename T, bool OPTS>
+__device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
+                                                       int B, int S, int D, float eps, float out_scale, float p_drop, unsigned long long seed,
+                                                       const unsigned long long* __restrict__ seed_inc, const float* __restrict__ W,
+                                                       const float* __restrict__ bias, float* __restrict__ logits, int C,
+                                                       const long long* __restrict__ target, float* __restrict__ loss,
+                                                       float* __restrict__ ce_scratch, int rows_in_lds, const HybCeOpts& o, const int nthreads,
+                                                       const unsigned int nclips) {                 // (the kernel's blockDim.x, gridDim.x)
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
     float* pooled = reinterpret_cast<float*>(tail_smem);                    // [D]
     float* lg = pooled + D;                                                  // [64] this clip's logits
     float* part = lg + 64;                                                   // [256] loss tree
-    T* rows = reinterpret_cast<T*>(part + 256);                              // [S][D] when rows_in_lds
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
+    float* wl = part + 256;                                                  // [64] class weights (OPTS)
+    T* rows = reinterpret_cast<T*>(part + 256 + (OPTS ? 64 : 0));            // [S][D] when rows_in_lds
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = nthreads >> 6;
     const int M = B * S;
+    float wreg = 1.f;                                                        // the class weights ride with the up-front requests
+    if constexpr (OPTS) { if (tid < C && o.weight) wreg = o.weight[tid]; }
     // this wave's first class: its weight row does not depend on the tokens -- requested before the LayerNorm rows (a latency-bound kernel: one
     // memory round trip fewer on the critical path), up to 8 x 64 features in registers
     float w0[8];
@@ -409,8 +505,9 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restr
     for (int s = wave; s < S; s += nwaves)
         ln_fwd_row<T>(f, x1, gamma, beta, enc_out, rows_in_lds ? rows + (long long)s * D : nullptr, stats, M, b * S + s, D, eps, out_scale, p_drop,
                       seed, seed_inc, lane);
+    if constexpr (OPTS) { if (tid < C) wl[tid] = wreg; }
     __syncthreads();                                                         // (also makes the rows just stored to enc_out readable by this workgroup)
-    for (int d = tid; d < D; d += blockDim.x) {
+    for (int d = tid; d < D; d += nthreads) {
         if (rows_in_lds) {
             float s = 0.f;
             for (int t = 0; t < S; ++t) s += to_f32<T>(rows[(long long)t * D + d]);      // token_mean's order
@@ -436,11 +533,14 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restr
     // invalidate per workgroup: ~3 us each on this chip, see optim.hip -- as much as the launch this fusion removes.)
     __shared__ int s_last;
     if (tid == 0) {
-        __hip_atomic_store(ce_scratch + b, ce_clip_loss(lg, target[b], C), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        float term;
+        if constexpr (OPTS) term = ce_clip_loss_opts(lg, o.weight ? wl : nullptr, target[b], C, o);
+        else term = ce_clip_loss(lg, target[b], C);
+        __hip_atomic_store(ce_scratch + b, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         unsigned int* ticket = reinterpret_cast<unsigned int*>(ce_scratch + B);
         const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == gridDim.x - 1;
+        s_last = t == nclips - 1;
         if (s_last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
@@ -448,7 +548,34 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restr
     float acc = 0.f;
     if (tid < 256)
         for (int i = tid; i < B; i += 256) acc += __hip_atomic_load(ce_scratch + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    ce_tree_mean(acc, part, loss, B);
+    if constexpr (OPTS) {           // ce_opts_fwd_kernel's two trees, the terms coming from the other workgroups
+        const float num = ce_tree_sum(acc, part);
+        const float den = ce_den(target, o.weight ? wl : nullptr, B, C, o, part);
+        if (tid == 0) loss[0] = ce_loss_opts(num, den);
+    } else ce_tree_mean(acc, part, loss, B);
+}
+template <typename T>
+__global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
+                                                                 int B, int S, int D, float eps, float out_scale, float p_drop, unsigned long long seed,
+                                                                 const unsigned long long* __restrict__ seed_inc, const float* __restrict__ W,
+                                                                 const float* __restrict__ bias, float* __restrict__ logits, int C,
+                                                                 const long long* __restrict__ target, float* __restrict__ loss,
+                                                                 float* __restrict__ ce_scratch, int rows_in_lds) {
+    temporal_tail_fwd_body<T, false>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
+                                     ce_scratch, rows_in_lds, HybCeOpts{}, blockDim.x, gridDim.x);
+}
+template <typename T>
+__global__ __launch_bounds__(512) void temporal_tail_fwd_opts_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
+                                                                      const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
+                                                                      int B, int S, int D, float eps, float out_scale, float p_drop,
+                                                                      unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
+                                                                      const float* __restrict__ W, const float* __restrict__ bias,
+                                                                      float* __restrict__ logits, int C, const long long* __restrict__ target,
+                                                                      float* __restrict__ loss, float* __restrict__ ce_scratch, int rows_in_lds,
+                                                                      HybCeOpts o) {
+    temporal_tail_fwd_body<T, true>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
+                                    ce_scratch, rows_in_lds, o, blockDim.x, gridDim.x);
 }
 
 // backward: cross-entropy backward (from the saved logits, when a target is given; else the caller's dlogits) -> head backward (the
@@ -458,18 +585,22 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restr
 // column.  Everything a workgroup reads -- its rows of the LayerNorm input, the head weights, the token means -- is requested up front: one
 // memory round trip.  Writes dx (d LN input), dskip and ln_rows affine-gradient partial rows as ln_residual_bwd_kernel<T, true> does for
 // the launch it replaces (workgroup (sb, b) writes row b * nsb + sb; rows no workgroup owns are zero-filled).
-template <typename T>
-__global__ __launch_bounds__(256) void temporal_tail_bwd_kernel(const float* __restrict__ dlogits_in, const float* __restrict__ logits,
-                                                                const long long* __restrict__ target, const float* __restrict__ dloss,
-                                                                const float* __restrict__ W, const T* __restrict__ enc_out, const T* __restrict__ f,
-                                                                const float* __restrict__ gamma, const float* __restrict__ stats, T* __restrict__ dx,
-                                                                T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
-                                                                float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
-                                                                float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc) {
+// OPTS (a target is given): the loss backward with options; [64] class weights and the [256] den tree in LDS behind lnred.
+template <typename T, bool OPTS>
+__device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__ dlogits_in, const float* __restrict__ logits,
+                                                       const long long* __restrict__ target, const float* __restrict__ dloss,
+                                                       const float* __restrict__ W, const T* __restrict__ enc_out, const T* __restrict__ f,
+                                                       const float* __restrict__ gamma, const float* __restrict__ stats, T* __restrict__ dx,
+                                                       T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
+                                                       float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
+                                                       float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
+                                                       const HybCeOpts& o) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
     float* dl = reinterpret_cast<float*>(tail_smem);                         // [64]
     float* v = dl + 64;                                                      // [D] the clip's token-gradient row (T-rounded values)
     float* lnred = v + D;                                                    // [4][2][D]
+    float* wl = lnred + 8 * D;                                               // [64] class weights, [256] den tree (OPTS)
+    float* part = wl + 64;
     const int sb = blockIdx.x, nsb = gridDim.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int M = B * S, nchunk = D >> 3;
     const int s_begin = sb * rpw, s_end = s_begin + rpw < S ? s_begin + rpw : S;
@@ -487,7 +618,16 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_kernel(const float* __r
     }
     const int d_first = sb + tid * nsb;                                      // this thread's first head column: its token mean does not wait for dl
     const float pooled_first = d_first < D ? token_mean(enc_out, b, S, D, d_first) : 0.f;
-    if (tid < C) dl[tid] = target ? ce_clip_dlogit(logits + (long long)b * C, target[b], C, tid, dloss[0] / (float)B) : dlogits_in[b * C + tid];
+    if constexpr (OPTS) {
+        if (tid < C) wl[tid] = o.weight ? o.weight[tid] : 1.f;
+        const float dlo = dloss[0];
+        __syncthreads();
+        const float* w = o.weight ? wl : nullptr;
+        const float g = ce_gscale_opts(dlo, ce_den(target, w, B, C, o, part));           // the forward's den: same function, same inputs
+        if (tid < C) dl[tid] = ce_clip_dlogit_opts(logits + (long long)b * C, w, target[b], C, tid, g, o);
+    } else {
+        if (tid < C) dl[tid] = target ? ce_clip_dlogit(logits + (long long)b * C, target[b], C, tid, dloss[0] / (float)B) : dlogits_in[b * C + tid];
+    }
     if (p_drop > 0.f && seed_inc) seed += *seed_inc;
     __syncthreads();
     for (int d = tid; d < D; d += 256) {
@@ -528,6 +668,29 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_kernel(const float* __r
         ln_part[(long long)prow * 2 * D + i] = (lnred[i] + lnred[2 * D + i]) + (lnred[4 * D + i] + lnred[6 * D + i]);
         for (int r = nrows + prow; r < ln_rows; r += nrows) ln_part[(long long)r * 2 * D + i] = 0.f;
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void temporal_tail_bwd_kernel(const float* __restrict__ dlogits_in, const float* __restrict__ logits,
+                                                                const long long* __restrict__ target, const float* __restrict__ dloss,
+                                                                const float* __restrict__ W, const T* __restrict__ enc_out, const T* __restrict__ f,
+                                                                const float* __restrict__ gamma, const float* __restrict__ stats, T* __restrict__ dx,
+                                                                T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
+                                                                float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
+                                                                float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc) {
+    temporal_tail_bwd_body<T, false>(dlogits_in, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C,
+                                     rpw, out_scale, p_drop, seed, seed_inc, HybCeOpts{});
+}
+template <typename T>
+__global__ __launch_bounds__(256) void temporal_tail_bwd_opts_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                                     const float* __restrict__ dloss, const float* __restrict__ W,
+                                                                     const T* __restrict__ enc_out, const T* __restrict__ f,
+                                                                     const float* __restrict__ gamma, const float* __restrict__ stats,
+                                                                     T* __restrict__ dx, T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
+                                                                     float* __restrict__ head_part, int B, int S, int D, int C, int rpw,
+                                                                     float out_scale, float p_drop, unsigned long long seed,
+                                                                     const unsigned long long* __restrict__ seed_inc, HybCeOpts o) {
+    temporal_tail_bwd_body<T, true>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
+                                    out_scale, p_drop, seed, seed_inc, o);
 }
 
 }  // namespace
@@ -597,14 +760,21 @@ int hyb_temporal_tail_ok(int B, int S, int D, int C, int ln_rows) {
 }
 int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float* gamma, const float* beta, void* enc_out, float* stats, int B, int S,
                           int D, float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const float* W,
-                          const float* bias, float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st) {
-    HYB_CHECK_ARG(f && x1 && gamma && beta && enc_out && stats && W && logits && (!target || (loss && ce_scratch)));
+                          const float* bias, float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st,
+                          const HybCeOpts* ce) {
+    HYB_CHECK_ARG(f && x1 && gamma && beta && enc_out && stats && W && logits && (!target || (loss && ce_scratch)) && (!ce || target));
     const size_t es = dtype == HYB_F32 ? 4 : 2;
-    const size_t base = ((size_t)D + 64 + 256) * sizeof(float);
+    const size_t base = ((size_t)D + 64 + 256 + (ce ? 64 : 0)) * sizeof(float);
     const int rows_in_lds = base + (size_t)S * D * es <= 60 * 1024;
     const size_t lds = base + (rows_in_lds ? (size_t)S * D * es : 0);
     const int threads = S >= 8 ? 512 : 256;             // (1024 threads leave 128 registers per lane: the LayerNorm row spills -- measured 13 -> 24 us)
-    if (dtype == HYB_F32)
+    if (ce && dtype == HYB_F32)
+        hipLaunchKernelGGL(temporal_tail_fwd_opts_kernel<float>, dim3(B), dim3(threads), lds, st, (const float*)f, (const float*)x1, gamma, beta, (float*)enc_out, stats, B, S,
+                           D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce);
+    else if (ce && dtype == HYB_BF16)
+        hipLaunchKernelGGL(temporal_tail_fwd_opts_kernel<bf16>, dim3(B), dim3(threads), lds, st, (const bf16*)f, (const bf16*)x1, gamma, beta, (bf16*)enc_out, stats, B, S,
+                           D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce);
+    else if (dtype == HYB_F32)
         hipLaunchKernelGGL(temporal_tail_fwd_kernel<float>, dim3(B), dim3(threads), lds, st, (const float*)f, (const float*)x1, gamma, beta, (float*)enc_out, stats, B, S, D,
                            eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds);
     else if (dtype == HYB_BF16)
@@ -617,9 +787,10 @@ int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float*
 int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* W,
                           const void* enc_out, const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part,
                           int ln_rows, float* head_part, int B, int S, int D, int C, float out_scale, float p_drop, unsigned long long seed,
-                          const unsigned long long* seed_inc, hipStream_t st) {
+                          const unsigned long long* seed_inc, hipStream_t st, const HybCeOpts* ce) {
     HYB_CHECK_ARG((dlogits || (logits && target && dloss)) && W && enc_out && f && gamma && stats && dx && dskip && ln_part && head_part);
-    const size_t lds = (64 + 9 * (size_t)D) * sizeof(float);
+    HYB_CHECK_ARG(!ce || (!dlogits && logits && target && dloss));
+    const size_t lds = (64 + 9 * (size_t)D + (ce ? 64 + 256 : 0)) * sizeof(float);
     // row blocks per clip: as many as the ln_rows partial rows allow (>= 1: hyb_temporal_tail_ok), four-row granules
     int nsb = hyb_cdiv(S, 4);
     if (nsb > ln_rows / B) nsb = ln_rows / B;
@@ -627,7 +798,13 @@ int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, 
     nsb = hyb_cdiv(S, rpw);
     const dim3 grid(nsb, B);
     if (lds > 64 * 1024) return HYB_E_ARG;
-    if (dtype == HYB_F32)
+    if (ce && dtype == HYB_F32)
+        hipLaunchKernelGGL(temporal_tail_bwd_opts_kernel<float>, grid, dim3(256), lds, st, logits, target, dloss, W, (const float*)enc_out, (const float*)f, gamma, stats,
+                           (float*)dx, (float*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce);
+    else if (ce && dtype == HYB_BF16)
+        hipLaunchKernelGGL(temporal_tail_bwd_opts_kernel<bf16>, grid, dim3(256), lds, st, logits, target, dloss, W, (const bf16*)enc_out, (const bf16*)f, gamma, stats,
+                           (bf16*)dx, (bf16*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce);
+    else if (dtype == HYB_F32)
         hipLaunchKernelGGL(temporal_tail_bwd_kernel<float>, grid, dim3(256), lds, st, dlogits, logits, target, dloss, W, (const float*)enc_out, (const float*)f, gamma,
                            stats, (float*)dx, (float*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc);
     else if (dtype == HYB_BF16)
@@ -677,6 +854,27 @@ extern "C" int hyb_cross_entropy_fwd(const float* logits, const long long* targe
 extern "C" int hyb_cross_entropy_bwd(const float* logits, const long long* target, const float* dloss, float* dlogits, int B, int C, void* stream) {
     HYB_CHECK_ARG(logits && target && dloss && dlogits && B > 0 && C > 0);
     hipLaunchKernelGGL(ce_bwd_kernel, dim3(hyb_cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// The loss with options (ce_opts_*_kernel).  hyb_ce_opts_ok: what every *_opts_* entry point asks of them.
+int hyb_ce_opts_ok(const HybCeOpts& o) {
+    return (o.has_ignore == 0 || o.has_ignore == 1) && o.label_smoothing >= 0.f && o.label_smoothing <= 1.f;
+}
+extern "C" int hyb_cross_entropy_opts_fwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                          float label_smoothing, float* loss, int B, int C, void* stream) {
+    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
+    HYB_CHECK_ARG(logits && target && loss && B > 0 && C > 0 && hyb_ce_opts_ok(o));
+    hipLaunchKernelGGL(ce_opts_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, B, C, o);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int hyb_cross_entropy_opts_bwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                          float label_smoothing, const float* dloss, float* dlogits, int B, int C, void* stream) {
+    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
+    HYB_CHECK_ARG(logits && target && dloss && dlogits && B > 0 && C > 0 && hyb_ce_opts_ok(o));
+    hipLaunchKernelGGL(ce_opts_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o);
     HYB_LAUNCH_CHECK();
     return 0;
 }

@@ -17,6 +17,9 @@ What makes capture legal here
     optimizer) AdamW's hyper-parameters live on the device too: step() uploads what changed (optimizer.sync_hyper(), never captured)
     before it replays, so a torch.optim.lr_scheduler works across replays, and the gradient norm is taken and applied inside piece C --
     with data parallelism over the averaged gradients in the buckets, as DistributedDataParallel + clip_grad_norm_ would;
+  * a HybridCrossEntropyLoss with options (class weights, ignore_index, label smoothing) stays inside the temporal part's launches: the
+    weights are read from the criterion's ``weight`` buffer when a replay runs, so an in-place update of that buffer is picked up by the
+    next replay; ignore_index and label_smoothing travel by value, and step() refuses a change of either after capture;
   * BatchNorm running statistics are updated in place by the captured statistics kernels (hybrid::backbone_).
 
 Data parallelism (world > 1): the backward pass is captured in two pieces so that the gradient all-reduce of the temporal part
@@ -58,6 +61,9 @@ class GraphedTrainStep:
         from .modules import HybridCrossEntropyLoss
         self._fused_loss = (type(criterion) is HybridCrossEntropyLoss and hasattr(model, "forward_temporal_loss")
                             and os.environ.get("HYB_FUSED_LOSS", "1") != "0")       # (=0: A/B, the criterion as its own two launches)
+        # the captured loss launch carries ignore_index and label_smoothing by value (the class weights are read from the criterion's buffer
+        # when a replay runs, so an in-place update of criterion.weight is picked up); a later change is refused like an optimizer's (_check_hyper)
+        self._captured_loss_opts = self._loss_opts_now()
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         dev = x.device
@@ -128,9 +134,23 @@ class GraphedTrainStep:
     def _hyper_now(self):
         return [(g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"], g.get("max_grad_norm") is not None) for g in self.optimizer.param_groups]
 
+    def _loss_opts_now(self):
+        """What a HybridCrossEntropyLoss's launches carry by value or by address: (ignore_index, label_smoothing, the weight buffer's address)."""
+        c = self.criterion
+        if not hasattr(c, "has_options"):
+            return None
+        return (c.ignore_index, c.label_smoothing, c.weight.data_ptr() if c.weight is not None else None)
+
     def _check_hyper(self):
         """In front of every replay.  Device path: upload what changed.  Plain path: a few comparisons per group (the host is the step's pacemaker
         between graph launches, so this stays allocation-free) -- a changed value must not be lost silently."""
+        now = self._loss_opts_now()
+        if now != self._captured_loss_opts:
+            what = [n for n, a, b in zip(("ignore_index", "label_smoothing", "the weight buffer (replaced, not updated in place)"), now,
+                                         self._captured_loss_opts) if a != b]
+            raise RuntimeError(f"GraphedTrainStep: the criterion's {', '.join(what)} changed after capture, but the captured loss launch carries "
+                               "the old value -- construct a new GraphedTrainStep (an in-place update of criterion.weight needs none: the "
+                               "buffer is read at replay time)")
         if self._dev_hyper:
             if any((g.get("max_grad_norm") is not None) != self._clipping for g in self.optimizer.param_groups):
                 raise RuntimeError("GraphedTrainStep: max_grad_norm was switched on or off after capture; the norm launch is (not) part of the "
@@ -168,7 +188,7 @@ class GraphedTrainStep:
     def _piece_a(self, bind=True):
         h, B = self.model.forward_backbone(self.x)
         if self._fused_loss:                                   # the loss rides in the temporal part's last launch, its backward in the backward's first
-            loss, logits = self.model.forward_temporal_loss(h, B, self.y, self.mask)
+            loss, logits = self.model.forward_temporal_loss(h, B, self.y, self.mask, self.criterion)
         else:
             logits = self.model.forward_temporal(h, B, self.mask)
             loss = self.criterion(logits, self.y)

@@ -171,10 +171,54 @@ class TransformerEncoder(nn.Module, _ComputeDtypeMixin):
 
 
 class HybridCrossEntropyLoss(nn.Module):
-    """Mean cross-entropy over the batch (the composite's own loss), one HIP kernel each way."""
+    """Mean cross-entropy over the batch (the composite's own loss), one HIP kernel each way.
+
+    ``weight`` (one fp32 entry >= 0 per class), ``ignore_index`` and ``label_smoothing`` mean what they mean in ``nn.CrossEntropyLoss``
+    with reduction "mean": the kept clips' terms are summed and divided by the sum of their target weights.  Two differences: the default
+    ``ignore_index`` is None (no class index is ignored; torch's default is -100), and a target outside [0, C) that is not ``ignore_index``
+    makes the loss NaN instead of raising a device assert.  When every clip is ignored or carries zero weight, the loss is NaN and the
+    gradient is zero.  With all three at their defaults this is the plain batch mean, through the operators it always used.
+
+    ``weight`` is a registered buffer (``.cuda()`` and ``state_dict()`` carry it) and is read by the kernels when they run: an in-place update
+    of the buffer is seen by the next call, and by the next replay of a GraphedTrainStep.  Under data parallelism each rank divides by the
+    weight sum of its own clips and the gradients are averaged over the ranks -- exactly what DistributedDataParallel does with
+    ``nn.CrossEntropyLoss(weight=...)``; no global weight sum is exchanged."""
+
+    def __init__(self, weight=None, ignore_index=None, label_smoothing=0.0):
+        super().__init__()
+        label_smoothing = float(label_smoothing)
+        if not 0.0 <= label_smoothing <= 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+        if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
+            raise TypeError(f"ignore_index must be an int or None, got {ignore_index!r}")
+        if weight is not None:
+            if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or weight.dtype != torch.float32:
+                raise ValueError("weight must be a 1-D float32 tensor with one entry per class")
+            if bool((weight < 0).any()) or bool(torch.isnan(weight).any()):
+                raise ValueError("weight must not have a negative entry")
+            weight = weight.detach().clone()
+        self.register_buffer("weight", weight)
+        self.ignore_index, self.label_smoothing = ignore_index, label_smoothing
+
+    def has_options(self):
+        return self.weight is not None or self.ignore_index is not None or self.label_smoothing != 0.0
+
+    def options(self):
+        """(weight buffer or None, ignore_index or None, label_smoothing): what the option-carrying operators take."""
+        return self.weight, self.ignore_index, self.label_smoothing
+
+    def _check_weight(self, C):
+        if self.weight is not None and self.weight.shape[0] != C:
+            raise ValueError(f"weight has {self.weight.shape[0]} entries but the logits have {C} classes")
 
     def forward(self, logits, target):
-        return ops.cross_entropy(logits, target)
+        if not self.has_options():
+            return ops.cross_entropy(logits, target)
+        self._check_weight(logits.shape[-1])
+        return ops.cross_entropy_opts(logits, target, self.weight, self.ignore_index, self.label_smoothing)
+
+    def extra_repr(self):
+        return f"ignore_index={self.ignore_index}, label_smoothing={self.label_smoothing}"
 
 
 class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
@@ -272,14 +316,26 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
         tok = ops.token(h, self.token_proj.weight, self.token_proj.bias, self._dt_t).reshape(B, h.shape[0] // B, -1)
         return ops.head(enc.forward_compute(tok, mask), self.head.weight, self.head.bias, self._dt_t)
 
-    def forward_temporal_loss(self, h, B, target, mask=None):
-        """Last pooled map + class indices [B] -> (mean cross-entropy loss, logits): ``HybridCrossEntropyLoss()(forward_temporal(h, B, mask), target)``
-        with the loss inside the temporal part's own launches (hybrid::temporal_ce; same bits).  Plain-structure models only (``_fused()``)."""
+    def forward_temporal_loss(self, h, B, target, mask=None, criterion=None):
+        """Last pooled map + class indices [B] -> (mean cross-entropy loss, logits): ``criterion(forward_temporal(h, B, mask), target)``
+        with the loss inside the temporal part's own launches (hybrid::temporal_ce, or hybrid::temporal_ce_opts when the criterion carries
+        options; same bits, same number of launches).  ``criterion``: a HybridCrossEntropyLoss, None = ``HybridCrossEntropyLoss()``.
+        Plain-structure models only (``_fused()``)."""
         enc = self.encoder
+        if criterion is not None and type(criterion) is not HybridCrossEntropyLoss:
+            raise TypeError("forward_temporal_loss fuses HybridCrossEntropyLoss only")
+        opts = criterion is not None and criterion.has_options()
         if not self._fused():
             logits = self.forward_temporal(h, B, mask)
-            return ops.cross_entropy(logits, target), logits
+            return (criterion(logits, target) if opts else ops.cross_entropy(logits, target)), logits
         tdt = self._temporal_dt()
+        if opts:
+            criterion._check_weight(self.head.weight.shape[0])
+            weight, ignore_index, label_smoothing = criterion.options()
+            return ops.temporal_ce_opts(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias,
+                                        enc._flat_params(), self.head.weight, self.head.bias, mask, target, weight, ignore_index, label_smoothing, B, tdt,
+                                        enc.hidden_dim, enc.num_layers, enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout),
+                                        ops.next_seed())
         return ops.temporal_ce(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias, enc._flat_params(),
                                self.head.weight, self.head.bias, mask, target, B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout),
                                ops.next_seed())

@@ -20,6 +20,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::mha              MultiheadAttention.forward                          (src L67-89)
     hybrid::head             mean over T + Linear(d, classes)                    (composite's own)
     hybrid::cross_entropy    mean cross-entropy                                  (composite's own)
+    hybrid::cross_entropy_opts   ... with class weights, label smoothing, ignore_index   (torch.nn.functional.cross_entropy's "mean")
     hybrid::cast, hybrid::nchw_to_nhwc, hybrid::nhwc_to_nchw                     layout / dtype glue for standalone module use
     hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
 """
@@ -619,6 +620,64 @@ def cross_entropy(logits, target):
     return torch.ops.hybrid.cross_entropy(logits, target)
 
 
+def _ce_weight(weight, C, device):
+    """The class-weight vector as the hyb_*_opts_* entry points read it: [C] fp32 contiguous on the device, or None."""
+    if weight is None:
+        return None
+    _require_cuda(weight)
+    if weight.dim() != 1 or weight.shape[0] != C:
+        raise ValueError(f"weight must have one entry per class: expected [{C}], got {tuple(weight.shape)}")
+    if weight.dtype != torch.float32:
+        raise TypeError(f"weight must be float32, got {weight.dtype}")
+    if weight.device != device:
+        raise RuntimeError(f"weight is on {weight.device} but the logits are on {device}")
+    return weight.contiguous()
+
+
+def cross_entropy_opts_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
+                          label_smoothing: float) -> Tensor:
+    """Mean cross-entropy with class weights, label smoothing and an ignored class index (hyb_cross_entropy_opts_fwd): the sum of the kept
+    clips' terms over the sum of their target weights, torch.nn.functional.cross_entropy's "mean"."""
+    _require_cuda(logits, target)
+    if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
+        raise ValueError(f"expected logits [B,C] and class indices [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
+    logits = logits.contiguous().float()
+    target = target.contiguous().to(torch.int64)
+    B, C = logits.shape
+    weight = _ce_weight(weight, C, logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    lib.call("hyb_cross_entropy_opts_fwd", logits.data_ptr(), target.data_ptr(), _opt_ptr(weight), int(ignore_index), int(has_ignore),
+             float(label_smoothing), loss.data_ptr(), B, C, _stream())
+    return loss
+
+
+def cross_entropy_opts_fake(logits, target, weight, ignore_index, has_ignore, label_smoothing):
+    return logits.new_empty((), dtype=torch.float32)
+
+
+def cross_entropy_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
+                              label_smoothing: float) -> Tensor:
+    _require_cuda(dloss, logits)
+    logits = logits.contiguous().float()
+    target = target.contiguous().to(torch.int64)
+    B, C = logits.shape
+    weight = _ce_weight(weight, C, logits.device)
+    dl = dloss.contiguous().float().reshape(1)
+    dlogits = torch.empty_like(logits)
+    lib.call("hyb_cross_entropy_opts_bwd", logits.data_ptr(), target.data_ptr(), _opt_ptr(weight), int(ignore_index), int(has_ignore),
+             float(label_smoothing), dl.data_ptr(), dlogits.data_ptr(), B, C, _stream())
+    return dlogits
+
+
+def cross_entropy_opts_bwd_fake(dloss, logits, target, weight, ignore_index, has_ignore, label_smoothing):
+    return logits.new_empty(logits.shape, dtype=torch.float32)
+
+
+def cross_entropy_opts(logits, target, weight=None, ignore_index=None, label_smoothing=0.0):
+    return torch.ops.hybrid.cross_entropy_opts(logits, target, weight, 0 if ignore_index is None else int(ignore_index), ignore_index is not None,
+                                               float(label_smoothing))
+
+
 # ---------------------------------------------------------------------------------------------
 # model-level operators: the whole CNN backbone / the whole temporal part in one call each way (hyb_backbone_*, hyb_temporal_*).
 # Same kernels as the stage operators above, chained in C: a training step is three operator calls each way, which keeps the
@@ -1005,6 +1064,12 @@ def temporal_ce_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequ
                    target: Tensor, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
                    seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """hybrid::temporal + hybrid::cross_entropy in the same launches (hyb_temporal_ce_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
+    return _temporal_ce_fwd(None, h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
+def _temporal_ce_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc):
+    """ce None: hyb_temporal_ce_fwd; ce = (weight, ignore_index, has_ignore, label_smoothing): hyb_temporal_ce_opts_fwd, the same call with
+    the loss options behind the target."""
     _require_cuda(h, token_w, head_w, target, *enc_params)
     _check_h_dtype(h, dt)
     h = h.contiguous()
@@ -1024,11 +1089,30 @@ def temporal_ce_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequ
     logits = torch.empty(B, classes, dtype=torch.float32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     ps = [p.contiguous() for p in enc_params]
-    lib.call("hyb_temporal_ce_fwd", dt, h.data_ptr(), token_w.contiguous().data_ptr(), token_b.contiguous().data_ptr(), ptr_array([p.data_ptr() for p in ps]),
-             head_w.contiguous().data_ptr(), head_b.contiguous().data_ptr(), _opt_ptr(mask), target.data_ptr(), feat.data_ptr(), tok.data_ptr(),
+    opts = ()
+    if ce is not None:
+        weight = _ce_weight(ce[0], classes, dev)              # (kept alive until the call below)
+        opts = (_opt_ptr(weight), int(ce[1]), int(ce[2]), float(ce[3]))
+    lib.call("hyb_temporal_ce_fwd" if ce is None else "hyb_temporal_ce_opts_fwd", dt, h.data_ptr(), token_w.contiguous().data_ptr(),
+             token_b.contiguous().data_ptr(), ptr_array([p.data_ptr() for p in ps]),
+             head_w.contiguous().data_ptr(), head_b.contiguous().data_ptr(), _opt_ptr(mask), target.data_ptr(), *opts, feat.data_ptr(), tok.data_ptr(),
              saved.data_ptr(), enc_out.data_ptr(), logits.data_ptr(), loss.data_ptr(), _ce_scratch(B, dev).data_ptr(), B, S, Hh * Ww, C, Cp, D, hid, L, H,
              classes, float(attn_p), float(layer_p), seed, _opt_ptr(seed_inc), _stream())
     return loss, logits, feat, saved, enc_out
+
+
+def temporal_ce_opts_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
+                        mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
+                        B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
+                        seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """hybrid::temporal + hybrid::cross_entropy_opts in the same launches (hyb_temporal_ce_opts_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
+    return _temporal_ce_fwd((weight, ignore_index, has_ignore, label_smoothing), h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt,
+                            hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
+def temporal_ce_opts_fake(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid,
+                          L, H, attn_p, layer_p, seed, seed_inc=None):
+    return temporal_ce_fake(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed)
 
 
 def temporal_ce_fake(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
@@ -1039,6 +1123,13 @@ def temporal_ce_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, token_w: T
                        mask: Optional[Tensor], feat: Tensor, saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int,
                        attn_p: float, layer_p: float, seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
     """-> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]: hybrid::cross_entropy_bwd + hybrid::temporal_bwd in the same launches."""
+    return _temporal_ce_bwd(None, dloss, logits, target, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p,
+                            seed, seed_inc)
+
+
+def _temporal_ce_bwd(ce, dloss, logits, target, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed,
+                     seed_inc):
+    """ce as in _temporal_ce_fwd: hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd."""
     _require_cuda(dloss, logits, feat)
     B, S, D = enc_out.shape
     N, Cp = feat.shape
@@ -1054,11 +1145,30 @@ def temporal_ce_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, token_w: T
     dhw = torch.empty_like(head_w, memory_format=torch.contiguous_format)
     dhb = torch.empty(classes, dtype=torch.float32, device=dev)
     ws = _ws(_query("hyb_temporal_bwd_workspace", dt & 0xff, B, S, Hh * Ww, Cp, D, hid, L, H), dev)
-    lib.call("hyb_temporal_ce_bwd", dt, dl.data_ptr(), logits.contiguous().data_ptr(), target.contiguous().data_ptr(), token_w.contiguous().data_ptr(),
+    opts = ()
+    if ce is not None:
+        weight = _ce_weight(ce[0], classes, dev)
+        opts = (_opt_ptr(weight), int(ce[1]), int(ce[2]), float(ce[3]))
+    lib.call("hyb_temporal_ce_bwd" if ce is None else "hyb_temporal_ce_opts_bwd", dt, dl.data_ptr(), logits.contiguous().data_ptr(),
+             target.contiguous().data_ptr(), *opts, token_w.contiguous().data_ptr(),
              ptr_array([p.data_ptr() for p in ps]), head_w.contiguous().data_ptr(), _opt_ptr(mask), feat.data_ptr(), saved.data_ptr(), enc_out.data_ptr(),
              dtw.data_ptr(), dtb.data_ptr(), ptr_array([g.data_ptr() for g in grads]), dhw.data_ptr(), dhb.data_ptr(), dh.data_ptr(), B, S, Hh * Ww, C, Cp,
              D, hid, L, H, classes, float(attn_p), float(layer_p), seed, _opt_ptr(seed_inc), ws.data_ptr(), ws.numel(), _stream())
     return [dh, dtw, dtb, dhw, dhb] + grads
+
+
+def temporal_ce_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
+                            label_smoothing: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
+                            saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
+                            seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
+    """-> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]: hybrid::cross_entropy_opts_bwd + hybrid::temporal_bwd in the same launches."""
+    return _temporal_ce_bwd((weight, ignore_index, has_ignore, label_smoothing), dloss, logits, target, token_w, enc_params, head_w, mask, feat, saved,
+                            enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
+def temporal_ce_opts_bwd_fake(dloss, logits, target, weight, ignore_index, has_ignore, label_smoothing, token_w, enc_params, head_w, mask, feat, saved,
+                              enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
+    return temporal_bwd_fake(logits, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed)
 
 
 def temporal_ce_bwd_fake(dloss, logits, target, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed,
@@ -1072,6 +1182,17 @@ def temporal_ce(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B
     S = h.shape[0] // B
     r = torch.ops.hybrid.temporal_ce(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, B, dt, hid, L, H,
                                      float(attn_p), float(layer_p), seed, step_counter())
+    return r[0], r[1]
+
+
+def temporal_ce_opts(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, label_smoothing, B, dt, hid, L, H, attn_p,
+                     layer_p, seed):
+    """-> (loss, logits): temporal_ce with class weights [classes] (or None), an ignored class index (or None) and label smoothing: the same
+    launches, the options ride in them."""
+    S = h.shape[0] // B
+    r = torch.ops.hybrid.temporal_ce_opts(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
+                                          0 if ignore_index is None else int(ignore_index), ignore_index is not None, float(label_smoothing), B, dt, hid,
+                                          L, H, float(attn_p), float(layer_p), seed, step_counter())
     return r[0], r[1]
 
 
@@ -1244,6 +1365,21 @@ class _CrossEntropyFn(torch.autograd.Function):
         return torch.ops.hybrid.cross_entropy_bwd(dloss, logits, target), None
 
 
+class _CrossEntropyOptsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, has_ignore, label_smoothing):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(logits, target, weight)
+        ctx.cfg = (ignore_index, has_ignore, label_smoothing)
+        with _below_autograd():
+            return torch.ops.hybrid.cross_entropy_opts(logits, target, weight, ignore_index, has_ignore, label_smoothing)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, target, weight = ctx.saved_tensors
+        return (torch.ops.hybrid.cross_entropy_opts_bwd(dloss, logits, target, weight, *ctx.cfg),) + (None,) * 5        # (no gradient for the class weights)
+
+
 class _BackboneFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, S, training, momentum, eps, dt, *tensors):
@@ -1327,6 +1463,34 @@ class _TemporalCeFn(torch.autograd.Function):
         return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 11 + tuple(g[5:])
 
 
+class _TemporalCeOptsFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, token_w, token_b, head_w, head_b, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
+                layer_p, seed, seed_inc, *enc_params):
+        ctx.set_materialize_grads(False)
+        with _below_autograd():
+            loss, logits, feat, saved, enc_out = torch.ops.hybrid.temporal_ce_opts(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight,
+                                                                                   ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
+                                                                                   layer_p, seed, seed_inc)
+        ctx.seed_inc = seed_inc
+        opt = [t for t in (weight, mask) if t is not None]
+        ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, logits, target, *opt, *enc_params)
+        ctx.cfg = (weight is not None, mask is not None, ignore_index, has_ignore, label_smoothing, h.shape[1], h.shape[2], dt, hid, L, H, attn_p, layer_p,
+                   seed)
+        ctx.mark_non_differentiable(logits, feat, saved, enc_out)
+        return loss, logits, feat, saved, enc_out
+
+    @staticmethod
+    def backward(ctx, dloss, *unused):
+        has_weight, has_mask, ignore_index, has_ignore, label_smoothing, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed = ctx.cfg
+        token_w, head_w, feat, saved, enc_out, logits, target, *rest = ctx.saved_tensors
+        weight = rest.pop(0) if has_weight else None
+        mask = rest.pop(0) if has_mask else None
+        g = torch.ops.hybrid.temporal_ce_opts_bwd(dloss, logits, target, weight, ignore_index, has_ignore, label_smoothing, token_w, rest, head_w, mask,
+                                                  feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, ctx.seed_inc)
+        return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 15 + tuple(g[5:])
+
+
 _define("nchw_to_nhwc", "(Tensor x, int dt, int cp) -> Tensor", nchw_to_nhwc_op, nchw_to_nhwc_fake, _NchwToNhwcFn.apply)
 _define("nhwc_to_nchw", "(Tensor x, int dt, int C) -> Tensor", nhwc_to_nchw_op, nhwc_to_nchw_fake, _NhwcToNchwFn.apply)
 _define("cast", "(Tensor x, int dt, bool to_t) -> Tensor", cast_op, cast_fake, _CastFn.apply)
@@ -1352,6 +1516,10 @@ _define("head", "(Tensor x, Tensor weight, Tensor? bias, int dt) -> Tensor", hea
 _define("head_bwd", "(Tensor dlogits, Tensor x, Tensor weight, bool has_bias, int dt) -> (Tensor, Tensor, Tensor)", head_bwd_op, head_bwd_fake)
 _define("cross_entropy", "(Tensor logits, Tensor target) -> Tensor", cross_entropy_op, cross_entropy_fake, _CrossEntropyFn.apply)
 _define("cross_entropy_bwd", "(Tensor dloss, Tensor logits, Tensor target) -> Tensor", cross_entropy_bwd_op, cross_entropy_bwd_fake)
+_define("cross_entropy_opts", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing) -> Tensor",
+        cross_entropy_opts_op, cross_entropy_opts_fake, _CrossEntropyOptsFn.apply)
+_define("cross_entropy_opts_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, "
+        "float label_smoothing) -> Tensor", cross_entropy_opts_bwd_op, cross_entropy_opts_bwd_fake)
 _define("backbone", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, bool training, "
         "float momentum, float eps, int dt) -> Tensor[]", backbone_op, backbone_fake,
         lambda x, ws, gs, bs, rms, rvs, training, momentum, eps, dt: list(_BackboneFn.apply(x, len(ws), training, momentum, eps, dt, *ws, *gs, *bs,
@@ -1384,6 +1552,15 @@ _define("temporal_ce", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_
 _define("temporal_ce_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, "
         "Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) "
         "-> Tensor[]", temporal_ce_bwd_op, temporal_ce_bwd_fake)
+_define("temporal_ce_opts", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
+        "Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int B, int dt, int hid, int L, int H, float attn_p, float layer_p, "
+        "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_opts_op, temporal_ce_opts_fake,
+        lambda h, tw, tb, ps, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p, layer_p, seed,
+        seed_inc=None: _TemporalCeOptsFn.apply(h, tw, tb, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H,
+                                               attn_p, layer_p, seed, seed_inc, *ps))
+_define("temporal_ce_opts_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, "
+        "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
+        "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_opts_bwd_op, temporal_ce_opts_bwd_fake)
 
 
 # ---------------------------------------------------------------------------------------------
