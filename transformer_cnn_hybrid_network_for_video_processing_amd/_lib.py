@@ -1,6 +1,12 @@
 """ctypes binding of libhybrid_hip.so.  Prototypes are parsed from include/hybrid_hip.h so the
 Python side cannot drift from the C ABI.  There is NO fallback: if the shared object is missing or
-a call fails, a RuntimeError is raised."""
+a call fails, a RuntimeError is raised.
+
+call() and query() take tensors for pointer parameters and own them for the length of the call: a
+temporary made in the argument list (``w.contiguous()``) is referenced by the argument tuple until
+the C function has returned, i.e. until its launches are enqueued, after which the allocator's
+same-stream reuse rule orders any reuse of the block behind them.  A tensor is anything with
+``data_ptr()`` and ``is_contiguous()``: this module does not import torch."""
 import ctypes
 import os
 import re
@@ -55,11 +61,31 @@ def parse_header(path=HEADER):
     return protos
 
 
+_PLAIN = frozenset((int, float, bool))
+_PASS, _TENSOR, _SEQUENCE = 0, 1, 2
+_KIND = {}                   # class of a pointer argument -> how _marshal treats it; filled as classes are met
+
+
+def _kind(cls):
+    k = _KIND.get(cls)
+    if k is None:
+        k = _KIND[cls] = _SEQUENCE if cls in (list, tuple) else _TENSOR if hasattr(cls, "data_ptr") and hasattr(cls, "is_contiguous") else _PASS
+    return k
+
+
+def _not_contiguous(name, i):
+    return ValueError(f"{name}: argument {i} is a tensor that is not contiguous; pass t.contiguous() (the binding holds it through the call and "
+                      "never copies by itself)")
+
+
 class _Lib:
     def __init__(self, path=LIB_PATH):
         self._dll = None
         self._path = path
         self.protos = parse_header()
+        # per entry point, once: (parameter count, positions of the pointer parameters, positions of the others)
+        self._sig = {name: (len(args), tuple(i for i, a in enumerate(args) if a == "ptr"), tuple(i for i, a in enumerate(args) if a != "ptr"))
+                     for name, (_, args) in self.protos.items()}
 
     def _load(self):
         if self._dll is not None:
@@ -80,16 +106,48 @@ class _Lib:
     def raw(self, name):
         return getattr(self._load(), name)
 
+    def _marshal(self, name, args):
+        """The argument list as ctypes takes it.  Pointer parameters: None, an int address and a ctypes array pass as they are, a tensor
+        becomes its address, a list / tuple of tensors (None and int entries allowed) a host array of their addresses.  Only the pointer
+        positions are looked at one by one; the others get one type-set test, which is what refuses a tensor where a number belongs."""
+        n, ptr_pos, plain_pos = self._sig[name]
+        if len(args) != n:
+            raise TypeError(f"{name} takes {n} arguments ({len(args)} given)")
+        out = list(args)
+        for i in ptr_pos:
+            a = args[i]
+            kind = _KIND.get(a.__class__)
+            if kind is None:
+                kind = _kind(a.__class__)
+            if kind == _TENSOR:
+                if not a.is_contiguous():
+                    raise _not_contiguous(name, i)
+                out[i] = a.data_ptr()
+            elif kind == _SEQUENCE:
+                try:
+                    if False in [t.is_contiguous() for t in a]:
+                        raise _not_contiguous(name, i)
+                    out[i] = (ctypes.c_void_p * len(a))(*[t.data_ptr() for t in a])
+                except AttributeError:          # an entry that is no tensor: None or an int address
+                    if any(_kind(t.__class__) == _TENSOR and not t.is_contiguous() for t in a):
+                        raise _not_contiguous(name, i) from None
+                    out[i] = (ctypes.c_void_p * len(a))(*[t.data_ptr() if _kind(t.__class__) == _TENSOR else t for t in a])
+        if not _PLAIN.issuperset(map(type, map(args.__getitem__, plain_pos))):
+            for i in plain_pos:
+                if _kind(args[i].__class__) == _TENSOR:
+                    raise TypeError(f"{name}: argument {i} is a `{self.protos[name][1][i]}` parameter, got a tensor")
+        return out
+
     def call(self, name, *args):
-        """Call an int-returning entry point; raise on a non-zero status."""
-        rc = getattr(self._load(), name)(*args)
+        """Call an int-returning entry point; raise on a non-zero status.  `args` keeps every tensor alive until the function has returned."""
+        rc = getattr(self._load(), name)(*self._marshal(name, args))
         if rc != 0:
             kind = "argument check" if rc == -1 else "workspace too small" if rc == -2 else f"hipError_t {rc}"
             raise RuntimeError(f"{name} failed: {kind} (status {rc})")
 
     def query(self, name, *args):
         """Call a size/count-returning entry point."""
-        return getattr(self._load(), name)(*args)
+        return getattr(self._load(), name)(*self._marshal(name, args))
 
 
 class _Mux(_Lib):

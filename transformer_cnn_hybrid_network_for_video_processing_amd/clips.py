@@ -108,7 +108,7 @@ class ClipPipeline:
         with torch.cuda.stream(self.stream):
             s["dev_u8"].copy_(s["host"], non_blocking=True)
             s["y"].copy_(s["host_y"], non_blocking=True)
-            lib.call("hyb_frames_u8hwc_to_f32chw", s["dev_u8"].data_ptr(), s["x"].data_ptr(), B * T, H, W, C, self.stream.cuda_stream)
+            lib.call("hyb_frames_u8hwc_to_f32chw", s["dev_u8"], s["x"], B * T, H, W, C, self.stream.cuda_stream)
             s["ready"].record(self.stream)
 
     def __iter__(self):

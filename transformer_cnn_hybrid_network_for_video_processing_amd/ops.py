@@ -1,6 +1,8 @@
 """The hot path as custom torch operators: ``torch.ops.hybrid.*`` over the C ABI of include/hybrid_hip.h.
 
-Every operator enqueues HIP kernels on torch's current stream through ctypes; tensors only provide device memory.
+Every operator enqueues HIP kernels on torch's current stream through ctypes; tensors only provide device memory, and
+``lib.call`` takes the tensors themselves for pointer parameters: it holds them until the C function has returned and refuses
+a non-contiguous one (_lib.py), so a call site writes ``weight.contiguous()`` where it needs a copy and never ``.data_ptr()``.
 Forward operators return the tensors their backward needs as extra outputs; each backward is itself an operator
 (``hybrid::*_bwd``), so the whole path is visible to the dispatcher, has fake (meta) implementations for shape inference
 (``torch.library.register_fake``) and passes ``torch.library.opcheck``.  There is no eager/CPU implementation behind them:
@@ -24,6 +26,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::cast, hybrid::nchw_to_nhwc, hybrid::nhwc_to_nchw                     layout / dtype glue for standalone module use
     hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
 """
+import ctypes
 import functools
 import os
 from typing import List, Optional, Sequence, Tuple
@@ -31,7 +34,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from ._lib import HYB_BF16, HYB_F32, HYB_F32X3, HYB_H_BF16, lib, ptr_array
+from ._lib import HYB_BF16, HYB_F32, HYB_F32X3, HYB_H_BF16, lib
 
 _TORCH_DTYPE = {HYB_F32: torch.float32, HYB_BF16: torch.bfloat16, HYB_F32X3: torch.float32}
 _LIB = torch.library.Library("hybrid", "DEF")
@@ -46,6 +49,8 @@ def _define(name, schema, impl, fake, autograd=None):
     torch.library.register_fake("hybrid::" + name, fake)
     if autograd is not None:
         _LIB.impl(name, autograd, "Autograd")
+
+
 _SEED_COUNTER = [0]
 _SEED_MASK = 0x7FFFFFFFFFFFFFFF          # operator schemas carry ints as int64
 
@@ -88,7 +93,6 @@ def _ws(nbytes, device):
 def _query(name, *args):
     """Size queries are pure host functions of their integer arguments: ask the library once per shape.  A tuple argument is
     passed as a C int array."""
-    import ctypes
     return lib.query(name, *[(ctypes.c_int * len(a))(*a) if isinstance(a, tuple) else a for a in args])
 
 
@@ -123,10 +127,6 @@ def step_counter():
     return _STEP_COUNTER[0]
 
 
-def _opt_ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def check_mask(mask, B, S, device):
     """The reference applies ``masked_fill(mask.repeat(H,1,1) == 0, -1e9)`` to scores [B*H,S,S] (src L54-55, L77-78): the mask
     must have B leading entries and broadcast to [S,S].  Returns fp32 [B,S,S] contiguous on the device, or raises like torch."""
@@ -150,7 +150,7 @@ def nchw_to_nhwc_op(x: Tensor, dt: int, cp: int) -> Tensor:
     x = x.contiguous().float()
     N, C, H, W = x.shape
     out = torch.empty(N, H, W, cp, dtype=_TORCH_DTYPE[dt], device=x.device)
-    lib.call("hyb_nchw_to_nhwc", dt, x.data_ptr(), out.data_ptr(), N, C, H, W, cp, _stream())
+    lib.call("hyb_nchw_to_nhwc", dt, x, out, N, C, H, W, cp, _stream())
     return out
 
 
@@ -164,23 +164,13 @@ def nhwc_to_nchw_op(x: Tensor, dt: int, C: int) -> Tensor:
     x = x.contiguous()
     N, H, W, cp = x.shape
     out = torch.empty(N, C, H, W, dtype=torch.float32, device=x.device)
-    lib.call("hyb_nhwc_to_nchw", dt, x.data_ptr(), out.data_ptr(), N, C, H, W, cp, _stream())
+    lib.call("hyb_nhwc_to_nchw", dt, x, out, N, C, H, W, cp, _stream())
     return out
 
 
 def nhwc_to_nchw_fake(x, dt, C):
     N, H, W, cp = x.shape
     return x.new_empty((N, C, H, W), dtype=torch.float32)
-
-
-
-
-
-
-
-
-
-
 
 
 def nchw_to_nhwc(x, dt, cp):
@@ -198,19 +188,15 @@ def cast_op(x: Tensor, dt: int, to_t: bool) -> Tensor:
     if to_t:
         x = x.float()
         out = torch.empty(x.shape, dtype=_TORCH_DTYPE[dt], device=x.device)
-        lib.call("hyb_cast_from_f32", dt, x.data_ptr(), out.data_ptr(), x.numel(), _stream())
+        lib.call("hyb_cast_from_f32", dt, x, out, x.numel(), _stream())
     else:
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        lib.call("hyb_cast_to_f32", dt, x.data_ptr(), out.data_ptr(), x.numel(), _stream())
+        lib.call("hyb_cast_to_f32", dt, x, out, x.numel(), _stream())
     return out
 
 
 def cast_fake(x, dt, to_t):
     return x.new_empty(x.shape, dtype=_TORCH_DTYPE[dt] if to_t else torch.float32)
-
-
-
-
 
 
 def to_compute(x, dt):
@@ -264,11 +250,9 @@ def convstage_op(x: Tensor, weight: Tensor, gamma: Tensor, beta: Tensor, running
     mean_invstd = torch.empty(2, Cop, dtype=torch.float32, device=dev)
     ws = _ws(_query("hyb_convstage_fwd_workspace", dt, int(first), Cip, Cop), dev)
     packed_bwd = torch.empty(_query("hyb_convstage_packed_bwd_elems", int(first), Cip, Cop), dtype=tdt, device=dev)
-    lib.call("hyb_convstage_fwd", dt, int(first), x.data_ptr(), weight.contiguous().data_ptr(), gamma.contiguous().data_ptr(),
-             beta.contiguous().data_ptr(), running_mean.contiguous().data_ptr(), running_var.contiguous().data_ptr(), None,
-             int(training), float(momentum), float(eps), N, H, W, Ci, Cip, Co, Cop, None if first else y_raw.data_ptr(), pooled.data_ptr(),
-             scale_shift.data_ptr(), mean_invstd.data_ptr(), packed_bwd.data_ptr(), running_out.data_ptr() if training else None,
-             ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_convstage_fwd", dt, int(first), x, weight.contiguous(), gamma.contiguous(), beta.contiguous(), running_mean.contiguous(),
+             running_var.contiguous(), None, int(training), float(momentum), float(eps), N, H, W, Ci, Cip, Co, Cop, None if first else y_raw, pooled,
+             scale_shift, mean_invstd, packed_bwd, running_out if training else None, ws, ws.numel(), _stream())
     if training and not track:
         running_out = running_out.new_empty((0,))
     return pooled, y_raw, scale_shift, mean_invstd, packed_bwd, running_out
@@ -297,11 +281,9 @@ def convstage_bwd_op(dpooled: Tensor, x: Tensor, y_raw: Tensor, pooled: Optional
     dgamma = torch.empty(Co, dtype=torch.float32, device=dev)
     dbeta = torch.empty(Co, dtype=torch.float32, device=dev)
     ws = _ws(_query("hyb_convstage_bwd_workspace", dt, int(first), N, H, W, Cip, Cop), dev)
-    lib.call("hyb_convstage_bwd", dt, int(first), dpooled.data_ptr(), x.data_ptr(), None if first else y_raw.data_ptr(),
-             None if (first or pooled is None) else pooled.contiguous().data_ptr(), weight.contiguous().data_ptr(),
-             gamma.contiguous().data_ptr(), scale_shift.data_ptr(), mean_invstd.data_ptr(), int(training), N, H, W, Ci, Cip, Co, Cop,
-             None if first else dx.data_ptr(), dw.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-             packed_bwd.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_convstage_bwd", dt, int(first), dpooled, x.contiguous(), None if first else y_raw, None if (first or pooled is None) else pooled.contiguous(),
+             weight.contiguous(), gamma.contiguous(), scale_shift, mean_invstd, int(training), N, H, W, Ci, Cip, Co, Cop, None if first else dx,
+             dw, dgamma, dbeta, packed_bwd, ws, ws.numel(), _stream())
     return dx, dw, dgamma, dbeta
 
 
@@ -309,10 +291,6 @@ def convstage_bwd_fake(dpooled, x, y_raw, pooled, weight, gamma, scale_shift, me
     N, H, W, Ci, Cip, Co, Cop = _convstage_dims(x, weight, first)
     return (x.new_empty((0,) if first else (N, H, W, Cip), dtype=_TORCH_DTYPE[dt]), torch.empty_like(weight, memory_format=torch.contiguous_format),
             x.new_empty((Co,), dtype=torch.float32), x.new_empty((Co,), dtype=torch.float32))
-
-
-
-
 
 
 def convstage(x, weight, gamma, beta, running_mean, running_var, num_batches_tracked, training, momentum, eps, dt, first, commit=None):
@@ -358,9 +336,8 @@ def token_op(x: Tensor, weight: Tensor, bias: Optional[Tensor], dt: int) -> Tupl
     feat = torch.empty(N, Cp, dtype=_TORCH_DTYPE[dt], device=dev)
     tok = torch.empty(N, d, dtype=_TORCH_DTYPE[dt], device=dev)
     st = _stream()
-    lib.call("hyb_gap_fwd", dt, x.data_ptr(), feat.data_ptr(), N, Hh * Ww, Cp, st)
-    lib.call("hyb_linear_fwd", dt, feat.data_ptr(), Cp, weight.contiguous().data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-             tok.data_ptr(), N, d, C, 0, st)
+    lib.call("hyb_gap_fwd", dt, x, feat, N, Hh * Ww, Cp, st)
+    lib.call("hyb_linear_fwd", dt, feat, Cp, weight.contiguous(), bias.contiguous() if bias is not None else None, tok, N, d, C, 0, st)
     return tok, feat
 
 
@@ -379,10 +356,9 @@ def token_bwd_op(dtok: Tensor, feat: Tensor, weight: Tensor, Hh: int, Ww: int, h
     dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
     db = torch.empty(d if has_bias else 0, dtype=torch.float32, device=dev)
     st = _stream()
-    lib.call("hyb_linear_bwd", dt, feat.data_ptr(), Cp, weight.contiguous().data_ptr(), None, dtok.data_ptr(), dfeat.data_ptr(), 0, dw.data_ptr(),
-             db.data_ptr() if has_bias else None, N, d, C, 0, None, 0, st)
+    lib.call("hyb_linear_bwd", dt, feat, Cp, weight.contiguous(), None, dtok, dfeat, 0, dw, db if has_bias else None, N, d, C, 0, None, 0, st)
     dx = torch.empty(N, Hh, Ww, Cp, dtype=_TORCH_DTYPE[dt], device=dev)
-    lib.call("hyb_gap_bwd", dt, dfeat.data_ptr(), dx.data_ptr(), N, Hh * Ww, Cp, st)
+    lib.call("hyb_gap_bwd", dt, dfeat, dx, N, Hh * Ww, Cp, st)
     return dx, dw, db
 
 
@@ -390,10 +366,6 @@ def token_bwd_fake(dtok, feat, weight, Hh, Ww, has_bias, dt):
     N, Cp = feat.shape
     return (feat.new_empty((N, Hh, Ww, Cp)), torch.empty_like(weight, memory_format=torch.contiguous_format),
             feat.new_empty((weight.shape[0] if has_bias else 0,), dtype=torch.float32))
-
-
-
-
 
 
 def token(x, weight, bias, dt):
@@ -421,8 +393,7 @@ def encoder_op(x: Tensor, mask: Optional[Tensor], params: Sequence[Tensor], dt: 
     ps = [p.contiguous() for p in params]
     saved = _ws(_query("hyb_encoder_saved_bytes", dt, B, S, D, hid, L, H), dev)
     out = torch.empty(B, S, D, dtype=_TORCH_DTYPE[dt], device=dev)
-    lib.call("hyb_encoder_fwd", dt, x.data_ptr(), _opt_ptr(mask), ptr_array([p.data_ptr() for p in ps]), out.data_ptr(), saved.data_ptr(),
-             B, S, D, hid, L, H, float(attn_p), float(layer_p), seed, _opt_ptr(seed_inc), _stream())
+    lib.call("hyb_encoder_fwd", dt, x, mask, ps, out, saved, B, S, D, hid, L, H, float(attn_p), float(layer_p), seed, seed_inc, _stream())
     return out, saved
 
 
@@ -443,18 +414,13 @@ def encoder_bwd_op(dout: Tensor, mask: Optional[Tensor], params: Sequence[Tensor
     grads = [torch.empty_like(p) for p in ps]
     dx = torch.empty(B, S, D, dtype=_TORCH_DTYPE[dt], device=dev)
     ws = _ws(_query("hyb_encoder_workspace_bytes", dt, B, S, D, hid, L, H), dev)
-    lib.call("hyb_encoder_bwd", dt, dout.data_ptr(), _opt_ptr(mask), ptr_array([p.data_ptr() for p in ps]),
-             ptr_array([g.data_ptr() for g in grads]), saved.data_ptr(), dx.data_ptr(), B, S, D, hid, L, H, float(attn_p),
-             float(layer_p), seed, _opt_ptr(seed_inc), ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_encoder_bwd", dt, dout, mask, ps, grads, saved, dx, B, S, D, hid, L, H, float(attn_p), float(layer_p), seed, seed_inc, ws,
+             ws.numel(), _stream())
     return [dx] + grads
 
 
 def encoder_bwd_fake(dout, mask, params, saved, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
     return [torch.empty_like(dout, memory_format=torch.contiguous_format)] + [torch.empty_like(p, memory_format=torch.contiguous_format) for p in params]
-
-
-
-
 
 
 def encoder(x, mask, params, dt, hid, L, H, attn_p, layer_p, seed):
@@ -479,15 +445,13 @@ def mha_op(q_in: Tensor, k_in: Tensor, v_in: Tensor, mask: Optional[Tensor], par
     probs = torch.empty(B * H, S, 2, dtype=torch.float32, device=dev)       # softmax row statistics (max, sum)
     st = _stream()
     for src, W_, b_, dst in ((q_in, ps[0], ps[1], q), (k_in, ps[2], ps[3], k), (v_in, ps[4], ps[5], v)):
-        lib.call("hyb_linear_fwd", dt, src.data_ptr(), D, W_.data_ptr(), b_.data_ptr(), dst.data_ptr(), M, D, D, 1, st)
+        lib.call("hyb_linear_fwd", dt, src, D, W_, b_, dst, M, D, D, 1, st)
     if S > 64:           # probs then holds the log-sum-exp per (clip, head, query) in its first B*H*S floats
         ws = _ws(_query("hyb_attention_long_workspace", dt, B, S, D, H), dev)
-        lib.call("hyb_attention_long_fwd", dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), D, _opt_ptr(mask), a.data_ptr(), probs.data_ptr(), B, S, D, H,
-                 float(p_drop), seed, None, ws.data_ptr(), ws.numel(), st)
+        lib.call("hyb_attention_long_fwd", dt, q, k, v, D, mask, a, probs, B, S, D, H, float(p_drop), seed, None, ws, ws.numel(), st)
     else:
-        lib.call("hyb_attention_fwd", dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), _opt_ptr(mask), a.data_ptr(),
-                 probs.data_ptr(), B, S, D, H, float(p_drop), seed, st)
-    lib.call("hyb_linear_fwd", dt, a.data_ptr(), D, ps[6].data_ptr(), ps[7].data_ptr(), out.data_ptr(), M, D, D, 0, st)
+        lib.call("hyb_attention_fwd", dt, q, k, v, mask, a, probs, B, S, D, H, float(p_drop), seed, st)
+    lib.call("hyb_linear_fwd", dt, a, D, ps[6], ps[7], out, M, D, D, 0, st)
     return out, q, k, v, a, probs
 
 
@@ -509,27 +473,20 @@ def mha_bwd_op(dout: Tensor, q_in: Tensor, k_in: Tensor, v_in: Tensor, mask: Opt
     grads = [torch.empty_like(p) for p in ps]
     da, dq, dk, dv, dqi, dki, dvi = (torch.empty(B, S, D, dtype=tdt, device=dev) for _ in range(7))
     ws = _ws(M * D * 4, dev)
-    lib.call("hyb_linear_bwd", dt, a.data_ptr(), D, ps[6].data_ptr(), None, dout.data_ptr(), da.data_ptr(), 0, grads[6].data_ptr(),
-             grads[7].data_ptr(), M, D, D, 0, None, 0, st)
+    lib.call("hyb_linear_bwd", dt, a, D, ps[6], None, dout, da, 0, grads[6], grads[7], M, D, D, 0, None, 0, st)
     if S > 64:
         lws = _ws(_query("hyb_attention_long_workspace", dt, B, S, D, H), dev)
-        lib.call("hyb_attention_long_bwd", dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), D, _opt_ptr(mask), a.data_ptr(), probs.data_ptr(), da.data_ptr(),
-                 dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), D, B, S, D, H, float(p_drop), seed, None, lws.data_ptr(), lws.numel(), st)
+        lib.call("hyb_attention_long_bwd", dt, q, k, v, D, mask, a, probs, da, dq, dk, dv, D, B, S, D, H, float(p_drop), seed, None, lws,
+                 lws.numel(), st)
     else:
-        lib.call("hyb_attention_bwd", dt, q.data_ptr(), k.data_ptr(), v.data_ptr(), _opt_ptr(mask), probs.data_ptr(), da.data_ptr(), dq.data_ptr(),
-                 dk.data_ptr(), dv.data_ptr(), B, S, D, H, float(p_drop), seed, st)
+        lib.call("hyb_attention_bwd", dt, q, k, v, mask, probs, da, dq, dk, dv, B, S, D, H, float(p_drop), seed, st)
     for src, y, dy, dsrc, iw in ((q_in, q, dq, dqi, 0), (k_in, k, dk, dki, 2), (v_in, v, dv, dvi, 4)):
-        lib.call("hyb_linear_bwd", dt, src.contiguous().data_ptr(), D, ps[iw].data_ptr(), y.data_ptr(), dy.data_ptr(), dsrc.data_ptr(), 0,
-                 grads[iw].data_ptr(), grads[iw + 1].data_ptr(), M, D, D, 1, ws.data_ptr(), ws.numel(), st)
+        lib.call("hyb_linear_bwd", dt, src.contiguous(), D, ps[iw], y, dy, dsrc, 0, grads[iw], grads[iw + 1], M, D, D, 1, ws, ws.numel(), st)
     return [dqi, dki, dvi] + grads
 
 
 def mha_bwd_fake(dout, q_in, k_in, v_in, mask, q, k, v, a, probs, params, dt, H, p_drop, seed):
     return [torch.empty_like(q) for _ in range(3)] + [torch.empty_like(p, memory_format=torch.contiguous_format) for p in params]
-
-
-
-
 
 
 def mha(q, k, v, mask, params, dt, H, p_drop, seed):
@@ -546,8 +503,7 @@ def head_op(x: Tensor, weight: Tensor, bias: Optional[Tensor], dt: int) -> Tenso
     B, S, D = x.shape
     C = weight.shape[0]
     logits = torch.empty(B, C, dtype=torch.float32, device=x.device)
-    lib.call("hyb_head_fwd", dt, x.data_ptr(), weight.contiguous().data_ptr(), bias.contiguous().data_ptr() if bias is not None else None,
-             logits.data_ptr(), B, S, D, C, _stream())
+    lib.call("hyb_head_fwd", dt, x, weight.contiguous(), bias.contiguous() if bias is not None else None, logits, B, S, D, C, _stream())
     return logits
 
 
@@ -563,8 +519,7 @@ def head_bwd_op(dlogits: Tensor, x: Tensor, weight: Tensor, has_bias: bool, dt: 
     dx = torch.empty_like(x)
     dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
     db = torch.empty(C if has_bias else 0, dtype=torch.float32, device=x.device)
-    lib.call("hyb_head_bwd", dt, x.data_ptr(), weight.contiguous().data_ptr(), dlogits.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-             db.data_ptr() if has_bias else None, B, S, D, C, _stream())
+    lib.call("hyb_head_bwd", dt, x, weight.contiguous(), dlogits, dx, dw, db if has_bias else None, B, S, D, C, _stream())
     return dx, dw, db
 
 
@@ -573,51 +528,8 @@ def head_bwd_fake(dlogits, x, weight, has_bias, dt):
             x.new_empty((weight.shape[0] if has_bias else 0,), dtype=torch.float32))
 
 
-
-
-
-
 def head(x, weight, bias, dt):
     return torch.ops.hybrid.head(x, weight, bias, dt)
-
-
-def cross_entropy_op(logits: Tensor, target: Tensor) -> Tensor:
-    _require_cuda(logits, target)
-    if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
-        raise ValueError(f"expected logits [B,C] and class indices [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
-    logits = logits.contiguous().float()
-    target = target.contiguous().to(torch.int64)
-    B, C = logits.shape
-    loss = torch.empty((), dtype=torch.float32, device=logits.device)
-    lib.call("hyb_cross_entropy_fwd", logits.data_ptr(), target.data_ptr(), loss.data_ptr(), B, C, _stream())
-    return loss
-
-
-def cross_entropy_fake(logits, target):
-    return logits.new_empty((), dtype=torch.float32)
-
-
-def cross_entropy_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor) -> Tensor:
-    _require_cuda(dloss, logits)
-    logits = logits.contiguous().float()
-    target = target.contiguous().to(torch.int64)
-    B, C = logits.shape
-    dl = dloss.contiguous().float().reshape(1)
-    dlogits = torch.empty_like(logits)
-    lib.call("hyb_cross_entropy_bwd", logits.data_ptr(), target.data_ptr(), dl.data_ptr(), dlogits.data_ptr(), B, C, _stream())
-    return dlogits
-
-
-def cross_entropy_bwd_fake(dloss, logits, target):
-    return logits.new_empty(logits.shape, dtype=torch.float32)
-
-
-
-
-
-
-def cross_entropy(logits, target):
-    return torch.ops.hybrid.cross_entropy(logits, target)
 
 
 def _ce_weight(weight, C, device):
@@ -634,43 +546,68 @@ def _ce_weight(weight, C, device):
     return weight.contiguous()
 
 
-def cross_entropy_opts_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
-                          label_smoothing: float) -> Tensor:
-    """Mean cross-entropy with class weights, label smoothing and an ignored class index (hyb_cross_entropy_opts_fwd): the sum of the kept
-    clips' terms over the sum of their target weights, torch.nn.functional.cross_entropy's "mean"."""
+def _ce_opts(opts, C, device):
+    """(weight, ignore_index, has_ignore, label_smoothing) as the hyb_*_opts_* entry points take them behind the target; () stays ()."""
+    return (_ce_weight(opts[0], C, device), int(opts[1]), int(opts[2]), float(opts[3])) if opts else ()
+
+
+def _cross_entropy_fwd(logits, target, opts):
+    """opts (): hyb_cross_entropy_fwd; opts = (weight, ignore_index, has_ignore, label_smoothing): hyb_cross_entropy_opts_fwd, the same call
+    with the loss options behind the target."""
     _require_cuda(logits, target)
     if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
         raise ValueError(f"expected logits [B,C] and class indices [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
     logits = logits.contiguous().float()
     target = target.contiguous().to(torch.int64)
     B, C = logits.shape
-    weight = _ce_weight(weight, C, logits.device)
+    opts = _ce_opts(opts, C, logits.device)
     loss = torch.empty((), dtype=torch.float32, device=logits.device)
-    lib.call("hyb_cross_entropy_opts_fwd", logits.data_ptr(), target.data_ptr(), _opt_ptr(weight), int(ignore_index), int(has_ignore),
-             float(label_smoothing), loss.data_ptr(), B, C, _stream())
+    lib.call("hyb_cross_entropy_opts_fwd" if opts else "hyb_cross_entropy_fwd", logits, target, *opts, loss, B, C, _stream())
     return loss
 
 
-def cross_entropy_opts_fake(logits, target, weight, ignore_index, has_ignore, label_smoothing):
-    return logits.new_empty((), dtype=torch.float32)
-
-
-def cross_entropy_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
-                              label_smoothing: float) -> Tensor:
+def _cross_entropy_bwd(dloss, logits, target, opts):
     _require_cuda(dloss, logits)
     logits = logits.contiguous().float()
     target = target.contiguous().to(torch.int64)
     B, C = logits.shape
-    weight = _ce_weight(weight, C, logits.device)
+    opts = _ce_opts(opts, C, logits.device)
     dl = dloss.contiguous().float().reshape(1)
     dlogits = torch.empty_like(logits)
-    lib.call("hyb_cross_entropy_opts_bwd", logits.data_ptr(), target.data_ptr(), _opt_ptr(weight), int(ignore_index), int(has_ignore),
-             float(label_smoothing), dl.data_ptr(), dlogits.data_ptr(), B, C, _stream())
+    lib.call("hyb_cross_entropy_opts_bwd" if opts else "hyb_cross_entropy_bwd", logits, target, *opts, dl, dlogits, B, C, _stream())
     return dlogits
 
 
-def cross_entropy_opts_bwd_fake(dloss, logits, target, weight, ignore_index, has_ignore, label_smoothing):
+def cross_entropy_op(logits: Tensor, target: Tensor) -> Tensor:
+    return _cross_entropy_fwd(logits, target, ())
+
+
+def cross_entropy_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor) -> Tensor:
+    return _cross_entropy_bwd(dloss, logits, target, ())
+
+
+def cross_entropy_opts_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
+                          label_smoothing: float) -> Tensor:
+    """Mean cross-entropy with class weights, label smoothing and an ignored class index (hyb_cross_entropy_opts_fwd): the sum of the kept
+    clips' terms over the sum of their target weights, torch.nn.functional.cross_entropy's "mean"."""
+    return _cross_entropy_fwd(logits, target, (weight, ignore_index, has_ignore, label_smoothing))
+
+
+def cross_entropy_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
+                              label_smoothing: float) -> Tensor:
+    return _cross_entropy_bwd(dloss, logits, target, (weight, ignore_index, has_ignore, label_smoothing))
+
+
+def cross_entropy_fake(logits, target, *opts):
+    return logits.new_empty((), dtype=torch.float32)
+
+
+def cross_entropy_bwd_fake(dloss, logits, target, *opts):
     return logits.new_empty(logits.shape, dtype=torch.float32)
+
+
+def cross_entropy(logits, target):
+    return torch.ops.hybrid.cross_entropy(logits, target)
 
 
 def cross_entropy_opts(logits, target, weight=None, ignore_index=None, label_smoothing=0.0):
@@ -683,11 +620,8 @@ def cross_entropy_opts(logits, target, weight=None, ignore_index=None, label_smo
 # Same kernels as the stage operators above, chained in C: a training step is three operator calls each way, which keeps the
 # host (Python dispatch ~50 us per operator call) off the critical path.
 # ---------------------------------------------------------------------------------------------
-import ctypes as _ct
-
-
 def _int_array(vals):
-    return (_ct.c_int * len(vals))(*vals)
+    return (ctypes.c_int * len(vals))(*vals)
 
 
 def _backbone_geometry(x, weights):
@@ -748,14 +682,12 @@ def _backbone_impl(x, weights, gammas, betas, running_means, running_vars, nbts,
         pk = torch.empty(_query("hyb_convstage_packed_bwd_elems", int(s == 0), Cip, Cop), dtype=tdt, device=dev)
         ro = torch.empty((2, Co) if training and not inplace else (0,), dtype=torch.float32, device=dev)
         per_stage.append((y_raw, pooled, ss, mi, pk, ro))
-        params += [weights[s].contiguous().data_ptr(), gammas[s].contiguous().data_ptr(), betas[s].contiguous().data_ptr(),
-                   running_means[s].contiguous().data_ptr(), running_vars[s].contiguous().data_ptr()]
-        outs += [y_raw.data_ptr() if y_raw.numel() else None, pooled.data_ptr(), ss.data_ptr(), mi.data_ptr(), pk.data_ptr(),
-                 ro.data_ptr() if training and not inplace else None]
+        params += [t.contiguous() for t in (weights[s], gammas[s], betas[s], running_means[s], running_vars[s])]
+        outs += [y_raw if y_raw.numel() else None, pooled, ss, mi, pk, ro if training and not inplace else None]
     ch = _int_array(chans)
     ws = _ws(_query("hyb_backbone_fwd_workspace", dt, S, tuple(chans)), dev)
-    lib.call("hyb_backbone_fwd", dt, S, ch, x.data_ptr(), ptr_array(params), ptr_array([t.data_ptr() for t in nbts]) if inplace else None,
-             int(training), float(momentum), float(eps), N, H, W, ptr_array(outs), ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_backbone_fwd", dt, S, ch, x, params, nbts if inplace else None, int(training), float(momentum), float(eps), N, H, W, outs, ws,
+             ws.numel(), _stream())
     res = [pooled]
     for s, (y_raw, p, ss, mi, pk, ro) in enumerate(per_stage):
         res += [y_raw] + ([p] if s < S - 1 else []) + [ss, mi, pk, ro]
@@ -804,19 +736,18 @@ def backbone_bwd_op(dpooled: Tensor, pooled: Tensor, x: Tensor, weights: Sequenc
     N, H, W, chans, dims = _backbone_geometry(x, weights)
     dev = x.device
     dpooled = dpooled.contiguous()
-    grads, gptr, pptr, sptr = [], [], [], []
+    grads, pptr, sptr = [], [], []
     for s in range(S):
         dw = torch.empty_like(weights[s], memory_format=torch.contiguous_format)
         dg = torch.empty(chans[s + 1], dtype=torch.float32, device=dev)
         db = torch.empty(chans[s + 1], dtype=torch.float32, device=dev)
         grads += [dw, dg, db]
-        gptr += [dw.data_ptr(), dg.data_ptr(), db.data_ptr()]
-        pptr += [weights[s].contiguous().data_ptr(), gammas[s].contiguous().data_ptr()]
+        pptr += [weights[s].contiguous(), gammas[s].contiguous()]
         sv = saved[5 * s:5 * s + 5]
-        sptr += [sv[0].data_ptr() if sv[0].numel() else None, None if s == 0 else sv[1].data_ptr(), sv[2].data_ptr(), sv[3].data_ptr(), sv[4].data_ptr()]
+        sptr += [sv[0] if sv[0].numel() else None, None if s == 0 else sv[1], sv[2], sv[3], sv[4]]
     ws = _ws(_query("hyb_backbone_bwd_workspace", dt, S, tuple(chans), N, H, W), dev)
-    lib.call("hyb_backbone_bwd", dt, S, _int_array(chans), dpooled.data_ptr(), pooled.contiguous().data_ptr(), x.data_ptr(), ptr_array(pptr), ptr_array(sptr), int(training),
-             N, H, W, ptr_array(gptr), ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_backbone_bwd", dt, S, _int_array(chans), dpooled, pooled.contiguous(), x.contiguous(), pptr, sptr, int(training), N, H, W, grads, ws,
+             ws.numel(), _stream())
     return grads
 
 
@@ -826,10 +757,6 @@ def backbone_bwd_fake(dpooled, pooled, x, weights, gammas, saved, training, dt):
         res += [torch.empty_like(w, memory_format=torch.contiguous_format), x.new_empty((w.shape[0],), dtype=torch.float32),
                 x.new_empty((w.shape[0],), dtype=torch.float32)]
     return res
-
-
-
-
 
 
 def backbone(x, stages, training, dt):
@@ -894,9 +821,8 @@ def convstage_infer_op(x: Tensor, weight: Tensor, gamma: Tensor, beta: Tensor, r
     dev = x.device
     pooled = torch.empty(N, H // 2, W // 2, Cop, dtype=_TORCH_DTYPE[dt], device=dev)
     ws = _ws(_query("hyb_convstage_infer_workspace", dt, int(first), N, H, W, Cip, Cop), dev)
-    lib.call("hyb_convstage_infer", dt, int(first), x.data_ptr(), weight.contiguous().data_ptr(), gamma.contiguous().data_ptr(),
-             beta.contiguous().data_ptr(), running_mean.contiguous().data_ptr(), running_var.contiguous().data_ptr(), float(eps), N, H, W, Ci, Cip,
-             Co, Cop, pooled.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_convstage_infer", dt, int(first), x, weight.contiguous(), gamma.contiguous(), beta.contiguous(), running_mean.contiguous(),
+             running_var.contiguous(), float(eps), N, H, W, Ci, Cip, Co, Cop, pooled, ws, ws.numel(), _stream())
     return pooled
 
 
@@ -920,13 +846,9 @@ def backbone_infer_op(x: Tensor, weights: Sequence[Tensor], gammas: Sequence[Ten
     dev = x.device
     h, w_, _, Cop = dims[-1]
     pooled = torch.empty(N, h // 2, w_ // 2, Cop, dtype=_TORCH_DTYPE[dt], device=dev)
-    keep, params = [], []
-    for s in range(S):
-        ts = [t.contiguous() for t in (weights[s], gammas[s], betas[s], running_means[s], running_vars[s])]
-        keep += ts
-        params += [t.data_ptr() for t in ts]
+    params = [t.contiguous() for s in range(S) for t in (weights[s], gammas[s], betas[s], running_means[s], running_vars[s])]
     ws = _ws(_query("hyb_backbone_infer_workspace", dt, S, tuple(chans), N, H, W), dev)
-    lib.call("hyb_backbone_infer", dt, S, _int_array(chans), x.data_ptr(), ptr_array(params), float(eps), N, H, W, pooled.data_ptr(), ws.data_ptr(),
+    lib.call("hyb_backbone_infer", dt, S, _int_array(chans), x, params, float(eps), N, H, W, pooled, ws,
              ws.numel(), _stream())
     return pooled
 
@@ -955,77 +877,6 @@ def _check_h_dtype(h, dt):
         raise ValueError("HYB_H_BF16 goes with an fp32-storage temporal part ('fp32' / 'bf16x3')")
     if h.dtype != want:
         raise TypeError(f"the pooled map must be {want} for this compute dtype, got {h.dtype}")
-
-
-def temporal_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor, mask: Optional[Tensor],
-                B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """h [B*S, Hh, Ww, Cp] T (last pooled map) -> (logits [B, classes] fp32, feat, enc_saved, enc_out); the last three are saved for backward."""
-    _require_cuda(h, token_w, head_w, *enc_params)
-    _check_h_dtype(h, dt)
-    h = h.contiguous()
-    N, Hh, Ww, Cp = h.shape
-    S = N // B
-    D, C = token_w.shape
-    classes = head_w.shape[0]
-    _check_attention_limits(S, D, H)
-    dev, tdt = h.device, _TORCH_DTYPE[dt & 0xff]
-    feat = torch.empty(N, Cp, dtype=tdt, device=dev)
-    tok = torch.empty(B, S, D, dtype=tdt, device=dev)
-    enc_out = torch.empty(B, S, D, dtype=tdt, device=dev)
-    saved = _ws(_query("hyb_encoder_saved_bytes", dt & 0xff, B, S, D, hid, L, H), dev)
-    logits = torch.empty(B, classes, dtype=torch.float32, device=dev)
-    ps = [p.contiguous() for p in enc_params]
-    lib.call("hyb_temporal_fwd", dt, h.data_ptr(), token_w.contiguous().data_ptr(), token_b.contiguous().data_ptr(), ptr_array([p.data_ptr() for p in ps]),
-             head_w.contiguous().data_ptr(), head_b.contiguous().data_ptr(), _opt_ptr(mask), feat.data_ptr(), tok.data_ptr(), saved.data_ptr(),
-             enc_out.data_ptr(), logits.data_ptr(), B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed,
-             _opt_ptr(seed_inc), _stream())
-    return logits, feat, saved, enc_out
-
-
-def temporal_fake(h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
-    N, Hh, Ww, Cp = h.shape
-    S, D = N // B, token_w.shape[0]
-    tdt = _TORCH_DTYPE[dt & 0xff]
-    return (h.new_empty((B, head_w.shape[0]), dtype=torch.float32), h.new_empty((N, Cp), dtype=tdt),
-            h.new_empty((max(_query("hyb_encoder_saved_bytes", dt & 0xff, B, S, D, hid, L, H), 256),), dtype=torch.uint8), h.new_empty((B, S, D), dtype=tdt))
-
-
-def temporal_bwd_op(dlogits: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
-                    saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
-                    seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """-> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
-    _require_cuda(dlogits, feat)
-    B, S, D = enc_out.shape
-    N, Cp = feat.shape
-    C = token_w.shape[1]
-    classes = head_w.shape[0]
-    dev, tdt = feat.device, _TORCH_DTYPE[dt & 0xff]
-    dlogits = dlogits.contiguous().float()
-    ps = [p.contiguous() for p in enc_params]
-    grads = [torch.empty_like(p) for p in ps]
-    dh = torch.empty(N, Hh, Ww, Cp, dtype=torch.bfloat16 if dt & HYB_H_BF16 else tdt, device=dev)
-    dtw = torch.empty_like(token_w, memory_format=torch.contiguous_format)
-    dtb = torch.empty(D, dtype=torch.float32, device=dev)
-    dhw = torch.empty_like(head_w, memory_format=torch.contiguous_format)
-    dhb = torch.empty(classes, dtype=torch.float32, device=dev)
-    ws = _ws(_query("hyb_temporal_bwd_workspace", dt & 0xff, B, S, Hh * Ww, Cp, D, hid, L, H), dev)
-    lib.call("hyb_temporal_bwd", dt, dlogits.data_ptr(), token_w.contiguous().data_ptr(), ptr_array([p.data_ptr() for p in ps]),
-             head_w.contiguous().data_ptr(), _opt_ptr(mask), feat.data_ptr(), saved.data_ptr(), enc_out.data_ptr(), dtw.data_ptr(), dtb.data_ptr(),
-             ptr_array([g.data_ptr() for g in grads]), dhw.data_ptr(), dhb.data_ptr(), dh.data_ptr(), B, S, Hh * Ww, C, Cp, D, hid, L, H, classes,
-             float(attn_p), float(layer_p), seed, _opt_ptr(seed_inc), ws.data_ptr(), ws.numel(), _stream())
-    return [dh, dtw, dtb, dhw, dhb] + grads
-
-
-def temporal_bwd_fake(dlogits, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
-    N, Cp = feat.shape
-    c = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
-    return [feat.new_empty((N, Hh, Ww, Cp), dtype=torch.bfloat16 if dt & HYB_H_BF16 else feat.dtype), c(token_w), feat.new_empty((token_w.shape[0],), dtype=torch.float32), c(head_w),
-            feat.new_empty((head_w.shape[0],), dtype=torch.float32)] + [c(p) for p in enc_params]
-
-
-
-
 
 
 _CE_SCRATCH = {}
@@ -1060,17 +911,11 @@ def prepare_ce_scratch(B, device, stream):
     return t
 
 
-def temporal_ce_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor, mask: Optional[Tensor],
-                   target: Tensor, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                   seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """hybrid::temporal + hybrid::cross_entropy in the same launches (hyb_temporal_ce_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
-    return _temporal_ce_fwd(None, h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def _temporal_ce_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc):
-    """ce None: hyb_temporal_ce_fwd; ce = (weight, ignore_index, has_ignore, label_smoothing): hyb_temporal_ce_opts_fwd, the same call with
-    the loss options behind the target."""
-    _require_cuda(h, token_w, head_w, target, *enc_params)
+def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc):
+    """The temporal part, one body for the three operators.  ce (): hyb_temporal_fwd; ce = (target,): hyb_temporal_ce_fwd, the loss in the
+    same launches; ce = (target, weight, ignore_index, has_ignore, label_smoothing): hyb_temporal_ce_opts_fwd, the same call with the loss
+    options behind the target.  -> (logits, feat, enc_saved, enc_out), behind the loss [] when there is one."""
+    _require_cuda(h, token_w, head_w, *ce[:1], *enc_params)
     _check_h_dtype(h, dt)
     h = h.contiguous()
     N, Hh, Ww, Cp = h.shape
@@ -1078,65 +923,35 @@ def _temporal_ce_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, 
     D, C = token_w.shape
     classes = head_w.shape[0]
     _check_attention_limits(S, D, H)
-    if target.dim() != 1 or target.shape[0] != B:
-        raise ValueError(f"expected class indices [B={B}], got {tuple(target.shape)}")
-    target = target.contiguous().to(torch.int64)
     dev, tdt = h.device, _TORCH_DTYPE[dt & 0xff]
+    if ce and (ce[0].dim() != 1 or ce[0].shape[0] != B):
+        raise ValueError(f"expected class indices [B={B}], got {tuple(ce[0].shape)}")
     feat = torch.empty(N, Cp, dtype=tdt, device=dev)
     tok = torch.empty(B, S, D, dtype=tdt, device=dev)
     enc_out = torch.empty(B, S, D, dtype=tdt, device=dev)
     saved = _ws(_query("hyb_encoder_saved_bytes", dt & 0xff, B, S, D, hid, L, H), dev)
     logits = torch.empty(B, classes, dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
     ps = [p.contiguous() for p in enc_params]
-    opts = ()
-    if ce is not None:
-        weight = _ce_weight(ce[0], classes, dev)              # (kept alive until the call below)
-        opts = (_opt_ptr(weight), int(ce[1]), int(ce[2]), float(ce[3]))
-    lib.call("hyb_temporal_ce_fwd" if ce is None else "hyb_temporal_ce_opts_fwd", dt, h.data_ptr(), token_w.contiguous().data_ptr(),
-             token_b.contiguous().data_ptr(), ptr_array([p.data_ptr() for p in ps]),
-             head_w.contiguous().data_ptr(), head_b.contiguous().data_ptr(), _opt_ptr(mask), target.data_ptr(), *opts, feat.data_ptr(), tok.data_ptr(),
-             saved.data_ptr(), enc_out.data_ptr(), logits.data_ptr(), loss.data_ptr(), _ce_scratch(B, dev).data_ptr(), B, S, Hh * Ww, C, Cp, D, hid, L, H,
-             classes, float(attn_p), float(layer_p), seed, _opt_ptr(seed_inc), _stream())
-    return loss, logits, feat, saved, enc_out
+    name, loss_in, loss_out = "hyb_temporal_fwd", (), ()
+    if ce:
+        name = "hyb_temporal_ce_opts_fwd" if ce[1:] else "hyb_temporal_ce_fwd"
+        loss_in = (ce[0].contiguous().to(torch.int64), *_ce_opts(ce[1:], classes, dev))
+        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
+    lib.call(name, dt, h, token_w.contiguous(), token_b.contiguous(), ps, head_w.contiguous(), head_b.contiguous(), mask, *loss_in, feat, tok, saved,
+             enc_out, logits, *loss_out, B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, _stream())
+    return (*loss_out[:1], logits, feat, saved, enc_out)
 
 
-def temporal_ce_opts_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
-                        mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
-                        B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                        seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """hybrid::temporal + hybrid::cross_entropy_opts in the same launches (hyb_temporal_ce_opts_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
-    return _temporal_ce_fwd((weight, ignore_index, has_ignore, label_smoothing), h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt,
-                            hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def temporal_ce_opts_fake(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid,
-                          L, H, attn_p, layer_p, seed, seed_inc=None):
-    return temporal_ce_fake(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed)
-
-
-def temporal_ce_fake(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
-    return (h.new_empty((), dtype=torch.float32),) + temporal_fake(h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed)
-
-
-def temporal_ce_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor,
-                       mask: Optional[Tensor], feat: Tensor, saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int,
-                       attn_p: float, layer_p: float, seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """-> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]: hybrid::cross_entropy_bwd + hybrid::temporal_bwd in the same launches."""
-    return _temporal_ce_bwd(None, dloss, logits, target, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p,
-                            seed, seed_inc)
-
-
-def _temporal_ce_bwd(ce, dloss, logits, target, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed,
-                     seed_inc):
-    """ce as in _temporal_ce_fwd: hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd."""
-    _require_cuda(dloss, logits, feat)
+def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc):
+    """ce (): dout is dlogits, hyb_temporal_bwd; ce = (logits, target) + the loss options of _temporal_fwd, if any: dout is dloss,
+    hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
+    _require_cuda(dout, *ce[:1], feat)
     B, S, D = enc_out.shape
     N, Cp = feat.shape
     C = token_w.shape[1]
     classes = head_w.shape[0]
     dev, tdt = feat.device, _TORCH_DTYPE[dt & 0xff]
-    dl = dloss.contiguous().float().reshape(1)
+    dout = dout.contiguous().float()
     ps = [p.contiguous() for p in enc_params]
     grads = [torch.empty_like(p) for p in ps]
     dh = torch.empty(N, Hh, Ww, Cp, dtype=torch.bfloat16 if dt & HYB_H_BF16 else tdt, device=dev)
@@ -1145,35 +960,81 @@ def _temporal_ce_bwd(ce, dloss, logits, target, token_w, enc_params, head_w, mas
     dhw = torch.empty_like(head_w, memory_format=torch.contiguous_format)
     dhb = torch.empty(classes, dtype=torch.float32, device=dev)
     ws = _ws(_query("hyb_temporal_bwd_workspace", dt & 0xff, B, S, Hh * Ww, Cp, D, hid, L, H), dev)
-    opts = ()
-    if ce is not None:
-        weight = _ce_weight(ce[0], classes, dev)
-        opts = (_opt_ptr(weight), int(ce[1]), int(ce[2]), float(ce[3]))
-    lib.call("hyb_temporal_ce_bwd" if ce is None else "hyb_temporal_ce_opts_bwd", dt, dl.data_ptr(), logits.contiguous().data_ptr(),
-             target.contiguous().data_ptr(), *opts, token_w.contiguous().data_ptr(),
-             ptr_array([p.data_ptr() for p in ps]), head_w.contiguous().data_ptr(), _opt_ptr(mask), feat.data_ptr(), saved.data_ptr(), enc_out.data_ptr(),
-             dtw.data_ptr(), dtb.data_ptr(), ptr_array([g.data_ptr() for g in grads]), dhw.data_ptr(), dhb.data_ptr(), dh.data_ptr(), B, S, Hh * Ww, C, Cp,
-             D, hid, L, H, classes, float(attn_p), float(layer_p), seed, _opt_ptr(seed_inc), ws.data_ptr(), ws.numel(), _stream())
+    name, loss_in = "hyb_temporal_bwd", ()
+    if ce:
+        name = "hyb_temporal_ce_opts_bwd" if ce[2:] else "hyb_temporal_ce_bwd"
+        dout = dout.reshape(1)
+        loss_in = (ce[0].contiguous(), ce[1].contiguous(), *_ce_opts(ce[2:], classes, dev))
+    lib.call(name, dt, dout, *loss_in, token_w.contiguous(), ps, head_w.contiguous(), mask, feat, saved, enc_out, dtw, dtb, grads, dhw, dhb, dh,
+             B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, ws, ws.numel(), _stream())
     return [dh, dtw, dtb, dhw, dhb] + grads
+
+
+def temporal_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor, mask: Optional[Tensor],
+                B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
+                seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """h [B*S, Hh, Ww, Cp] T (last pooled map) -> (logits [B, classes] fp32, feat, enc_saved, enc_out); the last three are saved for backward."""
+    return _temporal_fwd((), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
+def temporal_ce_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor, mask: Optional[Tensor],
+                   target: Tensor, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
+                   seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """hybrid::temporal + hybrid::cross_entropy in the same launches (hyb_temporal_ce_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
+    return _temporal_fwd((target,), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
+def temporal_ce_opts_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
+                        mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
+                        B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
+                        seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """hybrid::temporal + hybrid::cross_entropy_opts in the same launches (hyb_temporal_ce_opts_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
+    return _temporal_fwd((target, weight, ignore_index, has_ignore, label_smoothing), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt,
+                         hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
+def temporal_bwd_op(dlogits: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
+                    saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
+                    seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
+    """-> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
+    return _temporal_bwd((), dlogits, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
+def temporal_ce_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor,
+                       mask: Optional[Tensor], feat: Tensor, saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int,
+                       attn_p: float, layer_p: float, seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
+    """hybrid::cross_entropy_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
+    return _temporal_bwd((logits, target), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p,
+                         seed, seed_inc)
 
 
 def temporal_ce_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
                             label_smoothing: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
                             saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
                             seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """-> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]: hybrid::cross_entropy_opts_bwd + hybrid::temporal_bwd in the same launches."""
-    return _temporal_ce_bwd((weight, ignore_index, has_ignore, label_smoothing), dloss, logits, target, token_w, enc_params, head_w, mask, feat, saved,
-                            enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+    """hybrid::cross_entropy_opts_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
+    return _temporal_bwd((logits, target, weight, ignore_index, has_ignore, label_smoothing), dloss, token_w, enc_params, head_w, mask, feat, saved,
+                         enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
 
 
-def temporal_ce_opts_bwd_fake(dloss, logits, target, weight, ignore_index, has_ignore, label_smoothing, token_w, enc_params, head_w, mask, feat, saved,
-                              enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
-    return temporal_bwd_fake(logits, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed)
+def _temporal_fake(n_loss, h, token_w, token_b, enc_params, head_w, head_b, mask, *rest, seed_inc=None):
+    """Fake of the three forward operators: rest = the n_loss loss arguments of the schema (0, 1 or 5), then B, dt, hid, L, H, ..."""
+    B, dt, hid, L, H = rest[n_loss:n_loss + 5]
+    N, Hh, Ww, Cp = h.shape
+    S, D = N // B, token_w.shape[0]
+    tdt = _TORCH_DTYPE[dt & 0xff]
+    out = (h.new_empty((B, head_w.shape[0]), dtype=torch.float32), h.new_empty((N, Cp), dtype=tdt),
+           h.new_empty((max(_query("hyb_encoder_saved_bytes", dt & 0xff, B, S, D, hid, L, H), 256),), dtype=torch.uint8), h.new_empty((B, S, D), dtype=tdt))
+    return (h.new_empty((), dtype=torch.float32), *out) if n_loss else out
 
 
-def temporal_ce_bwd_fake(dloss, logits, target, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed,
-                         seed_inc=None):
-    return temporal_bwd_fake(logits, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed)
+def _temporal_bwd_fake(n_loss, dout, *rest, seed_inc=None):
+    """Fake of the three backward operators: rest = the n_loss loss arguments of the schema (0, 2 or 6), then token_w, enc_params, ..."""
+    token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt = rest[n_loss:n_loss + 10]
+    N, Cp = feat.shape
+    c = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
+    return [feat.new_empty((N, Hh, Ww, Cp), dtype=torch.bfloat16 if dt & HYB_H_BF16 else feat.dtype), c(token_w),
+            feat.new_empty((token_w.shape[0],), dtype=torch.float32), c(head_w), feat.new_empty((head_w.shape[0],), dtype=torch.float32)] + [c(p) for p in enc_params]
 
 
 def temporal_ce(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed):
@@ -1352,32 +1213,26 @@ class _HeadFn(torch.autograd.Function):
 
 
 class _CrossEntropyFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target):
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(logits, target)
-        with _below_autograd():
-            return torch.ops.hybrid.cross_entropy(logits, target)
+    """hybrid::cross_entropy (has_ignore None: no loss options) and hybrid::cross_entropy_opts."""
 
-    @staticmethod
-    def backward(ctx, dloss):
-        logits, target = ctx.saved_tensors
-        return torch.ops.hybrid.cross_entropy_bwd(dloss, logits, target), None
-
-
-class _CrossEntropyOptsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, has_ignore, label_smoothing):
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(logits, target, weight)
-        ctx.cfg = (ignore_index, has_ignore, label_smoothing)
+        ctx.cfg = None if has_ignore is None else (ignore_index, has_ignore, label_smoothing)
         with _below_autograd():
+            if ctx.cfg is None:
+                return torch.ops.hybrid.cross_entropy(logits, target)
             return torch.ops.hybrid.cross_entropy_opts(logits, target, weight, ignore_index, has_ignore, label_smoothing)
 
     @staticmethod
     def backward(ctx, dloss):
         logits, target, weight = ctx.saved_tensors
-        return (torch.ops.hybrid.cross_entropy_opts_bwd(dloss, logits, target, weight, *ctx.cfg),) + (None,) * 5        # (no gradient for the class weights)
+        if ctx.cfg is None:
+            dlogits = torch.ops.hybrid.cross_entropy_bwd(dloss, logits, target)
+        else:
+            dlogits = torch.ops.hybrid.cross_entropy_opts_bwd(dloss, logits, target, weight, *ctx.cfg)
+        return (dlogits,) + (None,) * 5        # (no gradient for the class weights)
 
 
 class _BackboneFn(torch.autograd.Function):
@@ -1412,82 +1267,45 @@ class _BackboneFn(torch.autograd.Function):
 
 
 class _TemporalFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, h, token_w, token_b, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, *enc_params):
-        ctx.set_materialize_grads(False)
-        with _below_autograd():
-            logits, feat, saved, enc_out = torch.ops.hybrid.temporal(h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H,
-                                                                      attn_p, layer_p, seed, seed_inc)
-        ctx.seed_inc = seed_inc
-        if mask is None:
-            ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, *enc_params)
-        else:
-            ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, mask, *enc_params)
-        ctx.cfg = (mask is not None, h.shape[1], h.shape[2], dt, hid, L, H, attn_p, layer_p, seed)
-        ctx.mark_non_differentiable(feat, saved, enc_out)
-        return logits, feat, saved, enc_out
+    """hybrid::temporal (target None), hybrid::temporal_ce (has_ignore None: no loss options) and hybrid::temporal_ce_opts."""
 
-    @staticmethod
-    def backward(ctx, dlogits, *unused):
-        has_mask, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed = ctx.cfg
-        token_w, head_w, feat, saved, enc_out, *rest = ctx.saved_tensors
-        mask = rest.pop(0) if has_mask else None
-        g = torch.ops.hybrid.temporal_bwd(dlogits, token_w, rest, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed,
-                                          ctx.seed_inc)
-        return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 10 + tuple(g[5:])
-
-
-class _TemporalCeFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, h, token_w, token_b, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, *enc_params):
-        ctx.set_materialize_grads(False)
-        with _below_autograd():
-            loss, logits, feat, saved, enc_out = torch.ops.hybrid.temporal_ce(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid,
-                                                                              L, H, attn_p, layer_p, seed, seed_inc)
-        ctx.seed_inc = seed_inc
-        if mask is None:
-            ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, logits, target, *enc_params)
-        else:
-            ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, logits, target, mask, *enc_params)
-        ctx.cfg = (mask is not None, h.shape[1], h.shape[2], dt, hid, L, H, attn_p, layer_p, seed)
-        ctx.mark_non_differentiable(logits, feat, saved, enc_out)      # (logits: an output for the caller's metrics; the objective is the loss)
-        return loss, logits, feat, saved, enc_out
-
-    @staticmethod
-    def backward(ctx, dloss, *unused):
-        has_mask, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed = ctx.cfg
-        token_w, head_w, feat, saved, enc_out, logits, target, *rest = ctx.saved_tensors
-        mask = rest.pop(0) if has_mask else None
-        g = torch.ops.hybrid.temporal_ce_bwd(dloss, logits, target, token_w, rest, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p,
-                                             layer_p, seed, ctx.seed_inc)
-        return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 11 + tuple(g[5:])
-
-
-class _TemporalCeOptsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, token_w, token_b, head_w, head_b, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
                 layer_p, seed, seed_inc, *enc_params):
         ctx.set_materialize_grads(False)
+        tail = (B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
         with _below_autograd():
-            loss, logits, feat, saved, enc_out = torch.ops.hybrid.temporal_ce_opts(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight,
-                                                                                   ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
-                                                                                   layer_p, seed, seed_inc)
+            if target is None:
+                out = torch.ops.hybrid.temporal(h, token_w, token_b, enc_params, head_w, head_b, mask, *tail)
+            elif has_ignore is None:
+                out = torch.ops.hybrid.temporal_ce(h, token_w, token_b, enc_params, head_w, head_b, mask, target, *tail)
+            else:
+                out = torch.ops.hybrid.temporal_ce_opts(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, has_ignore,
+                                                        label_smoothing, *tail)
+        feat, saved, enc_out = out[-3:]
         ctx.seed_inc = seed_inc
-        opt = [t for t in (weight, mask) if t is not None]
-        ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, logits, target, *opt, *enc_params)
-        ctx.cfg = (weight is not None, mask is not None, ignore_index, has_ignore, label_smoothing, h.shape[1], h.shape[2], dt, hid, L, H, attn_p, layer_p,
-                   seed)
-        ctx.mark_non_differentiable(logits, feat, saved, enc_out)
-        return loss, logits, feat, saved, enc_out
+        opt = [t for t in (None if target is None else out[1], target, weight, mask) if t is not None]      # (out[1]: the logits behind the loss)
+        ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, *opt, *enc_params)
+        ctx.cfg = (target is not None, weight is not None, mask is not None, None if has_ignore is None else (ignore_index, has_ignore, label_smoothing),
+                   h.shape[1], h.shape[2], dt, hid, L, H, attn_p, layer_p, seed)
+        ctx.mark_non_differentiable(*out[1:])          # (with a loss, logits too: an output for the caller's metrics; the objective is the loss)
+        return tuple(out)
 
     @staticmethod
-    def backward(ctx, dloss, *unused):
-        has_weight, has_mask, ignore_index, has_ignore, label_smoothing, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed = ctx.cfg
-        token_w, head_w, feat, saved, enc_out, logits, target, *rest = ctx.saved_tensors
+    def backward(ctx, dout, *unused):
+        has_target, has_weight, has_mask, opts, *tail = ctx.cfg
+        token_w, head_w, feat, saved, enc_out, *rest = ctx.saved_tensors
+        logits = rest.pop(0) if has_target else None
+        target = rest.pop(0) if has_target else None
         weight = rest.pop(0) if has_weight else None
         mask = rest.pop(0) if has_mask else None
-        g = torch.ops.hybrid.temporal_ce_opts_bwd(dloss, logits, target, weight, ignore_index, has_ignore, label_smoothing, token_w, rest, head_w, mask,
-                                                  feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, ctx.seed_inc)
+        tail = (token_w, rest, head_w, mask, feat, saved, enc_out, *tail, ctx.seed_inc)
+        if not has_target:
+            g = torch.ops.hybrid.temporal_bwd(dout, *tail)
+        elif opts is None:
+            g = torch.ops.hybrid.temporal_ce_bwd(dout, logits, target, *tail)
+        else:
+            g = torch.ops.hybrid.temporal_ce_opts_bwd(dout, logits, target, weight, *opts, *tail)
         return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 15 + tuple(g[5:])
 
 
@@ -1514,12 +1332,13 @@ _define("mha_bwd", "(Tensor dout, Tensor q_in, Tensor k_in, Tensor v_in, Tensor?
         "int dt, int H, float p_drop, int seed) -> Tensor[]", mha_bwd_op, mha_bwd_fake)
 _define("head", "(Tensor x, Tensor weight, Tensor? bias, int dt) -> Tensor", head_op, head_fake, _HeadFn.apply)
 _define("head_bwd", "(Tensor dlogits, Tensor x, Tensor weight, bool has_bias, int dt) -> (Tensor, Tensor, Tensor)", head_bwd_op, head_bwd_fake)
-_define("cross_entropy", "(Tensor logits, Tensor target) -> Tensor", cross_entropy_op, cross_entropy_fake, _CrossEntropyFn.apply)
+_define("cross_entropy", "(Tensor logits, Tensor target) -> Tensor", cross_entropy_op, cross_entropy_fake,
+        lambda logits, target: _CrossEntropyFn.apply(logits, target, None, None, None, None))
 _define("cross_entropy_bwd", "(Tensor dloss, Tensor logits, Tensor target) -> Tensor", cross_entropy_bwd_op, cross_entropy_bwd_fake)
 _define("cross_entropy_opts", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing) -> Tensor",
-        cross_entropy_opts_op, cross_entropy_opts_fake, _CrossEntropyOptsFn.apply)
+        cross_entropy_opts_op, cross_entropy_fake, _CrossEntropyFn.apply)
 _define("cross_entropy_opts_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, "
-        "float label_smoothing) -> Tensor", cross_entropy_opts_bwd_op, cross_entropy_opts_bwd_fake)
+        "float label_smoothing) -> Tensor", cross_entropy_opts_bwd_op, cross_entropy_bwd_fake)
 _define("backbone", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, bool training, "
         "float momentum, float eps, int dt) -> Tensor[]", backbone_op, backbone_fake,
         lambda x, ws, gs, bs, rms, rvs, training, momentum, eps, dt: list(_BackboneFn.apply(x, len(ws), training, momentum, eps, dt, *ws, *gs, *bs,
@@ -1538,29 +1357,30 @@ _define("backbone_infer", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[
 _LIB.impl("backbone_infer", _inference_only("backbone_infer"), "Autograd")
 _define("temporal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, int B, int dt, "
         "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor)", temporal_op,
-        temporal_fake,
+        functools.partial(_temporal_fake, 0),
         lambda h, tw, tb, ps, hw, hb, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None: _TemporalFn.apply(
-            h, tw, tb, hw, hb, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, *ps))
+            h, tw, tb, hw, hb, mask, None, None, None, None, None, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, *ps))
 _define("temporal_bwd", "(Tensor dlogits, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, "
         "Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]",
-        temporal_bwd_op, temporal_bwd_fake)
+        temporal_bwd_op, functools.partial(_temporal_bwd_fake, 0))
 _define("temporal_ce", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, int B, "
         "int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
-        temporal_ce_op, temporal_ce_fake,
-        lambda h, tw, tb, ps, hw, hb, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None: _TemporalCeFn.apply(
-            h, tw, tb, hw, hb, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, *ps))
+        temporal_ce_op, functools.partial(_temporal_fake, 1),
+        lambda h, tw, tb, ps, hw, hb, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None: _TemporalFn.apply(
+            h, tw, tb, hw, hb, mask, target, None, None, None, None, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, *ps))
 _define("temporal_ce_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, "
         "Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) "
-        "-> Tensor[]", temporal_ce_bwd_op, temporal_ce_bwd_fake)
+        "-> Tensor[]", temporal_ce_bwd_op, functools.partial(_temporal_bwd_fake, 2))
 _define("temporal_ce_opts", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
         "Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int B, int dt, int hid, int L, int H, float attn_p, float layer_p, "
-        "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_opts_op, temporal_ce_opts_fake,
+        "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_opts_op, functools.partial(_temporal_fake, 5),
         lambda h, tw, tb, ps, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p, layer_p, seed,
-        seed_inc=None: _TemporalCeOptsFn.apply(h, tw, tb, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H,
-                                               attn_p, layer_p, seed, seed_inc, *ps))
+        seed_inc=None: _TemporalFn.apply(h, tw, tb, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
+                                          layer_p, seed, seed_inc, *ps))
 _define("temporal_ce_opts_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, "
         "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
-        "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_opts_bwd_op, temporal_ce_opts_bwd_fake)
+        "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_opts_bwd_op,
+        functools.partial(_temporal_bwd_fake, 6))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1588,8 +1408,8 @@ def fct_conv_op(x: Tensor, weight: Tensor, bias: Optional[Tensor], dilation: int
     y = torch.empty(N, H, W, Co, dtype=torch.float32, device=x.device)
     z = torch.empty_like(y) if act == ACT_GELU else _e0(x)
     ws = _ws(_query("hyb_fct_conv_workspace", N, H, W, Ci, Co), x.device)
-    lib.call("hyb_fct_conv_fwd", x.data_ptr(), _f32c(weight).data_ptr(), _f32c(bias).data_ptr() if bias is not None else None, y.data_ptr(),
-             z.data_ptr() if act == ACT_GELU else None, N, H, W, Ci, Co, dilation, act, ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_fct_conv_fwd", x, _f32c(weight), _f32c(bias) if bias is not None else None, y,
+             z if act == ACT_GELU else None, N, H, W, Ci, Co, dilation, act, ws, ws.numel(), _stream())
     return y, z
 
 
@@ -1609,9 +1429,8 @@ def fct_conv_bwd_op(dy: Tensor, x: Tensor, weight: Tensor, saved: Tensor, has_bi
     dw = torch.empty_like(weight, memory_format=torch.contiguous_format, dtype=torch.float32)
     db = torch.empty(Co if has_bias else 0, dtype=torch.float32, device=x.device)
     ws = _ws(_query("hyb_fct_conv_bwd_workspace", N, H, W, Ci, Co), x.device)
-    lib.call("hyb_fct_conv_bwd", dy.data_ptr(), x.data_ptr(), _f32c(weight).data_ptr(), saved.data_ptr() if act != ACT_NONE else None,
-             dx.data_ptr() if need_dx else None, dw.data_ptr(), db.data_ptr() if has_bias else None, N, H, W, Ci, Co, dilation, act,
-             ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_fct_conv_bwd", dy, x, _f32c(weight), saved if act != ACT_NONE else None, dx if need_dx else None, dw, db if has_bias else None,
+             N, H, W, Ci, Co, dilation, act, ws, ws.numel(), _stream())
     return dx, dw, db
 
 
@@ -1646,9 +1465,7 @@ def fct_qkv_proj_op(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tenso
     N, H, W, C = x.shape
     q, k, v = (torch.empty_like(x) for _ in range(3))
     ws_, bs_, gs_, be_ = ([_f32c(t) for t in lst] for lst in (weights, biases, ln_weights, ln_biases))
-    lib.call("hyb_fct_qkv_proj_fwd", x.data_ptr(), ptr_array([t.data_ptr() for t in ws_]), ptr_array([t.data_ptr() for t in bs_]),
-             ptr_array([t.data_ptr() for t in gs_]), ptr_array([t.data_ptr() for t in be_]), q.data_ptr(), k.data_ptr(), v.data_ptr(),
-             N, H, W, C, float(eps), _stream())
+    lib.call("hyb_fct_qkv_proj_fwd", x, ws_, bs_, gs_, be_, q, k, v, N, H, W, C, float(eps), _stream())
     return q, k, v
 
 
@@ -1669,9 +1486,7 @@ def fct_qkv_proj_bwd_op(x: Tensor, weights: Sequence[Tensor], biases: Sequence[T
     dws = [torch.empty(C, 1, 3, 3, dtype=torch.float32, device=dev) for _ in range(3)]
     dbs, dgs, dbetas = ([torch.empty(C, dtype=torch.float32, device=dev) for _ in range(3)] for _ in range(3))
     ws = _ws(_query("hyb_fct_qkv_proj_bwd_workspace", N, H, W, C), dev)
-    pa = lambda lst: ptr_array([t.data_ptr() for t in lst])
-    lib.call("hyb_fct_qkv_proj_bwd", x.data_ptr(), pa(ws_), pa(bs_), pa(gs_), pa(dq_), dx.data_ptr(), pa(dws), pa(dbs), pa(dgs), pa(dbetas),
-             N, H, W, C, float(eps), ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_fct_qkv_proj_bwd", x, ws_, bs_, gs_, dq_, dx, dws, dbs, dgs, dbetas, N, H, W, C, float(eps), ws, ws.numel(), _stream())
     return [dx] + dws + dbs + dgs + dbetas
 
 
@@ -1704,7 +1519,7 @@ def fct_ln_op(x: Tensor, weight: Tensor, bias: Tensor, eps: float) -> Tensor:
     x = _f32c(x)
     y = torch.empty_like(x)
     C = x.shape[-1]
-    lib.call("hyb_fct_ln_fwd", x.data_ptr(), _f32c(weight).data_ptr(), _f32c(bias).data_ptr(), y.data_ptr(), x.numel() // C, C, float(eps), _stream())
+    lib.call("hyb_fct_ln_fwd", x, _f32c(weight), _f32c(bias), y, x.numel() // C, C, float(eps), _stream())
     return y
 
 
@@ -1720,8 +1535,7 @@ def fct_ln_bwd_op(dy: Tensor, x: Tensor, weight: Tensor, eps: float) -> Tuple[Te
     dx = torch.empty_like(x)
     dg, db = (torch.empty(C, dtype=torch.float32, device=x.device) for _ in range(2))
     ws = _ws(_query("hyb_fct_ln_bwd_workspace", P, C), x.device)
-    lib.call("hyb_fct_ln_bwd", dy.data_ptr(), x.data_ptr(), _f32c(weight).data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), P, C, float(eps),
-             ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_fct_ln_bwd", dy, x, _f32c(weight), dx, dg, db, P, C, float(eps), ws, ws.numel(), _stream())
     return dx, dg, db
 
 
@@ -1755,9 +1569,8 @@ def fct_mha_op(q: Tensor, k: Tensor, v: Tensor, in_w: Tensor, in_b: Optional[Ten
     out = torch.empty_like(q)
     saved = _ws(_query("hyb_fct_mha_saved_bytes", N, L, C, heads), q.device)
     ws = _ws(_query("hyb_fct_mha_workspace", N, L, C, heads), q.device)
-    lib.call("hyb_fct_mha_fwd", q.data_ptr(), k.data_ptr(), v.data_ptr(), _f32c(in_w).data_ptr(), _f32c(in_b).data_ptr() if in_b is not None else None,
-             _f32c(out_w).data_ptr(), _f32c(out_b).data_ptr() if out_b is not None else None, out.data_ptr(), saved.data_ptr(), N, L, C, heads,
-             ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_fct_mha_fwd", q, k, v, _f32c(in_w), _f32c(in_b) if in_b is not None else None, _f32c(out_w),
+             _f32c(out_b) if out_b is not None else None, out, saved, N, L, C, heads, ws, ws.numel(), _stream())
     return out, saved
 
 
@@ -1779,9 +1592,8 @@ def fct_mha_bwd_op(dout: Tensor, q: Tensor, k: Tensor, v: Tensor, in_w: Tensor, 
     dout_w = torch.empty(C, C, dtype=torch.float32, device=dev)
     dout_b = torch.empty(C if has_out_b else 0, dtype=torch.float32, device=dev)
     ws = _ws(_query("hyb_fct_mha_bwd_workspace", N, L, C, heads), dev)
-    lib.call("hyb_fct_mha_bwd", dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), _f32c(in_w).data_ptr(), _f32c(out_w).data_ptr(),
-             saved.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), din_w.data_ptr(), din_b.data_ptr() if has_in_b else None,
-             dout_w.data_ptr(), dout_b.data_ptr() if has_out_b else None, N, L, C, heads, ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_fct_mha_bwd", dout, q, k, v, _f32c(in_w), _f32c(out_w), saved, dq, dk, dv, din_w, din_b if has_in_b else None, dout_w,
+             dout_b if has_out_b else None, N, L, C, heads, ws, ws.numel(), _stream())
     return [dq, dk, dv, din_w, din_b, dout_w, dout_b]
 
 
@@ -1816,7 +1628,7 @@ def fct_add_op(a: Tensor, b: Tensor) -> Tensor:
     if a.shape != b.shape:
         raise RuntimeError(f"shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
     y = torch.empty_like(a)
-    lib.call("hyb_fct_add", a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), _stream())
+    lib.call("hyb_fct_add", a, b, y, a.numel(), _stream())
     return y
 
 
@@ -1842,7 +1654,7 @@ def fct_resample_op(x: Tensor, mode: int) -> Tensor:
     x = _f32c(x)
     N, H, W, C = x.shape
     y = torch.empty((N, 2 * H, 2 * W, C) if mode == 2 else (N, H // 2, W // 2, C), dtype=torch.float32, device=x.device)
-    lib.call("hyb_fct_resample", mode, x.data_ptr(), y.data_ptr(), N, H, W, C, _stream())
+    lib.call("hyb_fct_resample", mode, x, y, N, H, W, C, _stream())
     return y
 
 
@@ -1856,7 +1668,7 @@ def fct_resample_bwd_op(dy: Tensor, x: Tensor, mode: int) -> Tensor:
     dy, x = _f32c(dy), _f32c(x)
     N, H, W, C = x.shape
     dx = torch.empty_like(x)
-    lib.call("hyb_fct_resample_bwd", mode, dy.data_ptr(), x.data_ptr(), dx.data_ptr(), N, H, W, C, _stream())
+    lib.call("hyb_fct_resample_bwd", mode, dy, x, dx, N, H, W, C, _stream())
     return dx
 
 
@@ -1887,7 +1699,7 @@ def fct_concat_op(a: Tensor, b: Tensor) -> Tensor:
     if a.shape[:-1] != b.shape[:-1]:
         raise RuntimeError(f"Sizes of tensors must match except in the channel dimension: {tuple(a.shape)} vs {tuple(b.shape)}")
     y = torch.empty(*a.shape[:-1], a.shape[-1] + b.shape[-1], dtype=torch.float32, device=a.device)
-    lib.call("hyb_fct_concat", a.data_ptr(), a.shape[-1], b.data_ptr(), b.shape[-1], y.data_ptr(), a.numel() // a.shape[-1], _stream())
+    lib.call("hyb_fct_concat", a, a.shape[-1], b, b.shape[-1], y, a.numel() // a.shape[-1], _stream())
     return y
 
 
@@ -1900,7 +1712,7 @@ def fct_concat_bwd_op(dy: Tensor, Ca: int, Cb: int) -> Tuple[Tensor, Tensor]:
     dy = _f32c(dy)
     da = torch.empty(*dy.shape[:-1], Ca, dtype=torch.float32, device=dy.device)
     db = torch.empty(*dy.shape[:-1], Cb, dtype=torch.float32, device=dy.device)
-    lib.call("hyb_fct_concat_bwd", dy.data_ptr(), da.data_ptr(), Ca, db.data_ptr(), Cb, dy.numel() // (Ca + Cb), _stream())
+    lib.call("hyb_fct_concat_bwd", dy, da, Ca, db, Cb, dy.numel() // (Ca + Cb), _stream())
     return da, db
 
 
@@ -1925,7 +1737,7 @@ def fct_dropout_op(x: Tensor, p: float, seed: int, seed_inc: Optional[Tensor] = 
     _require_cuda(x)
     x = _f32c(x)
     y = torch.empty_like(x)
-    lib.call("hyb_fct_dropout", x.data_ptr(), y.data_ptr(), x.numel(), float(p), seed, _opt_ptr(seed_inc), _stream())
+    lib.call("hyb_fct_dropout", x, y, x.numel(), float(p), seed, seed_inc, _stream())
     return y
 
 
@@ -1956,7 +1768,7 @@ def dice_loss_op(pred: Tensor, true: Tensor, smooth: float) -> Tensor:
     N, C = pred.shape[0], pred.shape[1]
     loss = torch.empty((), dtype=torch.float32, device=pred.device)
     ws = _ws(_query("hyb_dice_workspace"), pred.device)
-    lib.call("hyb_dice_fwd", pred.data_ptr(), true.data_ptr(), loss.data_ptr(), N, C, pred.numel() // (N * C), float(smooth), ws.data_ptr(),
+    lib.call("hyb_dice_fwd", pred, true, loss, N, C, pred.numel() // (N * C), float(smooth), ws,
              ws.numel(), _stream())
     return loss
 
@@ -1971,8 +1783,8 @@ def dice_loss_bwd_op(dloss: Tensor, pred: Tensor, true: Tensor, smooth: float) -
     N, C = pred.shape[0], pred.shape[1]
     dpred = torch.empty_like(pred)
     ws = _ws(4096, pred.device)
-    lib.call("hyb_dice_bwd", pred.data_ptr(), true.data_ptr(), _f32c(dloss).reshape(1).data_ptr(), dpred.data_ptr(), N, C, pred.numel() // (N * C),
-             float(smooth), ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_dice_bwd", pred, true, _f32c(dloss).reshape(1), dpred, N, C, pred.numel() // (N * C),
+             float(smooth), ws, ws.numel(), _stream())
     return dpred
 
 
@@ -2017,8 +1829,8 @@ def conv2d_op(x: Tensor, weight: Tensor, bias: Optional[Tensor], stride: int, pa
     y = torch.empty(N, Ho, Wo, Co, dtype=torch.float32, device=x.device)
     z = torch.empty_like(y) if act == ACT_GELU else _e0(x)
     ws = _ws(_query("hyb_conv2d_workspace", N, H, W, Ci, Co, k, stride, padding, dilation), x.device)
-    lib.call("hyb_conv2d_fwd", x.data_ptr(), _f32c(weight).data_ptr(), _f32c(bias).data_ptr() if bias is not None else None, y.data_ptr(),
-             z.data_ptr() if act == ACT_GELU else None, N, H, W, Ci, Co, k, stride, padding, dilation, act, ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_conv2d_fwd", x, _f32c(weight), _f32c(bias) if bias is not None else None, y,
+             z if act == ACT_GELU else None, N, H, W, Ci, Co, k, stride, padding, dilation, act, ws, ws.numel(), _stream())
     return y, z
 
 
@@ -2039,9 +1851,8 @@ def conv2d_bwd_op(dy: Tensor, x: Tensor, weight: Tensor, saved: Tensor, has_bias
     dw = torch.empty_like(weight, memory_format=torch.contiguous_format, dtype=torch.float32)
     db = torch.empty(Co if has_bias else 0, dtype=torch.float32, device=x.device)
     ws = _ws(_query("hyb_conv2d_bwd_workspace", N, H, W, Ci, Co, k, stride, padding, dilation), x.device)
-    lib.call("hyb_conv2d_bwd", dy.data_ptr(), x.data_ptr(), _f32c(weight).data_ptr(), saved.data_ptr() if act != ACT_NONE else None,
-             dx.data_ptr() if need_dx else None, dw.data_ptr(), db.data_ptr() if has_bias else None, N, H, W, Ci, Co, k, stride, padding, dilation, act,
-             ws.data_ptr(), ws.numel(), _stream())
+    lib.call("hyb_conv2d_bwd", dy, x, _f32c(weight), saved if act != ACT_NONE else None, dx if need_dx else None, dw, db if has_bias else None,
+             N, H, W, Ci, Co, k, stride, padding, dilation, act, ws, ws.numel(), _stream())
     return dx, dw, db
 
 
@@ -2092,8 +1903,8 @@ def bn2d_op(x: Tensor, weight: Tensor, bias: Tensor, residual: Optional[Tensor],
     y = torch.empty_like(x)
     coef = torch.empty(4, C, dtype=torch.float32, device=x.device)
     ws = _ws(_query("hyb_bn2d_workspace", P, C), x.device)
-    lib.call("hyb_bn2d_fwd", x.data_ptr(), _f32c(weight).data_ptr(), _f32c(bias).data_ptr(), _opt_ptr(residual), y.data_ptr(), coef.data_ptr(),
-             _opt_ptr(running_mean), _opt_ptr(running_var), P, C, float(eps), float(momentum), int(training), int(relu), ws.data_ptr(), ws.numel(),
+    lib.call("hyb_bn2d_fwd", x, _f32c(weight), _f32c(bias), residual, y, coef,
+             running_mean, running_var, P, C, float(eps), float(momentum), int(training), int(relu), ws, ws.numel(),
              _stream())
     return y, coef
 
@@ -2115,8 +1926,8 @@ def bn2d_bwd_op(dy: Tensor, x: Tensor, y: Tensor, weight: Tensor, coef: Tensor, 
     dg = torch.empty(C, dtype=torch.float32, device=x.device)
     db = torch.empty(C, dtype=torch.float32, device=x.device)
     ws = _ws(_query("hyb_bn2d_workspace", P, C), x.device)
-    lib.call("hyb_bn2d_bwd", dy.data_ptr(), x.data_ptr(), y.data_ptr() if (relu and has_residual) else None, _f32c(weight).data_ptr(), coef.data_ptr(), dx.data_ptr(),
-             dres.data_ptr() if has_residual else None, dg.data_ptr(), db.data_ptr(), P, C, int(training), int(relu), ws.data_ptr(), ws.numel(),
+    lib.call("hyb_bn2d_bwd", dy, x, y if (relu and has_residual) else None, _f32c(weight), coef, dx,
+             dres if has_residual else None, dg, db, P, C, int(training), int(relu), ws, ws.numel(),
              _stream())
     return dx, dres, dg, db
 
@@ -2151,7 +1962,7 @@ def dropout2d_op(x: Tensor, p: float, seed: int, seed_inc: Optional[Tensor] = No
     x = _f32c(x)
     N, H, W, C = x.shape
     y = torch.empty_like(x)
-    lib.call("hyb_dropout2d", x.data_ptr(), y.data_ptr(), N, H * W, C, float(p), seed, _opt_ptr(seed_inc), _stream())
+    lib.call("hyb_dropout2d", x, y, N, H * W, C, float(p), seed, seed_inc, _stream())
     return y
 
 

@@ -94,7 +94,7 @@ class HybridAdamW(torch.optim.Optimizer):
             if self._hyper_sent.get(gi) != vals:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
-                lib.call("hyb_adamw_hyper_set", hyper[gi].data_ptr(), *vals, _stream())
+                lib.call("hyb_adamw_hyper_set", hyper[gi], *vals, _stream())
                 self._hyper_sent[gi] = vals
 
     @property
@@ -169,15 +169,14 @@ class HybridAdamW(torch.optim.Optimizer):
                     g = g.float().contiguous()
                 grads.append(g)
             work.append((gi, len(ps), tab, grads, steps.pop()))
-        counter = self._step_counter.data_ptr() if self._step_counter is not None else None
-        ticket = self._ticket.data_ptr() if self._advance else None
+        counter = self._step_counter
+        ticket = self._ticket if self._advance else None
         if not dev_path:
             for gi, n, tab, grads, step in work:
                 group = self.param_groups[gi]
                 b1, b2 = group["betas"]
-                lib.call("hyb_adamw_step", n, tab[2], ptr_array([g.data_ptr() for g in grads]), tab[3], tab[4], tab[5],
-                         float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), step, counter, ticket,
-                         _stream())
+                lib.call("hyb_adamw_step", n, tab[2], grads, tab[3], tab[4], tab[5], float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                         float(group["weight_decay"]), step, counter, ticket, _stream())
             return loss
         # ---- device path: hyper-parameters (and the clip coefficient) are read from device memory by the launches themselves ----
         clip = self._clip_value()
@@ -190,7 +189,7 @@ class HybridAdamW(torch.optim.Optimizer):
             self.sync_hyper()
         if not work:
             return loss
-        clip_ptr = None
+        clip_coef = None
         if clip is not None:                        # ONE norm over the gradients of all groups, as clip_grad_norm_(model.parameters())
             all_grads = [g for w in work for g in w[3]]
             numels = tuple(g.numel() for g in all_grads)
@@ -201,10 +200,8 @@ class HybridAdamW(torch.optim.Optimizer):
                 arr = (ctypes.c_longlong * len(numels))(*numels)
                 chunks = lib.query("hyb_grad_norm_workspace", len(numels), arr)
                 self._partials = (numels, torch.zeros(chunks, dtype=torch.float32, device=hyper.device), arr)
-            lib.call("hyb_grad_norm", len(all_grads), ptr_array([g.data_ptr() for g in all_grads]), self._partials[2],
-                     self._partials[1].data_ptr(), hyper[work[0][0]].data_ptr(), self._norm_out.data_ptr(), _stream())
-            clip_ptr = self._norm_out.data_ptr()
+            lib.call("hyb_grad_norm", len(all_grads), all_grads, self._partials[2], self._partials[1], hyper[work[0][0]], self._norm_out, _stream())
+            clip_coef = self._norm_out
         for gi, n, tab, grads, step in work:
-            lib.call("hyb_adamw_step_dev", n, tab[2], ptr_array([g.data_ptr() for g in grads]), tab[3], tab[4], tab[5], hyper[gi].data_ptr(),
-                     step, counter, ticket, clip_ptr, _stream())
+            lib.call("hyb_adamw_step_dev", n, tab[2], grads, tab[3], tab[4], tab[5], hyper[gi], step, counter, ticket, clip_coef, _stream())
         return loss
