@@ -476,6 +476,26 @@ int hyb_fct_dropout(const float* x, float* y, long long n, float p, unsigned lon
  * dst[f][c][h][w] = src[f][h][w][c] / 255 for `frames` uint8 HWC frames (what PIL / cv2 decode to; Dataloader.py:19-23,
  * dataset.pyc src L106-113): frames cross PCIe as bytes and become the fp32 NCHW clip tensor the first conv stage reads. */
 int hyb_frames_u8hwc_to_f32chw(const unsigned char* src, float* dst, long long frames, int H, int W, int C, void* stream);
+/* Clip augmentation in the same pass (torchvision's Resize / RandomResizedCrop / RandomHorizontalFlip / Normalize plus temporal
+ * sub-sampling, applied with ONE parameter row per clip so that all frames of a clip get the same crop and flip).  A row is
+ * {y0, x0, ch, cw, flip, t0, tstride, 0}; rows live in device memory (no host value per batch: the launch can sit on the copy stream
+ * behind the H2D of the rows and can be captured and replayed with new rows).  For clip b, output frame t, channel c, pixel (oy, ox):
+ *   ts  = clamp(t0 + t*tstride, 0, Tin-1)
+ *   oxs = flip ? Wo-1-ox : ox
+ *   ny  = max((2*oy +1)*ch - Ho, 0);  iy0 = ny / (2*Ho);  ry = ny % (2*Ho);  iy1 = min(iy0+1, ch-1);  fy = float(ry) / float(2*Ho)
+ *   nx  = max((2*oxs+1)*cw - Wo, 0);  ix0 = nx / (2*Wo);  rx = nx % (2*Wo);  ix1 = min(ix0+1, cw-1);  fx = float(rx) / float(2*Wo)
+ *   aYX = (float) src[b][ts][y0+iyY][x0+ixX][c]
+ *   top = a00 + fx*(a01-a00);   bot = a10 + fx*(a11-a10);   v = top + fy*(bot-top)
+ *   out = v / 255.0f;           if (mean_invstd) out = (out - mean[c]) * invstd[c]
+ * i.e. F.interpolate(crop, (Ho,Wo), mode="bilinear", align_corners=False, antialias=False) / 255, flipped, normalised: NO antialias
+ * filter.  ch == Ho, cw == Wo gives bit-for-bit what hyb_frames_u8hwc_to_f32chw writes.  The kernel clamps every row before use (y0 to
+ * [0, Hin-1], ch to [1, Hin-y0], the same for x0 / cw, flip read as != 0, ts as above): no row value reads outside src.
+ * C <= 4; Hin, Win, Ho, Wo <= 16384. */
+int hyb_clips_u8_transform(const unsigned char* src /* [B][Tin][Hin][Win][C] uint8 */,
+                           const int* params        /* device, [B][8] int32, one row per CLIP */,
+                           const float* mean_invstd /* device, [2][C]: mean then 1/std; or NULL = no normalisation */,
+                           float* dst               /* [B][Tout][C][Ho][Wo] fp32 */,
+                           int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
 
 /* ---- ResNet-bottleneck backbone `Encoder_32K` (only bytecode of it ships with the reference:
  * __pycache__/AE_256_32K.cpython-38.pyc, read as data -- `Bottleneck` src L21-53, `Encoder_32K` src L58-137).  NHWC fp32 with the

@@ -11,6 +11,10 @@ What is MI355X-specific: frames cross PCIe as uint8 from pinned host memory (19 
 instead of ~1.2 ms on a 63 GB/s link, against a ~1.6 ms training step), on a dedicated copy stream, two batches deep, and are
 expanded to the fp32 ``[B,T,3,H,W]`` clip tensor by ``hyb_frames_u8hwc_to_f32chw`` on that stream -- the training stream only
 waits on an event.  No CPU fallback for the device leg.
+
+Augmentation (``ClipTransform``): crop, bilinear resize, horizontal flip, temporal sub-sampling and mean/std normalisation happen in
+that same expansion pass (``hyb_clips_u8_transform``), from ONE int32 parameter row per clip drawn on the host -- every frame of a
+clip gets the same crop and flip, which per-image host transforms get wrong by default -- so the host never touches a pixel.
 """
 import csv
 import os
@@ -75,10 +79,12 @@ def t_major(x):
 class ClipPipeline:
     """Iterates over ``source`` (any iterable of (uint8 [B,T,H,W,3], labels [B]) host batches -- a DataLoader over ClipCSVDataset
     with ``collate_fn=collate_clips``, or SyntheticClipSource) and yields device tensors (clips fp32 [B,T,3,H,W] in [0,1], labels),
-    ``depth`` batches ahead of the consumer: pinned staging buffers, async H2D on its own stream, ToTensor on the device."""
+    ``depth`` batches ahead of the consumer: pinned staging buffers, async H2D on its own stream, ToTensor on the device.
+    ``transform`` (a ClipTransform): the clips come out augmented instead, fp32 [B,Tout,C,Ho,Wo] -- one parameter row per clip is drawn
+    on the host, copied next to the bytes, and hyb_clips_u8_transform takes the ToTensor kernel's place on the copy stream."""
 
-    def __init__(self, source, device="cuda", depth=2):
-        self.source, self.depth = source, max(1, int(depth))
+    def __init__(self, source, device="cuda", depth=2, transform=None):
+        self.source, self.depth, self.transform = source, max(1, int(depth)), transform
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("ClipPipeline feeds the MI355X HIP path: device must be cuda (there is no CPU fallback)")
@@ -87,13 +93,25 @@ class ClipPipeline:
 
     def _make_slots(self, shape):
         B, T, H, W, C = shape
+        xshape = (B, T, C, H, W)
+        if self.transform is not None:
+            Tout, (Ho, Wo) = self.transform.out_frames(T), self.transform.size
+            xshape = (B, Tout, C, Ho, Wo)
+            mi = self.transform.mean_invstd(C)
+            self._mean_invstd = None if mi is None else torch.from_numpy(mi).to(self.device)
         self._slots = [dict(host=torch.empty(shape, dtype=torch.uint8).pin_memory(), host_y=torch.empty(B, dtype=torch.int64).pin_memory(),
                             dev_u8=torch.empty(shape, dtype=torch.uint8, device=self.device),
-                            x=torch.empty(B, T, C, H, W, dtype=torch.float32, device=self.device),
+                            x=torch.empty(xshape, dtype=torch.float32, device=self.device),
                             y=torch.empty(B, dtype=torch.int64, device=self.device), ready=torch.cuda.Event(), free=torch.cuda.Event())
                        for _ in range(self.depth + 1)]
         for s in self._slots:
             s["free"].record(torch.cuda.current_stream(self.device))
+        if self.transform is not None:
+            # the parameter rows are per slot for the same reason the bytes are: the copy stream writes batch n+2's while batch n's are read
+            for s in self._slots:
+                s["host_p"] = torch.empty(B, 8, dtype=torch.int32).pin_memory()
+                s["dev_p"] = torch.empty(B, 8, dtype=torch.int32, device=self.device)
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))      # mean_invstd was uploaded on the consumer's stream
 
     def _issue(self, slot, batch):
         frames, labels = batch
@@ -105,10 +123,18 @@ class ClipPipeline:
         s["free"].synchronize()                               # the consumer has finished with this slot's device tensors
         s["host"].numpy()[...] = frames                       # pageable -> pinned (the decoder could write here directly)
         s["host_y"].numpy()[...] = np.asarray(labels, dtype=np.int64)
+        if self.transform is not None:
+            s["host_p"].numpy()[...] = self.transform.sample(B, T, H, W)      # one row per clip: all T frames share crop and flip
         with torch.cuda.stream(self.stream):
             s["dev_u8"].copy_(s["host"], non_blocking=True)
             s["y"].copy_(s["host_y"], non_blocking=True)
-            lib.call("hyb_frames_u8hwc_to_f32chw", s["dev_u8"], s["x"], B * T, H, W, C, self.stream.cuda_stream)
+            if self.transform is None:
+                lib.call("hyb_frames_u8hwc_to_f32chw", s["dev_u8"], s["x"], B * T, H, W, C, self.stream.cuda_stream)
+            else:
+                s["dev_p"].copy_(s["host_p"], non_blocking=True)
+                Tout, Ho, Wo = s["x"].shape[1], s["x"].shape[3], s["x"].shape[4]
+                lib.call("hyb_clips_u8_transform", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho, Wo,
+                         self.stream.cuda_stream)
             s["ready"].record(self.stream)
 
     def __iter__(self):
@@ -136,3 +162,114 @@ class ClipPipeline:
             cur.wait_event(s["ready"])                        # GPU-side wait only: the host does not block
             yield s["x"], s["y"]
             s["free"].record(torch.cuda.current_stream(self.device))      # everything the consumer enqueued on x / y so far
+
+
+class ClipTransform:
+    """Per-clip augmentation parameters for the device kernel ``hyb_clips_u8_transform`` (torchvision's ``RandomResizedCrop(size, scale,
+    ratio)`` + ``RandomHorizontalFlip(hflip)`` + ``Normalize(mean, std)`` + a temporal window of ``frames`` frames, applied to all frames
+    of a clip alike).  The host only draws one row ``{y0, x0, ch, cw, flip, t0, tstride, 0}`` per clip; the pixels are resampled on the
+    device with ``F.interpolate(mode="bilinear", align_corners=False, antialias=False)`` arithmetic (no antialias filter).
+
+    size          output (Ho, Wo), or one int for a square
+    scale, ratio  RandomResizedCrop's area fraction and aspect-ratio (w / h) ranges              (train=True)
+    hflip         probability of the horizontal flip                                             (train=True)
+    mean, std     per-channel Normalize constants on the [0,1] scale, both or neither; the kernel gets fp32 ``mean`` and fp32 ``1/std``
+    frames        output frames per clip (None: all of them, stride 1); frame_stride = (lo, hi): the stride is drawn among lo..hi
+    seed          of the numpy Generator that draws the rows; data-parallel ranks pass ``seed + rank`` so that they augment differently
+    train=False   the deterministic evaluation transform: largest centred crop of the output's aspect ratio, no flip, the smallest
+                  stride, the centred temporal window
+    """
+
+    def __init__(self, size, scale=(0.35, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, mean=None, std=None, frames=None, frame_stride=(1, 1), seed=0,
+                 train=True):
+        self.size = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        if min(self.size) <= 0:
+            raise ValueError(f"size must be positive, got {size!r}")
+        self.scale, self.ratio = (float(scale[0]), float(scale[1])), (float(ratio[0]), float(ratio[1]))
+        if not (0 < self.scale[0] <= self.scale[1]) or not (0 < self.ratio[0] <= self.ratio[1]):
+            raise ValueError("scale and ratio are (lo, hi) ranges of positive numbers")
+        self.hflip = float(hflip)
+        if (mean is None) != (std is None):
+            raise ValueError("mean and std go together: give both or neither")
+        self.mean = self.invstd = None
+        if mean is not None:
+            self.mean = np.atleast_1d(np.asarray(mean, dtype=np.float32))
+            std32 = np.atleast_1d(np.asarray(std, dtype=np.float32))
+            if self.mean.ndim != 1 or self.mean.shape != std32.shape:
+                raise ValueError("mean and std must be sequences of the same length (one entry per channel)")
+            if not np.all(std32 != 0):
+                raise ValueError("std has a zero entry")
+            self.invstd = (np.float32(1) / std32).astype(np.float32)          # the fp32 values the kernel multiplies by
+        self.frames = None if frames is None else int(frames)
+        if self.frames is not None and self.frames <= 0:
+            raise ValueError("frames must be positive")
+        self.frame_stride = (int(frame_stride[0]), int(frame_stride[1]))
+        if not (1 <= self.frame_stride[0] <= self.frame_stride[1]):
+            raise ValueError("frame_stride is a (lo, hi) range with 1 <= lo <= hi")
+        self.seed, self.train = int(seed), bool(train)
+        self.rng = np.random.default_rng(self.seed)
+
+    def out_frames(self, Tin):
+        if self.frames is not None and self.frames > Tin:
+            raise ValueError(f"frames={self.frames} exceeds the clip length {Tin}")
+        return Tin if self.frames is None else self.frames
+
+    def mean_invstd(self, C):
+        """fp32 [2,C] (mean, then 1/std) as the kernel reads it, or None without normalisation."""
+        if self.mean is None:
+            return None
+        if len(self.mean) != C:
+            raise ValueError(f"mean/std have {len(self.mean)} entries, the clips have {C} channels")
+        return np.stack([self.mean, self.invstd])
+
+    def _strides(self, Tin):
+        fit = [s for s in range(self.frame_stride[0], self.frame_stride[1] + 1) if (self.frames - 1) * s < Tin]
+        if not fit:
+            raise ValueError(f"no stride of frame_stride={self.frame_stride} fits {self.frames} frames into a clip of {Tin}")
+        return fit
+
+    def _crop(self, Hin, Win):
+        """torchvision's RandomResizedCrop.get_params: up to 10 tries of area x log-uniform ratio that fit, then the largest centred
+        crop with the image's ratio clamped into range."""
+        g, area = self.rng, Hin * Win
+        for _ in range(10):
+            target = area * g.uniform(self.scale[0], self.scale[1])
+            ar = float(np.exp(g.uniform(np.log(self.ratio[0]), np.log(self.ratio[1]))))
+            w, h = int(round(np.sqrt(target * ar))), int(round(np.sqrt(target / ar)))
+            if 0 < w <= Win and 0 < h <= Hin:
+                return int(g.integers(0, Hin - h + 1)), int(g.integers(0, Win - w + 1)), h, w
+        in_ratio = Win / Hin
+        if in_ratio < self.ratio[0]:
+            w, h = Win, min(Hin, max(1, int(round(Win / self.ratio[0]))))
+        elif in_ratio > self.ratio[1]:
+            h, w = Hin, min(Win, max(1, int(round(Hin * self.ratio[1]))))
+        else:
+            w, h = Win, Hin
+        return (Hin - h) // 2, (Win - w) // 2, h, w
+
+    def sample(self, B, Tin, Hin, Win):
+        """-> int32 [B,8]: one row {y0, x0, ch, cw, flip, t0, tstride, 0} per clip of a [B,Tin,Hin,Win,C] batch."""
+        Tout = self.out_frames(Tin)
+        rows = np.zeros((B, 8), dtype=np.int32)
+        Ho, Wo = self.size
+        for b in range(B):
+            if self.train:
+                y0, x0, h, w = self._crop(Hin, Win)
+                flip = int(self.rng.random() < self.hflip)
+            else:
+                if Win * Ho >= Hin * Wo:
+                    h, w = Hin, max(1, Hin * Wo // Ho)
+                else:
+                    h, w = max(1, Win * Ho // Wo), Win
+                y0, x0, flip = (Hin - h) // 2, (Win - w) // 2, 0
+            t0, stride = 0, 1
+            if self.frames is not None:
+                fit = self._strides(Tin)
+                if self.train:
+                    stride = fit[int(self.rng.integers(0, len(fit)))]
+                    t0 = int(self.rng.integers(0, Tin - (Tout - 1) * stride))
+                else:
+                    stride = fit[0]
+                    t0 = (Tin - ((Tout - 1) * stride + 1)) // 2
+            rows[b] = (y0, x0, h, w, flip, t0, stride, 0)
+        return rows

@@ -25,6 +25,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::cross_entropy_opts   ... with class weights, label smoothing, ignore_index   (torch.nn.functional.cross_entropy's "mean")
     hybrid::cast, hybrid::nchw_to_nhwc, hybrid::nhwc_to_nchw                     layout / dtype glue for standalone module use
     hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
+    hybrid::clip_transform   uint8 clips -> crop, resize, flip, sub-sample, ToTensor, Normalize   (clips.ClipTransform; no autograd formula)
 """
 import ctypes
 import functools
@@ -870,6 +871,41 @@ def backbone_infer(x, stages, dt):
                                            [bn.running_mean for bn in bns], [bn.running_var for bn in bns], float(bns[0].eps), int(dt))
 
 
+def _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo):
+    if src.dim() != 5 or src.dtype != torch.uint8:
+        raise TypeError("hybrid::clip_transform reads uint8 clips [B,Tin,Hin,Win,C]")
+    B, Tin, Hin, Win, C = src.shape
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, 8):
+        raise TypeError(f"params must be int32 [{B},8]: one row {{y0, x0, ch, cw, flip, t0, tstride, 0}} per clip")
+    if mean_invstd is not None and (mean_invstd.dtype != torch.float32 or tuple(mean_invstd.shape) != (2, C)):
+        raise TypeError(f"mean_invstd must be float32 [2,{C}]: mean, then 1/std")
+    if C > 4 or max(Hin, Win, Ho, Wo) > 16384 or min(B, Tin, Hin, Win, C, Tout, Ho, Wo) <= 0:
+        raise ValueError("hybrid::clip_transform needs C <= 4, extents > 0 and Hin, Win, Ho, Wo <= 16384")
+    return B, Tin, Hin, Win, C
+
+
+def clip_transform_op(src: Tensor, params: Tensor, mean_invstd: Optional[Tensor], Tout: int, Ho: int, Wo: int) -> Tensor:
+    """uint8 [B,Tin,Hin,Win,C] -> fp32 [B,Tout,C,Ho,Wo]: crop, bilinear resize, flip, temporal sub-sampling, / 255, normalise, one parameter
+    row per clip (hyb_clips_u8_transform in include/hybrid_hip.h has the sampling rule)."""
+    _require_cuda(src, params, mean_invstd)
+    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
+    out = torch.empty(B, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
+    lib.call("hyb_clips_u8_transform", src.contiguous(), params.contiguous(), None if mean_invstd is None else mean_invstd.contiguous(), out,
+             B, Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
+    return out
+
+
+def clip_transform_fake(src, params, mean_invstd, Tout, Ho, Wo):
+    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
+    return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
+
+
+def clip_transform(src, params, mean_invstd, Tout, Ho, Wo):
+    """The device leg of ClipTransform on its own: src uint8 [B,Tin,Hin,Win,C], params int32 [B,8] (ClipTransform.sample), mean_invstd fp32
+    [2,C] or None -> fp32 [B,Tout,C,Ho,Wo] on the current stream (hybrid::clip_transform checks devices, dtypes and shapes)."""
+    return torch.ops.hybrid.clip_transform(src, params, mean_invstd, int(Tout), int(Ho), int(Wo))
+
+
 def _check_h_dtype(h, dt):
     """dt | HYB_H_BF16 (fp32 / bf16x3 temporal part behind bf16 conv stages): the pooled map is bf16, the global-average-pool kernels convert."""
     want = torch.bfloat16 if dt & HYB_H_BF16 else _TORCH_DTYPE[dt & 0xff]
@@ -1355,6 +1391,8 @@ _LIB.impl("convstage_infer", _inference_only("convstage_infer"), "Autograd")
 _define("backbone_infer", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, float eps, "
         "int dt) -> Tensor", backbone_infer_op, backbone_infer_fake)
 _LIB.impl("backbone_infer", _inference_only("backbone_infer"), "Autograd")
+_define("clip_transform", "(Tensor src, Tensor params, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor", clip_transform_op, clip_transform_fake)
+_LIB.impl("clip_transform", _inference_only("clip_transform"), "Autograd")
 _define("temporal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, int B, int dt, "
         "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor)", temporal_op,
         functools.partial(_temporal_fake, 0),
