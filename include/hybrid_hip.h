@@ -198,6 +198,10 @@ int hyb_conv3x3_pool_fused(int dtype, int W, int Cip, int Cop);
  * of this shape with the 2x2 window extremes stored by the conv's epilogue (no full-resolution re-read for BatchNorm + ReLU + MaxPool);
  * the outputs are the same bit for bit either way. */
 int hyb_conv3x3_pool_ext(int dtype, int W, int Cip, int Cop);
+/* pure host query: the kernel variant a non-first hyb_conv3x3_fwd of this shape runs, 100 * family + table row (family 0 first-generation rows 0-3, 1 asynchronous ring rows 0-6, 2 k32 rows 0-1: csrc/conv_plan.h) */
+int hyb_conv3x3_fwd_variant(int dtype, int N, int H, int W, int Cip, int Cop);
+/* pure host query: the non-first weight-gradient kernel of this shape (fused = hyb_convstage_bwd's form), 100 * generation (1, 2, 3) + input channels per workgroup (32, 64) */
+int hyb_conv3x3_wgrad_variant(int dtype, int fused, int N, int H, int W, int Cip, int Cop);
 size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop);
 int hyb_convstage_infer(int dtype, int first, const void* x, const float* weight, const float* gamma, const float* beta,
                         const float* running_mean, const float* running_var, float eps,

@@ -46,10 +46,24 @@ def to_nchw(x, code, C):
     return out
 
 
+# The last five: every asynchronous variant in both tile orientations (csrc/conv_plan.h).  The 4 x 56 tile wins the cost comparison only when
+# the 8 x 28 tiling needs a second round of 256 workgroups: N = 130, H = 4 is the smallest such shape (260 tiles against 130), and its 4-row
+# image is a ragged tile for the 8-row kernels.  N = 2, H = 8, W = 28 takes the 8 x 28 tile of the one channel configuration the older
+# cases miss.
+FWD_EXACT_SHAPES = [(32, 32, 2, 16, 32), (32, 64, 2, 19, 37), (64, 128, 2, 16, 16), (128, 256, 1, 12, 20),
+                    (256, 128, 1, 9, 17), (96, 96, 1, 8, 16), (64, 32, 1, 33, 35), (40, 72, 1, 8, 8),
+                    (3, 32, 2, 16, 32), (3, 64, 1, 21, 45), (2, 32, 1, 8, 8), (1, 96, 1, 5, 5),
+                    (32, 64, 130, 4, 56), (64, 64, 130, 4, 56), (64, 128, 130, 4, 56), (64, 256, 130, 4, 56), (64, 64, 2, 8, 28)]
+FWD_ASYNC_CODES = set(range(100, 107)) | {200, 201}       # hyb_conv3x3_fwd_variant: ring rows 0-6, k32 rows 0-1
+
+
+def test_fwd_exact_shapes_reach_every_asynchronous_variant():
+    got = {L().query("hyb_conv3x3_fwd_variant", 1, n, h, w, pad32(ci), pad32(co)) for (ci, co, n, h, w) in FWD_EXACT_SHAPES if ci > 3}
+    assert got == FWD_ASYNC_CODES
+
+
 @pytest.mark.parametrize("mode", ["bf16", "fp32"])
-@pytest.mark.parametrize("ci,co,n,h,w", [(32, 32, 2, 16, 32), (32, 64, 2, 19, 37), (64, 128, 2, 16, 16), (128, 256, 1, 12, 20),
-                                         (256, 128, 1, 9, 17), (96, 96, 1, 8, 16), (64, 32, 1, 33, 35), (40, 72, 1, 8, 8),
-                                         (3, 32, 2, 16, 32), (3, 64, 1, 21, 45), (2, 32, 1, 8, 8), (1, 96, 1, 5, 5)])
+@pytest.mark.parametrize("ci,co,n,h,w", FWD_EXACT_SHAPES)
 def test_conv3x3_fwd_and_stats_exact(mode, ci, co, n, h, w):
     code, tdt = DT[mode]
     g = torch.Generator().manual_seed(ci * 1000 + co)
@@ -57,6 +71,7 @@ def test_conv3x3_fwd_and_stats_exact(mode, ci, co, n, h, w):
     wt = sparse_int((co, ci, 3, 3), g, -2, 2, 0.15 if ci > 3 else 0.6)
     want = F.conv2d(x, wt, padding=1)
     assert want.abs().max() <= 256
+    assert (want * want).sum(dim=(0, 2, 3)).max() < 2 ** 24          # the statistics comparison below is exact
     first = ci <= 3
     cip, cop = (0 if first else pad32(ci)), pad32(co)
     wp = torch.empty(L().query("hyb_conv_packed_elems", int(first), cip, cop), dtype=tdt, device="cuda")

@@ -142,3 +142,72 @@ def test_product_package_never_imports_the_oracle():
     for f in os.listdir(os.path.join(pkg, "csrc")):
         if f.endswith((".hip", ".h")):
             assert "oracle" not in open(os.path.join(pkg, "csrc", f)).read(), f
+
+
+# ---- conv3x3 variant queries (csrc/conv_plan.h; include/hybrid_hip.h documents the codes) ----------------------------------------------------
+F32, BF16 = 0, 1
+# code = 100 * family + table row -> a shape (dtype, N, H, W, Cip, Cop) that takes it.  Asynchronous rows come in two tile orientations:
+# 8 x 28 (N = 2, H = 8, W = 28) and 4 x 56, which wins the cost comparison only when 8 x 28 needs a second round of 256 workgroups
+# (N = 130, H = 4, W = 56: 260 tiles against 130).
+FWD_VARIANTS = {
+    0: (F32, 1, 12, 20, 128, 256), 1: (F32, 2, 16, 16, 64, 128), 2: (F32, 2, 19, 37, 32, 64), 3: (F32, 2, 16, 32, 32, 32),
+    100: (BF16, 2, 16, 32, 32, 32),
+    101: (BF16, 2, 8, 28, 64, 64), 102: (BF16, 130, 4, 56, 64, 64),
+    103: (BF16, 2, 8, 28, 64, 128), 104: (BF16, 130, 4, 56, 64, 128),
+    105: (BF16, 2, 8, 28, 64, 256), 106: (BF16, 130, 4, 56, 64, 256),
+    200: (BF16, 2, 8, 28, 32, 64), 201: (BF16, 130, 4, 56, 32, 64),
+}
+FWD_HAS_EXT = {100, 101, 102, 103, 104, 200, 201}          # 105 / 106 (eight waves, 64 channels per wave) have no EXT instantiation
+FWD_HAS_POOL = set(range(100, 107)) | {200, 201}
+CHANNELS = (32, 64, 96, 128, 192, 256)
+
+
+def test_every_forward_variant_code_has_a_shape(built, monkeypatch):
+    for k in [k for k in os.environ if k.startswith("HYB_")]:
+        monkeypatch.delenv(k)
+    q = lambda *a: built.query("hyb_conv3x3_fwd_variant", *a)
+    for code, args in FWD_VARIANTS.items():
+        assert q(*args) == code, (code, args)
+    # the table has no other code: a sweep over channel counts, both orientations and both dtypes returns nothing else
+    seen = {q(dt, n, h, w, ci, co) for dt in (F32, BF16) for (n, h, w) in ((2, 8, 28), (130, 4, 56), (1, 5, 5)) for ci in CHANNELS for co in CHANNELS}
+    assert seen == set(FWD_VARIANTS)
+    assert q(BF16, 32, 112, 112, 32, 64) == 200 and q(BF16, 32, 14, 14, 128, 256) in (105, 106)      # config-2 stages 2 and 4
+    for bad in ((BF16, 0, 8, 8, 32, 32), (BF16, 1, 8, 8, 33, 32), (BF16, 1, 8, 8, 32, 40), (7, 1, 8, 8, 32, 32), (BF16, 1, 0, 8, 32, 32)):
+        assert q(*bad) == -1, bad
+
+
+def test_pool_queries_and_stats_rows_follow_the_forward_variant(built, monkeypatch):
+    for k in [k for k in os.environ if k.startswith("HYB_")]:
+        monkeypatch.delenv(k)
+    for dt in (F32, BF16):
+        for ci in CHANNELS:
+            for co in CHANNELS:
+                for (n, h, w) in ((2, 8, 28), (130, 4, 56), (3, 30, 58)):
+                    code = built.query("hyb_conv3x3_fwd_variant", dt, n, h, w, ci, co)
+                    assert built.query("hyb_conv3x3_pool_ext", dt, w, ci, co) == int(code in FWD_HAS_EXT), (dt, ci, co, code)
+                    assert built.query("hyb_conv3x3_pool_fused", dt, w, ci, co) == int(code in FWD_HAS_POOL), (dt, ci, co, code)
+                    # the promised partial-statistics rows: the first-generation tiling of Cop (8 x 16, 16 x 16 or 16 x 32 pixels), at most 512
+                    th, tw = (8, 16) if co % 256 == 0 else (16, 16) if co % 128 == 0 else (16, 32)
+                    rows = min(512, n * -(-h // th) * -(-w // tw))
+                    assert built.query("hyb_conv_stats_rows", 0, n, h, w, co) == rows, (n, h, w, co)
+
+
+def test_wgrad_variant_reproduces_the_benchmarks_third_generation_rule(built, monkeypatch):
+    """bench.py names the weight-gradient kernel of stages 2-4 by its own copy of the rule (it may not ask the library while it is the yardstick);
+    the plan must agree with it on the benchmark's own shapes, bf16 and fp32."""
+    for k in [k for k in os.environ if k.startswith("HYB_")]:
+        monkeypatch.delenv(k)
+    chans = (3, 32, 64, 128, 256)
+    for size in (224, 448, 112):                     # CONFIGS 2 / 4, 5, and the accuracy leg
+        H = size // 2
+        for li in range(1, 4):
+            ci, co = chans[li], chans[li + 1]
+            gen3 = ci % 64 == 0 and co % 64 == 0 and H % 28 == 0 and H % 4 == 0            # bench.py, kernel_specs of the conv stages
+            want = 364 if gen3 else 200 + (64 if ci % 64 == 0 else 32)
+            assert built.query("hyb_conv3x3_wgrad_variant", BF16, 1, 32, H, H, ci, co) == want, (size, li)
+            assert built.query("hyb_conv3x3_wgrad_variant", F32, 1, 32, H, H, ci, co) == 100 + (64 if ci % 64 == 0 else 32)
+            H //= 2
+    q = lambda *a: built.query("hyb_conv3x3_wgrad_variant", *a)
+    assert q(BF16, 0, 2, 8, 28, 64, 64) == 264 and q(BF16, 1, 2, 8, 28, 64, 64) == 364          # only the fused form has a third generation
+    assert q(BF16, 1, 2, 8, 28, 64, 96) == 164 and q(BF16, 1, 2, 8, 28, 96, 64) == 232           # Cop % 64 != 0: first generation
+    assert q(BF16, 1, 2, 8, 28, 33, 64) == -1 and q(BF16, 1, 0, 8, 28, 32, 64) == -1

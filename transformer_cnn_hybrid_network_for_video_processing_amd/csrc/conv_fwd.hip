@@ -11,6 +11,7 @@
 // output channel, UNet.py:59) into the epilogue from the fp32 accumulators.
 #include "hyb_common.h"
 #include "hyb_internal.h"
+#include "conv_plan.h"
 #include "conv_first.h"
 
 namespace {
@@ -453,18 +454,19 @@ __global__ __launch_bounds__(1024) void stats_reduce_kernel(const float* __restr
     if (rows_reduce_1024(part, G, n, i, v)) stats[i] = v;
 }
 
-constexpr int MAX_STAT_PARTIALS = 512;
+int reduce_stat_rows(const float* part, float* stats, int rows, int Cop, hipStream_t st) {
+    hipLaunchKernelGGL(stats_reduce_kernel, dim3(hyb_cdiv(2 * Cop, 32)), dim3(1024), 0, st, part, stats, rows, 2 * Cop);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
 
+// first-generation kernel of plan row <NT, CB, PG> with CK channels staged per LDS halo image; one partial-statistics row per workgroup
 template <typename T, int NT, int CB, int PG, int CK, bool WLDS = false>
-int launch_conv_ck(const T* x, const T* wp, T* y, float* stats, float* part, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
+int launch_conv_ck(const ConvFwdPlan& p, const T* x, const T* wp, T* y, float* stats, float* part, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
     constexpr int TH = 4 * TileGeom<PG>::PHP, TW = 4 * TileGeom<PG>::PWP, HP = (TH + 2) * (TW + 2);
+    static_assert(TH == conv_gen1_th(PG) && TW == conv_gen1_tw(PG), "the plan's tile is the kernel's");
     const size_t lds = (size_t)HP * CK * sizeof(T) + 4 * 2 * NT * 16 * sizeof(float) + (WLDS ? 3 * (size_t)CB * NT * 16 * 32 * sizeof(T) : 0);
-    const int tilesX = hyb_cdiv(W, TW), tilesY = hyb_cdiv(H, TH);
-    const long long numTiles = (long long)N * tilesX * tilesY;
-    const int gy = Cop / (CB * NT * 16);
-    int gx = (int)(numTiles < MAX_STAT_PARTIALS ? numTiles : MAX_STAT_PARTIALS);
-    if (gx < 1) gx = 1;
-    dim3 grid(gx, gy);
+    const dim3 grid(p.gx, p.gy);
     if (lds > 64 * 1024) {
         static HybAttrOnce once_stats, once_plain;             // per template instantiation (lds is fixed by it), per device
         if (int e = part ? hyb_set_lds_attr(once_stats, (const void*)conv3x3_nhwc_kernel<T, NT, CB, PG, CK, true, WLDS>, (int)lds)
@@ -472,41 +474,42 @@ int launch_conv_ck(const T* x, const T* wp, T* y, float* stats, float* part, int
     }
     HybProfileHook* hook = hyb_find_hook(1, Cip, Cop);
     if (hook) hipEventRecord(hook->ev0, st);
-    if (part) {
+    if (part)
         hipLaunchKernelGGL((conv3x3_nhwc_kernel<T, NT, CB, PG, CK, true, WLDS>), grid, dim3(256), lds, st, x, wp, y, part, N, H, W, Cip, Cop,
-                           tilesX, tilesY, (int)numTiles);
-        if (hook) hipEventRecord(hook->ev1, st);
-        HYB_LAUNCH_CHECK();
-        if (stats) hipLaunchKernelGGL(stats_reduce_kernel, dim3(hyb_cdiv(2 * Cop, 32)), dim3(1024), 0, st, part, stats, gx, 2 * Cop);
-    } else {
+                           p.tiles_x, p.tiles_y, (int)p.num_tiles);
+    else
         hipLaunchKernelGGL((conv3x3_nhwc_kernel<T, NT, CB, PG, CK, false, WLDS>), grid, dim3(256), lds, st, x, wp, y, stats, N, H, W, Cip, Cop,
-                           tilesX, tilesY, (int)numTiles);
-        if (hook) hipEventRecord(hook->ev1, st);
-    }
+                           p.tiles_x, p.tiles_y, (int)p.num_tiles);
+    if (hook) hipEventRecord(hook->ev1, st);
     HYB_LAUNCH_CHECK();
-    return 0;
+    return part && stats ? reduce_stat_rows(part, stats, p.gx, Cop, st) : 0;
 }
 
-// CK = channels staged per LDS halo image: the largest of {128, 64, 32} that divides Cip and keeps the image <= ~48 KB (bf16)
+// CK = channels staged per LDS halo image.  bf16: weight fragments come from an LDS ring shared by the workgroup (WLDS), 64 channels where the
+// tile is small enough for the image to stay <= ~48 KB; fp32: per-wave global loads
 template <typename T, int NT, int CB, int PG>
-int launch_conv(const T* x, const T* wp, T* y, float* stats, float* part, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
-    constexpr int ES = (int)sizeof(T);
-    if constexpr (ES == 2) {
-        static const int wlds = hyb_env_int("HYB_CONV_WLDS", 1);
-        if (wlds) {     // default: weight fragments come from an LDS ring shared by the workgroup (HYB_CONV_WLDS=0: per-wave global loads)
-            if constexpr (PG == 1) { if (Cip % 64 == 0) return launch_conv_ck<T, NT, CB, PG, 64, true>(x, wp, y, stats, part, N, H, W, Cip, Cop, st); }
-            if constexpr (PG == 2) { if (Cip % 64 == 0) return launch_conv_ck<T, NT, CB, PG, 64, true>(x, wp, y, stats, part, N, H, W, Cip, Cop, st); }
-            return launch_conv_ck<T, NT, CB, PG, 32, true>(x, wp, y, stats, part, N, H, W, Cip, Cop, st);
-        }
+int launch_conv(const ConvFwdPlan& p, const T* x, const T* wp, T* y, float* stats, float* part, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
+    if constexpr (sizeof(T) == 2) {
+        if constexpr (PG <= 2) { if (Cip % 64 == 0) return launch_conv_ck<T, NT, CB, PG, 64, true>(p, x, wp, y, stats, part, N, H, W, Cip, Cop, st); }
+        return launch_conv_ck<T, NT, CB, PG, 32, true>(p, x, wp, y, stats, part, N, H, W, Cip, Cop, st);
+    } else {
+        if constexpr (PG == 1) { if (Cip % 64 == 0) return launch_conv_ck<T, NT, CB, PG, 64>(p, x, wp, y, stats, part, N, H, W, Cip, Cop, st); }
+        return launch_conv_ck<T, NT, CB, PG, 32>(p, x, wp, y, stats, part, N, H, W, Cip, Cop, st);
     }
-    if constexpr (PG == 1) {
-        if (Cip % 128 == 0 && ES == 2) return launch_conv_ck<T, NT, CB, PG, 128>(x, wp, y, stats, part, N, H, W, Cip, Cop, st);
-        if (Cip % 64 == 0) return launch_conv_ck<T, NT, CB, PG, 64>(x, wp, y, stats, part, N, H, W, Cip, Cop, st);
-    }
-    if constexpr (PG == 2) {
-        if (Cip % 64 == 0 && ES == 2) return launch_conv_ck<T, NT, CB, PG, 64>(x, wp, y, stats, part, N, H, W, Cip, Cop, st);
-    }
-    return launch_conv_ck<T, NT, CB, PG, 32>(x, wp, y, stats, part, N, H, W, Cip, Cop, st);
+}
+
+// An asynchronous conv (conv_v2.hip) as every caller runs it: the measurement hook brackets the one launch, then the fixed-order sum of the
+// partial rows when the caller wants the reduced statistics.  ext_pooled != NULL: the EXT flavour.  The caller has asked the plan first, so
+// "no variant" is an argument error here.
+int conv_async_run(const ConvFwdPlan& p, const void* x, const void* wp, void* y, float* stats, float* part, void* ext_pooled, const float* gamma, int Co,
+                   int N, int H, int W, int Cip, int Cop, hipStream_t st, long long xblk = 0) {
+    HybProfileHook* hook = hyb_find_hook(1, Cip, Cop);
+    if (hook) hipEventRecord(hook->ev0, st);
+    const int rc = ext_pooled ? hyb_conv_v2_ext(p, x, wp, y, part, ext_pooled, gamma, Co, N, H, W, Cip, Cop, st)
+                              : hyb_conv_v2(p, x, wp, y, part, N, H, W, Cip, Cop, st, xblk);
+    if (hook) hipEventRecord(hook->ev1, st);
+    if (rc) return rc == HYB_NO_VARIANT ? HYB_E_ARG : rc;
+    return part && stats ? reduce_stat_rows(part, stats, p.stat_rows, Cop, st) : 0;
 }
 
 template <typename T>
@@ -514,79 +517,47 @@ int conv_fwd_t(int first, const void* x, const void* wp, void* y, float* stats, 
                hipStream_t st) {
     if (first) {
         HYB_CHECK_ARG(Ci >= 1 && Ci <= 3);
-        constexpr int TH = 16, TW = 32;
-        const int tilesX = hyb_cdiv(W, TW), tilesY = hyb_cdiv(H, TH);
-        const long long numTiles = (long long)N * tilesX * tilesY;
+        const int tilesX = hyb_cdiv(W, CONV_FIRST_TW), tilesY = hyb_cdiv(H, CONV_FIRST_TH);
         const int nt = (Cop % 64 == 0) ? 4 : 2;
-        const int gy = Cop / (nt * 16);
-        int gx = (int)(numTiles < MAX_STAT_PARTIALS ? numTiles : MAX_STAT_PARTIALS);
-        if (gx < 1) gx = 1;
-            dim3 grid(gx, gy);
+        const int gx = conv_stat_rows(N, H, W, CONV_FIRST_TH, CONV_FIRST_TW);
+        const dim3 grid(gx, Cop / (nt * 16));
 #define HYB_FIRST(NT_, ST_) hipLaunchKernelGGL((conv3x3_first_kernel<T, NT_, ST_>), grid, dim3(256), 0, st, (const float*)x, (const T*)wp, \
-                                               (T*)y, part, N, H, W, Ci, Cop, tilesX, tilesY, (int)numTiles)
+                                               (T*)y, part, N, H, W, Ci, Cop, tilesX, tilesY, N * tilesX * tilesY)
         if (nt == 4) { if (part) HYB_FIRST(4, true); else HYB_FIRST(4, false); }
         else         { if (part) HYB_FIRST(2, true); else HYB_FIRST(2, false); }
 #undef HYB_FIRST
         HYB_LAUNCH_CHECK();
-        if (stats) {
-            hipLaunchKernelGGL(stats_reduce_kernel, dim3(hyb_cdiv(2 * Cop, 32)), dim3(1024), 0, st, part, stats, gx, 2 * Cop);
-            HYB_LAUNCH_CHECK();
-        }
-        return 0;
+        return stats ? reduce_stat_rows(part, stats, gx, Cop, st) : 0;
     }
     HYB_CHECK_ARG(Cip % 32 == 0);
-    if constexpr (sizeof(T) == 2) {
-        // bf16: the asynchronous kernel (conv_v2.hip) takes every shape it has a variant for; HYB_CONV_V2=0 keeps the first-generation kernel
-        if (hyb_sw_conv_v2()) {
-            const int rows = part ? hyb_conv_stats_rows(0, N, H, W, Cop) : 0;
-            HybProfileHook* hook = hyb_find_hook(1, Cip, Cop);
-            if (hook) hipEventRecord(hook->ev0, st);
-            const int rc = hyb_conv_v2(x, wp, y, part, N, H, W, Cip, Cop, rows, st);
-            if (rc != HYB_NO_VARIANT) {
-                if (hook) hipEventRecord(hook->ev1, st);
-                if (rc) return rc;
-                if (part && stats) {
-                    hipLaunchKernelGGL(stats_reduce_kernel, dim3(hyb_cdiv(2 * Cop, 32)), dim3(1024), 0, st, part, stats, rows, 2 * Cop);
-                    HYB_LAUNCH_CHECK();
-                }
-                return 0;
-            }
-        }
+    // bf16: the asynchronous kernels take every shape they have a variant for; fp32, HYB_CONV_V2=0 and the rest: the first-generation kernel
+    const ConvFwdPlan p = conv_fwd_plan(sizeof(T) == 2 ? HYB_BF16 : HYB_F32, N, H, W, Cip, Cop);
+    if (p.v.family != CONV_GEN1) return conv_async_run(p, x, wp, y, stats, part, nullptr, nullptr, 0, N, H, W, Cip, Cop, st);
+    switch (p.v.row) {
+#define X(ROW, NT, CB, PG) case ROW: return launch_conv<T, NT, CB, PG>(p, (const T*)x, (const T*)wp, (T*)y, stats, part, N, H, W, Cip, Cop, st);
+        HYB_CONV_GEN1_ROWS(X)
+#undef X
     }
-    static const int cfg = hyb_env_int("HYB_CONV_CFG", 0);
-    if (cfg != 2 && Cop % 256 == 0) return launch_conv<T, 4, 4, 1>((const T*)x, (const T*)wp, (T*)y, stats, part, N, H, W, Cip, Cop, st);
-    if (Cop % 128 == 0) return launch_conv<T, 4, 2, 2>((const T*)x, (const T*)wp, (T*)y, stats, part, N, H, W, Cip, Cop, st);
-    if (Cop % 64 == 0) return launch_conv<T, 4, 1, 4>((const T*)x, (const T*)wp, (T*)y, stats, part, N, H, W, Cip, Cop, st);
-    return launch_conv<T, 2, 1, 4>((const T*)x, (const T*)wp, (T*)y, stats, part, N, H, W, Cip, Cop, st);
+    return HYB_E_ARG;
 }
 
 }  // namespace
 
 // Internal (hyb_convstage_bwd): does the bf16 dgrad conv of this shape run on the asynchronous kernel (which can read a block-planar input)?
-int hyb_conv_dgrad_planar_ok(int dtype, int W, int Cin_p, int Cout_p) {
-    return dtype == HYB_BF16 && hyb_sw_conv_v2() && hyb_conv_v2_supported(W, Cin_p, Cout_p);
-}
+int hyb_conv_dgrad_planar_ok(int dtype, int W, int Cin_p, int Cout_p) { return conv_fwd_path(dtype, W, Cin_p, Cout_p).family != CONV_GEN1; }
 // Internal: conv3x3 (dgrad weights) of a block-planar bf16 input [Cin_p/32][N][H][W][32] -> NHWC output
 int hyb_conv3x3_planar_in(const void* x, const void* wp, void* y, int N, int H, int W, int Cin_p, int Cout_p, hipStream_t st) {
-    HybProfileHook* hook = hyb_find_hook(1, Cin_p, Cout_p);
-    if (hook) hipEventRecord(hook->ev0, st);
-    const int rc = hyb_conv_v2(x, wp, y, nullptr, N, H, W, Cin_p, Cout_p, 0, st, (long long)N * H * W * 32);
-    if (hook) hipEventRecord(hook->ev1, st);
-    return rc;
+    return conv_async_run(conv_fwd_plan(HYB_BF16, N, H, W, Cin_p, Cout_p), x, wp, y, nullptr, nullptr, nullptr, nullptr, 0, N, H, W, Cin_p, Cout_p, st,
+                          (long long)N * H * W * 32);
 }
 
 // Internal (hyb_convstage_fwd_impl, training, shapes hyb_conv3x3_pool_ext takes): hyb_conv3x3_fwd(bf16, stats_partials = part) whose epilogue
-// also leaves the raw extreme of every 2 x 2 window in pooled (conv_v2.hip, EXT).  The measurement hook brackets the launch as in conv_fwd_t.
+// also leaves the raw extreme of every 2 x 2 window in pooled (conv_v2.hip, EXT)
 int hyb_conv3x3_fwd_ext(const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
                         hipStream_t st) {
     HYB_CHECK_ARG(x && wp && y && part && pooled && gamma && N > 0 && H >= 2 && W >= 2 && Cop > 0 && Cop % 32 == 0 && Cip % 32 == 0);
     HYB_CHECK_ARG((long long)N * H * W * (Cop > Cip ? Cop : Cip) < (1ll << 40));
-    const int rows = hyb_conv_stats_rows(0, N, H, W, Cop);
-    HybProfileHook* hook = hyb_find_hook(1, Cip, Cop);
-    if (hook) hipEventRecord(hook->ev0, st);
-    const int rc = hyb_conv_v2_ext(x, wp, y, part, pooled, gamma, Co, N, H, W, Cip, Cop, rows, st);
-    if (hook) hipEventRecord(hook->ev1, st);
-    return rc == HYB_NO_VARIANT ? HYB_E_ARG : rc;          // (the caller asked hyb_conv3x3_pool_ext first: not reached)
+    return conv_async_run(conv_fwd_plan(HYB_BF16, N, H, W, Cip, Cop), x, wp, y, nullptr, part, pooled, gamma, Co, N, H, W, Cip, Cop, st);
 }
 
 extern "C" long long hyb_conv_packed_elems(int first, int Cip, int Cop) {
@@ -711,15 +682,15 @@ extern "C" int hyb_conv_pack_weight(int dtype, int mode, const float* w, void* w
 
 extern "C" int hyb_conv_stats_rows(int first, int N, int H, int W, int Cop) {
     if (N <= 0 || H <= 0 || W <= 0 || Cop <= 0) return HYB_E_ARG;
-    int th, tw;
-    if (first || Cop % 128 != 0) { th = 16; tw = 32; }            // PG = 4 tiles
-    else if (Cop % 256 == 0) { th = 8; tw = 16; }                   // PG = 1
-    else { th = 16; tw = 16; }                                      // PG = 2
-    const long long numTiles = (long long)N * hyb_cdiv(W, tw) * hyb_cdiv(H, th);
-    return (int)(numTiles < MAX_STAT_PARTIALS ? numTiles : MAX_STAT_PARTIALS);
+    return first ? conv_stat_rows(N, H, W, CONV_FIRST_TH, CONV_FIRST_TW) : conv_fwd_plan(HYB_F32, N, H, W, 32, Cop).stat_rows;      // (any dtype, any Cip: the same count)
 }
 
-extern "C" size_t hyb_conv_stats_workspace(int Cop) { return Cop > 0 ? (size_t)MAX_STAT_PARTIALS * 2 * Cop * sizeof(float) : 0; }
+extern "C" size_t hyb_conv_stats_workspace(int Cop) { return Cop > 0 ? (size_t)CONV_MAX_STAT_ROWS * 2 * Cop * sizeof(float) : 0; }
+
+extern "C" int hyb_conv3x3_fwd_variant(int dtype, int N, int H, int W, int Cip, int Cop) {
+    HYB_CHECK_ARG((dtype == HYB_F32 || dtype == HYB_BF16) && N > 0 && H > 0 && W > 0 && Cip > 0 && Cop > 0 && Cip % 32 == 0 && Cop % 32 == 0);
+    return conv_fwd_plan(dtype, N, H, W, Cip, Cop).code();
+}
 
 extern "C" int hyb_conv3x3_fwd(int dtype, int first, const void* x, const void* wp, void* y, float* stats, float* stats_partials, int N,
                                int H, int W, int Ci, int Cip, int Cop, void* stream) {

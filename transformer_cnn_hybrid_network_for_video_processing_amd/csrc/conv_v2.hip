@@ -25,6 +25,7 @@
 #include <type_traits>
 #include "hyb_common.h"
 #include "hyb_internal.h"
+#include "conv_plan.h"
 
 namespace {
 
@@ -95,10 +96,6 @@ template <int NT> __device__ __forceinline__ unsigned ext_negative_mask(const fl
     return m;
 }
 __device__ __forceinline__ unsigned ext_flip(unsigned mask, int bit) { return (mask << (31 - bit)) & 0x80000000u; }
-// Which variants have an EXT instantiation.  The eight-wave ones with 64 channels per wave (NT = 4) do not: their STATS siblings already use
-// all 256 registers and with the extremes each of them spills (88 - 124 bytes of scratch per lane).  A variant that spills is not built; its
-// shapes keep the conv -> bn_relu_pool pair (hyb_conv_v2_ext_supported below answers for a shape).
-constexpr bool v2_ext_built(int NT, int NW) { return NT == 2 || NW == 4; }
 // what the EXT instantiations get beside the STATS arguments: the pooled map [N][H/2][W/2][Cop] to fill with extremes, and gamma[Co]
 struct V2Ext { bf16* pooled; const float* gamma; int Co; };
 
@@ -717,178 +714,75 @@ __global__ __launch_bounds__(CB * PGR * PGC * 64, 2) void conv3x3_k32_kernel(con
     }
 }
 
-// ss != NULL (with part == NULL): the POOL instantiation, y = the pooled map; ext.pooled != NULL (with part): the EXT instantiation
-template <int CB, int PGR, int PGC>
-int launch_k32(const bf16* x, const bf16* wp, bf16* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st,
-               int xpix, long long xblk, V2Ext ext) {
-    using G = V2Geom<2, CB, PGR, PGC, 3>;
-    constexpr size_t LDS = (size_t)3 * G::HBUF * 2 + G::STAT_FLOATS * 4;
-    static_assert(LDS <= 80 * 1024, "two workgroups per CU");
-    const int tilesX = hyb_cdiv(W, G::TW), tilesY = hyb_cdiv(H, G::TH);
-    const long long numTiles = (long long)N * tilesX * tilesY;
-    int gx = (int)(numTiles < 512 ? numTiles : 512);
-    if (part && gx > stat_rows) gx = stat_rows;
-    if (gx < 1) gx = 1;
-    gx = hyb_cdiv(numTiles, hyb_cdiv(numTiles, gx));
-    const dim3 grid(gx, Cop / G::CBW);
-    static HybAttrOnce once_stats, once_plain, once_pool, once_ext;
-    if (ss) {
-        if (int e = hyb_set_lds_attr(once_pool, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, false, true>, (int)LDS)) return e;
-        hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, false, true>), grid, dim3(256), LDS, st, x, wp, y, const_cast<float*>(ss), N, H, W, Cip, Cop,
-                           tilesX, tilesY, (int)numTiles, 0, xpix, xblk, V2Ext{});
-        HYB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (ext.pooled) {
-        if (!part) return HYB_E_ARG;
-        if (int e = hyb_set_lds_attr(once_ext, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, true, false, true>, (int)LDS)) return e;
-        hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, true, false, true>), grid, dim3(256), LDS, st, x, wp, y, part, N, H, W, Cip, Cop, tilesX, tilesY,
-                           (int)numTiles, stat_rows, xpix, xblk, ext);
-        HYB_LAUNCH_CHECK();
-        return 0;
-    }
-    if (int e = hyb_set_lds_attr(once_stats, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, true>, (int)LDS)) return e;
-    if (int e = hyb_set_lds_attr(once_plain, (const void*)conv3x3_k32_kernel<CB, PGR, PGC, false>, (int)LDS)) return e;
-    if (part)
-        hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, true>), grid, dim3(256), LDS, st, x, wp, y, part, N, H, W, Cip, Cop, tilesX, tilesY, (int)numTiles,
-                           stat_rows, xpix, xblk, V2Ext{});
-    else
-        hipLaunchKernelGGL((conv3x3_k32_kernel<CB, PGR, PGC, false>), grid, dim3(256), LDS, st, x, wp, y, (float*)nullptr, N, H, W, Cip, Cop, tilesX, tilesY,
-                           (int)numTiles, 0, xpix, xblk, V2Ext{});
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int NT, int CB, int PGR, int PGC, int R>
-int launch_v2(const bf16* x, const bf16* wp, bf16* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st,
-              int xpix, long long xblk, V2Ext ext) {
+// One line of HYB_CONV_ASYNC_ROWS as the launcher sees it: the kernel of each flavour, its geometry and its LDS size
+template <int FAM, int NT, int CB, int PGR, int PGC, int R>
+struct V2Variant {
     using G = V2Geom<NT, CB, PGR, PGC, R>;
-    const int tilesX = hyb_cdiv(W, G::TW), tilesY = hyb_cdiv(H, G::TH);
-    const long long numTiles = (long long)N * tilesX * tilesY;
-    constexpr int SLOTS = G::NW == 8 ? 256 : 512;           // resident workgroups on 256 CUs
-    int gx = (int)(numTiles < SLOTS ? numTiles : SLOTS);
-    if (part && gx > stat_rows) gx = stat_rows;
-    if (gx < 1) gx = 1;
-    gx = hyb_cdiv(numTiles, hyb_cdiv(numTiles, gx));          // contiguous runs of ceil(numTiles / gx) tiles: drop the empty ones
-    const dim3 grid(gx, Cop / G::CBW);
-    static HybAttrOnce once_stats, once_plain, once_pool, once_ext;      // per template instantiation, per device
-    if (ss) {
-        if (int e = hyb_set_lds_attr(once_pool, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false, true>, (int)G::LDS_BYTES)) return e;
-        hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false, true>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, const_cast<float*>(ss),
-                           N, H, W, Cip, Cop, tilesX, tilesY, (int)numTiles, 0, xpix, xblk, V2Ext{});
-        HYB_LAUNCH_CHECK();
-        return 0;
+    static constexpr bool K32 = FAM == CONV_K32;
+    static constexpr size_t LDS = K32 ? (size_t)3 * G::HBUF * 2 + G::STAT_FLOATS * 4 : G::LDS_BYTES;      // (k32: three halo images, no weight ring)
+    static constexpr bool HAS_EXT = v2_ext_built(NT, G::NW);
+    static_assert(!K32 || (NT == 2 && R == 3 && G::NW == 4 && LDS <= 80 * 1024), "conv3x3_k32_kernel: V2Geom<2, CB, PGR, PGC, 3>, two workgroups per CU");
+    template <bool STATS, bool POOL, bool EXT> static constexpr auto kernel() {
+        if constexpr (K32) return &conv3x3_k32_kernel<CB, PGR, PGC, STATS, POOL, EXT>;
+        else return &conv3x3_v2_kernel<NT, CB, PGR, PGC, R, STATS, POOL, EXT>;
     }
-    if (ext.pooled) {
-        if constexpr (v2_ext_built(NT, G::NW)) {
-            if (!part) return HYB_E_ARG;
-            if (int e = hyb_set_lds_attr(once_ext, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true, false, true>, (int)G::LDS_BYTES)) return e;
-            hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true, false, true>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, part, N, H, W,
-                               Cip, Cop, tilesX, tilesY, (int)numTiles, stat_rows, xpix, xblk, ext);
-            HYB_LAUNCH_CHECK();
-            return 0;
-        } else {
-            return HYB_NO_VARIANT;
-        }
-    }
-    if (int e = hyb_set_lds_attr(once_stats, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true>, (int)G::LDS_BYTES)) return e;
-    if (int e = hyb_set_lds_attr(once_plain, (const void*)conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false>, (int)G::LDS_BYTES)) return e;
-    if (part)
-        hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, true>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, part, N, H, W, Cip, Cop,
-                           tilesX, tilesY, (int)numTiles, stat_rows, xpix, xblk, V2Ext{});
-    else
-        hipLaunchKernelGGL((conv3x3_v2_kernel<NT, CB, PGR, PGC, R, false>), grid, dim3(G::NW * 64), G::LDS_BYTES, st, x, wp, y, (float*)nullptr, N, H, W,
-                           Cip, Cop, tilesX, tilesY, (int)numTiles, 0, xpix, xblk, V2Ext{});
+};
+
+// xblk / xpix: see conv3x3_v2_kernel.  ss != NULL (with part == NULL): the POOL instantiation, y = the pooled map; ext.pooled != NULL (with
+// part): the EXT instantiation
+struct V2Args { const bf16* x; const bf16* wp; bf16* y; float* part; const float* ss; int N, H, W, Cip, Cop, xpix; long long xblk; V2Ext ext; hipStream_t st; };
+
+template <class V, bool STATS, bool POOL, bool EXT>
+int launch_flavour(const ConvFwdPlan& p, const V2Args& a) {
+    static HybAttrOnce once;                                   // per kernel instantiation, per device
+    const auto kernel = V::template kernel<STATS, POOL, EXT>();
+    if (int e = hyb_set_lds_attr(once, (const void*)kernel, (int)V::LDS)) return e;
+    hipLaunchKernelGGL(kernel, dim3(STATS ? p.gx_stats : p.gx, p.gy), dim3(V::G::NW * 64), V::LDS, a.st, a.x, a.wp, a.y, POOL ? const_cast<float*>(a.ss) : a.part,
+                       a.N, a.H, a.W, a.Cip, a.Cop, p.tiles_x, p.tiles_y, (int)p.num_tiles, STATS ? p.stat_rows : 0, a.xpix, a.xblk, EXT ? a.ext : V2Ext{});
     HYB_LAUNCH_CHECK();
     return 0;
 }
+template <class V>
+int launch_variant(const ConvFwdPlan& p, const V2Args& a) {
+    if (a.ss) return launch_flavour<V, false, true, false>(p, a);
+    if (a.ext.pooled) {
+        if constexpr (V::HAS_EXT) return a.part ? launch_flavour<V, true, false, true>(p, a) : HYB_E_ARG;
+        else return HYB_NO_VARIANT;
+    }
+    return a.part ? launch_flavour<V, true, false, false>(p, a) : launch_flavour<V, false, false, false>(p, a);
+}
 
-// relative cost of covering an H x W image with TH x TW tiles on 256 persistent workgroups
-double v2_cost(int N, int H, int W, int TH, int TW, int gy) {
-    const long long tiles = (long long)N * hyb_cdiv(W, TW) * hyb_cdiv(H, TH) * gy;
-    const long long rounds = (tiles + 255) / 256;
-    return (double)rounds * TH * TW;
+// p = conv_fwd_plan of this shape; HYB_NO_VARIANT when it is not an asynchronous one.  part: partial-statistics rows [plan.stat_rows][2][Cop] (may be
+// NULL), all of them written.  xblk = 0: NHWC input; else the block-planar input's block stride in elements (see conv3x3_v2_kernel)
+int conv_v2_dispatch(const ConvFwdPlan& p, const void* x, const void* wp, void* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st,
+                     long long xblk, V2Ext ext = V2Ext{}) {
+    const V2Args a{(const bf16*)x, (const bf16*)wp, (bf16*)y, part, ss, N, H, W, Cip, Cop, xblk ? 32 : Cip, xblk ? xblk : 32, ext, st};
+    switch (p.code()) {
+#define X(FAM, ROW, NT, CB, PGR, PGC, R) case 100 * FAM + ROW: return launch_variant<V2Variant<FAM, NT, CB, PGR, PGC, R>>(p, a);
+        HYB_CONV_ASYNC_ROWS(X)
+#undef X
+    }
+    return HYB_NO_VARIANT;
 }
 
 }  // namespace
 
-// Which shapes the asynchronous kernels take (conv_v2_dispatch asks this function: every channel count that is a multiple of 32 has a
-// variant; the bounds keep a halo row block and a weight block inside 32-bit buffer offsets)
-int hyb_conv_v2_supported(int W, int Cip, int Cop) {
-    return Cip % 32 == 0 && Cop % 32 == 0 && (long long)40 * W * Cip < (1ll << 29) && (long long)256 * 9 * Cip < (1ll << 29);
-}
-
-// Waves per workgroup of the family conv_v2_dispatch picks for Cop.  Measured on the 224 x 224 clip stages: two four-wave workgroups per CU
-// (their epilogues and MFMA phases interleave) win for Cop <= 128; 256-channel blocks need the whole CU's LDS for a deep weight ring.
-// HYB_V2_NW=4|8 forces one family.
-static int v2_waves(int Cop) {
-    static const int nw_env = hyb_env_int("HYB_V2_NW", 0);
-    return nw_env ? nw_env : (Cop % 256 == 0 ? 8 : 4);
-}
-// Does the variant hyb_conv_v2_ext would launch for this shape exist (v2_ext_built)?  The two tile shapes conv_v2_dispatch chooses between
-// by cost share NT and the wave count, so the answer does not depend on N and H.
-int hyb_conv_v2_ext_supported(int W, int Cip, int Cop) {
-    if (!hyb_conv_v2_supported(W, Cip, Cop) || W < 2) return 0;
-    const int nw = v2_waves(Cop);
-    const int nt = nw == 4 ? (Cop % 128 == 0 ? 4 : 2) : (Cop % 64 == 0 ? 4 : 2);       // conv3x3_k32_kernel: NT = 2, four waves
-    return v2_ext_built(nt, nw) ? 1 : 0;
-}
-
-// Internal (conv_fwd.hip): returns HYB_NO_VARIANT when no asynchronous variant fits this shape.  part: partial-statistics rows
-// [stat_rows][2][Cop] (may be NULL), all of them written.
-
-// xblk = 0: NHWC input; else the block-planar input's block stride in elements (see conv3x3_v2_kernel)
-// ss != NULL: the POOL instantiation of the same variant (y = the pooled map, no statistics)
-// ext.pooled != NULL: the EXT instantiation of the same variant (part required)
-static int conv_v2_dispatch(const void* x, const void* wp, void* y, float* part, const float* ss, int N, int H, int W, int Cip, int Cop, int stat_rows,
-                            hipStream_t st, long long xblk, V2Ext ext = V2Ext{}) {
-    const int xpix = xblk ? 32 : Cip;
-    if (!xblk) xblk = 32;
-    if (!hyb_conv_v2_supported(W, Cip, Cop)) return HYB_NO_VARIANT;
-    const bf16* xb = (const bf16*)x; const bf16* wb = (const bf16*)wp; bf16* yb = (bf16*)y;
-#define V2(NT_, CB_, PGR_, PGC_, R_) launch_v2<NT_, CB_, PGR_, PGC_, R_>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk, ext)
-    const int nw = v2_waves(Cop);
-    static const int k32_env = hyb_env_int("HYB_CONV_K32", 1);      // (=0: A/B, the ring kernel for 32 input channels too)
-    if (k32_env && nw == 4 && Cip == 32 && Cop % 64 == 0) {
-        // one channel block per tile: weights in registers, one barrier per tile (conv3x3_k32_kernel)
-        return v2_cost(N, H, W, 8, 28, Cop / 64) <= v2_cost(N, H, W, 4, 56, Cop / 64)
-                   ? launch_k32<2, 2, 1>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk, ext)
-                   : launch_k32<2, 1, 2>(xb, wb, yb, part, ss, N, H, W, Cip, Cop, stat_rows, st, xpix, xblk, ext);
-    }
-    if (nw == 4) {
-        if (Cop % 256 == 0) return V2(4, 4, 1, 1, 3);
-        if (Cop % 128 == 0) return v2_cost(N, H, W, 8, 28, Cop / 128) <= v2_cost(N, H, W, 4, 56, Cop / 128) ? V2(4, 2, 2, 1, 4) : V2(4, 2, 1, 2, 4);
-        if (Cop % 64 == 0) return v2_cost(N, H, W, 8, 28, Cop / 64) <= v2_cost(N, H, W, 4, 56, Cop / 64) ? V2(2, 2, 2, 1, 4) : V2(2, 2, 1, 2, 4);
-        if (Cop % 32 == 0) return V2(2, 1, 4, 1, 4);
-        return HYB_NO_VARIANT;
-    }
-    if (Cop % 256 == 0) {
-        return v2_cost(N, H, W, 8, 28, Cop / 256) <= v2_cost(N, H, W, 4, 56, Cop / 256) ? V2(4, 4, 2, 1, 6) : V2(4, 4, 1, 2, 6);
-    }
-    if (Cop % 128 == 0) {
-        return v2_cost(N, H, W, 16, 28, Cop / 128) <= v2_cost(N, H, W, 8, 56, Cop / 128) ? V2(4, 2, 4, 1, 6) : V2(4, 2, 2, 2, 6);
-    }
-    if (Cop % 64 == 0) return V2(4, 1, 4, 2, 5);
-    if (Cop % 32 == 0) return V2(2, 1, 4, 2, 6);
-#undef V2
-    return HYB_NO_VARIANT;
-}
-
-int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st, long long xblk) {
-    return conv_v2_dispatch(x, wp, y, part, nullptr, N, H, W, Cip, Cop, stat_rows, st, xblk);
+// Internal (conv_fwd.hip): y = conv3x3(x, wp), with the partial statistics when part != NULL
+int hyb_conv_v2(const ConvFwdPlan& p, const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, hipStream_t st, long long xblk) {
+    return conv_v2_dispatch(p, x, wp, y, part, nullptr, N, H, W, Cip, Cop, st, xblk);
 }
 
 // Internal (hyb_convstage_infer): pooled[N][H/2][W/2][Cop] = maxpool2x2(relu(conv3x3(x, wp) * scale + shift)), ss = [2][Cop] scale | shift, the raw
 // convolution never stored.  HYB_NO_VARIANT for the shapes hyb_conv_v2 does not take.
-int hyb_conv_v2_pool(const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
-    if (!ss || H < 2 || W < 2 || !hyb_conv_v2_supported(W, Cip, Cop)) return HYB_NO_VARIANT;
-    return conv_v2_dispatch(x, wp, pooled, nullptr, ss, N, H, W, Cip, Cop, 0, st, 0);
+int hyb_conv_v2_pool(const ConvFwdPlan& p, const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st) {
+    if (!ss || H < 2 || W < 2) return HYB_NO_VARIANT;
+    return conv_v2_dispatch(p, x, wp, pooled, nullptr, ss, N, H, W, Cip, Cop, st, 0);
 }
 
 // Internal (hyb_conv3x3_fwd_ext): hyb_conv_v2 with partial statistics, and pooled[N][H/2][W/2][Cop] = the raw extreme of every 2 x 2 window of y
 // (its maximum where gamma >= 0, its minimum where gamma < 0; channels >= Co count as non-negative).  HYB_NO_VARIANT as hyb_conv_v2.
-int hyb_conv_v2_ext(const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
-                    int stat_rows, hipStream_t st) {
+int hyb_conv_v2_ext(const ConvFwdPlan& p, const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
+                    hipStream_t st) {
     if (!part || !pooled || !gamma || H < 2 || W < 2 || Co < 1 || Co > Cop) return HYB_E_ARG;
-    return conv_v2_dispatch(x, wp, y, part, nullptr, N, H, W, Cip, Cop, stat_rows, st, 0, V2Ext{(bf16*)pooled, gamma, Co});
+    return conv_v2_dispatch(p, x, wp, y, part, nullptr, N, H, W, Cip, Cop, st, 0, V2Ext{(bf16*)pooled, gamma, Co});
 }

@@ -342,11 +342,6 @@ struct W2Unit {
 
 // the prefetch loads of the tile after next must be ISSUED before the vector work on the next tile (the compiler otherwise sinks
 // them behind it, next to their first use, and their HBM latency lands on the critical path of the following iteration)
-#ifdef HYB_NO_KEEP_EARLY
-#define W2_KEEP_EARLY
-#else
-#define W2_KEEP_EARLY asm volatile("" ::: "memory")
-#endif
 template <bool FUSE, int CI, int CW, int PW>
 __global__ __launch_bounds__((CW + PW) * 64) void wgrad_v2_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy, float* __restrict__ slab,
                                                        int N, int H, int W, int Cip, int Cop, int tilesX, int tilesY, int numTiles,
@@ -527,7 +522,7 @@ __global__ __launch_bounds__((CW + PW) * 64) void wgrad_v2_kernel(const bf16* __
                 const W2Tile t2 = tl(i + 2);
                 x_dma(t1, xbuf + W2_XBUF);
                 asm volatile("" ::: "memory");         // the DMAs stay the OLDEST vector-memory operations of the iteration (see publish)
-                if (FUSE) { fuse_load(t2, ub); W2_KEEP_EARLY; fuse_compute(t1, ua, dbuf + W2_DBUF); } else dy_dma(t1, dbuf + W2_DBUF);
+                if (FUSE) { fuse_load(t2, ub); asm volatile("" ::: "memory"); fuse_compute(t1, ua, dbuf + W2_DBUF); } else dy_dma(t1, dbuf + W2_DBUF);
                 publish();
                 t1 = t2;
             }
@@ -537,7 +532,7 @@ __global__ __launch_bounds__((CW + PW) * 64) void wgrad_v2_kernel(const bf16* __
                 const W2Tile t2 = tl(i + 3);
                 x_dma(t1, xbuf);
                 asm volatile("" ::: "memory");
-                if (FUSE) { fuse_load(t2, ua); W2_KEEP_EARLY; fuse_compute(t1, ub, dbuf); } else dy_dma(t1, dbuf);
+                if (FUSE) { fuse_load(t2, ua); asm volatile("" ::: "memory"); fuse_compute(t1, ub, dbuf); } else dy_dma(t1, dbuf);
                 publish();
                 t1 = t2;
             }
@@ -625,33 +620,7 @@ __global__ __launch_bounds__((CW + PW) * 64) void wgrad_v2_kernel(const bf16* __
             }
 }
 
-template <bool FUSE, int CI, int CW, int PW>
-int w2_launch_cw(dim3 grid, HybProfileHook* hook, hipStream_t st, const bf16* x, const bf16* dy, float* slab, int N, int H, int W, int Cip, int Cop,
-                 int tX, int tY, int nT, const WgradFuse& fz) {
-    static HybAttrOnce once;                                   // per template instantiation, per device
-    if (int e = hyb_set_lds_attr(once, (const void*)wgrad_v2_kernel<FUSE, CI, CW, PW>, (int)W2X<CI>::LDS)) return e;
-    if (hook) hipEventRecord(hook->ev0, st);
-    hipLaunchKernelGGL((wgrad_v2_kernel<FUSE, CI, CW, PW>), grid, dim3((CW + PW) * 64), W2X<CI>::LDS, st, x, dy, slab, N, H, W, Cip, Cop, tX, tY, nT, fz);
-    if (hook) hipEventRecord(hook->ev1, st);
-    return 0;
-}
-template <bool FUSE, int CI>
-int w2_launch(dim3 grid, HybProfileHook* hook, hipStream_t st, const bf16* x, const bf16* dy, float* slab, int N, int H, int W, int Cip, int Cop,
-              int tX, int tY, int nT, const WgradFuse& fz) {
-    // consumer x producer waves per workgroup: 4x4 (one of each per SIMD) or 8x8 (two of each per SIMD).  Measured in one call
-    // (fused, config 2): the HBM-bound 32-channel-block stage gains from 8x8 (127 -> 110 us), the 64-channel-block stages lose
-    // (94 -> 110 us: 128 VGPRs spill the 36-tile accumulators' helpers); 8 consumers + 4 producers is never best when fused.
-    static const int env = hyb_env_int("HYB_WGRAD_WAVES", 0);
-    const int cfg = env ? env : (CI == 32 ? 88 : 44);
-    if (cfg == 88) return w2_launch_cw<FUSE, CI, 8, 8>(grid, hook, st, x, dy, slab, N, H, W, Cip, Cop, tX, tY, nT, fz);
-    return w2_launch_cw<FUSE, CI, 4, 4>(grid, hook, st, x, dy, slab, N, H, W, Cip, Cop, tX, tY, nT, fz);
-}
-
 #include "conv_wgrad_v3.h"
-#ifdef HYB_WGRAD_EXPERIMENTS      // scripts/micro/wgrad_variants: the 16-wave and the pipelined 12-wave forms measured in round 3 (not faster)
-#include "conv_wgrad_v4.h"
-#include "conv_wgrad_v5.h"
-#endif
 
 // few slabs (second-generation kernel: S = 256 / blocks): one thread per output element walks the S slabs; loads are issued
 // eight at a time, the additions keep the slab order
@@ -711,90 +680,114 @@ int hyb_wgrad_reduce_multi(int n, const HybSlabInfo* infos, hipStream_t st) {
     HYB_LAUNCH_CHECK();
     return 0;
 }
-// Which non-first shapes take the warp-specialised kernel (the only one that can write a block-planar dyraw): wgrad_t asks this function
-int hyb_wgrad_v2_supported(int dtype, int W, int Cip, int Cop) {
-    const int ci_blk = Cip % 64 == 0 ? 64 : 32;
-    return dtype == HYB_BF16 && hyb_sw_wgrad_v2() && Cip % 32 == 0 && Cop % 64 == 0 && (Cop / 64) * (Cip / ci_blk) <= 256 &&
-           (long long)12 * W * (Cip > Cop ? Cip : Cop) < (1ll << 29);
-}
 namespace {
 
-struct WgradPlan { int S, gy, cit; long long per_slab; };
+// Everything the host decides about the weight gradient of a shape, decided once: hyb_conv3x3_wgrad_workspace,
+// hyb_wgrad_v2_supported, hyb_conv3x3_wgrad_variant and wgrad_t read this plan.
+struct WgradPlan {
+    int gen;                    // 1 first generation (conv3x3_wgrad_kernel, conv3x3_wgrad_first_kernel), 2 warp-specialised (wgrad_v2_kernel), 3 its third generation (wgrad_v3_kernel)
+    int ci_blk;                 // input channels per workgroup: 64 or 32 (first stage: 0)
+    int blocks;                 // grid y: (output, input) channel-block pairs
+    int tX, tY, nT;             // tiles of the generation's own tile: WG_TH x WG_TW, or W2_TH x W2_TW
+    int S;                      // slabs written = grid x
+    int S_ws;                   // slabs the workspace holds: the first generation's count whatever runs, so the size does not depend on a switch
+    int cw, pw;                 // consumer x producer waves per workgroup (generations 2 and 3)
+    long long per_slab;
+    int code() const { return 100 * gen + ci_blk; }
+};
 
-inline WgradPlan wgrad_plan(int first, int N, int H, int W, int Cip, int Cop) {
-    WgradPlan p;
-    const long long numTiles = (long long)N * hyb_cdiv(H, WG_TH) * hyb_cdiv(W, WG_TW);
-    if (first) { p.cit = 0; p.gy = Cop / 32; p.per_slab = (long long)Cop * 32; }
-    else { p.cit = (Cip % 64 == 0) ? 4 : 2; p.gy = ((Cop + 63) / 64) * (Cip / (p.cit * 16)); p.per_slab = (long long)Cop * 9 * Cip; }
-    static const int wgs = hyb_env_int("HYB_WGRAD1_WGS", 512);       // first-generation kernel: workgroups in total (A/B)
-    long long s = (wgs > 0 ? wgs : 512) / p.gy;
+// fused: the BatchNorm / ReLU / MaxPool backward runs inside the tile staging (hyb_conv3x3_wgrad_fused); only that form has a third generation
+inline WgradPlan wgrad_plan(int dtype, int first, int fused, int N, int H, int W, int Cip, int Cop) {
+    WgradPlan p{};
+    p.ci_blk = first ? 0 : (Cip % 64 == 0 ? 64 : 32);
+    p.per_slab = first ? (long long)Cop * 32 : (long long)Cop * 9 * Cip;
+    p.gen = 1;
+    p.blocks = first ? Cop / 32 : ((Cop + 63) / 64) * (Cip / p.ci_blk);
+    p.tX = hyb_cdiv(W, WG_TW); p.tY = hyb_cdiv(H, WG_TH);
+    const long long nT1 = (long long)N * p.tX * p.tY;
+    p.nT = (int)nT1;
+    long long s = 512 / p.blocks;                       // 512 workgroups in total
+    if (s > nT1) s = nT1;
     if (s < 1) s = 1;
-    if (s > numTiles) s = numTiles;
-    p.S = (int)s;
+    p.S = p.S_ws = (int)s;
+    // the warp-specialised kernels (the only ones that can write a block-planar dyraw): bf16, 64 output channels per workgroup, at most 256
+    // workgroups per slab, a 12-row block of either tensor inside 32-bit buffer offsets
+    if (first || dtype != HYB_BF16 || !hyb_sw_wgrad_v2() || Cip % 32 != 0 || Cop < 64 || Cop % 64 != 0 || (Cop / 64) * (Cip / p.ci_blk) > 256 ||
+        (long long)12 * W * (Cip > Cop ? Cip : Cop) >= (1ll << 29)) return p;
+    // third generation: 64-channel blocks on images of 28 k columns whose rows tile into whole and half 8-row tiles (conv_wgrad_v3.h)
+    p.gen = (fused && hyb_sw_wgrad_v3() && p.ci_blk == 64 && W % W3_TW == 0 && H % 4 == 0 && H >= 8) ? 3 : 2;
+    p.blocks = (Cop / 64) * (Cip / p.ci_blk);
+    p.tX = hyb_cdiv(W, W2_TW); p.tY = hyb_cdiv(H, W2_TH);
+    const long long nT = (long long)N * p.tX * p.tY;
+    p.nT = (int)nT;
+    s = 256 / p.blocks;
+    if (s > p.S_ws) s = p.S_ws;                         // never more slabs than the workspace query promised
+    if (s > nT) s = nT;
+    p.S = hyb_cdiv(nT, hyb_cdiv(nT, s));                // contiguous runs of ceil(nT / S) tiles: drop the empty ones
+    // consumer x producer waves: 4x4 (one of each per SIMD) or 8x8 (two of each per SIMD).  Measured in one call (fused, config 2): the
+    // HBM-bound 32-channel-block stage gains from 8x8 (127 -> 110 us), the 64-channel-block stages lose (94 -> 110 us: 128 VGPRs spill the
+    // 36-tile accumulators' helpers); 8 consumers + 4 producers is never best when fused.
+    p.cw = p.pw = (p.gen == 2 && p.ci_blk == 32) ? 8 : 4;
     return p;
+}
+
+// One launch of a warp-specialised kernel (second or third generation): its LDS attribute, the measurement hook around the launch
+template <auto Kernel, typename... A>
+int wgrad_ws_launch(size_t lds, dim3 grid, int waves, HybProfileHook* hook, hipStream_t st, A... args) {
+    static HybAttrOnce once;                                   // per kernel instantiation, per device
+    if (int e = hyb_set_lds_attr(once, (const void*)Kernel, (int)lds)) return e;
+    if (hook) hipEventRecord(hook->ev0, st);
+    hipLaunchKernelGGL(Kernel, grid, dim3(waves * 64), lds, st, args...);
+    if (hook) hipEventRecord(hook->ev1, st);
+    return 0;
 }
 
 template <typename T>
 int wgrad_t(int first, const void* x, const void* dy, float* dw, int N, int H, int W, int Ci, int Cip, int Co, int Cop, void* ws,
             size_t ws_bytes, hipStream_t st, const WgradFuse* fz = nullptr, HybSlabInfo* defer = nullptr) {
     if (defer) defer->S = 0;
-    const WgradPlan p = wgrad_plan(first, N, H, W, Cip, Cop);
-    if (ws_bytes < (size_t)p.S * p.per_slab * sizeof(float)) return HYB_E_WORKSPACE;
+    const WgradPlan p = wgrad_plan(sizeof(T) == 2 ? HYB_BF16 : HYB_F32, first, fz != nullptr, N, H, W, Cip, Cop);
+    if (ws_bytes < (size_t)p.S_ws * p.per_slab * sizeof(float)) return HYB_E_WORKSPACE;
     float* slab = (float*)ws;
+    const dim3 grid(p.S, p.blocks);
+    HybProfileHook* hook = first ? nullptr : hyb_find_hook(2, Cip, Cop);
+    const WgradFuse fzv = fz ? *fz : WgradFuse{};
     if constexpr (sizeof(T) == 2) {
-        if (!first && hyb_wgrad_v2_supported(HYB_BF16, W, Cip, Cop)) {
-            const int ci_blk = Cip % 64 == 0 ? 64 : 32;
-            const int blocks = (Cop / 64) * (Cip / ci_blk);
-            // generation of the fused kernel for this shape: 0 second (below), 1 third (conv_wgrad_v3.h); 2 / 3 only in experiment builds
-            const int gen3 = (fz && ci_blk == 64) ? w3_supported(H, W, Cip, Cop) : 0;
-            const int tX = hyb_cdiv(W, W2_TW), tY = gen3 == 3 ? H / 4 : hyb_cdiv(H, W2_TH);
-            const long long nT = (long long)N * tX * tY;
-            int S = 256 / blocks;
-            if (S > p.S) S = p.S;                          // never more slabs than the workspace query promised
-            if (S > nT) S = (int)nT;
-            S = hyb_cdiv(nT, hyb_cdiv(nT, S));                // contiguous runs of ceil(nT / S) tiles: drop the empty ones
-            HybProfileHook* hook2 = hyb_find_hook(2, Cip, Cop);
-            const WgradFuse fzv = fz ? *fz : WgradFuse{};
-            const dim3 grid2(S, blocks);
-            int lrc = 0;
-#ifdef HYB_WGRAD_EXPERIMENTS
-            if (gen3 == 3) lrc = w5_launch(grid2, hook2, st, (const bf16*)x, slab, N, H, W, Cip, Cop, (int)nT, fzv);
-            else if (gen3 == 2) lrc = w4_launch(grid2, hook2, st, (const bf16*)x, slab, N, H, W, Cip, Cop, tX, tY, (int)nT, fzv);
-            else
-#endif
-            if (gen3) lrc = w3_launch(grid2, hook2, st, (const bf16*)x, slab, N, H, W, Cip, Cop, tX, tY, (int)nT, fzv);
-            else if (ci_blk == 64) lrc = fz ? w2_launch<true, 64>(grid2, hook2, st, (const bf16*)x, (const bf16*)dy, slab, N, H, W, Cip, Cop, tX, tY, (int)nT, fzv)
-                                       : w2_launch<false, 64>(grid2, hook2, st, (const bf16*)x, (const bf16*)dy, slab, N, H, W, Cip, Cop, tX, tY, (int)nT, fzv);
-            else lrc = fz ? w2_launch<true, 32>(grid2, hook2, st, (const bf16*)x, (const bf16*)dy, slab, N, H, W, Cip, Cop, tX, tY, (int)nT, fzv)
-                          : w2_launch<false, 32>(grid2, hook2, st, (const bf16*)x, (const bf16*)dy, slab, N, H, W, Cip, Cop, tX, tY, (int)nT, fzv);
-            if (lrc) return lrc;
+        if (p.gen >= 2) {
+            const bf16 *xb = (const bf16*)x, *dyb = (const bf16*)dy;
+            auto v2 = [&](auto fuse, auto ci, auto waves) {
+                if (p.cw != waves() || p.pw != waves()) return (int)HYB_E_ARG;            // (the instantiations built are the plan's pairs)
+                return wgrad_ws_launch<wgrad_v2_kernel<fuse(), ci(), waves(), waves()>>(W2X<ci()>::LDS, grid, p.cw + p.pw, hook, st, xb, dyb, slab, N, H, W, Cip,
+                                                                                       Cop, p.tX, p.tY, p.nT, fzv);
+            };
+            using std::bool_constant;
+            using c64 = std::integral_constant<int, 64>; using c32 = std::integral_constant<int, 32>;
+            using w4 = std::integral_constant<int, 4>; using w8 = std::integral_constant<int, 8>;
+            int rc;
+            if (p.gen == 3) rc = wgrad_ws_launch<wgrad_v3_kernel>(W3_LDS, grid, p.cw + p.pw, hook, st, xb, slab, N, H, W, Cip, Cop, p.tX, p.tY, p.nT, fzv);
+            else if (p.ci_blk == 64) rc = fz ? v2(bool_constant<true>{}, c64{}, w4{}) : v2(bool_constant<false>{}, c64{}, w4{});
+            else rc = fz ? v2(bool_constant<true>{}, c32{}, w8{}) : v2(bool_constant<false>{}, c32{}, w8{});
+            if (rc) return rc;
             HYB_LAUNCH_CHECK();
             if (!dw) return 0;
-            const HybSlabInfo info{slab, dw, S, Co, Ci, Cip, p.per_slab};
+            const HybSlabInfo info{slab, dw, p.S, Co, Ci, Cip, p.per_slab};
             if (defer) { *defer = info; return 0; }              // the caller sums the slabs later (hyb_wgrad_reduce_multi), with other stages'
             return hyb_wgrad_reduce_multi(1, &info, st);
         }
     }
-    const int tilesX = hyb_cdiv(W, WG_TW), tilesY = hyb_cdiv(H, WG_TH);
-    const int numTiles = N * tilesX * tilesY;
-    dim3 grid(p.S, p.gy);
-    HybProfileHook* hook = first ? nullptr : hyb_find_hook(2, Cip, Cop);
     if (hook) hipEventRecord(hook->ev0, st);
     if (first) {
-        hipLaunchKernelGGL(conv3x3_wgrad_first_kernel<T>, grid, dim3(256), 0, st, (const float*)x, (const T*)dy, slab, N, H, W, Ci, Cop, tilesX,
-                           tilesY, numTiles);
-    } else if (p.cit == 4) {
-        const size_t lds = (size_t)(WG_TH * WG_TW * DY_STRIDE + WG_HP * (64 + 16)) * sizeof(T) + 5 * 64 * sizeof(float);
-        if (fz) hipLaunchKernelGGL((conv3x3_wgrad_kernel<T, 4, true>), grid, dim3(256), lds, st, (const T*)x, (const T*)dy, slab, N, H, W, Cip, Cop,
-                                   tilesX, tilesY, numTiles, *fz);
-        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<T, 4, false>), grid, dim3(256), lds, st, (const T*)x, (const T*)dy, slab, N, H, W, Cip, Cop,
-                                tilesX, tilesY, numTiles, WgradFuse{});
+        hipLaunchKernelGGL(conv3x3_wgrad_first_kernel<T>, grid, dim3(256), 0, st, (const float*)x, (const T*)dy, slab, N, H, W, Ci, Cop, p.tX, p.tY, p.nT);
     } else {
-        const size_t lds = (size_t)(WG_TH * WG_TW * DY_STRIDE + WG_HP * (32 + 16)) * sizeof(T) + 5 * 64 * sizeof(float);
-        if (fz) hipLaunchKernelGGL((conv3x3_wgrad_kernel<T, 2, true>), grid, dim3(256), lds, st, (const T*)x, (const T*)dy, slab, N, H, W, Cip, Cop,
-                                   tilesX, tilesY, numTiles, *fz);
-        else hipLaunchKernelGGL((conv3x3_wgrad_kernel<T, 2, false>), grid, dim3(256), lds, st, (const T*)x, (const T*)dy, slab, N, H, W, Cip, Cop,
-                                tilesX, tilesY, numTiles, WgradFuse{});
+        auto v1 = [&](auto cit, auto fuse) {
+            const size_t lds = (size_t)(WG_TH * WG_TW * DY_STRIDE + WG_HP * (cit() * 16 + 16)) * sizeof(T) + 5 * 64 * sizeof(float);
+            hipLaunchKernelGGL((conv3x3_wgrad_kernel<T, cit(), fuse()>), grid, dim3(256), lds, st, (const T*)x, (const T*)dy, slab, N, H, W, Cip, Cop, p.tX,
+                               p.tY, p.nT, fzv);
+        };
+        using std::bool_constant;
+        using c4 = std::integral_constant<int, 4>; using c2 = std::integral_constant<int, 2>;
+        if (p.ci_blk == 64) { if (fz) v1(c4{}, bool_constant<true>{}); else v1(c4{}, bool_constant<false>{}); }
+        else                { if (fz) v1(c2{}, bool_constant<true>{}); else v1(c2{}, bool_constant<false>{}); }
     }
     if (hook) hipEventRecord(hook->ev1, st);
     HYB_LAUNCH_CHECK();
@@ -805,6 +798,9 @@ int wgrad_t(int first, const void* x, const void* dy, float* dw, int N, int H, i
 }
 
 }  // namespace
+
+// Which non-first shapes take the warp-specialised kernels (N, H and the fused flag choose between the second and the third generation only)
+int hyb_wgrad_v2_supported(int dtype, int W, int Cip, int Cop) { return Cip > 0 && wgrad_plan(dtype, 0, 0, 1, 1, W, Cip, Cop).gen >= 2; }
 
 // Internal: weight gradient with the BatchNorm/ReLU/MaxPool backward fused into the tile staging (non-first stages)
 
@@ -819,8 +815,13 @@ int hyb_conv3x3_wgrad_fused(int dtype, const void* x, const void* y, const void*
 
 extern "C" size_t hyb_conv3x3_wgrad_workspace(int first, int N, int H, int W, int Cip, int Cop) {
     if (N <= 0 || H <= 0 || W <= 0 || Cop <= 0 || Cop % 32 != 0 || (!first && (Cip <= 0 || Cip % 32 != 0))) return 0;
-    const WgradPlan p = wgrad_plan(first, N, H, W, Cip, Cop);
-    return (size_t)p.S * p.per_slab * sizeof(float);
+    const WgradPlan p = wgrad_plan(HYB_F32, first, 0, N, H, W, Cip, Cop);        // (S_ws: the same for every dtype)
+    return (size_t)p.S_ws * p.per_slab * sizeof(float);
+}
+
+extern "C" int hyb_conv3x3_wgrad_variant(int dtype, int fused, int N, int H, int W, int Cip, int Cop) {
+    HYB_CHECK_ARG((dtype == HYB_F32 || dtype == HYB_BF16) && N > 0 && H > 0 && W > 0 && Cip > 0 && Cop > 0 && Cip % 32 == 0 && Cop % 32 == 0);
+    return wgrad_plan(dtype, 0, fused != 0, N, H, W, Cip, Cop).code();
 }
 
 extern "C" int hyb_conv3x3_wgrad(int dtype, int first, const void* x, const void* dy, float* dw, int N, int H, int W, int Ci, int Cip,

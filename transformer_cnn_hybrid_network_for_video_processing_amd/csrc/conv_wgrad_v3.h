@@ -1,8 +1,8 @@
 // Third generation of the fused weight-gradient kernel (bf16, Cip % 64 == 0, Cop % 64 == 0, W % 28 == 0, H % 4 == 0).
 // Included by conv_wgrad.hip inside its anonymous namespace (uses WgradFuse, hyb_rsrc, the W2 tile constants' conventions).
 //
-// What the round-3 ablations of the second generation showed (scripts/micro/wgrad_bench on scripts/micro/wgrad_variants/conv_wgrad_abl.hip -- the copy
-// of these sources that carries the timing-only ablation bits; profiles/r03_wgrad_ablation.txt): with the
+// What the round-3 ablations of the second generation showed (timing-only ablation bits in a copy of these sources, since removed; the
+// figures are in profiles/r03_wgrad_ablation.txt): with the
 // consumer waves idle the producers alone took 66 / 52 us (stages 3 / 4), with the producers idle the consumers alone 58 / 61 us,
 // together 108 / 97 us -- the two halves overlapped badly, and the consumer loop reloaded spilled registers from scratch at its
 // 256-register limit.  Changes:
@@ -26,9 +26,6 @@ constexpr int W3_TW = 28, W3_HW = 30, W3_HP = 10 * 30, W3_PX = 8 * 28;
 constexpr int W3_XW = (W3_HP * 8 + 63) / 64;          // x-halo DMA wave-instructions (38)
 constexpr int W3_XBUF = W3_XW * 512;                  // bf16 elements per x-halo buffer
 constexpr int W3_DBUF = W3_PX * 64;                   // bf16 elements per gradient-tile buffer
-#ifndef W3_DEFAULT
-#define W3_DEFAULT 1    // generation of the fused kernel: 0 second (conv_wgrad.hip), 1 third (this file); 2, 3: experiment builds only
-#endif
 #ifndef W3_RING
 #define W3_RING 6
 #endif
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(512) void wgrad_v3_kernel(const bf16* __restrict__ 
             fuse_load(t0, true, ua);
             x_dma(t0, xbuf);
             fuse_load(tl(1), tcount > 1, ub);
-            W2_KEEP_EARLY;
+            asm volatile("" ::: "memory");
             fuse_compute(t0, ua, dbuf);
             publish();                                    // barrier 1: tile 0 staged
         }
@@ -199,7 +196,7 @@ __global__ __launch_bounds__(512) void wgrad_v3_kernel(const bf16* __restrict__ 
                 const W3Tile t1 = tl(i + 1);
                 fuse_load(tl(i + 2), i + 2 < tcount, ua);
                 x_dma(t1, xbuf + W3_XBUF);
-                W2_KEEP_EARLY;
+                asm volatile("" ::: "memory");
                 fuse_compute(t1, ub, dbuf + W3_DBUF);
                 publish();
             }
@@ -208,7 +205,7 @@ __global__ __launch_bounds__(512) void wgrad_v3_kernel(const bf16* __restrict__ 
                 const W3Tile t2 = tl(i + 2);
                 fuse_load(tl(i + 3), i + 3 < tcount, ub);
                 x_dma(t2, xbuf);
-                W2_KEEP_EARLY;
+                asm volatile("" ::: "memory");
                 fuse_compute(t2, ua, dbuf);
                 publish();
             }
@@ -290,28 +287,4 @@ __global__ __launch_bounds__(512) void wgrad_v3_kernel(const bf16* __restrict__ 
             const int co = co0 + 32 * cot + 8 * (r >> 2) + 4 * h + (r & 3);
             out[((long long)co * 9 + tap) * Cip + ci0 + 32 * cit + (lane & 31)] = acc[tap][r];
         }
-}
-
-inline int w3_supported(int H, int W, int Cip, int Cop) {
-#ifdef HYB_NO_V3
-    static const int v3 = 0;
-#else
-    static const int v3_env = hyb_env_int("HYB_WGRAD_V3", W3_DEFAULT);
-#ifdef HYB_WGRAD_EXPERIMENTS
-    static const int v3 = v3_env;                       // 2 / 3: the experiment kernels of scripts/micro/wgrad_variants
-#else
-    static const int v3 = v3_env != 0;                  // the product build knows generations 0 and 1 only: any other value means "third"
-#endif
-#endif
-    return (Cip % 64 == 0 && Cop % 64 == 0 && W % W3_TW == 0 && H % 4 == 0 && H >= 8) ? v3 : 0;
-}
-
-inline int w3_launch(dim3 grid, HybProfileHook* hook, hipStream_t st, const bf16* x, float* slab, int N, int H, int W, int Cip, int Cop, int tX, int tY,
-                     int nT, const WgradFuse& fz) {
-    static HybAttrOnce once;
-    if (int e = hyb_set_lds_attr(once, (const void*)wgrad_v3_kernel, (int)W3_LDS)) return e;
-    if (hook) hipEventRecord(hook->ev0, st);
-    hipLaunchKernelGGL(wgrad_v3_kernel, grid, dim3(512), W3_LDS, st, x, slab, N, H, W, Cip, Cop, tX, tY, nT, fz);
-    if (hook) hipEventRecord(hook->ev1, st);
-    return 0;
 }

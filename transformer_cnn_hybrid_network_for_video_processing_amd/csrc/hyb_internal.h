@@ -22,6 +22,7 @@ inline int hyb_env_int(const char* name, int dflt) { const char* v = getenv(name
 // The switches more than one function consults: every reader calls the accessor, so they cannot disagree.
 inline int hyb_sw_conv_v2() { static const int v = hyb_env_int("HYB_CONV_V2", 1); return v; }                  // asynchronous bf16 conv3x3 (conv_v2.hip)
 inline int hyb_sw_wgrad_v2() { static const int v = hyb_env_int("HYB_WGRAD_V2", 1); return v; }                // warp-specialised weight gradient
+inline int hyb_sw_wgrad_v3() { static const int v = hyb_env_int("HYB_WGRAD_V3", 1); return v; }                // its third generation (fused, conv_wgrad_v3.h)
 inline int hyb_sw_s1_wave() { static const int v = hyb_env_int("HYB_S1_WAVE", 1); return v; }                  // stage 1: wave-private forward passes
 inline int hyb_sw_s1_wave_bwd() { static const int v = hyb_env_int("HYB_S1_WAVE_BWD", 1); return v; }          // stage 1: wave-private backward pass
 inline int hyb_sw_s1_gram() { static const int v = hyb_env_int("HYB_S1_GRAM", 1); return v; }                  // stage 1: statistics from the Gram matrix
@@ -64,13 +65,12 @@ int hyb_conv_pack_weight_many(int dtype, int n, const float* const* w, void* con
                               const int* Cip, const float* s1_w, void* s1_wp, int s1_Co, int s1_Ci, int s1_Cop, hipStream_t st);
 int hyb_conv_pack_weight_fwd_many(int dtype, int n, const float* const* w, void* const* wp0, const int* Co, const int* Ci, const int* Cop, const int* Cip,
                                   const float* s1_w, void* s1_wp, int s1_Co, int s1_Ci, int s1_Cop, hipStream_t st);
-// conv_v2.hip
-int hyb_conv_v2_supported(int W, int Cip, int Cop);
-int hyb_conv_v2_ext_supported(int W, int Cip, int Cop);
-int hyb_conv_v2(const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, int stat_rows, hipStream_t st, long long xblk = 0);
-int hyb_conv_v2_pool(const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st);
-int hyb_conv_v2_ext(const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
-                    int stat_rows, hipStream_t st);
+// conv_v2.hip (the plan: conv_plan.h, conv_fwd_plan of the same shape)
+struct ConvFwdPlan;
+int hyb_conv_v2(const ConvFwdPlan& p, const void* x, const void* wp, void* y, float* part, int N, int H, int W, int Cip, int Cop, hipStream_t st, long long xblk = 0);
+int hyb_conv_v2_pool(const ConvFwdPlan& p, const void* x, const void* wp, void* pooled, const float* ss, int N, int H, int W, int Cip, int Cop, hipStream_t st);
+int hyb_conv_v2_ext(const ConvFwdPlan& p, const void* x, const void* wp, void* y, float* part, void* pooled, const float* gamma, int Co, int N, int H, int W, int Cip, int Cop,
+                    hipStream_t st);
 // conv_wgrad.hip
 int hyb_wgrad_reduce_multi(int n, const HybSlabInfo* infos, hipStream_t st);
 int hyb_wgrad_v2_supported(int dtype, int W, int Cip, int Cop);

@@ -5,6 +5,7 @@
 #include <math.h>
 #include "hyb_common.h"
 #include "hyb_internal.h"
+#include "conv_plan.h"
 
 namespace {
 // more than 64 tokens per clip: attention goes through hyb_attention_long_* (attention.hip), which need scratch
@@ -197,17 +198,15 @@ extern "C" int hyb_convstage_fwd(int dtype, int first, const void* x, const floa
 // 0: hyb_convstage_infer runs the conv -> bn_relu_pool pair with the raw output in its workspace.  HYB_POOL_FUSED=0 forces the pair (A/B).
 extern "C" int hyb_conv3x3_pool_fused(int dtype, int W, int Cip, int Cop) {
     static const int fused_env = hyb_env_int("HYB_POOL_FUSED", 1);
-    if (dtype != HYB_BF16 || W < 2 || Cip <= 0 || Cop <= 0 || Cip % 32 != 0 || Cop % 32 != 0) return 0;
-    return fused_env && hyb_sw_conv_v2() && hyb_conv_v2_supported(W, Cip, Cop) ? 1 : 0;
+    return fused_env && W >= 2 && conv_fwd_path(dtype, W, Cip, Cop).pool ? 1 : 0;
 }
 
 // 1 when a TRAINING conv stage of this shape stores the raw 2 x 2 window extremes from the conv's epilogue and applies BatchNorm + ReLU to the
-// pooled map in place (bf16 storage, a shape the asynchronous kernels take with a variant that has the epilogue: hyb_conv_v2_ext_supported);
+// pooled map in place (bf16 storage, a shape the asynchronous kernels take with a variant that has the epilogue: conv_plan.h);
 // 0: the conv -> bn_relu_pool pair.  Same results bit for bit either way.  HYB_POOL_EXT=0 forces the pair (A/B).
 extern "C" int hyb_conv3x3_pool_ext(int dtype, int W, int Cip, int Cop) {
     static const int ext_env = hyb_env_int("HYB_POOL_EXT", 1);
-    if (dtype != HYB_BF16 || W < 2 || Cip <= 0 || Cop <= 0 || Cip % 32 != 0 || Cop % 32 != 0) return 0;
-    return ext_env && hyb_sw_conv_v2() && hyb_conv_v2_ext_supported(W, Cip, Cop) ? 1 : 0;
+    return ext_env && W >= 2 && conv_fwd_path(dtype, W, Cip, Cop).ext ? 1 : 0;
 }
 
 extern "C" size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop) {
@@ -223,8 +222,8 @@ int hyb_convstage_infer_core(int dtype, int first, const void* x, const float* w
     const void* wp = prepacked;
     if (!wp) { HYB_TRY(hyb_conv_pack_weight(dtype, 0, weight, pack_ws, Co, Ci, Cop, Cip, stream)); wp = pack_ws; }
     if (hyb_conv3x3_pool_fused(dtype, W, Cip, Cop)) {
-        const int rc = hyb_conv_v2_pool(x, wp, pooled, scale_shift, N, H, W, Cip, Cop, (hipStream_t)stream);
-        return rc != HYB_NO_VARIANT ? rc : HYB_E_ARG;          // (hyb_conv3x3_pool_fused asked the dispatcher's own shape test: not reached)
+        const int rc = hyb_conv_v2_pool(conv_fwd_plan(dtype, N, H, W, Cip, Cop), x, wp, pooled, scale_shift, N, H, W, Cip, Cop, (hipStream_t)stream);
+        return rc != HYB_NO_VARIANT ? rc : HYB_E_ARG;          // (hyb_conv3x3_pool_fused asked the same plan: not reached)
     }
     HYB_CHECK_ARG(y_raw);
     HYB_TRY(hyb_conv3x3_fwd(dtype, 0, x, wp, y_raw, nullptr, nullptr, N, H, W, Ci, Cip, Cop, stream));
