@@ -200,6 +200,10 @@ int hyb_conv3x3_pool_fused(int dtype, int W, int Cip, int Cop);
 int hyb_conv3x3_pool_ext(int dtype, int W, int Cip, int Cop);
 /* pure host query: the kernel variant a non-first hyb_conv3x3_fwd of this shape runs, 100 * family + table row (family 0 first-generation rows 0-3, 1 asynchronous ring rows 0-6, 2 k32 rows 0-1: csrc/conv_plan.h) */
 int hyb_conv3x3_fwd_variant(int dtype, int N, int H, int W, int Cip, int Cop);
+/* pure host query (new symbol, hyb_abi_version() stays 9): the tiles in a workgroup's run of that launch -- the asynchronous kernels are persistent, a workgroup
+ * walks ceil(tiles / grid) consecutive tiles -- without (stats = 0: stats_partials == NULL) or with (stats = 1) partial statistics; 0 for the
+ * first-generation kernel (one tile per workgroup) and for bad arguments */
+int hyb_conv3x3_fwd_run(int dtype, int stats, int N, int H, int W, int Cip, int Cop);
 /* pure host query: the non-first weight-gradient kernel of this shape (fused = hyb_convstage_bwd's form), 100 * generation (1, 2, 3) + input channels per workgroup (32, 64) */
 int hyb_conv3x3_wgrad_variant(int dtype, int fused, int N, int H, int W, int Cip, int Cop);
 size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop);

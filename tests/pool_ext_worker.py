@@ -23,6 +23,10 @@ STAGES = {
     "odd_31x45_32to64": (2, 31, 45, 32, 64),
     "padded_24_16to24": (2, 24, 24, 16, 24),
     "tiles_in_a_row_56_32to64": (3, 56, 56, 32, 64),
+    # runs of 4 tiles per workgroup, across images and through every order of full and edge tiles (tests/conv_run_shapes.py); the cases above
+    # reach runs of 2.  Four-wave variants: the eight-wave ones with 64 channels per wave have no such epilogue.
+    "runs_257x10x58_32to64": (257, 10, 58, 32, 64),
+    "runs_257x10x58_64to128": (257, 10, 58, 64, 128),
 }
 SIGNS = "signs_28_32to64"
 SMOKE_KW = dict(cnn_channels=(32, 64, 128, 256), d_model=512, num_heads=8, num_layers=2, hidden_dim=2048)      # __graft_entry__.smoke()

@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_run_shapes import RUN_IDS, RUN_SHAPES
+
 pytestmark = pytest.mark.gpu
 
 DT = {"fp32": (0, torch.float32), "bf16": (1, torch.bfloat16)}
@@ -151,8 +153,10 @@ def _fuzz_shapes(seed, count, cis, cos):
 
 @pytest.mark.parametrize("ci,co,n,h,w", _fuzz_shapes(101, 10, [32, 64, 128], [32, 64, 128, 256]))
 def test_conv3x3_fwd_stats_dgrad_exact_fuzz(ci, co, n, h, w):
-    """Seeded shape fuzz of the asynchronous bf16 conv kernel (tile edges, 1-pixel images, several tiles per workgroup, all channel
-    configurations): forward + statistics, and dgrad through the same kernel with mode-1 weights."""
+    """Seeded shape fuzz of the asynchronous bf16 conv kernel (tile edges, 1-pixel images, all channel configurations): forward +
+    statistics, and dgrad through the same kernel with mode-1 weights.  Several tiles per workgroup holds for the statistics launch only
+    (its grid is at most the statistics rows, which count coarser tiles); the dgrad launch has at most 160 tiles, one per workgroup --
+    runs of tiles without statistics: the *_on_runs_of_tiles tests below."""
     code, tdt = DT["bf16"]
     g = torch.Generator().manual_seed(ci * 7 + co * 3 + h * 11 + w)
     x = sparse_int((n, ci, h, w), g, 0, 2, 0.5)
@@ -199,6 +203,100 @@ def test_conv3x3_wgrad_exact_fuzz(ci, co, n, h, w):
     ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
     L().call("hyb_conv3x3_wgrad", code, 0, xin.data_ptr(), dyn.data_ptr(), dw.data_ptr(), n, h, w, ci, cip, co, cop, ws.data_ptr(), nb, st())
     assert torch.equal(dw.cpu(), wt.grad)
+
+
+# ---- the asynchronous kernels where a workgroup walks a run of several tiles (tests/conv_run_shapes.py) -------------------------------------
+# Persistent workgroups carry the halo ping-pong, the weight-ring position, the prefetch of the next tile and the count of epilogue stores
+# still in flight from one tile to the next.  Without statistics (the dgrad launches of a training step, the pooled epilogue of predict())
+# a run is longer than one tile only above 256 / 512 tiles, which no shape above reaches.  Every launch below runs twice into buffers of
+# their own and the two results must be bit-equal: a counted wait that is one too loose shows first as a difference between runs.
+def _fwd_twice(cin, cout, n, h, w, xin, wp, with_stats):
+    """hyb_conv3x3_fwd (bf16, non-first) twice -> [(y NHWC, stats [2][cout] or None)] * 2; y pre-filled with 7.0: an unwritten pixel shows"""
+    code, tdt = DT["bf16"]
+    out = []
+    for _ in range(2):
+        y = torch.full((n, h, w, cout), 7.0, dtype=tdt, device="cuda")
+        stats = part = None
+        if with_stats:
+            stats = torch.full((2, cout), 7.0, device="cuda")
+            part = torch.empty(L().query("hyb_conv_stats_workspace", cout), dtype=torch.uint8, device="cuda")
+        L().call("hyb_conv3x3_fwd", code, 0, xin, wp, y, stats, part, n, h, w, cin, cin, cout, st())
+        out.append((y, stats))
+    assert torch.equal(out[0][0], out[1][0]), "two runs of the same launch differ"
+    if with_stats:
+        assert torch.equal(out[0][1], out[1][1]), "the statistics of two runs of the same launch differ"
+    return out[0]
+
+
+def _pack(wt, mode, cop, cip):
+    """the layer's weights [co][ci][3][3] in the forward (mode 0) or the dgrad (mode 1) layout"""
+    code, tdt = DT["bf16"]
+    wp = torch.empty(cop * 9 * cip, dtype=tdt, device="cuda")
+    L().call("hyb_conv_pack_weight", code, mode, wt.cuda().contiguous(), wp, wt.shape[0], wt.shape[1], cop, cip, st())
+    return wp
+
+
+def test_run_shapes_reach_every_asynchronous_variant_with_runs_of_three_tiles():
+    q = L().query
+    assert {q("hyb_conv3x3_fwd_variant", 1, n, h, w, ci, co) for (ci, co, n, h, w) in RUN_SHAPES} == FWD_ASYNC_CODES
+    for (ci, co, n, h, w) in RUN_SHAPES:
+        for stats in (0, 1):
+            assert q("hyb_conv3x3_fwd_run", 1, stats, n, h, w, ci, co) >= 3, (ci, co, n, h, w, stats)
+
+
+@pytest.mark.parametrize("ci,co,n,h,w", RUN_SHAPES, ids=RUN_IDS)
+def test_conv3x3_fwd_exact_on_runs_of_tiles(ci, co, n, h, w):
+    """The plain epilogue (no statistics): grid of 256 / 512 workgroups, runs of 3 - 4 tiles."""
+    code, tdt = DT["bf16"]
+    g = torch.Generator().manual_seed(ci * 1000 + co + h)
+    x = sparse_int((n, ci, h, w), g, 0, 2, 0.5)
+    wt = sparse_int((co, ci, 3, 3), g, -2, 2, 0.15)
+    want = F.conv2d(x, wt, padding=1)
+    assert want.abs().max() <= 256
+    cip, cop = pad32(ci), pad32(co)
+    y, _ = _fwd_twice(cip, cop, n, h, w, to_nhwc(x, code, tdt, cip), _pack(wt, 0, cop, cip), False)
+    assert torch.equal(to_nchw(y, code, co).cpu(), want)
+    if cop > co:
+        assert torch.all(y[..., co:] == 0)
+
+
+@pytest.mark.parametrize("ci,co,n,h,w", RUN_SHAPES, ids=RUN_IDS)
+def test_conv3x3_dgrad_exact_on_runs_of_tiles(ci, co, n, h, w):
+    """The same launches as the dgrad of a layer with co input and ci output channels: the kernel reads dy [n, ci, h, w] and mode-1 packed
+    weights and writes dx [n, co, h, w]; compared with autograd of F.conv2d."""
+    code, tdt = DT["bf16"]
+    lci, lco = co, ci                                   # the layer's channels
+    g = torch.Generator().manual_seed(7 + ci * 1000 + co + h)
+    wt = sparse_int((lco, lci, 3, 3), g, -2, 2, 0.15)
+    dy = sparse_int((n, lco, h, w), g, -1, 1, 0.4)
+    x = torch.zeros(n, lci, h, w, requires_grad=True)
+    F.conv2d(x, wt, padding=1).backward(dy)
+    want = x.grad
+    assert want.abs().max() <= 256
+    cip, cop = pad32(lci), pad32(lco)
+    assert L().query("hyb_conv3x3_fwd_variant", 1, n, h, w, cop, cip) == L().query("hyb_conv3x3_fwd_variant", 1, n, h, w, ci, co)
+    dx, _ = _fwd_twice(cop, cip, n, h, w, to_nhwc(dy, code, tdt, cop), _pack(wt, 1, cop, cip), False)
+    assert torch.equal(to_nchw(dx, code, lci).cpu(), want)
+
+
+@pytest.mark.parametrize("ci,co,n,h,w", RUN_SHAPES, ids=RUN_IDS)
+def test_conv3x3_fwd_and_stats_exact_on_runs_of_tiles(ci, co, n, h, w):
+    """The statistics epilogue over the same shapes (512 statistics rows: the same grid and runs).  The weights are thinned with the input
+    channels so that every per-channel sum of squares over these many pixels stays an exact fp32 integer."""
+    code, tdt = DT["bf16"]
+    g = torch.Generator().manual_seed(13 + ci * 1000 + co + h)
+    x = sparse_int((n, ci, h, w), g, 0, 2, 0.5)
+    wt = sparse_int((co, ci, 3, 3), g, -2, 2, min(0.15, 0.8 / ci))
+    want = F.conv2d(x, wt, padding=1)
+    assert want.abs().max() <= 256
+    assert (want * want).sum(dim=(0, 2, 3)).max() < 2 ** 24          # the statistics comparison below is exact
+    cip, cop = pad32(ci), pad32(co)
+    y, stats = _fwd_twice(cip, cop, n, h, w, to_nhwc(x, code, tdt, cip), _pack(wt, 0, cop, cip), True)
+    assert torch.equal(to_nchw(y, code, co).cpu(), want)
+    if cop > co:
+        assert torch.all(y[..., co:] == 0)
+    assert torch.equal(stats[0, :co].cpu(), want.sum(dim=(0, 2, 3)))
+    assert torch.equal(stats[1, :co].cpu(), (want * want).sum(dim=(0, 2, 3)))
 
 
 @pytest.mark.parametrize("mode", ["bf16", "fp32"])

@@ -61,6 +61,13 @@ STAGES = [
     pytest.param(2, 30, 44, 32, 64, id="edge_tiles_30x44_32to64"),
     pytest.param(2, 31, 45, 32, 64, id="odd_31x45_32to64"),
     pytest.param(2, 24, 24, 16, 24, id="padded_24x24_16to24"),
+    # more than 256 / 512 tiles: a workgroup of the pooled launch walks a run of 3 - 4 tiles, across images and through every order of full
+    # and edge tiles (tests/conv_run_shapes.py); every case above is one tile per workgroup
+    pytest.param(257, 10, 58, 32, 64, id="runs_257x10x58_32to64"),
+    pytest.param(107, 18, 112, 32, 64, id="runs_107x18x112_32to64"),
+    pytest.param(257, 10, 58, 64, 128, id="runs_257x10x58_64to128"),
+    pytest.param(129, 10, 58, 128, 256, id="runs_129x10x58_128to256"),
+    pytest.param(65, 18, 112, 64, 256, id="runs_65x18x112_64to256"),
 ]
 
 

@@ -692,6 +692,13 @@ extern "C" int hyb_conv3x3_fwd_variant(int dtype, int N, int H, int W, int Cip, 
     return conv_fwd_plan(dtype, N, H, W, Cip, Cop).code();
 }
 
+extern "C" int hyb_conv3x3_fwd_run(int dtype, int stats, int N, int H, int W, int Cip, int Cop) {
+    if ((dtype != HYB_F32 && dtype != HYB_BF16) || N <= 0 || H <= 0 || W <= 0 || Cip <= 0 || Cop <= 0 || Cip % 32 != 0 || Cop % 32 != 0) return 0;
+    const ConvFwdPlan p = conv_fwd_plan(dtype, N, H, W, Cip, Cop);
+    if (p.v.family == CONV_GEN1) return 0;
+    return (int)hyb_cdiv(p.num_tiles, stats ? p.gx_stats : p.gx);         // conv_v2.hip: tchunk of the grid launch_flavour gives the kernel
+}
+
 extern "C" int hyb_conv3x3_fwd(int dtype, int first, const void* x, const void* wp, void* y, float* stats, float* stats_partials, int N,
                                int H, int W, int Ci, int Cip, int Cop, void* stream) {
     HYB_CHECK_ARG(x && wp && y && N > 0 && H > 0 && W > 0 && Cop > 0 && Cop % 32 == 0);
