@@ -326,6 +326,24 @@ int hyb_cross_entropy_opts_bwd(const float* logits, const long long* target, con
                                long long ignore_index, int has_ignore, float label_smoothing, const float* dloss /* [1] */,
                                float* dlogits, int B, int C, void* stream);
 
+/* hyb_cross_entropy_mix_*: hyb_cross_entropy_opts_* with TWO targets per clip, the labels of a Mixup / CutMix batch (new symbols,
+ *   hyb_abi_version() stays 9).  Behind `target`: target_b [B] class indices and lam [B] floats, both read on the device.  With
+ *   a_b = target[b], c_b = target_b[b], l_b = lam[b], and term(b, y), d(b, y) = keep w[y] the per-clip term and den share defined above:
+ *     num = sum_b [ l_b term(b, a_b) + (1 - l_b) term(b, c_b) ],   den = sum_b [ l_b d(b, a_b) + (1 - l_b) d(b, c_b) ],   loss = num / den,
+ *     dlogits[b,c] = (dloss / den) [ l_b r(b, a_b, c) + (1 - l_b) r(b, c_b, c) ],  r the bracket of hyb_cross_entropy_opts_bwd's formula.
+ *   Each side keeps the rules above on its own: a target equal to ignore_index drops that side, a kept target outside [0, C) poisons the
+ *   loss with NaN.  l_b == 1 does not look at c_b and l_b == 0 does not look at a_b (an out-of-range index there changes nothing); an l_b
+ *   outside [0, 1], NaN included, poisons den: the loss is NaN.  den == 0: NaN loss, zero gradient.  The log-sum-exp is formed once per
+ *   clip; numerator and den go through the same fixed trees.  lam == 1 everywhere gives hyb_cross_entropy_opts_* bit for bit.  With a
+ *   uniform lam, target_b a permutation of target and nothing ignored the loss is lam CE(z, a) + (1 - lam) CE(z, c) of
+ *   torch.nn.functional.cross_entropy for any weights and smoothing.  HYB_E_ARG as for the *_opts_* family, and a NULL target_b or lam. */
+int hyb_cross_entropy_mix_fwd(const float* logits, const long long* target, const long long* target_b /* [B] */, const float* lam /* [B] */,
+                              const float* weight /* [C] or NULL */, long long ignore_index, int has_ignore, float label_smoothing,
+                              float* loss /* [1] */, int B, int C, void* stream);
+int hyb_cross_entropy_mix_bwd(const float* logits, const long long* target, const long long* target_b /* [B] */, const float* lam /* [B] */,
+                              const float* weight /* [C] or NULL */, long long ignore_index, int has_ignore, float label_smoothing,
+                              const float* dloss /* [1] */, float* dlogits, int B, int C, void* stream);
+
 /* ---- model-level entry points: whole CNN backbone / whole temporal part in ONE call each way ---------------------------
  * They chain the stage-level entry points above on the caller's stream; their purpose is host time (a training step is three
  * operator calls each way), not different arithmetic: results are bit-identical to calling the stages one by one.
@@ -412,6 +430,26 @@ int hyb_temporal_ce_opts_bwd(int dtype, const float* dloss, const float* logits,
                              float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
                              int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* hyb_temporal_ce_mix_*: hyb_temporal_ce_opts_* with target_b [B] and lam [B] (hyb_cross_entropy_mix_*) behind the target: the same
+ *   launches, the same ce_scratch, all three read when the kernels run -- a captured call replays with new labels and new lam.  Results
+ *   equal hyb_temporal_* followed by hyb_cross_entropy_mix_* bit for bit; shapes the fused tail does not take run hyb_cross_entropy_mix_*
+ *   as launches of their own.  (New symbols, hyb_abi_version() stays 9.) */
+int hyb_temporal_ce_mix_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                            const float* head_w, const float* head_b, const float* mask, const long long* target,
+                            const long long* target_b /* [B] */, const float* lam /* [B] */,
+                            const float* weight /* [classes] or NULL */, long long ignore_index, int has_ignore, float label_smoothing,
+                            void* feat, void* tok, void* enc_saved, void* enc_out, float* logits, float* loss, float* ce_scratch, int B,
+                            int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
+                            unsigned long long seed, const unsigned long long* seed_inc, void* stream);
+int hyb_temporal_ce_mix_bwd(int dtype, const float* dloss, const float* logits, const long long* target,
+                            const long long* target_b /* [B] */, const float* lam /* [B] */,
+                            const float* weight /* [classes] or NULL */, long long ignore_index, int has_ignore, float label_smoothing,
+                            const float* token_w, const float* const* enc_params, const float* head_w, const float* mask, const void* feat,
+                            const void* enc_saved, const void* enc_out, float* dtoken_w, float* dtoken_b, float* const* enc_grads,
+                            float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
+                            int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- FCT, the reference's "Fully Convolutional Transformer" (FCT.py:24-254; SURVEY.md section 8f-1, first "next" row) -----------
  * FORWARD entry points (the backward is the next step of this row).  Arrays are NHWC fp32 with the TRUE channel count
@@ -504,6 +542,25 @@ int hyb_clips_u8_transform(const unsigned char* src /* [B][Tin][Hin][Win][C] uin
                            const float* mean_invstd /* device, [2][C]: mean then 1/std; or NULL = no normalisation */,
                            float* dst               /* [B][Tout][C][Ho][Wo] fp32 */,
                            int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
+
+/* hyb_clips_u8_transform_mix: the same pass with Mixup / CutMix (new symbol, hyb_abi_version() stays 9).  `mix`: one more int32 row of 8 per
+ * clip, in device memory: {partner, kind, by0, bx0, bh, bw, lam_bits, 0}.  own[b] is what hyb_clips_u8_transform writes for clip b from its
+ * own params row (crop, flip, temporal window, / 255, mean / std); the partner's value own[partner] comes from the PARTNER's params row,
+ * temporal window included.
+ *   kind 0 (none):   out = own[b]; the partner is not read; the bits of hyb_clips_u8_transform.
+ *   kind 1 (Mixup):  out = lam*own[b] + (1-lam)*own[partner] per element in fp32, after both operands' full pipelines; lam = the fp32
+ *                    whose bits are lam_bits, clamped into [0, 1], a NaN counts as 1.
+ *   kind 2 (CutMix): inside the box [by0, by0+bh) x [bx0, bx0+bw) of OUTPUT coordinates (the same box for every frame of the clip) the pixel
+ *                    is own[partner] at the same position, outside it own[b]; no arithmetic on the values -- every output element is bit
+ *                    for bit one of the two -- and a pixel gathers only the taps of the clip it comes from.  lam_bits is not read.
+ * The rows are clamped before use like the params rows: partner into [0, B-1], by0 into [0, Ho] and bh into [0, Ho-by0], bx0 into [0, Wo]
+ * and bw into [0, Wo-bx0], a kind outside 0..2 counts as 0: no row value reads outside src.  Same limits as hyb_clips_u8_transform. */
+int hyb_clips_u8_transform_mix(const unsigned char* src /* [B][Tin][Hin][Win][C] uint8 */,
+                               const int* params        /* device, [B][8] int32, one row per CLIP */,
+                               const int* mix           /* device, [B][8] int32, one row per CLIP */,
+                               const float* mean_invstd /* device, [2][C]: mean then 1/std; or NULL = no normalisation */,
+                               float* dst               /* [B][Tout][C][Ho][Wo] fp32 */,
+                               int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
 
 /* ---- ResNet-bottleneck backbone `Encoder_32K` (only bytecode of it ships with the reference:
  * __pycache__/AE_256_32K.cpython-38.pyc, read as data -- `Bottleneck` src L21-53, `Encoder_32K` src L58-137).  NHWC fp32 with the

@@ -15,6 +15,8 @@ waits on an event.  No CPU fallback for the device leg.
 Augmentation (``ClipTransform``): crop, bilinear resize, horizontal flip, temporal sub-sampling and mean/std normalisation happen in
 that same expansion pass (``hyb_clips_u8_transform``), from ONE int32 parameter row per clip drawn on the host -- every frame of a
 clip gets the same crop and flip, which per-image host transforms get wrong by default -- so the host never touches a pixel.
+Mixup and CutMix (``ClipTransform(mixup_alpha=..., cutmix_alpha=...)``) ride in that pass too (``hyb_clips_u8_transform_mix``): one more
+int32 row per clip names its partner and lam or the box, the labels come out as a ``MixTarget`` for the fused two-target loss.
 """
 import csv
 import os
@@ -23,6 +25,7 @@ import numpy as np
 import torch
 
 from ._lib import lib
+from .modules import MixTarget
 
 
 class ClipCSVDataset(torch.utils.data.Dataset):
@@ -81,7 +84,9 @@ class ClipPipeline:
     with ``collate_fn=collate_clips``, or SyntheticClipSource) and yields device tensors (clips fp32 [B,T,3,H,W] in [0,1], labels),
     ``depth`` batches ahead of the consumer: pinned staging buffers, async H2D on its own stream, ToTensor on the device.
     ``transform`` (a ClipTransform): the clips come out augmented instead, fp32 [B,Tout,C,Ho,Wo] -- one parameter row per clip is drawn
-    on the host, copied next to the bytes, and hyb_clips_u8_transform takes the ToTensor kernel's place on the copy stream."""
+    on the host, copied next to the bytes, and hyb_clips_u8_transform takes the ToTensor kernel's place on the copy stream.
+    A transform that mixes (``transform.mixing()``): a mix row and a lam per clip travel with the parameter rows, the partners' labels are
+    gathered on the host before the copy, hyb_clips_u8_transform_mix is the kernel, and the second item is ``MixTarget(y, y[partner], lam)``."""
 
     def __init__(self, source, device="cuda", depth=2, transform=None):
         self.source, self.depth, self.transform = source, max(1, int(depth)), transform
@@ -111,6 +116,13 @@ class ClipPipeline:
             for s in self._slots:
                 s["host_p"] = torch.empty(B, 8, dtype=torch.int32).pin_memory()
                 s["dev_p"] = torch.empty(B, 8, dtype=torch.int32, device=self.device)
+                if self.transform.mixing():
+                    s["host_m"] = torch.empty(B, 8, dtype=torch.int32).pin_memory()
+                    s["dev_m"] = torch.empty(B, 8, dtype=torch.int32, device=self.device)
+                    s["host_yb"] = torch.empty(B, dtype=torch.int64).pin_memory()
+                    s["y_b"] = torch.empty(B, dtype=torch.int64, device=self.device)
+                    s["host_lam"] = torch.empty(B, dtype=torch.float32).pin_memory()
+                    s["lam"] = torch.empty(B, dtype=torch.float32, device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))      # mean_invstd was uploaded on the consumer's stream
 
     def _issue(self, slot, batch):
@@ -125,6 +137,12 @@ class ClipPipeline:
         s["host_y"].numpy()[...] = np.asarray(labels, dtype=np.int64)
         if self.transform is not None:
             s["host_p"].numpy()[...] = self.transform.sample(B, T, H, W)      # one row per clip: all T frames share crop and flip
+        mixing = self.transform is not None and self.transform.mixing()
+        if mixing:
+            rows, lam, partner = self.transform.sample_mix(B, *self.transform.size)
+            s["host_m"].numpy()[...] = rows
+            s["host_lam"].numpy()[...] = lam
+            s["host_yb"].numpy()[...] = s["host_y"].numpy()[partner]            # the partners' labels, gathered here: the device only copies
         with torch.cuda.stream(self.stream):
             s["dev_u8"].copy_(s["host"], non_blocking=True)
             s["y"].copy_(s["host_y"], non_blocking=True)
@@ -133,8 +151,15 @@ class ClipPipeline:
             else:
                 s["dev_p"].copy_(s["host_p"], non_blocking=True)
                 Tout, Ho, Wo = s["x"].shape[1], s["x"].shape[3], s["x"].shape[4]
-                lib.call("hyb_clips_u8_transform", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho, Wo,
-                         self.stream.cuda_stream)
+                if mixing:
+                    s["dev_m"].copy_(s["host_m"], non_blocking=True)
+                    s["y_b"].copy_(s["host_yb"], non_blocking=True)
+                    s["lam"].copy_(s["host_lam"], non_blocking=True)
+                    lib.call("hyb_clips_u8_transform_mix", s["dev_u8"], s["dev_p"], s["dev_m"], self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho,
+                             Wo, self.stream.cuda_stream)
+                else:
+                    lib.call("hyb_clips_u8_transform", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho, Wo,
+                             self.stream.cuda_stream)
             s["ready"].record(self.stream)
 
     def __iter__(self):
@@ -160,7 +185,7 @@ class ClipPipeline:
             s = self._slots[slot]
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(s["ready"])                        # GPU-side wait only: the host does not block
-            yield s["x"], s["y"]
+            yield s["x"], (MixTarget(s["y"], s["y_b"], s["lam"]) if "lam" in s else s["y"])
             s["free"].record(torch.cuda.current_stream(self.device))      # everything the consumer enqueued on x / y so far
 
 
@@ -177,11 +202,17 @@ class ClipTransform:
     frames        output frames per clip (None: all of them, stride 1); frame_stride = (lo, hi): the stride is drawn among lo..hi
     seed          of the numpy Generator that draws the rows; data-parallel ranks pass ``seed + rank`` so that they augment differently
     train=False   the deterministic evaluation transform: largest centred crop of the output's aspect ratio, no flip, the smallest
-                  stride, the centred temporal window
+                  stride, the centred temporal window, no mixing
+    mixup_alpha, cutmix_alpha   > 0 switches Mixup / CutMix on (both 0, the default: nothing mixes, ``sample()`` draws what it always drew and
+                  the plain kernel runs); lam ~ Beta(alpha, alpha).  The mix rows come from ``sample_mix`` and a SECOND Generator derived
+                  from ``seed``: the crop rows of a seed are the same with mixing on and off
+    mix_prob      probability that a batch (mix_mode="clip": a clip) is mixed at all
+    switch_prob   probability of CutMix when both alphas are > 0
+    mix_mode      "batch": one kind and one lam per batch; "clip": every clip draws its own.  The partner is a random permutation either way
     """
 
     def __init__(self, size, scale=(0.35, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, mean=None, std=None, frames=None, frame_stride=(1, 1), seed=0,
-                 train=True):
+                 train=True, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, switch_prob=0.5, mix_mode="batch"):
         self.size = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
         if min(self.size) <= 0:
             raise ValueError(f"size must be positive, got {size!r}")
@@ -208,6 +239,16 @@ class ClipTransform:
             raise ValueError("frame_stride is a (lo, hi) range with 1 <= lo <= hi")
         self.seed, self.train = int(seed), bool(train)
         self.rng = np.random.default_rng(self.seed)
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.mix_prob, self.switch_prob = float(mix_prob), float(switch_prob)
+        if self.mixup_alpha < 0 or self.cutmix_alpha < 0:
+            raise ValueError("mixup_alpha and cutmix_alpha must be >= 0")
+        if not (0.0 <= self.mix_prob <= 1.0 and 0.0 <= self.switch_prob <= 1.0):
+            raise ValueError("mix_prob and switch_prob are probabilities")
+        if mix_mode not in ("batch", "clip"):
+            raise ValueError(f"mix_mode must be 'batch' or 'clip', got {mix_mode!r}")
+        self.mix_mode = mix_mode
+        self.mix_rng = np.random.default_rng([self.seed, 0x6d6978])          # its own stream: the crop rows do not move when mixing is switched on
 
     def out_frames(self, Tin):
         if self.frames is not None and self.frames > Tin:
@@ -273,3 +314,48 @@ class ClipTransform:
                     t0 = (Tin - ((Tout - 1) * stride + 1)) // 2
             rows[b] = (y0, x0, h, w, flip, t0, stride, 0)
         return rows
+
+    def mixing(self):
+        """Whether this transform mixes clips (ClipPipeline then calls the mix kernel and yields MixTargets)."""
+        return self.train and (self.mixup_alpha > 0 or self.cutmix_alpha > 0)
+
+    def _mix_draw(self, Ho, Wo):
+        """One (kind, lam, box) draw: kind 1 Mixup, 2 CutMix (the usual recipe: centre uniform, sides sqrt(1 - lam) of the output's, clipped to the
+        frame, lam recomputed from the clipped box), 0 when mix_prob says not this time."""
+        g = self.mix_rng
+        if g.random() >= self.mix_prob:
+            return 0, np.float32(1), (0, 0, 0, 0)
+        cut = self.cutmix_alpha > 0 and (self.mixup_alpha <= 0 or g.random() < self.switch_prob)
+        alpha = self.cutmix_alpha if cut else self.mixup_alpha
+        lam = float(g.beta(alpha, alpha))
+        if not cut:
+            return 1, np.float32(lam), (0, 0, 0, 0)
+        r = np.sqrt(1.0 - lam)
+        h, w = int(Ho * r), int(Wo * r)
+        cy, cx = int(g.integers(0, Ho)), int(g.integers(0, Wo))
+        y0, y1 = min(max(cy - h // 2, 0), Ho), min(max(cy + h // 2, 0), Ho)
+        x0, x1 = min(max(cx - w // 2, 0), Wo), min(max(cx + w // 2, 0), Wo)
+        bh, bw = y1 - y0, x1 - x0
+        return 2, np.float32(1.0 - bh * bw / float(Ho * Wo)), (y0, x0, bh, bw)
+
+    def sample_mix(self, B, Ho, Wo):
+        """-> (rows int32 [B,8], lam fp32 [B], partner int64 [B]): one mix row {partner, kind, by0, bx0, bh, bw, lam_bits, 0} per clip for
+        hyb_clips_u8_transform_mix, the label weight of each clip's own class (CutMix: 1 - box area / frame area, from the clipped box) and the
+        partner permutation.  Un-mixed clips: kind 0, lam 1, partner = self."""
+        rows = np.zeros((B, 8), dtype=np.int32)
+        lam = np.ones(B, dtype=np.float32)
+        partner = np.arange(B, dtype=np.int64)
+        rows[:, 0] = partner
+        if not self.mixing():
+            rows[:, 6] = lam.view(np.int32)
+            return rows, lam, partner
+        perm = self.mix_rng.permutation(B).astype(np.int64)
+        shared = self._mix_draw(Ho, Wo) if self.mix_mode == "batch" else None
+        for b in range(B):
+            kind, l, (y0, x0, bh, bw) = shared if shared is not None else self._mix_draw(Ho, Wo)
+            if kind == 0:
+                continue
+            partner[b], lam[b] = perm[b], l
+            rows[b, :6] = (perm[b], kind, y0, x0, bh, bw)
+        rows[:, 6] = lam.view(np.int32)
+        return rows, lam, partner

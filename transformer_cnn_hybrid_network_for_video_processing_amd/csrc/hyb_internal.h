@@ -89,14 +89,17 @@ int hyb_temporal_tail_ok(int B, int S, int D, int C, int ln_rows);
 // the cross-entropy loss's options as the *_opts_* entry points and kernels carry them (weight: [C] device floats, or nullptr = all ones)
 struct HybCeOpts { const float* weight; long long ignore_index; int has_ignore; float label_smoothing; };
 int hyb_ce_opts_ok(const HybCeOpts& o);
-// ce != nullptr (a target is given): the loss with options, in the same one launch
+// the second target and the mixing weight of every clip as the *_mix_* entry points and kernels carry them ([B] each, device memory)
+struct HybCeMix { const long long* target_b; const float* lam; };
+// ce != nullptr (a target is given): the loss with options, in the same one launch; mix != nullptr (needs ce): two targets per clip
 int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float* gamma, const float* beta, void* enc_out, float* stats, int B, int S, int D,
                           float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const float* W, const float* bias,
-                          float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st, const HybCeOpts* ce = nullptr);
+                          float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st, const HybCeOpts* ce = nullptr,
+                          const HybCeMix* mix = nullptr);
 int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* W, const void* enc_out,
                           const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part, int ln_rows, float* head_part, int B, int S,
                           int D, int C, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, hipStream_t st,
-                          const HybCeOpts* ce = nullptr);
+                          const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr);
 // linear.hip
 int hyb_linear_bwd_wt(int dtype, const void* x, int ldx, const float* W, const void* Wt, const void* y, const void* dy, void* dx, int accumulate_dx, float* dW,
                       float* db, int M, int N, int K, int relu, void* ws, size_t ws_bytes, hipStream_t st);

@@ -460,6 +460,96 @@ __global__ __launch_bounds__(256) void ce_opts_bwd_kernel(const float* __restric
     for (int c = 0; c < C; ++c) dlogits[(long long)b * C + c] = ce_clip_dlogit_opts(logits + (long long)b * C, o.weight, t, C, c, g, o);
 }
 
+// ---- two targets per clip (the labels of a Mixup / CutMix batch): a_b = target[b], c_b = target_b[b], l_b = lam[b], read on the device ----
+//   num = sum_b [ l_b term(b, a_b) + (1 - l_b) term(b, c_b) ],  den = sum_b [ l_b d(b, a_b) + (1 - l_b) d(b, c_b) ],  loss = num / den,
+// term = ce_clip_loss_opts and d = ce_clip_den above, each side under its own ignore_index / out-of-range rule.  The log-sum-exp (and the
+// smoothing sum, which does not depend on the target) is formed once per clip and serves both sides; a side is written with
+// ce_clip_loss_opts' expressions, and l_b == 1 returns the a side as it stands -- not 1 * a + 0 * c -- so that lam == 1 everywhere gives the
+// bits of the *_opts_* family and never looks at c_b (l_b == 0: the mirror image).  An l_b outside [0, 1] or NaN poisons den.
+// (ce_side_loss / ce_side_dlogit are SECOND COPIES of the expressions in ce_clip_loss_opts / ce_clip_dlogit_opts, which keep theirs so that
+// the *_opts_* kernels keep their instructions: a change to either formula must be made in both; tests/test_gpu_mix_loss.py compares
+// lam == 1 and lam == 0 with the *_opts_* operators bit for bit, loss and gradient, and fails when one copy is forgotten.)
+__device__ __forceinline__ float ce_side_loss(const float* lg, const float* w, long long t, int C, float lse, float sm, const HybCeOpts& o) {
+    if (!ce_keep(t, o)) return 0.f;
+    if (!(t >= 0 && t < C)) return NAN;
+    float r = (1.f - o.label_smoothing) * (ce_w(w, (int)t) * (lse - lg[(int)t]));
+    if (o.label_smoothing > 0.f) r += (o.label_smoothing / (float)C) * sm;
+    return r;
+}
+__device__ __forceinline__ float ce_clip_den_mix(const float* w, long long ta, long long tc, float l, int C, const HybCeOpts& o) {
+    if (!(l >= 0.f && l <= 1.f)) return NAN;
+    if (l == 1.f) return ce_clip_den(w, ta, C, o);
+    if (l == 0.f) return ce_clip_den(w, tc, C, o);
+    return l * ce_clip_den(w, ta, C, o) + (1.f - l) * ce_clip_den(w, tc, C, o);
+}
+__device__ __forceinline__ float ce_clip_loss_mix(const float* lg, const float* w, long long ta, long long tc, float l, int C, const HybCeOpts& o) {
+    const bool use_a = !(l == 0.f), use_c = !(l == 1.f);
+    if (!((use_a && ce_keep(ta, o)) || (use_c && ce_keep(tc, o)))) return 0.f;
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(lg[c] - mx);
+    const float lse = logf(s) + mx;
+    float sm = 0.f;
+    if (o.label_smoothing > 0.f)
+        for (int c = 0; c < C; ++c) sm += ce_w(w, c) * (lse - lg[c]);
+    if (!use_c) return ce_side_loss(lg, w, ta, C, lse, sm, o);
+    if (!use_a) return ce_side_loss(lg, w, tc, C, lse, sm, o);
+    return l * ce_side_loss(lg, w, ta, C, lse, sm, o) + (1.f - l) * ce_side_loss(lg, w, tc, C, lse, sm, o);
+}
+// one side's d(term)/d(logits[c]) before the scale g (ce_clip_dlogit_opts' expressions); p = softmax(logits)[c], ws = sum_k w[k]
+__device__ __forceinline__ float ce_side_dlogit(const float* w, long long t, int C, int c, float p, float ws, const HybCeOpts& o) {
+    if (!ce_keep(t, o)) return 0.f;
+    if (!(t >= 0 && t < C)) return NAN;
+    float r = (1.f - o.label_smoothing) * (ce_w(w, (int)t) * (p - (c == (int)t ? 1.f : 0.f)));
+    if (o.label_smoothing > 0.f) r += (o.label_smoothing / (float)C) * (p * ws - ce_w(w, c));
+    return r;
+}
+__device__ __forceinline__ float ce_clip_dlogit_mix(const float* lg, const float* w, long long ta, long long tc, float l, int C, int c, float g,
+                                                    const HybCeOpts& o) {
+    const bool use_a = !(l == 0.f), use_c = !(l == 1.f);
+    if (!((use_a && ce_keep(ta, o)) || (use_c && ce_keep(tc, o)))) return 0.f;      // (rows of clips with nothing kept stay 0 whatever g is)
+    float mx = -INFINITY;
+    for (int k = 0; k < C; ++k) mx = fmaxf(mx, lg[k]);
+    float s = 0.f;
+    for (int k = 0; k < C; ++k) s += expf(lg[k] - mx);
+    const float p = expf(lg[c] - mx) / s;
+    float ws = 0.f;
+    if (o.label_smoothing > 0.f)
+        for (int k = 0; k < C; ++k) ws += ce_w(w, k);
+    if (!use_c) return g * ce_side_dlogit(w, ta, C, c, p, ws, o);
+    if (!use_a) return g * ce_side_dlogit(w, tc, C, c, p, ws, o);
+    return g * (l * ce_side_dlogit(w, ta, C, c, p, ws, o) + (1.f - l) * ce_side_dlogit(w, tc, C, c, p, ws, o));
+}
+// den by the calling workgroup, as ce_den
+__device__ __forceinline__ float ce_den_mix(const long long* __restrict__ target, const HybCeMix& m, const float* w, int B, int C, const HybCeOpts& o,
+                                            float* part) {
+    float acc = 0.f;
+    if (threadIdx.x < 256)
+        for (int i = threadIdx.x; i < B; i += 256) acc += ce_clip_den_mix(w, target[i], m.target_b[i], m.lam[i], C, o);
+    return ce_tree_sum(acc, part);
+}
+__global__ __launch_bounds__(256) void ce_mix_fwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target, float* __restrict__ loss,
+                                                         int B, int C, HybCeOpts o, HybCeMix m) {
+    __shared__ float part[256];
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) acc += ce_clip_loss_mix(logits + (long long)b * C, o.weight, target[b], m.target_b[b], m.lam[b], C, o);
+    const float num = ce_tree_sum(acc, part);
+    const float den = ce_den_mix(target, m, o.weight, B, C, o, part);
+    if (threadIdx.x == 0) loss[0] = ce_loss_opts(num, den);
+}
+__global__ __launch_bounds__(256) void ce_mix_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                         const float* __restrict__ dloss, float* __restrict__ dlogits, int B, int C, HybCeOpts o,
+                                                         HybCeMix m) {
+    __shared__ float part[256];
+    const float g = ce_gscale_opts(dloss[0], ce_den_mix(target, m, o.weight, B, C, o, part));
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const long long ta = target[b], tc = m.target_b[b];
+    const float l = m.lam[b];
+    for (int c = 0; c < C; ++c) dlogits[(long long)b * C + c] = ce_clip_dlogit_mix(logits + (long long)b * C, o.weight, ta, tc, l, C, c, g, o);
+}
+
 // ---- the tail of the temporal part as ONE launch each way --------------------------------------------------------------------
 // forward: the last encoder layer's second LayerNorm (+ residual, scale, dropout: src L120-123) -> mean over the clip's tokens -> Linear
 // head -> (when a target is given) the clip's cross-entropy term, and the batch mean by the last workgroup to finish.  One workgroup per
@@ -476,15 +566,18 @@ __device__ __forceinline__ float head_logit(const float* pooled, const float* __
 // code it always was: every OPTS line is compiled out of it.  nthreads / nclips are the kernel's blockDim.x / gridDim.x, read by the
 // __global__ wrappers: read in here, outside a kernel, blockDim.x compiles to the general form (a select on the grid's remainder and a
 // 16-bit global load of the implicit arguments) in front of the first row request instead of one scalar load of the kernel argument block.
-template <typename T, bool OPTS>
+// MODE 0: the plain loss; 1: with options (OPTS); 2: with options and two targets per clip (OPTS and MIX; `m`): every MIX line is compiled out of
+// the other two.
+template <typename T, int MODE>
 __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
                                                        int B, int S, int D, float eps, float out_scale, float p_drop, unsigned long long seed,
                                                        const unsigned long long* __restrict__ seed_inc, const float* __restrict__ W,
                                                        const float* __restrict__ bias, float* __restrict__ logits, int C,
                                                        const long long* __restrict__ target, float* __restrict__ loss,
-                                                       float* __restrict__ ce_scratch, int rows_in_lds, const HybCeOpts& o, const int nthreads,
-                                                       const unsigned int nclips) {                 // (the kernel's blockDim.x, gridDim.x)
+                                                       float* __restrict__ ce_scratch, int rows_in_lds, const HybCeOpts& o, const HybCeMix& m,
+                                                       const int nthreads, const unsigned int nclips) {                 // (the kernel's blockDim.x, gridDim.x)
+    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
     float* pooled = reinterpret_cast<float*>(tail_smem);                    // [D]
     float* lg = pooled + D;                                                  // [64] this clip's logits
@@ -534,7 +627,8 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
     __shared__ int s_last;
     if (tid == 0) {
         float term;
-        if constexpr (OPTS) term = ce_clip_loss_opts(lg, o.weight ? wl : nullptr, target[b], C, o);
+        if constexpr (MIX) term = ce_clip_loss_mix(lg, o.weight ? wl : nullptr, target[b], m.target_b[b], m.lam[b], C, o);
+        else if constexpr (OPTS) term = ce_clip_loss_opts(lg, o.weight ? wl : nullptr, target[b], C, o);
         else term = ce_clip_loss(lg, target[b], C);
         __hip_atomic_store(ce_scratch + b, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -550,7 +644,9 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
         for (int i = tid; i < B; i += 256) acc += __hip_atomic_load(ce_scratch + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if constexpr (OPTS) {           // ce_opts_fwd_kernel's two trees, the terms coming from the other workgroups
         const float num = ce_tree_sum(acc, part);
-        const float den = ce_den(target, o.weight ? wl : nullptr, B, C, o, part);
+        float den;
+        if constexpr (MIX) den = ce_den_mix(target, m, o.weight ? wl : nullptr, B, C, o, part);
+        else den = ce_den(target, o.weight ? wl : nullptr, B, C, o, part);
         if (tid == 0) loss[0] = ce_loss_opts(num, den);
     } else ce_tree_mean(acc, part, loss, B);
 }
@@ -562,8 +658,8 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restr
                                                                  const float* __restrict__ bias, float* __restrict__ logits, int C,
                                                                  const long long* __restrict__ target, float* __restrict__ loss,
                                                                  float* __restrict__ ce_scratch, int rows_in_lds) {
-    temporal_tail_fwd_body<T, false>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
-                                     ce_scratch, rows_in_lds, HybCeOpts{}, blockDim.x, gridDim.x);
+    temporal_tail_fwd_body<T, 0>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
+                                 ce_scratch, rows_in_lds, HybCeOpts{}, HybCeMix{}, blockDim.x, gridDim.x);
 }
 template <typename T>
 __global__ __launch_bounds__(512) void temporal_tail_fwd_opts_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
@@ -574,8 +670,20 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_opts_kernel(const T* __
                                                                       float* __restrict__ logits, int C, const long long* __restrict__ target,
                                                                       float* __restrict__ loss, float* __restrict__ ce_scratch, int rows_in_lds,
                                                                       HybCeOpts o) {
-    temporal_tail_fwd_body<T, true>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
-                                    ce_scratch, rows_in_lds, o, blockDim.x, gridDim.x);
+    temporal_tail_fwd_body<T, 1>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
+                                 ce_scratch, rows_in_lds, o, HybCeMix{}, blockDim.x, gridDim.x);
+}
+template <typename T>
+__global__ __launch_bounds__(512) void temporal_tail_fwd_mix_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
+                                                                     int B, int S, int D, float eps, float out_scale, float p_drop,
+                                                                     unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
+                                                                     const float* __restrict__ W, const float* __restrict__ bias,
+                                                                     float* __restrict__ logits, int C, const long long* __restrict__ target,
+                                                                     float* __restrict__ loss, float* __restrict__ ce_scratch, int rows_in_lds,
+                                                                     HybCeOpts o, HybCeMix m) {
+    temporal_tail_fwd_body<T, 2>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
+                                 ce_scratch, rows_in_lds, o, m, blockDim.x, gridDim.x);
 }
 
 // backward: cross-entropy backward (from the saved logits, when a target is given; else the caller's dlogits) -> head backward (the
@@ -585,8 +693,8 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_opts_kernel(const T* __
 // column.  Everything a workgroup reads -- its rows of the LayerNorm input, the head weights, the token means -- is requested up front: one
 // memory round trip.  Writes dx (d LN input), dskip and ln_rows affine-gradient partial rows as ln_residual_bwd_kernel<T, true> does for
 // the launch it replaces (workgroup (sb, b) writes row b * nsb + sb; rows no workgroup owns are zero-filled).
-// OPTS (a target is given): the loss backward with options; [64] class weights and the [256] den tree in LDS behind lnred.
-template <typename T, bool OPTS>
+// OPTS (a target is given): the loss backward with options; [64] class weights and the [256] den tree in LDS behind lnred.  MODE as in the forward.
+template <typename T, int MODE>
 __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__ dlogits_in, const float* __restrict__ logits,
                                                        const long long* __restrict__ target, const float* __restrict__ dloss,
                                                        const float* __restrict__ W, const T* __restrict__ enc_out, const T* __restrict__ f,
@@ -594,7 +702,8 @@ __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__
                                                        T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
                                                        float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
                                                        float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
-                                                       const HybCeOpts& o) {
+                                                       const HybCeOpts& o, const HybCeMix& m) {
+    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
     float* dl = reinterpret_cast<float*>(tail_smem);                         // [64]
     float* v = dl + 64;                                                      // [D] the clip's token-gradient row (T-rounded values)
@@ -623,8 +732,13 @@ __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__
         const float dlo = dloss[0];
         __syncthreads();
         const float* w = o.weight ? wl : nullptr;
-        const float g = ce_gscale_opts(dlo, ce_den(target, w, B, C, o, part));           // the forward's den: same function, same inputs
-        if (tid < C) dl[tid] = ce_clip_dlogit_opts(logits + (long long)b * C, w, target[b], C, tid, g, o);
+        if constexpr (MIX) {
+            const float g = ce_gscale_opts(dlo, ce_den_mix(target, m, w, B, C, o, part));
+            if (tid < C) dl[tid] = ce_clip_dlogit_mix(logits + (long long)b * C, w, target[b], m.target_b[b], m.lam[b], C, tid, g, o);
+        } else {
+            const float g = ce_gscale_opts(dlo, ce_den(target, w, B, C, o, part));       // the forward's den: same function, same inputs
+            if (tid < C) dl[tid] = ce_clip_dlogit_opts(logits + (long long)b * C, w, target[b], C, tid, g, o);
+        }
     } else {
         if (tid < C) dl[tid] = target ? ce_clip_dlogit(logits + (long long)b * C, target[b], C, tid, dloss[0] / (float)B) : dlogits_in[b * C + tid];
     }
@@ -677,8 +791,8 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_kernel(const float* __r
                                                                 T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
                                                                 float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
                                                                 float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc) {
-    temporal_tail_bwd_body<T, false>(dlogits_in, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C,
-                                     rpw, out_scale, p_drop, seed, seed_inc, HybCeOpts{});
+    temporal_tail_bwd_body<T, 0>(dlogits_in, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C,
+                                 rpw, out_scale, p_drop, seed, seed_inc, HybCeOpts{}, HybCeMix{});
 }
 template <typename T>
 __global__ __launch_bounds__(256) void temporal_tail_bwd_opts_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
@@ -689,8 +803,20 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_opts_kernel(const float
                                                                      float* __restrict__ head_part, int B, int S, int D, int C, int rpw,
                                                                      float out_scale, float p_drop, unsigned long long seed,
                                                                      const unsigned long long* __restrict__ seed_inc, HybCeOpts o) {
-    temporal_tail_bwd_body<T, true>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
-                                    out_scale, p_drop, seed, seed_inc, o);
+    temporal_tail_bwd_body<T, 1>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
+                                 out_scale, p_drop, seed, seed_inc, o, HybCeMix{});
+}
+template <typename T>
+__global__ __launch_bounds__(256) void temporal_tail_bwd_mix_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                                    const float* __restrict__ dloss, const float* __restrict__ W,
+                                                                    const T* __restrict__ enc_out, const T* __restrict__ f,
+                                                                    const float* __restrict__ gamma, const float* __restrict__ stats,
+                                                                    T* __restrict__ dx, T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
+                                                                    float* __restrict__ head_part, int B, int S, int D, int C, int rpw,
+                                                                    float out_scale, float p_drop, unsigned long long seed,
+                                                                    const unsigned long long* __restrict__ seed_inc, HybCeOpts o, HybCeMix m) {
+    temporal_tail_bwd_body<T, 2>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
+                                 out_scale, p_drop, seed, seed_inc, o, m);
 }
 
 }  // namespace
@@ -761,14 +887,21 @@ int hyb_temporal_tail_ok(int B, int S, int D, int C, int ln_rows) {
 int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float* gamma, const float* beta, void* enc_out, float* stats, int B, int S,
                           int D, float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const float* W,
                           const float* bias, float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st,
-                          const HybCeOpts* ce) {
+                          const HybCeOpts* ce, const HybCeMix* mix) {
     HYB_CHECK_ARG(f && x1 && gamma && beta && enc_out && stats && W && logits && (!target || (loss && ce_scratch)) && (!ce || target));
+    HYB_CHECK_ARG(!mix || (ce && mix->target_b && mix->lam));
     const size_t es = dtype == HYB_F32 ? 4 : 2;
     const size_t base = ((size_t)D + 64 + 256 + (ce ? 64 : 0)) * sizeof(float);
     const int rows_in_lds = base + (size_t)S * D * es <= 60 * 1024;
     const size_t lds = base + (rows_in_lds ? (size_t)S * D * es : 0);
     const int threads = S >= 8 ? 512 : 256;             // (1024 threads leave 128 registers per lane: the LayerNorm row spills -- measured 13 -> 24 us)
-    if (ce && dtype == HYB_F32)
+    if (mix && dtype == HYB_F32)
+        hipLaunchKernelGGL(temporal_tail_fwd_mix_kernel<float>, dim3(B), dim3(threads), lds, st, (const float*)f, (const float*)x1, gamma, beta, (float*)enc_out, stats, B, S,
+                           D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce, *mix);
+    else if (mix && dtype == HYB_BF16)
+        hipLaunchKernelGGL(temporal_tail_fwd_mix_kernel<bf16>, dim3(B), dim3(threads), lds, st, (const bf16*)f, (const bf16*)x1, gamma, beta, (bf16*)enc_out, stats, B, S,
+                           D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce, *mix);
+    else if (ce && dtype == HYB_F32)
         hipLaunchKernelGGL(temporal_tail_fwd_opts_kernel<float>, dim3(B), dim3(threads), lds, st, (const float*)f, (const float*)x1, gamma, beta, (float*)enc_out, stats, B, S,
                            D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce);
     else if (ce && dtype == HYB_BF16)
@@ -787,9 +920,10 @@ int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float*
 int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* W,
                           const void* enc_out, const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part,
                           int ln_rows, float* head_part, int B, int S, int D, int C, float out_scale, float p_drop, unsigned long long seed,
-                          const unsigned long long* seed_inc, hipStream_t st, const HybCeOpts* ce) {
+                          const unsigned long long* seed_inc, hipStream_t st, const HybCeOpts* ce, const HybCeMix* mix) {
     HYB_CHECK_ARG((dlogits || (logits && target && dloss)) && W && enc_out && f && gamma && stats && dx && dskip && ln_part && head_part);
     HYB_CHECK_ARG(!ce || (!dlogits && logits && target && dloss));
+    HYB_CHECK_ARG(!mix || (ce && mix->target_b && mix->lam));
     const size_t lds = (64 + 9 * (size_t)D + (ce ? 64 + 256 : 0)) * sizeof(float);
     // row blocks per clip: as many as the ln_rows partial rows allow (>= 1: hyb_temporal_tail_ok), four-row granules
     int nsb = hyb_cdiv(S, 4);
@@ -798,7 +932,13 @@ int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, 
     nsb = hyb_cdiv(S, rpw);
     const dim3 grid(nsb, B);
     if (lds > 64 * 1024) return HYB_E_ARG;
-    if (ce && dtype == HYB_F32)
+    if (mix && dtype == HYB_F32)
+        hipLaunchKernelGGL(temporal_tail_bwd_mix_kernel<float>, grid, dim3(256), lds, st, logits, target, dloss, W, (const float*)enc_out, (const float*)f, gamma, stats,
+                           (float*)dx, (float*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *mix);
+    else if (mix && dtype == HYB_BF16)
+        hipLaunchKernelGGL(temporal_tail_bwd_mix_kernel<bf16>, grid, dim3(256), lds, st, logits, target, dloss, W, (const bf16*)enc_out, (const bf16*)f, gamma, stats,
+                           (bf16*)dx, (bf16*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *mix);
+    else if (ce && dtype == HYB_F32)
         hipLaunchKernelGGL(temporal_tail_bwd_opts_kernel<float>, grid, dim3(256), lds, st, logits, target, dloss, W, (const float*)enc_out, (const float*)f, gamma, stats,
                            (float*)dx, (float*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce);
     else if (ce && dtype == HYB_BF16)
@@ -875,6 +1015,26 @@ extern "C" int hyb_cross_entropy_opts_bwd(const float* logits, const long long* 
     const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
     HYB_CHECK_ARG(logits && target && dloss && dlogits && B > 0 && C > 0 && hyb_ce_opts_ok(o));
     hipLaunchKernelGGL(ce_opts_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// The loss with options and two targets per clip (ce_mix_*_kernel; include/hybrid_hip.h states the definition)
+extern "C" int hyb_cross_entropy_mix_fwd(const float* logits, const long long* target, const long long* target_b, const float* lam, const float* weight,
+                                         long long ignore_index, int has_ignore, float label_smoothing, float* loss, int B, int C, void* stream) {
+    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
+    HYB_CHECK_ARG(logits && target && target_b && lam && loss && B > 0 && C > 0 && hyb_ce_opts_ok(o));
+    hipLaunchKernelGGL(ce_mix_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, B, C, o, HybCeMix{target_b, lam});
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int hyb_cross_entropy_mix_bwd(const float* logits, const long long* target, const long long* target_b, const float* lam, const float* weight,
+                                         long long ignore_index, int has_ignore, float label_smoothing, const float* dloss, float* dlogits, int B, int C,
+                                         void* stream) {
+    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
+    HYB_CHECK_ARG(logits && target && target_b && lam && dloss && dlogits && B > 0 && C > 0 && hyb_ce_opts_ok(o));
+    hipLaunchKernelGGL(ce_mix_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o,
+                       HybCeMix{target_b, lam});
     HYB_LAUNCH_CHECK();
     return 0;
 }

@@ -20,6 +20,8 @@ What makes capture legal here
   * a HybridCrossEntropyLoss with options (class weights, ignore_index, label smoothing) stays inside the temporal part's launches: the
     weights are read from the criterion's ``weight`` buffer when a replay runs, so an in-place update of that buffer is picked up by the
     next replay; ignore_index and label_smoothing travel by value, and step() refuses a change of either after capture;
+  * a MixTarget (the labels of a Mixup / CutMix batch) is three static tensors: both targets and lam are read from device memory when a
+    replay runs, so load() brings new labels and new mixing weights without a recapture, and the loss stays in the same launches;
   * BatchNorm running statistics are updated in place by the captured statistics kernels (hybrid::backbone_).
 
 Data parallelism (world > 1): the backward pass is captured in two pieces so that the gradient all-reduce of the temporal part
@@ -67,7 +69,12 @@ class GraphedTrainStep:
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         dev = x.device
-        self.x, self.y = x.clone(), y.clone()                 # static inputs: copy new batches in with load()
+        from .modules import MixTarget
+        self._mix = isinstance(y, MixTarget)
+        if self._mix and not hasattr(criterion, "has_options"):
+            raise TypeError("a MixTarget needs a HybridCrossEntropyLoss criterion")
+        # static inputs: copy new batches in with load() (a MixTarget: static copies of all three tensors)
+        self.x, self.y = x.clone(), MixTarget(*(t.clone() for t in y)) if self._mix else y.clone()
         self.mask = mask.clone() if mask is not None else None
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
         self._one = None
@@ -232,9 +239,17 @@ class GraphedTrainStep:
 
     # ---- public ---------------------------------------------------------------------------------------------------------
     def load(self, x, y, mask=None):
-        """Copy the next batch into the static input buffers (same shapes as at construction)."""
+        """Copy the next batch into the static input buffers (same shapes as at construction; y a MixTarget exactly when it was one there)."""
+        from .modules import MixTarget
+        if isinstance(y, MixTarget) != self._mix:
+            raise TypeError("GraphedTrainStep was captured with " + ("a MixTarget: load() needs one too" if self._mix else
+                            "a class-index tensor: a MixTarget needs a step constructed with one"))
         self.x.copy_(x, non_blocking=True)
-        self.y.copy_(y, non_blocking=True)
+        if self._mix:
+            for dst, src in zip(self.y, y):
+                dst.copy_(src, non_blocking=True)
+        else:
+            self.y.copy_(y, non_blocking=True)
         if mask is not None:
             self.mask.copy_(mask, non_blocking=True)
 

@@ -15,6 +15,7 @@ all-reduce work unchanged.  All compute runs in the HIP library through the ``to
 """
 import math
 from collections import OrderedDict
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -170,6 +171,15 @@ class TransformerEncoder(nn.Module, _ComputeDtypeMixin):
         return ops.to_f32(self.forward_compute(ops.to_compute(input, self._dt), mask), self._dt)
 
 
+class MixTarget(NamedTuple):
+    """The labels of a Mixup / CutMix batch, all on the device: clip b carries class ``y_a[b]`` with weight ``lam[b]`` and class ``y_b[b]`` with
+    weight ``1 - lam[b]`` (int64 [B], int64 [B], fp32 [B]).  ClipPipeline yields one with a mixing ClipTransform; HybridCrossEntropyLoss,
+    forward_temporal_loss and GraphedTrainStep take one where they take a class-index tensor."""
+    y_a: torch.Tensor
+    y_b: torch.Tensor
+    lam: torch.Tensor
+
+
 class HybridCrossEntropyLoss(nn.Module):
     """Mean cross-entropy over the batch (the composite's own loss), one HIP kernel each way.
 
@@ -182,7 +192,12 @@ class HybridCrossEntropyLoss(nn.Module):
     ``weight`` is a registered buffer (``.cuda()`` and ``state_dict()`` carry it) and is read by the kernels when they run: an in-place update
     of the buffer is seen by the next call, and by the next replay of a GraphedTrainStep.  Under data parallelism each rank divides by the
     weight sum of its own clips and the gradients are averaged over the ranks -- exactly what DistributedDataParallel does with
-    ``nn.CrossEntropyLoss(weight=...)``; no global weight sum is exchanged."""
+    ``nn.CrossEntropyLoss(weight=...)``; no global weight sum is exchanged.
+
+    ``target`` may be a ``MixTarget(y_a, y_b, lam)``: the loss is sum_b [lam_b term(b, y_a) + (1 - lam_b) term(b, y_b)] over the same mix of
+    the target weights (include/hybrid_hip.h, hyb_cross_entropy_mix_*), with any combination of the options, none included; each side keeps
+    the rules above on its own, a lam outside [0, 1] makes the loss NaN.  With one lam for the batch, ``y_b`` a permutation of ``y_a`` and
+    nothing ignored it is ``lam * CE(logits, y_a) + (1 - lam) * CE(logits, y_b)``.  A plain tensor target takes the path it always took."""
 
     def __init__(self, weight=None, ignore_index=None, label_smoothing=0.0):
         super().__init__()
@@ -212,6 +227,9 @@ class HybridCrossEntropyLoss(nn.Module):
             raise ValueError(f"weight has {self.weight.shape[0]} entries but the logits have {C} classes")
 
     def forward(self, logits, target):
+        if isinstance(target, MixTarget):
+            self._check_weight(logits.shape[-1])
+            return ops.cross_entropy_mix(logits, target.y_a, target.y_b, target.lam, self.weight, self.ignore_index, self.label_smoothing)
         if not self.has_options():
             return ops.cross_entropy(logits, target)
         self._check_weight(logits.shape[-1])
@@ -320,15 +338,27 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
         """Last pooled map + class indices [B] -> (mean cross-entropy loss, logits): ``criterion(forward_temporal(h, B, mask), target)``
         with the loss inside the temporal part's own launches (hybrid::temporal_ce, or hybrid::temporal_ce_opts when the criterion carries
         options; same bits, same number of launches).  ``criterion``: a HybridCrossEntropyLoss, None = ``HybridCrossEntropyLoss()``.
-        Plain-structure models only (``_fused()``)."""
+        ``target`` may be a MixTarget: hybrid::temporal_ce_mix, again the same launches.  Models ``_fused()`` rejects run the criterion behind
+        forward_temporal."""
         enc = self.encoder
         if criterion is not None and type(criterion) is not HybridCrossEntropyLoss:
             raise TypeError("forward_temporal_loss fuses HybridCrossEntropyLoss only")
         opts = criterion is not None and criterion.has_options()
+        mixed = isinstance(target, MixTarget)
         if not self._fused():
             logits = self.forward_temporal(h, B, mask)
+            if mixed:
+                return (criterion or HybridCrossEntropyLoss())(logits, target), logits
             return (criterion(logits, target) if opts else ops.cross_entropy(logits, target)), logits
         tdt = self._temporal_dt()
+        if mixed:
+            weight, ignore_index, label_smoothing = criterion.options() if criterion is not None else (None, None, 0.0)
+            if criterion is not None:
+                criterion._check_weight(self.head.weight.shape[0])
+            return ops.temporal_ce_mix(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias,
+                                       enc._flat_params(), self.head.weight, self.head.bias, mask, target.y_a, target.y_b, target.lam, weight,
+                                       ignore_index, label_smoothing, B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads,
+                                       enc.attention_layers[0]._attn_p(), float(enc.dropout), ops.next_seed())
         if opts:
             criterion._check_weight(self.head.weight.shape[0])
             weight, ignore_index, label_smoothing = criterion.options()

@@ -23,9 +23,11 @@ fake kernel and an autograd kernel per operator.
     hybrid::head             mean over T + Linear(d, classes)                    (composite's own)
     hybrid::cross_entropy    mean cross-entropy                                  (composite's own)
     hybrid::cross_entropy_opts   ... with class weights, label smoothing, ignore_index   (torch.nn.functional.cross_entropy's "mean")
+    hybrid::cross_entropy_mix    ... and two targets per clip with a mixing weight lam [B]: the labels of a Mixup / CutMix batch
     hybrid::cast, hybrid::nchw_to_nhwc, hybrid::nhwc_to_nchw                     layout / dtype glue for standalone module use
     hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
     hybrid::clip_transform   uint8 clips -> crop, resize, flip, sub-sample, ToTensor, Normalize   (clips.ClipTransform; no autograd formula)
+    hybrid::clip_transform_mix   ... with Mixup / CutMix against a partner clip in the same pass   (one more int32 row per clip)
 """
 import ctypes
 import functools
@@ -552,9 +554,28 @@ def _ce_opts(opts, C, device):
     return (_ce_weight(opts[0], C, device), int(opts[1]), int(opts[2]), float(opts[3])) if opts else ()
 
 
-def _cross_entropy_fwd(logits, target, opts):
+def _ce_mix(mix, B, device):
+    """(target_b, lam) as the hyb_*_mix_* entry points take them behind the target: int64 [B] and fp32 [B] on the logits' device; () stays ()."""
+    if not mix:
+        return ()
+    target_b, lam = mix
+    _require_cuda(target_b, lam)
+    if target_b.dim() != 1 or target_b.shape[0] != B or lam.dim() != 1 or lam.shape[0] != B:
+        raise ValueError(f"expected second class indices [B={B}] and lam [B={B}], got {tuple(target_b.shape)} and {tuple(lam.shape)}")
+    if lam.dtype != torch.float32:
+        raise TypeError(f"lam must be float32, got {lam.dtype}")
+    if target_b.device != device or lam.device != device:
+        raise RuntimeError(f"target_b / lam are on {target_b.device} / {lam.device} but the logits are on {device}")
+    return target_b.contiguous().to(torch.int64), lam.contiguous()
+
+
+def _ce_name(stem, opts, mix, way):
+    return f"hyb_{stem}_mix_{way}" if mix else f"hyb_{stem}_opts_{way}" if opts else f"hyb_{stem}_{way}"
+
+
+def _cross_entropy_fwd(logits, target, opts, mix=()):
     """opts (): hyb_cross_entropy_fwd; opts = (weight, ignore_index, has_ignore, label_smoothing): hyb_cross_entropy_opts_fwd, the same call
-    with the loss options behind the target."""
+    with the loss options behind the target; mix = (target_b, lam), with opts: hyb_cross_entropy_mix_fwd, the two in front of the options."""
     _require_cuda(logits, target)
     if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
         raise ValueError(f"expected logits [B,C] and class indices [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
@@ -562,20 +583,22 @@ def _cross_entropy_fwd(logits, target, opts):
     target = target.contiguous().to(torch.int64)
     B, C = logits.shape
     opts = _ce_opts(opts, C, logits.device)
+    mix = _ce_mix(mix, B, logits.device)
     loss = torch.empty((), dtype=torch.float32, device=logits.device)
-    lib.call("hyb_cross_entropy_opts_fwd" if opts else "hyb_cross_entropy_fwd", logits, target, *opts, loss, B, C, _stream())
+    lib.call(_ce_name("cross_entropy", opts, mix, "fwd"), logits, target, *mix, *opts, loss, B, C, _stream())
     return loss
 
 
-def _cross_entropy_bwd(dloss, logits, target, opts):
+def _cross_entropy_bwd(dloss, logits, target, opts, mix=()):
     _require_cuda(dloss, logits)
     logits = logits.contiguous().float()
     target = target.contiguous().to(torch.int64)
     B, C = logits.shape
     opts = _ce_opts(opts, C, logits.device)
+    mix = _ce_mix(mix, B, logits.device)
     dl = dloss.contiguous().float().reshape(1)
     dlogits = torch.empty_like(logits)
-    lib.call("hyb_cross_entropy_opts_bwd" if opts else "hyb_cross_entropy_bwd", logits, target, *opts, dl, dlogits, B, C, _stream())
+    lib.call(_ce_name("cross_entropy", opts, mix, "bwd"), logits, target, *mix, *opts, dl, dlogits, B, C, _stream())
     return dlogits
 
 
@@ -599,6 +622,18 @@ def cross_entropy_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, wei
     return _cross_entropy_bwd(dloss, logits, target, (weight, ignore_index, has_ignore, label_smoothing))
 
 
+def cross_entropy_mix_op(logits: Tensor, target: Tensor, target_b: Tensor, lam: Tensor, weight: Optional[Tensor], ignore_index: int,
+                         has_ignore: bool, label_smoothing: float) -> Tensor:
+    """hybrid::cross_entropy_opts with two targets per clip (hyb_cross_entropy_mix_fwd): sum_b [lam_b term(b, target_b) + (1 - lam_b)
+    term(b, target_b_b)] over the same mix of the target weights -- the loss of a Mixup / CutMix batch."""
+    return _cross_entropy_fwd(logits, target, (weight, ignore_index, has_ignore, label_smoothing), (target_b, lam))
+
+
+def cross_entropy_mix_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, target_b: Tensor, lam: Tensor, weight: Optional[Tensor],
+                             ignore_index: int, has_ignore: bool, label_smoothing: float) -> Tensor:
+    return _cross_entropy_bwd(dloss, logits, target, (weight, ignore_index, has_ignore, label_smoothing), (target_b, lam))
+
+
 def cross_entropy_fake(logits, target, *opts):
     return logits.new_empty((), dtype=torch.float32)
 
@@ -614,6 +649,13 @@ def cross_entropy(logits, target):
 def cross_entropy_opts(logits, target, weight=None, ignore_index=None, label_smoothing=0.0):
     return torch.ops.hybrid.cross_entropy_opts(logits, target, weight, 0 if ignore_index is None else int(ignore_index), ignore_index is not None,
                                                float(label_smoothing))
+
+
+def cross_entropy_mix(logits, target, target_b, lam, weight=None, ignore_index=None, label_smoothing=0.0):
+    """The mean cross-entropy of a Mixup / CutMix batch: class indices target / target_b [B] and fp32 lam [B] (the weight of ``target``), all
+    on the device; the options as in cross_entropy_opts.  No gradient for lam, the targets or the class weights."""
+    return torch.ops.hybrid.cross_entropy_mix(logits, target, target_b, lam, weight, 0 if ignore_index is None else int(ignore_index),
+                                              ignore_index is not None, float(label_smoothing))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -895,6 +937,29 @@ def clip_transform_op(src: Tensor, params: Tensor, mean_invstd: Optional[Tensor]
     return out
 
 
+def _clip_mix_rows(mix, B):
+    if mix.dtype != torch.int32 or tuple(mix.shape) != (B, 8):
+        raise TypeError(f"mix must be int32 [{B},8]: one row {{partner, kind, by0, bx0, bh, bw, lam_bits, 0}} per clip")
+
+
+def clip_transform_mix_op(src: Tensor, params: Tensor, mix: Tensor, mean_invstd: Optional[Tensor], Tout: int, Ho: int, Wo: int) -> Tensor:
+    """hybrid::clip_transform with Mixup / CutMix in the same pass (hyb_clips_u8_transform_mix in include/hybrid_hip.h has the rules): one more
+    int32 row per clip names the partner clip, the kind and the box or lam."""
+    _require_cuda(src, params, mix, mean_invstd)
+    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
+    _clip_mix_rows(mix, B)
+    out = torch.empty(B, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
+    lib.call("hyb_clips_u8_transform_mix", src.contiguous(), params.contiguous(), mix.contiguous(),
+             None if mean_invstd is None else mean_invstd.contiguous(), out, B, Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
+    return out
+
+
+def clip_transform_mix_fake(src, params, mix, mean_invstd, Tout, Ho, Wo):
+    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
+    _clip_mix_rows(mix, B)
+    return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
+
+
 def clip_transform_fake(src, params, mean_invstd, Tout, Ho, Wo):
     B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
     return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
@@ -904,6 +969,12 @@ def clip_transform(src, params, mean_invstd, Tout, Ho, Wo):
     """The device leg of ClipTransform on its own: src uint8 [B,Tin,Hin,Win,C], params int32 [B,8] (ClipTransform.sample), mean_invstd fp32
     [2,C] or None -> fp32 [B,Tout,C,Ho,Wo] on the current stream (hybrid::clip_transform checks devices, dtypes and shapes)."""
     return torch.ops.hybrid.clip_transform(src, params, mean_invstd, int(Tout), int(Ho), int(Wo))
+
+
+def clip_transform_mix(src, params, mix, mean_invstd, Tout, Ho, Wo):
+    """clip_transform with mix rows int32 [B,8] (ClipTransform.sample_mix): Mixup blends each clip with its partner, CutMix pastes the partner's
+    box, kind 0 leaves the clip as clip_transform writes it."""
+    return torch.ops.hybrid.clip_transform_mix(src, params, mix, mean_invstd, int(Tout), int(Ho), int(Wo))
 
 
 def _check_h_dtype(h, dt):
@@ -950,7 +1021,8 @@ def prepare_ce_scratch(B, device, stream):
 def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc):
     """The temporal part, one body for the three operators.  ce (): hyb_temporal_fwd; ce = (target,): hyb_temporal_ce_fwd, the loss in the
     same launches; ce = (target, weight, ignore_index, has_ignore, label_smoothing): hyb_temporal_ce_opts_fwd, the same call with the loss
-    options behind the target.  -> (logits, feat, enc_saved, enc_out), behind the loss [] when there is one."""
+    options behind the target; ce = (target, target_b, lam, weight, ...): hyb_temporal_ce_mix_fwd, the second target and lam in front of the
+    options.  -> (logits, feat, enc_saved, enc_out), behind the loss [] when there is one."""
     _require_cuda(h, token_w, head_w, *ce[:1], *enc_params)
     _check_h_dtype(h, dt)
     h = h.contiguous()
@@ -970,8 +1042,10 @@ def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, 
     ps = [p.contiguous() for p in enc_params]
     name, loss_in, loss_out = "hyb_temporal_fwd", (), ()
     if ce:
-        name = "hyb_temporal_ce_opts_fwd" if ce[1:] else "hyb_temporal_ce_fwd"
-        loss_in = (ce[0].contiguous().to(torch.int64), *_ce_opts(ce[1:], classes, dev))
+        mix = ce[1:3] if len(ce) == 7 else ()
+        opts = ce[3:] if mix else ce[1:]
+        name = _ce_name("temporal_ce", opts, mix, "fwd")
+        loss_in = (ce[0].contiguous().to(torch.int64), *_ce_mix(mix, B, dev), *_ce_opts(opts, classes, dev))
         loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
     lib.call(name, dt, h, token_w.contiguous(), token_b.contiguous(), ps, head_w.contiguous(), head_b.contiguous(), mask, *loss_in, feat, tok, saved,
              enc_out, logits, *loss_out, B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, _stream())
@@ -979,8 +1053,8 @@ def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, 
 
 
 def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc):
-    """ce (): dout is dlogits, hyb_temporal_bwd; ce = (logits, target) + the loss options of _temporal_fwd, if any: dout is dloss,
-    hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
+    """ce (): dout is dlogits, hyb_temporal_bwd; ce = (logits, target) + what follows the target in _temporal_fwd's ce, if anything: dout is
+    dloss, hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd / hyb_temporal_ce_mix_bwd.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
     _require_cuda(dout, *ce[:1], feat)
     B, S, D = enc_out.shape
     N, Cp = feat.shape
@@ -998,9 +1072,11 @@ def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_
     ws = _ws(_query("hyb_temporal_bwd_workspace", dt & 0xff, B, S, Hh * Ww, Cp, D, hid, L, H), dev)
     name, loss_in = "hyb_temporal_bwd", ()
     if ce:
-        name = "hyb_temporal_ce_opts_bwd" if ce[2:] else "hyb_temporal_ce_bwd"
+        mix = ce[2:4] if len(ce) == 8 else ()
+        opts = ce[4:] if mix else ce[2:]
+        name = _ce_name("temporal_ce", opts, mix, "bwd")
         dout = dout.reshape(1)
-        loss_in = (ce[0].contiguous(), ce[1].contiguous(), *_ce_opts(ce[2:], classes, dev))
+        loss_in = (ce[0].contiguous(), ce[1].contiguous(), *_ce_mix(mix, B, dev), *_ce_opts(opts, classes, dev))
     lib.call(name, dt, dout, *loss_in, token_w.contiguous(), ps, head_w.contiguous(), mask, feat, saved, enc_out, dtw, dtb, grads, dhw, dhb, dh,
              B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, ws, ws.numel(), _stream())
     return [dh, dtw, dtb, dhw, dhb] + grads
@@ -1029,6 +1105,15 @@ def temporal_ce_opts_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params:
                          hid, L, H, attn_p, layer_p, seed, seed_inc)
 
 
+def temporal_ce_mix_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
+                       mask: Optional[Tensor], target: Tensor, target_b: Tensor, lam: Tensor, weight: Optional[Tensor], ignore_index: int,
+                       has_ignore: bool, label_smoothing: float, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
+                       seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """hybrid::temporal + hybrid::cross_entropy_mix in the same launches (hyb_temporal_ce_mix_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
+    return _temporal_fwd((target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing), h, token_w, token_b, enc_params, head_w, head_b,
+                         mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
 def temporal_bwd_op(dlogits: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
                     saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
                     seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
@@ -1053,8 +1138,17 @@ def temporal_ce_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weigh
                          enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
 
 
+def temporal_ce_mix_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, target_b: Tensor, lam: Tensor, weight: Optional[Tensor],
+                           ignore_index: int, has_ignore: bool, label_smoothing: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor,
+                           mask: Optional[Tensor], feat: Tensor, saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int,
+                           attn_p: float, layer_p: float, seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
+    """hybrid::cross_entropy_mix_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
+    return _temporal_bwd((logits, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing), dloss, token_w, enc_params, head_w, mask,
+                         feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
 def _temporal_fake(n_loss, h, token_w, token_b, enc_params, head_w, head_b, mask, *rest, seed_inc=None):
-    """Fake of the three forward operators: rest = the n_loss loss arguments of the schema (0, 1 or 5), then B, dt, hid, L, H, ..."""
+    """Fake of the four forward operators: rest = the n_loss loss arguments of the schema (0, 1, 5 or 7), then B, dt, hid, L, H, ..."""
     B, dt, hid, L, H = rest[n_loss:n_loss + 5]
     N, Hh, Ww, Cp = h.shape
     S, D = N // B, token_w.shape[0]
@@ -1065,7 +1159,7 @@ def _temporal_fake(n_loss, h, token_w, token_b, enc_params, head_w, head_b, mask
 
 
 def _temporal_bwd_fake(n_loss, dout, *rest, seed_inc=None):
-    """Fake of the three backward operators: rest = the n_loss loss arguments of the schema (0, 2 or 6), then token_w, enc_params, ..."""
+    """Fake of the four backward operators: rest = the n_loss loss arguments of the schema (0, 2, 6 or 8), then token_w, enc_params, ..."""
     token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt = rest[n_loss:n_loss + 10]
     N, Cp = feat.shape
     c = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
@@ -1090,6 +1184,17 @@ def temporal_ce_opts(h, token_w, token_b, enc_params, head_w, head_b, mask, targ
     r = torch.ops.hybrid.temporal_ce_opts(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
                                           0 if ignore_index is None else int(ignore_index), ignore_index is not None, float(label_smoothing), B, dt, hid,
                                           L, H, float(attn_p), float(layer_p), seed, step_counter())
+    return r[0], r[1]
+
+
+def temporal_ce_mix(h, token_w, token_b, enc_params, head_w, head_b, mask, target, target_b, lam, weight, ignore_index, label_smoothing, B, dt, hid,
+                    L, H, attn_p, layer_p, seed):
+    """-> (loss, logits): temporal_ce_opts with two targets per clip and their mixing weight lam [B] (cross_entropy_mix): the same launches; the
+    targets and lam are read on the device when the kernels run."""
+    S = h.shape[0] // B
+    r = torch.ops.hybrid.temporal_ce_mix(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, target_b, lam,
+                                         weight, 0 if ignore_index is None else int(ignore_index), ignore_index is not None, float(label_smoothing), B,
+                                         dt, hid, L, H, float(attn_p), float(layer_p), seed, step_counter())
     return r[0], r[1]
 
 
@@ -1249,23 +1354,28 @@ class _HeadFn(torch.autograd.Function):
 
 
 class _CrossEntropyFn(torch.autograd.Function):
-    """hybrid::cross_entropy (has_ignore None: no loss options) and hybrid::cross_entropy_opts."""
+    """hybrid::cross_entropy (has_ignore None: no loss options), hybrid::cross_entropy_opts and (target_b, lam given) hybrid::cross_entropy_mix."""
 
     @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, has_ignore, label_smoothing):
+    def forward(ctx, logits, target, weight, ignore_index, has_ignore, label_smoothing, target_b=None, lam=None):
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(logits, target, weight)
+        ctx.save_for_backward(logits, target, weight, target_b, lam)
         ctx.cfg = None if has_ignore is None else (ignore_index, has_ignore, label_smoothing)
         with _below_autograd():
             if ctx.cfg is None:
                 return torch.ops.hybrid.cross_entropy(logits, target)
+            if target_b is not None:
+                return torch.ops.hybrid.cross_entropy_mix(logits, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing)
             return torch.ops.hybrid.cross_entropy_opts(logits, target, weight, ignore_index, has_ignore, label_smoothing)
 
     @staticmethod
     def backward(ctx, dloss):
-        logits, target, weight = ctx.saved_tensors
+        logits, target, weight, target_b, lam = ctx.saved_tensors
         if ctx.cfg is None:
             dlogits = torch.ops.hybrid.cross_entropy_bwd(dloss, logits, target)
+        elif target_b is not None:
+            dlogits = torch.ops.hybrid.cross_entropy_mix_bwd(dloss, logits, target, target_b, lam, weight, *ctx.cfg)
+            return (dlogits,) + (None,) * 7    # (no gradient for lam, the second target or the class weights)
         else:
             dlogits = torch.ops.hybrid.cross_entropy_opts_bwd(dloss, logits, target, weight, *ctx.cfg)
         return (dlogits,) + (None,) * 5        # (no gradient for the class weights)
@@ -1303,11 +1413,12 @@ class _BackboneFn(torch.autograd.Function):
 
 
 class _TemporalFn(torch.autograd.Function):
-    """hybrid::temporal (target None), hybrid::temporal_ce (has_ignore None: no loss options) and hybrid::temporal_ce_opts."""
+    """hybrid::temporal (target None), hybrid::temporal_ce (has_ignore None: no loss options), hybrid::temporal_ce_opts and (target_b and lam
+    given) hybrid::temporal_ce_mix."""
 
     @staticmethod
     def forward(ctx, h, token_w, token_b, head_w, head_b, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
-                layer_p, seed, seed_inc, *enc_params):
+                layer_p, seed, seed_inc, target_b, lam, *enc_params):
         ctx.set_materialize_grads(False)
         tail = (B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
         with _below_autograd():
@@ -1315,24 +1426,28 @@ class _TemporalFn(torch.autograd.Function):
                 out = torch.ops.hybrid.temporal(h, token_w, token_b, enc_params, head_w, head_b, mask, *tail)
             elif has_ignore is None:
                 out = torch.ops.hybrid.temporal_ce(h, token_w, token_b, enc_params, head_w, head_b, mask, target, *tail)
+            elif target_b is not None:
+                out = torch.ops.hybrid.temporal_ce_mix(h, token_w, token_b, enc_params, head_w, head_b, mask, target, target_b, lam, weight, ignore_index,
+                                                       has_ignore, label_smoothing, *tail)
             else:
                 out = torch.ops.hybrid.temporal_ce_opts(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, has_ignore,
                                                         label_smoothing, *tail)
         feat, saved, enc_out = out[-3:]
         ctx.seed_inc = seed_inc
-        opt = [t for t in (None if target is None else out[1], target, weight, mask) if t is not None]      # (out[1]: the logits behind the loss)
+        opt = [t for t in (None if target is None else out[1], target, target_b, lam, weight, mask) if t is not None]      # (out[1]: the logits behind the loss)
         ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, *opt, *enc_params)
-        ctx.cfg = (target is not None, weight is not None, mask is not None, None if has_ignore is None else (ignore_index, has_ignore, label_smoothing),
+        ctx.cfg = (target is not None, target_b is not None, weight is not None, mask is not None, None if has_ignore is None else (ignore_index, has_ignore, label_smoothing),
                    h.shape[1], h.shape[2], dt, hid, L, H, attn_p, layer_p, seed)
         ctx.mark_non_differentiable(*out[1:])          # (with a loss, logits too: an output for the caller's metrics; the objective is the loss)
         return tuple(out)
 
     @staticmethod
     def backward(ctx, dout, *unused):
-        has_target, has_weight, has_mask, opts, *tail = ctx.cfg
+        has_target, has_mix, has_weight, has_mask, opts, *tail = ctx.cfg
         token_w, head_w, feat, saved, enc_out, *rest = ctx.saved_tensors
         logits = rest.pop(0) if has_target else None
         target = rest.pop(0) if has_target else None
+        mix = (rest.pop(0), rest.pop(0)) if has_mix else None
         weight = rest.pop(0) if has_weight else None
         mask = rest.pop(0) if has_mask else None
         tail = (token_w, rest, head_w, mask, feat, saved, enc_out, *tail, ctx.seed_inc)
@@ -1340,9 +1455,11 @@ class _TemporalFn(torch.autograd.Function):
             g = torch.ops.hybrid.temporal_bwd(dout, *tail)
         elif opts is None:
             g = torch.ops.hybrid.temporal_ce_bwd(dout, logits, target, *tail)
+        elif has_mix:
+            g = torch.ops.hybrid.temporal_ce_mix_bwd(dout, logits, target, *mix, weight, *opts, *tail)
         else:
             g = torch.ops.hybrid.temporal_ce_opts_bwd(dout, logits, target, weight, *opts, *tail)
-        return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 15 + tuple(g[5:])
+        return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 17 + tuple(g[5:])
 
 
 _define("nchw_to_nhwc", "(Tensor x, int dt, int cp) -> Tensor", nchw_to_nhwc_op, nchw_to_nhwc_fake, _NchwToNhwcFn.apply)
@@ -1375,6 +1492,12 @@ _define("cross_entropy_opts", "(Tensor logits, Tensor target, Tensor? weight, in
         cross_entropy_opts_op, cross_entropy_fake, _CrossEntropyFn.apply)
 _define("cross_entropy_opts_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, "
         "float label_smoothing) -> Tensor", cross_entropy_opts_bwd_op, cross_entropy_bwd_fake)
+_define("cross_entropy_mix", "(Tensor logits, Tensor target, Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, bool has_ignore, "
+        "float label_smoothing) -> Tensor", cross_entropy_mix_op, cross_entropy_fake,
+        lambda logits, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing: _CrossEntropyFn.apply(
+            logits, target, weight, ignore_index, has_ignore, label_smoothing, target_b, lam))
+_define("cross_entropy_mix_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, "
+        "bool has_ignore, float label_smoothing) -> Tensor", cross_entropy_mix_bwd_op, cross_entropy_bwd_fake)
 _define("backbone", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, bool training, "
         "float momentum, float eps, int dt) -> Tensor[]", backbone_op, backbone_fake,
         lambda x, ws, gs, bs, rms, rvs, training, momentum, eps, dt: list(_BackboneFn.apply(x, len(ws), training, momentum, eps, dt, *ws, *gs, *bs,
@@ -1393,11 +1516,14 @@ _define("backbone_infer", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[
 _LIB.impl("backbone_infer", _inference_only("backbone_infer"), "Autograd")
 _define("clip_transform", "(Tensor src, Tensor params, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor", clip_transform_op, clip_transform_fake)
 _LIB.impl("clip_transform", _inference_only("clip_transform"), "Autograd")
+_define("clip_transform_mix", "(Tensor src, Tensor params, Tensor mix, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor", clip_transform_mix_op,
+        clip_transform_mix_fake)
+_LIB.impl("clip_transform_mix", _inference_only("clip_transform_mix"), "Autograd")
 _define("temporal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, int B, int dt, "
         "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor)", temporal_op,
         functools.partial(_temporal_fake, 0),
         lambda h, tw, tb, ps, hw, hb, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None: _TemporalFn.apply(
-            h, tw, tb, hw, hb, mask, None, None, None, None, None, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, *ps))
+            h, tw, tb, hw, hb, mask, None, None, None, None, None, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, None, None, *ps))
 _define("temporal_bwd", "(Tensor dlogits, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, "
         "Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]",
         temporal_bwd_op, functools.partial(_temporal_bwd_fake, 0))
@@ -1405,7 +1531,7 @@ _define("temporal_ce", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_
         "int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
         temporal_ce_op, functools.partial(_temporal_fake, 1),
         lambda h, tw, tb, ps, hw, hb, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None: _TemporalFn.apply(
-            h, tw, tb, hw, hb, mask, target, None, None, None, None, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, *ps))
+            h, tw, tb, hw, hb, mask, target, None, None, None, None, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, None, None, *ps))
 _define("temporal_ce_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, "
         "Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) "
         "-> Tensor[]", temporal_ce_bwd_op, functools.partial(_temporal_bwd_fake, 2))
@@ -1414,11 +1540,22 @@ _define("temporal_ce_opts", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[]
         "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_opts_op, functools.partial(_temporal_fake, 5),
         lambda h, tw, tb, ps, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p, layer_p, seed,
         seed_inc=None: _TemporalFn.apply(h, tw, tb, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
-                                          layer_p, seed, seed_inc, *ps))
+                                          layer_p, seed, seed_inc, None, None, *ps))
 _define("temporal_ce_opts_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, "
         "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
         "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_opts_bwd_op,
         functools.partial(_temporal_bwd_fake, 6))
+_define("temporal_ce_mix", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
+        "Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int B, int dt, int hid, int L, int H, "
+        "float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_mix_op,
+        functools.partial(_temporal_fake, 7),
+        lambda h, tw, tb, ps, hw, hb, mask, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p, layer_p,
+        seed, seed_inc=None: _TemporalFn.apply(h, tw, tb, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H,
+                                               attn_p, layer_p, seed, seed_inc, target_b, lam, *ps))
+_define("temporal_ce_mix_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, "
+        "bool has_ignore, float label_smoothing, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, "
+        "Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]",
+        temporal_ce_mix_bwd_op, functools.partial(_temporal_bwd_fake, 8))
 
 
 # ---------------------------------------------------------------------------------------------
