@@ -639,6 +639,24 @@ int hyb_adamw_step_dev(int count, float* const* params, const float* const* grad
                        const long long* numel, const double* hyper, long long step, long long* step_inc, unsigned int* advance_ticket,
                        const float* clip /* norm_out of hyb_grad_norm, or NULL */, void* stream);
 
+/* ---- exponential moving average of the weights, kept inside the AdamW launch ---------------------------------------------------------
+ * (New symbols only; hyb_abi_version() stays 9.)  The average's two hyper-parameters live in a DEVICE block `double ema_hyper[2]` =
+ * {decay, warmup}, owned by the caller, for the reason hyper[] does: a captured launch must follow a decay that changes between replays.
+ *
+ * hyb_adamw_ema_set: writes {decay, warmup} from a one-workgroup kernel that received them as kernel arguments (as hyb_adamw_hyper_set;
+ * NOT meant to be captured).  0 <= decay < 1; warmup is 0 or 1. */
+int hyb_adamw_ema_set(double* ema_hyper /* [2] */, double decay, double warmup, void* stream);
+/* hyb_adamw_step_dev_ema: hyb_adamw_step_dev -- params, exp_avg and exp_avg_sq come out bit for bit as it gives them -- which also moves
+ * ema[i] (fp32, numel[i] elements, never the parameter itself), in the same launch, from the parameter value it has just formed:
+ *     t = step + (step_inc ? *step_inc : 0), n = t - 1;  d = warmup ? min(decay, (1 + n) / (10 + n)) : decay      (double, on the device)
+ *     e <- fmaf((float)d, e, (float)(1 - d) * p_new)                                                            (decay 0: e == p_new exactly)
+ * 9 x 4 bytes of traffic per parameter instead of 7 x 4.  One launch holds 64 tensors (80 without the average: a sixth pointer per tensor
+ * in 4 KB of kernel arguments); more tensors = more launches, the last of which advances the counter. */
+int hyb_adamw_step_dev_ema(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                           float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
+                           long long* step_inc, unsigned int* advance_ticket, const float* clip /* norm_out of hyb_grad_norm, or NULL */,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,10 @@
 //     p <- p * (1 - lr*wd);  m <- m + (1-b1)(g - m);  v <- b2*v + (1-b2) g^2;
 //     p <- p - (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // The tensor table travels in the kernel arguments (up to 80 tensors per launch), a workgroup owns 4096 consecutive elements
-// of one tensor and finds it by scanning the table's chunk offsets; HBM-bound: 7 x 4 bytes per parameter.
+// of one tensor and finds it by scanning the table's chunk offsets; HBM-bound: 7 x 4 bytes per parameter (9 x 4 in the variant that also keeps
+// an exponential moving average of the weights, hyb_adamw_step_dev_ema: 64 tensors per launch).
+#include <type_traits>
+
 #include "hyb_common.h"
 #include "hyb_internal.h"
 
@@ -205,9 +208,9 @@ __global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* parti
 // expressions, in the same precision, as hyb_adamw_step forms on the host (and as adamw_kernel's own step_inc branch).  clip: NULL, or the
 // norm_out of grad_norm_kernel: every gradient element is multiplied by clip[1] first (g * 1.0f is exact: an unclipped step is the plain step).
 struct AdamScalars { float decay, omb1, beta2, omb2, eps, step_size, inv_sqrt_bc2, clip; };
-struct AdamDevArgs {
-    AdamTensor t[ADAM_MAX];
-    int chunk_begin[ADAM_MAX + 1];
+template <int N> struct AdamDevTable {
+    AdamTensor t[N];
+    int chunk_begin[N + 1];
     int count;
     const double* hyper;
     const long long* step_inc;
@@ -216,6 +219,15 @@ struct AdamDevArgs {
     long long step;
     const float* clip;
 };
+using AdamDevArgs = AdamDevTable<ADAM_MAX>;
+// The same launch keeping an exponential moving average of the weights (hyb_adamw_step_dev_ema): a sixth pointer per tensor.  80 entries
+// of 48 bytes would not fit the 4 KB of kernel arguments, so this variant's table holds 64.
+constexpr int ADAM_EMA_MAX = 64;
+struct AdamEmaArgs : AdamDevTable<ADAM_EMA_MAX> {
+    float* e[ADAM_EMA_MAX];
+    const double* ema_hyper;     // device double [2] = {decay, warmup (0 or 1)}, written by hyb_adamw_ema_set
+};
+static_assert(sizeof(AdamArgs) <= 4096 && sizeof(AdamDevArgs) <= 4096 && sizeof(AdamEmaArgs) <= 4096, "the tensor table travels in the kernel arguments");
 
 // adam_one with every fused multiply-add written out, so that the device path computes what adamw_kernel computes as the compiler contracts
 // it (test_unclipped_equals_no_clipping: bit-equal to the plain launch).  adamw_kernel's 16-byte groups end in p = fma(p, decay, -(step * q)),
@@ -229,7 +241,13 @@ template <bool VEC> __device__ __forceinline__ void adam_dev_one(float& p, float
     p = VEC ? __builtin_fmaf(p, a.decay, -(a.step_size * q)) : __builtin_fmaf(-a.step_size, q, p * a.decay);
 }
 
-__device__ __forceinline__ void adam_dev_scalars(const AdamDevArgs& a, float* out /* [8] */) {
+// e <- d * e + (1 - d) * p_new: the product rounded, then one fused multiply-add (d == 0: e == p_new exactly, whatever e held)
+__device__ __forceinline__ float adam_ema_one(float e, float p_new, float d32, float omd32) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(d32, e, omd32 * p_new);
+}
+
+template <int N> __device__ __forceinline__ void adam_dev_scalars(const AdamDevTable<N>& a, float* out /* [8] */) {
 #pragma clang fp contract(off)                                    // 1.0 - lr * wd: a product rounded, then a difference, as on the host (no fma)
     const double lr = a.hyper[0], b1 = a.hyper[1], b2 = a.hyper[2], eps = a.hyper[3], wd = a.hyper[4];
     const double tt = (double)(a.step + (a.step_inc ? *a.step_inc : 0ll));
@@ -244,35 +262,66 @@ __device__ __forceinline__ void adam_dev_scalars(const AdamDevArgs& a, float* ou
     out[7] = a.clip ? a.clip[1] : 1.0f;
 }
 
-__global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevArgs a) {
-    __shared__ float s_sc[8];
+// the average's decay at step t = step + *step_inc (n = t - 1 updates so far): d = warmup ? min(decay, (1 + n) / (10 + n)) : decay, in double;
+// d and 1 - d are rounded to fp32 once each
+__device__ __forceinline__ void adam_ema_scalars(const AdamEmaArgs& a, float* out /* [2] */) {
+#pragma clang fp contract(off)
+    const double decay = a.ema_hyper[0];
+    const double n = (double)(a.step + (a.step_inc ? *a.step_inc : 0ll) - 1ll);
+    double d = decay;
+    if (a.ema_hyper[1] != 0.0) {
+        const double w = (1.0 + n) / (10.0 + n);
+        d = w < decay ? w : decay;
+    }
+    out[0] = (float)d;
+    out[1] = (float)(1.0 - d);
+}
+
+template <bool EMA> using AdamDevKernelArgs = std::conditional_t<EMA, AdamEmaArgs, AdamDevArgs>;
+
+// EMA = false: hyb_adamw_step_dev, the launch as it always was.  EMA = true: hyb_adamw_step_dev_ema -- the same body, and where it holds a new
+// parameter value in a register it also moves that parameter's average (2 x 4 more bytes per parameter, no second pass over the weights).
+template <bool EMA> __global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevKernelArgs<EMA> a) {
+    __shared__ float s_sc[EMA ? 10 : 8];
     int ti = 0;
     for (int i = 1; i < a.count; ++i)
         if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
     const AdamTensor t = a.t[ti];
+    float* te = nullptr;
+    if constexpr (EMA) te = a.e[ti];
     const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
-    const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0);
+    const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v | (uintptr_t)te) & 15) == 0);
     constexpr int NK = ADAM_CHUNK / (256 * 4);
     const bool full = vec && base + ADAM_CHUNK <= t.n;            // as in adamw_kernel: a full chunk's 16 loads go out before the scalar work
-    f32x4 p[NK], m[NK], v[NK], g[NK];
+    f32x4 p[NK], m[NK], v[NK], g[NK], ea[EMA ? NK : 1];
     if (full) {
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
             p[k] = *reinterpret_cast<const f32x4*>(t.p + i); m[k] = *reinterpret_cast<const f32x4*>(t.m + i);
             v[k] = *reinterpret_cast<const f32x4*>(t.v + i); g[k] = *reinterpret_cast<const f32x4*>(t.g + i);
+            if constexpr (EMA) ea[k] = *reinterpret_cast<const f32x4*>(te + i);
         }
     }
-    if (threadIdx.x == 0) adam_dev_scalars(a, s_sc);
+    if (threadIdx.x == 0) {
+        adam_dev_scalars(a, s_sc);
+        if constexpr (EMA) adam_ema_scalars(a, s_sc + 8);
+    }
     __syncthreads();
     const AdamScalars sc{s_sc[0], s_sc[1], s_sc[2], s_sc[3], s_sc[4], s_sc[5], s_sc[6], s_sc[7]};
+    float d32 = 0.f, omd32 = 0.f;
+    if constexpr (EMA) { d32 = s_sc[8]; omd32 = s_sc[9]; }
     if (full) {
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { float pj = p[k][j], mj = m[k][j], vj = v[k][j]; adam_dev_one<true>(pj, g[k][j], mj, vj, sc); p[k][j] = pj; m[k][j] = mj; v[k][j] = vj; }
+            for (int j = 0; j < 4; ++j) {
+                float pj = p[k][j], mj = m[k][j], vj = v[k][j]; adam_dev_one<true>(pj, g[k][j], mj, vj, sc); p[k][j] = pj; m[k][j] = mj; v[k][j] = vj;
+                if constexpr (EMA) ea[k][j] = adam_ema_one(ea[k][j], pj, d32, omd32);
+            }
             *reinterpret_cast<f32x4*>(t.p + i) = p[k]; *reinterpret_cast<f32x4*>(t.m + i) = m[k]; *reinterpret_cast<f32x4*>(t.v + i) = v[k];
+            if constexpr (EMA) *reinterpret_cast<f32x4*>(te + i) = ea[k];
         }
     } else {
 #pragma unroll 1
@@ -282,11 +331,20 @@ __global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevArgs a) {
             if (vec && i + 4 <= t.n) {
                 f32x4 pp = *reinterpret_cast<f32x4*>(t.p + i), mm = *reinterpret_cast<f32x4*>(t.m + i), vv = *reinterpret_cast<f32x4*>(t.v + i);
                 const f32x4 gg = *reinterpret_cast<const f32x4*>(t.g + i);
+                f32x4 ee{};
+                if constexpr (EMA) ee = *reinterpret_cast<const f32x4*>(te + i);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { float pj = pp[j], mj = mm[j], vj = vv[j]; adam_dev_one<true>(pj, gg[j], mj, vj, sc); pp[j] = pj; mm[j] = mj; vv[j] = vj; }
+                for (int j = 0; j < 4; ++j) {
+                    float pj = pp[j], mj = mm[j], vj = vv[j]; adam_dev_one<true>(pj, gg[j], mj, vj, sc); pp[j] = pj; mm[j] = mj; vv[j] = vj;
+                    if constexpr (EMA) ee[j] = adam_ema_one(ee[j], pj, d32, omd32);
+                }
                 *reinterpret_cast<f32x4*>(t.p + i) = pp; *reinterpret_cast<f32x4*>(t.m + i) = mm; *reinterpret_cast<f32x4*>(t.v + i) = vv;
+                if constexpr (EMA) *reinterpret_cast<f32x4*>(te + i) = ee;
             } else {
-                for (long long e = i; e < i + 4 && e < t.n; ++e) adam_dev_one<false>(t.p[e], t.g[e], t.m[e], t.v[e], sc);
+                for (long long e = i; e < i + 4 && e < t.n; ++e) {
+                    adam_dev_one<false>(t.p[e], t.g[e], t.m[e], t.v[e], sc);
+                    if constexpr (EMA) te[e] = adam_ema_one(te[e], t.p[e], d32, omd32);
+                }
             }
         }
     }
@@ -297,6 +355,38 @@ __global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevArgs a) {
             *a.advance += 1;
         }
     }
+}
+
+__global__ __launch_bounds__(64) void ema_set_kernel(double* ema_hyper, double decay, double warmup) {
+    if (threadIdx.x < 2) ema_hyper[threadIdx.x] = threadIdx.x == 0 ? decay : warmup;
+}
+
+// hyb_adamw_step_dev (ema == NULL) and hyb_adamw_step_dev_ema: the tensor table in launches of at most the variant's capacity, the last
+// of which advances the counter
+template <bool EMA> int adamw_dev_launch(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                         float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
+                                         long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream) {
+    constexpr int MAX = EMA ? ADAM_EMA_MAX : ADAM_MAX;
+    for (int first = 0; first < count; first += MAX) {
+        AdamDevKernelArgs<EMA> a{};
+        const int n = count - first < MAX ? count - first : MAX;
+        int chunks = 0;
+        for (int i = 0; i < n; ++i) {
+            a.t[i] = AdamTensor{params[first + i], grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
+            if constexpr (EMA) a.e[i] = ema[first + i];
+            a.chunk_begin[i] = chunks;
+            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
+        }
+        a.chunk_begin[n] = chunks;
+        a.count = n;
+        a.hyper = hyper; a.step_inc = step_inc; a.step = step; a.clip = clip;
+        if constexpr (EMA) a.ema_hyper = ema_hyper;
+        a.advance = (advance_ticket && first + MAX >= count) ? step_inc : nullptr;            // the last launch of the call advances the counter
+        a.ticket = advance_ticket;
+        hipLaunchKernelGGL(adamw_dev_kernel<EMA>, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        HYB_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 }  // namespace
@@ -358,24 +448,24 @@ extern "C" int hyb_adamw_step_dev(int count, float* const* params, const float* 
                                   unsigned int* advance_ticket, const float* clip, void* stream) {
     HYB_CHECK_ARG(count > 0 && params && grads && exp_avg && exp_avg_sq && numel && hyper && step >= 1 && (!advance_ticket || step_inc));
     for (int i = 0; i < count; ++i) HYB_CHECK_ARG(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && numel[i] > 0);
-    for (int first = 0; first < count; first += ADAM_MAX) {
-        AdamDevArgs a{};
-        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
-        int chunks = 0;
-        for (int i = 0; i < n; ++i) {
-            a.t[i] = AdamTensor{params[first + i], grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
-            a.chunk_begin[i] = chunks;
-            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
-        }
-        a.chunk_begin[n] = chunks;
-        a.count = n;
-        a.hyper = hyper; a.step_inc = step_inc; a.step = step; a.clip = clip;
-        a.advance = (advance_ticket && first + ADAM_MAX >= count) ? step_inc : nullptr;       // the last launch of the call advances the counter
-        a.ticket = advance_ticket;
-        hipLaunchKernelGGL(adamw_dev_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
-        HYB_LAUNCH_CHECK();
-    }
+    return adamw_dev_launch<false>(count, params, grads, exp_avg, exp_avg_sq, nullptr, numel, hyper, nullptr, step, step_inc, advance_ticket, clip, stream);
+}
+
+extern "C" int hyb_adamw_ema_set(double* ema_hyper, double decay, double warmup, void* stream) {
+    HYB_CHECK_ARG(ema_hyper && decay >= 0.0 && decay < 1.0 && (warmup == 0.0 || warmup == 1.0));
+    hipLaunchKernelGGL(ema_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ema_hyper, decay, warmup);
+    HYB_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int hyb_adamw_step_dev_ema(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                      float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
+                                      long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream) {
+    HYB_CHECK_ARG(count > 0 && params && grads && exp_avg && exp_avg_sq && ema && numel && hyper && ema_hyper && step >= 1 &&
+                  (!advance_ticket || step_inc));
+    for (int i = 0; i < count; ++i)
+        HYB_CHECK_ARG(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && ema[i] && ema[i] != params[i] && numel[i] > 0);
+    return adamw_dev_launch<true>(count, params, grads, exp_avg, exp_avg_sq, ema, numel, hyper, ema_hyper, step, step_inc, advance_ticket, clip, stream);
 }
 
 extern "C" int hyb_adamw_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,

@@ -14,7 +14,8 @@ What makes capture legal here
   * step-dependent scalars live on the device: the kernels add a device counter to their by-value dropout seed, and AdamW forms
     its bias corrections from state['step'] + counter on the device (hyb_*'s seed_inc / step_inc arguments).  The counter is
     advanced inside the last graph, so every replay is a new step with new masks.  With dynamic_hyper=True (or max_grad_norm set on the
-    optimizer) AdamW's hyper-parameters live on the device too: step() uploads what changed (optimizer.sync_hyper(), never captured)
+    optimizer, or ema_decay: the weight average the AdamW launch then keeps, its decay and warm-up flag read from the device as well)
+    AdamW's hyper-parameters live on the device too: step() uploads what changed (optimizer.sync_hyper(), never captured)
     before it replays, so a torch.optim.lr_scheduler works across replays, and the gradient norm is taken and applied inside piece C --
     with data parallelism over the averaged gradients in the buckets, as DistributedDataParallel + clip_grad_norm_ would;
   * a HybridCrossEntropyLoss with options (class weights, ignore_index, label smoothing) stays inside the temporal part's launches: the
@@ -59,6 +60,8 @@ class GraphedTrainStep:
         # them by value, so a later change would be lost silently -- step() refuses it instead
         self._dev_hyper = optimizer.uses_device_hyper()
         self._clipping = any(g.get("max_grad_norm") is not None for g in optimizer.param_groups)
+        # which groups' captured AdamW launch also keeps the weight average (hyb_adamw_step_dev_ema): a kernel variant, fixed by the capture
+        self._ema_on = [g.get("ema_decay") is not None for g in optimizer.param_groups]
         self._captured_hyper = self._hyper_now()
         from .modules import HybridCrossEntropyLoss
         self._fused_loss = (type(criterion) is HybridCrossEntropyLoss and hasattr(model, "forward_temporal_loss")
@@ -158,6 +161,9 @@ class GraphedTrainStep:
             raise RuntimeError(f"GraphedTrainStep: the criterion's {', '.join(what)} changed after capture, but the captured loss launch carries "
                                "the old value -- construct a new GraphedTrainStep (an in-place update of criterion.weight needs none: the "
                                "buffer is read at replay time)")
+        if [g.get("ema_decay") is not None for g in self.optimizer.param_groups] != self._ema_on:
+            raise RuntimeError("GraphedTrainStep: ema_decay was switched on or off after capture; the captured AdamW launch does (not) keep the "
+                               "average -- set it on the optimizer before constructing GraphedTrainStep (its value may change at any time)")
         if self._dev_hyper:
             if any((g.get("max_grad_norm") is not None) != self._clipping for g in self.optimizer.param_groups):
                 raise RuntimeError("GraphedTrainStep: max_grad_norm was switched on or off after capture; the norm launch is (not) part of the "

@@ -9,7 +9,14 @@ Two things a training run needs on top of that, both built on hyper-parameters t
     gradients and the clip coefficient (`hyb_grad_norm`, bit-reproducible), the AdamW launch scales every gradient element by it;
   * `set_dynamic_hyper(True)`: the AdamW launch reads lr / betas / eps / weight_decay from the device block (`hyb_adamw_step_dev`), so a
     launch captured into a hipGraph follows `param_groups[i]["lr"] = ...` -- i.e. any `torch.optim.lr_scheduler` -- after a
-    `sync_hyper()`, which `step()` (eager) and `GraphedTrainStep.step()` (before the replay) call."""
+    `sync_hyper()`, which `step()` (eager) and `GraphedTrainStep.step()` (before the replay) call;
+  * `ema_decay=d`: an exponential moving average of the weights (timm's ModelEma, swa_utils.AveragedModel) kept by the AdamW launch itself
+    (`hyb_adamw_step_dev_ema`): `state[p]["ema"] <- d * ema + (1 - d) * p_new` where the launch holds `p_new` in a register -- no second
+    pass over the weights, no extra launch.  `ema_warmup=True` uses `min(d, (1 + n) / (10 + n))` after n earlier steps.  Both live in a device
+    block (`double [groups, 2]`), so a captured step follows a decay changed between replays.  `ema_model(model)` gives a twin module whose
+    parameters ARE the averages, for `predict` / `GraphedPredict`.  The average follows only parameters that are stepped: a parameter
+    without a gradient keeps its old average."""
+import copy
 import ctypes
 
 import torch
@@ -19,13 +26,17 @@ from .ops import _stream
 
 
 class HybridAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_decay=None, ema_warmup=False):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be None (no clipping) or > 0")
-        # max_grad_norm sits in the groups only so that it travels in the state dict: clipping is global, every group carries the same value
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm))
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must be None (no average) or in [0, 1)")
+        # max_grad_norm sits in the groups only so that it travels in the state dict: clipping is global, every group carries the same value;
+        # ema_decay / ema_warmup are per group (None: that group takes the launch without the average)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                      ema_decay=ema_decay, ema_warmup=bool(ema_warmup)))
         self._tables = {}            # per group: cached pointer tables of the tensors whose addresses never change
         self._step_counter = None    # device int64 [1]: the kernel uses step + counter (captured launches, graph.GraphedTrainStep)
         self._advance = False
@@ -35,6 +46,8 @@ class HybridAdamW(torch.optim.Optimizer):
         self._hyper_sent = {}        # per group: the values last uploaded (sync_hyper uploads on change only)
         self._norm_out = None        # device fp32 [2]: the last step's unclipped total gradient norm, its clip coefficient
         self._partials = None        # (numels, device fp32 [chunks], host numel array): hyb_grad_norm's per-chunk sums of squares
+        self._ema_hyper = None       # device double [groups, 2]: ema_decay, ema_warmup (0 / 1) per group; created with _hyper
+        self._ema_sent = {}          # per group: the (decay, warmup) last uploaded
 
     def set_step_counter(self, counter, advance=False):
         """With a device counter the step number used by the kernel is state['step'] + counter, read on the device: one captured
@@ -52,7 +65,18 @@ class HybridAdamW(torch.optim.Optimizer):
         self._dynamic = bool(flag)
 
     def uses_device_hyper(self):
-        return self._dynamic or any(g.get("max_grad_norm") is not None for g in self.param_groups)
+        """(The average always takes the device path: its decay is read on the device, so a change between replays is picked up.)"""
+        return self._dynamic or any(g.get("max_grad_norm") is not None or g.get("ema_decay") is not None for g in self.param_groups)
+
+    @staticmethod
+    def _group_ema(group):
+        """None (no average; also a group loaded from a torch.optim.AdamW state dict, which lacks the key), or (decay, warmup as 0.0 / 1.0)."""
+        d = group.get("ema_decay")
+        if d is None:
+            return None
+        if not 0.0 <= float(d) < 1.0:
+            raise ValueError("ema_decay must be None (no average) or in [0, 1)")
+        return (float(d), 1.0 if group.get("ema_warmup") else 0.0)
 
     def _clip_value(self):
         vals = {None if g.get("max_grad_norm") is None else float(g["max_grad_norm"]) for g in self.param_groups}
@@ -75,6 +99,8 @@ class HybridAdamW(torch.optim.Optimizer):
                 raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
             self._hyper = torch.zeros(len(self.param_groups), 6, dtype=torch.float64, device=dev)
             self._hyper_sent = {}
+            self._ema_hyper = torch.zeros(len(self.param_groups), 2, dtype=torch.float64, device=dev)
+            self._ema_sent = {}
             if self._norm_out is None or self._norm_out.device != dev:
                 self._norm_out = torch.zeros(2, dtype=torch.float32, device=dev)
         return self._hyper
@@ -85,9 +111,9 @@ class HybridAdamW(torch.optim.Optimizer):
         return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), 0.0 if c is None else float(c))
 
     def sync_hyper(self):
-        """Upload every group's (lr, betas, eps, weight_decay, max_grad_norm) that differs from what the device holds (one tiny launch per
-        changed group on the current stream; the host never waits).  Must NOT be captured: the values travel as kernel arguments, a captured
-        upload would put the capture-time values back at every replay."""
+        """Upload every group's (lr, betas, eps, weight_decay, max_grad_norm), and (ema_decay, ema_warmup) where the group keeps an average,
+        that differs from what the device holds (one tiny launch per changed group on the current stream; the host never waits).  Must NOT
+        be captured: the values travel as kernel arguments, a captured upload would put the capture-time values back at every replay."""
         hyper = self._device_buffers()
         for gi, group in enumerate(self.param_groups):
             vals = self._group_hyper(group)
@@ -96,6 +122,12 @@ class HybridAdamW(torch.optim.Optimizer):
                     raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
                 lib.call("hyb_adamw_hyper_set", hyper[gi], *vals, _stream())
                 self._hyper_sent[gi] = vals
+            ema = self._group_ema(group)
+            if ema is not None and self._ema_sent.get(gi) != ema:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
+                lib.call("hyb_adamw_ema_set", self._ema_hyper[gi], *ema, _stream())
+                self._ema_sent[gi] = ema
 
     @property
     def grad_norm(self):
@@ -114,11 +146,56 @@ class HybridAdamW(torch.optim.Optimizer):
         super().load_state_dict(state_dict)
         self._tables.clear()
         for st in self.state.values():              # torch casts loaded state to the parameter's dtype/device; keep the layout the kernel needs
-            for k in ("exp_avg", "exp_avg_sq"):
+            for k in ("exp_avg", "exp_avg_sq", "ema"):
                 if k in st:
                     st[k] = st[k].to(torch.float32).contiguous()
             if "step" in st and torch.is_tensor(st["step"]):
                 st["step"] = int(st["step"].item())
+
+    def _new_ema(self, p):
+        if p.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("HybridAdamW: a parameter's weight average does not exist yet and cannot be created under stream capture -- "
+                               "call ema_init() (or take one eager step()) before capturing")
+        return p.detach().clone()
+
+    @torch.no_grad()
+    def ema_init(self):
+        """Create the average of every parameter of every group with an ema_decay that has none yet, as a copy of the parameter's current
+        value.  step() does the same for a parameter the first time it steps it (the value BEFORE that step, as a deep copy of the model
+        taken before training); call this to start all averages at once, e.g. before capturing, or for parameters that get gradients later."""
+        for group in self.param_groups:
+            if group.get("ema_decay") is None:
+                continue
+            for p in group["params"]:
+                st = self.state[p]
+                if "ema" not in st:
+                    st["ema"] = self._new_ema(p)
+
+    def ema_model(self, model):
+        """A twin of `model` (an nn.Module holding this optimizer's parameters) for evaluating the averaged weights while training goes on:
+        a deep copy of the module structure in which
+          * every parameter this optimizer averages IS its `state[p]["ema"]` tensor (same memory: nothing is copied, now or per use),
+          * every other parameter is the live parameter's memory, and every buffer is the live model's buffer itself (BatchNorm running
+            statistics are averages already, and always current),
+          * every parameter has requires_grad=False.
+        `twin.predict(x)` and `GraphedPredict(twin, x)` read whatever the averages hold when they run.  load_state_dict() replaces the
+        state tensors: build a new twin after it.  Raises if an averaged parameter has no average yet (step() or ema_init() first)."""
+        averaged = {}
+        for group in self.param_groups:
+            if group.get("ema_decay") is None:
+                continue
+            for p in group["params"]:
+                e = self.state[p].get("ema") if p in self.state else None
+                if e is None:
+                    raise RuntimeError("HybridAdamW.ema_model: a parameter of a group with ema_decay has no average yet -- take a step() or "
+                                       "call ema_init() first")
+                averaged[id(p)] = e
+        memo = {}
+        for p in model.parameters():
+            memo[id(p)] = torch.nn.Parameter(averaged.get(id(p), p.detach()), requires_grad=False)
+        for b in model.buffers():
+            memo[id(b)] = b
+        return copy.deepcopy(model, memo)
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
@@ -140,11 +217,14 @@ class HybridAdamW(torch.optim.Optimizer):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
+            ema = self._group_ema(group)
             for p in ps:
                 if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                     raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
                 st = self.state[p]
-                if not st:
+                if ema is not None and "ema" not in st:
+                    st["ema"] = self._new_ema(p)         # the value before this step
+                if "exp_avg" not in st:                  # (ema_init() may have left a state that holds the average only)
                     st["step"] = 0
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
@@ -155,12 +235,16 @@ class HybridAdamW(torch.optim.Optimizer):
             if len(steps) != 1:
                 raise RuntimeError("HybridAdamW: parameters of one group must share the step count")
             # the cached pointer tables are valid only while every parameter AND both of its moment tensors stay where they are:
-            # load_state_dict() / a rollback replaces the moments with new allocations (the old ones may already be freed)
-            addrs = [(p.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for p in ps]
+            # load_state_dict() / a rollback replaces the moments (and the averages) with new allocations (the old ones may already be freed)
+            if ema is None:
+                addrs = [(p.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for p in ps]
+            else:
+                addrs = [(p.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(), self.state[p]["ema"].data_ptr())
+                         for p in ps]
             tab = self._tables.get(gi)
             if tab is None or tab[1] != addrs:
                 tab = (None, addrs, ptr_array([a[0] for a in addrs]), ptr_array([a[1] for a in addrs]), ptr_array([a[2] for a in addrs]),
-                       (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps]))
+                       (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps]), None if ema is None else ptr_array([a[3] for a in addrs]))
                 self._tables[gi] = tab
             grads = []
             for p in ps:
@@ -183,7 +267,7 @@ class HybridAdamW(torch.optim.Optimizer):
         hyper = self._device_buffers()
         if torch.cuda.is_current_stream_capturing():
             # only hyb_grad_norm and hyb_adamw_step_dev are recorded; the upload is the replaying caller's (GraphedTrainStep.step)
-            if len(self._hyper_sent) != len(self.param_groups):
+            if len(self._hyper_sent) != len(self.param_groups) or any(gi not in self._ema_sent for gi, _, tab, _, _ in work if tab[6] is not None):
                 raise RuntimeError("HybridAdamW: hyper-parameters were never uploaded -- call sync_hyper() before capturing step()")
         else:
             self.sync_hyper()
@@ -203,5 +287,9 @@ class HybridAdamW(torch.optim.Optimizer):
             lib.call("hyb_grad_norm", len(all_grads), all_grads, self._partials[2], self._partials[1], hyper[work[0][0]], self._norm_out, _stream())
             clip_coef = self._norm_out
         for gi, n, tab, grads, step in work:
-            lib.call("hyb_adamw_step_dev", n, tab[2], grads, tab[3], tab[4], tab[5], hyper[gi], step, counter, ticket, clip_coef, _stream())
+            if tab[6] is None:
+                lib.call("hyb_adamw_step_dev", n, tab[2], grads, tab[3], tab[4], tab[5], hyper[gi], step, counter, ticket, clip_coef, _stream())
+            else:                                   # the same launch, which also moves the averages
+                lib.call("hyb_adamw_step_dev_ema", n, tab[2], grads, tab[3], tab[4], tab[6], tab[5], hyper[gi], self._ema_hyper[gi], step, counter,
+                         ticket, clip_coef, _stream())
         return loss
