@@ -657,6 +657,32 @@ int hyb_adamw_step_dev_ema(int count, float* const* params, const float* const* 
                            long long* step_inc, unsigned int* advance_ticket, const float* clip /* norm_out of hyb_grad_norm, or NULL */,
                            void* stream);
 
+/* ---- gradient accumulation: one optimizer step over k micro-batches --------------------------------------------------------------------
+ * (New symbols only; hyb_abi_version() stays 9.)  acc[i]: one fp32 accumulator of numel[i] elements per parameter, caller-owned, zero at
+ * every optimizer-step boundary.  Micro-batches 1 .. k - 1 end in hyb_grad_accumulate, the k-th in hyb_adamw_step_dev_acc (after
+ * hyb_grad_norm_acc when clipping).  With inv_k = (float)(1.0 / (double)k) the effective gradient of one element is
+ *     G = (acc + g) * inv_k        (grads == NULL as a whole: G = acc * inv_k -- data parallelism, acc is the all-reduced bucket)
+ * the sum rounded, then the product rounded (no contraction); k == 1 gives inv_k == 1.0f.
+ *
+ * hyb_grad_accumulate: acc[i][e] = acc[i][e] + grads[i][e] for every tensor of the table in one launch (80 tensors per launch, more
+ * tensors = more launches); 4096-element chunks, 16-byte accesses where both pointers are aligned; grads is only read.  3 x 4 bytes
+ * per parameter.  -1 for a NULL array or entry, acc[i] == grads[i], numel[i] <= 0, count <= 0. */
+int hyb_grad_accumulate(int count, float* const* acc, const float* const* grads, const long long* numel, void* stream);
+/* hyb_grad_norm_acc: hyb_grad_norm over G -- the same workspace (hyb_grad_norm_workspace), the same summation order, the same final
+ * launch, so the norm equals hyb_grad_norm over a materialised G bit for bit.  acc and grads are only read. */
+int hyb_grad_norm_acc(int count, const float* const* acc, const float* const* grads /* or NULL */, const long long* numel, long long k,
+                      float* partials, const double* hyper, float* norm_out /* [2] */, void* stream);
+/* hyb_adamw_step_dev_acc: hyb_adamw_step_dev (ema == ema_hyper == NULL) or hyb_adamw_step_dev_ema (both given) with G in place of the
+ * gradient (G * clip[1] follows as there), which also stores +0.0f to every element of acc in the same launch: 9 x 4 bytes per
+ * parameter, 11 x 4 with the average, and no sum, scale or memset pass.  The step number used (bias corrections, the average's warm-up)
+ * is step + (step_inc ? *step_inc / k : 0), integer division: the counter counts MICRO-steps, and an advancing call adds 1 to it like
+ * every other micro-step does.  76 tensors per launch, 64 with the average.  -1 also for k < 1, a NULL acc entry, acc[i] == params[i],
+ * ema without ema_hyper or the reverse. */
+int hyb_adamw_step_dev_acc(int count, float* const* params, const float* const* grads /* or NULL */, float* const* exp_avg,
+                           float* const* exp_avg_sq, float* const* acc, float* const* ema /* or NULL */, const long long* numel,
+                           const double* hyper, const double* ema_hyper /* or NULL */, long long k, long long step, long long* step_inc,
+                           unsigned int* advance_ticket, const float* clip /* norm_out of hyb_grad_norm_acc, or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,9 @@
 // The tensor table travels in the kernel arguments (up to 80 tensors per launch), a workgroup owns 4096 consecutive elements
 // of one tensor and finds it by scanning the table's chunk offsets; HBM-bound: 7 x 4 bytes per parameter (9 x 4 in the variant that also keeps
 // an exponential moving average of the weights, hyb_adamw_step_dev_ema: 64 tensors per launch).
+// Gradient accumulation over k micro-batches: hyb_grad_accumulate (acc += g, 3 x 4 bytes per parameter) ends micro-batches 1 .. k - 1,
+// hyb_adamw_step_dev_acc ends the k-th: it steps on (acc + g) / k and leaves acc zeroed (9 x 4 bytes, 11 x 4 with the average) -- no
+// separate sum, scale or memset pass.
 #include <type_traits>
 
 #include "hyb_common.h"
@@ -136,9 +139,27 @@ struct GradNormArgs {
     int chunk_offset;                     // index of this launch's first chunk among all chunks of the call (more than 80 tensors = several launches)
     float* partials;
 };
+// hyb_grad_norm_acc: the norm of the effective gradient of an accumulated step, G = (acc + g) * inv_k (g[] all NULL: G = acc * inv_k)
+struct GradNormAccArgs : GradNormArgs {
+    const float* acc[ADAM_MAX];
+    float inv_k;
+};
+static_assert(sizeof(GradNormAccArgs) <= 4096, "the tensor table travels in the kernel arguments");
+
+// Which gradient a launch works on.  GRAD_PLAIN: g.  GRAD_ACC_G: G = (acc + g) * inv_k, the sum rounded, then the product rounded (no
+// contraction; inv_k == 1.0f for k == 1).  GRAD_ACC: G = acc * inv_k (data parallelism: acc is the all-reduced bucket, there is no g).
+// (named constants of type int, not an unnamed enum: a kernel's template arguments are part of its mangled name, and the host and device
+// passes number unnamed types differently, so the launch would not find the kernel)
+constexpr int GRAD_PLAIN = 0, GRAD_ACC_G = 1, GRAD_ACC = 2;
+template <int MODE> __device__ __forceinline__ float eff_grad(float acc, float g, float inv_k) {
+#pragma clang fp contract(off)
+    if constexpr (MODE == GRAD_PLAIN) return g;
+    else if constexpr (MODE == GRAD_ACC) return acc * inv_k;
+    else { const float sum = acc + g; return sum * inv_k; }
+}
 
 // one chunk's sum of squares; every thread of the workgroup must call it, thread 0 gets the result
-__device__ __forceinline__ float grad_chunk_sumsq(const GradNormArgs& a, float* s_wave /* [4] */) {
+template <int MODE = GRAD_PLAIN, typename Args = GradNormArgs> __device__ __forceinline__ float grad_chunk_sumsq(const Args& a, float* s_wave /* [4] */) {
     int ti = 0;
     for (int i = 1; i < a.count; ++i)
         if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
@@ -147,19 +168,50 @@ __device__ __forceinline__ float grad_chunk_sumsq(const GradNormArgs& a, float* 
     const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
     constexpr int NK = ADAM_CHUNK / (256 * 4);
     float s = 0.f;
-    if ((((uintptr_t)g & 15) == 0) && base + ADAM_CHUNK <= n) {
-        f32x4 v[NK];
+    if constexpr (MODE == GRAD_PLAIN) {
+        if ((((uintptr_t)g & 15) == 0) && base + ADAM_CHUNK <= n) {
+            f32x4 v[NK];
 #pragma unroll
-        for (int k = 0; k < NK; ++k) v[k] = *reinterpret_cast<const f32x4*>(g + base + ((long long)k * 256 + threadIdx.x) * 4);
+            for (int k = 0; k < NK; ++k) v[k] = *reinterpret_cast<const f32x4*>(g + base + ((long long)k * 256 + threadIdx.x) * 4);
 #pragma unroll
-        for (int k = 0; k < NK; ++k)
+            for (int k = 0; k < NK; ++k)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) s = __builtin_fmaf(v[k][j], v[k][j], s);
-    } else {
+                for (int j = 0; j < 4; ++j) s = __builtin_fmaf(v[k][j], v[k][j], s);
+        } else {
 #pragma unroll 1
-        for (int k = 0; k < NK; ++k) {
-            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
-            for (long long e = i; e < i + 4 && e < n; ++e) s = __builtin_fmaf(g[e], g[e], s);
+            for (int k = 0; k < NK; ++k) {
+                const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+                for (long long e = i; e < i + 4 && e < n; ++e) s = __builtin_fmaf(g[e], g[e], s);
+            }
+        }
+    } else {                                                      // the same elements in the same order, each formed by eff_grad first
+        constexpr bool HAS_G = MODE != GRAD_ACC;
+        const float* __restrict__ acc = a.acc[ti];
+        const float inv_k = a.inv_k;
+        if (((((uintptr_t)g | (uintptr_t)acc) & 15) == 0) && base + ADAM_CHUNK <= n) {
+            f32x4 v[HAS_G ? NK : 1], w[NK];
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+                if constexpr (HAS_G) v[k] = *reinterpret_cast<const f32x4*>(g + i);
+                w[k] = *reinterpret_cast<const f32x4*>(acc + i);
+            }
+#pragma unroll
+            for (int k = 0; k < NK; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float x = eff_grad<MODE>(w[k][j], HAS_G ? v[k][j] : 0.f, inv_k);
+                    s = __builtin_fmaf(x, x, s);
+                }
+        } else {
+#pragma unroll 1
+            for (int k = 0; k < NK; ++k) {
+                const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+                for (long long e = i; e < i + 4 && e < n; ++e) {
+                    const float x = eff_grad<MODE>(acc[e], HAS_G ? g[e] : 0.f, inv_k);
+                    s = __builtin_fmaf(x, x, s);
+                }
+            }
         }
     }
     s = wave_sum(s);
@@ -199,6 +251,12 @@ __global__ __launch_bounds__(256) void grad_norm_kernel(GradNormArgs a) {
     if (threadIdx.x == 0) a.partials[a.chunk_offset + blockIdx.x] = s;
 }
 
+template <int MODE> __global__ __launch_bounds__(256) void grad_norm_acc_kernel(GradNormAccArgs a) {
+    __shared__ float s_wave[4];
+    const float s = grad_chunk_sumsq<MODE>(a, s_wave);
+    if (threadIdx.x == 0) a.partials[a.chunk_offset + blockIdx.x] = s;
+}
+
 __global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* partials, int total, const double* hyper, float* norm_out) {
     __shared__ double s_sum[256];
     grad_norm_finish([partials](int i) { return partials[i]; }, total, hyper, norm_out, s_sum);
@@ -227,7 +285,22 @@ struct AdamEmaArgs : AdamDevTable<ADAM_EMA_MAX> {
     float* e[ADAM_EMA_MAX];
     const double* ema_hyper;     // device double [2] = {decay, warmup (0 or 1)}, written by hyb_adamw_ema_set
 };
-static_assert(sizeof(AdamArgs) <= 4096 && sizeof(AdamDevArgs) <= 4096 && sizeof(AdamEmaArgs) <= 4096, "the tensor table travels in the kernel arguments");
+// The accumulated step (hyb_adamw_step_dev_acc): one more pointer per tensor, the accumulator, and k.  76 entries without the average, 64 with.
+constexpr int ADAM_ACC_MAX = 76, ADAM_EMA_ACC_MAX = 64;
+struct AdamAccArgs : AdamDevTable<ADAM_ACC_MAX> {
+    float* acc[ADAM_ACC_MAX];
+    long long k;                 // micro-batches per optimizer step; the step number is step + *step_inc / k (the counter counts micro-steps)
+    float inv_k;                 // (float)(1.0 / (double)k)
+};
+struct AdamEmaAccArgs : AdamDevTable<ADAM_EMA_ACC_MAX> {
+    float* e[ADAM_EMA_ACC_MAX];
+    const double* ema_hyper;
+    float* acc[ADAM_EMA_ACC_MAX];
+    long long k;
+    float inv_k;
+};
+static_assert(sizeof(AdamArgs) <= 4096 && sizeof(AdamDevArgs) <= 4096 && sizeof(AdamEmaArgs) <= 4096 && sizeof(AdamAccArgs) <= 4096 &&
+              sizeof(AdamEmaAccArgs) <= 4096, "the tensor table travels in the kernel arguments");
 
 // adam_one with every fused multiply-add written out, so that the device path computes what adamw_kernel computes as the compiler contracts
 // it (test_unclipped_equals_no_clipping: bit-equal to the plain launch).  adamw_kernel's 16-byte groups end in p = fma(p, decay, -(step * q)),
@@ -247,10 +320,16 @@ __device__ __forceinline__ float adam_ema_one(float e, float p_new, float d32, f
     return __builtin_fmaf(d32, e, omd32 * p_new);
 }
 
-template <int N> __device__ __forceinline__ void adam_dev_scalars(const AdamDevTable<N>& a, float* out /* [8] */) {
+// the step number: step + *step_inc; the accumulated step (ACCUM, a.k micro-steps per optimizer step): step + *step_inc / k
+template <bool ACCUM, typename Args> __device__ __forceinline__ long long adam_step_number(const Args& a) {
+    if constexpr (ACCUM) return a.step + (a.step_inc ? *a.step_inc / a.k : 0ll);
+    else return a.step + (a.step_inc ? *a.step_inc : 0ll);
+}
+
+template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_dev_scalars(const Args& a, float* out /* [8] */) {
 #pragma clang fp contract(off)                                    // 1.0 - lr * wd: a product rounded, then a difference, as on the host (no fma)
     const double lr = a.hyper[0], b1 = a.hyper[1], b2 = a.hyper[2], eps = a.hyper[3], wd = a.hyper[4];
-    const double tt = (double)(a.step + (a.step_inc ? *a.step_inc : 0ll));
+    const double tt = (double)adam_step_number<ACCUM>(a);
     const double prod = lr * wd;
     out[0] = (float)(1.0 - prod);
     out[1] = (float)(1.0 - b1);
@@ -264,10 +343,10 @@ template <int N> __device__ __forceinline__ void adam_dev_scalars(const AdamDevT
 
 // the average's decay at step t = step + *step_inc (n = t - 1 updates so far): d = warmup ? min(decay, (1 + n) / (10 + n)) : decay, in double;
 // d and 1 - d are rounded to fp32 once each
-__device__ __forceinline__ void adam_ema_scalars(const AdamEmaArgs& a, float* out /* [2] */) {
+template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_ema_scalars(const Args& a, float* out /* [2] */) {
 #pragma clang fp contract(off)
     const double decay = a.ema_hyper[0];
-    const double n = (double)(a.step + (a.step_inc ? *a.step_inc : 0ll) - 1ll);
+    const double n = (double)(adam_step_number<ACCUM>(a) - 1ll);
     double d = decay;
     if (a.ema_hyper[1] != 0.0) {
         const double w = (1.0 + n) / (10.0 + n);
@@ -277,11 +356,16 @@ __device__ __forceinline__ void adam_ema_scalars(const AdamEmaArgs& a, float* ou
     out[1] = (float)(1.0 - d);
 }
 
-template <bool EMA> using AdamDevKernelArgs = std::conditional_t<EMA, AdamEmaArgs, AdamDevArgs>;
+template <bool EMA, int ACC> using AdamDevKernelArgs =
+    std::conditional_t<ACC != GRAD_PLAIN, std::conditional_t<EMA, AdamEmaAccArgs, AdamAccArgs>, std::conditional_t<EMA, AdamEmaArgs, AdamDevArgs>>;
 
 // EMA = false: hyb_adamw_step_dev, the launch as it always was.  EMA = true: hyb_adamw_step_dev_ema -- the same body, and where it holds a new
 // parameter value in a register it also moves that parameter's average (2 x 4 more bytes per parameter, no second pass over the weights).
-template <bool EMA> __global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevKernelArgs<EMA> a) {
+// ACC != GRAD_PLAIN: hyb_adamw_step_dev_acc -- the same body again on the effective gradient G of an accumulated step (eff_grad: the
+// accumulator is one more 16-byte load per group, issued with the others), which also stores +0.0f over the accumulator it has read;
+// GRAD_ACC: there is no g (t.g is NULL and never read).
+template <bool EMA, int ACC = GRAD_PLAIN> __global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC> a) {
+    constexpr bool ACCUM = ACC != GRAD_PLAIN, HAS_G = ACC != GRAD_ACC;
     __shared__ float s_sc[EMA ? 10 : 8];
     int ti = 0;
     for (int i = 1; i < a.count; ++i)
@@ -289,23 +373,28 @@ template <bool EMA> __global__ __launch_bounds__(256) void adamw_dev_kernel(Adam
     const AdamTensor t = a.t[ti];
     float* te = nullptr;
     if constexpr (EMA) te = a.e[ti];
+    float* ta = nullptr;
+    float inv_k = 1.f;
+    if constexpr (ACCUM) { ta = a.acc[ti]; inv_k = a.inv_k; }
     const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
-    const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v | (uintptr_t)te) & 15) == 0);
+    const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v | (uintptr_t)te | (uintptr_t)ta) & 15) == 0);
     constexpr int NK = ADAM_CHUNK / (256 * 4);
     const bool full = vec && base + ADAM_CHUNK <= t.n;            // as in adamw_kernel: a full chunk's 16 loads go out before the scalar work
-    f32x4 p[NK], m[NK], v[NK], g[NK], ea[EMA ? NK : 1];
+    f32x4 p[NK], m[NK], v[NK], g[HAS_G ? NK : 1], ea[EMA ? NK : 1], ac[ACCUM ? NK : 1];
     if (full) {
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
             const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
             p[k] = *reinterpret_cast<const f32x4*>(t.p + i); m[k] = *reinterpret_cast<const f32x4*>(t.m + i);
-            v[k] = *reinterpret_cast<const f32x4*>(t.v + i); g[k] = *reinterpret_cast<const f32x4*>(t.g + i);
+            v[k] = *reinterpret_cast<const f32x4*>(t.v + i);
+            if constexpr (HAS_G) g[k] = *reinterpret_cast<const f32x4*>(t.g + i);
             if constexpr (EMA) ea[k] = *reinterpret_cast<const f32x4*>(te + i);
+            if constexpr (ACCUM) ac[k] = *reinterpret_cast<const f32x4*>(ta + i);
         }
     }
     if (threadIdx.x == 0) {
-        adam_dev_scalars(a, s_sc);
-        if constexpr (EMA) adam_ema_scalars(a, s_sc + 8);
+        adam_dev_scalars<ACCUM>(a, s_sc);
+        if constexpr (EMA) adam_ema_scalars<ACCUM>(a, s_sc + 8);
     }
     __syncthreads();
     const AdamScalars sc{s_sc[0], s_sc[1], s_sc[2], s_sc[3], s_sc[4], s_sc[5], s_sc[6], s_sc[7]};
@@ -317,11 +406,14 @@ template <bool EMA> __global__ __launch_bounds__(256) void adamw_dev_kernel(Adam
             const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float pj = p[k][j], mj = m[k][j], vj = v[k][j]; adam_dev_one<true>(pj, g[k][j], mj, vj, sc); p[k][j] = pj; m[k][j] = mj; v[k][j] = vj;
+                float pj = p[k][j], mj = m[k][j], vj = v[k][j];
+                adam_dev_one<true>(pj, eff_grad<ACC>(ACCUM ? ac[k][j] : 0.f, HAS_G ? g[k][j] : 0.f, inv_k), mj, vj, sc);
+                p[k][j] = pj; m[k][j] = mj; v[k][j] = vj;
                 if constexpr (EMA) ea[k][j] = adam_ema_one(ea[k][j], pj, d32, omd32);
             }
             *reinterpret_cast<f32x4*>(t.p + i) = p[k]; *reinterpret_cast<f32x4*>(t.m + i) = m[k]; *reinterpret_cast<f32x4*>(t.v + i) = v[k];
             if constexpr (EMA) *reinterpret_cast<f32x4*>(te + i) = ea[k];
+            if constexpr (ACCUM) *reinterpret_cast<f32x4*>(ta + i) = f32x4{0.f, 0.f, 0.f, 0.f};
         }
     } else {
 #pragma unroll 1
@@ -330,19 +422,29 @@ template <bool EMA> __global__ __launch_bounds__(256) void adamw_dev_kernel(Adam
             if (i >= t.n) break;
             if (vec && i + 4 <= t.n) {
                 f32x4 pp = *reinterpret_cast<f32x4*>(t.p + i), mm = *reinterpret_cast<f32x4*>(t.m + i), vv = *reinterpret_cast<f32x4*>(t.v + i);
-                const f32x4 gg = *reinterpret_cast<const f32x4*>(t.g + i);
-                f32x4 ee{};
+                f32x4 gg{}, ee{}, aa{};
+                if constexpr (HAS_G) gg = *reinterpret_cast<const f32x4*>(t.g + i);
                 if constexpr (EMA) ee = *reinterpret_cast<const f32x4*>(te + i);
+                if constexpr (ACCUM) aa = *reinterpret_cast<const f32x4*>(ta + i);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float pj = pp[j], mj = mm[j], vj = vv[j]; adam_dev_one<true>(pj, gg[j], mj, vj, sc); pp[j] = pj; mm[j] = mj; vv[j] = vj;
+                    float pj = pp[j], mj = mm[j], vj = vv[j];
+                    adam_dev_one<true>(pj, eff_grad<ACC>(aa[j], gg[j], inv_k), mj, vj, sc);
+                    pp[j] = pj; mm[j] = mj; vv[j] = vj;
                     if constexpr (EMA) ee[j] = adam_ema_one(ee[j], pj, d32, omd32);
                 }
                 *reinterpret_cast<f32x4*>(t.p + i) = pp; *reinterpret_cast<f32x4*>(t.m + i) = mm; *reinterpret_cast<f32x4*>(t.v + i) = vv;
                 if constexpr (EMA) *reinterpret_cast<f32x4*>(te + i) = ee;
+                if constexpr (ACCUM) *reinterpret_cast<f32x4*>(ta + i) = f32x4{0.f, 0.f, 0.f, 0.f};
             } else {
                 for (long long e = i; e < i + 4 && e < t.n; ++e) {
-                    adam_dev_one<false>(t.p[e], t.g[e], t.m[e], t.v[e], sc);
+                    if constexpr (ACCUM) {
+                        const float ae = ta[e];
+                        ta[e] = 0.f;
+                        adam_dev_one<false>(t.p[e], eff_grad<ACC>(ae, HAS_G ? t.g[e] : 0.f, inv_k), t.m[e], t.v[e], sc);
+                    } else {
+                        adam_dev_one<false>(t.p[e], t.g[e], t.m[e], t.v[e], sc);
+                    }
                     if constexpr (EMA) te[e] = adam_ema_one(te[e], t.p[e], d32, omd32);
                 }
             }
@@ -363,17 +465,19 @@ __global__ __launch_bounds__(64) void ema_set_kernel(double* ema_hyper, double d
 
 // hyb_adamw_step_dev (ema == NULL) and hyb_adamw_step_dev_ema: the tensor table in launches of at most the variant's capacity, the last
 // of which advances the counter
-template <bool EMA> int adamw_dev_launch(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                                         float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
-                                         long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream) {
-    constexpr int MAX = EMA ? ADAM_EMA_MAX : ADAM_MAX;
+template <bool EMA, int ACC = GRAD_PLAIN>
+int adamw_dev_launch(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                     float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
+                     long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream, float* const* acc = nullptr, long long k = 1) {
+    constexpr int MAX = ACC != GRAD_PLAIN ? (EMA ? ADAM_EMA_ACC_MAX : ADAM_ACC_MAX) : (EMA ? ADAM_EMA_MAX : ADAM_MAX);
     for (int first = 0; first < count; first += MAX) {
-        AdamDevKernelArgs<EMA> a{};
+        AdamDevKernelArgs<EMA, ACC> a{};
         const int n = count - first < MAX ? count - first : MAX;
         int chunks = 0;
         for (int i = 0; i < n; ++i) {
-            a.t[i] = AdamTensor{params[first + i], grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
+            a.t[i] = AdamTensor{params[first + i], ACC == GRAD_ACC ? nullptr : grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
             if constexpr (EMA) a.e[i] = ema[first + i];
+            if constexpr (ACC != GRAD_PLAIN) a.acc[i] = acc[first + i];
             a.chunk_begin[i] = chunks;
             chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
         }
@@ -381,15 +485,132 @@ template <bool EMA> int adamw_dev_launch(int count, float* const* params, const 
         a.count = n;
         a.hyper = hyper; a.step_inc = step_inc; a.step = step; a.clip = clip;
         if constexpr (EMA) a.ema_hyper = ema_hyper;
+        if constexpr (ACC != GRAD_PLAIN) { a.k = k; a.inv_k = (float)(1.0 / (double)k); }
         a.advance = (advance_ticket && first + MAX >= count) ? step_inc : nullptr;            // the last launch of the call advances the counter
         a.ticket = advance_ticket;
-        hipLaunchKernelGGL(adamw_dev_kernel<EMA>, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((adamw_dev_kernel<EMA, ACC>), dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
         HYB_LAUNCH_CHECK();
     }
     return 0;
 }
 
+// ---- gradient accumulation ----------------------------------------------------------------------------------------------------------------
+// acc += g over the whole tensor table in one launch: what ends micro-batches 1 .. k - 1 of an accumulated step.  The chunk -> tensor -> thread
+// mapping of adamw_dev_kernel; a full aligned chunk issues its eight 16-byte loads before the first add.
+struct AccumArgs {
+    float* acc[ADAM_MAX];
+    const float* g[ADAM_MAX];
+    long long n[ADAM_MAX];
+    int chunk_begin[ADAM_MAX + 1];
+    int count;
+};
+static_assert(sizeof(AccumArgs) <= 4096, "the tensor table travels in the kernel arguments");
+
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(AccumArgs a) {
+    int ti = 0;
+    for (int i = 1; i < a.count; ++i)
+        if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
+    float* __restrict__ acc = a.acc[ti];
+    const float* __restrict__ g = a.g[ti];
+    const long long n = a.n[ti];
+    const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
+    const bool vec = ((((uintptr_t)acc | (uintptr_t)g) & 15) == 0);
+    constexpr int NK = ADAM_CHUNK / (256 * 4);
+    if (vec && base + ADAM_CHUNK <= n) {
+        f32x4 x[NK], y[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            x[k] = *reinterpret_cast<const f32x4*>(acc + i); y[k] = *reinterpret_cast<const f32x4*>(g + i);
+        }
+#pragma unroll
+        for (int k = 0; k < NK; ++k) *reinterpret_cast<f32x4*>(acc + base + ((long long)k * 256 + threadIdx.x) * 4) = x[k] + y[k];
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            if (i >= n) break;
+            if (vec && i + 4 <= n) {
+                *reinterpret_cast<f32x4*>(acc + i) = *reinterpret_cast<const f32x4*>(acc + i) + *reinterpret_cast<const f32x4*>(g + i);
+            } else {
+                for (long long e = i; e < i + 4 && e < n; ++e) acc[e] = acc[e] + g[e];
+            }
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int hyb_grad_accumulate(int count, float* const* acc, const float* const* grads, const long long* numel, void* stream) {
+    HYB_CHECK_ARG(count > 0 && acc && grads && numel);
+    for (int i = 0; i < count; ++i) HYB_CHECK_ARG(acc[i] && grads[i] && acc[i] != grads[i] && numel[i] > 0);
+    for (int first = 0; first < count; first += ADAM_MAX) {
+        AccumArgs a{};
+        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
+        long long chunks = 0;
+        for (int i = 0; i < n; ++i) {
+            a.acc[i] = acc[first + i]; a.g[i] = grads[first + i]; a.n[i] = numel[first + i];
+            a.chunk_begin[i] = (int)chunks;
+            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
+            HYB_CHECK_ARG(chunks < (1ll << 31));
+        }
+        a.chunk_begin[n] = (int)chunks;
+        a.count = n;
+        hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, a);
+        HYB_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int hyb_grad_norm_acc(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k, float* partials,
+                                 const double* hyper, float* norm_out, void* stream) {
+    HYB_CHECK_ARG(count > 0 && acc && numel && k >= 1 && partials && hyper && norm_out);
+    long long total = 0;
+    for (int i = 0; i < count; ++i) {
+        HYB_CHECK_ARG(acc[i] && (!grads || grads[i]) && numel[i] > 0);
+        total += hyb_cdiv(numel[i], ADAM_CHUNK);
+    }
+    HYB_CHECK_ARG(total < (1ll << 31));
+    int offset = 0;
+    for (int first = 0; first < count; first += ADAM_MAX) {
+        GradNormAccArgs a{};
+        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
+        int chunks = 0;
+        for (int i = 0; i < n; ++i) {
+            a.acc[i] = acc[first + i]; a.g[i] = grads ? grads[first + i] : nullptr; a.n[i] = numel[first + i];
+            a.chunk_begin[i] = chunks;
+            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
+        }
+        a.chunk_begin[n] = chunks;
+        a.count = n;
+        a.chunk_offset = offset;
+        a.partials = partials;
+        a.inv_k = (float)(1.0 / (double)k);
+        if (grads) hipLaunchKernelGGL(grad_norm_acc_kernel<GRAD_ACC_G>, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(grad_norm_acc_kernel<GRAD_ACC>, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        HYB_LAUNCH_CHECK();
+        offset += chunks;
+    }
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partials, (int)total, hyper, norm_out);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int hyb_adamw_step_dev_acc(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                      float* const* acc, float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper,
+                                      long long k, long long step, long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream) {
+    HYB_CHECK_ARG(count > 0 && params && exp_avg && exp_avg_sq && acc && numel && hyper && k >= 1 && step >= 1 && (!advance_ticket || step_inc) &&
+                  (ema != nullptr) == (ema_hyper != nullptr));
+    for (int i = 0; i < count; ++i)
+        HYB_CHECK_ARG(params[i] && (!grads || grads[i]) && exp_avg[i] && exp_avg_sq[i] && acc[i] && acc[i] != params[i] &&
+                      (!ema || (ema[i] && ema[i] != params[i])) && numel[i] > 0);
+    if (ema) {
+        if (grads) return adamw_dev_launch<true, GRAD_ACC_G>(count, params, grads, exp_avg, exp_avg_sq, ema, numel, hyper, ema_hyper, step, step_inc, advance_ticket, clip, stream, acc, k);
+        return adamw_dev_launch<true, GRAD_ACC>(count, params, nullptr, exp_avg, exp_avg_sq, ema, numel, hyper, ema_hyper, step, step_inc, advance_ticket, clip, stream, acc, k);
+    }
+    if (grads) return adamw_dev_launch<false, GRAD_ACC_G>(count, params, grads, exp_avg, exp_avg_sq, nullptr, numel, hyper, nullptr, step, step_inc, advance_ticket, clip, stream, acc, k);
+    return adamw_dev_launch<false, GRAD_ACC>(count, params, nullptr, exp_avg, exp_avg_sq, nullptr, numel, hyper, nullptr, step, step_inc, advance_ticket, clip, stream, acc, k);
+}
 
 extern "C" int hyb_adamw_hyper_set(double* hyper, double lr, double beta1, double beta2, double eps, double weight_decay, double max_grad_norm,
                                    void* stream) {

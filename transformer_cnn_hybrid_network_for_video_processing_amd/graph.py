@@ -38,22 +38,52 @@ while the CNN backbone's backward graph executes:
 With one rank there is nothing to exchange and no bucket: the gradient tensors produced under capture live at fixed addresses in
 the graphs' private pool, so they are bound to ``p.grad`` and AdamW reads them in place (saves the two pack copies, ~25 us); and the
 whole step is one graph (A, B and C captured back to back: every graph launch leaves the GPU idle for ~8 us, scripts/step_trace.py).
+
+Gradient accumulation (accumulation_steps = k > 1): one optimizer step over k calls of step(), each a micro-batch brought by load().
+  * ONE device counter, counting MICRO-steps: the dropout-seed kernels use it as ever, so every micro-batch draws its own masks; the AdamW
+    launch derives its step number as counter / k (hyb_adamw_step_dev_acc) and, on update steps, advances the counter through its ticket;
+    the other micro-steps end in a `counter += 1`.
+  * One rank: a second graph holds A + B + one hyb_grad_accumulate launch (acc += g) + the counter increment; the single graph ends in
+    the AdamW launch that reads its own gradients and the accumulators together, steps on (acc + g) / k and leaves acc zeroed.  step()
+    replays the former k - 1 times, then the latter.  +4 bytes per parameter of memory.
+  * World > 1: the buckets ARE the accumulators (no extra memory).  A and B bind their gradients as on one rank; after each, one eager
+    hyb_grad_accumulate adds them into the bucket views.  The all-reduces are issued on the k-th micro-step only -- the equivalent of
+    DistributedDataParallel.no_sync() -- and graph C steps on bucket / k with no gradient tensors, which leaves the buckets zeroed.
+    Limitation: fwd_bwd() is refused with k > 1 and world > 1 (graphs A and B no longer fill the buckets by themselves).
 """
+import ctypes
 import os
 
 import torch
 import torch.distributed as dist
 
 from . import ops
+from ._lib import lib, ptr_array
 
 
 class GraphedTrainStep:
-    def __init__(self, model, criterion, optimizer, x, y, mask=None, process_group=None, warmup=3, dynamic_hyper=False):
+    def __init__(self, model, criterion, optimizer, x, y, mask=None, process_group=None, warmup=3, dynamic_hyper=False, accumulation_steps=1):
         if not (hasattr(model, "forward_backbone") and hasattr(model, "forward_temporal")):
             raise TypeError("GraphedTrainStep drives a TransformerCNNHybrid")
         if not hasattr(optimizer, "set_step_counter"):
             raise TypeError("GraphedTrainStep needs HybridAdamW (its step number lives on the device)")
         self.model, self.criterion, self.optimizer = model, criterion, optimizer
+        # micro-batches per optimizer step: captured by value (the number of replays per update, k inside the AdamW launch)
+        k = accumulation_steps
+        if not isinstance(k, int) or isinstance(k, bool) or k < 1:
+            raise ValueError("accumulation_steps must be an int >= 1")
+        if k != 1 or getattr(optimizer, "accumulation_steps", 1) != 1:
+            if not hasattr(optimizer, "set_accumulation"):
+                raise TypeError("GraphedTrainStep: accumulation_steps > 1 needs HybridAdamW (the accumulated step is its AdamW launch)")
+            if optimizer.accumulation_steps not in (1, k):
+                raise ValueError(f"GraphedTrainStep: accumulation_steps={k}, but the optimizer was given {optimizer.accumulation_steps}")
+            if max(1, warmup) % k:
+                raise ValueError(f"GraphedTrainStep: warmup counts micro-steps and must be a multiple of accumulation_steps ({warmup} is no "
+                                 f"multiple of {k}): the captured step starts at an optimizer-step boundary")
+            optimizer.set_accumulation(k)
+        self._k = k
+        self._micro = 0              # micro-steps taken since the last optimizer step (host side; the device counter holds the total)
+        self.is_update_step = False  # True after a step() that ran AdamW (with accumulation_steps == 1: after every step())
         if dynamic_hyper:
             optimizer.set_dynamic_hyper(True)
         # what the captured AdamW launch is bound to: the device path reads its hyper-parameters when it runs; the plain launch carries
@@ -97,9 +127,15 @@ class GraphedTrainStep:
         # one parameter group: the AdamW launch itself advances the counter (no separate `counter += 1` launch per step)
         self._advancing = sum(1 for g in optimizer.param_groups if any(p.requires_grad for p in g["params"])) == 1
         optimizer.set_step_counter(self.counter, advance=self._advancing)
-        if self.world > 1:
+        self._acc_tabs = {}                                    # world > 1, k > 1: the pointer tables of the two eager accumulate launches
+        self._captured = False
+        if self.world > 1 and k == 1:
             for p, v in zip(self.t_params + self.b_params, self.t_views + self.b_views):
                 p.grad = v                                     # AdamW reads the (all-reduced) buckets in place
+        elif self.world > 1:                                   # the buckets are the accumulators; AdamW gets no gradient tensors
+            optimizer._bind_accumulators(self.t_params + self.b_params, self.t_views + self.b_views, no_grad=True)
+        elif k > 1:
+            optimizer.accum_init()                             # eagerly, zeroed: a captured launch must not be the one that creates them
         # warm-up on a side stream (lazy initialisation, allocator steady state), then capture
         side = torch.cuda.Stream(device=dev)
         cap = torch.cuda.Stream(device=dev)                    # every capture below runs on this stream
@@ -111,9 +147,17 @@ class GraphedTrainStep:
             cap.wait_stream(torch.cuda.current_stream(dev))
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self._piece_a(); self._reduce_wait(self._reduce(self.t_bucket)); self._piece_b(); self._reduce_wait(self._reduce(self.b_bucket))
-                self._piece_c()
+            for i in range(max(1, warmup)):
+                update = (i + 1) % k == 0
+                self._piece_a(); self._accumulate_bucket("t")
+                if update:
+                    self._reduce_wait(self._reduce(self.t_bucket))
+                self._piece_b(); self._accumulate_bucket("b")
+                if update:
+                    self._reduce_wait(self._reduce(self.b_bucket))
+                    self._piece_c()
+                else:
+                    self._piece_acc()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self._warm_steps = max(1, warmup)
@@ -122,7 +166,8 @@ class GraphedTrainStep:
             self._piece_a()
         with torch.cuda.graph(self.gb, pool=self.ga.pool(), stream=cap):
             self._piece_b()
-        self.gs = None
+        self.gs = self.gm = None
+        self.is_update_step = True
         params = self.t_params + self.b_params
         if self.world == 1 and os.environ.get("HYB_GRAPH_SINGLE", "1") != "0":      # (=0: A/B switch, the three-graph form)
             # one rank: nothing happens between the pieces, so the whole step is ALSO captured as one graph (every graph launch leaves the
@@ -134,11 +179,23 @@ class GraphedTrainStep:
             # and a later fwd_bwd() would overwrite them -- ADVICE r3)
             with torch.cuda.graph(self.gs, stream=cap):
                 self._piece_a(); self._piece_b(); self._piece_c()
-            self._grads_step, self._loss_step = [p.grad for p in params], self.loss
+            self._grads_step, self._loss_step, self._logits_step = [p.grad for p in params], self.loss, self.logits
             self._bound = "step"
+            if k > 1:
+                # micro-batches 1 .. k - 1: A + B + the accumulate launch (+ counter += 1), in a pool of its own for the reason gs has one
+                self.gm = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.gm, stream=cap):
+                    self._piece_a(); self._piece_b(); self._piece_acc()
+                self._grads_micro, self._loss_micro, self._logits_micro = [p.grad for p in params], self.loss, self.logits
+                self._bound = "micro"
         else:
             with torch.cuda.graph(self.gc_, pool=self.ga.pool(), stream=cap):
                 self._piece_c()
+            if k > 1:                                          # what ends a micro-step that is no update (world > 1: the accumulation was eager)
+                self.gm = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.gm, pool=self.ga.pool(), stream=cap):
+                    self._piece_acc()
+        self._captured = True
         # the captures above did not execute: the state is still "after the warm-up steps"
 
     def _hyper_now(self):
@@ -181,9 +238,15 @@ class GraphedTrainStep:
         """optimizer.grad_norm: the device scalar holding the last step's unclipped total gradient norm (max_grad_norm set)."""
         return self.optimizer.grad_norm
 
+    def _check_accumulation(self):
+        if self.optimizer.accumulation_steps != self._k:
+            raise RuntimeError(f"GraphedTrainStep: the optimizer's accumulation_steps changed after capture ({self._k} -> "
+                               f"{self.optimizer.accumulation_steps}); the captured launches carry k and step() the number of replays per "
+                               "update -- construct a new GraphedTrainStep")
+
     def _bind(self, which):
         if self.gs is not None and self._bound != which:
-            for p, g in zip(self.t_params + self.b_params, self._grads_step if which == "step" else self._grads_fb):
+            for p, g in zip(self.t_params + self.b_params, {"step": self._grads_step, "fb": self._grads_fb}.get(which) or self._grads_micro):
                 p.grad = g
             self._bound = which
 
@@ -219,7 +282,7 @@ class GraphedTrainStep:
         self._h = self._gh = None
 
     def _deliver(self, params, views, grads, bind):
-        if views is not None:
+        if views is not None and self._k == 1:
             torch._foreach_copy_(views, list(grads))
         elif bind:                                             # one rank: the captured gradient tensors themselves (static addresses)
             for p, g in zip(params, grads):
@@ -232,6 +295,27 @@ class GraphedTrainStep:
         self.optimizer.step()
         if not self._advancing:
             self.counter.add_(1)
+
+    def _piece_acc(self):
+        """What ends a micro-batch that is no update: acc += g (one rank; with world > 1 _accumulate_bucket has done it) and counter += 1."""
+        if self.world == 1:
+            self.optimizer.accumulate()
+        self.counter.add_(1)
+
+    def _accumulate_bucket(self, which):
+        """World > 1 with accumulation: one eager hyb_grad_accumulate, bucket views += the gradients graph A (or B) has just written."""
+        if self.world == 1 or self._k == 1:
+            return
+        tab = self._acc_tabs.get(which)
+        if tab is None:
+            params, views = (self.t_params, self.t_views) if which == "t" else (self.b_params, self.b_views)
+            if not params:
+                return
+            tab = (len(params), ptr_array([v.data_ptr() for v in views]), ptr_array([p.grad.data_ptr() for p in params]),
+                   (ctypes.c_longlong * len(params))(*[p.numel() for p in params]), [p.grad for p in params])
+            if self._captured:                                 # the captured gradient tensors stay where they are (and tab[4] keeps them alive)
+                self._acc_tabs[which] = tab
+        lib.call("hyb_grad_accumulate", tab[0], tab[1], tab[2], tab[3], ops._stream())
 
     def _reduce(self, bucket):
         if self.world == 1:
@@ -262,6 +346,8 @@ class GraphedTrainStep:
     def step(self):
         """One training step; returns the (device) loss tensor of this step -- reading it synchronises."""
         self._check_hyper()
+        if self._k > 1:
+            return self._micro_step()
         if self.gs is not None:
             self._bind("step")
             self.gs.replay()
@@ -276,8 +362,42 @@ class GraphedTrainStep:
         self.gc_.replay()
         return self.loss
 
+    def _micro_step(self):
+        """step() with accumulation_steps = k > 1: micro-batches 1 .. k - 1 accumulate, the k-th runs AdamW; returns this micro-batch's loss."""
+        self._check_accumulation()
+        update = self._micro == self._k - 1
+        if self.gs is not None:
+            self._bind("step" if update else "micro")
+            (self.gs if update else self.gm).replay()
+            self.loss, self.logits = (self._loss_step, self._logits_step) if update else (self._loss_micro, self._logits_micro)
+        else:
+            self.ga.replay()
+            self._accumulate_bucket("t")
+            w1 = self._reduce(self.t_bucket) if update else None     # the k-th micro-step only; rides under graph B
+            self.gb.replay()
+            self._accumulate_bucket("b")
+            if update:
+                w2 = self._reduce(self.b_bucket)
+                self._reduce_wait(w1)
+                self._reduce_wait(w2)
+                self.gc_.replay()
+            else:
+                self.gm.replay()
+        self._micro = 0 if update else self._micro + 1
+        self.is_update_step = update
+        return self.loss
+
     def fwd_bwd(self):
-        """Forward + loss + backward (+ all-reduce) only: no optimizer, the step counter does not advance."""
+        """Forward + loss + backward (+ all-reduce) only: no optimizer, the step counter does not advance.  With accumulation_steps > 1:
+        refused between the micro-batches of one optimizer step, and always with world > 1 (see the module docstring)."""
+        if self._k > 1:
+            self._check_accumulation()
+            if self.world > 1:
+                raise RuntimeError("GraphedTrainStep.fwd_bwd() is not available with accumulation_steps > 1 and data parallelism: graphs A and "
+                                   "B no longer fill the buckets by themselves")
+            if self._micro:
+                raise RuntimeError(f"GraphedTrainStep.fwd_bwd() in the middle of an accumulated step ({self._micro} of {self._k} micro-batches "
+                                   "taken): finish the optimizer step first")
         self._bind("fb")
         self.ga.replay()
         w1 = self._reduce(self.t_bucket)
@@ -296,11 +416,19 @@ class GraphedTrainStep:
         return self.loss
 
     def steps_done(self):
-        """Steps taken through this object, warm-up included (reads the device counter: synchronises)."""
+        """Optimizer steps taken through this object, warm-up included (reads the device counter: synchronises)."""
+        return int(self.counter.item()) // self._k
+
+    def micro_steps_done(self):
+        """Micro-steps (forward + backward passes) taken through this object, warm-up included; = steps_done() with accumulation_steps 1."""
         return int(self.counter.item())
 
     def sync_optimizer_state(self):
-        """Fold the device step counter into the optimizer's Python-side state (before state_dict())."""
+        """Fold the device step counter into the optimizer's Python-side state (before state_dict()).  Refused between the micro-batches
+        of one optimizer step: the accumulators then hold a partial sum that no state dict carries."""
+        if self._micro:
+            raise RuntimeError(f"GraphedTrainStep.sync_optimizer_state() in the middle of an accumulated step ({self._micro} of {self._k} "
+                               "micro-batches taken): finish the optimizer step first")
         n = self.steps_done()
         for st in self.optimizer.state.values():
             if "step" in st:

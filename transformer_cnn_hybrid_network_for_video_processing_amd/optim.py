@@ -15,7 +15,12 @@ Two things a training run needs on top of that, both built on hyper-parameters t
     pass over the weights, no extra launch.  `ema_warmup=True` uses `min(d, (1 + n) / (10 + n))` after n earlier steps.  Both live in a device
     block (`double [groups, 2]`), so a captured step follows a decay changed between replays.  `ema_model(model)` gives a twin module whose
     parameters ARE the averages, for `predict` / `GraphedPredict`.  The average follows only parameters that are stepped: a parameter
-    without a gradient keeps its old average."""
+    without a gradient keeps its old average.
+  * `accumulation_steps=k`: one optimizer step over k micro-batches.  After each of the first k - 1 backward passes `accumulate()` adds
+    every `.grad` into an fp32 accumulator (`hyb_grad_accumulate`, one launch per group); `step()` after the k-th steps on
+    `(acc + grad) * (1 / k)` and leaves the accumulators zeroed, all inside the AdamW launch (`hyb_adamw_step_dev_acc`; the norm of a
+    clipped step is taken over the same mean, `hyb_grad_norm_acc`): no separate sum, scale or memset pass.  The accumulators are zero at
+    every optimizer-step boundary, so they are neither state nor part of the state dict."""
 import copy
 import ctypes
 
@@ -26,13 +31,16 @@ from .ops import _stream
 
 
 class HybridAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_decay=None, ema_warmup=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_decay=None, ema_warmup=False,
+                 accumulation_steps=1):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be None (no clipping) or > 0")
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("ema_decay must be None (no average) or in [0, 1)")
+        # (checked before the base class touches anything; neither a param-group key nor state: the accumulators are zero between steps)
+        self._accum_k = self._check_accumulation(accumulation_steps)
         # max_grad_norm sits in the groups only so that it travels in the state dict: clipping is global, every group carries the same value;
         # ema_decay / ema_warmup are per group (None: that group takes the launch without the average)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
@@ -48,6 +56,25 @@ class HybridAdamW(torch.optim.Optimizer):
         self._partials = None        # (numels, device fp32 [chunks], host numel array): hyb_grad_norm's per-chunk sums of squares
         self._ema_hyper = None       # device double [groups, 2]: ema_decay, ema_warmup (0 / 1) per group; created with _hyper
         self._ema_sent = {}          # per group: the (decay, warmup) last uploaded
+        self._acc = {}               # parameter -> its fp32 gradient accumulator (16-byte aligned; zero at every optimizer-step boundary)
+        self._acc_flat = []          # the flat buffers the accumulators created here are views of
+        self._acc_tables = {}        # per group: cached pointer tables of accumulate()
+        self._acc_only = False       # _bind_accumulators(no_grad=True): the accumulators hold the whole sum, step() passes no gradients
+
+    @staticmethod
+    def _check_accumulation(k):
+        if not isinstance(k, int) or isinstance(k, bool) or k < 1:
+            raise ValueError("accumulation_steps must be an int >= 1")
+        return k
+
+    def set_accumulation(self, k):
+        """Micro-batches per optimizer step from now on (1: plain steps).  Change it only at an optimizer-step boundary: step() divides
+        whatever the accumulators hold, plus the current gradients, by the k in force when it runs."""
+        self._accum_k = self._check_accumulation(k)
+
+    @property
+    def accumulation_steps(self):
+        return self._accum_k
 
     def set_step_counter(self, counter, advance=False):
         """With a device counter the step number used by the kernel is state['step'] + counter, read on the device: one captured
@@ -66,7 +93,7 @@ class HybridAdamW(torch.optim.Optimizer):
 
     def uses_device_hyper(self):
         """(The average always takes the device path: its decay is read on the device, so a change between replays is picked up.)"""
-        return self._dynamic or any(g.get("max_grad_norm") is not None or g.get("ema_decay") is not None for g in self.param_groups)
+        return self._dynamic or self._accum_k > 1 or any(g.get("max_grad_norm") is not None or g.get("ema_decay") is not None for g in self.param_groups)
 
     @staticmethod
     def _group_ema(group):
@@ -201,6 +228,80 @@ class HybridAdamW(torch.optim.Optimizer):
         super().add_param_group(param_group)
         if hasattr(self, "_tables"):
             self._tables.clear()
+            self._acc_tables.clear()
+
+    # ---- gradient accumulation --------------------------------------------------------------------------------------------------------
+    def _new_accumulators(self, params):
+        """Zeroed accumulators for `params`, views of ONE flat buffer, each starting on a multiple of 4 elements (16 bytes)."""
+        if not params:
+            return
+        if params[0].is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("HybridAdamW: a parameter's gradient accumulator does not exist yet and cannot be created under stream capture "
+                               "(it must be zero before the first micro-batch, and a buffer born in a capture is zeroed by that graph only) -- "
+                               "call accum_init() before capturing")
+        for p in params:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
+        offs, total = [], 0
+        for p in params:
+            offs.append(total)
+            total += (p.numel() + 3) // 4 * 4
+        flat = torch.zeros(max(total, 4), dtype=torch.float32, device=params[0].device)
+        self._acc_flat.append(flat)
+        for p, o in zip(params, offs):
+            self._acc[p] = flat[o:o + p.numel()].view(p.shape)
+
+    def _accumulators(self, params):
+        self._new_accumulators([p for p in params if p not in self._acc])
+        return [self._acc[p] for p in params]
+
+    @torch.no_grad()
+    def accum_init(self):
+        """Create (zeroed) the accumulator of every parameter that has none yet.  accumulate() and step() do the same on first eager use;
+        call this before capturing either, or to make the one allocation up front."""
+        for group in self.param_groups:
+            self._new_accumulators([p for p in group["params"] if p not in self._acc])
+
+    def _bind_accumulators(self, params, tensors, no_grad=False):
+        """(GraphedTrainStep.)  Use `tensors` -- fp32, contiguous, zero now, e.g. views of the data-parallel gradient buckets -- as the
+        accumulators of `params`.  no_grad=True: whoever binds them adds EVERY micro-batch's gradient into them itself (and all-reduces
+        them), so step() passes no gradient tensors and steps on acc * (1 / k); p.grad only says which parameters are stepped."""
+        for p, t in zip(params, tensors):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != p.numel() or t.device != p.device:
+                raise ValueError("HybridAdamW: an accumulator must be a contiguous fp32 tensor of its parameter's size, on its device")
+            self._acc[p] = t
+        self._acc_only = bool(no_grad)
+        self._tables.clear()
+        self._acc_tables.clear()
+
+    @torch.no_grad()
+    def accumulate(self):
+        """End one of the micro-batches 1 .. k - 1: acc += grad for every parameter with a gradient, one hyb_grad_accumulate launch per
+        group.  The gradients are only read (zero_grad() as usual before the next backward)."""
+        if self._accum_k < 2:
+            raise RuntimeError("HybridAdamW.accumulate() needs accumulation_steps > 1 (with 1, step() does not read the accumulators)")
+        if self._acc_only:
+            raise RuntimeError("HybridAdamW.accumulate(): the accumulators are bound to external buffers whose owner adds the gradients itself")
+        for gi, group in enumerate(self.param_groups):
+            ps = [p for p in group["params"] if p.grad is not None]
+            if not ps:
+                continue
+            accs = self._accumulators(ps)
+            addrs = [(p.data_ptr(), a.data_ptr()) for p, a in zip(ps, accs)]
+            tab = self._acc_tables.get(gi)
+            if tab is None or tab[0] != addrs:
+                tab = self._acc_tables[gi] = (addrs, ptr_array([a[1] for a in addrs]), (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps]))
+            lib.call("hyb_grad_accumulate", len(ps), tab[1], self._float_grads(ps), tab[2], _stream())
+
+    @staticmethod
+    def _float_grads(ps):
+        grads = []
+        for p in ps:
+            g = p.grad
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                g = g.float().contiguous()
+            grads.append(g)
+        return grads
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -212,12 +313,14 @@ class HybridAdamW(torch.optim.Optimizer):
         if self._advance and len(live) != 1:
             raise RuntimeError("HybridAdamW: an advancing step counter needs exactly one parameter group with gradients")
         dev_path = self.uses_device_hyper()
+        accum = self._accum_k > 1
         work = []                                   # per live group: (group index, tensor count, tables, gradients, step number)
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
             ema = self._group_ema(group)
+            accs = self._accumulators(ps) if accum else None     # (first: a refusal under capture leaves the step counts untouched)
             for p in ps:
                 if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                     raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
@@ -241,17 +344,15 @@ class HybridAdamW(torch.optim.Optimizer):
             else:
                 addrs = [(p.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(), self.state[p]["ema"].data_ptr())
                          for p in ps]
+            if accum:                               # ... and, in an accumulated step, the accumulators (the key's last entry)
+                addrs = [a + (acc.data_ptr(),) for a, acc in zip(addrs, accs)]
             tab = self._tables.get(gi)
             if tab is None or tab[1] != addrs:
                 tab = (None, addrs, ptr_array([a[0] for a in addrs]), ptr_array([a[1] for a in addrs]), ptr_array([a[2] for a in addrs]),
-                       (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps]), None if ema is None else ptr_array([a[3] for a in addrs]))
+                       (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps]), None if ema is None else ptr_array([a[3] for a in addrs]),
+                       ptr_array([a[-1] for a in addrs]) if accum else None)
                 self._tables[gi] = tab
-            grads = []
-            for p in ps:
-                g = p.grad
-                if g.dtype != torch.float32 or not g.is_contiguous():
-                    g = g.float().contiguous()
-                grads.append(g)
+            grads = None if accum and self._acc_only else self._float_grads(ps)
             work.append((gi, len(ps), tab, grads, steps.pop()))
         counter = self._step_counter
         ticket = self._ticket if self._advance else None
@@ -275,8 +376,8 @@ class HybridAdamW(torch.optim.Optimizer):
             return loss
         clip_coef = None
         if clip is not None:                        # ONE norm over the gradients of all groups, as clip_grad_norm_(model.parameters())
-            all_grads = [g for w in work for g in w[3]]
-            numels = tuple(g.numel() for g in all_grads)
+            all_grads = None if accum and self._acc_only else [g for w in work for g in w[3]]
+            numels = tuple(n for w in work for n in w[2][5])
             if self._partials is None or self._partials[0] != numels:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("HybridAdamW: the gradient-norm workspace cannot be created under stream capture -- take one eager "
@@ -284,10 +385,18 @@ class HybridAdamW(torch.optim.Optimizer):
                 arr = (ctypes.c_longlong * len(numels))(*numels)
                 chunks = lib.query("hyb_grad_norm_workspace", len(numels), arr)
                 self._partials = (numels, torch.zeros(chunks, dtype=torch.float32, device=hyper.device), arr)
-            lib.call("hyb_grad_norm", len(all_grads), all_grads, self._partials[2], self._partials[1], hyper[work[0][0]], self._norm_out, _stream())
+            if accum:                               # ... here over the mean of the k micro-batches' gradients
+                all_accs = ptr_array([a[-1] for w in work for a in w[2][1]])
+                lib.call("hyb_grad_norm_acc", len(numels), all_accs, all_grads, self._partials[2], self._accum_k, self._partials[1],
+                         hyper[work[0][0]], self._norm_out, _stream())
+            else:
+                lib.call("hyb_grad_norm", len(all_grads), all_grads, self._partials[2], self._partials[1], hyper[work[0][0]], self._norm_out, _stream())
             clip_coef = self._norm_out
         for gi, n, tab, grads, step in work:
-            if tab[6] is None:
+            if accum:                               # the same launch on (acc + g) / k, which leaves the accumulators zeroed
+                lib.call("hyb_adamw_step_dev_acc", n, tab[2], grads, tab[3], tab[4], tab[7], tab[6], tab[5], hyper[gi],
+                         None if tab[6] is None else self._ema_hyper[gi], self._accum_k, step, counter, ticket, clip_coef, _stream())
+            elif tab[6] is None:
                 lib.call("hyb_adamw_step_dev", n, tab[2], grads, tab[3], tab[4], tab[5], hyper[gi], step, counter, ticket, clip_coef, _stream())
             else:                                   # the same launch, which also moves the averages
                 lib.call("hyb_adamw_step_dev_ema", n, tab[2], grads, tab[3], tab[4], tab[6], tab[5], hyper[gi], self._ema_hyper[gi], step, counter,
