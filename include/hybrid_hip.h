@@ -344,6 +344,33 @@ int hyb_cross_entropy_mix_bwd(const float* logits, const long long* target, cons
                               const float* weight /* [C] or NULL */, long long ignore_index, int has_ignore, float label_smoothing,
                               const float* dloss /* [1] */, float* dlogits, int B, int C, void* stream);
 
+/* hyb_eval_metrics: the update of an accumulating classification meter, ONE launch of one 256-thread workgroup behind the logits (new
+ *   symbol, hyb_abi_version() stays 9).  It ADDS into sums, counts and confusion and overwrites none of them: repeated launches, and
+ *   replays of a graph that holds the launch, accumulate; the caller zeroes the three before the first.  Launches on one stream are ordered
+ *   and one thread makes the final add, so there is no floating-point atomic and the sums are reproducible bit for bit.  Never synchronises.
+ *   Each of the B videos has V = views rows of logits, adjacent (row b * V + v).  Its scores s [C] are
+ *     V == 1: the logits;   V > 1: pbar_c = (1 / V) sum_v softmax(z_v)_c, formed in fp32 and written to scores[b].
+ *   Loss, with the options of hyb_cross_entropy_opts_* (keep, w, e as defined there):
+ *     V == 1: term_b and the den share w[y_b] are the criterion's own per-clip functions, so sums[0] / sums[1] is its arithmetic;
+ *     V > 1:  term_b = keep_b [ (1 - e) w[y_b] (-log pbar_y) + (e / C) sum_c w[c] (-log pbar_c) ], the same den share.
+ *     Terms are fp32; numerator and den are summed in double over a fixed 256-leaf tree and added once to sums[0] and sums[1].
+ *   Prediction and rank (torch leaves ties open; these are this library's rules):
+ *     pred = the LOWEST index among the maxima of s;   rank = #{c : s_c > s_y} + #{c < y : s_c == s_y};
+ *     top-1 correct iff rank == 0 (iff pred == y), top-k correct iff rank < topk.
+ *   counts: [0] videos seen (B), [1] kept, [2] top-1 correct, [3] top-k correct, [4] kept videos whose scores hold a NaN.
+ *   A video whose target equals ignore_index (has_ignore set) counts in [0] and nowhere else and contributes nothing (pred is still
+ *   written).  A video whose scores hold a NaN gets pred = -1, is wrong for both accuracies, has no confusion entry and, when kept,
+ *   counts in [4]; its loss term is the NaN the loss functions give.  A kept target outside [0, C) makes both sums NaN as in the
+ *   criterion, counts as kept and as wrong, and neither touches confusion nor reads weight out of bounds.
+ *   confusion [C*C] (row = target, column = prediction; 64-bit integer adds, which commute) may be NULL, as may pred [B]; scores [B, C] is
+ *   required when V > 1 and optional otherwise (V == 1: a copy of the logits).
+ *   HYB_E_ARG, before any HIP call: a NULL logits, target, sums or counts; B < 1, C < 1, views < 1; topk outside [1, C]; label_smoothing
+ *   outside [0, 1]; has_ignore not 0 / 1; views > 1 without scores. */
+int hyb_eval_metrics(const float* logits /* [B*V, C] */, const long long* target /* [B] */, const float* weight /* [C] or NULL */,
+                     long long ignore_index, int has_ignore, float label_smoothing, int topk, int views,
+                     double* sums /* [2] */, long long* counts /* [5] */, long long* confusion /* [C*C] or NULL */,
+                     long long* pred /* [B] or NULL */, float* scores /* [B, C] or NULL */, int B, int C, void* stream);
+
 /* ---- model-level entry points: whole CNN backbone / whole temporal part in ONE call each way ---------------------------
  * They chain the stage-level entry points above on the caller's stream; their purpose is host time (a training step is three
  * operator calls each way), not different arithmetic: results are bit-identical to calling the stages one by one.

@@ -819,6 +819,102 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_mix_kernel(const float*
                                  out_scale, p_drop, seed, seed_inc, o, m);
 }
 
+// ---- evaluation: an accumulating classification meter behind the logits (hyb_eval_metrics; include/hybrid_hip.h states the rules) --------
+// ONE workgroup of 256 threads, thread t owns videos t, t + 256, .. as in ce_opts_fwd_kernel: evaluation batches are tens to a few hundred
+// videos of a handful of classes, and a single workgroup makes the final add into the caller's block without any hand-off -- launches on
+// one stream are ordered, so neither a ticket nor a floating-point atomic is needed and the sums are reproducible bit for bit.
+// V == 1: the scores are the logits and the loss term is ce_clip_loss_opts / ce_clip_den themselves (a validation loss is the training
+// criterion's arithmetic).  V > 1: the scores are the mean of the views' softmax rows, formed in fp32 in the video's own `scores` row (the
+// owning thread's scratch), and the term is the criterion's formula with -log(pbar_c) where it has lse - z_c.
+struct HybEvalArgs {
+    const float* logits; const long long* target; double* sums; long long* counts; long long* confusion; long long* pred; float* scores;
+    int B, C, V, topk;
+};
+__device__ __forceinline__ float eval_clip_loss_probs(const float* p, const float* w, long long t, int C, const HybCeOpts& o) {
+    if (!ce_keep(t, o)) return 0.f;
+    if (!(t >= 0 && t < C)) return NAN;
+    float r = (1.f - o.label_smoothing) * (ce_w(w, (int)t) * -logf(p[(int)t]));
+    if (o.label_smoothing > 0.f) {
+        float sm = 0.f;
+        for (int c = 0; c < C; ++c) sm += ce_w(w, c) * -logf(p[c]);
+        r += (o.label_smoothing / (float)C) * sm;
+    }
+    return r;
+}
+__global__ __launch_bounds__(256) void eval_metrics_kernel(HybEvalArgs a, HybCeOpts o) {
+    __shared__ double partd[2][256];
+    __shared__ int parti[4][256];
+    const int C = a.C, V = a.V;
+    double num = 0.0, den = 0.0;
+    int kept = 0, top1 = 0, topk = 0, nans = 0;
+    for (int b = threadIdx.x; b < a.B; b += 256) {
+        const long long t = a.target[b];
+        const float* s = a.logits + (long long)b * V * C;                       // V == 1: the scores are the logits
+        float term;
+        if (V > 1) {
+            float* sc = a.scores + (long long)b * C;
+            for (int v = 0; v < V; ++v) {
+                const float* z = s + (long long)v * C;
+                float mx = -INFINITY;
+                for (int c = 0; c < C; ++c) mx = fmaxf(mx, z[c]);
+                float e = 0.f;
+                for (int c = 0; c < C; ++c) e += expf(z[c] - mx);
+                for (int c = 0; c < C; ++c) {
+                    const float p = expf(z[c] - mx) / e;
+                    sc[c] = v ? sc[c] + p : p;
+                }
+            }
+            for (int c = 0; c < C; ++c) sc[c] = sc[c] / (float)V;
+            s = sc;
+            term = eval_clip_loss_probs(sc, o.weight, t, C, o);
+        } else {
+            term = ce_clip_loss_opts(s, o.weight, t, C, o);
+            if (a.scores)
+                for (int c = 0; c < C; ++c) a.scores[(long long)b * C + c] = s[c];
+        }
+        bool has_nan = false;
+        int pred = 0;
+        float best = s[0];
+        for (int c = 0; c < C; ++c) {
+            const float v = s[c];
+            has_nan |= v != v;
+            if (v > best) { best = v; pred = c; }                               // strict: the lowest index among the maxima
+        }
+        if (has_nan) pred = -1;
+        if (a.pred) a.pred[b] = pred;
+        if (!ce_keep(t, o)) continue;                                           // ignored: seen, and nothing else
+        num += (double)term;
+        den += (double)ce_clip_den(o.weight, t, C, o);
+        ++kept;
+        if (has_nan) { ++nans; continue; }                                      // wrong for both accuracies, no confusion entry
+        if (!(t >= 0 && t < C)) continue;                                       // kept and wrong; the sums went NaN above
+        const float sy = s[(int)t];
+        int rank = 0;
+        for (int c = 0; c < C; ++c) rank += (s[c] > sy || (c < (int)t && s[c] == sy)) ? 1 : 0;
+        top1 += rank == 0 ? 1 : 0;
+        topk += rank < a.topk ? 1 : 0;
+        // integer adds commute: whichever order the owning threads arrive in, the cell ends at the same value
+        if (a.confusion) atomicAdd(reinterpret_cast<unsigned long long*>(a.confusion + t * C + pred), 1ull);
+    }
+    const int tid = threadIdx.x;
+    partd[0][tid] = num; partd[1][tid] = den;
+    parti[0][tid] = kept; parti[1][tid] = top1; parti[2][tid] = topk; parti[3][tid] = nans;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {                                         // the fixed 256-leaf tree, in double
+        if (tid < h) {
+            partd[0][tid] += partd[0][tid + h]; partd[1][tid] += partd[1][tid + h];
+            for (int k = 0; k < 4; ++k) parti[k][tid] += parti[k][tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {                                                             // the one add into the caller's block
+        a.sums[0] += partd[0][0];
+        a.sums[1] += partd[1][0];
+        a.counts[0] += a.B;
+        for (int k = 0; k < 4; ++k) a.counts[1 + k] += parti[k][0];
+    }
+}
+
 }  // namespace
 
 extern "C" int hyb_ln_residual_fwd(int dtype, const void* x, const void* skip, const float* gamma, const float* beta, void* y, float* stats,
@@ -1035,6 +1131,20 @@ extern "C" int hyb_cross_entropy_mix_bwd(const float* logits, const long long* t
     HYB_CHECK_ARG(logits && target && target_b && lam && dloss && dlogits && B > 0 && C > 0 && hyb_ce_opts_ok(o));
     hipLaunchKernelGGL(ce_mix_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o,
                        HybCeMix{target_b, lam});
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// The classification meter's update (eval_metrics_kernel): one launch of one workgroup that ADDS into sums / counts / confusion.
+extern "C" int hyb_eval_metrics(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                float label_smoothing, int topk, int views, double* sums, long long* counts, long long* confusion,
+                                long long* pred, float* scores, int B, int C, void* stream) {
+    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
+    HYB_CHECK_ARG(logits && target && sums && counts && B >= 1 && C >= 1 && views >= 1 && topk >= 1 && topk <= C && hyb_ce_opts_ok(o));
+    HYB_CHECK_ARG(views == 1 || scores);
+    HYB_CHECK_ARG((long long)B * views <= 0x7fffffffll);
+    const HybEvalArgs a{logits, target, sums, counts, confusion, pred, scores, B, C, views, topk};
+    hipLaunchKernelGGL(eval_metrics_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, o);
     HYB_LAUNCH_CHECK();
     return 0;
 }

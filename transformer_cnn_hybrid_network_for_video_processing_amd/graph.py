@@ -490,3 +490,80 @@ class GraphedPredict:
         if self.graph is not None:
             self.graph.reset()
         self.graph = self.logits = None
+
+
+class GraphedEval:
+    """``model.evaluate(x, y, meter, mask, views)`` captured once as a hipGraph: predict plus the meter's update launch (hyb_eval_metrics)
+    on static buffers.  ``__call__(x, y)`` copies the batch in and replays; nothing synchronises until ``meter.compute()``.
+
+    The discipline is GraphedPredict's: static ``x``, ``y`` and ``mask``, warm-up on a side stream, then one capture on a stream of its own.
+    The meter's state exists before the capture (the meter creates it eagerly) and the captured launch adds into it in place, so every
+    replay accumulates.  The warm-up calls update the meter like any other call, and their batches must not remain in it: the meter is
+    RESET after the warm-up, before the capture -- a freshly built GraphedEval leaves the meter zeroed, whatever it held before.
+    The logits are bit-identical to GraphedPredict's on the same input, and the returned tensor is the graph's static output (clone to keep).
+    The criterion's class weights are read from its ``weight`` buffer when a replay runs (an in-place update reaches the next replay);
+    ``ignore_index`` and ``label_smoothing`` travel by value in the captured launch, and a change of either after capture is refused, as
+    GraphedTrainStep refuses it.  Works unchanged with the weight-average twin ``optimizer.ema_model(model)``."""
+
+    def __init__(self, model, x, y, meter, mask=None, views=1, warmup=3):
+        if not hasattr(model, "evaluate"):
+            raise TypeError("GraphedEval drives a TransformerCNNHybrid")
+        if not x.is_cuda:
+            raise RuntimeError("GraphedEval needs the model and the clip batch on a cuda (ROCm) device; there is no CPU fallback")
+        self.model, self.meter, self.views = model, meter, views
+        dev = x.device
+        self.x = x.detach().float().clone()                   # static inputs
+        self.y = y.detach().clone()
+        self.mask = mask.detach().clone() if mask is not None else None
+        self._captured_loss_opts = self._loss_opts_now()
+        side = torch.cuda.Stream(device=dev)
+        cap = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                model.evaluate(self.x, self.y, meter, self.mask, views)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        meter.reset()                                          # the warm-up batches do not stay in the meter
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cap):
+            self.logits = model.evaluate(self.x, self.y, meter, self.mask, views)
+        # the capture did not execute: the meter is still zeroed
+
+    def _loss_opts_now(self):
+        """What the captured meter launch carries by value or by address: (ignore_index, label_smoothing, the weight buffer's address)."""
+        c = self.meter.criterion
+        if c is None:
+            return None
+        return (c.ignore_index, c.label_smoothing, c.weight.data_ptr() if c.weight is not None else None)
+
+    def _check_loss_opts(self):
+        now = self._loss_opts_now()
+        if now != self._captured_loss_opts:
+            what = [n for n, a, b in zip(("ignore_index", "label_smoothing", "the weight buffer (replaced, not updated in place)"),
+                                         now or (None,) * 3, self._captured_loss_opts or (None,) * 3) if a != b] or ["criterion itself"]
+            raise RuntimeError(f"GraphedEval: the criterion's {', '.join(what)} changed after capture, but the captured meter launch carries "
+                               "the old value -- construct a new GraphedEval (an in-place update of criterion.weight needs none: the "
+                               "buffer is read at replay time)")
+
+    def __call__(self, x, y, mask=None):
+        if self.graph is None:
+            raise RuntimeError("GraphedEval is closed")
+        if x.shape != self.x.shape or y.shape != self.y.shape:
+            raise ValueError(f"GraphedEval was captured for clips of shape {tuple(self.x.shape)} and targets {tuple(self.y.shape)}, got "
+                             f"{tuple(x.shape)} and {tuple(y.shape)}")
+        self._check_loss_opts()
+        self.x.copy_(x, non_blocking=True)
+        self.y.copy_(y, non_blocking=True)
+        if mask is not None:
+            if self.mask is None:
+                raise ValueError("GraphedEval was captured without a mask")
+            self.mask.copy_(mask, non_blocking=True)
+        self.graph.replay()
+        return self.logits
+
+    def close(self):
+        """Release the graph and its private memory pool (the meter and its state stay)."""
+        if self.graph is not None:
+            self.graph.reset()
+        self.graph = self.logits = None

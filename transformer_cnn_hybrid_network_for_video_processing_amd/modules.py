@@ -427,6 +427,14 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
                             self.head.weight, self.head.bias, mask, B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads, 0.0, float(enc.dropout),
                             ops.next_seed())
 
+    @torch.no_grad()
+    def evaluate(self, x, y, meter, mask=None, views=1):
+        """``predict(x, mask)`` followed by ``meter.update(logits, y, views)`` (meter.ClassificationMeter): one more launch behind the forward,
+        no synchronisation.  x [B * views, T, 3, H, W] with the views of one video adjacent, y int64 [B]; returns the logits [B * views, C]."""
+        logits = self.predict(x, mask)
+        meter.update(logits, y, views)
+        return logits
+
     def backbone_parameters(self):
         return [p for i in range(self.num_stages) for p in getattr(self, f"encoder{i + 1}").parameters()]
 

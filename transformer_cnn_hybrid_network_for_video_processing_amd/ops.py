@@ -28,6 +28,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
     hybrid::clip_transform   uint8 clips -> crop, resize, flip, sub-sample, ToTensor, Normalize   (clips.ClipTransform; no autograd formula)
     hybrid::clip_transform_mix   ... with Mixup / CutMix against a partner clip in the same pass   (one more int32 row per clip)
+    hybrid::eval_metrics_    one launch behind the logits that adds loss, top-1 / top-k, confusion matrix into a meter's state (no autograd formula)
 """
 import ctypes
 import functools
@@ -656,6 +657,45 @@ def cross_entropy_mix(logits, target, target_b, lam, weight=None, ignore_index=N
     on the device; the options as in cross_entropy_opts.  No gradient for lam, the targets or the class weights."""
     return torch.ops.hybrid.cross_entropy_mix(logits, target, target_b, lam, weight, 0 if ignore_index is None else int(ignore_index),
                                               ignore_index is not None, float(label_smoothing))
+
+
+def eval_metrics_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
+                    topk: int, views: int, sums: Tensor, counts: Tensor, confusion: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """The classification meter's update (hyb_eval_metrics): ONE launch that ADDS this batch into sums (float64 [2]: loss numerator and
+    denominator), counts (int64 [5]: videos seen, kept, top-1 correct, top-k correct, NaN rows) and confusion (int64 [C, C], row = target,
+    or None) -> (pred int64 [B], scores fp32 [B, C]: the views' mean softmax, empty [0, C] when views == 1).  logits [B * views, C] fp32
+    contiguous, the views of one video adjacent; the loss options as hybrid::cross_entropy_opts takes them.  Never synchronises."""
+    _require_cuda(logits, target, sums, counts, confusion)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError(f"logits must be a contiguous float32 [B * views, C] tensor, got {logits.dtype} {tuple(logits.shape)}"
+                         + ("" if logits.is_contiguous() else " (not contiguous)"))
+    if views < 1:
+        raise ValueError(f"views must be >= 1, got {views}")
+    C = logits.shape[1]
+    if target.dim() != 1 or target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] * views != logits.shape[0]:
+        raise ValueError(f"expected int64 class indices [B] with logits [B * views, C]: got {target.dtype} {tuple(target.shape)}, "
+                         f"logits {tuple(logits.shape)}, views {views}")
+    B = target.shape[0]
+    if B < 1 or C < 1:
+        raise ValueError(f"an empty batch cannot be evaluated (logits {tuple(logits.shape)})")
+    if not 1 <= topk <= C:
+        raise ValueError(f"topk must be in [1, {C}], got {topk}")
+    for name, t, dtype, shape in (("sums", sums, torch.float64, (2,)), ("counts", counts, torch.int64, (5,)), ("confusion", confusion, torch.int64, (C, C))):
+        if t is not None and not (t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == logits.device):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {logits.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if target.device != logits.device:
+        raise RuntimeError(f"target is on {target.device} but the logits are on {logits.device}")
+    weight = _ce_weight(weight, C, logits.device)
+    pred = torch.empty(B, dtype=torch.int64, device=logits.device)
+    scores = torch.empty((B if views > 1 else 0, C), dtype=torch.float32, device=logits.device)
+    lib.call("hyb_eval_metrics", logits, target, weight, int(ignore_index), int(has_ignore), float(label_smoothing), int(topk), int(views),
+             sums, counts, confusion, pred, scores if views > 1 else None, B, C, _stream())
+    return pred, scores
+
+
+def eval_metrics_fake(logits, target, weight, ignore_index, has_ignore, label_smoothing, topk, views, sums, counts, confusion):
+    return (target.new_empty(target.shape, dtype=torch.int64),
+            logits.new_empty((target.shape[0] if views > 1 else 0, logits.shape[1]), dtype=torch.float32))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1498,6 +1538,9 @@ _define("cross_entropy_mix", "(Tensor logits, Tensor target, Tensor target_b, Te
             logits, target, weight, ignore_index, has_ignore, label_smoothing, target_b, lam))
 _define("cross_entropy_mix_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, "
         "bool has_ignore, float label_smoothing) -> Tensor", cross_entropy_mix_bwd_op, cross_entropy_bwd_fake)
+_define("eval_metrics_", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int topk, int views, "
+        "Tensor(a!) sums, Tensor(b!) counts, Tensor(c!)? confusion) -> (Tensor, Tensor)", eval_metrics_op, eval_metrics_fake)
+_LIB.impl("eval_metrics_", _inference_only("eval_metrics_"), "Autograd")
 _define("backbone", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, bool training, "
         "float momentum, float eps, int dt) -> Tensor[]", backbone_op, backbone_fake,
         lambda x, ws, gs, bs, rms, rvs, training, momentum, eps, dt: list(_BackboneFn.apply(x, len(ws), training, momentum, eps, dt, *ws, *gs, *bs,
