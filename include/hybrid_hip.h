@@ -710,6 +710,33 @@ int hyb_adamw_step_dev_acc(int count, float* const* params, const float* const* 
                            const double* hyper, const double* ema_hyper /* or NULL */, long long k, long long step, long long* step_inc,
                            unsigned int* advance_ticket, const float* clip /* norm_out of hyb_grad_norm_acc, or NULL */, void* stream);
 
+/* ---- skipping an optimizer step whose gradients are not finite, decided on the device ---------------------------------------------------
+ * (New symbols only; hyb_abi_version() stays 9.)  guard: a DEVICE block `long long guard[2]` = {skip_now, skipped_total}, owned by the
+ * caller, zero before the first step.  One norm call and then the AdamW calls of every parameter group, stream-ordered, make one step.
+ *
+ * hyb_grad_norm_guard / hyb_grad_norm_acc_guard: hyb_grad_norm / hyb_grad_norm_acc -- the same chunk launches, the same final sum in the
+ * same order, norm_out bit for bit as they write it -- whose final one-workgroup launch also writes skip_now = !isfinite(norm_out[0]) and
+ * adds it to skipped_total: once per step, the only place that counts.  Not finite means a NaN or infinite element, or finite elements
+ * whose sum of squares overflows fp32 (a single 1e20).  hyper[5] == 0 gives the coefficient 1 as ever: the guard without clipping.
+ * On a skipped step norm_out[0] holds the non-finite norm and norm_out[1] is unspecified. */
+int hyb_grad_norm_guard(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
+                        float* norm_out /* [2] */, long long* guard /* [2] */, void* stream);
+int hyb_grad_norm_acc_guard(int count, const float* const* acc, const float* const* grads /* or NULL */, const long long* numel, long long k,
+                            float* partials, const double* hyper, float* norm_out /* [2] */, long long* guard /* [2] */, void* stream);
+/* hyb_adamw_step_dev_guard: every device-path step behind one call -- acc == NULL (then k == 1 and grads != NULL): hyb_adamw_step_dev, or
+ * hyb_adamw_step_dev_ema when ema and ema_hyper are given; acc != NULL: hyb_adamw_step_dev_acc -- which reads guard[] when it runs.
+ *   skip_now != 0: params, exp_avg, exp_avg_sq and ema get NO stores (not a rewrite of the old values); every element of acc gets +0.0f;
+ *                  an advancing call advances the counter as ever (the counter also seeds dropout: the next replay draws new masks).
+ *   skip_now == 0: the update of the unguarded call, bit for bit, at the step number
+ *                      step + (step_inc ? *step_inc (/ k) : 0) - skipped_total
+ *                  i.e. the number of APPLIED updates: a run with a skipped step has from then on the parameters of a run that never
+ *                  attempted it.
+ * clip must be the norm_out the step's norm call has written (never NULL). */
+int hyb_adamw_step_dev_guard(int count, float* const* params, const float* const* grads /* or NULL */, float* const* exp_avg,
+                             float* const* exp_avg_sq, float* const* acc /* or NULL */, float* const* ema /* or NULL */, const long long* numel,
+                             const double* hyper, const double* ema_hyper /* or NULL */, long long k, long long step, long long* step_inc,
+                             unsigned int* advance_ticket, const float* clip, const long long* guard /* [2] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

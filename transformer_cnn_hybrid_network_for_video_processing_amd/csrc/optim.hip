@@ -9,6 +9,8 @@
 // Gradient accumulation over k micro-batches: hyb_grad_accumulate (acc += g, 3 x 4 bytes per parameter) ends micro-batches 1 .. k - 1,
 // hyb_adamw_step_dev_acc ends the k-th: it steps on (acc + g) / k and leaves acc zeroed (9 x 4 bytes, 11 x 4 with the average) -- no
 // separate sum, scale or memset pass.
+// The non-finite guard: hyb_grad_norm_guard / hyb_grad_norm_acc_guard also decide, on the device, whether the step is skipped (the norm is not
+// finite), and hyb_adamw_step_dev_guard reads the decision: a skipped step stores nothing to the model.
 #include <type_traits>
 
 #include "hyb_common.h"
@@ -220,8 +222,8 @@ template <int MODE = GRAD_PLAIN, typename Args = GradNormArgs> __device__ __forc
     return (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
 }
 
-// partials[0 .. total) -> norm_out; every thread of the (one) workgroup must call it.  LOAD(i) reads partials[i].
-template <typename Load> __device__ __forceinline__ void grad_norm_finish(Load load, int total, const double* hyper, float* norm_out, double* s_sum /* [256] */) {
+// partials[0 .. total) -> norm_out; every thread of the (one) workgroup must call it, thread 0 gets the norm back.  LOAD(i) reads partials[i].
+template <typename Load> __device__ __forceinline__ float grad_norm_finish(Load load, int total, const double* hyper, float* norm_out, double* s_sum /* [256] */) {
     double acc = 0.0;
     for (int i = threadIdx.x; i < total; i += 8 * 256) {          // eight loads in flight (one workgroup: pure latency), added in index order
         float v[8];
@@ -232,10 +234,11 @@ template <typename Load> __device__ __forceinline__ void grad_norm_finish(Load l
     }
     s_sum[threadIdx.x] = acc;
     __syncthreads();
+    float norm = 0.f;
     if (threadIdx.x == 0) {
         double sum = 0.0;
         for (int i = 0; i < 256; ++i) sum += s_sum[i];
-        const float norm = (float)sqrt(sum);
+        norm = (float)sqrt(sum);
         const double mx = hyper[5];
         // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (total_norm + 1e-6), max = 1); a NaN norm stays a NaN coefficient
         double coef = 1.0;
@@ -243,6 +246,7 @@ template <typename Load> __device__ __forceinline__ void grad_norm_finish(Load l
         norm_out[0] = norm;
         norm_out[1] = (float)coef;
     }
+    return norm;
 }
 
 __global__ __launch_bounds__(256) void grad_norm_kernel(GradNormArgs a) {
@@ -260,6 +264,24 @@ template <int MODE> __global__ __launch_bounds__(256) void grad_norm_acc_kernel(
 __global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* partials, int total, const double* hyper, float* norm_out) {
     __shared__ double s_sum[256];
     grad_norm_finish([partials](int i) { return partials[i]; }, total, hyper, norm_out, s_sum);
+}
+
+// ---- the non-finite guard (hyb_grad_norm_guard / hyb_grad_norm_acc_guard / hyb_adamw_step_dev_guard) -------------------------------------
+// A step whose global gradient norm is not finite (a NaN or an infinite element, or finite elements whose sum of squares overflows fp32)
+// must leave the model as it was: the host never looks at the gradients, and a captured launch cannot be left out, so the decision is taken
+// here.  long long guard[2] = {skip_now, skipped_total}, device memory owned by the caller and zero before the first step.  The final norm
+// launch -- one workgroup, once per optimizer step however many parameter groups follow -- is the only writer: the same sum, the same
+// norm_out, then skip_now = !isfinite(norm) and skipped_total += skip_now, plain stores from thread 0 like norm_out's.  Every AdamW launch
+// of the step reads both words (adamw_dev_kernel, GUARD).
+__global__ __launch_bounds__(256) void grad_norm_final_guard_kernel(const float* partials, int total, const double* hyper, float* norm_out,
+                                                                    long long* guard) {
+    __shared__ double s_sum[256];
+    const float norm = grad_norm_finish([partials](int i) { return partials[i]; }, total, hyper, norm_out, s_sum);
+    if (threadIdx.x == 0) {
+        const long long skip = (__float_as_uint(norm) & 0x7f800000u) == 0x7f800000u ? 1ll : 0ll;      // exponent all ones: inf or NaN
+        guard[0] = skip;
+        guard[1] += skip;
+    }
 }
 
 // adamw_kernel with every scalar formed on the device: from hyper[] and step + *step_inc by thread 0, in double, rounded once -- the same
@@ -301,6 +323,11 @@ struct AdamEmaAccArgs : AdamDevTable<ADAM_EMA_ACC_MAX> {
 };
 static_assert(sizeof(AdamArgs) <= 4096 && sizeof(AdamDevArgs) <= 4096 && sizeof(AdamEmaArgs) <= 4096 && sizeof(AdamAccArgs) <= 4096 &&
               sizeof(AdamEmaAccArgs) <= 4096, "the tensor table travels in the kernel arguments");
+// The guarded launches (hyb_adamw_step_dev_guard): the same tables with one more pointer, the guard block.  Types of their own -- the
+// unguarded kernels' arguments stay as they are.
+template <typename Base> struct AdamGuarded : Base { const long long* guard; };
+static_assert(sizeof(AdamGuarded<AdamDevArgs>) <= 4096 && sizeof(AdamGuarded<AdamEmaArgs>) <= 4096 && sizeof(AdamGuarded<AdamAccArgs>) <= 4096 &&
+              sizeof(AdamGuarded<AdamEmaAccArgs>) <= 4096, "the tensor table travels in the kernel arguments");
 
 // adam_one with every fused multiply-add written out, so that the device path computes what adamw_kernel computes as the compiler contracts
 // it (test_unclipped_equals_no_clipping: bit-equal to the plain launch).  adamw_kernel's 16-byte groups end in p = fma(p, decay, -(step * q)),
@@ -320,16 +347,18 @@ __device__ __forceinline__ float adam_ema_one(float e, float p_new, float d32, f
     return __builtin_fmaf(d32, e, omd32 * p_new);
 }
 
-// the step number: step + *step_inc; the accumulated step (ACCUM, a.k micro-steps per optimizer step): step + *step_inc / k
-template <bool ACCUM, typename Args> __device__ __forceinline__ long long adam_step_number(const Args& a) {
-    if constexpr (ACCUM) return a.step + (a.step_inc ? *a.step_inc / a.k : 0ll);
-    else return a.step + (a.step_inc ? *a.step_inc : 0ll);
+// the step number: step + *step_inc; the accumulated step (ACCUM, a.k micro-steps per optimizer step): step + *step_inc / k.  skipped (the
+// guarded launch: guard[1]) is the number of steps, among those that step and the counter count, that were attempted but not applied: bias
+// correction and the average's warm-up go by the number of APPLIED updates.
+template <bool ACCUM, typename Args> __device__ __forceinline__ long long adam_step_number(const Args& a, long long skipped) {
+    if constexpr (ACCUM) return a.step + (a.step_inc ? *a.step_inc / a.k : 0ll) - skipped;
+    else return a.step + (a.step_inc ? *a.step_inc : 0ll) - skipped;
 }
 
-template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_dev_scalars(const Args& a, float* out /* [8] */) {
+template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_dev_scalars(const Args& a, float* out /* [8] */, long long skipped = 0ll) {
 #pragma clang fp contract(off)                                    // 1.0 - lr * wd: a product rounded, then a difference, as on the host (no fma)
     const double lr = a.hyper[0], b1 = a.hyper[1], b2 = a.hyper[2], eps = a.hyper[3], wd = a.hyper[4];
-    const double tt = (double)adam_step_number<ACCUM>(a);
+    const double tt = (double)adam_step_number<ACCUM>(a, skipped);
     const double prod = lr * wd;
     out[0] = (float)(1.0 - prod);
     out[1] = (float)(1.0 - b1);
@@ -343,10 +372,10 @@ template <bool ACCUM = false, typename Args> __device__ __forceinline__ void ada
 
 // the average's decay at step t = step + *step_inc (n = t - 1 updates so far): d = warmup ? min(decay, (1 + n) / (10 + n)) : decay, in double;
 // d and 1 - d are rounded to fp32 once each
-template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_ema_scalars(const Args& a, float* out /* [2] */) {
+template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_ema_scalars(const Args& a, float* out /* [2] */, long long skipped = 0ll) {
 #pragma clang fp contract(off)
     const double decay = a.ema_hyper[0];
-    const double n = (double)(adam_step_number<ACCUM>(a) - 1ll);
+    const double n = (double)(adam_step_number<ACCUM>(a, skipped) - 1ll);
     double d = decay;
     if (a.ema_hyper[1] != 0.0) {
         const double w = (1.0 + n) / (10.0 + n);
@@ -356,17 +385,34 @@ template <bool ACCUM = false, typename Args> __device__ __forceinline__ void ada
     out[1] = (float)(1.0 - d);
 }
 
-template <bool EMA, int ACC> using AdamDevKernelArgs =
+template <bool EMA, int ACC> using AdamDevTableArgs =
     std::conditional_t<ACC != GRAD_PLAIN, std::conditional_t<EMA, AdamEmaAccArgs, AdamAccArgs>, std::conditional_t<EMA, AdamEmaArgs, AdamDevArgs>>;
+template <bool EMA, int ACC, bool GUARD = false> using AdamDevKernelArgs =
+    std::conditional_t<GUARD, AdamGuarded<AdamDevTableArgs<EMA, ACC>>, AdamDevTableArgs<EMA, ACC>>;
+
+// the counter's one read (thread 0, in front of the barrier) is complete in every workgroup that has taken a ticket: see adamw_kernel
+template <typename Args> __device__ __forceinline__ void adam_dev_advance(const Args& a) {
+    if (a.advance && threadIdx.x == 0) {
+        if (__hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
+            __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            *a.advance += 1;
+        }
+    }
+}
 
 // EMA = false: hyb_adamw_step_dev, the launch as it always was.  EMA = true: hyb_adamw_step_dev_ema -- the same body, and where it holds a new
 // parameter value in a register it also moves that parameter's average (2 x 4 more bytes per parameter, no second pass over the weights).
 // ACC != GRAD_PLAIN: hyb_adamw_step_dev_acc -- the same body again on the effective gradient G of an accumulated step (eff_grad: the
 // accumulator is one more 16-byte load per group, issued with the others), which also stores +0.0f over the accumulator it has read;
 // GRAD_ACC: there is no g (t.g is NULL and never read).
-template <bool EMA, int ACC = GRAD_PLAIN> __global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC> a) {
+// GUARD: hyb_adamw_step_dev_guard -- thread 0 reads guard[] = {skip_now, skipped_total} in the scalar phase.  skip_now: the workgroup forms
+// no scalars and stores nothing to p / m / v / e (not even their old values); it stores +0.0f over the accumulators (ACCUM: the poison must
+// not stay in them) and takes its ticket, so the counter -- which also seeds dropout -- advances as after an applied step.  Otherwise the
+// same body with the step number less skipped_total.
+template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false> __global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC, GUARD> a) {
     constexpr bool ACCUM = ACC != GRAD_PLAIN, HAS_G = ACC != GRAD_ACC;
     __shared__ float s_sc[EMA ? 10 : 8];
+    __shared__ int s_skip;
     int ti = 0;
     for (int i = 1; i < a.count; ++i)
         if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
@@ -393,10 +439,30 @@ template <bool EMA, int ACC = GRAD_PLAIN> __global__ __launch_bounds__(256) void
         }
     }
     if (threadIdx.x == 0) {
-        adam_dev_scalars<ACCUM>(a, s_sc);
-        if constexpr (EMA) adam_ema_scalars<ACCUM>(a, s_sc + 8);
+        long long skipped = 0ll;
+        bool skip = false;
+        if constexpr (GUARD) { skip = a.guard[0] != 0ll; skipped = a.guard[1]; s_skip = skip ? 1 : 0; }
+        if (!skip) {
+            adam_dev_scalars<ACCUM>(a, s_sc, skipped);
+            if constexpr (EMA) adam_ema_scalars<ACCUM>(a, s_sc + 8, skipped);
+        }
     }
     __syncthreads();
+    if constexpr (GUARD) {
+        if (s_skip) {                                              // uniform over the workgroup (and over the launch)
+            if constexpr (ACCUM) {
+#pragma unroll 1
+                for (int k = 0; k < NK; ++k) {
+                    const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+                    if (i >= t.n) break;
+                    if (vec && i + 4 <= t.n) *reinterpret_cast<f32x4*>(ta + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+                    else for (long long e = i; e < i + 4 && e < t.n; ++e) ta[e] = 0.f;
+                }
+            }
+            adam_dev_advance(a);
+            return;
+        }
+    }
     const AdamScalars sc{s_sc[0], s_sc[1], s_sc[2], s_sc[3], s_sc[4], s_sc[5], s_sc[6], s_sc[7]};
     float d32 = 0.f, omd32 = 0.f;
     if constexpr (EMA) { d32 = s_sc[8]; omd32 = s_sc[9]; }
@@ -450,13 +516,7 @@ template <bool EMA, int ACC = GRAD_PLAIN> __global__ __launch_bounds__(256) void
             }
         }
     }
-    // the counter's one read (thread 0, in front of the barrier) is complete in every workgroup that has taken a ticket: see adamw_kernel
-    if (a.advance && threadIdx.x == 0) {
-        if (__hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) {
-            __hip_atomic_store(a.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *a.advance += 1;
-        }
-    }
+    adam_dev_advance(a);
 }
 
 __global__ __launch_bounds__(64) void ema_set_kernel(double* ema_hyper, double decay, double warmup) {
@@ -465,13 +525,13 @@ __global__ __launch_bounds__(64) void ema_set_kernel(double* ema_hyper, double d
 
 // hyb_adamw_step_dev (ema == NULL) and hyb_adamw_step_dev_ema: the tensor table in launches of at most the variant's capacity, the last
 // of which advances the counter
-template <bool EMA, int ACC = GRAD_PLAIN>
+template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false>
 int adamw_dev_launch(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                      float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
-                     long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream, float* const* acc = nullptr, long long k = 1) {
+                     long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream, float* const* acc = nullptr, long long k = 1, const long long* guard = nullptr) {
     constexpr int MAX = ACC != GRAD_PLAIN ? (EMA ? ADAM_EMA_ACC_MAX : ADAM_ACC_MAX) : (EMA ? ADAM_EMA_MAX : ADAM_MAX);
     for (int first = 0; first < count; first += MAX) {
-        AdamDevKernelArgs<EMA, ACC> a{};
+        AdamDevKernelArgs<EMA, ACC, GUARD> a{};
         const int n = count - first < MAX ? count - first : MAX;
         int chunks = 0;
         for (int i = 0; i < n; ++i) {
@@ -486,9 +546,10 @@ int adamw_dev_launch(int count, float* const* params, const float* const* grads,
         a.hyper = hyper; a.step_inc = step_inc; a.step = step; a.clip = clip;
         if constexpr (EMA) a.ema_hyper = ema_hyper;
         if constexpr (ACC != GRAD_PLAIN) { a.k = k; a.inv_k = (float)(1.0 / (double)k); }
+        if constexpr (GUARD) a.guard = guard;
         a.advance = (advance_ticket && first + MAX >= count) ? step_inc : nullptr;            // the last launch of the call advances the counter
         a.ticket = advance_ticket;
-        hipLaunchKernelGGL((adamw_dev_kernel<EMA, ACC>), dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((adamw_dev_kernel<EMA, ACC, GUARD>), dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
         HYB_LAUNCH_CHECK();
     }
     return 0;
@@ -539,31 +600,48 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(AccumArgs a) {
     }
 }
 
-}  // namespace
-
-extern "C" int hyb_grad_accumulate(int count, float* const* acc, const float* const* grads, const long long* numel, void* stream) {
-    HYB_CHECK_ARG(count > 0 && acc && grads && numel);
-    for (int i = 0; i < count; ++i) HYB_CHECK_ARG(acc[i] && grads[i] && acc[i] != grads[i] && numel[i] > 0);
-    for (int first = 0; first < count; first += ADAM_MAX) {
-        AccumArgs a{};
-        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
-        long long chunks = 0;
-        for (int i = 0; i < n; ++i) {
-            a.acc[i] = acc[first + i]; a.g[i] = grads[first + i]; a.n[i] = numel[first + i];
-            a.chunk_begin[i] = (int)chunks;
-            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
-            HYB_CHECK_ARG(chunks < (1ll << 31));
-        }
-        a.chunk_begin[n] = (int)chunks;
-        a.count = n;
-        hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, a);
-        HYB_LAUNCH_CHECK();
-    }
+// the one-workgroup launch that ends a norm call; guard != NULL: the variant that also takes the skip decision
+int grad_norm_final_launch(const float* partials, long long total, const double* hyper, float* norm_out, long long* guard, void* stream) {
+    if (guard) hipLaunchKernelGGL(grad_norm_final_guard_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int)total, hyper, norm_out, guard);
+    else hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int)total, hyper, norm_out);
+    HYB_LAUNCH_CHECK();
     return 0;
 }
 
-extern "C" int hyb_grad_norm_acc(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k, float* partials,
-                                 const double* hyper, float* norm_out, void* stream) {
+// hyb_grad_norm (guard == NULL) and hyb_grad_norm_guard: the same chunk launches, the same final sum
+int grad_norm_call(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper, float* norm_out,
+                   long long* guard, void* stream) {
+    HYB_CHECK_ARG(count > 0 && grads && numel && partials && hyper && norm_out);
+    long long total = 0;
+    for (int i = 0; i < count; ++i) {
+        HYB_CHECK_ARG(grads[i] && numel[i] > 0);
+        total += hyb_cdiv(numel[i], ADAM_CHUNK);
+    }
+    HYB_CHECK_ARG(total < (1ll << 31));
+    int offset = 0;
+    for (int first = 0; first < count; first += ADAM_MAX) {
+        GradNormArgs a{};
+        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
+        int chunks = 0;
+        for (int i = 0; i < n; ++i) {
+            a.g[i] = grads[first + i]; a.n[i] = numel[first + i];
+            a.chunk_begin[i] = chunks;
+            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
+        }
+        a.chunk_begin[n] = chunks;
+        a.count = n;
+        a.chunk_offset = offset;
+        a.partials = partials;
+        hipLaunchKernelGGL(grad_norm_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        HYB_LAUNCH_CHECK();
+        offset += chunks;
+    }
+    return grad_norm_final_launch(partials, total, hyper, norm_out, guard, stream);
+}
+
+// hyb_grad_norm_acc (guard == NULL) and hyb_grad_norm_acc_guard
+int grad_norm_acc_call(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k, float* partials,
+                       const double* hyper, float* norm_out, long long* guard, void* stream) {
     HYB_CHECK_ARG(count > 0 && acc && numel && k >= 1 && partials && hyper && norm_out);
     long long total = 0;
     for (int i = 0; i < count; ++i) {
@@ -591,9 +669,41 @@ extern "C" int hyb_grad_norm_acc(int count, const float* const* acc, const float
         HYB_LAUNCH_CHECK();
         offset += chunks;
     }
-    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partials, (int)total, hyper, norm_out);
-    HYB_LAUNCH_CHECK();
+    return grad_norm_final_launch(partials, total, hyper, norm_out, guard, stream);
+}
+
+}  // namespace
+
+extern "C" int hyb_grad_accumulate(int count, float* const* acc, const float* const* grads, const long long* numel, void* stream) {
+    HYB_CHECK_ARG(count > 0 && acc && grads && numel);
+    for (int i = 0; i < count; ++i) HYB_CHECK_ARG(acc[i] && grads[i] && acc[i] != grads[i] && numel[i] > 0);
+    for (int first = 0; first < count; first += ADAM_MAX) {
+        AccumArgs a{};
+        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
+        long long chunks = 0;
+        for (int i = 0; i < n; ++i) {
+            a.acc[i] = acc[first + i]; a.g[i] = grads[first + i]; a.n[i] = numel[first + i];
+            a.chunk_begin[i] = (int)chunks;
+            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
+            HYB_CHECK_ARG(chunks < (1ll << 31));
+        }
+        a.chunk_begin[n] = (int)chunks;
+        a.count = n;
+        hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, a);
+        HYB_LAUNCH_CHECK();
+    }
     return 0;
+}
+
+extern "C" int hyb_grad_norm_acc(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k, float* partials,
+                                 const double* hyper, float* norm_out, void* stream) {
+    return grad_norm_acc_call(count, acc, grads, numel, k, partials, hyper, norm_out, nullptr, stream);
+}
+
+extern "C" int hyb_grad_norm_acc_guard(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k,
+                                       float* partials, const double* hyper, float* norm_out, long long* guard, void* stream) {
+    HYB_CHECK_ARG(guard);
+    return grad_norm_acc_call(count, acc, grads, numel, k, partials, hyper, norm_out, guard, stream);
 }
 
 extern "C" int hyb_adamw_step_dev_acc(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
@@ -610,6 +720,24 @@ extern "C" int hyb_adamw_step_dev_acc(int count, float* const* params, const flo
     }
     if (grads) return adamw_dev_launch<false, GRAD_ACC_G>(count, params, grads, exp_avg, exp_avg_sq, nullptr, numel, hyper, nullptr, step, step_inc, advance_ticket, clip, stream, acc, k);
     return adamw_dev_launch<false, GRAD_ACC>(count, params, nullptr, exp_avg, exp_avg_sq, nullptr, numel, hyper, nullptr, step, step_inc, advance_ticket, clip, stream, acc, k);
+}
+
+// every variant of the device-path step behind one entry point: acc == NULL (k == 1) is the plain step, with or without the average
+extern "C" int hyb_adamw_step_dev_guard(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                        float* const* acc, float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper,
+                                        long long k, long long step, long long* step_inc, unsigned int* advance_ticket, const float* clip,
+                                        const long long* guard, void* stream) {
+    HYB_CHECK_ARG(count > 0 && params && exp_avg && exp_avg_sq && numel && hyper && k >= 1 && step >= 1 && (!advance_ticket || step_inc) &&
+                  (ema != nullptr) == (ema_hyper != nullptr) && guard && clip && (acc || (k == 1 && grads)));
+    for (int i = 0; i < count; ++i)
+        HYB_CHECK_ARG(params[i] && (!grads || grads[i]) && exp_avg[i] && exp_avg_sq[i] && (!acc || (acc[i] && acc[i] != params[i])) &&
+                      (!ema || (ema[i] && ema[i] != params[i])) && numel[i] > 0);
+#define HYB_GUARDED(EMA, ACC, G, E, EH) \
+    adamw_dev_launch<EMA, ACC, true>(count, params, G, exp_avg, exp_avg_sq, E, numel, hyper, EH, step, step_inc, advance_ticket, clip, stream, acc, k, guard)
+    if (!acc) return ema ? HYB_GUARDED(true, GRAD_PLAIN, grads, ema, ema_hyper) : HYB_GUARDED(false, GRAD_PLAIN, grads, nullptr, nullptr);
+    if (ema) return grads ? HYB_GUARDED(true, GRAD_ACC_G, grads, ema, ema_hyper) : HYB_GUARDED(true, GRAD_ACC, nullptr, ema, ema_hyper);
+    return grads ? HYB_GUARDED(false, GRAD_ACC_G, grads, nullptr, nullptr) : HYB_GUARDED(false, GRAD_ACC, nullptr, nullptr, nullptr);
+#undef HYB_GUARDED
 }
 
 extern "C" int hyb_adamw_hyper_set(double* hyper, double lr, double beta1, double beta2, double eps, double weight_decay, double max_grad_norm,
@@ -634,34 +762,13 @@ extern "C" size_t hyb_grad_norm_workspace(int count, const long long* numel) {
 
 extern "C" int hyb_grad_norm(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
                              float* norm_out, void* stream) {
-    HYB_CHECK_ARG(count > 0 && grads && numel && partials && hyper && norm_out);
-    long long total = 0;
-    for (int i = 0; i < count; ++i) {
-        HYB_CHECK_ARG(grads[i] && numel[i] > 0);
-        total += hyb_cdiv(numel[i], ADAM_CHUNK);
-    }
-    HYB_CHECK_ARG(total < (1ll << 31));
-    int offset = 0;
-    for (int first = 0; first < count; first += ADAM_MAX) {
-        GradNormArgs a{};
-        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
-        int chunks = 0;
-        for (int i = 0; i < n; ++i) {
-            a.g[i] = grads[first + i]; a.n[i] = numel[first + i];
-            a.chunk_begin[i] = chunks;
-            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
-        }
-        a.chunk_begin[n] = chunks;
-        a.count = n;
-        a.chunk_offset = offset;
-        a.partials = partials;
-        hipLaunchKernelGGL(grad_norm_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
-        HYB_LAUNCH_CHECK();
-        offset += chunks;
-    }
-    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partials, (int)total, hyper, norm_out);
-    HYB_LAUNCH_CHECK();
-    return 0;
+    return grad_norm_call(count, grads, numel, partials, hyper, norm_out, nullptr, stream);
+}
+
+extern "C" int hyb_grad_norm_guard(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
+                                   float* norm_out, long long* guard, void* stream) {
+    HYB_CHECK_ARG(guard);
+    return grad_norm_call(count, grads, numel, partials, hyper, norm_out, guard, stream);
 }
 
 extern "C" int hyb_adamw_step_dev(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,

@@ -23,7 +23,11 @@ What makes capture legal here
     next replay; ignore_index and label_smoothing travel by value, and step() refuses a change of either after capture;
   * a MixTarget (the labels of a Mixup / CutMix batch) is three static tensors: both targets and lam are read from device memory when a
     replay runs, so load() brings new labels and new mixing weights without a recapture, and the loss stays in the same launches;
-  * BatchNorm running statistics are updated in place by the captured statistics kernels (hybrid::backbone_).
+  * BatchNorm running statistics are updated in place by the captured statistics kernels (hybrid::backbone_);
+  * with HybridAdamW(skip_nonfinite=True) a replay whose gradients are not finite changes nothing in the model: the captured norm launch
+    decides, the captured AdamW launch reads the decision (optim.py).  The counter advances all the same -- the next replay draws new
+    dropout masks -- and the AdamW launch subtracts the device's count of skipped steps from its step number.  The guard is part of the
+    captured launches (and active in the warm-up steps): a toggle after capture is refused.  Not rolled back: the BatchNorm statistics.
 
 Data parallelism (world > 1): the backward pass is captured in two pieces so that the gradient all-reduce of the temporal part
 (25 of the 27 MB) runs -- eagerly, on the collective's own stream, outside any graph, so any torch.distributed backend works --
@@ -62,6 +66,8 @@ from ._lib import lib, ptr_array
 
 
 class GraphedTrainStep:
+    _guard_on = False                # set by the constructor: whether the captured optimizer launches are the guarded ones
+
     def __init__(self, model, criterion, optimizer, x, y, mask=None, process_group=None, warmup=3, dynamic_hyper=False, accumulation_steps=1):
         if not (hasattr(model, "forward_backbone") and hasattr(model, "forward_temporal")):
             raise TypeError("GraphedTrainStep drives a TransformerCNNHybrid")
@@ -92,6 +98,8 @@ class GraphedTrainStep:
         self._clipping = any(g.get("max_grad_norm") is not None for g in optimizer.param_groups)
         # which groups' captured AdamW launch also keeps the weight average (hyb_adamw_step_dev_ema): a kernel variant, fixed by the capture
         self._ema_on = [g.get("ema_decay") is not None for g in optimizer.param_groups]
+        # whether the captured norm and AdamW launches are the guarded ones (skip_nonfinite): entry points, fixed by the capture
+        self._guard_on = bool(getattr(optimizer, "skip_nonfinite", False))
         self._captured_hyper = self._hyper_now()
         from .modules import HybridCrossEntropyLoss
         self._fused_loss = (type(criterion) is HybridCrossEntropyLoss and hasattr(model, "forward_temporal_loss")
@@ -211,6 +219,9 @@ class GraphedTrainStep:
     def _check_hyper(self):
         """In front of every replay.  Device path: upload what changed.  Plain path: a few comparisons per group (the host is the step's pacemaker
         between graph launches, so this stays allocation-free) -- a changed value must not be lost silently."""
+        if bool(getattr(self.optimizer, "skip_nonfinite", False)) != self._guard_on:
+            raise RuntimeError("GraphedTrainStep: skip_nonfinite was switched on or off after capture; the captured norm and AdamW launches are "
+                               "(not) the guarded ones -- set it on the optimizer before constructing GraphedTrainStep")
         now = self._loss_opts_now()
         if now != self._captured_loss_opts:
             what = [n for n, a, b in zip(("ignore_index", "label_smoothing", "the weight buffer (replaced, not updated in place)"), now,
@@ -237,6 +248,11 @@ class GraphedTrainStep:
     def grad_norm(self):
         """optimizer.grad_norm: the device scalar holding the last step's unclipped total gradient norm (max_grad_norm set)."""
         return self.optimizer.grad_norm
+
+    @property
+    def skipped_steps(self):
+        """optimizer.skipped_steps: the device scalar counting the optimizer steps the non-finite guard has skipped (skip_nonfinite=True)."""
+        return self.optimizer.skipped_steps
 
     def _check_accumulation(self):
         if self.optimizer.accumulation_steps != self._k:
@@ -424,12 +440,15 @@ class GraphedTrainStep:
         return int(self.counter.item())
 
     def sync_optimizer_state(self):
-        """Fold the device step counter into the optimizer's Python-side state (before state_dict()).  Refused between the micro-batches
-        of one optimizer step: the accumulators then hold a partial sum that no state dict carries."""
+        """Fold the device step counter into the optimizer's Python-side state (before state_dict()), less the steps the non-finite guard
+        skipped: `step` counts applied updates.  Both device counts are zeroed.  Refused between the micro-batches of one optimizer step:
+        the accumulators then hold a partial sum that no state dict carries."""
         if self._micro:
             raise RuntimeError(f"GraphedTrainStep.sync_optimizer_state() in the middle of an accumulated step ({self._micro} of {self._k} "
                                "micro-batches taken): finish the optimizer step first")
         n = self.steps_done()
+        if hasattr(self.optimizer, "_take_skipped"):
+            n -= self.optimizer._take_skipped()
         for st in self.optimizer.state.values():
             if "step" in st:
                 st["step"] = int(st["step"]) + n

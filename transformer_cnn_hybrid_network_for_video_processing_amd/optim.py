@@ -20,7 +20,20 @@ Two things a training run needs on top of that, both built on hyper-parameters t
     every `.grad` into an fp32 accumulator (`hyb_grad_accumulate`, one launch per group); `step()` after the k-th steps on
     `(acc + grad) * (1 / k)` and leaves the accumulators zeroed, all inside the AdamW launch (`hyb_adamw_step_dev_acc`; the norm of a
     clipped step is taken over the same mean, `hyb_grad_norm_acc`): no separate sum, scale or memset pass.  The accumulators are zero at
-    every optimizer-step boundary, so they are neither state nor part of the state dict."""
+    every optimizer-step boundary, so they are neither state nor part of the state dict.
+  * `skip_nonfinite=True`: an optimizer step whose global gradient norm is not finite -- a NaN or infinite gradient element, or finite ones
+    whose sum of squares overflows fp32 (a single 1e20: deliberate) -- leaves parameters, both moments and the weight average exactly as
+    they were, and is counted, all on the device: the norm launch's final workgroup writes `{skip_now, skipped_total}` into a device block
+    (`hyb_grad_norm_guard` / `hyb_grad_norm_acc_guard`), the AdamW launch reads it and, on a skip, makes no store to the model
+    (`hyb_adamw_step_dev_guard`); it still zeroes the accumulators and advances the device step counter.  What GradScaler.step does, with
+    no host read: it works inside a replayed hipGraph.  Bias correction and the average's warm-up go by the number of APPLIED updates, so
+    the run continues as if the batch had never been seen.  With max_grad_norm the norm is taken anyway and the guard adds no launch;
+    without, the guard runs the norm launches for its decision (coefficient 1).  With finite gradients every step is bit-identical to the
+    unguarded one.  `skipped_steps` / `last_step_skipped` are device scalars; on a skipped step `grad_norm` holds the non-finite norm and
+    `clip_coef` is unspecified.  In eager use `state[p]["step"]` counts ATTEMPTED steps until `fold_skipped()` (one host read; `state_dict()`
+    calls it) subtracts the device count, so saved steps are applied-update counts.  Out of scope: BatchNorm running statistics are
+    updated by the forward pass and are not rolled back (an inf activation reaches them, as in torch), and a learning-rate scheduler
+    stepped by the host is not held back on a skipped step (as with GradScaler)."""
 import copy
 import ctypes
 
@@ -32,7 +45,7 @@ from .ops import _stream
 
 class HybridAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_decay=None, ema_warmup=False,
-                 accumulation_steps=1):
+                 accumulation_steps=1, skip_nonfinite=False):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
@@ -41,6 +54,8 @@ class HybridAdamW(torch.optim.Optimizer):
             raise ValueError("ema_decay must be None (no average) or in [0, 1)")
         # (checked before the base class touches anything; neither a param-group key nor state: the accumulators are zero between steps)
         self._accum_k = self._check_accumulation(accumulation_steps)
+        self._skip_nonfinite = self._check_skip_nonfinite(skip_nonfinite)    # (handled the same way: a constructor argument and an attribute)
+        self._guard = None           # device int64 [2]: skip_now (the last guarded step was skipped), skipped_total (since the last fold)
         # max_grad_norm sits in the groups only so that it travels in the state dict: clipping is global, every group carries the same value;
         # ema_decay / ema_warmup are per group (None: that group takes the launch without the average)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
@@ -76,6 +91,71 @@ class HybridAdamW(torch.optim.Optimizer):
     def accumulation_steps(self):
         return self._accum_k
 
+    @staticmethod
+    def _check_skip_nonfinite(flag):
+        if not isinstance(flag, bool):
+            raise ValueError("skip_nonfinite must be a bool")
+        return flag
+
+    @property
+    def skip_nonfinite(self):
+        return self._skip_nonfinite
+
+    def set_skip_nonfinite(self, flag):
+        """Switch the non-finite guard on or off between steps.  Switching folds the device's count of skipped steps first (fold_skipped():
+        one host read), since only guarded launches subtract it from the step number."""
+        flag = self._check_skip_nonfinite(flag)
+        if flag != self._skip_nonfinite:
+            self.fold_skipped()
+            self._skip_nonfinite = flag
+
+    def _guard_block(self):
+        """The guard block, created and zeroed EAGERLY, for the reason _device_buffers gives."""
+        if self._guard is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("HybridAdamW: the non-finite guard's device block does not exist yet and cannot be created under stream "
+                                   "capture -- call sync_hyper() (or take one eager step()) with skip_nonfinite on before capturing")
+            dev = self.param_groups[0]["params"][0].device
+            if dev.type != "cuda":
+                raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
+            self._guard = torch.zeros(2, dtype=torch.int64, device=dev)
+        return self._guard
+
+    @property
+    def skipped_steps(self):
+        """Device int64 scalar: optimizer steps skipped by the guard since the last fold_skipped().  Reading it synchronises; holding it
+        does not."""
+        return self._guard_block()[1]
+
+    @property
+    def last_step_skipped(self):
+        """Device int64 scalar, 0 or 1: whether the last guarded step was skipped."""
+        return self._guard_block()[0]
+
+    def _take_skipped(self):
+        """The device's count of skipped steps, which is zeroed (one host read).  0 without a guard block."""
+        if self._guard is None:
+            return 0
+        n = int(self._guard[1].item())
+        if n:
+            self._guard[1:].zero_()
+        return n
+
+    def fold_skipped(self):
+        """Subtract the device's count of skipped steps from every stepped parameter's `step` and zero it: `step` then counts applied
+        updates.  The step number the kernel forms (step - skipped) is the same before and after.  One host read.  Returns the count."""
+        n = self._take_skipped()
+        if n:
+            for st in self.state.values():
+                if "step" in st:
+                    st["step"] = int(st["step"]) - n
+        return n
+
+    def state_dict(self):
+        """(A guarded optimizer folds the skipped steps first: saved `step` values are applied-update counts, as torch.optim.AdamW's.)"""
+        self.fold_skipped()
+        return super().state_dict()
+
     def set_step_counter(self, counter, advance=False):
         """With a device counter the step number used by the kernel is state['step'] + counter, read on the device: one captured
         launch then serves every replay of a hipGraph.  advance=True: step() also adds 1 to the counter (inside the AdamW launch, after
@@ -93,7 +173,7 @@ class HybridAdamW(torch.optim.Optimizer):
 
     def uses_device_hyper(self):
         """(The average always takes the device path: its decay is read on the device, so a change between replays is picked up.)"""
-        return self._dynamic or self._accum_k > 1 or any(g.get("max_grad_norm") is not None or g.get("ema_decay") is not None for g in self.param_groups)
+        return self._dynamic or self._accum_k > 1 or self._skip_nonfinite or any(g.get("max_grad_norm") is not None or g.get("ema_decay") is not None for g in self.param_groups)
 
     @staticmethod
     def _group_ema(group):
@@ -130,6 +210,8 @@ class HybridAdamW(torch.optim.Optimizer):
             self._ema_sent = {}
             if self._norm_out is None or self._norm_out.device != dev:
                 self._norm_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        if self._skip_nonfinite:
+            self._guard_block()
         return self._hyper
 
     def _group_hyper(self, group):
@@ -172,6 +254,8 @@ class HybridAdamW(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._tables.clear()
+        if self._guard is not None:                 # loaded `step` values are applied-update counts: nothing is left to subtract
+            self._guard[1:].zero_()
         for st in self.state.values():              # torch casts loaded state to the parameter's dtype/device; keep the layout the kernel needs
             for k in ("exp_avg", "exp_avg_sq", "ema"):
                 if k in st:
@@ -314,6 +398,7 @@ class HybridAdamW(torch.optim.Optimizer):
             raise RuntimeError("HybridAdamW: an advancing step counter needs exactly one parameter group with gradients")
         dev_path = self.uses_device_hyper()
         accum = self._accum_k > 1
+        guard = self._guard_block() if self._skip_nonfinite else None     # (first: a refusal under capture leaves the step counts untouched)
         work = []                                   # per live group: (group index, tensor count, tables, gradients, step number)
         for gi, group in enumerate(self.param_groups):
             ps = [p for p in group["params"] if p.grad is not None]
@@ -375,7 +460,9 @@ class HybridAdamW(torch.optim.Optimizer):
         if not work:
             return loss
         clip_coef = None
-        if clip is not None:                        # ONE norm over the gradients of all groups, as clip_grad_norm_(model.parameters())
+        # ONE norm over the gradients of all groups, as clip_grad_norm_(model.parameters()); the guard takes its decision from it, so it runs
+        # the norm launches without clipping too (hyper[5] == 0: coefficient 1)
+        if clip is not None or guard is not None:
             all_grads = None if accum and self._acc_only else [g for w in work for g in w[3]]
             numels = tuple(n for w in work for n in w[2][5])
             if self._partials is None or self._partials[0] != numels:
@@ -387,13 +474,23 @@ class HybridAdamW(torch.optim.Optimizer):
                 self._partials = (numels, torch.zeros(chunks, dtype=torch.float32, device=hyper.device), arr)
             if accum:                               # ... here over the mean of the k micro-batches' gradients
                 all_accs = ptr_array([a[-1] for w in work for a in w[2][1]])
-                lib.call("hyb_grad_norm_acc", len(numels), all_accs, all_grads, self._partials[2], self._accum_k, self._partials[1],
-                         hyper[work[0][0]], self._norm_out, _stream())
-            else:
+                if guard is None:
+                    lib.call("hyb_grad_norm_acc", len(numels), all_accs, all_grads, self._partials[2], self._accum_k, self._partials[1],
+                             hyper[work[0][0]], self._norm_out, _stream())
+                else:
+                    lib.call("hyb_grad_norm_acc_guard", len(numels), all_accs, all_grads, self._partials[2], self._accum_k, self._partials[1],
+                             hyper[work[0][0]], self._norm_out, guard, _stream())
+            elif guard is None:
                 lib.call("hyb_grad_norm", len(all_grads), all_grads, self._partials[2], self._partials[1], hyper[work[0][0]], self._norm_out, _stream())
+            else:
+                lib.call("hyb_grad_norm_guard", len(all_grads), all_grads, self._partials[2], self._partials[1], hyper[work[0][0]], self._norm_out,
+                         guard, _stream())
             clip_coef = self._norm_out
         for gi, n, tab, grads, step in work:
-            if accum:                               # the same launch on (acc + g) / k, which leaves the accumulators zeroed
+            if guard is not None:                   # every variant below behind one entry point, which reads the decision when it runs
+                lib.call("hyb_adamw_step_dev_guard", n, tab[2], grads, tab[3], tab[4], tab[7], tab[6], tab[5], hyper[gi],
+                         None if tab[6] is None else self._ema_hyper[gi], self._accum_k, step, counter, ticket, clip_coef, guard, _stream())
+            elif accum:                               # the same launch on (acc + g) / k, which leaves the accumulators zeroed
                 lib.call("hyb_adamw_step_dev_acc", n, tab[2], grads, tab[3], tab[4], tab[7], tab[6], tab[5], hyper[gi],
                          None if tab[6] is None else self._ema_hyper[gi], self._accum_k, step, counter, ticket, clip_coef, _stream())
             elif tab[6] is None:
