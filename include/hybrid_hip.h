@@ -589,6 +589,59 @@ int hyb_clips_u8_transform_mix(const unsigned char* src /* [B][Tin][Hin][Win][C]
                                float* dst               /* [B][Tout][C][Ho][Wo] fp32 */,
                                int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
 
+/* hyb_clips_u8_transform_photo: the same pass with colour jitter, grayscale, Gaussian noise and random erasing, with or without mixing (new
+ * symbols, hyb_abi_version() stays 9).  `photo`: one more int32 row of 16 per clip, in device memory; every field is clamped by the kernel:
+ *   [0] [1] [2]  brightness, contrast, saturation factor (fp32 bits): !(f >= 0) (NaN included) counts as 1, values above 16 as 16; a factor of
+ *                exactly 1.0f skips its op
+ *   [3]          order of the three ops, the lexicographic permutations of (B, C, S): 0 BCS, 1 BSC, 2 CBS, 3 CSB, 4 SBC, 5 SCB; outside 0..5: 0
+ *   [4]          gray: != 0, every channel becomes the luma after the jitter
+ *   [5]          noise sigma (fp32 bits, on the [0,1] scale): !(s > 0) is off, values above 1 count as 1
+ *   [6] [7]      low, high 32 bits of the 64-bit noise seed
+ *   [8..11]      erase box ey0, ex0, eh, ew in OUTPUT coordinates, clamped like the CutMix box (ey0 into [0, Ho], eh into [0, Ho-ey0], the same
+ *                for ex0 / ew); eh*ew == 0: no erase
+ *   [12]         erase mode: 0 "zero", 1 "black", 2 "pixel"; outside 0..2: 0
+ *   [13..15]     reserved, not read
+ * Per output pixel of clip b, frame t, all C channels together (C is 1 or 3), in fp32:
+ *   1. v_c = the value of hyb_clips_u8_transform up to and including the division by 255
+ *   2. the three ops in the row's order, each followed by a clamp to [0, 1]:
+ *        brightness v = f*v;   contrast v = f*v + (1-f)*mu;   saturation v = f*v + (1-f)*L(v)
+ *      L = 0.2989 r + 0.587 g + 0.114 b; for C == 1 L is the value itself, saturation and gray do nothing
+ *   3. gray: v_c = L(v)
+ *   4. noise: v = clamp(v + sigma*z, 0, 1), z a Box-Muller draw from the library's counter hash h(seed, idx) (splitmix64's finaliser of
+ *      idx * 0x9E3779B97F4A7C15 + seed, upper 32 bits) at the element's index inside its clip e = ((t*C + c)*Ho + oy)*Wo + ox:
+ *        u1 = ((h(seed, 2e) >> 8) + 1) * 2^-24;   u2 = (h(seed, 2e+1) >> 8) * 2^-24;   z = sqrt(-2 ln u1) * cos(2 pi u2)
+ *      so the noise differs from frame to frame; only the geometry and the colour map are shared over a clip
+ *   5. normalise: v = (v - mean[c]) * invstd[c]   (skipped when mean_invstd is NULL)
+ *   6. erase, inside the box: mode 0 0.0f; mode 1 (0 - mean[c]) * invstd[c] (black; 0.0f without mean_invstd); mode 2 a Box-Muller draw at
+ *      element index e + Tout*C*Ho*Wo (the same seed past the noise's range), on the normalised scale
+ *   7. mix as in hyb_clips_u8_transform_mix (mix == NULL: nothing mixes): the partner's pixel is formed by steps 1-6 under the PARTNER's params
+ *      and photo rows at the same output coordinates, so a mixed clip is the blend or composite of the two clips as this kernel alone would have
+ *      written them; kind 0 and CutMix still do no arithmetic on the values.
+ * The contrast pivot mu is per CLIP, so that all frames of a clip get the same affine map (the rule for crop and flip):
+ *   mu = (sum_t luma_sums[b][t]) / (10000 * 255 * ch * cw * Tout), formed in double and rounded to fp32 once; min(fb*mu, 1) instead when
+ *   brightness precedes contrast in the order.
+ * That is the mean luma of the UNTOUCHED source crop over the clip's frames -- on purpose not torchvision's per-frame mean of the already
+ * jittered, already resized image: it needs no pass over the output and is exact in integers.  luma_sums comes from hyb_clips_u8_luma_sums
+ * with the same src, params and Tout; it may be NULL when no contrast factor other than 1 can occur (with NULL every contrast factor counts
+ * as 1).  Photo rows of factors 1, sigma 0 and an empty box give the bits of hyb_clips_u8_transform / _mix.
+ * C must be 1 or 3; otherwise the limits of hyb_clips_u8_transform. */
+int hyb_clips_u8_transform_photo(const unsigned char* src /* [B][Tin][Hin][Win][C] uint8 */,
+                                 const int* params        /* device, [B][8] int32, one row per CLIP */,
+                                 const int* mix           /* device, [B][8] int32, one row per CLIP; or NULL = nothing mixes */,
+                                 const int* photo         /* device, [B][16] int32, one row per CLIP */,
+                                 const long long* luma_sums /* device, [B][Tout] int64 from hyb_clips_u8_luma_sums; or NULL */,
+                                 const float* mean_invstd /* device, [2][C]: mean then 1/std; or NULL = no normalisation */,
+                                 float* dst               /* [B][Tout][C][Ho][Wo] fp32 */,
+                                 int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
+/* sums[b][t] = the sum over the clamped crop box of output frame t's source frame (the params rows' clamps and temporal clamp of
+ * hyb_clips_u8_transform) of 2989 R + 5870 G + 1140 B; for C == 1 of 10000 * value.  Pure integer arithmetic: exact, independent of the
+ * summation order.  The call overwrites sums (it zeroes them itself, on the stream) and leaves no state behind.  C must be 1 or 3;
+ * Hin, Win <= 16384. */
+int hyb_clips_u8_luma_sums(const unsigned char* src /* [B][Tin][Hin][Win][C] uint8 */,
+                           const int* params        /* device, [B][8] int32, one row per CLIP */,
+                           long long* sums          /* device, [B][Tout] int64 */,
+                           int B, int Tin, int Hin, int Win, int C, int Tout, void* stream);
+
 /* ---- ResNet-bottleneck backbone `Encoder_32K` (only bytecode of it ships with the reference:
  * __pycache__/AE_256_32K.cpython-38.pyc, read as data -- `Bottleneck` src L21-53, `Encoder_32K` src L58-137).  NHWC fp32 with the
  * true channel counts, exact-fp32 arithmetic like the FCT entry points above, which these generalise.

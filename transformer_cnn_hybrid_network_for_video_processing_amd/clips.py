@@ -17,6 +17,8 @@ that same expansion pass (``hyb_clips_u8_transform``), from ONE int32 parameter 
 clip gets the same crop and flip, which per-image host transforms get wrong by default -- so the host never touches a pixel.
 Mixup and CutMix (``ClipTransform(mixup_alpha=..., cutmix_alpha=...)``) ride in that pass too (``hyb_clips_u8_transform_mix``): one more
 int32 row per clip names its partner and lam or the box, the labels come out as a ``MixTarget`` for the fused two-target loss.
+Colour jitter, grayscale, Gaussian noise and random erasing (``ClipTransform(brightness=..., noise_std=..., erase_prob=...)``) are arithmetic on
+the value that pass already holds in a register (``hyb_clips_u8_transform_photo``): a third int32 row per clip, no further pass over the clip.
 """
 import csv
 import os
@@ -86,7 +88,10 @@ class ClipPipeline:
     ``transform`` (a ClipTransform): the clips come out augmented instead, fp32 [B,Tout,C,Ho,Wo] -- one parameter row per clip is drawn
     on the host, copied next to the bytes, and hyb_clips_u8_transform takes the ToTensor kernel's place on the copy stream.
     A transform that mixes (``transform.mixing()``): a mix row and a lam per clip travel with the parameter rows, the partners' labels are
-    gathered on the host before the copy, hyb_clips_u8_transform_mix is the kernel, and the second item is ``MixTarget(y, y[partner], lam)``."""
+    gathered on the host before the copy, hyb_clips_u8_transform_mix is the kernel, and the second item is ``MixTarget(y, y[partner], lam)``.
+    A photometric transform (``transform.photometric()``): a photo row per clip travels too and hyb_clips_u8_transform_photo is the one kernel,
+    with the mix rows or without; with a contrast range hyb_clips_u8_luma_sums fills a per-slot int64 [B,Tout] buffer in front of it on the copy
+    stream.  What is yielded does not change."""
 
     def __init__(self, source, device="cuda", depth=2, transform=None):
         self.source, self.depth, self.transform = source, max(1, int(depth)), transform
@@ -123,6 +128,11 @@ class ClipPipeline:
                     s["y_b"] = torch.empty(B, dtype=torch.int64, device=self.device)
                     s["host_lam"] = torch.empty(B, dtype=torch.float32).pin_memory()
                     s["lam"] = torch.empty(B, dtype=torch.float32, device=self.device)
+                if self.transform.photometric():
+                    s["host_ph"] = torch.empty(B, 16, dtype=torch.int32).pin_memory()
+                    s["dev_ph"] = torch.empty(B, 16, dtype=torch.int32, device=self.device)
+                    if self.transform.needs_luma():
+                        s["luma"] = torch.empty(B, xshape[1], dtype=torch.int64, device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))      # mean_invstd was uploaded on the consumer's stream
 
     def _issue(self, slot, batch):
@@ -143,6 +153,9 @@ class ClipPipeline:
             s["host_m"].numpy()[...] = rows
             s["host_lam"].numpy()[...] = lam
             s["host_yb"].numpy()[...] = s["host_y"].numpy()[partner]            # the partners' labels, gathered here: the device only copies
+        photo = self.transform is not None and self.transform.photometric()
+        if photo:
+            s["host_ph"].numpy()[...] = self.transform.sample_photo(B, self.transform.out_frames(T), *self.transform.size)
         with torch.cuda.stream(self.stream):
             s["dev_u8"].copy_(s["host"], non_blocking=True)
             s["y"].copy_(s["host_y"], non_blocking=True)
@@ -155,6 +168,13 @@ class ClipPipeline:
                     s["dev_m"].copy_(s["host_m"], non_blocking=True)
                     s["y_b"].copy_(s["host_yb"], non_blocking=True)
                     s["lam"].copy_(s["host_lam"], non_blocking=True)
+                if photo:
+                    s["dev_ph"].copy_(s["host_ph"], non_blocking=True)
+                    if "luma" in s:
+                        lib.call("hyb_clips_u8_luma_sums", s["dev_u8"], s["dev_p"], s["luma"], B, T, H, W, C, Tout, self.stream.cuda_stream)
+                    lib.call("hyb_clips_u8_transform_photo", s["dev_u8"], s["dev_p"], s["dev_m"] if mixing else None, s["dev_ph"], s.get("luma"),
+                             self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho, Wo, self.stream.cuda_stream)
+                elif mixing:
                     lib.call("hyb_clips_u8_transform_mix", s["dev_u8"], s["dev_p"], s["dev_m"], self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho,
                              Wo, self.stream.cuda_stream)
                 else:
@@ -209,10 +229,21 @@ class ClipTransform:
     mix_prob      probability that a batch (mix_mode="clip": a clip) is mixed at all
     switch_prob   probability of CutMix when both alphas are > 0
     mix_mode      "batch": one kind and one lam per batch; "clip": every clip draws its own.  The partner is a random permutation either way
+    brightness, contrast, saturation   strength s >= 0 of torchvision's ColorJitter: the factor is drawn from U[max(0, 1-s), 1+s] per CLIP and
+                  the three ops run in a uniformly drawn order; jitter_prob: probability that a clip is jittered at all.  The contrast pivot is
+                  the mean luma of the clip's untouched source crops (one affine map for all frames of a clip), not torchvision's per-frame
+                  mean of the jittered image; there is no hue jitter
+    grayscale     probability that a clip becomes its luma in every channel (after the jitter)
+    noise_std     sigma of additive Gaussian noise on the [0,1] scale, a float or a (lo, hi) range to draw it from; noise_prob: per clip
+    erase_prob, erase_scale, erase_ratio   torchvision's RandomErasing: one box per clip in output coordinates, the same for all its frames;
+                  erase_mode "zero" (0 after the normalisation), "black" (0 before it) or "pixel" (standard normal values)
+                  All of these are drawn by ``sample_photo`` from a THIRD Generator derived from ``seed`` and applied by
+                  hyb_clips_u8_transform_photo; with every one at its default (or train=False) nothing changes: the same kernels, draws and bits
     """
 
     def __init__(self, size, scale=(0.35, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, mean=None, std=None, frames=None, frame_stride=(1, 1), seed=0,
-                 train=True, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, switch_prob=0.5, mix_mode="batch"):
+                 train=True, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, switch_prob=0.5, mix_mode="batch", brightness=0.0, contrast=0.0, saturation=0.0, jitter_prob=1.0,
+                 grayscale=0.0, noise_std=0.0, noise_prob=1.0, erase_prob=0.0, erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), erase_mode="zero"):
         self.size = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
         if min(self.size) <= 0:
             raise ValueError(f"size must be positive, got {size!r}")
@@ -249,6 +280,76 @@ class ClipTransform:
             raise ValueError(f"mix_mode must be 'batch' or 'clip', got {mix_mode!r}")
         self.mix_mode = mix_mode
         self.mix_rng = np.random.default_rng([self.seed, 0x6d6978])          # its own stream: the crop rows do not move when mixing is switched on
+        self.brightness, self.contrast, self.saturation = float(brightness), float(contrast), float(saturation)
+        if not all(v >= 0 for v in (self.brightness, self.contrast, self.saturation)):
+            raise ValueError("brightness, contrast and saturation are strengths >= 0")
+        if max(self.brightness, self.contrast, self.saturation) > 15:
+            raise ValueError("brightness, contrast and saturation must be <= 15 (the kernel clamps a factor to 16)")
+        self.jitter_prob, self.grayscale = float(jitter_prob), float(grayscale)
+        self.noise_prob, self.erase_prob = float(noise_prob), float(erase_prob)
+        if not all(0.0 <= p <= 1.0 for p in (self.jitter_prob, self.grayscale, self.noise_prob, self.erase_prob)):
+            raise ValueError("jitter_prob, grayscale, noise_prob and erase_prob are probabilities")
+        self.noise_std = (float(noise_std), float(noise_std)) if np.isscalar(noise_std) else (float(noise_std[0]), float(noise_std[1]))
+        if not (0 <= self.noise_std[0] <= self.noise_std[1] <= 1):
+            raise ValueError("noise_std is a sigma on the [0,1] scale or a (lo, hi) range with 0 <= lo <= hi <= 1")
+        self.erase_scale, self.erase_ratio = (float(erase_scale[0]), float(erase_scale[1])), (float(erase_ratio[0]), float(erase_ratio[1]))
+        if not (0 < self.erase_scale[0] <= self.erase_scale[1] <= 1) or not (0 < self.erase_ratio[0] <= self.erase_ratio[1]):
+            raise ValueError("erase_scale is a (lo, hi) range inside (0, 1], erase_ratio a (lo, hi) range of positive numbers")
+        if erase_mode not in self.ERASE_MODES:
+            raise ValueError(f"erase_mode must be one of {self.ERASE_MODES}, got {erase_mode!r}")
+        self.erase_mode = erase_mode
+        self.photo_rng = np.random.default_rng([self.seed, 0x70686f])        # a third stream: neither the crop rows nor the mix rows move
+
+    ERASE_MODES = ("zero", "black", "pixel")
+
+    def photometric(self):
+        """Whether this transform jitters, grays, adds noise or erases (ClipPipeline then calls hyb_clips_u8_transform_photo)."""
+        return self.train and (self.brightness > 0 or self.contrast > 0 or self.saturation > 0 or self.grayscale > 0 or self.noise_std[1] > 0
+                               or self.erase_prob > 0)
+
+    def needs_luma(self):
+        """Whether a contrast factor other than 1 may be drawn: the kernel then needs hyb_clips_u8_luma_sums for its pivot."""
+        return self.train and self.contrast > 0
+
+    def _erase_box(self, Ho, Wo):
+        """torchvision's RandomErasing.get_params: up to 10 tries of area x log-uniform ratio that fit strictly inside, else no box."""
+        g, area = self.photo_rng, Ho * Wo
+        for _ in range(10):
+            target = area * g.uniform(self.erase_scale[0], self.erase_scale[1])
+            ar = float(np.exp(g.uniform(np.log(self.erase_ratio[0]), np.log(self.erase_ratio[1]))))
+            h, w = int(round(np.sqrt(target * ar))), int(round(np.sqrt(target / ar)))
+            if 0 < h < Ho and 0 < w < Wo:
+                return int(g.integers(0, Ho - h + 1)), int(g.integers(0, Wo - w + 1)), h, w
+        return 0, 0, 0, 0
+
+    def sample_photo(self, B, Tout, Ho, Wo):
+        """-> int32 [B,16]: one photo row {brightness, contrast, saturation factor bits, order, gray, sigma bits, seed lo, seed hi, ey0, ex0, eh,
+        ew, mode, 0, 0, 0} per clip for hyb_clips_u8_transform_photo.  A clip that draws nothing gets the identity row: factors 1, sigma 0, no
+        box.  Every clip draws a seed, so that the noise and the "pixel" erase of two clips never repeat."""
+        rows = np.zeros((B, 16), dtype=np.int32)
+        one = np.ones(3, dtype=np.float32)
+        rows[:, 0:3] = one.view(np.int32)
+        rows[:, 12] = self.ERASE_MODES.index(self.erase_mode)
+        if not self.photometric():
+            return rows
+        g = self.photo_rng
+        strengths = (self.brightness, self.contrast, self.saturation)
+        for b in range(B):
+            f = one.copy()
+            if max(strengths) > 0 and g.random() < self.jitter_prob:
+                for i, s in enumerate(strengths):
+                    if s > 0:
+                        f[i] = np.float32(g.uniform(max(0.0, 1.0 - s), 1.0 + s))
+                rows[b, 3] = int(g.integers(0, 6))
+            rows[b, 0:3] = f.view(np.int32)
+            if self.grayscale > 0:
+                rows[b, 4] = int(g.random() < self.grayscale)
+            if self.noise_std[1] > 0 and g.random() < self.noise_prob:
+                rows[b, 5] = int(np.float32(g.uniform(self.noise_std[0], self.noise_std[1])).view(np.int32))
+            rows[b, 6:8] = np.asarray([g.integers(0, 1 << 64, dtype=np.uint64)], dtype=np.uint64).view(np.int32)
+            if self.erase_prob > 0 and g.random() < self.erase_prob:
+                rows[b, 8:12] = self._erase_box(Ho, Wo)
+        return rows
 
     def out_frames(self, Tin):
         if self.frames is not None and self.frames > Tin:

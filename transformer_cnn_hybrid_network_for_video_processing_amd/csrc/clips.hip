@@ -202,6 +202,298 @@ __global__ __launch_bounds__(256) void clips_u8_transform_mix_kernel(const unsig
         }
     }
 }
+
+// ---- Photometric augmentation and erasing (hyb_clips_u8_transform_photo; include/hybrid_hip.h has the rule in full).  The two kernels above
+// stay as they were written; clip_unit below is clip_pixel up to and including the division by 255 -- a THIRD copy of that arithmetic, see
+// the note above clips_u8_transform_kernel: change all or none.  tests/test_gpu_photo.py (identity rows against both kernels above with
+// torch.equal) is what catches a copy that was forgotten.
+__device__ __forceinline__ float clip_unit(const unsigned char* __restrict__ fb, unsigned row0, unsigned row1, unsigned c0, unsigned c1, float fx, float fy,
+                                           int c) {
+    const float a00 = (float)fb[row0 + c0 + c], a01 = (float)fb[row0 + c1 + c];
+    const float a10 = (float)fb[row1 + c0 + c], a11 = (float)fb[row1 + c1 + c];
+    // The lerps a + f * (b - a) of the kernels above, as the compiler forms them there: one subtraction and one fused multiply-add each.  Here
+    // the fusion is written out: with twelve values per lane in flight the vectoriser pairs some lerps and leaves others as a rounded product
+    // and a rounded sum, and identity photo rows would no longer give those kernels' bits.
+    const float top = fmaf(fx, a01 - a00, a00), bot = fmaf(fx, a11 - a10, a10);
+    return fmaf(fy, bot - top, top) / 255.0f;            // ToTensor divides by 255 (not a multiply by 1/255)
+}
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+__device__ __forceinline__ float photo_luma(float r, float g, float b) { return 0.2989f * r + 0.587f * g + 0.114f * b; }
+// A jitter factor from its bits: !(f >= 0) (NaN included) is 1, values above 16 are 16
+__device__ __forceinline__ float photo_factor(int bits) {
+    const float f = __int_as_float(bits);
+    return !(f >= 0.f) ? 1.f : (f > 16.f ? 16.f : f);
+}
+// One standard normal draw for element index idx: Box-Muller on two 24-bit uniforms of the project's counter hash; u1 in (0, 1], so the
+// logarithm is finite and |z| <= sqrt(48 ln 2) = 5.77
+__device__ __forceinline__ float photo_normal(unsigned long long seed, unsigned long long idx) {
+    const float u1 = (float)((hyb_hash(seed, 2ull * idx) >> 8) + 1u) * (1.0f / 16777216.0f);
+    const float u2 = (float)(hyb_hash(seed, 2ull * idx + 1ull) >> 8) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);         // cos(2 pi u2) without a rounded angle and without cosf's large-argument path
+}
+// One clip's photo row as the kernel uses it: every field clamped (the host never saw it), the contrast pivot formed.  Wave-uniform.
+// steps: the three colour ops in the row's order, two bits each (0 brightness, 1 contrast, 2 saturation), first op in the low bits.
+struct PhotoRow { float fb, fc, fs, mu, sigma; int steps; bool gray; unsigned long long seed; int ey0, ex0, eh, ew, mode; };
+__device__ __forceinline__ PhotoRow photo_row(const int* __restrict__ photo, const long long* __restrict__ luma_sums, long long b, const ClipRow& r,
+                                              int Tout, int Ho, int Wo) {
+    const int* q = photo + b * 16;
+    PhotoRow h;
+    h.fb = photo_factor(q[0]);
+    h.fc = luma_sums ? photo_factor(q[1]) : 1.f;             // without the sums there is no pivot: the contrast factor counts as 1
+    h.fs = photo_factor(q[2]);
+    int order = q[3];
+    if (order < 0 || order > 5) order = 0;
+    // BCS, BSC, CBS, CSB, SBC, SCB
+    h.steps = order == 0 ? 0x24 : order == 1 ? 0x18 : order == 2 ? 0x21 : order == 3 ? 0x09 : order == 4 ? 0x12 : 0x06;
+    h.gray = q[4] != 0;
+    const float s = __int_as_float(q[5]);
+    h.sigma = !(s > 0.f) ? 0.f : (s > 1.f ? 1.f : s);
+    h.seed = (unsigned long long)(unsigned)q[6] | ((unsigned long long)(unsigned)q[7] << 32);
+    h.ey0 = clampi(q[8], 0, Ho); h.ex0 = clampi(q[9], 0, Wo);
+    h.eh = clampi(q[10], 0, Ho - h.ey0); h.ew = clampi(q[11], 0, Wo - h.ex0);
+    h.mode = q[12];
+    if (h.mode < 0 || h.mode > 2) h.mode = 0;
+    h.mu = 0.f;
+    if (h.fc != 1.f) {
+        // the pivot of the clip: the mean luma of the untouched source crop over the clip's Tout frames, exact integers until this division
+        long long sum = 0;
+        for (int t = 0; t < Tout; ++t) sum += luma_sums[b * Tout + t];
+        float mu = (float)((double)sum / (10000.0 * 255.0 * (double)r.ch * (double)r.cw * (double)Tout));
+        // brightness in front of contrast moves the pivot with the values
+        const bool b_first = (h.steps & 3) == 0 || ((h.steps >> 2 & 3) == 0 && (h.steps & 3) != 1);
+        if (b_first) mu = fminf(h.fb * mu, 1.f);
+        h.mu = mu;
+    }
+    return h;
+}
+// Steps 1-6 of the rule for a lane's VEC pixels of output frame t, all C channels (C is 1 or 3): resample, jitter, gray, noise, normalise, erase
+template <int VEC>
+__device__ __forceinline__ void photo_values(float (&v)[3][VEC], const ClipRow& r, const ClipTaps<VEC>& k, const PhotoRow& h, int t, int oy, int ox0, int C,
+                                             int Tout, int Ho, int Wo, const float* __restrict__ mean_invstd) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if (c >= C) break;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) v[c][j] = clip_unit(r.fb, k.row0, k.row1, k.c0[j], k.c1[j], k.fx[j], k.fy, c);
+    }
+#pragma unroll
+    for (int step = 0; step < 3; ++step) {
+        const int op = h.steps >> (2 * step) & 3;
+        if (op == 0) {
+            if (h.fb != 1.f) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c >= C) break;
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) v[c][j] = clamp01(h.fb * v[c][j]);
+                }
+            }
+        } else if (op == 1) {
+            if (h.fc != 1.f) {
+                const float add = (1.f - h.fc) * h.mu;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c >= C) break;
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) v[c][j] = clamp01(h.fc * v[c][j] + add);
+                }
+            }
+        } else if (h.fs != 1.f && C == 3) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                const float add = (1.f - h.fs) * photo_luma(v[0][j], v[1][j], v[2][j]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][j] = clamp01(h.fs * v[c][j] + add);
+            }
+        }
+    }
+    if (h.gray && C == 3) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) v[0][j] = v[1][j] = v[2][j] = photo_luma(v[0][j], v[1][j], v[2][j]);
+    }
+    const unsigned long long plane = (unsigned long long)Ho * Wo;
+    if (h.sigma != 0.f) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+            const unsigned long long e0 = ((unsigned long long)(t * C + c) * Ho + oy) * Wo + ox0;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) v[c][j] = clamp01(v[c][j] + h.sigma * photo_normal(h.seed, e0 + j));
+        }
+    }
+    if (mean_invstd) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) v[c][j] = (v[c][j] - mean_invstd[c]) * mean_invstd[C + c];
+        }
+    }
+    if (oy >= h.ey0 && oy < h.ey0 + h.eh && h.ew > 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+            const unsigned long long e0 = ((unsigned long long)(t * C + c) * Ho + oy) * Wo + ox0 + (unsigned long long)Tout * C * plane;
+            const float black = mean_invstd ? (0.f - mean_invstd[c]) * mean_invstd[C + c] : 0.f;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                if (ox0 + j >= h.ex0 && ox0 + j < h.ex0 + h.ew) v[c][j] = h.mode == 0 ? 0.f : (h.mode == 1 ? black : photo_normal(h.seed, e0 + j));
+            }
+        }
+    }
+}
+
+// Mixup's blend as clips_u8_transform_mix_kernel compiles it: two rounded products and a rounded sum.  There the compiler forms the products as
+// one packed multiply and does not fuse; here, with other code around the expression, it would fuse one of them into an fma, and identity photo
+// rows would no longer give that kernel's bits (tests/test_gpu_photo.py holds the two together with torch.equal).
+__device__ __forceinline__ float mixup_blend(float lam, float own, float oth) {
+#pragma clang fp contract(off)
+    return lam * own + (1.f - lam) * oth;
+}
+
+// blockIdx.x walks the (row, quad) positions of a frame, blockIdx.y the frames: the clip, its three rows, the partner's, the factors, the
+// order, the box and the seed are wave-uniform, and an op whose factor is exactly 1 is skipped by a scalar branch.  All C channels of a pixel
+// are formed together (the luma needs them), then written as one 16-byte store per channel plane like the kernels above.
+template <int VEC>
+__global__ __launch_bounds__(256) void clips_u8_transform_photo_kernel(const unsigned char* __restrict__ src, const int* __restrict__ params,
+                                                                       const int* __restrict__ mix, const int* __restrict__ photo,
+                                                                       const long long* __restrict__ luma_sums, const float* __restrict__ mean_invstd,
+                                                                       float* __restrict__ dst, long long frames, int B, int Tin, int Hin, int Win, int C,
+                                                                       int Tout, int Ho, int Wo) {
+    const int Wq = Wo / VEC;
+    const unsigned pos = blockIdx.x * 256u + threadIdx.x;
+    if (pos >= (unsigned)(Ho * Wq)) return;
+    const int oy = (int)(pos / (unsigned)Wq), ox0 = ((int)pos - oy * Wq) * VEC;
+    const long long frame_bytes = (long long)Hin * Win * C;
+    for (long long f = blockIdx.y; f < frames; f += gridDim.y) {
+        const long long b = f / Tout;
+        const int t = (int)(f - b * Tout);
+        int kind = 0;
+        const int* m = mix ? mix + b * 8 : nullptr;
+        if (m) kind = m[1];
+        if (kind < 0 || kind > 2) kind = 0;
+        float lam = 1.f;
+        bool own_needed = true, oth_needed = false, in[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) in[j] = false;
+        if (kind == 1) {
+            lam = __int_as_float(m[6]);
+            lam = !(lam <= 1.f) ? 1.f : (lam < 0.f ? 0.f : lam);        // into [0, 1]; a NaN counts as 1
+            oth_needed = true;
+        } else if (kind == 2) {
+            const int by0 = clampi(m[2], 0, Ho), bx0 = clampi(m[3], 0, Wo);
+            const int bh = clampi(m[4], 0, Ho - by0), bw = clampi(m[5], 0, Wo - bx0);
+            const bool inrow = oy >= by0 && oy < by0 + bh;
+            own_needed = false;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                in[j] = inrow && ox0 + j >= bx0 && ox0 + j < bx0 + bw;
+                oth_needed |= in[j];
+                own_needed |= !in[j];
+            }
+        }
+        // ONE copy of the chain's instructions serves the clip and its partner (a loop that is not unrolled): a partner's pixel has the bits the
+        // partner's own launch position would have written, which is what makes a CutMix composite exact.  A quad wholly inside a CutMix box
+        // gathers only the partner, one wholly outside only its own clip.  res holds the clip's own value after side 0 and the mixed one after side 1.
+        float res[3][VEC];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) res[c][j] = 0.f;
+        }
+#pragma unroll 1
+        for (int side = 0; side < 2; ++side) {
+            if (!(side == 0 ? own_needed : oth_needed)) continue;
+            const long long sb = side == 0 ? b : (long long)clampi(m[0], 0, B - 1);      // the partner's own params and photo rows
+            const ClipRow r = clip_row(src, params, sb, t, Tin, Hin, Win, frame_bytes);
+            const PhotoRow h = photo_row(photo, luma_sums, sb, r, Tout, Ho, Wo);
+            const ClipTaps<VEC> k = clip_taps<VEC>(r, oy, ox0, Win, C, Ho, Wo);
+            float cur[3][VEC];
+            photo_values<VEC>(cur, r, k, h, t, oy, ox0, C, Tout, Ho, Wo, mean_invstd);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c >= C) break;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    if (side == 0) res[c][j] = cur[c][j];
+                    else if (kind == 1) res[c][j] = mixup_blend(lam, res[c][j], cur[c][j]);
+                    else if (in[j]) res[c][j] = cur[c][j];
+                }
+            }
+        }
+        float* out = dst + (f * C * Ho + oy) * (long long)Wo + ox0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+            float* oc = out + (long long)c * Ho * Wo;
+            if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(oc) = f32x4{res[c][0], res[c][1], res[c][2], res[c][3]};
+            else oc[0] = res[c][0];
+        }
+    }
+}
+
+// ---- hyb_clips_u8_luma_sums: the integer luma sum of every output frame's source crop, for the contrast pivot.  blockIdx.y is the output
+// frame, the blockIdx.x workgroups of a frame take its crop rows in turn.  A row is a run of cw * C consecutive bytes: its 16-byte aligned
+// middle is read as 16-byte loads, one per lane, the up to 15 bytes in front of and behind it one byte per lane.  For C == 3 a chunk's bytes are
+// summed by position mod 3 and the three sums go to the channels by the chunk's phase in the row.  Integer arithmetic and integer atomics: the
+// result is exact whatever the order; the launch function zeroes sums in front of the kernel.
+constexpr int LUMA_SPLIT_ROWS = 32;                                     // crop rows of a frame per workgroup, at most (Hin / split)
+__global__ __launch_bounds__(256) void clips_u8_luma_sums_kernel(const unsigned char* __restrict__ src, const int* __restrict__ params,
+                                                                 unsigned long long* __restrict__ sums, long long frames, int Tin, int Hin, int Win, int C,
+                                                                 int Tout) {
+    __shared__ unsigned long long red[4];
+    const long long frame_bytes = (long long)Hin * Win * C;
+    const int tid = threadIdx.x;
+    for (long long f = blockIdx.y; f < frames; f += gridDim.y) {
+        const long long b = f / Tout;
+        const int t = (int)(f - b * Tout);
+        const ClipRow r = clip_row(src, params, b, t, Tin, Hin, Win, frame_bytes);
+        const int n = r.cw * C;                                          // bytes of a crop row
+        unsigned long long ch_sum[3] = {0, 0, 0};                        // C == 1: everything in [0]
+        for (int y = blockIdx.x; y < r.ch; y += gridDim.x) {
+            const unsigned char* row = r.fb + ((long long)(r.y0 + y) * Win + r.x0) * C;
+            const int head = min((int)((16u - (unsigned)((unsigned long long)row & 15u)) & 15u), n);
+            const int nchunks = (n - head) >> 4, tail_at = head + (nchunks << 4);
+            for (int i = tid; i < nchunks; i += 256) {
+                const int at = head + (i << 4);
+                const uint4 q = *reinterpret_cast<const uint4*>(row + at);
+                const unsigned w[4] = {q.x, q.y, q.z, q.w};
+                unsigned s[3] = {0, 0, 0};
+#pragma unroll
+                for (int j = 0; j < 16; ++j) s[j % 3] += (w[j >> 2] >> (8 * (j & 3))) & 0xffu;
+                if (C == 1) {
+                    ch_sum[0] += s[0] + s[1] + s[2];
+                } else {
+                    const int p = at % 3;                                // channel of the chunk's first byte
+                    ch_sum[0] += p == 0 ? s[0] : (p == 1 ? s[2] : s[1]);
+                    ch_sum[1] += p == 0 ? s[1] : (p == 1 ? s[0] : s[2]);
+                    ch_sum[2] += p == 0 ? s[2] : (p == 1 ? s[1] : s[0]);
+                }
+            }
+            if (tid < head + (n - tail_at)) {
+                const int at = tid < head ? tid : tail_at + (tid - head);
+                const unsigned val = row[at];
+                if (C == 1) ch_sum[0] += val;
+                else {
+                    const int c = at % 3;
+                    ch_sum[0] += c == 0 ? val : 0u;
+                    ch_sum[1] += c == 1 ? val : 0u;
+                    ch_sum[2] += c == 2 ? val : 0u;
+                }
+            }
+        }
+        unsigned long long tot = C == 1 ? 10000ull * ch_sum[0] : 2989ull * ch_sum[0] + 5870ull * ch_sum[1] + 1140ull * ch_sum[2];
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) tot += __shfl_down(tot, d, 64);
+        if ((tid & 63) == 0) red[tid >> 6] = tot;
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned long long all = red[0] + red[1] + red[2] + red[3];
+            if (all) atomicAdd(sums + f, all);
+        }
+        __syncthreads();
+    }
+}
 }  // namespace
 
 extern "C" int hyb_clips_u8_transform(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int Tin, int Hin,
@@ -238,6 +530,42 @@ extern "C" int hyb_clips_u8_transform_mix(const unsigned char* src, const int* p
     else
         hipLaunchKernelGGL(clips_u8_transform_mix_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mix, mean_invstd, dst, frames, B, Tin,
                            Hin, Win, C, Tout, Ho, Wo);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int hyb_clips_u8_transform_photo(const unsigned char* src, const int* params, const int* mix, const int* photo, const long long* luma_sums,
+                                            const float* mean_invstd, float* dst, int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo,
+                                            void* stream) {
+    HYB_CHECK_ARG(src && params && photo && dst && B > 0 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Ho > 0 && Wo > 0);
+    HYB_CHECK_ARG((C == 1 || C == 3) && Hin <= 16384 && Win <= 16384 && Ho <= 16384 && Wo <= 16384);      // the luma is defined for grey and RGB
+    const long long frames = (long long)B * Tout;
+    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
+    const bool vec = Wo % 4 == 0 && ((unsigned long long)dst & 15) == 0;
+    const int per_frame = Ho * (vec ? Wo / 4 : Wo);
+    const dim3 grid(hyb_cdiv(per_frame, 256), gy);
+    if (vec)
+        hipLaunchKernelGGL(clips_u8_transform_photo_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mix, photo, luma_sums, mean_invstd,
+                           dst, frames, B, Tin, Hin, Win, C, Tout, Ho, Wo);
+    else
+        hipLaunchKernelGGL(clips_u8_transform_photo_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mix, photo, luma_sums, mean_invstd,
+                           dst, frames, B, Tin, Hin, Win, C, Tout, Ho, Wo);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int hyb_clips_u8_luma_sums(const unsigned char* src, const int* params, long long* sums, int B, int Tin, int Hin, int Win, int C, int Tout,
+                                      void* stream) {
+    HYB_CHECK_ARG(src && params && sums && B > 0 && Tin > 0 && Hin > 0 && Win > 0 && Tout > 0);
+    HYB_CHECK_ARG((C == 1 || C == 3) && Hin <= 16384 && Win <= 16384);
+    const long long frames = (long long)B * Tout;
+    // the workgroups of a frame meet in sums[f] through integer atomics: zeroed here, on the same stream, in every call
+    const hipError_t e = hipMemsetAsync(sums, 0, (size_t)frames * sizeof(long long), (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
+    const dim3 grid(hyb_cdiv(Hin, LUMA_SPLIT_ROWS), gy);
+    hipLaunchKernelGGL(clips_u8_luma_sums_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, params, reinterpret_cast<unsigned long long*>(sums), frames,
+                       Tin, Hin, Win, C, Tout);
     HYB_LAUNCH_CHECK();
     return 0;
 }

@@ -28,6 +28,8 @@ fake kernel and an autograd kernel per operator.
     hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
     hybrid::clip_transform   uint8 clips -> crop, resize, flip, sub-sample, ToTensor, Normalize   (clips.ClipTransform; no autograd formula)
     hybrid::clip_transform_mix   ... with Mixup / CutMix against a partner clip in the same pass   (one more int32 row per clip)
+    hybrid::clip_transform_photo ... with colour jitter, grayscale, Gaussian noise and random erasing too   (one int32 row of 16 per clip)
+    hybrid::clip_luma_sums       integer luma sums of the source crops: the contrast pivot of clip_transform_photo
     hybrid::eval_metrics_    one launch behind the logits that adds loss, top-1 / top-k, confusion matrix into a meter's state (no autograd formula)
 """
 import ctypes
@@ -1017,6 +1019,80 @@ def clip_transform_mix(src, params, mix, mean_invstd, Tout, Ho, Wo):
     return torch.ops.hybrid.clip_transform_mix(src, params, mix, mean_invstd, int(Tout), int(Ho), int(Wo))
 
 
+def _clip_photo_rows(photo, B):
+    if photo.dtype != torch.int32 or tuple(photo.shape) != (B, 16):
+        raise TypeError(f"photo must be int32 [{B},16]: one row {{brightness, contrast, saturation bits, order, gray, sigma bits, seed lo, seed hi, "
+                        "ey0, ex0, eh, ew, mode, 0, 0, 0} per clip")
+
+
+def _clip_photo_dims(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo):
+    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
+    if C not in (1, 3):
+        raise ValueError("hybrid::clip_transform_photo needs C == 1 or C == 3 (the luma is defined for grey and RGB clips)")
+    if mix is not None:
+        _clip_mix_rows(mix, B)
+    _clip_photo_rows(photo, B)
+    if luma_sums is not None and (luma_sums.dtype != torch.int64 or tuple(luma_sums.shape) != (B, Tout)):
+        raise TypeError(f"luma_sums must be int64 [{B},{Tout}]: hybrid::clip_luma_sums of the same src, params and Tout")
+    return B, Tin, Hin, Win, C
+
+
+def clip_transform_photo_op(src: Tensor, params: Tensor, mix: Optional[Tensor], photo: Tensor, luma_sums: Optional[Tensor],
+                            mean_invstd: Optional[Tensor], Tout: int, Ho: int, Wo: int) -> Tensor:
+    """hybrid::clip_transform / _mix with colour jitter, grayscale, Gaussian noise and random erasing in the same pass
+    (hyb_clips_u8_transform_photo in include/hybrid_hip.h has the rule): one int32 row of 16 per clip."""
+    _require_cuda(src, params, mix, photo, luma_sums, mean_invstd)
+    B, Tin, Hin, Win, C = _clip_photo_dims(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo)
+    out = torch.empty(B, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
+    lib.call("hyb_clips_u8_transform_photo", src.contiguous(), params.contiguous(), None if mix is None else mix.contiguous(), photo.contiguous(),
+             None if luma_sums is None else luma_sums.contiguous(), None if mean_invstd is None else mean_invstd.contiguous(), out,
+             B, Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
+    return out
+
+
+def clip_transform_photo_fake(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo):
+    B, Tin, Hin, Win, C = _clip_photo_dims(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo)
+    return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
+
+
+def _clip_luma_dims(src, params, Tout):
+    if src.dim() != 5 or src.dtype != torch.uint8:
+        raise TypeError("hybrid::clip_luma_sums reads uint8 clips [B,Tin,Hin,Win,C]")
+    B, Tin, Hin, Win, C = src.shape
+    if params.dtype != torch.int32 or tuple(params.shape) != (B, 8):
+        raise TypeError(f"params must be int32 [{B},8]: one row {{y0, x0, ch, cw, flip, t0, tstride, 0}} per clip")
+    if C not in (1, 3) or max(Hin, Win) > 16384 or min(B, Tin, Hin, Win, Tout) <= 0:
+        raise ValueError("hybrid::clip_luma_sums needs C == 1 or C == 3, extents > 0 and Hin, Win <= 16384")
+    return B, Tin, Hin, Win, C
+
+
+def clip_luma_sums_op(src: Tensor, params: Tensor, Tout: int) -> Tensor:
+    """int64 [B,Tout]: the integer luma sum (2989 R + 5870 G + 1140 B; grey: 10000 * value) over the crop of every output frame's source frame
+    (hyb_clips_u8_luma_sums in include/hybrid_hip.h), from which hybrid::clip_transform_photo forms its contrast pivot."""
+    _require_cuda(src, params)
+    B, Tin, Hin, Win, C = _clip_luma_dims(src, params, Tout)
+    out = torch.empty(B, Tout, dtype=torch.int64, device=src.device)
+    lib.call("hyb_clips_u8_luma_sums", src.contiguous(), params.contiguous(), out, B, Tin, Hin, Win, C, int(Tout), _stream())
+    return out
+
+
+def clip_luma_sums_fake(src, params, Tout):
+    B = _clip_luma_dims(src, params, Tout)[0]
+    return src.new_empty((B, Tout), dtype=torch.int64)
+
+
+def clip_transform_photo(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo):
+    """clip_transform with photo rows int32 [B,16] (ClipTransform.sample_photo): colour jitter, grayscale, Gaussian noise and random erasing in
+    the same pass.  mix: rows of clip_transform_mix or None; luma_sums: clip_luma_sums(src, params, Tout), needed when a contrast factor may
+    differ from 1, else None."""
+    return torch.ops.hybrid.clip_transform_photo(src, params, mix, photo, luma_sums, mean_invstd, int(Tout), int(Ho), int(Wo))
+
+
+def clip_luma_sums(src, params, Tout):
+    """int64 [B,Tout] luma sums of the source crops, the contrast pivot's numerator for clip_transform_photo."""
+    return torch.ops.hybrid.clip_luma_sums(src, params, int(Tout))
+
+
 def _check_h_dtype(h, dt):
     """dt | HYB_H_BF16 (fp32 / bf16x3 temporal part behind bf16 conv stages): the pooled map is bf16, the global-average-pool kernels convert."""
     want = torch.bfloat16 if dt & HYB_H_BF16 else _TORCH_DTYPE[dt & 0xff]
@@ -1562,6 +1638,11 @@ _LIB.impl("clip_transform", _inference_only("clip_transform"), "Autograd")
 _define("clip_transform_mix", "(Tensor src, Tensor params, Tensor mix, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor", clip_transform_mix_op,
         clip_transform_mix_fake)
 _LIB.impl("clip_transform_mix", _inference_only("clip_transform_mix"), "Autograd")
+_define("clip_transform_photo", "(Tensor src, Tensor params, Tensor? mix, Tensor photo, Tensor? luma_sums, Tensor? mean_invstd, int Tout, int Ho, int Wo) "
+        "-> Tensor", clip_transform_photo_op, clip_transform_photo_fake)
+_LIB.impl("clip_transform_photo", _inference_only("clip_transform_photo"), "Autograd")
+_define("clip_luma_sums", "(Tensor src, Tensor params, int Tout) -> Tensor", clip_luma_sums_op, clip_luma_sums_fake)
+_LIB.impl("clip_luma_sums", _inference_only("clip_luma_sums"), "Autograd")
 _define("temporal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, int B, int dt, "
         "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor)", temporal_op,
         functools.partial(_temporal_fake, 0),
