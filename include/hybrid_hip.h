@@ -589,6 +589,19 @@ int hyb_clips_u8_transform_mix(const unsigned char* src /* [B][Tin][Hin][Win][C]
                                float* dst               /* [B][Tout][C][Ho][Wo] fp32 */,
                                int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
 
+/* hyb_clips_u8_transform_views: multi-view evaluation clips, V views of every source clip in one launch (new symbol, hyb_abi_version() stays
+ * 9).  `params` holds V rows per SOURCE clip, adjacent: output clip r = b*V + v is what hyb_clips_u8_transform writes for row params[r] applied
+ * to source clip b = r / V -- the same clamps, the same sampling rule, the same division by 255 and (x - mean) * invstd, bit for bit; nothing
+ * but the source-clip index changes.  So B uint8 clips, copied to the device once, become the [B*V] rows that hyb_eval_metrics scores with
+ * views = V (the mean softmax of V adjacent rows), without replicating a source byte.  The kernel walks the output frames with v fastest inside
+ * (b, t): views that share a temporal window read one source frame from neighbouring workgroups; which frame a workgroup writes does not
+ * change its values.  V >= 1, B*V within int; otherwise the limits of hyb_clips_u8_transform.  V == 1 is that function's output. */
+int hyb_clips_u8_transform_views(const unsigned char* src /* [B][Tin][Hin][Win][C] uint8 */,
+                                 const int* params        /* device, [B*V][8] int32: V rows per SOURCE clip, adjacent */,
+                                 const float* mean_invstd /* device, [2][C]: mean then 1/std; or NULL = no normalisation */,
+                                 float* dst               /* [B*V][Tout][C][Ho][Wo] fp32 */,
+                                 int B, int V, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
+
 /* hyb_clips_u8_transform_photo: the same pass with colour jitter, grayscale, Gaussian noise and random erasing, with or without mixing (new
  * symbols, hyb_abi_version() stays 9).  `photo`: one more int32 row of 16 per clip, in device memory; every field is clamped by the kernel:
  *   [0] [1] [2]  brightness, contrast, saturation factor (fp32 bits): !(f >= 0) (NaN included) counts as 1, values above 16 as 16; a factor of

@@ -19,6 +19,9 @@ Mixup and CutMix (``ClipTransform(mixup_alpha=..., cutmix_alpha=...)``) ride in 
 int32 row per clip names its partner and lam or the box, the labels come out as a ``MixTarget`` for the fused two-target loss.
 Colour jitter, grayscale, Gaussian noise and random erasing (``ClipTransform(brightness=..., noise_std=..., erase_prob=...)``) are arithmetic on
 the value that pass already holds in a register (``hyb_clips_u8_transform_photo``): a third int32 row per clip, no further pass over the clip.
+Multi-view evaluation (``ClipTransform(train=False, eval_views=(K, S), eval_crop=..., eval_flip=...)``): K temporal windows x S spatial crops of
+every clip come out of ONE launch (``hyb_clips_u8_transform_views``) that reads each source clip in place, V parameter rows per clip -- the bytes
+cross PCIe once, and the rows are in the order ``ClassificationMeter.update(..., views=V)`` scores.
 """
 import csv
 import os
@@ -91,7 +94,11 @@ class ClipPipeline:
     gathered on the host before the copy, hyb_clips_u8_transform_mix is the kernel, and the second item is ``MixTarget(y, y[partner], lam)``.
     A photometric transform (``transform.photometric()``): a photo row per clip travels too and hyb_clips_u8_transform_photo is the one kernel,
     with the mix rows or without; with a contrast range hyb_clips_u8_luma_sums fills a per-slot int64 [B,Tout] buffer in front of it on the copy
-    stream.  What is yielded does not change."""
+    stream.  What is yielded does not change.
+    An evaluation transform with ``transform.views`` = V > 1: the source bytes are staged and copied once, [B,Tin,Hin,Win,C]; V parameter rows
+    per clip (``transform.sample_views``) travel with them, hyb_clips_u8_transform_views is the one kernel, and what is yielded is
+    (x fp32 [B*V,Tout,C,Ho,Wo], y int64 [B]) -- what ``model.evaluate(x, y, meter, views=V)`` and ``GraphedEval(..., views=V)`` take.
+    ``pipeline.views`` is V (1 without a transform)."""
 
     def __init__(self, source, device="cuda", depth=2, transform=None):
         self.source, self.depth, self.transform = source, max(1, int(depth)), transform
@@ -101,12 +108,17 @@ class ClipPipeline:
         self.stream = torch.cuda.Stream(device=self.device)
         self._slots = None
 
+    @property
+    def views(self):
+        """Output clips per source clip: the ``views=`` of the meter, model.evaluate and GraphedEval behind this pipeline."""
+        return 1 if self.transform is None else self.transform.views
+
     def _make_slots(self, shape):
         B, T, H, W, C = shape
         xshape = (B, T, C, H, W)
         if self.transform is not None:
             Tout, (Ho, Wo) = self.transform.out_frames(T), self.transform.size
-            xshape = (B, Tout, C, Ho, Wo)
+            xshape = (B * self.views, Tout, C, Ho, Wo)
             mi = self.transform.mean_invstd(C)
             self._mean_invstd = None if mi is None else torch.from_numpy(mi).to(self.device)
         self._slots = [dict(host=torch.empty(shape, dtype=torch.uint8).pin_memory(), host_y=torch.empty(B, dtype=torch.int64).pin_memory(),
@@ -119,8 +131,8 @@ class ClipPipeline:
         if self.transform is not None:
             # the parameter rows are per slot for the same reason the bytes are: the copy stream writes batch n+2's while batch n's are read
             for s in self._slots:
-                s["host_p"] = torch.empty(B, 8, dtype=torch.int32).pin_memory()
-                s["dev_p"] = torch.empty(B, 8, dtype=torch.int32, device=self.device)
+                s["host_p"] = torch.empty(B * self.views, 8, dtype=torch.int32).pin_memory()
+                s["dev_p"] = torch.empty(B * self.views, 8, dtype=torch.int32, device=self.device)
                 if self.transform.mixing():
                     s["host_m"] = torch.empty(B, 8, dtype=torch.int32).pin_memory()
                     s["dev_m"] = torch.empty(B, 8, dtype=torch.int32, device=self.device)
@@ -145,7 +157,12 @@ class ClipPipeline:
         s["free"].synchronize()                               # the consumer has finished with this slot's device tensors
         s["host"].numpy()[...] = frames                       # pageable -> pinned (the decoder could write here directly)
         s["host_y"].numpy()[...] = np.asarray(labels, dtype=np.int64)
-        if self.transform is not None:
+        views = self.views
+        if self.transform is not None and not self.transform.train:
+            # the evaluation rows, V adjacent ones per clip, no draw; with the default views they are sample()'s, and one view per clip
+            # (eval_crop alone, say) goes through the plain kernel below
+            s["host_p"].numpy()[...] = self.transform.sample_views(B, T, H, W)
+        elif self.transform is not None:
             s["host_p"].numpy()[...] = self.transform.sample(B, T, H, W)      # one row per clip: all T frames share crop and flip
         mixing = self.transform is not None and self.transform.mixing()
         if mixing:
@@ -174,6 +191,9 @@ class ClipPipeline:
                         lib.call("hyb_clips_u8_luma_sums", s["dev_u8"], s["dev_p"], s["luma"], B, T, H, W, C, Tout, self.stream.cuda_stream)
                     lib.call("hyb_clips_u8_transform_photo", s["dev_u8"], s["dev_p"], s["dev_m"] if mixing else None, s["dev_ph"], s.get("luma"),
                              self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho, Wo, self.stream.cuda_stream)
+                elif views > 1:
+                    lib.call("hyb_clips_u8_transform_views", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, views, T, H, W, C, Tout, Ho, Wo,
+                             self.stream.cuda_stream)
                 elif mixing:
                     lib.call("hyb_clips_u8_transform_mix", s["dev_u8"], s["dev_p"], s["dev_m"], self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho,
                              Wo, self.stream.cuda_stream)
@@ -239,11 +259,21 @@ class ClipTransform:
                   erase_mode "zero" (0 after the normalisation), "black" (0 before it) or "pixel" (standard normal values)
                   All of these are drawn by ``sample_photo`` from a THIRD Generator derived from ``seed`` and applied by
                   hyb_clips_u8_transform_photo; with every one at its default (or train=False) nothing changes: the same kernels, draws and bits
+    eval_views    (K, S) with train=False: K uniformly spaced temporal windows x S spatial crops per clip (the "clips x crops" protocol video
+                  classifiers are reported under); ``views`` = K * S * (2 with eval_flip) rows per clip come from ``sample_views`` and
+                  hyb_clips_u8_transform_views writes them in one launch.  (1, 1), the default: today's single centred view.  K > 1 needs ``frames``
+    eval_crop     fraction in (0, 1] of the sides of the largest centred crop that each spatial crop takes: 224/256 on a source whose short
+                  side is 256 is "resize 256, crop 224" (with ch == Ho bit for bit ToTensor of the crop).  The S crops are spread along the
+                  axis with more slack, the first and last touching the borders (S == 3 on a landscape frame: left, centre, right)
+    eval_flip     every view is followed by its horizontally flipped twin
+                  An axis without slack gives coinciding views (S = 3 of a square source at eval_crop = 1: three times the same crop); that is
+                  allowed.  All three are for train=False: a non-default value with train=True raises
     """
 
     def __init__(self, size, scale=(0.35, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, mean=None, std=None, frames=None, frame_stride=(1, 1), seed=0,
                  train=True, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, switch_prob=0.5, mix_mode="batch", brightness=0.0, contrast=0.0, saturation=0.0, jitter_prob=1.0,
-                 grayscale=0.0, noise_std=0.0, noise_prob=1.0, erase_prob=0.0, erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), erase_mode="zero"):
+                 grayscale=0.0, noise_std=0.0, noise_prob=1.0, erase_prob=0.0, erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), erase_mode="zero",
+                 eval_views=(1, 1), eval_crop=1.0, eval_flip=False):
         self.size = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
         if min(self.size) <= 0:
             raise ValueError(f"size must be positive, got {size!r}")
@@ -299,6 +329,15 @@ class ClipTransform:
             raise ValueError(f"erase_mode must be one of {self.ERASE_MODES}, got {erase_mode!r}")
         self.erase_mode = erase_mode
         self.photo_rng = np.random.default_rng([self.seed, 0x70686f])        # a third stream: neither the crop rows nor the mix rows move
+        self.eval_views, self.eval_crop, self.eval_flip = (int(eval_views[0]), int(eval_views[1])), float(eval_crop), bool(eval_flip)
+        if min(self.eval_views) < 1:
+            raise ValueError(f"eval_views is (K, S) with K >= 1 temporal windows and S >= 1 spatial crops, got {eval_views!r}")
+        if not (0.0 < self.eval_crop <= 1.0):
+            raise ValueError(f"eval_crop is a fraction in (0, 1], got {eval_crop!r}")
+        if self.train and (self.eval_views != (1, 1) or self.eval_crop != 1.0 or self.eval_flip):
+            raise ValueError("eval_views, eval_crop and eval_flip describe the evaluation transform: they need train=False")
+        if self.eval_views[0] > 1 and self.frames is None:
+            raise ValueError("eval_views with K > 1 temporal windows needs frames=: without it every window is the whole clip")
 
     ERASE_MODES = ("zero", "black", "pixel")
 
@@ -351,6 +390,52 @@ class ClipTransform:
                 rows[b, 8:12] = self._erase_box(Ho, Wo)
         return rows
 
+    @property
+    def views(self):
+        """Output clips per source clip: K * S * (2 with eval_flip); always 1 with train=True."""
+        return 1 if self.train else self.eval_views[0] * self.eval_views[1] * (2 if self.eval_flip else 1)
+
+    def _centre_crop(self, Hin, Win):
+        """(h, w) of the largest crop of the output's aspect ratio that fits the frame: the train=False crop."""
+        Ho, Wo = self.size
+        if Win * Ho >= Hin * Wo:
+            return Hin, max(1, Hin * Wo // Ho)
+        return max(1, Win * Ho // Wo), Win
+
+    def sample_views(self, B, Tin, Hin, Win):
+        """-> int32 [B*V,8]: the V = ``views`` rows {y0, x0, ch, cw, flip, t0, tstride, 0} of every clip for hyb_clips_u8_transform_views, clip-major,
+        then temporal window k, then spatial crop s, then flip (fastest).  Deterministic: nothing is drawn.
+          crop      (h0, w0) = the train=False crop of ``sample``; eval_crop == 1: (h, w) = (h0, w0), else max(1, round(h0 * eval_crop)), likewise w
+          position  slack sy = Hin - h, sx = Win - w; the crops are spread along x if sx >= sy, else along y; the other axis is centred at
+                    slack // 2; on the spread axis S == 1 gives slack // 2 and S > 1 gives slack * s // (S - 1): the first and last crops touch the
+                    two borders
+          time      the smallest fitting stride; span = (Tout - 1) * stride + 1, slack_t = Tin - span; K == 1: t0 = slack_t // 2, K > 1:
+                    t0 = slack_t * k // (K - 1)
+        No row needs the kernel's clamps.  With the defaults the rows are ``sample``'s."""
+        if self.train:
+            raise ValueError("sample_views is the evaluation sampler: it needs train=False")
+        Tout = self.out_frames(Tin)
+        (K, S), F = self.eval_views, 2 if self.eval_flip else 1
+        h, w = self._centre_crop(Hin, Win)
+        if self.eval_crop != 1.0:
+            h, w = max(1, int(round(h * self.eval_crop))), max(1, int(round(w * self.eval_crop)))
+        sy, sx = Hin - h, Win - w
+        along_x = sx >= sy
+        stride, slack_t = 1, 0
+        if self.frames is not None:
+            stride = self._strides(Tin)[0]
+            slack_t = Tin - ((Tout - 1) * stride + 1)
+        one = np.zeros((K, S, F, 8), dtype=np.int32)
+        for k in range(K):
+            t0 = slack_t // 2 if K == 1 else slack_t * k // (K - 1)
+            for s in range(S):
+                slack = sx if along_x else sy
+                at = slack // 2 if S == 1 else slack * s // (S - 1)
+                y0, x0 = (sy // 2, at) if along_x else (at, sx // 2)
+                for f in range(F):
+                    one[k, s, f] = (y0, x0, h, w, f, t0, stride, 0)
+        return np.tile(one.reshape(K * S * F, 8), (B, 1))                 # every clip of a batch has the same shape: the same V rows
+
     def out_frames(self, Tin):
         if self.frames is not None and self.frames > Tin:
             raise ValueError(f"frames={self.frames} exceeds the clip length {Tin}")
@@ -399,10 +484,7 @@ class ClipTransform:
                 y0, x0, h, w = self._crop(Hin, Win)
                 flip = int(self.rng.random() < self.hflip)
             else:
-                if Win * Ho >= Hin * Wo:
-                    h, w = Hin, max(1, Hin * Wo // Ho)
-                else:
-                    h, w = max(1, Win * Ho // Wo), Win
+                h, w = self._centre_crop(Hin, Win)
                 y0, x0, flip = (Hin - h) // 2, (Win - w) // 2, 0
             t0, stride = 0, 1
             if self.frames is not None:

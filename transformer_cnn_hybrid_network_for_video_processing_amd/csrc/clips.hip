@@ -13,6 +13,10 @@
 // are gathered straight from global memory as bytes: neighbouring lanes read neighbouring (down-scale: strided) bytes of the same two
 // source rows, which the vector L1 serves; no LDS, no barrier.  blockIdx.x walks the (row, quad) positions of a frame, blockIdx.y the
 // output frames, so the clip index, its parameter row and the clamps are wave-uniform.
+//
+// Four launches share the rule: the plain kernel, the mix kernel (Mixup / CutMix), the photo kernel (colour jitter, noise, erasing) and the
+// views kernel (V evaluation views of every source clip, hyb_clips_u8_transform_views).  The plain, mix, photo and luma kernels are to keep
+// their instruction schedules: a new variant is a new kernel built from clip_row / clip_taps / clip_pixel, not a change to one of them.
 #include "hyb_common.h"
 
 namespace {
@@ -199,6 +203,46 @@ __global__ __launch_bounds__(256) void clips_u8_transform_mix_kernel(const unsig
             float* oc = out + (long long)c * Ho * Wo;
             if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(oc) = f32x4{v[0], v[1], v[2], v[3]};
             else oc[0] = v[0];
+        }
+    }
+}
+
+// ---- Multi-view evaluation (hyb_clips_u8_transform_views): V parameter rows per SOURCE clip, output clip b * V + v from row b * V + v and the
+// bytes of clip b.  The pixel is the plain kernel's, through the helpers above: one gather, clip_pixel once -- its bits.
+// The walk over the B * V * Tout output frames is re-ordered: position g of the walk is (b, t, v) with v fastest, i.e. output frame
+// (b * V + v) * Tout + t.  ClipTransform.sample_views orders a clip's rows window-major with crops and flips inside, so neighbouring v of one t
+// are the crops of ONE temporal window: they read the same source frame, and workgroups dispatched one after the other find its bytes in the
+// L2.  In output order the second reader of a source frame would come Tout frames of workgroups later.  Which frame a workgroup writes does not
+// change what it writes; b, v, t and the row stay wave-uniform.
+template <int VEC>
+__global__ __launch_bounds__(256) void clips_u8_transform_views_kernel(const unsigned char* __restrict__ src, const int* __restrict__ params,
+                                                                       const float* __restrict__ mean_invstd, float* __restrict__ dst,
+                                                                       long long frames, int V, int Tin, int Hin, int Win, int C, int Tout, int Ho,
+                                                                       int Wo) {
+    const int Wq = Wo / VEC;
+    const unsigned pos = blockIdx.x * 256u + threadIdx.x;            // (oy, quad) inside a frame: Ho * Wq <= 2^28
+    if (pos >= (unsigned)(Ho * Wq)) return;
+    const int oy = (int)(pos / (unsigned)Wq), ox0 = ((int)pos - oy * Wq) * VEC;
+    const long long frame_bytes = (long long)Hin * Win * C;
+    for (long long g = blockIdx.y; g < frames; g += gridDim.y) {
+        const long long bt = g / V;
+        const int v = (int)(g - bt * V);
+        const long long b = bt / Tout;                               // the source clip
+        const int t = (int)(bt - b * Tout);
+        const long long row = b * V + v;                             // the output clip and its parameter row
+        // clip_row reads row `b` of the rows it is given and frame (b, ts) of src: hand it the rows shifted so that its row b is row `row`
+        const ClipRow r = clip_row(src, params + (row - b) * 8, b, t, Tin, Hin, Win, frame_bytes);
+        const ClipTaps<VEC> k = clip_taps<VEC>(r, oy, ox0, Win, C, Ho, Wo);
+        float* out = dst + ((row * Tout + t) * C * Ho + oy) * (long long)Wo + ox0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (c >= C) break;
+            float val[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) val[j] = clip_pixel(r.fb, k.row0, k.row1, k.c0[j], k.c1[j], k.fx[j], k.fy, c, C, mean_invstd);
+            float* oc = out + (long long)c * Ho * Wo;
+            if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(oc) = f32x4{val[0], val[1], val[2], val[3]};
+            else oc[0] = val[0];
         }
     }
 }
@@ -529,6 +573,26 @@ extern "C" int hyb_clips_u8_transform_mix(const unsigned char* src, const int* p
                            Hin, Win, C, Tout, Ho, Wo);
     else
         hipLaunchKernelGGL(clips_u8_transform_mix_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mix, mean_invstd, dst, frames, B, Tin,
+                           Hin, Win, C, Tout, Ho, Wo);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int hyb_clips_u8_transform_views(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int V, int Tin,
+                                            int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream) {
+    HYB_CHECK_ARG(src && params && dst && B > 0 && V >= 1 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Ho > 0 && Wo > 0);
+    HYB_CHECK_ARG(C <= 4 && Hin <= 16384 && Win <= 16384 && Ho <= 16384 && Wo <= 16384);
+    HYB_CHECK_ARG((long long)B * V <= 2147483647LL);                  // the output clips are counted in int like the plain kernel's
+    const long long frames = (long long)B * V * Tout;
+    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
+    const bool vec = Wo % 4 == 0 && ((unsigned long long)dst & 15) == 0;
+    const int per_frame = Ho * (vec ? Wo / 4 : Wo);
+    const dim3 grid(hyb_cdiv(per_frame, 256), gy);
+    if (vec)
+        hipLaunchKernelGGL(clips_u8_transform_views_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, V, Tin,
+                           Hin, Win, C, Tout, Ho, Wo);
+    else
+        hipLaunchKernelGGL(clips_u8_transform_views_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, V, Tin,
                            Hin, Win, C, Tout, Ho, Wo);
     HYB_LAUNCH_CHECK();
     return 0;

@@ -30,6 +30,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::clip_transform_mix   ... with Mixup / CutMix against a partner clip in the same pass   (one more int32 row per clip)
     hybrid::clip_transform_photo ... with colour jitter, grayscale, Gaussian noise and random erasing too   (one int32 row of 16 per clip)
     hybrid::clip_luma_sums       integer luma sums of the source crops: the contrast pivot of clip_transform_photo
+    hybrid::clip_transform_views V evaluation views (windows x crops) of every source clip in one launch: V rows per clip, the source read in place
     hybrid::eval_metrics_    one launch behind the logits that adds loss, top-1 / top-k, confusion matrix into a meter's state (no autograd formula)
 """
 import ctypes
@@ -1007,6 +1008,44 @@ def clip_transform_fake(src, params, mean_invstd, Tout, Ho, Wo):
     return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
 
 
+def _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo):
+    if src.dim() != 5 or src.dtype != torch.uint8:
+        raise TypeError("hybrid::clip_transform_views reads uint8 clips [B,Tin,Hin,Win,C]")
+    B, Tin, Hin, Win, C = src.shape
+    if V < 1 or B * V > 2 ** 31 - 1:
+        raise ValueError(f"hybrid::clip_transform_views needs V >= 1 and B * V within int32, got V = {V} for {B} clips")
+    if params.dtype != torch.int32 or tuple(params.shape) != (B * V, 8):
+        raise TypeError(f"params must be int32 [{B * V},8]: V = {V} adjacent rows {{y0, x0, ch, cw, flip, t0, tstride, 0}} per source clip")
+    if mean_invstd is not None and (mean_invstd.dtype != torch.float32 or tuple(mean_invstd.shape) != (2, C)):
+        raise TypeError(f"mean_invstd must be float32 [2,{C}]: mean, then 1/std")
+    if C > 4 or max(Hin, Win, Ho, Wo) > 16384 or min(B, Tin, Hin, Win, C, Tout, Ho, Wo) <= 0:
+        raise ValueError("hybrid::clip_transform_views needs C <= 4, extents > 0 and Hin, Win, Ho, Wo <= 16384")
+    return B, Tin, Hin, Win, C
+
+
+def clip_transform_views_op(src: Tensor, params: Tensor, mean_invstd: Optional[Tensor], V: int, Tout: int, Ho: int, Wo: int) -> Tensor:
+    """uint8 [B,Tin,Hin,Win,C] -> fp32 [B*V,Tout,C,Ho,Wo]: output clip b*V + v is hybrid::clip_transform's for row b*V + v applied to source
+    clip b, bit for bit (hyb_clips_u8_transform_views in include/hybrid_hip.h) -- the row order ClassificationMeter's views=V scores."""
+    _require_cuda(src, params, mean_invstd)
+    B, Tin, Hin, Win, C = _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo)
+    out = torch.empty(B * V, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
+    lib.call("hyb_clips_u8_transform_views", src.contiguous(), params.contiguous(), None if mean_invstd is None else mean_invstd.contiguous(), out,
+             B, int(V), Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
+    return out
+
+
+def clip_transform_views_fake(src, params, mean_invstd, V, Tout, Ho, Wo):
+    B, Tin, Hin, Win, C = _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo)
+    return src.new_empty((B * V, Tout, C, Ho, Wo), dtype=torch.float32)
+
+
+def clip_transform_views(src, params, mean_invstd, V, Tout, Ho, Wo):
+    """V evaluation views of every source clip in one launch: src uint8 [B,Tin,Hin,Win,C], params int32 [B*V,8] (ClipTransform.sample_views: V
+    adjacent rows per clip), mean_invstd fp32 [2,C] or None -> fp32 [B*V,Tout,C,Ho,Wo], equal to clip_transform on src.repeat_interleave(V, 0)
+    without that copy: what model.evaluate(x, y, meter, views=V) takes beside labels [B]."""
+    return torch.ops.hybrid.clip_transform_views(src, params, mean_invstd, int(V), int(Tout), int(Ho), int(Wo))
+
+
 def clip_transform(src, params, mean_invstd, Tout, Ho, Wo):
     """The device leg of ClipTransform on its own: src uint8 [B,Tin,Hin,Win,C], params int32 [B,8] (ClipTransform.sample), mean_invstd fp32
     [2,C] or None -> fp32 [B,Tout,C,Ho,Wo] on the current stream (hybrid::clip_transform checks devices, dtypes and shapes)."""
@@ -1641,6 +1680,9 @@ _LIB.impl("clip_transform_mix", _inference_only("clip_transform_mix"), "Autograd
 _define("clip_transform_photo", "(Tensor src, Tensor params, Tensor? mix, Tensor photo, Tensor? luma_sums, Tensor? mean_invstd, int Tout, int Ho, int Wo) "
         "-> Tensor", clip_transform_photo_op, clip_transform_photo_fake)
 _LIB.impl("clip_transform_photo", _inference_only("clip_transform_photo"), "Autograd")
+_define("clip_transform_views", "(Tensor src, Tensor params, Tensor? mean_invstd, int V, int Tout, int Ho, int Wo) -> Tensor", clip_transform_views_op,
+        clip_transform_views_fake)
+_LIB.impl("clip_transform_views", _inference_only("clip_transform_views"), "Autograd")
 _define("clip_luma_sums", "(Tensor src, Tensor params, int Tout) -> Tensor", clip_luma_sums_op, clip_luma_sums_fake)
 _LIB.impl("clip_luma_sums", _inference_only("clip_luma_sums"), "Autograd")
 _define("temporal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, int B, int dt, "
