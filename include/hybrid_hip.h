@@ -602,6 +602,30 @@ int hyb_clips_u8_transform_views(const unsigned char* src /* [B][Tin][Hin][Win][
                                  float* dst               /* [B*V][Tout][C][Ho][Wo] fp32 */,
                                  int B, int V, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
 
+/* hyb_clips_u8_transform_aa: the antialiased resize, torchvision's Resize(antialias=True) (new symbol, hyb_abi_version() stays 9).  Rows, views
+ * and layouts are hyb_clips_u8_transform_views': V rows {y0, x0, ch, cw, flip, t0, tstride, 0} per SOURCE clip, output clip r = b*V + v from row r
+ * and the bytes of clip b = r / V; V == 1 is the training / single-view case.  The clamps of a row, the temporal index ts and the flip
+ * (oxs = flip ? Wo-1-ox : ox: output column ox takes the value of column Wo-1-ox) are hyb_clips_u8_transform's.  Only the resampling differs.
+ * Per axis, a crop of n source positions resampled to m output positions (n = ch, m = Ho for rows; n = cw, m = Wo for columns), for output
+ * index i and source index k in [0, n), all in int32 (the largest value is about 2 * 16384^2):
+ *   D = 2*max(n, m);   W(i,k) = max(0, D - |(2k+1)*m - (2i+1)*n|);   S(i) = sum_k W(i,k)
+ *   v   = sum_ky sum_kx Wy(oy,ky) * Wx(oxs,kx) * (float) src[b][ts][y0+ky][x0+kx][c] / (Sy(oy) * Sx(oxs))
+ *   out = v / 255.0f;           if (mean_invstd) out = (out - mean[c]) * invstd[c]
+ * For n > m that is F.interpolate(crop, (Ho,Wo), mode="bilinear", align_corners=False, antialias=True): a triangle filter of support n/m,
+ * renormalised at the borders, at most 2*ceil(n/m)+1 taps.  For n <= m there are at most two taps with the weights (1-f, f) of
+ * hyb_clips_u8_transform's rule, its border clamp expressed as renormalisation (what torch does with antialias=True when up-scaling).
+ * Evaluation order in fp32: each weight is the correctly rounded quotient float(W) / float(S); the columns are summed first, the rows second,
+ * each sum a chain of fused multiply-adds in ascending k.  Two consequences are part of the contract:
+ *   - ch == Ho and cw == Wo (one tap of weight exactly 1 per axis): the bits of hyb_clips_u8_transform for that row, with and without mean_invstd
+ *   - n == 2m on both axes (interior weights (1,3,3,1)/8): an element whose windows are not clipped by a border is fp32(N/64) / 255, N the integer
+ *     weighted sum -- every partial sum is exact
+ * Same limits as hyb_clips_u8_transform_views: V >= 1, B*V within int, C <= 4, Hin, Win, Ho, Wo <= 16384. */
+int hyb_clips_u8_transform_aa(const unsigned char* src /* [B][Tin][Hin][Win][C] uint8 */,
+                              const int* params        /* device, [B*V][8] int32: V rows per SOURCE clip, adjacent */,
+                              const float* mean_invstd /* device, [2][C]: mean then 1/std; or NULL = no normalisation */,
+                              float* dst               /* [B*V][Tout][C][Ho][Wo] fp32 */,
+                              int B, int V, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
+
 /* hyb_clips_u8_transform_photo: the same pass with colour jitter, grayscale, Gaussian noise and random erasing, with or without mixing (new
  * symbols, hyb_abi_version() stays 9).  `photo`: one more int32 row of 16 per clip, in device memory; every field is clamped by the kernel:
  *   [0] [1] [2]  brightness, contrast, saturation factor (fp32 bits): !(f >= 0) (NaN included) counts as 1, values above 16 as 16; a factor of

@@ -22,6 +22,8 @@ the value that pass already holds in a register (``hyb_clips_u8_transform_photo`
 Multi-view evaluation (``ClipTransform(train=False, eval_views=(K, S), eval_crop=..., eval_flip=...)``): K temporal windows x S spatial crops of
 every clip come out of ONE launch (``hyb_clips_u8_transform_views``) that reads each source clip in place, V parameter rows per clip -- the bytes
 cross PCIe once, and the rows are in the order ``ClassificationMeter.update(..., views=V)`` scores.
+The antialiased resize (``ClipTransform(antialias=True)``, ``hyb_clips_u8_transform_aa``): the same rows, training or evaluation, resampled with
+torchvision's ``Resize(antialias=True)`` filter -- a separable triangle filter through LDS instead of two taps per axis.
 """
 import csv
 import os
@@ -98,7 +100,9 @@ class ClipPipeline:
     An evaluation transform with ``transform.views`` = V > 1: the source bytes are staged and copied once, [B,Tin,Hin,Win,C]; V parameter rows
     per clip (``transform.sample_views``) travel with them, hyb_clips_u8_transform_views is the one kernel, and what is yielded is
     (x fp32 [B*V,Tout,C,Ho,Wo], y int64 [B]) -- what ``model.evaluate(x, y, meter, views=V)`` and ``GraphedEval(..., views=V)`` take.
-    ``pipeline.views`` is V (1 without a transform)."""
+    ``pipeline.views`` is V (1 without a transform).
+    A transform with ``antialias=True``: hyb_clips_u8_transform_aa is the one kernel, for the training rows (V = 1) and the evaluation views alike;
+    the rows and what is yielded do not change."""
 
     def __init__(self, source, device="cuda", depth=2, transform=None):
         self.source, self.depth, self.transform = source, max(1, int(depth)), transform
@@ -191,6 +195,9 @@ class ClipPipeline:
                         lib.call("hyb_clips_u8_luma_sums", s["dev_u8"], s["dev_p"], s["luma"], B, T, H, W, C, Tout, self.stream.cuda_stream)
                     lib.call("hyb_clips_u8_transform_photo", s["dev_u8"], s["dev_p"], s["dev_m"] if mixing else None, s["dev_ph"], s.get("luma"),
                              self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho, Wo, self.stream.cuda_stream)
+                elif self.transform.antialias:
+                    lib.call("hyb_clips_u8_transform_aa", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, views, T, H, W, C, Tout, Ho, Wo,
+                             self.stream.cuda_stream)
                 elif views > 1:
                     lib.call("hyb_clips_u8_transform_views", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, views, T, H, W, C, Tout, Ho, Wo,
                              self.stream.cuda_stream)
@@ -233,7 +240,7 @@ class ClipTransform:
     """Per-clip augmentation parameters for the device kernel ``hyb_clips_u8_transform`` (torchvision's ``RandomResizedCrop(size, scale,
     ratio)`` + ``RandomHorizontalFlip(hflip)`` + ``Normalize(mean, std)`` + a temporal window of ``frames`` frames, applied to all frames
     of a clip alike).  The host only draws one row ``{y0, x0, ch, cw, flip, t0, tstride, 0}`` per clip; the pixels are resampled on the
-    device with ``F.interpolate(mode="bilinear", align_corners=False, antialias=False)`` arithmetic (no antialias filter).
+    device with ``F.interpolate(mode="bilinear", align_corners=False, antialias=False)`` arithmetic (``antialias=True`` below: with the filter).
 
     size          output (Ho, Wo), or one int for a square
     scale, ratio  RandomResizedCrop's area fraction and aspect-ratio (w / h) ranges              (train=True)
@@ -268,12 +275,17 @@ class ClipTransform:
     eval_flip     every view is followed by its horizontally flipped twin
                   An axis without slack gives coinciding views (S = 3 of a square source at eval_crop = 1: three times the same crop); that is
                   allowed.  All three are for train=False: a non-default value with train=True raises
+    antialias     True: the resize is torchvision's ``Resize(antialias=True)`` -- ``F.interpolate(..., antialias=True)``'s triangle filter, whose
+                  support grows with the down-scale -- for training rows and evaluation views alike (hyb_clips_u8_transform_aa); what to use
+                  when the source is more than about 2 x the output ("resize 256, crop 224" from a 720-line decoder).  The rows do not change:
+                  ``sample`` / ``sample_views`` of a seed are the same with it on and off.  Not provided together with mixing or the photometric
+                  options (raises).  False, the default: the kernels, draws and bits are what they were
     """
 
     def __init__(self, size, scale=(0.35, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, mean=None, std=None, frames=None, frame_stride=(1, 1), seed=0,
                  train=True, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, switch_prob=0.5, mix_mode="batch", brightness=0.0, contrast=0.0, saturation=0.0, jitter_prob=1.0,
                  grayscale=0.0, noise_std=0.0, noise_prob=1.0, erase_prob=0.0, erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), erase_mode="zero",
-                 eval_views=(1, 1), eval_crop=1.0, eval_flip=False):
+                 eval_views=(1, 1), eval_crop=1.0, eval_flip=False, antialias=False):
         self.size = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
         if min(self.size) <= 0:
             raise ValueError(f"size must be positive, got {size!r}")
@@ -338,6 +350,10 @@ class ClipTransform:
             raise ValueError("eval_views, eval_crop and eval_flip describe the evaluation transform: they need train=False")
         if self.eval_views[0] > 1 and self.frames is None:
             raise ValueError("eval_views with K > 1 temporal windows needs frames=: without it every window is the whole clip")
+        self.antialias = bool(antialias)
+        if self.antialias and (self.mixing() or self.photometric()):
+            raise ValueError("antialias=True together with Mixup / CutMix or the photometric options is not provided: the antialiased resize has "
+                             "no mix or photo kernel")
 
     ERASE_MODES = ("zero", "black", "pixel")
 

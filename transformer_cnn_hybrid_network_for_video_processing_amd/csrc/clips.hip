@@ -17,6 +17,8 @@
 // Four launches share the rule: the plain kernel, the mix kernel (Mixup / CutMix), the photo kernel (colour jitter, noise, erasing) and the
 // views kernel (V evaluation views of every source clip, hyb_clips_u8_transform_views).  The plain, mix, photo and luma kernels are to keep
 // their instruction schedules: a new variant is a new kernel built from clip_row / clip_taps / clip_pixel, not a change to one of them.
+// The antialiased resize (hyb_clips_u8_transform_aa, at the end of the file) has a rule and an access pattern of its own: a separable triangle
+// filter through LDS, with barriers.
 #include "hyb_common.h"
 
 namespace {
@@ -630,6 +632,227 @@ extern "C" int hyb_clips_u8_luma_sums(const unsigned char* src, const int* param
     const dim3 grid(hyb_cdiv(Hin, LUMA_SPLIT_ROWS), gy);
     hipLaunchKernelGGL(clips_u8_luma_sums_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, params, reinterpret_cast<unsigned long long*>(sums), frames,
                        Tin, Hin, Win, C, Tout);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- Antialiased resize (hyb_clips_u8_transform_aa; include/hybrid_hip.h has the rule in full): torchvision's Resize(antialias=True), i.e.
+// F.interpolate(bilinear, align_corners=False, antialias=True).  The kernels above stay as they were written; this one takes clip_row (the clamps,
+// the temporal index, the flip) and the views kernel's frame walk from them and nothing else.  Per axis, n crop positions -> m output positions:
+//   D = 2 max(n, m);   W(i, k) = max(0, D - |(2k + 1) m - (2i + 1) n|);   S(i) = sum_k W(i, k)          all int32 (<= 2 * 16384^2)
+//   out = sum_ky sum_kx (Wy / Sy) (Wx / Sx) a[ky][kx], then / 255 and (x - mean) * invstd as clip_pixel writes them
+// A weight is the correctly rounded QUOTIENT float(W) / float(S) of two integers (W <= 2^15 is exact in fp32): 1.0f for the single tap of an
+// identity axis and 1/8, 3/8 for n == 2m, so identity rows give the plain kernel's bits and a 2 x down-scale is exact (tests/test_gpu_antialias.py).
+// The filter is separable and a down-scale by s has about 2s taps per axis, so the pixels are NOT gathered (4 s^2 bytes each).  A workgroup owns
+// AA_TH x TW output pixels of one output frame (TW = AA_QW * VEC) and walks the source rows its tile needs -- a workgroup-uniform span from the
+// integer rule, about (AA_TH + 2) n / m rows -- in chunks of AA_R rows:
+//   phase 1  lane = (output column, row group): the taps of a column are count * C contiguous bytes of an HWC row; the lane forms each weight once
+//            and uses it for its AA_R / RG rows of the chunk, C fp32 sums per row, written to LDS as [row][c][column]
+//   barrier
+//   phase 2  lane = (output row, VEC columns): adds wy(row) * LDS[row][c][columns] for the chunk rows inside its row's window into VEC x C
+//            registers; neighbouring lanes read neighbouring 16 bytes
+//   barrier  (the next chunk's, or the next frame's, phase 1 overwrites the LDS)
+// LDS is AA_R * 4 * TW * 4 B = 32 KiB (VEC = 4) whatever the scale.  Why LDS: the horizontal sums of a source row are shared by every output row
+// whose window holds it (2 for an up-scale, 2 n / m otherwise), and those rows belong to different lanes.
+// NO lane returns before the last barrier: lanes outside a partial tile stay in every loop and skip their loads and stores.  The frame loop and the
+// chunk loop are bounded by blockIdx, the clip's row and the extents only -- workgroup-uniform.
+constexpr int AA_TH = 32;            // output rows of a tile
+constexpr int AA_QW = 8;             // lanes along a tile's output row: AA_TH * AA_QW = 256, the tile is AA_QW * VEC columns wide
+constexpr int AA_R = 64;             // source rows of a chunk
+static_assert(AA_TH * AA_QW == 256, "one lane per (output row, VEC columns) of a tile");
+
+namespace {
+// The window of output position i: the source positions k with W(i, k) > 0, clipped to [0, n - 1].  Never empty: the open interval of half-width
+// D / (2m) >= 1 around the centre (2i + 1) n / (2m) - 1/2, which lies in (-1/2, n - 1/2), holds the integer next to the centre.
+__device__ __forceinline__ int aa_lo(int i, int n, int m, int D) {
+    const int num = (2 * i + 1) * n - D - m;                         // k > num / (2m)
+    return num < 0 ? 0 : (int)((unsigned)num / (2u * m)) + 1;
+}
+__device__ __forceinline__ int aa_hi(int i, int n, int m, int D) {
+    const unsigned num = (unsigned)((2 * i + 1) * n + D - m - 1);    // k < (num + 1) / (2m); positive: D >= 2m
+    return min((int)(num / (2u * m)), n - 1);
+}
+// W(i, k) with ci = (2i + 1) n; positive for every k of the window
+__device__ __forceinline__ int aa_weight(int k, int m, int ci, int D) {
+    const int v = (2 * k + 1) * m - ci;
+    return D - (v < 0 ? -v : v);
+}
+__device__ __forceinline__ int aa_sum(int lo, int hi, int m, int ci, int D) {
+    int s = 0;
+    for (int k = lo; k <= hi; ++k) s += aa_weight(k, m, ci, D);
+    return s;
+}
+
+// Phase 1 for one lane: the horizontal sums h[j][c] of its RPL chunk rows (row j at byte offset ro[j] from the crop's origin, inside the tile's span
+// while RG * j < nrows) over the taps kx_lo .. kx_hi of its output column, a crop row being n positions wide.  The taps of a column are contiguous
+// bytes of a row.  They are read in groups of TG whole positions = G 32-bit words (CC = 3: 4 positions in 3 words) at the bytes' own, in general
+// unaligned, address.  The groups start at kx_lo, or further left where they would otherwise pass the end of the crop's row: every byte read is a
+// byte of the crop.  A position of a group outside the window has the rule's weight max(0, .) = 0, and fmaf(0, a, h) is h, bit for bit: every sum
+// is the fmaf chain over the window in ascending k.  A crop narrower than the groups is read one byte at a time.
+template <int CC, int RPL, int RG>
+__device__ __forceinline__ void aa_hsums(float (&h)[RPL][4], const unsigned char* __restrict__ crop, const unsigned (&ro)[RPL], int nrows, int kx_lo,
+                                         int kx_hi, int n, int m, int cx, int D, float sx) {
+    constexpr int TG = CC == 3 ? 4 : 4 / CC, G = TG * CC / 4;
+    const int ng = (kx_hi - kx_lo + TG) / TG;                         // groups that cover the window
+    int k = min(kx_lo, n - ng * TG);                                   // ... moved left where they would leave the crop's row
+    const int k_end = k < 0 ? kx_lo : k + ng * TG;                     // a crop narrower than the groups: every tap by bytes
+    if (k < 0) k = kx_lo;
+    for (; k < k_end; k += TG) {
+        float w[TG];
+#pragma unroll
+        for (int i = 0; i < TG; ++i) w[i] = (float)max(aa_weight(k + i, m, cx, D), 0) / sx;      // a quotient, not a product with 1 / sx: 1.0f stays 1.0f
+        const unsigned ko = (unsigned)(k * CC);
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) {
+            if (RG * j >= nrows) continue;                             // past the tile's span (and possibly past the crop): not read
+            unsigned d[G];
+            __builtin_memcpy(d, crop + ro[j] + ko, 4 * G);
+#pragma unroll
+            for (int i = 0; i < TG * CC; ++i) h[j][i % CC] = fmaf(w[i / CC], (float)((d[i >> 2] >> (8 * (i & 3))) & 0xffu), h[j][i % CC]);
+        }
+    }
+    for (; k <= kx_hi; ++k) {
+        const float w = (float)aa_weight(k, m, cx, D) / sx;
+        const unsigned ko = (unsigned)(k * CC);
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) {
+            if (RG * j >= nrows) continue;
+#pragma unroll
+            for (int c = 0; c < CC; ++c) h[j][c] = fmaf(w, (float)crop[ro[j] + ko + c], h[j][c]);
+        }
+    }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void clips_u8_transform_aa_kernel(const unsigned char* __restrict__ src, const int* __restrict__ params,
+                                                                    const float* __restrict__ mean_invstd, float* __restrict__ dst, long long frames,
+                                                                    int V, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo) {
+    constexpr int TW = AA_QW * VEC;          // output columns of a tile
+    constexpr int RG = 256 / TW;             // phase 1: lanes per column, each takes the chunk rows rg, rg + RG, ...
+    constexpr int RPL = AA_R / RG;           // ... RPL of them
+    static_assert(RG * TW == 256 && RPL * RG == AA_R, "phase 1 covers the chunk exactly");
+    __shared__ __attribute__((aligned(16))) float hsum[AA_R * 4 * TW];      // [row][c][column]
+    const int tid = threadIdx.x;
+    const int tiles_x = (Wo + TW - 1) / TW;
+    const int ty = (int)(blockIdx.x / (unsigned)tiles_x), tx = (int)blockIdx.x - ty * tiles_x;
+    const int oy_first = ty * AA_TH, oy_last = min(oy_first + AA_TH, Ho) - 1;      // the tile's output rows: workgroup-uniform
+    // phase 2 and the store: this lane's output row and VEC columns
+    const int oxl = (tid % AA_QW) * VEC, oy = oy_first + tid / AA_QW, ox0 = tx * TW + oxl;
+    const bool out_ok = oy < Ho && ox0 < Wo;                                       // (VEC == 4 only with Wo % 4 == 0: the whole quad is inside)
+    // phase 1: this lane's output column and row group
+    const int col = tid % TW, rg = tid / TW, oxc = tx * TW + col;
+    const bool col_ok = oxc < Wo;
+    const long long frame_bytes = (long long)Hin * Win * C;
+    for (long long g = blockIdx.y; g < frames; g += gridDim.y) {
+        // the views kernel's walk: position g is (b, t, v) with v fastest
+        const long long bt = g / V;
+        const int v = (int)(g - bt * V);
+        const long long b = bt / Tout;
+        const int t = (int)(bt - b * Tout);
+        const long long row = b * V + v;
+        const ClipRow r = clip_row(src, params + (row - b) * 8, b, t, Tin, Hin, Win, frame_bytes);
+        const unsigned char* crop = r.fb + ((long long)r.y0 * Win + r.x0) * C;      // offsets from here stay below 2^30
+        const int Dy = 2 * max(r.ch, Ho), Dx = 2 * max(r.cw, Wo);
+        const int span_lo = aa_lo(oy_first, r.ch, Ho, Dy), span_hi = aa_hi(oy_last, r.ch, Ho, Dy);      // source rows of the tile: workgroup-uniform
+
+        const int oxs = col_ok ? (r.flip ? Wo - 1 - oxc : oxc) : 0;
+        const int cx = (2 * oxs + 1) * r.cw;
+        const int kx_lo = aa_lo(oxs, r.cw, Wo, Dx), kx_hi = aa_hi(oxs, r.cw, Wo, Dx);
+        const float sx = (float)aa_sum(kx_lo, kx_hi, Wo, cx, Dx);
+
+        const int oyc = out_ok ? oy : oy_first;
+        const int cy = (2 * oyc + 1) * r.ch;
+        const int ky_lo = aa_lo(oyc, r.ch, Ho, Dy), ky_hi = out_ok ? aa_hi(oyc, r.ch, Ho, Dy) : -1;      // an empty window for a lane without a pixel
+        const float sy = (float)aa_sum(ky_lo, aa_hi(oyc, r.ch, Ho, Dy), Ho, cy, Dy);
+
+        float o[4][VEC];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) o[c][j] = 0.f;
+        }
+        for (int c0 = span_lo; c0 <= span_hi; c0 += AA_R) {
+            // ---- phase 1: horizontal sums of chunk rows c0 + rg + RG j for output column oxc
+            float h[RPL][4];
+            unsigned ro[RPL];
+#pragma unroll
+            for (int j = 0; j < RPL; ++j) {
+                ro[j] = (unsigned)((c0 + rg + RG * j) * Win) * (unsigned)C;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) h[j][c] = 0.f;
+            }
+            if (col_ok) {
+                const int nrows = span_hi - (c0 + rg) + 1;                         // rows j with RG * j < nrows are inside the tile's span
+                if (C == 3) aa_hsums<3, RPL, RG>(h, crop, ro, nrows, kx_lo, kx_hi, r.cw, Wo, cx, Dx, sx);
+                else if (C == 1) aa_hsums<1, RPL, RG>(h, crop, ro, nrows, kx_lo, kx_hi, r.cw, Wo, cx, Dx, sx);
+                else if (C == 4) aa_hsums<4, RPL, RG>(h, crop, ro, nrows, kx_lo, kx_hi, r.cw, Wo, cx, Dx, sx);
+                else aa_hsums<2, RPL, RG>(h, crop, ro, nrows, kx_lo, kx_hi, r.cw, Wo, cx, Dx, sx);
+            }
+#pragma unroll
+            for (int j = 0; j < RPL; ++j) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (c >= C) break;
+                    hsum[((rg + RG * j) * 4 + c) * TW + col] = h[j][c];
+                }
+            }
+            __syncthreads();
+            // ---- phase 2: the chunk rows inside this lane's window
+            const int lo = max(c0, ky_lo), hi = min(c0 + AA_R - 1, ky_hi);
+            for (int k = lo; k <= hi; ++k) {
+                const float w = (float)aa_weight(k, Ho, cy, Dy) / sy;
+                const float* hp = hsum + (k - c0) * 4 * TW + oxl;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (c >= C) break;
+                    if constexpr (VEC == 4) {
+                        const f32x4 x = *reinterpret_cast<const f32x4*>(hp + c * TW);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) o[c][j] = fmaf(w, x[j], o[c][j]);
+                    } else {
+                        o[c][0] = fmaf(w, hp[c * TW], o[c][0]);
+                    }
+                }
+            }
+            __syncthreads();                                                       // the LDS is free for the next chunk or frame
+        }
+        if (out_ok) {
+            float* out = dst + ((row * Tout + t) * C * Ho + oy) * (long long)Wo + ox0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (c >= C) break;
+                float val[VEC];
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    float q = o[c][j] / 255.0f;                                    // ToTensor divides by 255 (not a multiply by 1/255)
+                    if (mean_invstd) q = (q - mean_invstd[c]) * mean_invstd[C + c];
+                    val[j] = q;
+                }
+                float* oc = out + (long long)c * Ho * Wo;
+                if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(oc) = f32x4{val[0], val[1], val[2], val[3]};
+                else oc[0] = val[0];
+            }
+        }
+    }
+}
+}  // namespace
+
+extern "C" int hyb_clips_u8_transform_aa(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int V, int Tin, int Hin,
+                                         int Win, int C, int Tout, int Ho, int Wo, void* stream) {
+    HYB_CHECK_ARG(src && params && dst && B > 0 && V >= 1 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Ho > 0 && Wo > 0);
+    HYB_CHECK_ARG(C <= 4 && Hin <= 16384 && Win <= 16384 && Ho <= 16384 && Wo <= 16384);      // the rule's integer products stay below 2^31
+    HYB_CHECK_ARG((long long)B * V <= 2147483647LL);
+    const long long frames = (long long)B * V * Tout;
+    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
+    const bool vec = Wo % 4 == 0 && ((unsigned long long)dst & 15) == 0;
+    const int tw = AA_QW * (vec ? 4 : 1);
+    const dim3 grid(hyb_cdiv(Ho, AA_TH) * hyb_cdiv(Wo, tw), gy);                                  // <= 512 * 2048 tiles
+    if (vec)
+        hipLaunchKernelGGL(clips_u8_transform_aa_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, V, Tin, Hin,
+                           Win, C, Tout, Ho, Wo);
+    else
+        hipLaunchKernelGGL(clips_u8_transform_aa_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, V, Tin, Hin,
+                           Win, C, Tout, Ho, Wo);
     HYB_LAUNCH_CHECK();
     return 0;
 }

@@ -31,6 +31,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::clip_transform_photo ... with colour jitter, grayscale, Gaussian noise and random erasing too   (one int32 row of 16 per clip)
     hybrid::clip_luma_sums       integer luma sums of the source crops: the contrast pivot of clip_transform_photo
     hybrid::clip_transform_views V evaluation views (windows x crops) of every source clip in one launch: V rows per clip, the source read in place
+    hybrid::clip_transform_aa    clip_transform_views with the antialiased resize (torchvision's Resize(antialias=True)): a separable triangle filter
     hybrid::eval_metrics_    one launch behind the logits that adds loss, top-1 / top-k, confusion matrix into a meter's state (no autograd formula)
 """
 import ctypes
@@ -1008,18 +1009,18 @@ def clip_transform_fake(src, params, mean_invstd, Tout, Ho, Wo):
     return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
 
 
-def _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo):
+def _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo, op="clip_transform_views"):
     if src.dim() != 5 or src.dtype != torch.uint8:
-        raise TypeError("hybrid::clip_transform_views reads uint8 clips [B,Tin,Hin,Win,C]")
+        raise TypeError(f"hybrid::{op} reads uint8 clips [B,Tin,Hin,Win,C]")
     B, Tin, Hin, Win, C = src.shape
     if V < 1 or B * V > 2 ** 31 - 1:
-        raise ValueError(f"hybrid::clip_transform_views needs V >= 1 and B * V within int32, got V = {V} for {B} clips")
+        raise ValueError(f"hybrid::{op} needs V >= 1 and B * V within int32, got V = {V} for {B} clips")
     if params.dtype != torch.int32 or tuple(params.shape) != (B * V, 8):
         raise TypeError(f"params must be int32 [{B * V},8]: V = {V} adjacent rows {{y0, x0, ch, cw, flip, t0, tstride, 0}} per source clip")
     if mean_invstd is not None and (mean_invstd.dtype != torch.float32 or tuple(mean_invstd.shape) != (2, C)):
         raise TypeError(f"mean_invstd must be float32 [2,{C}]: mean, then 1/std")
     if C > 4 or max(Hin, Win, Ho, Wo) > 16384 or min(B, Tin, Hin, Win, C, Tout, Ho, Wo) <= 0:
-        raise ValueError("hybrid::clip_transform_views needs C <= 4, extents > 0 and Hin, Win, Ho, Wo <= 16384")
+        raise ValueError(f"hybrid::{op} needs C <= 4, extents > 0 and Hin, Win, Ho, Wo <= 16384")
     return B, Tin, Hin, Win, C
 
 
@@ -1044,6 +1045,29 @@ def clip_transform_views(src, params, mean_invstd, V, Tout, Ho, Wo):
     adjacent rows per clip), mean_invstd fp32 [2,C] or None -> fp32 [B*V,Tout,C,Ho,Wo], equal to clip_transform on src.repeat_interleave(V, 0)
     without that copy: what model.evaluate(x, y, meter, views=V) takes beside labels [B]."""
     return torch.ops.hybrid.clip_transform_views(src, params, mean_invstd, int(V), int(Tout), int(Ho), int(Wo))
+
+
+def clip_transform_aa_op(src: Tensor, params: Tensor, mean_invstd: Optional[Tensor], V: int, Tout: int, Ho: int, Wo: int) -> Tensor:
+    """uint8 [B,Tin,Hin,Win,C] -> fp32 [B*V,Tout,C,Ho,Wo] like hybrid::clip_transform_views, resampled with the antialias filter of
+    F.interpolate(bilinear, align_corners=False, antialias=True) (hyb_clips_u8_transform_aa in include/hybrid_hip.h has the rule)."""
+    _require_cuda(src, params, mean_invstd)
+    B, Tin, Hin, Win, C = _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo, "clip_transform_aa")
+    out = torch.empty(B * V, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
+    lib.call("hyb_clips_u8_transform_aa", src.contiguous(), params.contiguous(), None if mean_invstd is None else mean_invstd.contiguous(), out,
+             B, int(V), Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
+    return out
+
+
+def clip_transform_aa_fake(src, params, mean_invstd, V, Tout, Ho, Wo):
+    B, Tin, Hin, Win, C = _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo, "clip_transform_aa")
+    return src.new_empty((B * V, Tout, C, Ho, Wo), dtype=torch.float32)
+
+
+def clip_transform_aa(src, params, mean_invstd, V, Tout, Ho, Wo):
+    """clip_transform_views with the antialiased resize (ClipTransform(antialias=True)): src uint8 [B,Tin,Hin,Win,C], params int32 [B*V,8] (V adjacent
+    rows per clip from ClipTransform.sample_views, or V = 1 and the rows of ClipTransform.sample), mean_invstd fp32 [2,C] or None -> fp32
+    [B*V,Tout,C,Ho,Wo].  Rows with ch == Ho and cw == Wo give clip_transform's bits."""
+    return torch.ops.hybrid.clip_transform_aa(src, params, mean_invstd, int(V), int(Tout), int(Ho), int(Wo))
 
 
 def clip_transform(src, params, mean_invstd, Tout, Ho, Wo):
@@ -1683,6 +1707,9 @@ _LIB.impl("clip_transform_photo", _inference_only("clip_transform_photo"), "Auto
 _define("clip_transform_views", "(Tensor src, Tensor params, Tensor? mean_invstd, int V, int Tout, int Ho, int Wo) -> Tensor", clip_transform_views_op,
         clip_transform_views_fake)
 _LIB.impl("clip_transform_views", _inference_only("clip_transform_views"), "Autograd")
+_define("clip_transform_aa", "(Tensor src, Tensor params, Tensor? mean_invstd, int V, int Tout, int Ho, int Wo) -> Tensor", clip_transform_aa_op,
+        clip_transform_aa_fake)
+_LIB.impl("clip_transform_aa", _inference_only("clip_transform_aa"), "Autograd")
 _define("clip_luma_sums", "(Tensor src, Tensor params, int Tout) -> Tensor", clip_luma_sums_op, clip_luma_sums_fake)
 _LIB.impl("clip_luma_sums", _inference_only("clip_luma_sums"), "Autograd")
 _define("temporal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, int B, int dt, "
