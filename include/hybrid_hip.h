@@ -344,6 +344,28 @@ int hyb_cross_entropy_mix_bwd(const float* logits, const long long* target, cons
                               const float* weight /* [C] or NULL */, long long ignore_index, int has_ignore, float label_smoothing,
                               const float* dloss /* [1] */, float* dlogits, int B, int C, void* stream);
 
+/* hyb_cross_entropy_dense_*: the loss on DENSE targets, one fp32 row target[b][0..C) per clip, reduction "mean", fp32 arithmetic (new
+ *   symbols, hyb_abi_version() stays 9).  z = logits, t = target, w = weight [C] >= 0 or NULL = all ones, lse_b = logsumexp(z_b).
+ *   kind 0, soft-target cross-entropy -- torch.nn.functional.cross_entropy(z, t, weight=w, label_smoothing=e) with class probabilities:
+ *     q_bc = (1 - e) t_bc + e / C,   loss = (1 / B) sum_b sum_c w_c q_bc (lse_b - z_bc),
+ *     dlogits[b,c] = (dloss / B) (softmax(z_b)_c P_b - w_c q_bc),   P_b = sum_k w_k q_bk.
+ *   The divisor is B, not a weight sum (torch's rule for probability targets; the index-target families divide by den).  Rows are used
+ *   as given: neither normalised nor range-checked, a NaN propagates.  A one-hot row with no weight and no smoothing gives
+ *   hyb_cross_entropy_* bit for bit.
+ *   kind 1, binary cross-entropy with logits -- torch.nn.functional.binary_cross_entropy_with_logits(z, t, weight=w, pos_weight=pw),
+ *   pw = pos_weight [C] >= 0 or NULL = all ones, in the overflow-safe form (z = +-100 gives a finite loss and gradient):
+ *     L_bc = 1 + (pw_c - 1) t_bc,   term_bc = w_c [ (1 - t_bc) z_bc + L_bc (log1p(exp(-|z_bc|)) + max(-z_bc, 0)) ],
+ *     loss = (1 / (B C)) sum_bc term_bc,   dlogits[b,c] = (dloss / (B C)) w_c (L_bc sigmoid(z_bc) - pw_c t_bc).
+ *   A clip's sum over classes runs in class order, the sum over clips goes through the fixed tree of the other families, the division is
+ *   taken once at the end: results are reproducible bit for bit.  HYB_E_ARG, without a launch: a NULL pointer (other than weight and
+ *   pos_weight), kind not 0 / 1, label_smoothing outside [0, 1] or non-zero with kind 1, pos_weight given with kind 0. */
+int hyb_cross_entropy_dense_fwd(const float* logits, const float* target /* [B,C] */, const float* weight /* [C] or NULL */,
+                                const float* pos_weight /* [C] or NULL */, int kind, float label_smoothing, float* loss /* [1] */, int B,
+                                int C, void* stream);
+int hyb_cross_entropy_dense_bwd(const float* logits, const float* target /* [B,C] */, const float* weight /* [C] or NULL */,
+                                const float* pos_weight /* [C] or NULL */, int kind, float label_smoothing, const float* dloss /* [1] */,
+                                float* dlogits, int B, int C, void* stream);
+
 /* hyb_eval_metrics: the update of an accumulating classification meter, ONE launch of one 256-thread workgroup behind the logits (new
  *   symbol, hyb_abi_version() stays 9).  It ADDS into sums, counts and confusion and overwrites none of them: repeated launches, and
  *   replays of a graph that holds the launch, accumulate; the caller zeroes the three before the first.  Launches on one stream are ordered
@@ -477,6 +499,26 @@ int hyb_temporal_ce_mix_bwd(int dtype, const float* dloss, const float* logits, 
                             float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
                             int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* hyb_temporal_ce_dense_*: hyb_temporal_ce_* with a dense target [B, classes] and the arguments of hyb_cross_entropy_dense_* (same
+ *   meaning, same argument checks) in place of the class indices: the same launches, the same B + 1 floats of ce_scratch under the same
+ *   rules, target, weight and pos_weight read when the kernels run -- a captured call replays with new targets.  Results equal
+ *   hyb_temporal_* followed by hyb_cross_entropy_dense_* bit for bit; shapes the fused tail does not take run hyb_cross_entropy_dense_*
+ *   as launches of their own.  (New symbols, hyb_abi_version() stays 9.) */
+int hyb_temporal_ce_dense_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                              const float* head_w, const float* head_b, const float* mask, const float* target /* [B,classes] */,
+                              const float* weight /* [classes] or NULL */, const float* pos_weight /* [classes] or NULL */, int kind,
+                              float label_smoothing, void* feat, void* tok, void* enc_saved, void* enc_out, float* logits, float* loss,
+                              float* ce_scratch, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes,
+                              float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc, void* stream);
+int hyb_temporal_ce_dense_bwd(int dtype, const float* dloss, const float* logits, const float* target /* [B,classes] */,
+                              const float* weight /* [classes] or NULL */, const float* pos_weight /* [classes] or NULL */, int kind,
+                              float label_smoothing, const float* token_w, const float* const* enc_params, const float* head_w,
+                              const float* mask, const void* feat, const void* enc_saved, const void* enc_out, float* dtoken_w,
+                              float* dtoken_b, float* const* enc_grads, float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW,
+                              int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
+                              unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* ---- FCT, the reference's "Fully Convolutional Transformer" (FCT.py:24-254; SURVEY.md section 8f-1, first "next" row) -----------
  * FORWARD entry points (the backward is the next step of this row).  Arrays are NHWC fp32 with the TRUE channel count

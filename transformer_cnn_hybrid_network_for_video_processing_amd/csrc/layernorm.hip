@@ -550,6 +550,80 @@ __global__ __launch_bounds__(256) void ce_mix_bwd_kernel(const float* __restrict
     for (int c = 0; c < C; ++c) dlogits[(long long)b * C + c] = ce_clip_dlogit_mix(logits + (long long)b * C, o.weight, ta, tc, l, C, c, g, o);
 }
 
+// ---- dense targets: one fp32 row t_b[0..C) per clip (include/hybrid_hip.h states both definitions) ----------------------------------------
+// kind 0, soft-target cross-entropy (torch's cross_entropy with class probabilities): q_c = (1 - e) t_c + e / C,
+//   term_b = sum_c w_c q_c (lse_b - z_c),  loss = (sum_b term_b) / B,  dz_c = (dloss / B) (p_c P_b - w_c q_c),  P_b = sum_k w_k q_k.
+// kind 1, binary cross-entropy with logits: L_c = 1 + (pw_c - 1) t_c,  sp(z) = log1p(exp(-|z|)) + max(-z, 0) (no overflow at any z),
+//   term_b = sum_c w_c [ (1 - t_c) z_c + L_c sp(z_c) ],  loss = (sum_b term_b) / (B C),  dz_c = (dloss / (B C)) w_c (L_c sigmoid(z_c) - pw_c t_c).
+// The sum over classes runs in class order from 0.f and every product that feeds a sum is an explicit fmaf, so a one-hot row with no weights
+// and no smoothing adds exact zeros and multiplies by exact ones: kind 0 then gives the bits of ce_clip_loss / ce_clip_dlogit.  The divisor is
+// B or B C, known on the host side of every kernel: no den pass.  Rows are used as given (not normalised, not range-checked; NaN propagates).
+__device__ __forceinline__ float ce_soft_q(float t, float e, int C) { return fmaf(1.f - e, t, e / (float)C); }
+__device__ __forceinline__ float ce_clip_loss_soft(const float* lg, const float* w, const float* t, int C, float e) {
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
+    float s = 0.f;
+    for (int c = 0; c < C; ++c) s += expf(lg[c] - mx);
+    const float lse = logf(s) + mx;
+    float r = 0.f;
+    for (int c = 0; c < C; ++c) r = fmaf(ce_w(w, c) * ce_soft_q(t[c], e, C), lse - lg[c], r);
+    return r;
+}
+// one clip's d(loss)/d(logits[c]), g = dloss / B
+__device__ __forceinline__ float ce_clip_dlogit_soft(const float* lg, const float* w, const float* t, int C, int c, float g, float e) {
+    float mx = -INFINITY;
+    for (int k = 0; k < C; ++k) mx = fmaxf(mx, lg[k]);
+    float s = 0.f;
+    for (int k = 0; k < C; ++k) s += expf(lg[k] - mx);
+    const float p = expf(lg[c] - mx) / s;
+    float P = 0.f;
+    for (int k = 0; k < C; ++k) P = fmaf(ce_w(w, k), ce_soft_q(t[k], e, C), P);
+    return g * fmaf(p, P, -(ce_w(w, c) * ce_soft_q(t[c], e, C)));
+}
+__device__ __forceinline__ float ce_clip_loss_bce(const float* lg, const float* w, const float* pw, const float* t, int C) {
+    float r = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float z = lg[c], tc = t[c];
+        const float L = fmaf(ce_w(pw, c) - 1.f, tc, 1.f);
+        const float sp = log1pf(expf(-fabsf(z))) + fmaxf(-z, 0.f);
+        r = fmaf(ce_w(w, c), fmaf(L, sp, (1.f - tc) * z), r);
+    }
+    return r;
+}
+// one clip's d(loss)/d(logits[c]), g = dloss / (B C)
+__device__ __forceinline__ float ce_clip_dlogit_bce(const float* lg, const float* w, const float* pw, const float* t, int c, float g) {
+    const float z = lg[c], tc = t[c], pwc = ce_w(pw, c);
+    const float L = fmaf(pwc - 1.f, tc, 1.f);
+    const float ez = expf(-fabsf(z));
+    const float sg = (z >= 0.f ? 1.f : ez) / (1.f + ez);
+    return g * (ce_w(w, c) * fmaf(L, sg, -(pwc * tc)));
+}
+__device__ __forceinline__ float ce_dense_div(int B, int C, int kind) { return kind == 1 ? (float)B * (float)C : (float)B; }
+
+__global__ __launch_bounds__(256) void ce_dense_fwd_kernel(const float* __restrict__ logits, float* __restrict__ loss, int B, int C, HybCeOpts o,
+                                                           HybCeDense d) {
+    __shared__ float part[256];
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const float* lg = logits + (long long)b * C;
+        const float* t = d.target + (long long)b * C;
+        acc += d.kind == 1 ? ce_clip_loss_bce(lg, o.weight, d.pos_weight, t, C) : ce_clip_loss_soft(lg, o.weight, t, C, o.label_smoothing);
+    }
+    const float num = ce_tree_sum(acc, part);
+    if (threadIdx.x == 0) loss[0] = num / ce_dense_div(B, C, d.kind);
+}
+__global__ __launch_bounds__(256) void ce_dense_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ dloss,
+                                                           float* __restrict__ dlogits, int B, int C, HybCeOpts o, HybCeDense d) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const float g = dloss[0] / ce_dense_div(B, C, d.kind);
+    const float* lg = logits + (long long)b * C;
+    const float* t = d.target + (long long)b * C;
+    for (int c = 0; c < C; ++c)
+        dlogits[(long long)b * C + c] = d.kind == 1 ? ce_clip_dlogit_bce(lg, o.weight, d.pos_weight, t, c, g)
+                                                    : ce_clip_dlogit_soft(lg, o.weight, t, C, c, g, o.label_smoothing);
+}
+
 // ---- the tail of the temporal part as ONE launch each way --------------------------------------------------------------------
 // forward: the last encoder layer's second LayerNorm (+ residual, scale, dropout: src L120-123) -> mean over the clip's tokens -> Linear
 // head -> (when a target is given) the clip's cross-entropy term, and the batch mean by the last workgroup to finish.  One workgroup per
@@ -567,7 +641,9 @@ __device__ __forceinline__ float head_logit(const float* pooled, const float* __
 // __global__ wrappers: read in here, outside a kernel, blockDim.x compiles to the general form (a select on the grid's remainder and a
 // 16-bit global load of the implicit arguments) in front of the first row request instead of one scalar load of the kernel argument block.
 // MODE 0: the plain loss; 1: with options (OPTS); 2: with options and two targets per clip (OPTS and MIX; `m`): every MIX line is compiled out of
-// the other two.
+// the other two.  MODE 3 / 4: a dense target of kind 0 / 1 (OPTS and DENSE; `dn`; `target` is null): the clip's target row -- and pos_weight
+// for kind 1 -- ride with the up-front requests like the class weights and are staged in LDS, [64] floats each, behind wl; every DENSE line
+// is compiled out of the other three.
 template <typename T, int MODE>
 __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
@@ -576,18 +652,23 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
                                                        const float* __restrict__ bias, float* __restrict__ logits, int C,
                                                        const long long* __restrict__ target, float* __restrict__ loss,
                                                        float* __restrict__ ce_scratch, int rows_in_lds, const HybCeOpts& o, const HybCeMix& m,
-                                                       const int nthreads, const unsigned int nclips) {                 // (the kernel's blockDim.x, gridDim.x)
-    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2;
+                                                       const HybCeDense& dn, const int nthreads, const unsigned int nclips) {   // (the kernel's blockDim.x, gridDim.x)
+    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2, DENSE = MODE >= 3, BCE = MODE == 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
     float* pooled = reinterpret_cast<float*>(tail_smem);                    // [D]
     float* lg = pooled + D;                                                  // [64] this clip's logits
     float* part = lg + 64;                                                   // [256] loss tree
     float* wl = part + 256;                                                  // [64] class weights (OPTS)
-    T* rows = reinterpret_cast<T*>(part + 256 + (OPTS ? 64 : 0));            // [S][D] when rows_in_lds
+    float* tl = wl + 64;                                                     // [64] the clip's target row, [64] pos_weight (DENSE)
+    float* pl = tl + 64;
+    T* rows = reinterpret_cast<T*>(part + 256 + (OPTS ? 64 : 0) + (DENSE ? 128 : 0));       // [S][D] when rows_in_lds
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = nthreads >> 6;
     const int M = B * S;
     float wreg = 1.f;                                                        // the class weights ride with the up-front requests
     if constexpr (OPTS) { if (tid < C && o.weight) wreg = o.weight[tid]; }
+    float treg = 0.f, preg = 1.f;
+    if constexpr (DENSE) { if (tid < C) treg = dn.target[(long long)b * C + tid]; }
+    if constexpr (BCE) { if (tid < C && dn.pos_weight) preg = dn.pos_weight[tid]; }
     // this wave's first class: its weight row does not depend on the tokens -- requested before the LayerNorm rows (a latency-bound kernel: one
     // memory round trip fewer on the critical path), up to 8 x 64 features in registers
     float w0[8];
@@ -599,6 +680,8 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
         ln_fwd_row<T>(f, x1, gamma, beta, enc_out, rows_in_lds ? rows + (long long)s * D : nullptr, stats, M, b * S + s, D, eps, out_scale, p_drop,
                       seed, seed_inc, lane);
     if constexpr (OPTS) { if (tid < C) wl[tid] = wreg; }
+    if constexpr (DENSE) { if (tid < C) tl[tid] = treg; }
+    if constexpr (BCE) { if (tid < C) pl[tid] = preg; }
     __syncthreads();                                                         // (also makes the rows just stored to enc_out readable by this workgroup)
     for (int d = tid; d < D; d += nthreads) {
         if (rows_in_lds) {
@@ -618,7 +701,7 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
         } else s = head_logit(pooled, W + (long long)c * D, D, lane);
         if (lane == 0) { const float v = s + ((pre && c == wave) ? bias0 : (bias ? bias[c] : 0.f)); logits[b * C + c] = v; lg[c] = v; }
     }
-    if (!target) return;
+    if constexpr (!DENSE) { if (!target) return; }                           // (a dense target: the loss is always asked for)
     __syncthreads();
     // ce_scratch: [B] per-clip terms, then one ticket word (zero at rest).  The term is published by an agent-scope atomic store (performed at
     // the device's coherence point, not in this XCD's L2), which has completed when vmcnt reaches 0 -- only then is the ticket taken; the last
@@ -627,7 +710,9 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
     __shared__ int s_last;
     if (tid == 0) {
         float term;
-        if constexpr (MIX) term = ce_clip_loss_mix(lg, o.weight ? wl : nullptr, target[b], m.target_b[b], m.lam[b], C, o);
+        if constexpr (BCE) term = ce_clip_loss_bce(lg, o.weight ? wl : nullptr, dn.pos_weight ? pl : nullptr, tl, C);
+        else if constexpr (DENSE) term = ce_clip_loss_soft(lg, o.weight ? wl : nullptr, tl, C, o.label_smoothing);
+        else if constexpr (MIX) term = ce_clip_loss_mix(lg, o.weight ? wl : nullptr, target[b], m.target_b[b], m.lam[b], C, o);
         else if constexpr (OPTS) term = ce_clip_loss_opts(lg, o.weight ? wl : nullptr, target[b], C, o);
         else term = ce_clip_loss(lg, target[b], C);
         __hip_atomic_store(ce_scratch + b, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -642,7 +727,10 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
     float acc = 0.f;
     if (tid < 256)
         for (int i = tid; i < B; i += 256) acc += __hip_atomic_load(ce_scratch + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if constexpr (OPTS) {           // ce_opts_fwd_kernel's two trees, the terms coming from the other workgroups
+    if constexpr (DENSE) {          // ce_dense_fwd_kernel's tree and division
+        const float num = ce_tree_sum(acc, part);
+        if (tid == 0) loss[0] = num / ce_dense_div(B, C, BCE ? 1 : 0);
+    } else if constexpr (OPTS) {    // ce_opts_fwd_kernel's two trees, the terms coming from the other workgroups
         const float num = ce_tree_sum(acc, part);
         float den;
         if constexpr (MIX) den = ce_den_mix(target, m, o.weight ? wl : nullptr, B, C, o, part);
@@ -659,7 +747,7 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restr
                                                                  const long long* __restrict__ target, float* __restrict__ loss,
                                                                  float* __restrict__ ce_scratch, int rows_in_lds) {
     temporal_tail_fwd_body<T, 0>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
-                                 ce_scratch, rows_in_lds, HybCeOpts{}, HybCeMix{}, blockDim.x, gridDim.x);
+                                 ce_scratch, rows_in_lds, HybCeOpts{}, HybCeMix{}, HybCeDense{}, blockDim.x, gridDim.x);
 }
 template <typename T>
 __global__ __launch_bounds__(512) void temporal_tail_fwd_opts_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
@@ -671,7 +759,7 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_opts_kernel(const T* __
                                                                       float* __restrict__ loss, float* __restrict__ ce_scratch, int rows_in_lds,
                                                                       HybCeOpts o) {
     temporal_tail_fwd_body<T, 1>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
-                                 ce_scratch, rows_in_lds, o, HybCeMix{}, blockDim.x, gridDim.x);
+                                 ce_scratch, rows_in_lds, o, HybCeMix{}, HybCeDense{}, blockDim.x, gridDim.x);
 }
 template <typename T>
 __global__ __launch_bounds__(512) void temporal_tail_fwd_mix_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
@@ -683,7 +771,18 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_mix_kernel(const T* __r
                                                                      float* __restrict__ loss, float* __restrict__ ce_scratch, int rows_in_lds,
                                                                      HybCeOpts o, HybCeMix m) {
     temporal_tail_fwd_body<T, 2>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
-                                 ce_scratch, rows_in_lds, o, m, blockDim.x, gridDim.x);
+                                 ce_scratch, rows_in_lds, o, m, HybCeDense{}, blockDim.x, gridDim.x);
+}
+template <typename T, int KIND>
+__global__ __launch_bounds__(512) void temporal_tail_fwd_dense_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
+                                                                       const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
+                                                                       int B, int S, int D, float eps, float out_scale, float p_drop,
+                                                                       unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
+                                                                       const float* __restrict__ W, const float* __restrict__ bias,
+                                                                       float* __restrict__ logits, int C, float* __restrict__ loss,
+                                                                       float* __restrict__ ce_scratch, int rows_in_lds, HybCeOpts o, HybCeDense dn) {
+    temporal_tail_fwd_body<T, 3 + KIND>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, nullptr,
+                                        loss, ce_scratch, rows_in_lds, o, HybCeMix{}, dn, blockDim.x, gridDim.x);
 }
 
 // backward: cross-entropy backward (from the saved logits, when a target is given; else the caller's dlogits) -> head backward (the
@@ -693,7 +792,8 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_mix_kernel(const T* __r
 // column.  Everything a workgroup reads -- its rows of the LayerNorm input, the head weights, the token means -- is requested up front: one
 // memory round trip.  Writes dx (d LN input), dskip and ln_rows affine-gradient partial rows as ln_residual_bwd_kernel<T, true> does for
 // the launch it replaces (workgroup (sb, b) writes row b * nsb + sb; rows no workgroup owns are zero-filled).
-// OPTS (a target is given): the loss backward with options; [64] class weights and the [256] den tree in LDS behind lnred.  MODE as in the forward.
+// OPTS (a target is given): the loss backward with options; [64] class weights and the [256] den tree in LDS behind lnred.  MODE as in the forward;
+// DENSE: [64] class weights, the clip's [64] target row and [64] pos_weight behind lnred, no den tree.
 template <typename T, int MODE>
 __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__ dlogits_in, const float* __restrict__ logits,
                                                        const long long* __restrict__ target, const float* __restrict__ dloss,
@@ -702,8 +802,8 @@ __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__
                                                        T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
                                                        float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
                                                        float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
-                                                       const HybCeOpts& o, const HybCeMix& m) {
-    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2;
+                                                       const HybCeOpts& o, const HybCeMix& m, const HybCeDense& dn) {
+    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2, DENSE = MODE >= 3, BCE = MODE == 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
     float* dl = reinterpret_cast<float*>(tail_smem);                         // [64]
     float* v = dl + 64;                                                      // [D] the clip's token-gradient row (T-rounded values)
@@ -727,7 +827,20 @@ __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__
     }
     const int d_first = sb + tid * nsb;                                      // this thread's first head column: its token mean does not wait for dl
     const float pooled_first = d_first < D ? token_mean(enc_out, b, S, D, d_first) : 0.f;
-    if constexpr (OPTS) {
+    if constexpr (DENSE) {
+        float* tl = wl + 64;                                                 // [64] the clip's target row, [64] pos_weight
+        float* pl = tl + 64;
+        if (tid < C) {
+            wl[tid] = o.weight ? o.weight[tid] : 1.f;
+            tl[tid] = dn.target[(long long)b * C + tid];
+            if constexpr (BCE) pl[tid] = dn.pos_weight ? dn.pos_weight[tid] : 1.f;
+        }
+        const float g = dloss[0] / ce_dense_div(B, C, BCE ? 1 : 0);
+        __syncthreads();
+        const float* w = o.weight ? wl : nullptr;
+        if constexpr (BCE) { if (tid < C) dl[tid] = ce_clip_dlogit_bce(logits + (long long)b * C, w, dn.pos_weight ? pl : nullptr, tl, tid, g); }
+        else { if (tid < C) dl[tid] = ce_clip_dlogit_soft(logits + (long long)b * C, w, tl, C, tid, g, o.label_smoothing); }
+    } else if constexpr (OPTS) {
         if (tid < C) wl[tid] = o.weight ? o.weight[tid] : 1.f;
         const float dlo = dloss[0];
         __syncthreads();
@@ -792,7 +905,7 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_kernel(const float* __r
                                                                 float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
                                                                 float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc) {
     temporal_tail_bwd_body<T, 0>(dlogits_in, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C,
-                                 rpw, out_scale, p_drop, seed, seed_inc, HybCeOpts{}, HybCeMix{});
+                                 rpw, out_scale, p_drop, seed, seed_inc, HybCeOpts{}, HybCeMix{}, HybCeDense{});
 }
 template <typename T>
 __global__ __launch_bounds__(256) void temporal_tail_bwd_opts_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
@@ -804,7 +917,7 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_opts_kernel(const float
                                                                      float out_scale, float p_drop, unsigned long long seed,
                                                                      const unsigned long long* __restrict__ seed_inc, HybCeOpts o) {
     temporal_tail_bwd_body<T, 1>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
-                                 out_scale, p_drop, seed, seed_inc, o, HybCeMix{});
+                                 out_scale, p_drop, seed, seed_inc, o, HybCeMix{}, HybCeDense{});
 }
 template <typename T>
 __global__ __launch_bounds__(256) void temporal_tail_bwd_mix_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
@@ -816,7 +929,19 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_mix_kernel(const float*
                                                                     float out_scale, float p_drop, unsigned long long seed,
                                                                     const unsigned long long* __restrict__ seed_inc, HybCeOpts o, HybCeMix m) {
     temporal_tail_bwd_body<T, 2>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
-                                 out_scale, p_drop, seed, seed_inc, o, m);
+                                 out_scale, p_drop, seed, seed_inc, o, m, HybCeDense{});
+}
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void temporal_tail_bwd_dense_kernel(const float* __restrict__ logits, const float* __restrict__ dloss,
+                                                                      const float* __restrict__ W, const T* __restrict__ enc_out,
+                                                                      const T* __restrict__ f, const float* __restrict__ gamma,
+                                                                      const float* __restrict__ stats, T* __restrict__ dx, T* __restrict__ dskip,
+                                                                      float* __restrict__ ln_part, int ln_rows, float* __restrict__ head_part, int B,
+                                                                      int S, int D, int C, int rpw, float out_scale, float p_drop,
+                                                                      unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
+                                                                      HybCeOpts o, HybCeDense dn) {
+    temporal_tail_bwd_body<T, 3 + KIND>(nullptr, logits, nullptr, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C,
+                                        rpw, out_scale, p_drop, seed, seed_inc, o, HybCeMix{}, dn);
 }
 
 // ---- evaluation: an accumulating classification meter behind the logits (hyb_eval_metrics; include/hybrid_hip.h states the rules) --------
@@ -983,15 +1108,22 @@ int hyb_temporal_tail_ok(int B, int S, int D, int C, int ln_rows) {
 int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float* gamma, const float* beta, void* enc_out, float* stats, int B, int S,
                           int D, float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const float* W,
                           const float* bias, float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st,
-                          const HybCeOpts* ce, const HybCeMix* mix) {
-    HYB_CHECK_ARG(f && x1 && gamma && beta && enc_out && stats && W && logits && (!target || (loss && ce_scratch)) && (!ce || target));
+                          const HybCeOpts* ce, const HybCeMix* mix, const HybCeDense* dense) {
+    HYB_CHECK_ARG(f && x1 && gamma && beta && enc_out && stats && W && logits && (!target || (loss && ce_scratch)) && (!ce || target || dense));
     HYB_CHECK_ARG(!mix || (ce && mix->target_b && mix->lam));
+    HYB_CHECK_ARG(!dense || (ce && !target && !mix && loss && ce_scratch && hyb_ce_dense_ok(*ce, *dense)));
     const size_t es = dtype == HYB_F32 ? 4 : 2;
-    const size_t base = ((size_t)D + 64 + 256 + (ce ? 64 : 0)) * sizeof(float);
+    const size_t base = ((size_t)D + 64 + 256 + (ce ? 64 : 0) + (dense ? 128 : 0)) * sizeof(float);
     const int rows_in_lds = base + (size_t)S * D * es <= 60 * 1024;
     const size_t lds = base + (rows_in_lds ? (size_t)S * D * es : 0);
     const int threads = S >= 8 ? 512 : 256;             // (1024 threads leave 128 registers per lane: the LayerNorm row spills -- measured 13 -> 24 us)
-    if (mix && dtype == HYB_F32)
+#define HYB_TAIL_FWD_DENSE(T, KIND)                                                                                                                  \
+    hipLaunchKernelGGL((temporal_tail_fwd_dense_kernel<T, KIND>), dim3(B), dim3(threads), lds, st, (const T*)f, (const T*)x1, gamma, beta, (T*)enc_out, stats, \
+                       B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, loss, ce_scratch, rows_in_lds, *ce, *dense)
+    if (dense && dtype == HYB_F32) { if (dense->kind == 1) HYB_TAIL_FWD_DENSE(float, 1); else HYB_TAIL_FWD_DENSE(float, 0); }
+    else if (dense && dtype == HYB_BF16) { if (dense->kind == 1) HYB_TAIL_FWD_DENSE(bf16, 1); else HYB_TAIL_FWD_DENSE(bf16, 0); }
+#undef HYB_TAIL_FWD_DENSE
+    else if (mix && dtype == HYB_F32)
         hipLaunchKernelGGL(temporal_tail_fwd_mix_kernel<float>, dim3(B), dim3(threads), lds, st, (const float*)f, (const float*)x1, gamma, beta, (float*)enc_out, stats, B, S,
                            D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce, *mix);
     else if (mix && dtype == HYB_BF16)
@@ -1016,11 +1148,12 @@ int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float*
 int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* W,
                           const void* enc_out, const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part,
                           int ln_rows, float* head_part, int B, int S, int D, int C, float out_scale, float p_drop, unsigned long long seed,
-                          const unsigned long long* seed_inc, hipStream_t st, const HybCeOpts* ce, const HybCeMix* mix) {
-    HYB_CHECK_ARG((dlogits || (logits && target && dloss)) && W && enc_out && f && gamma && stats && dx && dskip && ln_part && head_part);
-    HYB_CHECK_ARG(!ce || (!dlogits && logits && target && dloss));
+                          const unsigned long long* seed_inc, hipStream_t st, const HybCeOpts* ce, const HybCeMix* mix, const HybCeDense* dense) {
+    HYB_CHECK_ARG((dlogits || (logits && (target || dense) && dloss)) && W && enc_out && f && gamma && stats && dx && dskip && ln_part && head_part);
+    HYB_CHECK_ARG(!ce || (!dlogits && logits && (target || dense) && dloss));
     HYB_CHECK_ARG(!mix || (ce && mix->target_b && mix->lam));
-    const size_t lds = (64 + 9 * (size_t)D + (ce ? 64 + 256 : 0)) * sizeof(float);
+    HYB_CHECK_ARG(!dense || (ce && !target && !mix && hyb_ce_dense_ok(*ce, *dense)));
+    const size_t lds = (64 + 9 * (size_t)D + (dense ? 3 * 64 : ce ? 64 + 256 : 0)) * sizeof(float);
     // row blocks per clip: as many as the ln_rows partial rows allow (>= 1: hyb_temporal_tail_ok), four-row granules
     int nsb = hyb_cdiv(S, 4);
     if (nsb > ln_rows / B) nsb = ln_rows / B;
@@ -1028,7 +1161,13 @@ int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, 
     nsb = hyb_cdiv(S, rpw);
     const dim3 grid(nsb, B);
     if (lds > 64 * 1024) return HYB_E_ARG;
-    if (mix && dtype == HYB_F32)
+#define HYB_TAIL_BWD_DENSE(T, KIND)                                                                                                                  \
+    hipLaunchKernelGGL((temporal_tail_bwd_dense_kernel<T, KIND>), grid, dim3(256), lds, st, logits, dloss, W, (const T*)enc_out, (const T*)f, gamma, stats,    \
+                       (T*)dx, (T*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *dense)
+    if (dense && dtype == HYB_F32) { if (dense->kind == 1) HYB_TAIL_BWD_DENSE(float, 1); else HYB_TAIL_BWD_DENSE(float, 0); }
+    else if (dense && dtype == HYB_BF16) { if (dense->kind == 1) HYB_TAIL_BWD_DENSE(bf16, 1); else HYB_TAIL_BWD_DENSE(bf16, 0); }
+#undef HYB_TAIL_BWD_DENSE
+    else if (mix && dtype == HYB_F32)
         hipLaunchKernelGGL(temporal_tail_bwd_mix_kernel<float>, grid, dim3(256), lds, st, logits, target, dloss, W, (const float*)enc_out, (const float*)f, gamma, stats,
                            (float*)dx, (float*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *mix);
     else if (mix && dtype == HYB_BF16)
@@ -1131,6 +1270,34 @@ extern "C" int hyb_cross_entropy_mix_bwd(const float* logits, const long long* t
     HYB_CHECK_ARG(logits && target && target_b && lam && dloss && dlogits && B > 0 && C > 0 && hyb_ce_opts_ok(o));
     hipLaunchKernelGGL(ce_mix_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o,
                        HybCeMix{target_b, lam});
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// The loss on dense targets (ce_dense_*_kernel; include/hybrid_hip.h states the two definitions).  hyb_ce_dense_ok: what every *_dense_* entry
+// point asks of the options beyond non-null pointers.
+int hyb_ce_dense_ok(const HybCeOpts& o, const HybCeDense& d) {
+    if (!d.target || (d.kind != 0 && d.kind != 1)) return 0;
+    if (!(o.label_smoothing >= 0.f && o.label_smoothing <= 1.f)) return 0;
+    if (d.kind == 1 && o.label_smoothing != 0.f) return 0;
+    if (d.kind == 0 && d.pos_weight) return 0;
+    return 1;
+}
+extern "C" int hyb_cross_entropy_dense_fwd(const float* logits, const float* target, const float* weight, const float* pos_weight, int kind,
+                                           float label_smoothing, float* loss, int B, int C, void* stream) {
+    const HybCeOpts o{weight, 0, 0, label_smoothing};
+    const HybCeDense d{target, pos_weight, kind};
+    HYB_CHECK_ARG(logits && loss && B > 0 && C > 0 && hyb_ce_dense_ok(o, d));
+    hipLaunchKernelGGL(ce_dense_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, loss, B, C, o, d);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int hyb_cross_entropy_dense_bwd(const float* logits, const float* target, const float* weight, const float* pos_weight, int kind,
+                                           float label_smoothing, const float* dloss, float* dlogits, int B, int C, void* stream) {
+    const HybCeOpts o{weight, 0, 0, label_smoothing};
+    const HybCeDense d{target, pos_weight, kind};
+    HYB_CHECK_ARG(logits && dloss && dlogits && B > 0 && C > 0 && hyb_ce_dense_ok(o, d));
+    hipLaunchKernelGGL(ce_dense_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, dloss, dlogits, B, C, o, d);
     HYB_LAUNCH_CHECK();
     return 0;
 }

@@ -23,6 +23,9 @@ What makes capture legal here
     next replay; ignore_index and label_smoothing travel by value, and step() refuses a change of either after capture;
   * a MixTarget (the labels of a Mixup / CutMix batch) is three static tensors: both targets and lam are read from device memory when a
     replay runs, so load() brings new labels and new mixing weights without a recapture, and the loss stays in the same launches;
+  * a dense target (floating [B, C]: class probabilities under a HybridCrossEntropyLoss, binary targets under a HybridBCEWithLogitsLoss) is
+    one static tensor read from device memory when a replay runs, as are the criterion's weight / pos_weight buffers; the loss stays in
+    the same launches (hybrid::temporal_ce_dense), and load() refuses a target of another form than the one captured;
   * BatchNorm running statistics are updated in place by the captured statistics kernels (hybrid::backbone_);
   * with HybridAdamW(skip_nonfinite=True) a replay whose gradients are not finite changes nothing in the model: the captured norm launch
     decides, the captured AdamW launch reads the decision (optim.py).  The counter advances all the same -- the next replay draws new
@@ -101,8 +104,8 @@ class GraphedTrainStep:
         # whether the captured norm and AdamW launches are the guarded ones (skip_nonfinite): entry points, fixed by the capture
         self._guard_on = bool(getattr(optimizer, "skip_nonfinite", False))
         self._captured_hyper = self._hyper_now()
-        from .modules import HybridCrossEntropyLoss
-        self._fused_loss = (type(criterion) is HybridCrossEntropyLoss and hasattr(model, "forward_temporal_loss")
+        from .modules import HybridBCEWithLogitsLoss, HybridCrossEntropyLoss
+        self._fused_loss = (type(criterion) in (HybridCrossEntropyLoss, HybridBCEWithLogitsLoss) and hasattr(model, "forward_temporal_loss")
                             and os.environ.get("HYB_FUSED_LOSS", "1") != "0")       # (=0: A/B, the criterion as its own two launches)
         # the captured loss launch carries ignore_index and label_smoothing by value (the class weights are read from the criterion's buffer
         # when a replay runs, so an in-place update of criterion.weight is picked up); a later change is refused like an optimizer's (_check_hyper)
@@ -114,6 +117,9 @@ class GraphedTrainStep:
         self._mix = isinstance(y, MixTarget)
         if self._mix and not hasattr(criterion, "has_options"):
             raise TypeError("a MixTarget needs a HybridCrossEntropyLoss criterion")
+        # a dense target (floating [B, C]: class probabilities, or the binary targets of a HybridBCEWithLogitsLoss) is one static tensor like
+        # the class indices, read from device memory when a replay runs; load() keeps to the form captured
+        self._dense = not self._mix and y.is_floating_point()
         # static inputs: copy new batches in with load() (a MixTarget: static copies of all three tensors)
         self.x, self.y = x.clone(), MixTarget(*(t.clone() for t in y)) if self._mix else y.clone()
         self.mask = mask.clone() if mask is not None else None
@@ -212,6 +218,9 @@ class GraphedTrainStep:
     def _loss_opts_now(self):
         """What a HybridCrossEntropyLoss's launches carry by value or by address: (ignore_index, label_smoothing, the weight buffer's address)."""
         c = self.criterion
+        from .modules import HybridBCEWithLogitsLoss
+        if type(c) is HybridBCEWithLogitsLoss:                      # nothing by value, two buffers by address
+            return (None, 0.0, tuple(None if t is None else t.data_ptr() for t in (c.weight, c.pos_weight)))
         if not hasattr(c, "has_options"):
             return None
         return (c.ignore_index, c.label_smoothing, c.weight.data_ptr() if c.weight is not None else None)
@@ -345,11 +354,16 @@ class GraphedTrainStep:
 
     # ---- public ---------------------------------------------------------------------------------------------------------
     def load(self, x, y, mask=None):
-        """Copy the next batch into the static input buffers (same shapes as at construction; y a MixTarget exactly when it was one there)."""
+        """Copy the next batch into the static input buffers (same shapes as at construction; y a MixTarget exactly when it was one there, a
+        dense floating [B, C] target exactly when it was one there)."""
         from .modules import MixTarget
         if isinstance(y, MixTarget) != self._mix:
             raise TypeError("GraphedTrainStep was captured with " + ("a MixTarget: load() needs one too" if self._mix else
+                            "a dense target: a MixTarget needs a step constructed with one" if self._dense else
                             "a class-index tensor: a MixTarget needs a step constructed with one"))
+        if not self._mix and y.is_floating_point() != self._dense:
+            raise TypeError("GraphedTrainStep was captured with " + ("a dense target: load() needs a floating [B,C] target too" if self._dense else
+                            "a class-index tensor: a dense target needs a step constructed with one"))
         self.x.copy_(x, non_blocking=True)
         if self._mix:
             for dst, src in zip(self.y, y):

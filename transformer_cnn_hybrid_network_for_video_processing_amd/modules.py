@@ -180,6 +180,52 @@ class MixTarget(NamedTuple):
     lam: torch.Tensor
 
 
+def _is_dense(target):
+    """A dense target: a floating tensor, one row of C numbers per clip (class indices are integer tensors, mixed labels a MixTarget)."""
+    return isinstance(target, torch.Tensor) and target.is_floating_point()
+
+
+def _class_vector(name, v):
+    """A per-class vector of a criterion (weight, pos_weight): 1-D fp32, no negative or NaN entry; cloned for the buffer."""
+    if v is None:
+        return None
+    if not isinstance(v, torch.Tensor) or v.dim() != 1 or v.dtype != torch.float32:
+        raise ValueError(f"{name} must be a 1-D float32 tensor with one entry per class")
+    if bool((v < 0).any()) or bool(torch.isnan(v).any()):
+        raise ValueError(f"{name} must not have a negative entry")
+    return v.detach().clone()
+
+
+def _check_dense(logits, target):
+    if target.dtype != torch.float32:
+        raise TypeError(f"a dense target must be float32, got {target.dtype}")
+    if logits.dim() != 2 or target.dim() != 2 or target.shape != logits.shape:
+        raise ValueError(f"a dense target has the shape of the logits [B,C]: got logits {tuple(logits.shape)} and target {tuple(target.shape)}")
+
+
+def dense_target(y, num_classes, label_smoothing=0.0):
+    """Class indices int64 [B], or a ``MixTarget``, as the dense fp32 [B, num_classes] target of the same labels, on their device, with plain
+    torch operations: one-hot rows, or ``lam * one_hot(y_a) + (1 - lam) * one_hot(y_b)``; with ``label_smoothing`` e the row is
+    ``(1 - e) * row + e / num_classes``.  What a mixing ClipPipeline's labels need in front of HybridBCEWithLogitsLoss."""
+    e = float(label_smoothing)
+    if not 0.0 <= e <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {e}")
+    C = int(num_classes)
+
+    def one_hot(t):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1:
+            raise TypeError("dense_target takes class indices int64 [B] or a MixTarget")
+        return torch.nn.functional.one_hot(t, C).to(torch.float32)
+    if isinstance(y, MixTarget):
+        lam = y.lam.to(torch.float32).unsqueeze(1)
+        t = lam * one_hot(y.y_a) + (1.0 - lam) * one_hot(y.y_b)
+    else:
+        t = one_hot(y)
+    if e != 0.0:
+        t = (1.0 - e) * t + e / C
+    return t.contiguous()
+
+
 class HybridCrossEntropyLoss(nn.Module):
     """Mean cross-entropy over the batch (the composite's own loss), one HIP kernel each way.
 
@@ -197,7 +243,12 @@ class HybridCrossEntropyLoss(nn.Module):
     ``target`` may be a ``MixTarget(y_a, y_b, lam)``: the loss is sum_b [lam_b term(b, y_a) + (1 - lam_b) term(b, y_b)] over the same mix of
     the target weights (include/hybrid_hip.h, hyb_cross_entropy_mix_*), with any combination of the options, none included; each side keeps
     the rules above on its own, a lam outside [0, 1] makes the loss NaN.  With one lam for the batch, ``y_b`` a permutation of ``y_a`` and
-    nothing ignored it is ``lam * CE(logits, y_a) + (1 - lam) * CE(logits, y_b)``.  A plain tensor target takes the path it always took."""
+    nothing ignored it is ``lam * CE(logits, y_a) + (1 - lam) * CE(logits, y_b)``.  A plain tensor target takes the path it always took.
+
+    A floating ``target`` [B, C] is a row of class probabilities per clip, torch's own convention: soft-target cross-entropy
+    (include/hybrid_hip.h, hyb_cross_entropy_dense_*, kind 0) with ``weight`` and ``label_smoothing``; the sum of the clips' terms is divided
+    by B, not by a weight sum (torch's rule for probability targets), rows are used as given (fp32, contiguous; not normalised), and a
+    criterion with an ``ignore_index`` raises ValueError, as torch does."""
 
     def __init__(self, weight=None, ignore_index=None, label_smoothing=0.0):
         super().__init__()
@@ -206,13 +257,7 @@ class HybridCrossEntropyLoss(nn.Module):
             raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
         if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
             raise TypeError(f"ignore_index must be an int or None, got {ignore_index!r}")
-        if weight is not None:
-            if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or weight.dtype != torch.float32:
-                raise ValueError("weight must be a 1-D float32 tensor with one entry per class")
-            if bool((weight < 0).any()) or bool(torch.isnan(weight).any()):
-                raise ValueError("weight must not have a negative entry")
-            weight = weight.detach().clone()
-        self.register_buffer("weight", weight)
+        self.register_buffer("weight", _class_vector("weight", weight))
         self.ignore_index, self.label_smoothing = ignore_index, label_smoothing
 
     def has_options(self):
@@ -226,7 +271,16 @@ class HybridCrossEntropyLoss(nn.Module):
         if self.weight is not None and self.weight.shape[0] != C:
             raise ValueError(f"weight has {self.weight.shape[0]} entries but the logits have {C} classes")
 
+    def _refuse_ignore_index(self):
+        if self.ignore_index is not None:
+            raise ValueError("ignore_index is not supported with a dense (class-probability) target")
+
     def forward(self, logits, target):
+        if _is_dense(target):
+            self._refuse_ignore_index()
+            _check_dense(logits, target)
+            self._check_weight(logits.shape[-1])
+            return ops.cross_entropy_dense(logits, target, self.weight, None, 0, self.label_smoothing)
         if isinstance(target, MixTarget):
             self._check_weight(logits.shape[-1])
             return ops.cross_entropy_mix(logits, target.y_a, target.y_b, target.lam, self.weight, self.ignore_index, self.label_smoothing)
@@ -237,6 +291,33 @@ class HybridCrossEntropyLoss(nn.Module):
 
     def extra_repr(self):
         return f"ignore_index={self.ignore_index}, label_smoothing={self.label_smoothing}"
+
+
+class HybridBCEWithLogitsLoss(nn.Module):
+    """Mean binary cross-entropy with logits over all B x C entries, ``nn.BCEWithLogitsLoss(weight, pos_weight)`` with per-class vectors, one
+    HIP kernel each way (include/hybrid_hip.h, hyb_cross_entropy_dense_*, kind 1; the overflow-safe form).  ``target`` is fp32 [B, C],
+    contiguous, on the logits' device: multi-label clips, or ``dense_target(y, C)`` of a mixing ClipPipeline's labels.
+
+    ``weight`` and ``pos_weight`` (one fp32 entry >= 0 per class, or None = all ones) are registered buffers read by the kernels when they
+    run: an in-place update is seen by the next call and by the next replay of a GraphedTrainStep."""
+
+    def __init__(self, weight=None, pos_weight=None):
+        super().__init__()
+        self.register_buffer("weight", _class_vector("weight", weight))
+        self.register_buffer("pos_weight", _class_vector("pos_weight", pos_weight))
+
+    def _check_weight(self, C):
+        for name in ("weight", "pos_weight"):
+            v = getattr(self, name)
+            if v is not None and v.shape[0] != C:
+                raise ValueError(f"{name} has {v.shape[0]} entries but the logits have {C} classes")
+
+    def forward(self, logits, target):
+        if not _is_dense(target):
+            raise TypeError("HybridBCEWithLogitsLoss takes a floating target [B,C] (dense_target() makes one from class indices or a MixTarget)")
+        _check_dense(logits, target)
+        self._check_weight(logits.shape[-1])
+        return ops.cross_entropy_dense(logits, target, self.weight, self.pos_weight, 1, 0.0)
 
 
 class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
@@ -338,11 +419,36 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
         """Last pooled map + class indices [B] -> (mean cross-entropy loss, logits): ``criterion(forward_temporal(h, B, mask), target)``
         with the loss inside the temporal part's own launches (hybrid::temporal_ce, or hybrid::temporal_ce_opts when the criterion carries
         options; same bits, same number of launches).  ``criterion``: a HybridCrossEntropyLoss, None = ``HybridCrossEntropyLoss()``.
-        ``target`` may be a MixTarget: hybrid::temporal_ce_mix, again the same launches.  Models ``_fused()`` rejects run the criterion behind
+        ``target`` may be a MixTarget: hybrid::temporal_ce_mix, again the same launches.  A floating ``target`` [B, num_classes] is a dense
+        target: hybrid::temporal_ce_dense, the same launches, as soft-target cross-entropy under a HybridCrossEntropyLoss (or None) and as
+        binary cross-entropy under a HybridBCEWithLogitsLoss, which takes nothing else.  Models ``_fused()`` rejects run the criterion behind
         forward_temporal."""
         enc = self.encoder
-        if criterion is not None and type(criterion) is not HybridCrossEntropyLoss:
-            raise TypeError("forward_temporal_loss fuses HybridCrossEntropyLoss only")
+        if criterion is not None and type(criterion) not in (HybridCrossEntropyLoss, HybridBCEWithLogitsLoss):
+            raise TypeError("forward_temporal_loss fuses HybridCrossEntropyLoss and HybridBCEWithLogitsLoss only")
+        bce = type(criterion) is HybridBCEWithLogitsLoss
+        if bce or _is_dense(target):
+            if not _is_dense(target):
+                raise TypeError("HybridBCEWithLogitsLoss takes a floating target [B,C] (dense_target() makes one from class indices or a MixTarget)")
+            if not self._fused():
+                logits = self.forward_temporal(h, B, mask)
+                return (criterion or HybridCrossEntropyLoss())(logits, target), logits
+            classes = self.head.weight.shape[0]
+            if not bce and criterion is not None:
+                criterion._refuse_ignore_index()
+            if target.dtype != torch.float32:
+                raise TypeError(f"a dense target must be float32, got {target.dtype}")
+            if target.dim() != 2 or tuple(target.shape) != (B, classes):
+                raise ValueError(f"a dense target has the shape of the logits [B={B},C={classes}]: got {tuple(target.shape)}")
+            if criterion is not None:
+                criterion._check_weight(classes)
+            weight = criterion.weight if criterion is not None else None
+            tdt = self._temporal_dt()
+            return ops.temporal_ce_dense(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias,
+                                         enc._flat_params(), self.head.weight, self.head.bias, mask, target, weight,
+                                         criterion.pos_weight if bce else None, 1 if bce else 0,
+                                         0.0 if bce or criterion is None else criterion.label_smoothing, B, tdt, enc.hidden_dim, enc.num_layers,
+                                         enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout), ops.next_seed())
         opts = criterion is not None and criterion.has_options()
         mixed = isinstance(target, MixTarget)
         if not self._fused():

@@ -23,6 +23,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::head             mean over T + Linear(d, classes)                    (composite's own)
     hybrid::cross_entropy    mean cross-entropy                                  (composite's own)
     hybrid::cross_entropy_opts   ... with class weights, label smoothing, ignore_index   (torch.nn.functional.cross_entropy's "mean")
+    hybrid::cross_entropy_dense  the loss on dense fp32 [B, C] targets: soft-target cross-entropy (kind 0) / BCE with logits (kind 1)
     hybrid::cross_entropy_mix    ... and two targets per clip with a mixing weight lam [B]: the labels of a Mixup / CutMix batch
     hybrid::cast, hybrid::nchw_to_nhwc, hybrid::nhwc_to_nchw                     layout / dtype glue for standalone module use
     hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
@@ -574,6 +575,31 @@ def _ce_mix(mix, B, device):
     return target_b.contiguous().to(torch.int64), lam.contiguous()
 
 
+def _ce_dense(dense, B, C, device):
+    """(target, weight, pos_weight, kind, label_smoothing) as the hyb_*_dense_* entry points take them: the target a contiguous fp32 [B, C]
+    on the logits' device, weight / pos_weight [C] fp32 or None; kind 0 = class probabilities, kind 1 = binary targets."""
+    target, weight, pos_weight, kind, label_smoothing = dense
+    _require_cuda(target)
+    if not isinstance(target, torch.Tensor) or target.dim() != 2 or tuple(target.shape) != (B, C):
+        raise ValueError(f"expected a dense target [B={B}, C={C}], got {tuple(target.shape)}")
+    if target.dtype != torch.float32:
+        raise TypeError(f"a dense target must be float32, got {target.dtype}")
+    if target.device != device:
+        raise RuntimeError(f"the target is on {target.device} but the logits are on {device}")
+    if not target.is_contiguous():
+        raise ValueError("a dense target must be contiguous (it is read in place when the kernels run)")
+    kind, label_smoothing = int(kind), float(label_smoothing)
+    if kind not in (0, 1):
+        raise ValueError(f"kind must be 0 (soft-target cross-entropy) or 1 (BCE with logits), got {kind}")
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+    if kind == 1 and label_smoothing != 0.0:
+        raise ValueError("label_smoothing goes with kind 0 only (smooth a BCE target with dense_target())")
+    if kind == 0 and pos_weight is not None:
+        raise ValueError("pos_weight goes with kind 1 (BCE with logits) only")
+    return target, _ce_weight(weight, C, device), _ce_weight(pos_weight, C, device), kind, label_smoothing
+
+
 def _ce_name(stem, opts, mix, way):
     return f"hyb_{stem}_mix_{way}" if mix else f"hyb_{stem}_opts_{way}" if opts else f"hyb_{stem}_{way}"
 
@@ -639,6 +665,34 @@ def cross_entropy_mix_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, targ
     return _cross_entropy_bwd(dloss, logits, target, (weight, ignore_index, has_ignore, label_smoothing), (target_b, lam))
 
 
+def cross_entropy_dense_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], kind: int,
+                           label_smoothing: float) -> Tensor:
+    """The mean loss on a dense fp32 target [B, C] (hyb_cross_entropy_dense_fwd).  kind 0: torch.nn.functional.cross_entropy with class
+    probabilities (weight, label_smoothing; the divisor is B); kind 1: binary_cross_entropy_with_logits (weight, pos_weight; the divisor is
+    B C)."""
+    _require_cuda(logits, target)
+    if logits.dim() != 2:
+        raise ValueError(f"expected logits [B,C], got {tuple(logits.shape)}")
+    logits = logits.contiguous().float()
+    B, C = logits.shape
+    dense = _ce_dense((target, weight, pos_weight, kind, label_smoothing), B, C, logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    lib.call("hyb_cross_entropy_dense_fwd", logits, *dense, loss, B, C, _stream())
+    return loss
+
+
+def cross_entropy_dense_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], kind: int,
+                               label_smoothing: float) -> Tensor:
+    _require_cuda(dloss, logits, target)
+    logits = logits.contiguous().float()
+    B, C = logits.shape
+    dense = _ce_dense((target, weight, pos_weight, kind, label_smoothing), B, C, logits.device)
+    dl = dloss.contiguous().float().reshape(1)
+    dlogits = torch.empty_like(logits)
+    lib.call("hyb_cross_entropy_dense_bwd", logits, *dense, dl, dlogits, B, C, _stream())
+    return dlogits
+
+
 def cross_entropy_fake(logits, target, *opts):
     return logits.new_empty((), dtype=torch.float32)
 
@@ -661,6 +715,13 @@ def cross_entropy_mix(logits, target, target_b, lam, weight=None, ignore_index=N
     on the device; the options as in cross_entropy_opts.  No gradient for lam, the targets or the class weights."""
     return torch.ops.hybrid.cross_entropy_mix(logits, target, target_b, lam, weight, 0 if ignore_index is None else int(ignore_index),
                                               ignore_index is not None, float(label_smoothing))
+
+
+def cross_entropy_dense(logits, target, weight=None, pos_weight=None, kind=0, label_smoothing=0.0):
+    """The mean loss on a dense target: a contiguous fp32 [B, C] on the logits' device.  kind 0: soft-target cross-entropy (rows are class
+    probabilities, used as given; class weights [C] and label smoothing as in torch.nn.functional.cross_entropy); kind 1: binary cross-entropy
+    with logits (weight and pos_weight [C]).  No gradient for the target or the weights."""
+    return torch.ops.hybrid.cross_entropy_dense(logits, target, weight, pos_weight, int(kind), float(label_smoothing))
 
 
 def eval_metrics_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
@@ -1197,12 +1258,13 @@ def prepare_ce_scratch(B, device, stream):
     return t
 
 
-def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc):
+def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, dense=()):
     """The temporal part, one body for the three operators.  ce (): hyb_temporal_fwd; ce = (target,): hyb_temporal_ce_fwd, the loss in the
     same launches; ce = (target, weight, ignore_index, has_ignore, label_smoothing): hyb_temporal_ce_opts_fwd, the same call with the loss
     options behind the target; ce = (target, target_b, lam, weight, ...): hyb_temporal_ce_mix_fwd, the second target and lam in front of the
-    options.  -> (logits, feat, enc_saved, enc_out), behind the loss [] when there is one."""
-    _require_cuda(h, token_w, head_w, *ce[:1], *enc_params)
+    options.  dense = (target [B, classes] fp32, weight, pos_weight, kind, label_smoothing) with ce (): hyb_temporal_ce_dense_fwd.
+    -> (logits, feat, enc_saved, enc_out), behind the loss [] when there is one."""
+    _require_cuda(h, token_w, head_w, *ce[:1], *dense[:1], *enc_params)
     _check_h_dtype(h, dt)
     h = h.contiguous()
     N, Hh, Ww, Cp = h.shape
@@ -1226,14 +1288,19 @@ def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, 
         name = _ce_name("temporal_ce", opts, mix, "fwd")
         loss_in = (ce[0].contiguous().to(torch.int64), *_ce_mix(mix, B, dev), *_ce_opts(opts, classes, dev))
         loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
+    elif dense:
+        name = "hyb_temporal_ce_dense_fwd"
+        loss_in = _ce_dense(dense, B, classes, dev)
+        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
     lib.call(name, dt, h, token_w.contiguous(), token_b.contiguous(), ps, head_w.contiguous(), head_b.contiguous(), mask, *loss_in, feat, tok, saved,
              enc_out, logits, *loss_out, B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, _stream())
     return (*loss_out[:1], logits, feat, saved, enc_out)
 
 
-def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc):
+def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, dense=()):
     """ce (): dout is dlogits, hyb_temporal_bwd; ce = (logits, target) + what follows the target in _temporal_fwd's ce, if anything: dout is
-    dloss, hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd / hyb_temporal_ce_mix_bwd.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
+    dloss, hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd / hyb_temporal_ce_mix_bwd.  dense = (logits,) + _temporal_fwd's dense, with ce ():
+    dout is dloss, hyb_temporal_ce_dense_bwd.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
     _require_cuda(dout, *ce[:1], feat)
     B, S, D = enc_out.shape
     N, Cp = feat.shape
@@ -1256,6 +1323,11 @@ def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_
         name = _ce_name("temporal_ce", opts, mix, "bwd")
         dout = dout.reshape(1)
         loss_in = (ce[0].contiguous(), ce[1].contiguous(), *_ce_mix(mix, B, dev), *_ce_opts(opts, classes, dev))
+    elif dense:
+        _require_cuda(dense[0])
+        name = "hyb_temporal_ce_dense_bwd"
+        dout = dout.reshape(1)
+        loss_in = (dense[0].contiguous(), *_ce_dense(dense[1:], B, classes, dev))
     lib.call(name, dt, dout, *loss_in, token_w.contiguous(), ps, head_w.contiguous(), mask, feat, saved, enc_out, dtw, dtb, grads, dhw, dhb, dh,
              B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, ws, ws.numel(), _stream())
     return [dh, dtw, dtb, dhw, dhb] + grads
@@ -1293,6 +1365,15 @@ def temporal_ce_mix_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: 
                          mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
 
 
+def temporal_ce_dense_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
+                         mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], kind: int,
+                         label_smoothing: float, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
+                         seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """hybrid::temporal + hybrid::cross_entropy_dense in the same launches (hyb_temporal_ce_dense_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
+    return _temporal_fwd((), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
+                         dense=(target, weight, pos_weight, kind, label_smoothing))
+
+
 def temporal_bwd_op(dlogits: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
                     saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
                     seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
@@ -1324,6 +1405,15 @@ def temporal_ce_mix_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, target
     """hybrid::cross_entropy_mix_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
     return _temporal_bwd((logits, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing), dloss, token_w, enc_params, head_w, mask,
                          feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+
+
+def temporal_ce_dense_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], kind: int,
+                             label_smoothing: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
+                             saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
+                             seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
+    """hybrid::cross_entropy_dense_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
+    return _temporal_bwd((), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
+                         dense=(logits, target, weight, pos_weight, kind, label_smoothing))
 
 
 def _temporal_fake(n_loss, h, token_w, token_b, enc_params, head_w, head_b, mask, *rest, seed_inc=None):
@@ -1374,6 +1464,17 @@ def temporal_ce_mix(h, token_w, token_b, enc_params, head_w, head_b, mask, targe
     r = torch.ops.hybrid.temporal_ce_mix(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, target_b, lam,
                                          weight, 0 if ignore_index is None else int(ignore_index), ignore_index is not None, float(label_smoothing), B,
                                          dt, hid, L, H, float(attn_p), float(layer_p), seed, step_counter())
+    return r[0], r[1]
+
+
+def temporal_ce_dense(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, pos_weight, kind, label_smoothing, B, dt, hid, L, H,
+                      attn_p, layer_p, seed):
+    """-> (loss, logits): the temporal part and the loss on a dense fp32 target [B, classes] (cross_entropy_dense) as one operator: the same
+    launches; the target, weight and pos_weight are read on the device when the kernels run."""
+    S = h.shape[0] // B
+    r = torch.ops.hybrid.temporal_ce_dense(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
+                                           pos_weight, int(kind), float(label_smoothing), B, dt, hid, L, H, float(attn_p), float(layer_p), seed,
+                                           step_counter())
     return r[0], r[1]
 
 
@@ -1560,6 +1661,24 @@ class _CrossEntropyFn(torch.autograd.Function):
         return (dlogits,) + (None,) * 5        # (no gradient for the class weights)
 
 
+class _CrossEntropyDenseFn(torch.autograd.Function):
+    """hybrid::cross_entropy_dense."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, pos_weight, kind, label_smoothing):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(logits, target, weight, pos_weight)
+        ctx.cfg = (kind, label_smoothing)
+        with _below_autograd():
+            return torch.ops.hybrid.cross_entropy_dense(logits, target, weight, pos_weight, kind, label_smoothing)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, target, weight, pos_weight = ctx.saved_tensors
+        dlogits = torch.ops.hybrid.cross_entropy_dense_bwd(dloss, logits, target, weight, pos_weight, *ctx.cfg)
+        return (dlogits,) + (None,) * 5        # (no gradient for the target or the weights)
+
+
 class _BackboneFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, S, training, momentum, eps, dt, *tensors):
@@ -1641,6 +1760,37 @@ class _TemporalFn(torch.autograd.Function):
         return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 17 + tuple(g[5:])
 
 
+class _TemporalDenseFn(torch.autograd.Function):
+    """hybrid::temporal_ce_dense."""
+
+    @staticmethod
+    def forward(ctx, h, token_w, token_b, head_w, head_b, mask, target, weight, pos_weight, kind, label_smoothing, B, dt, hid, L, H, attn_p, layer_p,
+                seed, seed_inc, *enc_params):
+        ctx.set_materialize_grads(False)
+        with _below_autograd():
+            out = torch.ops.hybrid.temporal_ce_dense(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, pos_weight, kind,
+                                                     label_smoothing, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+        feat, saved, enc_out = out[-3:]
+        ctx.seed_inc = seed_inc
+        opt = [t for t in (weight, pos_weight, mask) if t is not None]
+        ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, out[1], target, *opt, *enc_params)
+        ctx.cfg = (weight is not None, pos_weight is not None, mask is not None, kind, label_smoothing, h.shape[1], h.shape[2], dt, hid, L, H, attn_p,
+                   layer_p, seed)
+        ctx.mark_non_differentiable(*out[1:])
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, dout, *unused):
+        has_weight, has_pw, has_mask, kind, label_smoothing, *tail = ctx.cfg
+        token_w, head_w, feat, saved, enc_out, logits, target, *rest = ctx.saved_tensors
+        weight = rest.pop(0) if has_weight else None
+        pos_weight = rest.pop(0) if has_pw else None
+        mask = rest.pop(0) if has_mask else None
+        g = torch.ops.hybrid.temporal_ce_dense_bwd(dout, logits, target, weight, pos_weight, kind, label_smoothing, token_w, rest, head_w, mask, feat,
+                                                   saved, enc_out, *tail, ctx.seed_inc)
+        return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 15 + tuple(g[5:])
+
+
 _define("nchw_to_nhwc", "(Tensor x, int dt, int cp) -> Tensor", nchw_to_nhwc_op, nchw_to_nhwc_fake, _NchwToNhwcFn.apply)
 _define("nhwc_to_nchw", "(Tensor x, int dt, int C) -> Tensor", nhwc_to_nchw_op, nhwc_to_nchw_fake, _NhwcToNchwFn.apply)
 _define("cast", "(Tensor x, int dt, bool to_t) -> Tensor", cast_op, cast_fake, _CastFn.apply)
@@ -1677,6 +1827,10 @@ _define("cross_entropy_mix", "(Tensor logits, Tensor target, Tensor target_b, Te
             logits, target, weight, ignore_index, has_ignore, label_smoothing, target_b, lam))
 _define("cross_entropy_mix_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, "
         "bool has_ignore, float label_smoothing) -> Tensor", cross_entropy_mix_bwd_op, cross_entropy_bwd_fake)
+_define("cross_entropy_dense", "(Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing) -> Tensor",
+        cross_entropy_dense_op, cross_entropy_fake, _CrossEntropyDenseFn.apply)
+_define("cross_entropy_dense_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing) "
+        "-> Tensor", cross_entropy_dense_bwd_op, cross_entropy_bwd_fake)
 _define("eval_metrics_", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int topk, int views, "
         "Tensor(a!) sums, Tensor(b!) counts, Tensor(c!)? confusion) -> (Tensor, Tensor)", eval_metrics_op, eval_metrics_fake)
 _LIB.impl("eval_metrics_", _inference_only("eval_metrics_"), "Autograd")
@@ -1749,6 +1903,16 @@ _define("temporal_ce_mix_bwd", "(Tensor dloss, Tensor logits, Tensor target, Ten
         "bool has_ignore, float label_smoothing, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, "
         "Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]",
         temporal_ce_mix_bwd_op, functools.partial(_temporal_bwd_fake, 8))
+_define("temporal_ce_dense", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
+        "Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing, int B, int dt, int hid, int L, int H, float attn_p, float layer_p, "
+        "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_dense_op, functools.partial(_temporal_fake, 5),
+        lambda h, tw, tb, ps, hw, hb, mask, target, weight, pos_weight, kind, label_smoothing, B, dt, hid, L, H, attn_p, layer_p, seed,
+        seed_inc=None: _TemporalDenseFn.apply(h, tw, tb, hw, hb, mask, target, weight, pos_weight, kind, label_smoothing, B, dt, hid, L, H, attn_p,
+                                               layer_p, seed, seed_inc, *ps))
+_define("temporal_ce_dense_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing, "
+        "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
+        "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_dense_bwd_op,
+        functools.partial(_temporal_bwd_fake, 6))
 
 
 # ---------------------------------------------------------------------------------------------
