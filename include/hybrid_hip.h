@@ -393,6 +393,42 @@ int hyb_eval_metrics(const float* logits /* [B*V, C] */, const long long* target
                      double* sums /* [2] */, long long* counts /* [5] */, long long* confusion /* [C*C] or NULL */,
                      long long* pred /* [B] or NULL */, float* scores /* [B, C] or NULL */, int B, int C, void* stream);
 
+/* hyb_eval_multilabel: the update of an accumulating MULTI-LABEL meter, ONE launch of one 256-thread workgroup behind the logits (new
+ *   symbol, hyb_abi_version() stays 9).  Like hyb_eval_metrics it ADDS into sums, counts and cells and overwrites none of them, thread t
+ *   owns videos t, t + 256, .., the loss is summed in double over the fixed 256-leaf tree and one thread makes the final add: no
+ *   floating-point atomic, sums reproducible bit for bit, never synchronises.  The caller zeroes sums, counts and cells before the first.
+ *   Each of the B videos has V = views rows of logits, adjacent (row b * V + v), and one fp32 target row t_b [C].
+ *   Scores, with the overflow-safe sigmoid of the BCE gradient, ez = exp(-|z|), sg(z) = (z >= 0 ? 1 : ez) / (1 + ez):
+ *     V == 1: s_c = sg(z_c);   V > 1: s_c = (1 / V) sum_v sg(z_vc), summed in view order in fp32.  Always written to scores[b].
+ *   Loss term, fp32 per video, added into sums[0] in double (the meter reports sums[0] / (videos C)):
+ *     V == 1: the BCE-with-logits term of hyb_cross_entropy_dense_* (kind 1) on (z_b, t_b, weight, pos_weight): the criterion's function;
+ *     V > 1:  term_b = sum_c w_c [ pw_c t_c (-L(s_c)) + (1 - t_c) (-L1(s_c)) ],  L(p) = max(log(p), -100),  L1(p) = max(log1p(-p), -100)
+ *             (torch.nn.functional.binary_cross_entropy's clamp; a NaN passes through it), in class order, every product that feeds a
+ *             sum an explicit fma.
+ *   Labels and predictions: y_c = (t_c >= 0.5), so a NaN target is a negative label (its loss term is what the arithmetic gives);
+ *     pred_c = (s_c >= threshold[c]) on the fp32 score that was written;  cells[c] = {tp, fp, fn} (64-bit integer adds, which commute).
+ *   counts: [0] videos seen (B), [1] videos whose scores hold a NaN, [2] exact matches (pred_c == y_c for every c), [3] rows stored in the
+ *     bank (the cursor), [4] rows dropped.
+ *   A video whose scores hold a NaN counts in [1], predicts negative for every class (its positive labels become fn), is never an exact
+ *   match, is stored in the bank with score -inf in every class (it ranks last), and its loss term is the NaN the arithmetic gives.
+ *   Score bank (mean average precision needs every score of the validation set): when both bank pointers are given, video b of this launch
+ *   goes to row r = counts[3] + b if r < capacity: its fp32 scores to bank_scores[r] and its labels y (0 / 1) to bank_labels[r].  Every
+ *   thread reads the cursor before the reduction's first barrier; after the tree thread 0 alone writes counts[3] = min(cursor + B, capacity)
+ *   and counts[4] += the rows that did not fit.  No atomics, the row order is the arrival order, a replayed graph appends (the cursor
+ *   lives on the device), and nothing is ever written at or beyond `capacity`.  Without a bank counts[3] and counts[4] are left as they are.
+ *   pred [B, C] (0 / 1) may be NULL.  The inputs (logits, target, weight, pos_weight, threshold) are only read and must not overlap
+ *   anything the launch writes.
+ *   HYB_E_ARG, before any HIP call: a NULL logits, target, threshold, sums, counts, cells or scores; B < 1, C < 1, views < 1,
+ *   capacity < 0; exactly one of the two bank pointers given; a bank given with capacity == 0; B * views or views * C beyond int. */
+int hyb_eval_multilabel(const float* logits /* [B*V, C] */, const float* target /* [B, C] */,
+                        const float* weight /* [C] or NULL */, const float* pos_weight /* [C] or NULL */,
+                        const float* threshold /* [C] */, int views,
+                        double* sums /* [1] */, long long* counts /* [5] */, long long* cells /* [C, 3] */,
+                        float* bank_scores /* [capacity, C] or NULL */, unsigned char* bank_labels /* [capacity, C] or NULL */,
+                        long long capacity,
+                        unsigned char* pred /* [B, C] or NULL */, float* scores /* [B, C] */,
+                        int B, int C, void* stream);
+
 /* ---- model-level entry points: whole CNN backbone / whole temporal part in ONE call each way ---------------------------
  * They chain the stage-level entry points above on the caller's stream; their purpose is host time (a training step is three
  * operator calls each way), not different arithmetic: results are bit-identical to calling the stages one by one.

@@ -101,6 +101,10 @@ class ClipPipeline:
     per clip (``transform.sample_views``) travel with them, hyb_clips_u8_transform_views is the one kernel, and what is yielded is
     (x fp32 [B*V,Tout,C,Ho,Wo], y int64 [B]) -- what ``model.evaluate(x, y, meter, views=V)`` and ``GraphedEval(..., views=V)`` take.
     ``pipeline.views`` is V (1 without a transform).
+    2-D labels [B, classes] (multi-hot rows, or any dense target): the label slots are fp32 [B, classes], pinned on the host and on the device;
+    floating input is used as given, integer / bool input is converted, and ``y`` is yielded as fp32 [B, classes] -- what
+    HybridBCEWithLogitsLoss, GraphedTrainStep (dense target) and MultiLabelMeter take.  With a mixing transform the yielded row is
+    lam_b y_b + (1 - lam_b) y_partner(b), formed on the host in fp32, in place of a MixTarget.  The first batch decides which kind a pipeline carries.
     A transform with ``antialias=True``: hyb_clips_u8_transform_aa is the one kernel, for the training rows (V = 1) and the evaluation views alike;
     the rows and what is yielded do not change."""
 
@@ -117,18 +121,21 @@ class ClipPipeline:
         """Output clips per source clip: the ``views=`` of the meter, model.evaluate and GraphedEval behind this pipeline."""
         return 1 if self.transform is None else self.transform.views
 
-    def _make_slots(self, shape):
+    def _make_slots(self, shape, label_shape=()):
         B, T, H, W, C = shape
+        # 1-D labels: class indices, int64 [B]; 2-D labels: multi-hot / dense rows, fp32 [B, classes]
+        dense = len(label_shape) == 2
+        yshape, ydtype = ((B, int(label_shape[1])), torch.float32) if dense else ((B,), torch.int64)
         xshape = (B, T, C, H, W)
         if self.transform is not None:
             Tout, (Ho, Wo) = self.transform.out_frames(T), self.transform.size
             xshape = (B * self.views, Tout, C, Ho, Wo)
             mi = self.transform.mean_invstd(C)
             self._mean_invstd = None if mi is None else torch.from_numpy(mi).to(self.device)
-        self._slots = [dict(host=torch.empty(shape, dtype=torch.uint8).pin_memory(), host_y=torch.empty(B, dtype=torch.int64).pin_memory(),
+        self._slots = [dict(host=torch.empty(shape, dtype=torch.uint8).pin_memory(), host_y=torch.empty(yshape, dtype=ydtype).pin_memory(),
                             dev_u8=torch.empty(shape, dtype=torch.uint8, device=self.device),
                             x=torch.empty(xshape, dtype=torch.float32, device=self.device),
-                            y=torch.empty(B, dtype=torch.int64, device=self.device), ready=torch.cuda.Event(), free=torch.cuda.Event())
+                            y=torch.empty(yshape, dtype=ydtype, device=self.device), ready=torch.cuda.Event(), free=torch.cuda.Event())
                        for _ in range(self.depth + 1)]
         for s in self._slots:
             s["free"].record(torch.cuda.current_stream(self.device))
@@ -140,6 +147,7 @@ class ClipPipeline:
                 if self.transform.mixing():
                     s["host_m"] = torch.empty(B, 8, dtype=torch.int32).pin_memory()
                     s["dev_m"] = torch.empty(B, 8, dtype=torch.int32, device=self.device)
+                if self.transform.mixing() and not dense:     # dense rows are blended on the host: no second target, no lam
                     s["host_yb"] = torch.empty(B, dtype=torch.int64).pin_memory()
                     s["y_b"] = torch.empty(B, dtype=torch.int64, device=self.device)
                     s["host_lam"] = torch.empty(B, dtype=torch.float32).pin_memory()
@@ -160,7 +168,15 @@ class ClipPipeline:
         s = self._slots[slot]
         s["free"].synchronize()                               # the consumer has finished with this slot's device tensors
         s["host"].numpy()[...] = frames                       # pageable -> pinned (the decoder could write here directly)
-        s["host_y"].numpy()[...] = np.asarray(labels, dtype=np.int64)
+        dense = s["host_y"].dim() == 2
+        if dense:
+            rows = labels.numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+            if rows.ndim != 2:
+                raise ValueError(f"this pipeline's first batch had 2-D labels {tuple(s['host_y'].shape)}; got labels of shape {rows.shape}")
+            rows = rows.astype(np.float32, copy=False)        # floating input as given, integer / bool input converted
+            s["host_y"].numpy()[...] = rows
+        else:
+            s["host_y"].numpy()[...] = np.asarray(labels, dtype=np.int64)
         views = self.views
         if self.transform is not None and not self.transform.train:
             # the evaluation rows, V adjacent ones per clip, no draw; with the default views they are sample()'s, and one view per clip
@@ -171,9 +187,13 @@ class ClipPipeline:
         mixing = self.transform is not None and self.transform.mixing()
         if mixing:
             rows, lam, partner = self.transform.sample_mix(B, *self.transform.size)
-            s["host_m"].numpy()[...] = rows
-            s["host_lam"].numpy()[...] = lam
-            s["host_yb"].numpy()[...] = s["host_y"].numpy()[partner]            # the partners' labels, gathered here: the device only copies
+            s["host_m"].numpy()[...], own = rows, s["host_y"].numpy()
+            if dense:                                         # the dense row of the mixed clip, in fp32: two products and a sum
+                l = lam.astype(np.float32)[:, None]
+                own[...] = l * own + (np.float32(1) - l) * own[partner]
+            else:
+                s["host_lam"].numpy()[...] = lam
+                s["host_yb"].numpy()[...] = own[partner]      # the partners' labels, gathered here: the device only copies
         photo = self.transform is not None and self.transform.photometric()
         if photo:
             s["host_ph"].numpy()[...] = self.transform.sample_photo(B, self.transform.out_frames(T), *self.transform.size)
@@ -187,6 +207,7 @@ class ClipPipeline:
                 Tout, Ho, Wo = s["x"].shape[1], s["x"].shape[3], s["x"].shape[4]
                 if mixing:
                     s["dev_m"].copy_(s["host_m"], non_blocking=True)
+                if mixing and not dense:
                     s["y_b"].copy_(s["host_yb"], non_blocking=True)
                     s["lam"].copy_(s["host_lam"], non_blocking=True)
                 if photo:
@@ -222,7 +243,7 @@ class ClipPipeline:
                     exhausted = True
                     break
                 if self._slots is None:
-                    self._make_slots(tuple(batch[0].shape))
+                    self._make_slots(tuple(batch[0].shape), tuple(np.shape(batch[1])))
                 self._issue(nxt, batch)
                 pending.append(nxt)
                 nxt = (nxt + 1) % len(self._slots)

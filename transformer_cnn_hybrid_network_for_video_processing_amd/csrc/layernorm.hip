@@ -1040,6 +1040,97 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(HybEvalArgs a, HybCeO
     }
 }
 
+// ---- evaluation of multi-label clips (hyb_eval_multilabel; include/hybrid_hip.h states the rules) ------------------------------------------
+// The same shape as eval_metrics_kernel: ONE workgroup, thread t owns videos t, t + 256, .., the loss in double over the fixed tree, one
+// thread makes the final add.  V == 1: the term is ce_clip_loss_bce itself, the criterion's function.  The score bank is appended without a
+// hand-off: every thread reads the cursor counts[3] before the first barrier, video b owns row cursor + b, and thread 0 moves the cursor
+// after the last barrier, when nobody reads it any more.
+struct HybEvalMlArgs {
+    const float* logits; const float* target; const float* weight; const float* pos_weight; const float* threshold;
+    double* sums; long long* counts; long long* cells; float* bank_scores; unsigned char* bank_labels; long long capacity;
+    unsigned char* pred; float* scores;
+    int B, C, V;
+};
+__device__ __forceinline__ float eval_sigmoid(float z) {                        // ce_clip_dlogit_bce's: no overflow at any z, sg(0) = 0.5
+    const float ez = expf(-fabsf(z));
+    return (z >= 0.f ? 1.f : ez) / (1.f + ez);
+}
+__device__ __forceinline__ float eval_log_floor(float l) { return l < -100.f ? -100.f : l; }      // torch's clamp: a NaN passes through
+__global__ __launch_bounds__(256) void eval_multilabel_kernel(HybEvalMlArgs a) {
+    __shared__ double partd[256];
+    __shared__ int parti[2][256];
+    const int C = a.C, V = a.V;
+    const bool bank = a.bank_scores != nullptr;
+    const long long cursor = a.counts[3];                                       // read by every thread before the first barrier
+    double num = 0.0;
+    int nans = 0, exact = 0;
+    // the inputs are only read here: saying so lets their loads move ahead of the stores and integer adds of the loop below (a batch of 8
+    // videos is 8 lanes walking their rows alone, so what the kernel takes is its chain of dependent memory round trips)
+    const float* __restrict__ logits = a.logits;
+    const float* __restrict__ target = a.target;
+    const float* __restrict__ weight = a.weight;
+    const float* __restrict__ pos_weight = a.pos_weight;
+    const float* __restrict__ threshold = a.threshold;
+    for (int b = threadIdx.x; b < a.B; b += 256) {
+        const float* __restrict__ z = logits + (long long)b * V * C;
+        const float* __restrict__ t = target + (long long)b * C;
+        float* sc = a.scores + (long long)b * C;
+        // a score is NaN exactly when one of its logits is (the sigmoid of anything else lies in [0, 1], and so does a mean of those): the
+        // video's NaN flag, which every prediction below needs, comes from a pass of loads alone
+        bool has_nan = false;
+        for (int i = 0; i < V * C; ++i) has_nan |= z[i] != z[i];
+        float term = V == 1 ? ce_clip_loss_bce(z, weight, pos_weight, t, C) : 0.f;
+        const long long r = cursor + b;
+        const bool store = bank && r >= 0 && r < a.capacity;                    // nothing at or beyond capacity, whatever the cursor holds
+        bool match = !has_nan;
+        for (int c = 0; c < C; ++c) {
+            float s = eval_sigmoid(z[c]);
+            const float tc = t[c];
+            if (V > 1) {
+                for (int v = 1; v < V; ++v) s += eval_sigmoid(z[(long long)v * C + c]);
+                s = s / (float)V;
+                term = fmaf(ce_w(weight, c), fmaf(ce_w(pos_weight, c) * tc, -eval_log_floor(logf(s)), (1.f - tc) * -eval_log_floor(log1pf(-s))), term);
+            }
+            sc[c] = s;
+            const bool y = tc >= 0.5f;                                          // a NaN target: negative
+            const bool p = !has_nan && s >= threshold[c];                       // on the fp32 score just written
+            if (a.pred) a.pred[(long long)b * C + c] = p ? 1 : 0;
+            // integer adds commute: whichever order the owning threads arrive in, the cell ends at the same value
+            if (p || y) atomicAdd(reinterpret_cast<unsigned long long*>(a.cells + 3ll * c + (p ? (y ? 0 : 1) : 2)), 1ull);
+            match &= p == y;
+            if (store) {
+                a.bank_scores[r * C + c] = has_nan ? -INFINITY : s;
+                a.bank_labels[r * C + c] = y ? 1 : 0;
+            }
+        }
+        num += (double)term;
+        nans += has_nan ? 1 : 0;
+        exact += match ? 1 : 0;
+    }
+    const int tid = threadIdx.x;
+    partd[tid] = num;
+    parti[0][tid] = nans; parti[1][tid] = exact;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {                                         // the fixed 256-leaf tree, in double
+        if (tid < h) {
+            partd[tid] += partd[tid + h];
+            parti[0][tid] += parti[0][tid + h]; parti[1][tid] += parti[1][tid + h];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {                                                             // the one add into the caller's block
+        a.sums[0] += partd[0];
+        a.counts[0] += a.B;
+        a.counts[1] += parti[0][0];
+        a.counts[2] += parti[1][0];
+        if (bank) {
+            const long long end = cursor + a.B, stored = end < a.capacity ? end : a.capacity;
+            a.counts[3] = stored;
+            a.counts[4] += end - stored;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int hyb_ln_residual_fwd(int dtype, const void* x, const void* skip, const float* gamma, const float* beta, void* y, float* stats,
@@ -1312,6 +1403,21 @@ extern "C" int hyb_eval_metrics(const float* logits, const long long* target, co
     HYB_CHECK_ARG((long long)B * views <= 0x7fffffffll);
     const HybEvalArgs a{logits, target, sums, counts, confusion, pred, scores, B, C, views, topk};
     hipLaunchKernelGGL(eval_metrics_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, o);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// The multi-label meter's update (eval_multilabel_kernel): one launch of one workgroup that ADDS into sums / counts / cells and appends to the bank.
+extern "C" int hyb_eval_multilabel(const float* logits, const float* target, const float* weight, const float* pos_weight, const float* threshold,
+                                   int views, double* sums, long long* counts, long long* cells, float* bank_scores,
+                                   unsigned char* bank_labels, long long capacity, unsigned char* pred, float* scores, int B, int C,
+                                   void* stream) {
+    HYB_CHECK_ARG(logits && target && threshold && sums && counts && cells && scores && B >= 1 && C >= 1 && views >= 1 && capacity >= 0);
+    HYB_CHECK_ARG((bank_scores != nullptr) == (bank_labels != nullptr) && (!bank_scores || capacity > 0));
+    HYB_CHECK_ARG((long long)B * views <= 0x7fffffffll && (long long)views * C <= 0x7fffffffll);
+    const HybEvalMlArgs a{logits, target, weight, pos_weight, threshold, sums, counts, cells, bank_scores, bank_labels, capacity, pred, scores,
+                          B, C, views};
+    hipLaunchKernelGGL(eval_multilabel_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
     HYB_LAUNCH_CHECK();
     return 0;
 }

@@ -66,6 +66,7 @@ import torch.distributed as dist
 
 from . import ops
 from ._lib import lib, ptr_array
+from .meter import MultiLabelMeter
 
 
 class GraphedTrainStep:
@@ -536,7 +537,11 @@ class GraphedEval:
     The logits are bit-identical to GraphedPredict's on the same input, and the returned tensor is the graph's static output (clone to keep).
     The criterion's class weights are read from its ``weight`` buffer when a replay runs (an in-place update reaches the next replay);
     ``ignore_index`` and ``label_smoothing`` travel by value in the captured launch, and a change of either after capture is refused, as
-    GraphedTrainStep refuses it.  Works unchanged with the weight-average twin ``optimizer.ema_model(model)``."""
+    GraphedTrainStep refuses it.  Works unchanged with the weight-average twin ``optimizer.ema_model(model)``.
+    With a ``meter.MultiLabelMeter`` the captured launch is hyb_eval_multilabel and the static ``y`` is fp32 [B, C].  Nothing travels by
+    value: the criterion's ``weight`` and ``pos_weight`` buffers and the meter's ``threshold`` buffer are captured by address, so an in-place
+    update of any of them reaches the next replay and a REPLACED buffer is refused.  The reset after the warm-up zeroes the bank's cursor
+    too: a freshly built GraphedEval leaves an empty bank, and every replay appends behind the cursor on the device."""
 
     def __init__(self, model, x, y, meter, mask=None, views=1, warmup=3):
         if not hasattr(model, "evaluate"):
@@ -546,7 +551,8 @@ class GraphedEval:
         self.model, self.meter, self.views = model, meter, views
         dev = x.device
         self.x = x.detach().float().clone()                   # static inputs
-        self.y = y.detach().clone()
+        self._multilabel = isinstance(meter, MultiLabelMeter)
+        self.y = y.detach().float().clone() if self._multilabel else y.detach().clone()     # multi-label: the static y is fp32 [B, C]
         self.mask = mask.detach().clone() if mask is not None else None
         self._captured_loss_opts = self._loss_opts_now()
         side = torch.cuda.Stream(device=dev)
@@ -564,14 +570,22 @@ class GraphedEval:
         # the capture did not execute: the meter is still zeroed
 
     def _loss_opts_now(self):
-        """What the captured meter launch carries by value or by address: (ignore_index, label_smoothing, the weight buffer's address)."""
+        """What the captured meter launch carries by value or by address: (ignore_index, label_smoothing, the weight buffer's address); with
+        a MultiLabelMeter the addresses of the criterion's weight and pos_weight buffers and of the meter's threshold buffer."""
         c = self.meter.criterion
+        if self._multilabel:
+            return tuple(None if t is None else t.data_ptr() for t in (*self.meter.loss_options(), self.meter.threshold))
         if c is None:
             return None
         return (c.ignore_index, c.label_smoothing, c.weight.data_ptr() if c.weight is not None else None)
 
     def _check_loss_opts(self):
         now = self._loss_opts_now()
+        if now != self._captured_loss_opts and self._multilabel:
+            what = [n for n, a, b in zip(("criterion's weight buffer", "criterion's pos_weight buffer", "meter's threshold buffer"), now,
+                                         self._captured_loss_opts) if a != b]
+            raise RuntimeError(f"GraphedEval: the {', the '.join(what)} was replaced after capture, but the captured meter launch reads the old "
+                               "address -- construct a new GraphedEval (an in-place update needs none: the buffers are read at replay time)")
         if now != self._captured_loss_opts:
             what = [n for n, a, b in zip(("ignore_index", "label_smoothing", "the weight buffer (replaced, not updated in place)"),
                                          now or (None,) * 3, self._captured_loss_opts or (None,) * 3) if a != b] or ["criterion itself"]

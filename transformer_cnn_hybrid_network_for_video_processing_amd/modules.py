@@ -536,7 +536,8 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
     @torch.no_grad()
     def evaluate(self, x, y, meter, mask=None, views=1):
         """``predict(x, mask)`` followed by ``meter.update(logits, y, views)`` (meter.ClassificationMeter): one more launch behind the forward,
-        no synchronisation.  x [B * views, T, 3, H, W] with the views of one video adjacent, y int64 [B]; returns the logits [B * views, C]."""
+        no synchronisation.  x [B * views, T, 3, H, W] with the views of one video adjacent, y int64 [B]; returns the logits [B * views, C].
+        With a meter.MultiLabelMeter y is the fp32 multi-hot target [B, C] and the launch is hyb_eval_multilabel."""
         logits = self.predict(x, mask)
         meter.update(logits, y, views)
         return logits

@@ -34,6 +34,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::clip_transform_views V evaluation views (windows x crops) of every source clip in one launch: V rows per clip, the source read in place
     hybrid::clip_transform_aa    clip_transform_views with the antialiased resize (torchvision's Resize(antialias=True)): a separable triangle filter
     hybrid::eval_metrics_    one launch behind the logits that adds loss, top-1 / top-k, confusion matrix into a meter's state (no autograd formula)
+    hybrid::eval_multilabel_ the multi-label twin: BCE loss, per-class tp / fp / fn, exact matches, and the scores appended to a bank for exact mAP
 """
 import ctypes
 import functools
@@ -761,6 +762,52 @@ def eval_metrics_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ig
 def eval_metrics_fake(logits, target, weight, ignore_index, has_ignore, label_smoothing, topk, views, sums, counts, confusion):
     return (target.new_empty(target.shape, dtype=torch.int64),
             logits.new_empty((target.shape[0] if views > 1 else 0, logits.shape[1]), dtype=torch.float32))
+
+
+def eval_multilabel_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], threshold: Tensor, views: int,
+                       sums: Tensor, counts: Tensor, cells: Tensor, bank_scores: Optional[Tensor],
+                       bank_labels: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """The multi-label meter's update (hyb_eval_multilabel): ONE launch that ADDS this batch into sums (float64 [1]: the BCE loss numerator),
+    counts (int64 [5]: videos seen, NaN videos, exact matches, rows stored in the bank, rows dropped) and cells (int64 [C, 3]: tp, fp, fn per
+    class) and appends the scores and labels to the bank (fp32 / uint8 [capacity, C], or both None) behind the cursor counts[3]
+    -> (pred uint8 [B, C], scores fp32 [B, C]: the views' mean sigmoid).  logits [B * views, C] fp32 contiguous, the views of one video
+    adjacent; target fp32 [B, C]; weight / pos_weight [C] or None; threshold fp32 [C].  Never synchronises."""
+    _require_cuda(logits, target, weight, pos_weight, threshold, sums, counts, cells, bank_scores, bank_labels)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError(f"logits must be a contiguous float32 [B * views, C] tensor, got {logits.dtype} {tuple(logits.shape)}"
+                         + ("" if logits.is_contiguous() else " (not contiguous)"))
+    if views < 1:
+        raise ValueError(f"views must be >= 1, got {views}")
+    C = logits.shape[1]
+    if (target.dim() != 2 or target.dtype != torch.float32 or not target.is_contiguous() or target.shape[1] != C
+            or target.shape[0] * views != logits.shape[0]):
+        raise ValueError(f"expected a contiguous float32 multi-hot target [B, C] with logits [B * views, C]: got {target.dtype} "
+                         f"{tuple(target.shape)}, logits {tuple(logits.shape)}, views {views}")
+    B = target.shape[0]
+    if B < 1 or C < 1:
+        raise ValueError(f"an empty batch cannot be evaluated (logits {tuple(logits.shape)})")
+    if target.device != logits.device:
+        raise RuntimeError(f"target is on {target.device} but the logits are on {logits.device}")
+    if (bank_scores is None) != (bank_labels is None):
+        raise ValueError("bank_scores and bank_labels go together: give both or neither")
+    capacity = 0 if bank_scores is None else int(bank_scores.shape[0]) if bank_scores.dim() == 2 else -1
+    if bank_scores is not None and capacity < 1:
+        raise ValueError(f"a score bank must be a [capacity >= 1, C] tensor, got {tuple(bank_scores.shape)}")
+    for name, t, dtype, shape in (("threshold", threshold, torch.float32, (C,)), ("sums", sums, torch.float64, (1,)),
+                                  ("counts", counts, torch.int64, (5,)), ("cells", cells, torch.int64, (C, 3)),
+                                  ("bank_scores", bank_scores, torch.float32, (capacity, C)), ("bank_labels", bank_labels, torch.uint8, (capacity, C))):
+        if t is not None and not (t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == logits.device):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {logits.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    weight, pos_weight = _ce_weight(weight, C, logits.device), _ce_weight(pos_weight, C, logits.device)
+    pred = torch.empty((B, C), dtype=torch.uint8, device=logits.device)
+    scores = torch.empty((B, C), dtype=torch.float32, device=logits.device)
+    lib.call("hyb_eval_multilabel", logits, target, weight, pos_weight, threshold, int(views), sums, counts, cells, bank_scores, bank_labels,
+             capacity, pred, scores, B, C, _stream())
+    return pred, scores
+
+
+def eval_multilabel_fake(logits, target, weight, pos_weight, threshold, views, sums, counts, cells, bank_scores, bank_labels):
+    return (target.new_empty(target.shape, dtype=torch.uint8), target.new_empty(target.shape, dtype=torch.float32))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1834,6 +1881,10 @@ _define("cross_entropy_dense_bwd", "(Tensor dloss, Tensor logits, Tensor target,
 _define("eval_metrics_", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int topk, int views, "
         "Tensor(a!) sums, Tensor(b!) counts, Tensor(c!)? confusion) -> (Tensor, Tensor)", eval_metrics_op, eval_metrics_fake)
 _LIB.impl("eval_metrics_", _inference_only("eval_metrics_"), "Autograd")
+_define("eval_multilabel_", "(Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, Tensor threshold, int views, Tensor(a!) sums, "
+        "Tensor(b!) counts, Tensor(c!) cells, Tensor(d!)? bank_scores, Tensor(e!)? bank_labels) -> (Tensor, Tensor)", eval_multilabel_op,
+        eval_multilabel_fake)
+_LIB.impl("eval_multilabel_", _inference_only("eval_multilabel_"), "Autograd")
 _define("backbone", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, bool training, "
         "float momentum, float eps, int dt) -> Tensor[]", backbone_op, backbone_fake,
         lambda x, ws, gs, bs, rms, rvs, training, momentum, eps, dt: list(_BackboneFn.apply(x, len(ws), training, momentum, eps, dt, *ws, *gs, *bs,
