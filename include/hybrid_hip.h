@@ -905,6 +905,35 @@ int hyb_adamw_step_dev_guard(int count, float* const* params, const float* const
                              const double* hyper, const double* ema_hyper /* or NULL */, long long k, long long step, long long* step_inc,
                              unsigned int* advance_ticket, const float* clip, const long long* guard /* [2] */, void* stream);
 
+/* ---- parameter groups: one AdamW launch for all of them -----------------------------------------------------------------------------------
+ * (New symbols only; hyb_abi_version() stays 9.)  Weight decay off for biases and norm parameters, a learning rate per layer: such recipes
+ * are parameter groups, and with the calls above every group is a launch of its own.  The caller's DEVICE blocks are contiguous over the
+ * groups -- `double hyper[groups, 6]`, `double ema_hyper[groups, 2]`, rows as above -- so one launch can serve them all: its tensor table
+ * carries one byte per tensor, the group, and a workgroup forms its scalars from the row of its tensor's group.
+ *
+ * hyb_adamw_step_dev_groups: every device-path step over the tensors of SEVERAL groups behind one call.  group: a HOST array of `count`
+ * bytes, group[i] < groups <= 255 the parameter group of tensor i (tensors of one group need not be adjacent); hyper, ema_hyper: the BASES
+ * of the blocks.  acc == NULL (then k == 1 and grads != NULL): hyb_adamw_step_dev, or hyb_adamw_step_dev_ema when ema and ema_hyper are
+ * given (all groups keep the average or none does); acc != NULL: hyb_adamw_step_dev_acc.  guard == NULL: the unguarded launches, clip may
+ * be NULL; guard != NULL: hyb_adamw_step_dev_guard (clip is then the step's norm_out).  Every element of every tensor comes out bit for bit
+ * as the call over its group alone, with that group's rows, gives it.  The counter is advanced once, by the last launch of the call, so an
+ * advancing step may span several groups.  80 tensors per launch, 72 with acc, 64 with ema.  -1 as the calls it stands for, and for
+ * group == NULL, a group[i] >= groups, groups < 1 or > 255. */
+int hyb_adamw_step_dev_groups(int count, float* const* params, const float* const* grads /* or NULL */, float* const* exp_avg,
+                              float* const* exp_avg_sq, float* const* acc /* or NULL */, float* const* ema /* or NULL */, const long long* numel,
+                              const unsigned char* group, int groups, const double* hyper /* [groups, 6] */,
+                              const double* ema_hyper /* [groups, 2], or NULL */, long long k, long long step, long long* step_inc,
+                              unsigned int* advance_ticket, const float* clip /* or NULL */, const long long* guard /* [2], or NULL */, void* stream);
+/* hyb_adamw_hyper_set_groups: hyb_adamw_hyper_set for `count` groups and hyb_adamw_ema_set for `ema_count` groups in ONE one-workgroup
+ * launch: row group[i] of hyper gets values[6 i .. 6 i + 5], row ema_group[i] of ema_hyper gets ema_values[2 i], ema_values[2 i + 1].
+ * group, values, ema_group, ema_values are HOST arrays, copied into the kernel arguments before the call returns (no staging memory, nothing
+ * to keep alive); more than 60 rows of a block = more launches.  Either count may be 0 (its three pointers are then not read), not both.
+ * NOT meant to be captured, as the calls it stands for.  -1 for a value they refuse, a group index >= groups or listed twice in one list,
+ * groups < 1 or > 255. */
+int hyb_adamw_hyper_set_groups(double* hyper /* [groups, 6] */, double* ema_hyper /* [groups, 2], or NULL */, int groups, int count,
+                               const unsigned char* group, const double* values /* [count, 6] */, int ema_count,
+                               const unsigned char* ema_group, const double* ema_values /* [ema_count, 2] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

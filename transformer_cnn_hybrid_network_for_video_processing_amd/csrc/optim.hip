@@ -11,6 +11,9 @@
 // separate sum, scale or memset pass.
 // The non-finite guard: hyb_grad_norm_guard / hyb_grad_norm_acc_guard also decide, on the device, whether the step is skipped (the norm is not
 // finite), and hyb_adamw_step_dev_guard reads the decision: a skipped step stores nothing to the model.
+// Parameter groups: hyb_adamw_step_dev_groups serves the tensors of ALL groups from one launch -- the table carries one byte per tensor, its
+// group, and thread 0 of a workgroup forms its scalars from that group's row of the device blocks hyper[groups, 6] / ema_hyper[groups, 2];
+// hyb_adamw_hyper_set_groups writes the rows of several groups in one launch.
 #include <type_traits>
 
 #include "hyb_common.h"
@@ -328,6 +331,23 @@ static_assert(sizeof(AdamArgs) <= 4096 && sizeof(AdamDevArgs) <= 4096 && sizeof(
 template <typename Base> struct AdamGuarded : Base { const long long* guard; };
 static_assert(sizeof(AdamGuarded<AdamDevArgs>) <= 4096 && sizeof(AdamGuarded<AdamEmaArgs>) <= 4096 && sizeof(AdamGuarded<AdamAccArgs>) <= 4096 &&
               sizeof(AdamGuarded<AdamEmaAccArgs>) <= 4096, "the tensor table travels in the kernel arguments");
+// The grouped launches (hyb_adamw_step_dev_groups): one byte per tensor, the index of its parameter group; hyper and ema_hyper are the BASES
+// of the blocks double [groups, 6] and double [groups, 2], of which a workgroup reads the row of its tensor's group.  Types of their own
+// again, with the members of the tables above under the same names (e / acc hold one unused entry in the variants without them; guard is
+// read by the guarded instantiations only).  The accumulating table gives up four tensors for the bytes: 72, not 76.
+constexpr int ADAM_GROUPS_MAX = 255;                               // group indices are bytes; 255 itself is not one
+template <bool EMA, bool ACCUM> struct AdamGroupArgs : AdamDevTable<EMA ? 64 : ACCUM ? 72 : ADAM_MAX> {
+    static constexpr int MAX = EMA ? 64 : ACCUM ? 72 : ADAM_MAX;
+    unsigned char group[MAX];
+    float* e[EMA ? MAX : 1];
+    const double* ema_hyper;
+    float* acc[ACCUM ? MAX : 1];
+    long long k;
+    float inv_k;
+    const long long* guard;
+};
+static_assert(sizeof(AdamGroupArgs<false, false>) <= 4096 && sizeof(AdamGroupArgs<true, false>) <= 4096 && sizeof(AdamGroupArgs<false, true>) <= 4096 &&
+              sizeof(AdamGroupArgs<true, true>) <= 4096, "the tensor table travels in the kernel arguments");
 
 // adam_one with every fused multiply-add written out, so that the device path computes what adamw_kernel computes as the compiler contracts
 // it (test_unclipped_equals_no_clipping: bit-equal to the plain launch).  adamw_kernel's 16-byte groups end in p = fma(p, decay, -(step * q)),
@@ -355,9 +375,10 @@ template <bool ACCUM, typename Args> __device__ __forceinline__ long long adam_s
     else return a.step + (a.step_inc ? *a.step_inc : 0ll) - skipped;
 }
 
-template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_dev_scalars(const Args& a, float* out /* [8] */, long long skipped = 0ll) {
+// (hyper: the six values of the tensor's parameter group -- a.hyper itself, or in a grouped launch the group's row of the block)
+template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_dev_scalars(const Args& a, const double* hyper, float* out /* [8] */, long long skipped = 0ll) {
 #pragma clang fp contract(off)                                    // 1.0 - lr * wd: a product rounded, then a difference, as on the host (no fma)
-    const double lr = a.hyper[0], b1 = a.hyper[1], b2 = a.hyper[2], eps = a.hyper[3], wd = a.hyper[4];
+    const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
     const double tt = (double)adam_step_number<ACCUM>(a, skipped);
     const double prod = lr * wd;
     out[0] = (float)(1.0 - prod);
@@ -372,12 +393,12 @@ template <bool ACCUM = false, typename Args> __device__ __forceinline__ void ada
 
 // the average's decay at step t = step + *step_inc (n = t - 1 updates so far): d = warmup ? min(decay, (1 + n) / (10 + n)) : decay, in double;
 // d and 1 - d are rounded to fp32 once each
-template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_ema_scalars(const Args& a, float* out /* [2] */, long long skipped = 0ll) {
+template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_ema_scalars(const Args& a, const double* ema_hyper, float* out /* [2] */, long long skipped = 0ll) {
 #pragma clang fp contract(off)
-    const double decay = a.ema_hyper[0];
+    const double decay = ema_hyper[0];
     const double n = (double)(adam_step_number<ACCUM>(a, skipped) - 1ll);
     double d = decay;
-    if (a.ema_hyper[1] != 0.0) {
+    if (ema_hyper[1] != 0.0) {
         const double w = (1.0 + n) / (10.0 + n);
         d = w < decay ? w : decay;
     }
@@ -387,8 +408,8 @@ template <bool ACCUM = false, typename Args> __device__ __forceinline__ void ada
 
 template <bool EMA, int ACC> using AdamDevTableArgs =
     std::conditional_t<ACC != GRAD_PLAIN, std::conditional_t<EMA, AdamEmaAccArgs, AdamAccArgs>, std::conditional_t<EMA, AdamEmaArgs, AdamDevArgs>>;
-template <bool EMA, int ACC, bool GUARD = false> using AdamDevKernelArgs =
-    std::conditional_t<GUARD, AdamGuarded<AdamDevTableArgs<EMA, ACC>>, AdamDevTableArgs<EMA, ACC>>;
+template <bool EMA, int ACC, bool GUARD = false, bool GROUPS = false> using AdamDevKernelArgs =
+    std::conditional_t<GROUPS, AdamGroupArgs<EMA, ACC != GRAD_PLAIN>, std::conditional_t<GUARD, AdamGuarded<AdamDevTableArgs<EMA, ACC>>, AdamDevTableArgs<EMA, ACC>>>;
 
 // the counter's one read (thread 0, in front of the barrier) is complete in every workgroup that has taken a ticket: see adamw_kernel
 template <typename Args> __device__ __forceinline__ void adam_dev_advance(const Args& a) {
@@ -409,7 +430,11 @@ template <typename Args> __device__ __forceinline__ void adam_dev_advance(const 
 // no scalars and stores nothing to p / m / v / e (not even their old values); it stores +0.0f over the accumulators (ACCUM: the poison must
 // not stay in them) and takes its ticket, so the counter -- which also seeds dropout -- advances as after an applied step.  Otherwise the
 // same body with the step number less skipped_total.
-template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false> __global__ __launch_bounds__(256) void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC, GUARD> a) {
+// GROUPS: hyb_adamw_step_dev_groups -- the table holds the tensors of several parameter groups, and thread 0 reads the hyper-parameters from
+// the row of ITS tensor's group (a.group[ti]) where the other launches read the one row they were given.  Nothing else differs: every
+// element comes out as the launch over its group alone gives it.
+template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false, bool GROUPS = false> __global__ __launch_bounds__(256)
+void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS> a) {
     constexpr bool ACCUM = ACC != GRAD_PLAIN, HAS_G = ACC != GRAD_ACC;
     __shared__ float s_sc[EMA ? 10 : 8];
     __shared__ int s_skip;
@@ -443,8 +468,14 @@ template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false> __global__ __launc
         bool skip = false;
         if constexpr (GUARD) { skip = a.guard[0] != 0ll; skipped = a.guard[1]; s_skip = skip ? 1 : 0; }
         if (!skip) {
-            adam_dev_scalars<ACCUM>(a, s_sc, skipped);
-            if constexpr (EMA) adam_ema_scalars<ACCUM>(a, s_sc + 8, skipped);
+            const double* hyper = a.hyper;
+            if constexpr (GROUPS) hyper += HYPER_N * (int)a.group[ti];
+            adam_dev_scalars<ACCUM>(a, hyper, s_sc, skipped);
+            if constexpr (EMA) {
+                const double* ema_hyper = a.ema_hyper;
+                if constexpr (GROUPS) ema_hyper += 2 * (int)a.group[ti];
+                adam_ema_scalars<ACCUM>(a, ema_hyper, s_sc + 8, skipped);
+            }
         }
     }
     __syncthreads();
@@ -523,21 +554,44 @@ __global__ __launch_bounds__(64) void ema_set_kernel(double* ema_hyper, double d
     if (threadIdx.x < 2) ema_hyper[threadIdx.x] = threadIdx.x == 0 ? decay : warmup;
 }
 
+// hyb_adamw_hyper_set_groups: the rows of several groups of hyper[groups, 6] and of ema_hyper[groups, 2] from ONE one-workgroup launch.  The
+// values travel in the kernel arguments as hyb_adamw_hyper_set's do; 60 rows of each block fit the 4 KB.  A group appears at most once in
+// each list (checked by the caller), so no two threads write one word.
+constexpr int HYPER_SET_MAX = 60;
+struct HyperSetArgs {
+    double* hyper;
+    double* ema_hyper;
+    int n, ema_n;
+    double v[HYPER_SET_MAX * HYPER_N];
+    double ema_v[HYPER_SET_MAX * 2];
+    unsigned char group[HYPER_SET_MAX], ema_group[HYPER_SET_MAX];
+};
+static_assert(sizeof(HyperSetArgs) <= 4096, "the values travel in the kernel arguments");
+
+__global__ __launch_bounds__(256) void hyper_set_groups_kernel(HyperSetArgs a) {
+    for (int i = threadIdx.x; i < a.n * HYPER_N; i += 256) a.hyper[HYPER_N * (int)a.group[i / HYPER_N] + i % HYPER_N] = a.v[i];
+    for (int i = threadIdx.x; i < a.ema_n * 2; i += 256) a.ema_hyper[2 * (int)a.ema_group[i / 2] + i % 2] = a.ema_v[i];
+}
+
 // hyb_adamw_step_dev (ema == NULL) and hyb_adamw_step_dev_ema: the tensor table in launches of at most the variant's capacity, the last
-// of which advances the counter
-template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false>
+// of which advances the counter.  GROUPS (hyb_adamw_step_dev_groups): the grouped table and kernel; group[i] is tensor i's parameter group,
+// hyper / ema_hyper the bases of the blocks.
+template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false, bool GROUPS = false>
 int adamw_dev_launch(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                      float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
-                     long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream, float* const* acc = nullptr, long long k = 1, const long long* guard = nullptr) {
-    constexpr int MAX = ACC != GRAD_PLAIN ? (EMA ? ADAM_EMA_ACC_MAX : ADAM_ACC_MAX) : (EMA ? ADAM_EMA_MAX : ADAM_MAX);
+                     long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream, float* const* acc = nullptr, long long k = 1, const long long* guard = nullptr,
+                     const unsigned char* group = nullptr) {
+    constexpr int MAX = GROUPS ? AdamGroupArgs<EMA, ACC != GRAD_PLAIN>::MAX
+                               : ACC != GRAD_PLAIN ? (EMA ? ADAM_EMA_ACC_MAX : ADAM_ACC_MAX) : (EMA ? ADAM_EMA_MAX : ADAM_MAX);
     for (int first = 0; first < count; first += MAX) {
-        AdamDevKernelArgs<EMA, ACC, GUARD> a{};
+        AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS> a{};
         const int n = count - first < MAX ? count - first : MAX;
         int chunks = 0;
         for (int i = 0; i < n; ++i) {
             a.t[i] = AdamTensor{params[first + i], ACC == GRAD_ACC ? nullptr : grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
             if constexpr (EMA) a.e[i] = ema[first + i];
             if constexpr (ACC != GRAD_PLAIN) a.acc[i] = acc[first + i];
+            if constexpr (GROUPS) a.group[i] = group[first + i];
             a.chunk_begin[i] = chunks;
             chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
         }
@@ -549,7 +603,7 @@ int adamw_dev_launch(int count, float* const* params, const float* const* grads,
         if constexpr (GUARD) a.guard = guard;
         a.advance = (advance_ticket && first + MAX >= count) ? step_inc : nullptr;            // the last launch of the call advances the counter
         a.ticket = advance_ticket;
-        hipLaunchKernelGGL((adamw_dev_kernel<EMA, ACC, GUARD>), dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((adamw_dev_kernel<EMA, ACC, GUARD, GROUPS>), dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
         HYB_LAUNCH_CHECK();
     }
     return 0;
@@ -738,6 +792,66 @@ extern "C" int hyb_adamw_step_dev_guard(int count, float* const* params, const f
     if (ema) return grads ? HYB_GUARDED(true, GRAD_ACC_G, grads, ema, ema_hyper) : HYB_GUARDED(true, GRAD_ACC, nullptr, ema, ema_hyper);
     return grads ? HYB_GUARDED(false, GRAD_ACC_G, grads, nullptr, nullptr) : HYB_GUARDED(false, GRAD_ACC, nullptr, nullptr, nullptr);
 #undef HYB_GUARDED
+}
+
+// the same variants over the tensors of several parameter groups: hyper / ema_hyper are the bases of the blocks, group[i] picks tensor i's row
+extern "C" int hyb_adamw_step_dev_groups(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                         float* const* acc, float* const* ema, const long long* numel, const unsigned char* group, int groups,
+                                         const double* hyper, const double* ema_hyper, long long k, long long step, long long* step_inc,
+                                         unsigned int* advance_ticket, const float* clip, const long long* guard, void* stream) {
+    HYB_CHECK_ARG(count > 0 && params && exp_avg && exp_avg_sq && numel && group && groups >= 1 && groups <= ADAM_GROUPS_MAX && hyper && k >= 1 &&
+                  step >= 1 && (!advance_ticket || step_inc) && (ema != nullptr) == (ema_hyper != nullptr) && (!guard || clip) &&
+                  (acc || (k == 1 && grads)));
+    long long chunks = 0;
+    for (int i = 0; i < count; ++i) {
+        HYB_CHECK_ARG(params[i] && (!grads || grads[i]) && exp_avg[i] && exp_avg_sq[i] && (!acc || (acc[i] && acc[i] != params[i])) &&
+                      (!ema || (ema[i] && ema[i] != params[i])) && numel[i] > 0 && (int)group[i] < groups);
+        chunks += hyb_cdiv(numel[i], ADAM_CHUNK);
+    }
+    HYB_CHECK_ARG(chunks < (1ll << 31));
+#define HYB_GROUPED(EMA, ACC, GUARD, G, E, EH) \
+    adamw_dev_launch<EMA, ACC, GUARD, true>(count, params, G, exp_avg, exp_avg_sq, E, numel, hyper, EH, step, step_inc, advance_ticket, clip, stream, acc, k, guard, group)
+#define HYB_GROUPED_ACC(EMA, GUARD, E, EH) \
+    (!acc ? HYB_GROUPED(EMA, GRAD_PLAIN, GUARD, grads, E, EH) : grads ? HYB_GROUPED(EMA, GRAD_ACC_G, GUARD, grads, E, EH) : HYB_GROUPED(EMA, GRAD_ACC, GUARD, nullptr, E, EH))
+    if (guard) return ema ? HYB_GROUPED_ACC(true, true, ema, ema_hyper) : HYB_GROUPED_ACC(false, true, nullptr, nullptr);
+    return ema ? HYB_GROUPED_ACC(true, false, ema, ema_hyper) : HYB_GROUPED_ACC(false, false, nullptr, nullptr);
+#undef HYB_GROUPED_ACC
+#undef HYB_GROUPED
+}
+
+extern "C" int hyb_adamw_hyper_set_groups(double* hyper, double* ema_hyper, int groups, int count, const unsigned char* group, const double* values,
+                                          int ema_count, const unsigned char* ema_group, const double* ema_values, void* stream) {
+    HYB_CHECK_ARG(groups >= 1 && groups <= ADAM_GROUPS_MAX && count >= 0 && ema_count >= 0 && count + ema_count > 0 &&
+                  (count == 0 || (hyper && group && values)) && (ema_count == 0 || (ema_hyper && ema_group && ema_values)));
+    bool seen[ADAM_GROUPS_MAX] = {}, ema_seen[ADAM_GROUPS_MAX] = {};
+    for (int i = 0; i < count; ++i) {
+        const double* v = values + (long long)HYPER_N * i;          // the checks of hyb_adamw_hyper_set, and no group twice
+        HYB_CHECK_ARG((int)group[i] < groups && !seen[group[i]] && v[0] >= 0.0 && v[1] >= 0.0 && v[1] < 1.0 && v[2] >= 0.0 && v[2] < 1.0 && v[3] >= 0.0 &&
+                      v[4] >= 0.0 && v[5] == v[5]);
+        seen[group[i]] = true;
+    }
+    for (int i = 0; i < ema_count; ++i) {
+        const double* v = ema_values + 2ll * i;                     // the checks of hyb_adamw_ema_set
+        HYB_CHECK_ARG((int)ema_group[i] < groups && !ema_seen[ema_group[i]] && v[0] >= 0.0 && v[0] < 1.0 && (v[1] == 0.0 || v[1] == 1.0));
+        ema_seen[ema_group[i]] = true;
+    }
+    for (int first = 0; first < count || first < ema_count; first += HYPER_SET_MAX) {        // more than 60 rows of a block: more launches
+        HyperSetArgs a{};
+        a.hyper = hyper; a.ema_hyper = ema_hyper;
+        a.n = count - first < 0 ? 0 : count - first < HYPER_SET_MAX ? count - first : HYPER_SET_MAX;
+        a.ema_n = ema_count - first < 0 ? 0 : ema_count - first < HYPER_SET_MAX ? ema_count - first : HYPER_SET_MAX;
+        for (int i = 0; i < a.n; ++i) {
+            a.group[i] = group[first + i];
+            for (int j = 0; j < HYPER_N; ++j) a.v[HYPER_N * i + j] = values[(long long)HYPER_N * (first + i) + j];
+        }
+        for (int i = 0; i < a.ema_n; ++i) {
+            a.ema_group[i] = ema_group[first + i];
+            a.ema_v[2 * i] = ema_values[2ll * (first + i)]; a.ema_v[2 * i + 1] = ema_values[2ll * (first + i) + 1];
+        }
+        hipLaunchKernelGGL(hyper_set_groups_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+        HYB_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 extern "C" int hyb_adamw_hyper_set(double* hyper, double lr, double beta1, double beta2, double eps, double weight_decay, double max_grad_norm,

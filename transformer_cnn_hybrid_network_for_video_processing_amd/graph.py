@@ -71,6 +71,7 @@ from .meter import MultiLabelMeter
 
 class GraphedTrainStep:
     _guard_on = False                # set by the constructor: whether the captured optimizer launches are the guarded ones
+    _merge_on = None                 # set by the constructor: the optimizer's merge_groups at capture (None: nothing captured, nothing to hold it to)
 
     def __init__(self, model, criterion, optimizer, x, y, mask=None, process_group=None, warmup=3, dynamic_hyper=False, accumulation_steps=1):
         if not (hasattr(model, "forward_backbone") and hasattr(model, "forward_temporal")):
@@ -139,8 +140,11 @@ class GraphedTrainStep:
                     dist.broadcast(t.data, src=0, group=process_group)
 
         ops.set_step_counter(self.counter)
-        # one parameter group: the AdamW launch itself advances the counter (no separate `counter += 1` launch per step)
-        self._advancing = sum(1 for g in optimizer.param_groups if any(p.requires_grad for p in g["params"])) == 1
+        # one parameter group, or several that the optimizer serves from one launch (merge_groups, fixed by the capture): the AdamW launch
+        # itself advances the counter (no separate `counter += 1` launch per step)
+        self._merge_on = bool(getattr(optimizer, "merge_groups", False))
+        self._advancing = (sum(1 for g in optimizer.param_groups if any(p.requires_grad for p in g["params"])) == 1
+                           or (hasattr(optimizer, "merges_groups") and optimizer.merges_groups()))
         optimizer.set_step_counter(self.counter, advance=self._advancing)
         self._acc_tabs = {}                                    # world > 1, k > 1: the pointer tables of the two eager accumulate launches
         self._captured = False
@@ -232,6 +236,9 @@ class GraphedTrainStep:
         if bool(getattr(self.optimizer, "skip_nonfinite", False)) != self._guard_on:
             raise RuntimeError("GraphedTrainStep: skip_nonfinite was switched on or off after capture; the captured norm and AdamW launches are "
                                "(not) the guarded ones -- set it on the optimizer before constructing GraphedTrainStep")
+        if self._merge_on is not None and bool(getattr(self.optimizer, "merge_groups", False)) != self._merge_on:
+            raise RuntimeError("GraphedTrainStep: merge_groups was switched on or off after capture; the captured AdamW launches are (not) the "
+                               "one launch over all parameter groups -- set it on the optimizer before constructing GraphedTrainStep")
         now = self._loss_opts_now()
         if now != self._captured_loss_opts:
             what = [n for n, a, b in zip(("ignore_index", "label_smoothing", "the weight buffer (replaced, not updated in place)"), now,

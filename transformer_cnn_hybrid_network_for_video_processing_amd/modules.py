@@ -548,6 +548,42 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
     def temporal_parameters(self):
         return list(self.token_proj.parameters()) + list(self.encoder.parameters()) + list(self.head.parameters())
 
+    def param_groups(self, lr=1e-3, weight_decay=1e-2, layer_decay=1.0, no_decay_1d=True):
+        """The usual fine-tuning recipe as a list of parameter-group dicts for HybridAdamW (which serves them all from one AdamW launch,
+        merge_groups) or torch.optim.AdamW: no weight decay on biases, BatchNorm and LayerNorm parameters (`no_decay_1d`: every parameter
+        with ndim <= 1 gets weight_decay 0.0), and a learning rate that decays layer by layer towards the input,
+            lr * layer_decay ** (D - depth)
+        with depth i for conv stage encoder{i+1} (i = 0 .. S - 1), S for token_proj, S + 1 + l for encoder layer l (its attention,
+        feed-forward and LayerNorm) and D = S + 1 + L for the head, which trains at `lr`.  Every trainable parameter is in exactly one
+        group, in depth order; empty groups are dropped; layer_decay=1.0 merges the depths, so the defaults give two groups and
+        no_decay_1d=False then one.  Each group also carries "name" ("stage1.decay", "layer0.no_decay", ...) and "lr_scale" (its factor of
+        `lr`, for schedulers that set lr = base * lr_scale themselves); "lr" itself is set, so a torch scheduler's initial_lr is right."""
+        if lr < 0.0 or weight_decay < 0.0 or not 0.0 < layer_decay <= 1.0:
+            raise ValueError("param_groups: lr >= 0, weight_decay >= 0 and 0 < layer_decay <= 1")
+        S, L = self.num_stages, self.encoder.num_layers
+        depths = [(f"stage{i + 1}", [getattr(self, f"encoder{i + 1}")]) for i in range(S)] + [("token_proj", [self.token_proj])]
+        depths += [(f"layer{l}", [self.encoder.attention_layers[l], self.encoder.feedforward_layers[l], self.encoder.layer_norm[l]]) for l in range(L)]
+        depths.append(("head", [self.head]))
+        D = len(depths) - 1
+        groups, seen = {}, set()
+        for depth, (name, mods) in enumerate(depths):
+            scale = float(layer_decay) ** (D - depth)
+            for p in (p for m in mods for p in m.parameters()):
+                if not p.requires_grad or id(p) in seen:
+                    continue
+                seen.add(id(p))
+                no_decay = no_decay_1d and p.ndim <= 1
+                # one learning rate for all depths: the depth is no part of the key, and the groups are named after what tells them apart
+                key = (depth if layer_decay != 1.0 else 0, no_decay)
+                if key not in groups:
+                    kind = ("no_decay" if no_decay else "decay") if no_decay_1d else None
+                    label = ".".join(s for s in (name if layer_decay != 1.0 else None, kind) if s) or "all"
+                    groups[key] = {"params": [], "lr": lr * scale, "weight_decay": 0.0 if no_decay else weight_decay, "name": label, "lr_scale": scale}
+                groups[key]["params"].append(p)
+        if len(seen) != sum(1 for p in self.parameters() if p.requires_grad):
+            raise RuntimeError("model has trainable parameters outside its conv stages, token projection, encoder layers and head")
+        return [groups[k] for k in sorted(groups)]
+
     def forward(self, x, mask=None):
         h, B = self.forward_backbone(x)
         return self.forward_temporal(h, B, mask)

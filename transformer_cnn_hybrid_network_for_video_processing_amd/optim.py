@@ -33,7 +33,14 @@ Two things a training run needs on top of that, both built on hyper-parameters t
     `clip_coef` is unspecified.  In eager use `state[p]["step"]` counts ATTEMPTED steps until `fold_skipped()` (one host read; `state_dict()`
     calls it) subtracts the device count, so saved steps are applied-update counts.  Out of scope: BatchNorm running statistics are
     updated by the forward pass and are not rolled back (an inf activation reaches them, as in torch), and a learning-rate scheduler
-    stepped by the host is not held back on a skipped step (as with GradScaler)."""
+    stepped by the host is not held back on a skipped step (as with GradScaler).
+  * `merge_groups=True` (the default): on the device path ONE AdamW launch serves the tensors of all parameter groups
+    (`hyb_adamw_step_dev_groups`: the tensor table carries each tensor's group, and a workgroup reads that group's row of the device
+    blocks), `accumulate()` is one launch and `sync_hyper()` uploads all changed groups with one (`hyb_adamw_hyper_set_groups`) -- so
+    no-decay groups and a per-layer learning rate (`TransformerCNNHybrid.param_groups`) cost no launch per group, and an advancing step
+    counter works with them.  Bit for bit the per-group launches' result.  It applies when more than one group has gradients, all of
+    them keep a weight average or none does, they share the step number and there are at most 255 groups; otherwise, and on the plain
+    by-value path, every group is a launch of its own as before.  An attribute like `skip_nonfinite`, neither a group key nor state."""
 import copy
 import ctypes
 
@@ -45,7 +52,7 @@ from .ops import _stream
 
 class HybridAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_decay=None, ema_warmup=False,
-                 accumulation_steps=1, skip_nonfinite=False):
+                 accumulation_steps=1, skip_nonfinite=False, merge_groups=True):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
@@ -55,6 +62,7 @@ class HybridAdamW(torch.optim.Optimizer):
         # (checked before the base class touches anything; neither a param-group key nor state: the accumulators are zero between steps)
         self._accum_k = self._check_accumulation(accumulation_steps)
         self._skip_nonfinite = self._check_skip_nonfinite(skip_nonfinite)    # (handled the same way: a constructor argument and an attribute)
+        self._merge_groups = self._check_merge_groups(merge_groups)          # (and this one: which launches serve the groups, not what they compute)
         self._guard = None           # device int64 [2]: skip_now (the last guarded step was skipped), skipped_total (since the last fold)
         # max_grad_norm sits in the groups only so that it travels in the state dict: clipping is global, every group carries the same value;
         # ema_decay / ema_warmup are per group (None: that group takes the launch without the average)
@@ -109,6 +117,39 @@ class HybridAdamW(torch.optim.Optimizer):
             self.fold_skipped()
             self._skip_nonfinite = flag
 
+    @staticmethod
+    def _check_merge_groups(flag):
+        if not isinstance(flag, bool):
+            raise ValueError("merge_groups must be a bool")
+        return flag
+
+    @property
+    def merge_groups(self):
+        return self._merge_groups
+
+    def set_merge_groups(self, flag):
+        """Switch the one-launch step over all parameter groups on or off between steps (the cached pointer tables go with it)."""
+        flag = self._check_merge_groups(flag)
+        if flag != self._merge_groups:
+            self._merge_groups = flag
+            self._tables.clear()
+            self._acc_tables.clear()
+
+    def _merged(self, stepped):
+        """Whether ONE hyb_adamw_step_dev_groups call serves every live group -- a group with a parameter for which stepped(p) holds: the
+        device path, more than one live group, all of them with the average or all without, one step number, at most 255 groups."""
+        if not self._merge_groups or len(self.param_groups) > 255 or not self.uses_device_hyper():
+            return False
+        live = [g for g in self.param_groups if any(stepped(p) for p in g["params"])]
+        if len(live) < 2 or len({self._group_ema(g) is not None for g in live}) != 1:
+            return False
+        return len({int(self.state.get(p, {}).get("step", 0)) for g in live for p in g["params"] if stepped(p)}) == 1
+
+    def merges_groups(self):
+        """Whether step() will serve all parameter groups from one AdamW launch, judged by requires_grad (for a caller that captures
+        step() before any gradient exists, GraphedTrainStep): an advancing step counter is then allowed with several groups."""
+        return self._merged(lambda p: p.requires_grad)
+
     def _guard_block(self):
         """The guard block, created and zeroed EAGERLY, for the reason _device_buffers gives."""
         if self._guard is None:
@@ -159,8 +200,8 @@ class HybridAdamW(torch.optim.Optimizer):
     def set_step_counter(self, counter, advance=False):
         """With a device counter the step number used by the kernel is state['step'] + counter, read on the device: one captured
         launch then serves every replay of a hipGraph.  advance=True: step() also adds 1 to the counter (inside the AdamW launch, after
-        every workgroup has read it) -- the caller then needs no separate `counter += 1` launch; every parameter must then be in
-        ONE group, so that one launch ends the step."""
+        every workgroup has read it) -- the caller then needs no separate `counter += 1` launch; ONE call must then end the step: every
+        parameter in one group, or several groups that step() merges (merges_groups())."""
         self._step_counter = counter
         self._advance = bool(advance) and counter is not None
         if self._advance and (self._ticket is None or self._ticket.device != counter.device):
@@ -221,9 +262,23 @@ class HybridAdamW(torch.optim.Optimizer):
 
     def sync_hyper(self):
         """Upload every group's (lr, betas, eps, weight_decay, max_grad_norm), and (ema_decay, ema_warmup) where the group keeps an average,
-        that differs from what the device holds (one tiny launch per changed group on the current stream; the host never waits).  Must NOT
-        be captured: the values travel as kernel arguments, a captured upload would put the capture-time values back at every replay."""
+        that differs from what the device holds (one tiny launch on the current stream for all changed groups, hyb_adamw_hyper_set_groups;
+        the per-group calls where a single group changed, merge_groups is off or there are more than 255; the host never waits).  Must NOT be captured: the
+        values travel as kernel arguments, a captured upload would put the capture-time values back at every replay."""
         hyper = self._device_buffers()
+        changed = [(gi, vals) for gi, vals in enumerate(map(self._group_hyper, self.param_groups)) if self._hyper_sent.get(gi) != vals]
+        ema_changed = [(gi, ema) for gi, ema in enumerate(map(self._group_ema, self.param_groups)) if ema is not None and self._ema_sent.get(gi) != ema]
+        if self._merge_groups and len({gi for gi, _ in changed + ema_changed}) > 1 and len(self.param_groups) <= 255:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
+            lib.call("hyb_adamw_hyper_set_groups", hyper, self._ema_hyper, len(self.param_groups),
+                     len(changed), (ctypes.c_ubyte * len(changed))(*[gi for gi, _ in changed]),
+                     (ctypes.c_double * (6 * len(changed)))(*[v for _, vals in changed for v in vals]),
+                     len(ema_changed), (ctypes.c_ubyte * len(ema_changed))(*[gi for gi, _ in ema_changed]),
+                     (ctypes.c_double * (2 * len(ema_changed)))(*[v for _, ema in ema_changed for v in ema]), _stream())
+            self._hyper_sent.update(changed)
+            self._ema_sent.update(ema_changed)
+            return
         for gi, group in enumerate(self.param_groups):
             vals = self._group_hyper(group)
             if self._hyper_sent.get(gi) != vals:
@@ -361,13 +416,17 @@ class HybridAdamW(torch.optim.Optimizer):
     @torch.no_grad()
     def accumulate(self):
         """End one of the micro-batches 1 .. k - 1: acc += grad for every parameter with a gradient, one hyb_grad_accumulate launch per
-        group.  The gradients are only read (zero_grad() as usual before the next backward)."""
+        group, or one for all groups where step() merges them.  The gradients are only read (zero_grad() as usual before the next backward)."""
         if self._accum_k < 2:
             raise RuntimeError("HybridAdamW.accumulate() needs accumulation_steps > 1 (with 1, step() does not read the accumulators)")
         if self._acc_only:
             raise RuntimeError("HybridAdamW.accumulate(): the accumulators are bound to external buffers whose owner adds the gradients itself")
-        for gi, group in enumerate(self.param_groups):
-            ps = [p for p in group["params"] if p.grad is not None]
+        # where step() serves all groups from one launch, so does this: the tensors of every live group in one table (key "all")
+        merged = self._merged(lambda p: p.grad is not None)
+        tables = [("all", [p for group in self.param_groups for p in group["params"]])] if merged else \
+            [(gi, group["params"]) for gi, group in enumerate(self.param_groups)]
+        for gi, params in tables:
+            ps = [p for p in params if p.grad is not None]
             if not ps:
                 continue
             accs = self._accumulators(ps)
@@ -394,17 +453,27 @@ class HybridAdamW(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         live = [gi for gi, group in enumerate(self.param_groups) if any(p.grad is not None for p in group["params"])]
-        if self._advance and len(live) != 1:
+        # one hyb_adamw_step_dev_groups call over the tensors of all live groups (device path only): one call ends the step, so the counter
+        # may advance with several groups
+        merged = self._merged(lambda p: p.grad is not None)
+        if self._advance and len(live) != 1 and not merged:
             raise RuntimeError("HybridAdamW: an advancing step counter needs exactly one parameter group with gradients")
         dev_path = self.uses_device_hyper()
         accum = self._accum_k > 1
         guard = self._guard_block() if self._skip_nonfinite else None     # (first: a refusal under capture leaves the step counts untouched)
-        work = []                                   # per live group: (group index, tensor count, tables, gradients, step number)
-        for gi, group in enumerate(self.param_groups):
-            ps = [p for p in group["params"] if p.grad is not None]
-            if not ps:
-                continue
-            ema = self._group_ema(group)
+        work = []                                   # per launch unit: (first group index, tensor count, tables, gradients, step number)
+        ema_groups = []                             # the live groups that keep an average
+        # a launch unit: the live groups one AdamW call serves -- all of them (merged; table key "all"), or one each (key: the group's index)
+        for key, unit in ([("all", live)] if merged else [(gi, [gi]) for gi in live]):
+            ps, layout, ema = [], [], None
+            for gi in unit:
+                group = self.param_groups[gi]
+                gps = [p for p in group["params"] if p.grad is not None]
+                ema = self._group_ema(group)        # (merged: every group of the unit has one, or none has)
+                if ema is not None:
+                    ema_groups.append(gi)
+                ps += gps
+                layout += [gi] * len(gps)
             accs = self._accumulators(ps) if accum else None     # (first: a refusal under capture leaves the step counts untouched)
             for p in ps:
                 if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
@@ -431,14 +500,14 @@ class HybridAdamW(torch.optim.Optimizer):
                          for p in ps]
             if accum:                               # ... and, in an accumulated step, the accumulators (the key's last entry)
                 addrs = [a + (acc.data_ptr(),) for a, acc in zip(addrs, accs)]
-            tab = self._tables.get(gi)
-            if tab is None or tab[1] != addrs:
+            tab = self._tables.get(key)
+            if tab is None or tab[1] != addrs or tab[9] != layout:      # (merged: ... and while every tensor stays in its group)
                 tab = (None, addrs, ptr_array([a[0] for a in addrs]), ptr_array([a[1] for a in addrs]), ptr_array([a[2] for a in addrs]),
                        (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps]), None if ema is None else ptr_array([a[3] for a in addrs]),
-                       ptr_array([a[-1] for a in addrs]) if accum else None)
-                self._tables[gi] = tab
+                       ptr_array([a[-1] for a in addrs]) if accum else None, (ctypes.c_ubyte * len(ps))(*layout) if merged else None, layout)
+                self._tables[key] = tab
             grads = None if accum and self._acc_only else self._float_grads(ps)
-            work.append((gi, len(ps), tab, grads, steps.pop()))
+            work.append((unit[0], len(ps), tab, grads, steps.pop()))
         counter = self._step_counter
         ticket = self._ticket if self._advance else None
         if not dev_path:
@@ -453,7 +522,7 @@ class HybridAdamW(torch.optim.Optimizer):
         hyper = self._device_buffers()
         if torch.cuda.is_current_stream_capturing():
             # only hyb_grad_norm and hyb_adamw_step_dev are recorded; the upload is the replaying caller's (GraphedTrainStep.step)
-            if len(self._hyper_sent) != len(self.param_groups) or any(gi not in self._ema_sent for gi, _, tab, _, _ in work if tab[6] is not None):
+            if len(self._hyper_sent) != len(self.param_groups) or any(gi not in self._ema_sent for gi in ema_groups):
                 raise RuntimeError("HybridAdamW: hyper-parameters were never uploaded -- call sync_hyper() before capturing step()")
         else:
             self.sync_hyper()
@@ -487,7 +556,10 @@ class HybridAdamW(torch.optim.Optimizer):
                          guard, _stream())
             clip_coef = self._norm_out
         for gi, n, tab, grads, step in work:
-            if guard is not None:                   # every variant below behind one entry point, which reads the decision when it runs
+            if merged:                              # every variant below, for all groups: the blocks' bases, and each tensor's group
+                lib.call("hyb_adamw_step_dev_groups", n, tab[2], grads, tab[3], tab[4], tab[7], tab[6], tab[5], tab[8], len(self.param_groups), hyper,
+                         None if tab[6] is None else self._ema_hyper, self._accum_k, step, counter, ticket, clip_coef, guard, _stream())
+            elif guard is not None:                 # every variant below behind one entry point, which reads the decision when it runs
                 lib.call("hyb_adamw_step_dev_guard", n, tab[2], grads, tab[3], tab[4], tab[7], tab[6], tab[5], hyper[gi],
                          None if tab[6] is None else self._ema_hyper[gi], self._accum_k, step, counter, ticket, clip_coef, guard, _stream())
             elif accum:                               # the same launch on (acc + g) / k, which leaves the accumulators zeroed
