@@ -366,6 +366,41 @@ int hyb_cross_entropy_dense_bwd(const float* logits, const float* target /* [B,C
                                 const float* pos_weight /* [C] or NULL */, int kind, float label_smoothing, const float* dloss /* [1] */,
                                 float* dlogits, int B, int C, void* stream);
 
+/* hyb_cross_entropy_focal_* / hyb_cross_entropy_asym_*: the two focusing losses for imbalanced data, reduction "mean" (new symbols,
+ *   hyb_abi_version() stays 9).  fp32 arithmetic throughout; every product that feeds a sum is one fused multiply-add; a clip's sums over
+ *   classes run in class order and the sum over clips goes through the fixed 256-leaf tree of the other families: results are reproducible
+ *   bit for bit.  Each exponent (gamma, gamma_pos, gamma_neg) must be 0 or >= 1: between 0 and 1 the derivative of base^g is singular at
+ *   base == 0, which a clipped negative reaches exactly.  Wherever an exponent is 0, x^0 is taken as 1 and its derivative as 0; x^(g-1) at
+ *   g == 1 is 1.  HYB_E_ARG, without a launch: a NULL pointer (other than weight and pos_weight), an exponent that is neither 0 nor >= 1
+ *   (NaN and infinity included), clip outside [0, 1).
+ *   FOCAL, class-index targets y (Lin et al. 2017, softmax form).  keep_b, w, lse_b, den and the out-of-range / all-ignored rules are
+ *   those of hyb_cross_entropy_opts_*; there is no label smoothing.  With mx_b = max_c z_bc, s_b = sum_c exp(z_bc - mx_b), p = softmax(z_b):
+ *     u_b = (sum_{c != y} exp(z_bc - mx_b)) / s_b   -- the other classes' probability as that sum, not as 1 - p_y,
+ *     term_b = keep_b w[y] u_b^gamma (lse_b - z_by),   loss = (sum_b term_b) / den,
+ *     dlogits[b,c] = (dloss / den) keep_b w[y] M_b (p_bc - [c == y]),   M_b = u^gamma + gamma u^(gamma-1) p_y (lse_b - z_by).
+ *   gamma == 0 gives hyb_cross_entropy_opts_* with the same weight and ignore_index (label_smoothing 0), loss and gradient bit for bit.
+ *   ASYMMETRIC, dense fp32 targets t [B,C] (Ridnik et al. 2021).  With ez = exp(-|z|), sp(x) = log1p(exp(-|x|)) + max(-x, 0),
+ *   p = sigmoid(z) and q = sigmoid(-z) in the overflow-safe form of hyb_cross_entropy_dense_* kind 1, m = clip:
+ *     logp = -sp(z),   r = max(p - m, 0),   logn = -sp(-z) if m == 0, else log(min(q + m, 1)),
+ *     base = t q + (1 - t) r,   g_t = gamma_pos t + gamma_neg (1 - t),   L = 1 + (pw_c - 1) t,
+ *     cell_bc = -w_c L base^g_t (t logp + (1 - t) logn),   loss = (1 / (B C)) sum_bc cell_bc,
+ *   the clip's sum formed as fma(-(w_c L), base^g_t (t logp + (1 - t) logn), sum) over c.  dlogits is (dloss / (B C)) times the derivative
+ *   of exactly this expression, the focusing factor included: d r / dz = p q where p > m, else 0; d logn / dz = -p for m == 0, else
+ *   -p q / min(q + m, 1) where p > m, else 0.  Soft rows are used as given (their per-cell exponent g_t may then fall between 0 and 1); a
+ *   NaN propagates.  gamma_pos == gamma_neg == g with m == 0, w = 1 - alpha and pw = alpha / (1 - alpha) is the sigmoid focal loss with
+ *   reduction "mean"; all three 0 is kind-1 BCE in value (another form of the same number: not bit for bit).  z = +-100 gives a finite
+ *   loss and gradient. */
+int hyb_cross_entropy_focal_fwd(const float* logits, const long long* target, const float* weight /* [C] or NULL */, long long ignore_index,
+                                int has_ignore, float gamma, float* loss /* [1] */, int B, int C, void* stream);
+int hyb_cross_entropy_focal_bwd(const float* logits, const long long* target, const float* weight /* [C] or NULL */, long long ignore_index,
+                                int has_ignore, float gamma, const float* dloss /* [1] */, float* dlogits, int B, int C, void* stream);
+int hyb_cross_entropy_asym_fwd(const float* logits, const float* target /* [B,C] */, const float* weight /* [C] or NULL */,
+                               const float* pos_weight /* [C] or NULL */, float gamma_pos, float gamma_neg, float clip, float* loss /* [1] */,
+                               int B, int C, void* stream);
+int hyb_cross_entropy_asym_bwd(const float* logits, const float* target /* [B,C] */, const float* weight /* [C] or NULL */,
+                               const float* pos_weight /* [C] or NULL */, float gamma_pos, float gamma_neg, float clip,
+                               const float* dloss /* [1] */, float* dlogits, int B, int C, void* stream);
+
 /* hyb_eval_metrics: the update of an accumulating classification meter, ONE launch of one 256-thread workgroup behind the logits (new
  *   symbol, hyb_abi_version() stays 9).  It ADDS into sums, counts and confusion and overwrites none of them: repeated launches, and
  *   replays of a graph that holds the launch, accumulate; the caller zeroes the three before the first.  Launches on one stream are ordered
@@ -555,6 +590,39 @@ int hyb_temporal_ce_dense_bwd(int dtype, const float* dloss, const float* logits
                               int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
                               unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes,
                               void* stream);
+
+/* hyb_temporal_ce_focal_* / hyb_temporal_ce_asym_*: hyb_temporal_ce_opts_* / hyb_temporal_ce_dense_* with the arguments of
+ *   hyb_cross_entropy_focal_* / hyb_cross_entropy_asym_* (same meaning, same argument checks) in place of theirs: the same launches, the
+ *   same B + 1 floats of ce_scratch, target, weight and pos_weight read when the kernels run; the exponents and clip travel by value.
+ *   Results equal hyb_temporal_* followed by the stand-alone loss bit for bit; shapes the fused tail does not take run it as launches of
+ *   its own.  (New symbols, hyb_abi_version() stays 9.) */
+int hyb_temporal_ce_focal_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                              const float* head_w, const float* head_b, const float* mask, const long long* target /* [B] */,
+                              const float* weight /* [classes] or NULL */, long long ignore_index, int has_ignore, float gamma, void* feat,
+                              void* tok, void* enc_saved, void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW,
+                              int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
+                              const unsigned long long* seed_inc, void* stream);
+int hyb_temporal_ce_focal_bwd(int dtype, const float* dloss, const float* logits, const long long* target /* [B] */,
+                              const float* weight /* [classes] or NULL */, long long ignore_index, int has_ignore, float gamma,
+                              const float* token_w, const float* const* enc_params, const float* head_w, const float* mask, const void* feat,
+                              const void* enc_saved, const void* enc_out, float* dtoken_w, float* dtoken_b, float* const* enc_grads,
+                              float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
+                              int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int hyb_temporal_ce_asym_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                             const float* head_w, const float* head_b, const float* mask, const float* target /* [B,classes] */,
+                             const float* weight /* [classes] or NULL */, const float* pos_weight /* [classes] or NULL */, float gamma_pos,
+                             float gamma_neg, float clip, void* feat, void* tok, void* enc_saved, void* enc_out, float* logits, float* loss,
+                             float* ce_scratch, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes,
+                             float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc, void* stream);
+int hyb_temporal_ce_asym_bwd(int dtype, const float* dloss, const float* logits, const float* target /* [B,classes] */,
+                             const float* weight /* [classes] or NULL */, const float* pos_weight /* [classes] or NULL */, float gamma_pos,
+                             float gamma_neg, float clip, const float* token_w, const float* const* enc_params, const float* head_w,
+                             const float* mask, const void* feat, const void* enc_saved, const void* enc_out, float* dtoken_w,
+                             float* dtoken_b, float* const* enc_grads, float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW,
+                             int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
+                             unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /* ---- FCT, the reference's "Fully Convolutional Transformer" (FCT.py:24-254; SURVEY.md section 8f-1, first "next" row) -----------
  * FORWARD entry points (the backward is the next step of this row).  Arrays are NHWC fp32 with the TRUE channel count

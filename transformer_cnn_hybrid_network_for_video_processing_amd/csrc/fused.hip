@@ -267,7 +267,7 @@ static int temporal_fwd_impl(int dtype, const void* h, const float* token_w, con
                              void* enc_out, float* logits, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes,
                              float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc, const long long* target,
                              float* loss, float* ce_scratch, void* stream, const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr,
-                             const HybCeDense* dense = nullptr) {
+                             const HybCeDense* dense = nullptr, const HybCeFocal* focal = nullptr) {
     HYB_CHECK_ARG(h && token_w && enc_params && head_w && feat && tok && enc_saved && enc_out && logits && B > 0 && S > 0 && HW > 0);
     const int N = B * S;
     const bool h16 = (dtype & HYB_H_BF16) != 0;                 // the pooled map is bf16, everything from the frame features on is fp32
@@ -285,9 +285,12 @@ static int temporal_fwd_impl(int dtype, const void* h, const float* token_w, con
                                  tail ? &t : nullptr));
     if (tail)
         return hyb_temporal_tail_fwd(dtype, t.f, t.x1, t.gamma, t.beta, enc_out, t.st2, B, S, D, t.eps, t.out_scale, t.p_drop, t.seed, seed_inc, head_w,
-                                     head_b, logits, classes, target, loss, ce_scratch, (hipStream_t)stream, ce, mix, dense);
+                                     head_b, logits, classes, target, loss, ce_scratch, (hipStream_t)stream, ce, mix, dense, focal);
     HYB_TRY(hyb_head_fwd(dtype, enc_out, head_w, head_b, logits, B, S, D, classes, stream));
-    if (dense) HYB_TRY(hyb_cross_entropy_dense_fwd(logits, dense->target, ce->weight, dense->pos_weight, dense->kind, ce->label_smoothing, loss, B, classes,
+    if (focal && dense) HYB_TRY(hyb_cross_entropy_asym_fwd(logits, dense->target, ce->weight, dense->pos_weight, focal->gamma, focal->gamma_neg, focal->clip,
+                                                           loss, B, classes, stream));
+    else if (focal) HYB_TRY(hyb_cross_entropy_focal_fwd(logits, target, ce->weight, ce->ignore_index, ce->has_ignore, focal->gamma, loss, B, classes, stream));
+    else if (dense) HYB_TRY(hyb_cross_entropy_dense_fwd(logits, dense->target, ce->weight, dense->pos_weight, dense->kind, ce->label_smoothing, loss, B, classes,
                                                    stream));
     else if (mix) HYB_TRY(hyb_cross_entropy_mix_fwd(logits, target, mix->target_b, mix->lam, ce->weight, ce->ignore_index, ce->has_ignore, ce->label_smoothing, loss, B,
                                                classes, stream));
@@ -329,7 +332,8 @@ static int temporal_bwd_impl(int dtype, const float* dlogits, const float* logit
                              const void* enc_out, float* dtoken_w, float* dtoken_b, float* const* enc_grads, float* dhead_w, float* dhead_b, void* dh,
                              int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
                              unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes, void* stream,
-                             const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr) {
+                             const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr,
+                             const HybCeFocal* focal = nullptr) {
     HYB_CHECK_ARG((dlogits || (logits && (target || dense) && dloss)) && token_w && enc_params && head_w && feat && enc_saved && enc_out && dtoken_w && enc_grads &&
                   dhead_w && dh && workspace);
     const bool h16 = (dtype & HYB_H_BF16) != 0;                 // dh is written as bf16
@@ -350,7 +354,7 @@ static int temporal_bwd_impl(int dtype, const float* dlogits, const float* logit
     if (tail) {
         const HybEncBwdTail t = hyb_encoder_bwd_tail(dtype, enc_params, enc_saved, enc_ws, B, S, D, Hid, L, H, layer_p, seed);
         HYB_TRY(hyb_temporal_tail_bwd(dtype, dlogits, logits, target, dloss, head_w, enc_out, t.f, t.gamma, t.stats, t.dx, t.dskip, t.ln_part, t.ln_rows,
-                                      head_part, B, S, D, classes, t.out_scale, t.p_drop, t.seed, seed_inc, (hipStream_t)stream, ce, mix, dense));
+                                      head_part, B, S, D, classes, t.out_scale, t.p_drop, t.seed, seed_inc, (hipStream_t)stream, ce, mix, dense, focal));
         const long long cd = (long long)classes * D;
         const HybDwRider hr{head_part, dhead_w, dhead_b, B, cd + classes, cd};
         HYB_TRY(hyb_encoder_bwd_impl(dtype, nullptr, mask, enc_params, enc_grads, enc_saved, dtok, B, S, D, Hid, L, H, attn_p, layer_p, seed, seed_inc, enc_ws,
@@ -359,7 +363,11 @@ static int temporal_bwd_impl(int dtype, const float* dlogits, const float* logit
         const float* dl = dlogits;
         if (!dl) {      // cross-entropy backward as its own launch, into the head of the (not yet used) dfeat scratch
             HYB_CHECK_ARG((size_t)B * classes * sizeof(float) <= lay.dfeat_bytes);
-            if (dense) HYB_TRY(hyb_cross_entropy_dense_bwd(logits, dense->target, ce->weight, dense->pos_weight, dense->kind, ce->label_smoothing, dloss,
+            if (focal && dense) HYB_TRY(hyb_cross_entropy_asym_bwd(logits, dense->target, ce->weight, dense->pos_weight, focal->gamma, focal->gamma_neg,
+                                                                   focal->clip, dloss, (float*)dfeat, B, classes, stream));
+            else if (focal) HYB_TRY(hyb_cross_entropy_focal_bwd(logits, target, ce->weight, ce->ignore_index, ce->has_ignore, focal->gamma, dloss,
+                                                                (float*)dfeat, B, classes, stream));
+            else if (dense) HYB_TRY(hyb_cross_entropy_dense_bwd(logits, dense->target, ce->weight, dense->pos_weight, dense->kind, ce->label_smoothing, dloss,
                                                            (float*)dfeat, B, classes, stream));
             else if (mix) HYB_TRY(hyb_cross_entropy_mix_bwd(logits, target, mix->target_b, mix->lam, ce->weight, ce->ignore_index, ce->has_ignore, ce->label_smoothing,
                                                        dloss, (float*)dfeat, B, classes, stream));
@@ -467,4 +475,61 @@ extern "C" int hyb_temporal_ce_dense_bwd(int dtype, const float* dloss, const fl
     return temporal_bwd_impl(dtype, nullptr, logits, nullptr, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
                              enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
                              workspace_bytes, stream, &ce, nullptr, &dense);
+}
+
+// index focal and the asymmetric loss in the temporal part's own launches (include/hybrid_hip.h); shapes the tail does not take run the
+// stand-alone launches behind the same entry points
+extern "C" int hyb_temporal_ce_focal_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                                         const float* head_w, const float* head_b, const float* mask, const long long* target, const float* weight,
+                                         long long ignore_index, int has_ignore, float gamma, void* feat, void* tok, void* enc_saved, void* enc_out,
+                                         float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
+                                         int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
+                                         void* stream) {
+    const HybCeOpts ce{weight, ignore_index, has_ignore, 0.f};
+    const HybCeFocal focal{gamma, 0.f, 0.f};
+    HYB_CHECK_ARG(target && loss && ce_scratch && hyb_ce_focal_ok(ce, focal, nullptr));
+    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
+                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, target, loss, ce_scratch, stream, &ce, nullptr, nullptr, &focal);
+}
+extern "C" int hyb_temporal_ce_focal_bwd(int dtype, const float* dloss, const float* logits, const long long* target, const float* weight,
+                                         long long ignore_index, int has_ignore, float gamma, const float* token_w, const float* const* enc_params,
+                                         const float* head_w, const float* mask, const void* feat, const void* enc_saved, const void* enc_out,
+                                         float* dtoken_w, float* dtoken_b, float* const* enc_grads, float* dhead_w, float* dhead_b, void* dh, int B, int S,
+                                         int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
+                                         unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+    const HybCeOpts ce{weight, ignore_index, has_ignore, 0.f};
+    const HybCeFocal focal{gamma, 0.f, 0.f};
+    HYB_CHECK_ARG(dloss && logits && target && hyb_ce_focal_ok(ce, focal, nullptr));
+    return temporal_bwd_impl(dtype, nullptr, logits, target, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
+                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
+                             workspace_bytes, stream, &ce, nullptr, nullptr, &focal);
+}
+extern "C" int hyb_temporal_ce_asym_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                                        const float* head_w, const float* head_b, const float* mask, const float* target, const float* weight,
+                                        const float* pos_weight, float gamma_pos, float gamma_neg, float clip, void* feat, void* tok, void* enc_saved,
+                                        void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D,
+                                        int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
+                                        const unsigned long long* seed_inc, void* stream) {
+    const HybCeOpts ce{weight, 0, 0, 0.f};
+    const HybCeDense dense{target, pos_weight, 1};
+    const HybCeFocal focal{gamma_pos, gamma_neg, clip};
+    HYB_CHECK_ARG(loss && ce_scratch && hyb_ce_focal_ok(ce, focal, &dense));
+    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
+                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, nullptr, loss, ce_scratch, stream, &ce, nullptr, &dense, &focal);
+}
+extern "C" int hyb_temporal_ce_asym_bwd(int dtype, const float* dloss, const float* logits, const float* target, const float* weight,
+                                        const float* pos_weight, float gamma_pos, float gamma_neg, float clip, const float* token_w,
+                                        const float* const* enc_params, const float* head_w, const float* mask, const void* feat,
+                                        const void* enc_saved, const void* enc_out, float* dtoken_w, float* dtoken_b, float* const* enc_grads,
+                                        float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
+                                        int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    const HybCeOpts ce{weight, 0, 0, 0.f};
+    const HybCeDense dense{target, pos_weight, 1};
+    const HybCeFocal focal{gamma_pos, gamma_neg, clip};
+    HYB_CHECK_ARG(dloss && logits && hyb_ce_focal_ok(ce, focal, &dense));
+    return temporal_bwd_impl(dtype, nullptr, logits, nullptr, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
+                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
+                             workspace_bytes, stream, &ce, nullptr, &dense, &focal);
 }

@@ -96,16 +96,22 @@ struct HybCeMix { const long long* target_b; const float* lam; };
 // travel in HybCeOpts (whose ignore fields are unused).
 struct HybCeDense { const float* target; const float* pos_weight; int kind; };
 int hyb_ce_dense_ok(const HybCeOpts& o, const HybCeDense& d);
+// the focusing scalars as the *_focal_* / *_asym_* entry points and kernels carry them, by value.  Index focal: gamma (gamma_neg and clip
+// are 0), beside HybCeOpts (no label smoothing).  Asymmetric: gamma is the positives' exponent, gamma_neg the negatives', clip the
+// probability shift m in [0, 1), beside HybCeOpts (weight only) and a HybCeDense of kind 1 (target, pos_weight).
+struct HybCeFocal { float gamma; float gamma_neg; float clip; };
+int hyb_ce_focal_ok(const HybCeOpts& o, const HybCeFocal& f, const HybCeDense* d);
 // ce != nullptr (a target is given): the loss with options, in the same one launch; mix != nullptr (needs ce): two targets per clip;
-// dense != nullptr (needs ce, target == nullptr, no mix): the dense-target loss
+// dense != nullptr (needs ce, target == nullptr, no mix): the dense-target loss; focal != nullptr (needs ce, no mix): index focal with a
+// target, the asymmetric loss with dense (kind 1)
 int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float* gamma, const float* beta, void* enc_out, float* stats, int B, int S, int D,
                           float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const float* W, const float* bias,
                           float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st, const HybCeOpts* ce = nullptr,
-                          const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr);
+                          const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr, const HybCeFocal* focal = nullptr);
 int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* W, const void* enc_out,
                           const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part, int ln_rows, float* head_part, int B, int S,
                           int D, int C, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, hipStream_t st,
-                          const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr);
+                          const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr, const HybCeFocal* focal = nullptr);
 // linear.hip
 int hyb_linear_bwd_wt(int dtype, const void* x, int ldx, const float* W, const void* Wt, const void* y, const void* dy, void* dx, int accumulate_dx, float* dW,
                       float* db, int M, int N, int K, int relu, void* ws, size_t ws_bytes, hipStream_t st);

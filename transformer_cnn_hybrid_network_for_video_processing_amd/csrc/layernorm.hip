@@ -624,6 +624,127 @@ __global__ __launch_bounds__(256) void ce_dense_bwd_kernel(const float* __restri
                                                     : ce_clip_dlogit_soft(lg, o.weight, t, C, c, g, o.label_smoothing);
 }
 
+// ---- focal and asymmetric losses (include/hybrid_hip.h states both definitions) ------------------------------------------------------------
+// x^g and d(x^g)/dx = g x^(g-1) under the family's rules: an exponent of 0 gives exactly 1 and a derivative of exactly 0, x^(g-1) at g == 1
+// is exactly 1.  (Every g the entry points take is 0 or >= 1; the per-cell exponent of a soft asymmetric row may fall between: powf then.)
+__device__ __forceinline__ float ce_pow(float x, float g) { return g == 0.f ? 1.f : g == 1.f ? x : g == 2.f ? x * x : powf(x, g); }
+__device__ __forceinline__ float ce_dpow(float x, float g) { return g == 0.f ? 0.f : g == 1.f ? 1.f : g * ce_pow(x, g - 1.f); }
+// Index focal: term_b = keep_b w[y] u^g (lse_b - z_by), u = (sum_{c != y} exp(z_c - mx)) / s in class order -- the other classes' softmax
+// mass as a sum, not 1 - p_y, which cancels for a confident clip.  keep, den, the out-of-range and all-ignored rules are ce_clip_loss_opts'
+// (no label smoothing), and so are the log-sum-exp loops: u's numerator is a second accumulator in the loop that forms s -- no further pass
+// over the logits, which the backward reads from global memory: a pass is a memory round trip on the tail's critical path -- and leaves s as
+// it was, so g == 0 gives ce_clip_loss_opts' / ce_clip_dlogit_opts' bits ((1 - 0) * x there is x).
+__device__ __forceinline__ float ce_clip_loss_focal(const float* lg, const float* w, long long t, int C, const HybCeOpts& o, float gm) {
+    if (!ce_keep(t, o)) return 0.f;
+    if (!(t >= 0 && t < C)) return NAN;
+    float mx = -INFINITY;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[c]);
+    float s = 0.f, a = 0.f;
+    for (int c = 0; c < C; ++c) { const float e = expf(lg[c] - mx); s += e; if (c != (int)t) a += e; }
+    const float lse = logf(s) + mx;
+    const float r = ce_w(w, (int)t) * (lse - lg[(int)t]);
+    if (gm == 0.f) return r;
+    return ce_pow(a / s, gm) * r;
+}
+// one clip's d(loss)/d(logits[c]), g = dloss / den:  g w[y] M (p_c - [c == y]),  M = u^gm + gm u^(gm-1) p_y (lse - z_y)
+__device__ __forceinline__ float ce_clip_dlogit_focal(const float* lg, const float* w, long long t, int C, int c, float g, const HybCeOpts& o, float gm) {
+    if (!ce_keep(t, o)) return 0.f;
+    if (!(t >= 0 && t < C)) return NAN;
+    float mx = -INFINITY;
+    for (int k = 0; k < C; ++k) mx = fmaxf(mx, lg[k]);
+    const float zt = lg[(int)t];
+    float s = 0.f, a = 0.f;
+    for (int k = 0; k < C; ++k) { const float e = expf(lg[k] - mx); s += e; if (k != (int)t) a += e; }
+    const float p = expf(lg[c] - mx) / s;
+    const float r = ce_w(w, (int)t) * (p - (c == (int)t ? 1.f : 0.f));
+    if (gm == 0.f) return g * r;
+    const float u = a / s, py = expf(zt - mx) / s;
+    const float M = fmaf(ce_dpow(u, gm) * py, (logf(s) + mx) - zt, ce_pow(u, gm));
+    return g * (M * r);
+}
+__global__ __launch_bounds__(256) void ce_focal_fwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target, float* __restrict__ loss,
+                                                           int B, int C, HybCeOpts o, HybCeFocal fo) {
+    __shared__ float part[256];
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) acc += ce_clip_loss_focal(logits + (long long)b * C, o.weight, target[b], C, o, fo.gamma);
+    const float num = ce_tree_sum(acc, part);
+    const float den = ce_den(target, o.weight, B, C, o, part);
+    if (threadIdx.x == 0) loss[0] = ce_loss_opts(num, den);
+}
+__global__ __launch_bounds__(256) void ce_focal_bwd_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                           const float* __restrict__ dloss, float* __restrict__ dlogits, int B, int C, HybCeOpts o,
+                                                           HybCeFocal fo) {
+    __shared__ float part[256];
+    const float g = ce_gscale_opts(dloss[0], ce_den(target, o.weight, B, C, o, part));
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const long long t = target[b];
+    for (int c = 0; c < C; ++c) dlogits[(long long)b * C + c] = ce_clip_dlogit_focal(logits + (long long)b * C, o.weight, t, C, c, g, o, fo.gamma);
+}
+// Asymmetric, one cell (clip b, class c): with ez = exp(-|z|), p = sigmoid(z), q = sigmoid(-z) (kind 1's overflow-safe form), m = clip,
+//   logp = -sp(z),  r = max(p - m, 0),  logn = -sp(-z) if m == 0 else log(min(q + m, 1)),  base = t q + (1 - t) r,
+//   gt = gamma t + gamma_neg (1 - t),  L = 1 + (pw - 1) t,  cell = a * e with a = -(w L) and e = base^gt (t logp + (1 - t) logn).
+// The cell is handed out as its two factors: the clip's term is r = fmaf(a_c, e_c, r) over c in class order from 0.f, the same fmaf whether
+// one thread walks the classes (the stand-alone kernel) or C lanes formed the factors and one thread adds them (the fused tail).
+struct CeAsymCell { float p, q, logp, logn, r, base, gt, L; };
+__device__ __forceinline__ CeAsymCell ce_asym_cell(float z, float t, float pw, const HybCeFocal& fo) {
+    CeAsymCell k;
+    const float ez = expf(-fabsf(z)), l1 = log1pf(ez);
+    k.p = (z >= 0.f ? 1.f : ez) / (1.f + ez);
+    k.q = (z >= 0.f ? ez : 1.f) / (1.f + ez);
+    k.logp = -(l1 + fmaxf(-z, 0.f));
+    k.r = fmaxf(k.p - fo.clip, 0.f);
+    k.logn = fo.clip == 0.f ? -(l1 + fmaxf(z, 0.f)) : logf(fminf(k.q + fo.clip, 1.f));
+    k.base = fmaf(t, k.q, (1.f - t) * k.r);
+    k.gt = fmaf(fo.gamma, t, fo.gamma_neg * (1.f - t));
+    k.L = fmaf(pw - 1.f, t, 1.f);
+    return k;
+}
+__device__ __forceinline__ void ce_asym_factors(float z, float t, float w, float pw, const HybCeFocal& fo, float& a, float& e) {
+    const CeAsymCell k = ce_asym_cell(z, t, pw, fo);
+    a = -(w * k.L);
+    e = ce_pow(k.base, k.gt) * fmaf(t, k.logp, (1.f - t) * k.logn);
+}
+__device__ __forceinline__ float ce_clip_loss_asym(const float* lg, const float* w, const float* pw, const float* t, int C, const HybCeFocal& fo) {
+    float r = 0.f;
+    for (int c = 0; c < C; ++c) {
+        float a, e;
+        ce_asym_factors(lg[c], t[c], ce_w(w, c), ce_w(pw, c), fo, a, e);
+        r = fmaf(a, e, r);
+    }
+    return r;
+}
+// one clip's d(loss)/d(logits[c]), g = dloss / (B C): the derivative of the cell as written, the focusing factor included.
+//   d base / dz = -t p q + (1 - t) [p > m] p q,   d logp / dz = q,   d logn / dz = -p (m == 0), else -[p > m] p q / min(q + m, 1)
+__device__ __forceinline__ float ce_clip_dlogit_asym(const float* lg, const float* w, const float* pw, const float* t, int c, float g, const HybCeFocal& fo) {
+    const float z = lg[c], tc = t[c];
+    const CeAsymCell k = ce_asym_cell(z, tc, ce_w(pw, c), fo);
+    const float pq = k.p * k.q;
+    const bool open = k.p > fo.clip;                                         // the shifted probability is off its floor
+    const float dbase = fmaf(tc, -pq, (1.f - tc) * (open ? pq : 0.f));
+    const float dlogn = fo.clip == 0.f ? -k.p : (open ? -(pq / fminf(k.q + fo.clip, 1.f)) : 0.f);
+    const float G = fmaf(tc, k.logp, (1.f - tc) * k.logn), dG = fmaf(tc, k.q, (1.f - tc) * dlogn);
+    const float F = ce_pow(k.base, k.gt), dF = ce_dpow(k.base, k.gt) * dbase;
+    return g * (-(ce_w(w, c) * k.L) * fmaf(dF, G, F * dG));
+}
+__global__ __launch_bounds__(256) void ce_asym_fwd_kernel(const float* __restrict__ logits, float* __restrict__ loss, int B, int C, HybCeOpts o,
+                                                          HybCeDense d, HybCeFocal fo) {
+    __shared__ float part[256];
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256)
+        acc += ce_clip_loss_asym(logits + (long long)b * C, o.weight, d.pos_weight, d.target + (long long)b * C, C, fo);
+    const float num = ce_tree_sum(acc, part);
+    if (threadIdx.x == 0) loss[0] = num / ce_dense_div(B, C, 1);
+}
+__global__ __launch_bounds__(256) void ce_asym_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ dloss, float* __restrict__ dlogits,
+                                                          int B, int C, HybCeOpts o, HybCeDense d, HybCeFocal fo) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const float g = dloss[0] / ce_dense_div(B, C, 1);
+    for (int c = 0; c < C; ++c)
+        dlogits[(long long)b * C + c] = ce_clip_dlogit_asym(logits + (long long)b * C, o.weight, d.pos_weight, d.target + (long long)b * C, c, g, fo);
+}
+
 // ---- the tail of the temporal part as ONE launch each way --------------------------------------------------------------------
 // forward: the last encoder layer's second LayerNorm (+ residual, scale, dropout: src L120-123) -> mean over the clip's tokens -> Linear
 // head -> (when a target is given) the clip's cross-entropy term, and the batch mean by the last workgroup to finish.  One workgroup per
@@ -643,7 +764,11 @@ __device__ __forceinline__ float head_logit(const float* pooled, const float* __
 // MODE 0: the plain loss; 1: with options (OPTS); 2: with options and two targets per clip (OPTS and MIX; `m`): every MIX line is compiled out of
 // the other two.  MODE 3 / 4: a dense target of kind 0 / 1 (OPTS and DENSE; `dn`; `target` is null): the clip's target row -- and pos_weight
 // for kind 1 -- ride with the up-front requests like the class weights and are staged in LDS, [64] floats each, behind wl; every DENSE line
-// is compiled out of the other three.
+// is compiled out of the other three.  MODE 5: index focal (OPTS and FOCAL; `fo`): ce_clip_loss_focal on thread 0 like the other index losses
+// -- one power and one more accumulate per clip, not worth a hand-over -- with OPTS' two trees and den.  MODE 6: asymmetric (OPTS, DENSE and
+// ASYM; kind 1's staging of the target row and pos_weight): an exponential, two logarithms and a power per cell would make thread 0's chain
+// grow with C, so lane c forms cell c's two factors (ce_asym_factors), parks them over its own tl[c] / pl[c], and thread 0 runs
+// ce_clip_loss_asym's fmaf chain over them in class order: the stand-alone kernel's bits.
 template <typename T, int MODE>
 __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
@@ -652,8 +777,10 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
                                                        const float* __restrict__ bias, float* __restrict__ logits, int C,
                                                        const long long* __restrict__ target, float* __restrict__ loss,
                                                        float* __restrict__ ce_scratch, int rows_in_lds, const HybCeOpts& o, const HybCeMix& m,
-                                                       const HybCeDense& dn, const int nthreads, const unsigned int nclips) {   // (the kernel's blockDim.x, gridDim.x)
-    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2, DENSE = MODE >= 3, BCE = MODE == 4;
+                                                       const HybCeDense& dn, const HybCeFocal& fo, const int nthreads,
+                                                       const unsigned int nclips) {                 // (the kernel's blockDim.x, gridDim.x)
+    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2, DENSE = MODE == 3 || MODE == 4 || MODE == 6, BCE = MODE == 4, FOCAL = MODE == 5, ASYM = MODE == 6;
+    constexpr bool PW = BCE || ASYM;
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
     float* pooled = reinterpret_cast<float*>(tail_smem);                    // [D]
     float* lg = pooled + D;                                                  // [64] this clip's logits
@@ -668,7 +795,7 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
     if constexpr (OPTS) { if (tid < C && o.weight) wreg = o.weight[tid]; }
     float treg = 0.f, preg = 1.f;
     if constexpr (DENSE) { if (tid < C) treg = dn.target[(long long)b * C + tid]; }
-    if constexpr (BCE) { if (tid < C && dn.pos_weight) preg = dn.pos_weight[tid]; }
+    if constexpr (PW) { if (tid < C && dn.pos_weight) preg = dn.pos_weight[tid]; }
     // this wave's first class: its weight row does not depend on the tokens -- requested before the LayerNorm rows (a latency-bound kernel: one
     // memory round trip fewer on the critical path), up to 8 x 64 features in registers
     float w0[8];
@@ -681,7 +808,7 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
                       seed, seed_inc, lane);
     if constexpr (OPTS) { if (tid < C) wl[tid] = wreg; }
     if constexpr (DENSE) { if (tid < C) tl[tid] = treg; }
-    if constexpr (BCE) { if (tid < C) pl[tid] = preg; }
+    if constexpr (PW) { if (tid < C) pl[tid] = preg; }
     __syncthreads();                                                         // (also makes the rows just stored to enc_out readable by this workgroup)
     for (int d = tid; d < D; d += nthreads) {
         if (rows_in_lds) {
@@ -708,9 +835,17 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
     // workgroup reads the terms with agent-scope atomic loads.  (The release / acquire pair of the memory model would be an L2 write-back +
     // invalidate per workgroup: ~3 us each on this chip, see optim.hip -- as much as the launch this fusion removes.)
     __shared__ int s_last;
+    if constexpr (ASYM) {
+        if (tid < C) ce_asym_factors(lg[tid], tl[tid], wl[tid], pl[tid], fo, tl[tid], pl[tid]);
+        __syncthreads();
+    }
     if (tid == 0) {
         float term;
-        if constexpr (BCE) term = ce_clip_loss_bce(lg, o.weight ? wl : nullptr, dn.pos_weight ? pl : nullptr, tl, C);
+        if constexpr (ASYM) {
+            term = 0.f;
+            for (int c = 0; c < C; ++c) term = fmaf(tl[c], pl[c], term);
+        } else if constexpr (FOCAL) term = ce_clip_loss_focal(lg, o.weight ? wl : nullptr, target[b], C, o, fo.gamma);
+        else if constexpr (BCE) term = ce_clip_loss_bce(lg, o.weight ? wl : nullptr, dn.pos_weight ? pl : nullptr, tl, C);
         else if constexpr (DENSE) term = ce_clip_loss_soft(lg, o.weight ? wl : nullptr, tl, C, o.label_smoothing);
         else if constexpr (MIX) term = ce_clip_loss_mix(lg, o.weight ? wl : nullptr, target[b], m.target_b[b], m.lam[b], C, o);
         else if constexpr (OPTS) term = ce_clip_loss_opts(lg, o.weight ? wl : nullptr, target[b], C, o);
@@ -729,7 +864,7 @@ __device__ __forceinline__ void temporal_tail_fwd_body(const T* __restrict__ f, 
         for (int i = tid; i < B; i += 256) acc += __hip_atomic_load(ce_scratch + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if constexpr (DENSE) {          // ce_dense_fwd_kernel's tree and division
         const float num = ce_tree_sum(acc, part);
-        if (tid == 0) loss[0] = num / ce_dense_div(B, C, BCE ? 1 : 0);
+        if (tid == 0) loss[0] = num / ce_dense_div(B, C, PW ? 1 : 0);
     } else if constexpr (OPTS) {    // ce_opts_fwd_kernel's two trees, the terms coming from the other workgroups
         const float num = ce_tree_sum(acc, part);
         float den;
@@ -747,7 +882,7 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_kernel(const T* __restr
                                                                  const long long* __restrict__ target, float* __restrict__ loss,
                                                                  float* __restrict__ ce_scratch, int rows_in_lds) {
     temporal_tail_fwd_body<T, 0>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
-                                 ce_scratch, rows_in_lds, HybCeOpts{}, HybCeMix{}, HybCeDense{}, blockDim.x, gridDim.x);
+                                 ce_scratch, rows_in_lds, HybCeOpts{}, HybCeMix{}, HybCeDense{}, HybCeFocal{}, blockDim.x, gridDim.x);
 }
 template <typename T>
 __global__ __launch_bounds__(512) void temporal_tail_fwd_opts_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
@@ -759,7 +894,7 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_opts_kernel(const T* __
                                                                       float* __restrict__ loss, float* __restrict__ ce_scratch, int rows_in_lds,
                                                                       HybCeOpts o) {
     temporal_tail_fwd_body<T, 1>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
-                                 ce_scratch, rows_in_lds, o, HybCeMix{}, HybCeDense{}, blockDim.x, gridDim.x);
+                                 ce_scratch, rows_in_lds, o, HybCeMix{}, HybCeDense{}, HybCeFocal{}, blockDim.x, gridDim.x);
 }
 template <typename T>
 __global__ __launch_bounds__(512) void temporal_tail_fwd_mix_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
@@ -771,7 +906,7 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_mix_kernel(const T* __r
                                                                      float* __restrict__ loss, float* __restrict__ ce_scratch, int rows_in_lds,
                                                                      HybCeOpts o, HybCeMix m) {
     temporal_tail_fwd_body<T, 2>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
-                                 ce_scratch, rows_in_lds, o, m, HybCeDense{}, blockDim.x, gridDim.x);
+                                 ce_scratch, rows_in_lds, o, m, HybCeDense{}, HybCeFocal{}, blockDim.x, gridDim.x);
 }
 template <typename T, int KIND>
 __global__ __launch_bounds__(512) void temporal_tail_fwd_dense_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
@@ -782,7 +917,31 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_dense_kernel(const T* _
                                                                        float* __restrict__ logits, int C, float* __restrict__ loss,
                                                                        float* __restrict__ ce_scratch, int rows_in_lds, HybCeOpts o, HybCeDense dn) {
     temporal_tail_fwd_body<T, 3 + KIND>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, nullptr,
-                                        loss, ce_scratch, rows_in_lds, o, HybCeMix{}, dn, blockDim.x, gridDim.x);
+                                        loss, ce_scratch, rows_in_lds, o, HybCeMix{}, dn, HybCeFocal{}, blockDim.x, gridDim.x);
+}
+template <typename T>
+__global__ __launch_bounds__(512) void temporal_tail_fwd_focal_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
+                                                                       const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
+                                                                       int B, int S, int D, float eps, float out_scale, float p_drop,
+                                                                       unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
+                                                                       const float* __restrict__ W, const float* __restrict__ bias,
+                                                                       float* __restrict__ logits, int C, const long long* __restrict__ target,
+                                                                       float* __restrict__ loss, float* __restrict__ ce_scratch, int rows_in_lds,
+                                                                       HybCeOpts o, HybCeFocal fo) {
+    temporal_tail_fwd_body<T, 5>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss,
+                                 ce_scratch, rows_in_lds, o, HybCeMix{}, HybCeDense{}, fo, blockDim.x, gridDim.x);
+}
+template <typename T>
+__global__ __launch_bounds__(512) void temporal_tail_fwd_asym_kernel(const T* __restrict__ f, const T* __restrict__ x1, const float* __restrict__ gamma,
+                                                                      const float* __restrict__ beta, T* __restrict__ enc_out, float* __restrict__ stats,
+                                                                      int B, int S, int D, float eps, float out_scale, float p_drop,
+                                                                      unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
+                                                                      const float* __restrict__ W, const float* __restrict__ bias,
+                                                                      float* __restrict__ logits, int C, float* __restrict__ loss,
+                                                                      float* __restrict__ ce_scratch, int rows_in_lds, HybCeOpts o, HybCeDense dn,
+                                                                      HybCeFocal fo) {
+    temporal_tail_fwd_body<T, 6>(f, x1, gamma, beta, enc_out, stats, B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, nullptr, loss,
+                                 ce_scratch, rows_in_lds, o, HybCeMix{}, dn, fo, blockDim.x, gridDim.x);
 }
 
 // backward: cross-entropy backward (from the saved logits, when a target is given; else the caller's dlogits) -> head backward (the
@@ -793,7 +952,8 @@ __global__ __launch_bounds__(512) void temporal_tail_fwd_dense_kernel(const T* _
 // memory round trip.  Writes dx (d LN input), dskip and ln_rows affine-gradient partial rows as ln_residual_bwd_kernel<T, true> does for
 // the launch it replaces (workgroup (sb, b) writes row b * nsb + sb; rows no workgroup owns are zero-filled).
 // OPTS (a target is given): the loss backward with options; [64] class weights and the [256] den tree in LDS behind lnred.  MODE as in the forward;
-// DENSE: [64] class weights, the clip's [64] target row and [64] pos_weight behind lnred, no den tree.
+// DENSE: [64] class weights, the clip's [64] target row and [64] pos_weight behind lnred, no den tree.  FOCAL (5) is OPTS with
+// ce_clip_dlogit_focal, ASYM (6) is DENSE of kind 1 with ce_clip_dlogit_asym: a lane per class either way, as the others.
 template <typename T, int MODE>
 __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__ dlogits_in, const float* __restrict__ logits,
                                                        const long long* __restrict__ target, const float* __restrict__ dloss,
@@ -802,8 +962,9 @@ __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__
                                                        T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
                                                        float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
                                                        float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
-                                                       const HybCeOpts& o, const HybCeMix& m, const HybCeDense& dn) {
-    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2, DENSE = MODE >= 3, BCE = MODE == 4;
+                                                       const HybCeOpts& o, const HybCeMix& m, const HybCeDense& dn, const HybCeFocal& fo) {
+    constexpr bool OPTS = MODE >= 1, MIX = MODE == 2, DENSE = MODE == 3 || MODE == 4 || MODE == 6, BCE = MODE == 4, FOCAL = MODE == 5, ASYM = MODE == 6;
+    constexpr bool PW = BCE || ASYM;
     extern __shared__ __attribute__((aligned(16))) unsigned char tail_smem[];
     float* dl = reinterpret_cast<float*>(tail_smem);                         // [64]
     float* v = dl + 64;                                                      // [D] the clip's token-gradient row (T-rounded values)
@@ -833,12 +994,13 @@ __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__
         if (tid < C) {
             wl[tid] = o.weight ? o.weight[tid] : 1.f;
             tl[tid] = dn.target[(long long)b * C + tid];
-            if constexpr (BCE) pl[tid] = dn.pos_weight ? dn.pos_weight[tid] : 1.f;
+            if constexpr (PW) pl[tid] = dn.pos_weight ? dn.pos_weight[tid] : 1.f;
         }
-        const float g = dloss[0] / ce_dense_div(B, C, BCE ? 1 : 0);
+        const float g = dloss[0] / ce_dense_div(B, C, PW ? 1 : 0);
         __syncthreads();
         const float* w = o.weight ? wl : nullptr;
-        if constexpr (BCE) { if (tid < C) dl[tid] = ce_clip_dlogit_bce(logits + (long long)b * C, w, dn.pos_weight ? pl : nullptr, tl, tid, g); }
+        if constexpr (ASYM) { if (tid < C) dl[tid] = ce_clip_dlogit_asym(logits + (long long)b * C, w, dn.pos_weight ? pl : nullptr, tl, tid, g, fo); }
+        else if constexpr (BCE) { if (tid < C) dl[tid] = ce_clip_dlogit_bce(logits + (long long)b * C, w, dn.pos_weight ? pl : nullptr, tl, tid, g); }
         else { if (tid < C) dl[tid] = ce_clip_dlogit_soft(logits + (long long)b * C, w, tl, C, tid, g, o.label_smoothing); }
     } else if constexpr (OPTS) {
         if (tid < C) wl[tid] = o.weight ? o.weight[tid] : 1.f;
@@ -850,7 +1012,8 @@ __device__ __forceinline__ void temporal_tail_bwd_body(const float* __restrict__
             if (tid < C) dl[tid] = ce_clip_dlogit_mix(logits + (long long)b * C, w, target[b], m.target_b[b], m.lam[b], C, tid, g, o);
         } else {
             const float g = ce_gscale_opts(dlo, ce_den(target, w, B, C, o, part));       // the forward's den: same function, same inputs
-            if (tid < C) dl[tid] = ce_clip_dlogit_opts(logits + (long long)b * C, w, target[b], C, tid, g, o);
+            if constexpr (FOCAL) { if (tid < C) dl[tid] = ce_clip_dlogit_focal(logits + (long long)b * C, w, target[b], C, tid, g, o, fo.gamma); }
+            else { if (tid < C) dl[tid] = ce_clip_dlogit_opts(logits + (long long)b * C, w, target[b], C, tid, g, o); }
         }
     } else {
         if (tid < C) dl[tid] = target ? ce_clip_dlogit(logits + (long long)b * C, target[b], C, tid, dloss[0] / (float)B) : dlogits_in[b * C + tid];
@@ -905,7 +1068,7 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_kernel(const float* __r
                                                                 float* __restrict__ head_part, int B, int S, int D, int C, int rpw, float out_scale,
                                                                 float p_drop, unsigned long long seed, const unsigned long long* __restrict__ seed_inc) {
     temporal_tail_bwd_body<T, 0>(dlogits_in, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C,
-                                 rpw, out_scale, p_drop, seed, seed_inc, HybCeOpts{}, HybCeMix{}, HybCeDense{});
+                                 rpw, out_scale, p_drop, seed, seed_inc, HybCeOpts{}, HybCeMix{}, HybCeDense{}, HybCeFocal{});
 }
 template <typename T>
 __global__ __launch_bounds__(256) void temporal_tail_bwd_opts_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
@@ -917,7 +1080,7 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_opts_kernel(const float
                                                                      float out_scale, float p_drop, unsigned long long seed,
                                                                      const unsigned long long* __restrict__ seed_inc, HybCeOpts o) {
     temporal_tail_bwd_body<T, 1>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
-                                 out_scale, p_drop, seed, seed_inc, o, HybCeMix{}, HybCeDense{});
+                                 out_scale, p_drop, seed, seed_inc, o, HybCeMix{}, HybCeDense{}, HybCeFocal{});
 }
 template <typename T>
 __global__ __launch_bounds__(256) void temporal_tail_bwd_mix_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
@@ -929,7 +1092,7 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_mix_kernel(const float*
                                                                     float out_scale, float p_drop, unsigned long long seed,
                                                                     const unsigned long long* __restrict__ seed_inc, HybCeOpts o, HybCeMix m) {
     temporal_tail_bwd_body<T, 2>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
-                                 out_scale, p_drop, seed, seed_inc, o, m, HybCeDense{});
+                                 out_scale, p_drop, seed, seed_inc, o, m, HybCeDense{}, HybCeFocal{});
 }
 template <typename T, int KIND>
 __global__ __launch_bounds__(256) void temporal_tail_bwd_dense_kernel(const float* __restrict__ logits, const float* __restrict__ dloss,
@@ -941,7 +1104,31 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_dense_kernel(const floa
                                                                       unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
                                                                       HybCeOpts o, HybCeDense dn) {
     temporal_tail_bwd_body<T, 3 + KIND>(nullptr, logits, nullptr, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C,
-                                        rpw, out_scale, p_drop, seed, seed_inc, o, HybCeMix{}, dn);
+                                        rpw, out_scale, p_drop, seed, seed_inc, o, HybCeMix{}, dn, HybCeFocal{});
+}
+template <typename T>
+__global__ __launch_bounds__(256) void temporal_tail_bwd_focal_kernel(const float* __restrict__ logits, const long long* __restrict__ target,
+                                                                      const float* __restrict__ dloss, const float* __restrict__ W,
+                                                                      const T* __restrict__ enc_out, const T* __restrict__ f,
+                                                                      const float* __restrict__ gamma, const float* __restrict__ stats,
+                                                                      T* __restrict__ dx, T* __restrict__ dskip, float* __restrict__ ln_part, int ln_rows,
+                                                                      float* __restrict__ head_part, int B, int S, int D, int C, int rpw,
+                                                                      float out_scale, float p_drop, unsigned long long seed,
+                                                                      const unsigned long long* __restrict__ seed_inc, HybCeOpts o, HybCeFocal fo) {
+    temporal_tail_bwd_body<T, 5>(nullptr, logits, target, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
+                                 out_scale, p_drop, seed, seed_inc, o, HybCeMix{}, HybCeDense{}, fo);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void temporal_tail_bwd_asym_kernel(const float* __restrict__ logits, const float* __restrict__ dloss,
+                                                                     const float* __restrict__ W, const T* __restrict__ enc_out,
+                                                                     const T* __restrict__ f, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ stats, T* __restrict__ dx, T* __restrict__ dskip,
+                                                                     float* __restrict__ ln_part, int ln_rows, float* __restrict__ head_part, int B,
+                                                                     int S, int D, int C, int rpw, float out_scale, float p_drop,
+                                                                     unsigned long long seed, const unsigned long long* __restrict__ seed_inc,
+                                                                     HybCeOpts o, HybCeDense dn, HybCeFocal fo) {
+    temporal_tail_bwd_body<T, 6>(nullptr, logits, nullptr, dloss, W, enc_out, f, gamma, stats, dx, dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw,
+                                 out_scale, p_drop, seed, seed_inc, o, HybCeMix{}, dn, fo);
 }
 
 // ---- evaluation: an accumulating classification meter behind the logits (hyb_eval_metrics; include/hybrid_hip.h states the rules) --------
@@ -1199,15 +1386,29 @@ int hyb_temporal_tail_ok(int B, int S, int D, int C, int ln_rows) {
 int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float* gamma, const float* beta, void* enc_out, float* stats, int B, int S,
                           int D, float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const float* W,
                           const float* bias, float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st,
-                          const HybCeOpts* ce, const HybCeMix* mix, const HybCeDense* dense) {
+                          const HybCeOpts* ce, const HybCeMix* mix, const HybCeDense* dense, const HybCeFocal* focal) {
     HYB_CHECK_ARG(f && x1 && gamma && beta && enc_out && stats && W && logits && (!target || (loss && ce_scratch)) && (!ce || target || dense));
     HYB_CHECK_ARG(!mix || (ce && mix->target_b && mix->lam));
     HYB_CHECK_ARG(!dense || (ce && !target && !mix && loss && ce_scratch && hyb_ce_dense_ok(*ce, *dense)));
+    HYB_CHECK_ARG(!focal || (ce && !mix && (dense || target) && hyb_ce_focal_ok(*ce, *focal, dense)));
     const size_t es = dtype == HYB_F32 ? 4 : 2;
     const size_t base = ((size_t)D + 64 + 256 + (ce ? 64 : 0) + (dense ? 128 : 0)) * sizeof(float);
     const int rows_in_lds = base + (size_t)S * D * es <= 60 * 1024;
     const size_t lds = base + (rows_in_lds ? (size_t)S * D * es : 0);
     const int threads = S >= 8 ? 512 : 256;             // (1024 threads leave 128 registers per lane: the LayerNorm row spills -- measured 13 -> 24 us)
+#define HYB_TAIL_FWD_FOCAL(T)                                                                                                                        \
+    do {                                                                                                                                            \
+        if (dense)                                                                                                                                  \
+            hipLaunchKernelGGL(temporal_tail_fwd_asym_kernel<T>, dim3(B), dim3(threads), lds, st, (const T*)f, (const T*)x1, gamma, beta, (T*)enc_out, stats, B, \
+                               S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, loss, ce_scratch, rows_in_lds, *ce, *dense, *focal); \
+        else                                                                                                                                        \
+            hipLaunchKernelGGL(temporal_tail_fwd_focal_kernel<T>, dim3(B), dim3(threads), lds, st, (const T*)f, (const T*)x1, gamma, beta, (T*)enc_out, stats, B, \
+                               S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce, *focal); \
+    } while (0)
+    if (focal && dtype == HYB_F32) HYB_TAIL_FWD_FOCAL(float);
+    else if (focal && dtype == HYB_BF16) HYB_TAIL_FWD_FOCAL(bf16);
+    else
+#undef HYB_TAIL_FWD_FOCAL
 #define HYB_TAIL_FWD_DENSE(T, KIND)                                                                                                                  \
     hipLaunchKernelGGL((temporal_tail_fwd_dense_kernel<T, KIND>), dim3(B), dim3(threads), lds, st, (const T*)f, (const T*)x1, gamma, beta, (T*)enc_out, stats, \
                        B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, loss, ce_scratch, rows_in_lds, *ce, *dense)
@@ -1239,11 +1440,13 @@ int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float*
 int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* W,
                           const void* enc_out, const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part,
                           int ln_rows, float* head_part, int B, int S, int D, int C, float out_scale, float p_drop, unsigned long long seed,
-                          const unsigned long long* seed_inc, hipStream_t st, const HybCeOpts* ce, const HybCeMix* mix, const HybCeDense* dense) {
+                          const unsigned long long* seed_inc, hipStream_t st, const HybCeOpts* ce, const HybCeMix* mix, const HybCeDense* dense,
+                          const HybCeFocal* focal) {
     HYB_CHECK_ARG((dlogits || (logits && (target || dense) && dloss)) && W && enc_out && f && gamma && stats && dx && dskip && ln_part && head_part);
     HYB_CHECK_ARG(!ce || (!dlogits && logits && (target || dense) && dloss));
     HYB_CHECK_ARG(!mix || (ce && mix->target_b && mix->lam));
     HYB_CHECK_ARG(!dense || (ce && !target && !mix && hyb_ce_dense_ok(*ce, *dense)));
+    HYB_CHECK_ARG(!focal || (ce && !mix && (dense || target) && hyb_ce_focal_ok(*ce, *focal, dense)));
     const size_t lds = (64 + 9 * (size_t)D + (dense ? 3 * 64 : ce ? 64 + 256 : 0)) * sizeof(float);
     // row blocks per clip: as many as the ln_rows partial rows allow (>= 1: hyb_temporal_tail_ok), four-row granules
     int nsb = hyb_cdiv(S, 4);
@@ -1252,6 +1455,19 @@ int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, 
     nsb = hyb_cdiv(S, rpw);
     const dim3 grid(nsb, B);
     if (lds > 64 * 1024) return HYB_E_ARG;
+#define HYB_TAIL_BWD_FOCAL(T)                                                                                                                        \
+    do {                                                                                                                                            \
+        if (dense)                                                                                                                                  \
+            hipLaunchKernelGGL(temporal_tail_bwd_asym_kernel<T>, grid, dim3(256), lds, st, logits, dloss, W, (const T*)enc_out, (const T*)f, gamma, stats,       \
+                               (T*)dx, (T*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *dense, *focal); \
+        else                                                                                                                                        \
+            hipLaunchKernelGGL(temporal_tail_bwd_focal_kernel<T>, grid, dim3(256), lds, st, logits, target, dloss, W, (const T*)enc_out, (const T*)f, gamma,     \
+                               stats, (T*)dx, (T*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *focal); \
+    } while (0)
+    if (focal && dtype == HYB_F32) HYB_TAIL_BWD_FOCAL(float);
+    else if (focal && dtype == HYB_BF16) HYB_TAIL_BWD_FOCAL(bf16);
+    else
+#undef HYB_TAIL_BWD_FOCAL
 #define HYB_TAIL_BWD_DENSE(T, KIND)                                                                                                                  \
     hipLaunchKernelGGL((temporal_tail_bwd_dense_kernel<T, KIND>), grid, dim3(256), lds, st, logits, dloss, W, (const T*)enc_out, (const T*)f, gamma, stats,    \
                        (T*)dx, (T*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *dense)
@@ -1389,6 +1605,55 @@ extern "C" int hyb_cross_entropy_dense_bwd(const float* logits, const float* tar
     const HybCeDense d{target, pos_weight, kind};
     HYB_CHECK_ARG(logits && dloss && dlogits && B > 0 && C > 0 && hyb_ce_dense_ok(o, d));
     hipLaunchKernelGGL(ce_dense_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, dloss, dlogits, B, C, o, d);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+// The focal and asymmetric losses (ce_focal_*_kernel, ce_asym_*_kernel; include/hybrid_hip.h states the definitions).  hyb_ce_focal_ok: what
+// every *_focal_* (d == nullptr) and *_asym_* (d: the dense target, kind 1) entry point asks beyond non-null pointers: each exponent 0 or
+// >= 1 (between, the derivative of base^g is singular at base == 0, which clipped negatives reach exactly), clip in [0, 1), no label
+// smoothing.
+static int ce_gamma_ok(float g) { return g == 0.f || (g >= 1.f && g <= 3.0e38f); }
+int hyb_ce_focal_ok(const HybCeOpts& o, const HybCeFocal& f, const HybCeDense* d) {
+    if (o.label_smoothing != 0.f || !ce_gamma_ok(f.gamma)) return 0;
+    if (!d) return f.gamma_neg == 0.f && f.clip == 0.f;
+    return d->target && d->kind == 1 && ce_gamma_ok(f.gamma_neg) && f.clip >= 0.f && f.clip < 1.f;
+}
+extern "C" int hyb_cross_entropy_focal_fwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                           float gamma, float* loss, int B, int C, void* stream) {
+    const HybCeOpts o{weight, ignore_index, has_ignore, 0.f};
+    const HybCeFocal f{gamma, 0.f, 0.f};
+    HYB_CHECK_ARG(logits && target && loss && B > 0 && C > 0 && hyb_ce_focal_ok(o, f, nullptr));
+    hipLaunchKernelGGL(ce_focal_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, B, C, o, f);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int hyb_cross_entropy_focal_bwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                           float gamma, const float* dloss, float* dlogits, int B, int C, void* stream) {
+    const HybCeOpts o{weight, ignore_index, has_ignore, 0.f};
+    const HybCeFocal f{gamma, 0.f, 0.f};
+    HYB_CHECK_ARG(logits && target && dloss && dlogits && B > 0 && C > 0 && hyb_ce_focal_ok(o, f, nullptr));
+    hipLaunchKernelGGL(ce_focal_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o, f);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int hyb_cross_entropy_asym_fwd(const float* logits, const float* target, const float* weight, const float* pos_weight, float gamma_pos,
+                                          float gamma_neg, float clip, float* loss, int B, int C, void* stream) {
+    const HybCeOpts o{weight, 0, 0, 0.f};
+    const HybCeDense d{target, pos_weight, 1};
+    const HybCeFocal f{gamma_pos, gamma_neg, clip};
+    HYB_CHECK_ARG(logits && loss && B > 0 && C > 0 && hyb_ce_focal_ok(o, f, &d));
+    hipLaunchKernelGGL(ce_asym_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, loss, B, C, o, d, f);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int hyb_cross_entropy_asym_bwd(const float* logits, const float* target, const float* weight, const float* pos_weight, float gamma_pos,
+                                          float gamma_neg, float clip, const float* dloss, float* dlogits, int B, int C, void* stream) {
+    const HybCeOpts o{weight, 0, 0, 0.f};
+    const HybCeDense d{target, pos_weight, 1};
+    const HybCeFocal f{gamma_pos, gamma_neg, clip};
+    HYB_CHECK_ARG(logits && dloss && dlogits && B > 0 && C > 0 && hyb_ce_focal_ok(o, f, &d));
+    hipLaunchKernelGGL(ce_asym_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, dloss, dlogits, B, C, o, d, f);
     HYB_LAUNCH_CHECK();
     return 0;
 }

@@ -26,6 +26,9 @@ What makes capture legal here
   * a dense target (floating [B, C]: class probabilities under a HybridCrossEntropyLoss, binary targets under a HybridBCEWithLogitsLoss) is
     one static tensor read from device memory when a replay runs, as are the criterion's weight / pos_weight buffers; the loss stays in
     the same launches (hybrid::temporal_ce_dense), and load() refuses a target of another form than the one captured;
+  * a HybridFocalLoss (class indices) and a HybridAsymmetricLoss (a dense target) ride the same way (hybrid::temporal_ce_focal /
+    hybrid::temporal_ce_asym): targets and the weight / pos_weight buffers are read when a replay runs, the exponents and clip travel by
+    value, and step() refuses a change of them after capture;
   * BatchNorm running statistics are updated in place by the captured statistics kernels (hybrid::backbone_);
   * with HybridAdamW(skip_nonfinite=True) a replay whose gradients are not finite changes nothing in the model: the captured norm launch
     decides, the captured AdamW launch reads the decision (optim.py).  The counter advances all the same -- the next replay draws new
@@ -106,11 +109,14 @@ class GraphedTrainStep:
         # whether the captured norm and AdamW launches are the guarded ones (skip_nonfinite): entry points, fixed by the capture
         self._guard_on = bool(getattr(optimizer, "skip_nonfinite", False))
         self._captured_hyper = self._hyper_now()
-        from .modules import HybridBCEWithLogitsLoss, HybridCrossEntropyLoss
-        self._fused_loss = (type(criterion) in (HybridCrossEntropyLoss, HybridBCEWithLogitsLoss) and hasattr(model, "forward_temporal_loss")
+        from .modules import HybridAsymmetricLoss, HybridBCEWithLogitsLoss, HybridCrossEntropyLoss, HybridFocalLoss
+        self._fused_loss = (type(criterion) in (HybridCrossEntropyLoss, HybridBCEWithLogitsLoss, HybridFocalLoss, HybridAsymmetricLoss)
+                            and hasattr(model, "forward_temporal_loss")
                             and os.environ.get("HYB_FUSED_LOSS", "1") != "0")       # (=0: A/B, the criterion as its own two launches)
         # the captured loss launch carries ignore_index and label_smoothing by value (the class weights are read from the criterion's buffer
         # when a replay runs, so an in-place update of criterion.weight is picked up); a later change is refused like an optimizer's (_check_hyper)
+        if type(criterion) is HybridAsymmetricLoss and hasattr(model, "head"):
+            criterion._check_weight(model.head.weight.shape[0], x.device)         # (sigmoid_focal's two vectors exist before their addresses are noted)
         self._captured_loss_opts = self._loss_opts_now()
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
@@ -223,9 +229,13 @@ class GraphedTrainStep:
     def _loss_opts_now(self):
         """What a HybridCrossEntropyLoss's launches carry by value or by address: (ignore_index, label_smoothing, the weight buffer's address)."""
         c = self.criterion
-        from .modules import HybridBCEWithLogitsLoss
+        from .modules import HybridAsymmetricLoss, HybridBCEWithLogitsLoss, HybridFocalLoss
         if type(c) is HybridBCEWithLogitsLoss:                      # nothing by value, two buffers by address
             return (None, 0.0, tuple(None if t is None else t.data_ptr() for t in (c.weight, c.pos_weight)))
+        if type(c) is HybridFocalLoss:                              # (ignore_index, gamma in label_smoothing's place, the weight buffer)
+            return (c.ignore_index, c.gamma, c.weight.data_ptr() if c.weight is not None else None)
+        if type(c) is HybridAsymmetricLoss:                         # the three scalars by value, two buffers by address
+            return ((c.gamma_pos, c.gamma_neg, c.clip), 0.0, tuple(None if t is None else t.data_ptr() for t in (c.weight, c.pos_weight)))
         if not hasattr(c, "has_options"):
             return None
         return (c.ignore_index, c.label_smoothing, c.weight.data_ptr() if c.weight is not None else None)
@@ -241,7 +251,10 @@ class GraphedTrainStep:
                                "one launch over all parameter groups -- set it on the optimizer before constructing GraphedTrainStep")
         now = self._loss_opts_now()
         if now != self._captured_loss_opts:
-            what = [n for n, a, b in zip(("ignore_index", "label_smoothing", "the weight buffer (replaced, not updated in place)"), now,
+            from .modules import HybridAsymmetricLoss, HybridFocalLoss
+            first, second = (("gamma_pos / gamma_neg / clip", "label_smoothing") if type(self.criterion) is HybridAsymmetricLoss else
+                             ("ignore_index", "gamma") if type(self.criterion) is HybridFocalLoss else ("ignore_index", "label_smoothing"))
+            what = [n for n, a, b in zip((first, second, "the weight buffer (replaced, not updated in place)"), now,
                                          self._captured_loss_opts) if a != b]
             raise RuntimeError(f"GraphedTrainStep: the criterion's {', '.join(what)} changed after capture, but the captured loss launch carries "
                                "the old value -- construct a new GraphedTrainStep (an in-place update of criterion.weight needs none: the "

@@ -320,6 +320,112 @@ class HybridBCEWithLogitsLoss(nn.Module):
         return ops.cross_entropy_dense(logits, target, self.weight, self.pos_weight, 1, 0.0)
 
 
+def _gamma(name, g):
+    """A focusing exponent: a real number that is 0 or >= 1 (include/hybrid_hip.h says why nothing between)."""
+    if isinstance(g, bool) or not isinstance(g, (int, float)):
+        raise TypeError(f"{name} must be a number, got {g!r}")
+    g = float(g)
+    if not (g == 0.0 or 1.0 <= g < float("inf")):
+        raise ValueError(f"{name} must be 0 or >= 1, got {g}")
+    return g
+
+
+class HybridFocalLoss(nn.Module):
+    """Mean focal loss on class indices int64 [B] (Lin et al. 2017, the softmax form), one HIP kernel each way (include/hybrid_hip.h,
+    hyb_cross_entropy_focal_*): every kept clip's cross-entropy term times ``(1 - p_target) ** gamma``, summed and divided by the kept
+    clips' target weights -- ``HybridCrossEntropyLoss(weight, ignore_index)``'s rules throughout (an ignored clip adds nothing, all ignored
+    gives NaN with a zero gradient, a kept target outside [0, C) gives NaN), and its bits at ``gamma == 0``.  ``gamma`` is 0 or >= 1; there
+    is no label smoothing.  A ``MixTarget`` or a dense floating target raises TypeError.
+
+    ``weight`` (one fp32 entry >= 0 per class, or None) is a registered buffer read by the kernels when they run: an in-place update is
+    seen by the next call and by the next replay of a GraphedTrainStep; ``gamma`` and ``ignore_index`` travel by value."""
+
+    def __init__(self, gamma=2.0, weight=None, ignore_index=None):
+        super().__init__()
+        if ignore_index is not None and (isinstance(ignore_index, bool) or not isinstance(ignore_index, int)):
+            raise TypeError(f"ignore_index must be an int or None, got {ignore_index!r}")
+        self.gamma = _gamma("gamma", gamma)
+        self.register_buffer("weight", _class_vector("weight", weight))
+        self.ignore_index = ignore_index
+
+    def _check_weight(self, C):
+        if self.weight is not None and self.weight.shape[0] != C:
+            raise ValueError(f"weight has {self.weight.shape[0]} entries but the logits have {C} classes")
+
+    @staticmethod
+    def _check_target(target):
+        if isinstance(target, MixTarget) or _is_dense(target):
+            raise TypeError("HybridFocalLoss takes class indices int64 [B] (no MixTarget, no dense target)")
+
+    def forward(self, logits, target):
+        self._check_target(target)
+        self._check_weight(logits.shape[-1])
+        return ops.cross_entropy_focal(logits, target, self.weight, self.ignore_index, _gamma("gamma", self.gamma))
+
+    def extra_repr(self):
+        return f"gamma={self.gamma}, ignore_index={self.ignore_index}"
+
+
+class HybridAsymmetricLoss(nn.Module):
+    """Mean asymmetric loss over all B x C entries (Ridnik et al. 2021) on a floating target [B, C], one HIP kernel each way
+    (include/hybrid_hip.h, hyb_cross_entropy_asym_*): positives are focused with ``gamma_pos``, negatives with ``gamma_neg`` after their
+    probability is shifted down by ``clip`` (a negative below it adds nothing); the gradient includes the focusing factor.  Each exponent
+    is 0 or >= 1, ``clip`` in [0, 1).  ``target`` is fp32, contiguous, on the logits' device; soft rows are used as given.
+
+    ``weight`` and ``pos_weight`` (one fp32 entry >= 0 per class, or None = all ones) are registered buffers read by the kernels when they
+    run, as in HybridBCEWithLogitsLoss; the exponents and ``clip`` travel by value.  ``sigmoid_focal(gamma, alpha)`` is the sigmoid focal
+    loss with reduction "mean" as a special case."""
+
+    def __init__(self, gamma_neg=4.0, gamma_pos=0.0, clip=0.05, weight=None, pos_weight=None):
+        super().__init__()
+        self.gamma_neg, self.gamma_pos = _gamma("gamma_neg", gamma_neg), _gamma("gamma_pos", gamma_pos)
+        self.clip = self._clip(clip)
+        self.register_buffer("weight", _class_vector("weight", weight))
+        self.register_buffer("pos_weight", _class_vector("pos_weight", pos_weight))
+
+    @staticmethod
+    def _clip(clip):
+        if isinstance(clip, bool) or not isinstance(clip, (int, float)):
+            raise TypeError(f"clip must be a number, got {clip!r}")
+        if not 0.0 <= float(clip) < 1.0:
+            raise ValueError(f"clip must be in [0, 1), got {clip}")
+        return float(clip)
+
+    @classmethod
+    def sigmoid_focal(cls, gamma=2.0, alpha=0.25):
+        """``mean(alpha_t * (1 - p_t) ** gamma * bce)`` with ``alpha_t = alpha`` on positives and ``1 - alpha`` on negatives: one exponent, no
+        clip, a scalar ``weight = 1 - alpha`` and ``pos_weight = alpha / (1 - alpha)`` (kept as 0-d marks until the class count is known:
+        ``num_classes`` vectors are made on the first call).  ``alpha`` in (0, 1)."""
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 < float(alpha) < 1.0:
+            raise ValueError(f"alpha must be in (0, 1), got {alpha!r}")
+        self = cls(gamma_neg=gamma, gamma_pos=gamma, clip=0.0)
+        self._alpha = float(alpha)
+        return self
+
+    def _scalars(self):
+        return _gamma("gamma_pos", self.gamma_pos), _gamma("gamma_neg", self.gamma_neg), self._clip(self.clip)
+
+    def _check_weight(self, C, device=None):
+        alpha = getattr(self, "_alpha", None)
+        if alpha is not None and self.weight is None and device is not None:       # sigmoid_focal: the two vectors, once the class count is known
+            self.weight = torch.full((C,), 1.0 - alpha, dtype=torch.float32, device=device)
+            self.pos_weight = torch.full((C,), alpha / (1.0 - alpha), dtype=torch.float32, device=device)
+        for name in ("weight", "pos_weight"):
+            v = getattr(self, name)
+            if v is not None and v.shape[0] != C:
+                raise ValueError(f"{name} has {v.shape[0]} entries but the logits have {C} classes")
+
+    def forward(self, logits, target):
+        if not _is_dense(target):
+            raise TypeError("HybridAsymmetricLoss takes a floating target [B,C] (dense_target() makes one from class indices or a MixTarget)")
+        _check_dense(logits, target)
+        self._check_weight(logits.shape[-1], logits.device)
+        return ops.cross_entropy_asym(logits, target, self.weight, self.pos_weight, *self._scalars())
+
+    def extra_repr(self):
+        return f"gamma_neg={self.gamma_neg}, gamma_pos={self.gamma_pos}, clip={self.clip}"
+
+
 class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
     """CNN backbone + temporal Transformer encoder over clips [B,T,3,H,W] (or [B,3,H,W] => T=1) -> logits [B,num_classes].
 
@@ -422,10 +528,34 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
         ``target`` may be a MixTarget: hybrid::temporal_ce_mix, again the same launches.  A floating ``target`` [B, num_classes] is a dense
         target: hybrid::temporal_ce_dense, the same launches, as soft-target cross-entropy under a HybridCrossEntropyLoss (or None) and as
         binary cross-entropy under a HybridBCEWithLogitsLoss, which takes nothing else.  Models ``_fused()`` rejects run the criterion behind
-        forward_temporal."""
+        forward_temporal.  A HybridFocalLoss (class indices) and a HybridAsymmetricLoss (a dense target) ride the same way:
+        hybrid::temporal_ce_focal / hybrid::temporal_ce_asym."""
         enc = self.encoder
-        if criterion is not None and type(criterion) not in (HybridCrossEntropyLoss, HybridBCEWithLogitsLoss):
-            raise TypeError("forward_temporal_loss fuses HybridCrossEntropyLoss and HybridBCEWithLogitsLoss only")
+        if criterion is not None and type(criterion) not in (HybridCrossEntropyLoss, HybridBCEWithLogitsLoss, HybridFocalLoss, HybridAsymmetricLoss):
+            raise TypeError("forward_temporal_loss fuses HybridCrossEntropyLoss, HybridBCEWithLogitsLoss, HybridFocalLoss and HybridAsymmetricLoss only")
+        if type(criterion) in (HybridFocalLoss, HybridAsymmetricLoss):
+            asym = type(criterion) is HybridAsymmetricLoss
+            if asym and not _is_dense(target):
+                raise TypeError("HybridAsymmetricLoss takes a floating target [B,C] (dense_target() makes one from class indices or a MixTarget)")
+            if not asym:
+                criterion._check_target(target)
+            if not self._fused():
+                logits = self.forward_temporal(h, B, mask)
+                return criterion(logits, target), logits
+            classes = self.head.weight.shape[0]
+            tdt = self._temporal_dt()
+            front = (h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias, enc._flat_params(),
+                     self.head.weight, self.head.bias, mask)
+            back = (B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout), ops.next_seed())
+            if asym:
+                if target.dtype != torch.float32:
+                    raise TypeError(f"a dense target must be float32, got {target.dtype}")
+                if target.dim() != 2 or tuple(target.shape) != (B, classes):
+                    raise ValueError(f"a dense target has the shape of the logits [B={B},C={classes}]: got {tuple(target.shape)}")
+                criterion._check_weight(classes, h.device)
+                return ops.temporal_ce_asym(*front, target, criterion.weight, criterion.pos_weight, *criterion._scalars(), *back)
+            criterion._check_weight(classes)
+            return ops.temporal_ce_focal(*front, target, criterion.weight, criterion.ignore_index, _gamma("gamma", criterion.gamma), *back)
         bce = type(criterion) is HybridBCEWithLogitsLoss
         if bce or _is_dense(target):
             if not _is_dense(target):

@@ -24,6 +24,8 @@ fake kernel and an autograd kernel per operator.
     hybrid::cross_entropy    mean cross-entropy                                  (composite's own)
     hybrid::cross_entropy_opts   ... with class weights, label smoothing, ignore_index   (torch.nn.functional.cross_entropy's "mean")
     hybrid::cross_entropy_dense  the loss on dense fp32 [B, C] targets: soft-target cross-entropy (kind 0) / BCE with logits (kind 1)
+    hybrid::cross_entropy_focal  focal loss on class indices (weight, ignore_index, gamma): cross_entropy_opts' rules, u^gamma per clip
+    hybrid::cross_entropy_asym   asymmetric loss on dense fp32 [B, C] targets (gamma_pos, gamma_neg, clip; weight, pos_weight)
     hybrid::cross_entropy_mix    ... and two targets per clip with a mixing weight lam [B]: the labels of a Mixup / CutMix batch
     hybrid::cast, hybrid::nchw_to_nhwc, hybrid::nhwc_to_nchw                     layout / dtype glue for standalone module use
     hybrid::convstage_infer, hybrid::backbone_infer                              the conv stages for inference (no autograd formula)
@@ -601,6 +603,31 @@ def _ce_dense(dense, B, C, device):
     return target, _ce_weight(weight, C, device), _ce_weight(pos_weight, C, device), kind, label_smoothing
 
 
+def _ce_gamma(name, g):
+    """A focusing exponent as the hyb_*_focal_* / hyb_*_asym_* entry points take it: 0, or a finite number >= 1 (between 0 and 1 the
+    derivative of base ** g is singular at base == 0, which a clipped negative reaches exactly)."""
+    g = float(g)
+    if not (g == 0.0 or 1.0 <= g < float("inf")):
+        raise ValueError(f"{name} must be 0 or >= 1, got {g}")
+    return g
+
+
+def _ce_asym(asym, B, C, device):
+    """(target, weight, pos_weight, gamma_pos, gamma_neg, clip) as the hyb_*_asym_* entry points take them: the tensors under _ce_dense's
+    rules for kind 1, each exponent 0 or >= 1, clip in [0, 1)."""
+    target, weight, pos_weight, gamma_pos, gamma_neg, clip = asym
+    target, weight, pos_weight, _, _ = _ce_dense((target, weight, pos_weight, 1, 0.0), B, C, device)
+    clip = float(clip)
+    if not 0.0 <= clip < 1.0:
+        raise ValueError(f"clip must be in [0, 1), got {clip}")
+    return target, weight, pos_weight, _ce_gamma("gamma_pos", gamma_pos), _ce_gamma("gamma_neg", gamma_neg), clip
+
+
+def _ce_focal(focal, C, device):
+    """(weight, ignore_index, has_ignore, gamma) as the hyb_*_focal_* entry points take them behind the target."""
+    return (_ce_weight(focal[0], C, device), int(focal[1]), int(focal[2]), _ce_gamma("gamma", focal[3]))
+
+
 def _ce_name(stem, opts, mix, way):
     return f"hyb_{stem}_mix_{way}" if mix else f"hyb_{stem}_opts_{way}" if opts else f"hyb_{stem}_{way}"
 
@@ -694,6 +721,59 @@ def cross_entropy_dense_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, we
     return dlogits
 
 
+def _ce_index_checked(logits, target):
+    _require_cuda(logits, target)
+    if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
+        raise ValueError(f"expected logits [B,C] and class indices [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
+    return logits.contiguous().float(), target.contiguous().to(torch.int64)
+
+
+def cross_entropy_focal_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, gamma: float) -> Tensor:
+    """Mean focal loss on class indices (hyb_cross_entropy_focal_fwd): hybrid::cross_entropy_opts' terms, each times u ** gamma with u the
+    softmax mass of the other classes; the same den.  gamma == 0: cross_entropy_opts' bits."""
+    logits, target = _ce_index_checked(logits, target)
+    B, C = logits.shape
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    lib.call("hyb_cross_entropy_focal_fwd", logits, target, *_ce_focal((weight, ignore_index, has_ignore, gamma), C, logits.device), loss, B, C, _stream())
+    return loss
+
+
+def cross_entropy_focal_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
+                               gamma: float) -> Tensor:
+    _require_cuda(dloss)
+    logits, target = _ce_index_checked(logits, target)
+    B, C = logits.shape
+    dlogits = torch.empty_like(logits)
+    lib.call("hyb_cross_entropy_focal_bwd", logits, target, *_ce_focal((weight, ignore_index, has_ignore, gamma), C, logits.device),
+             dloss.contiguous().float().reshape(1), dlogits, B, C, _stream())
+    return dlogits
+
+
+def cross_entropy_asym_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float, gamma_neg: float,
+                          clip: float) -> Tensor:
+    """Mean asymmetric loss on a dense fp32 target [B, C] (hyb_cross_entropy_asym_fwd); the divisor is B C."""
+    _require_cuda(logits, target)
+    if logits.dim() != 2:
+        raise ValueError(f"expected logits [B,C], got {tuple(logits.shape)}")
+    logits = logits.contiguous().float()
+    B, C = logits.shape
+    asym = _ce_asym((target, weight, pos_weight, gamma_pos, gamma_neg, clip), B, C, logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    lib.call("hyb_cross_entropy_asym_fwd", logits, *asym, loss, B, C, _stream())
+    return loss
+
+
+def cross_entropy_asym_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float,
+                              gamma_neg: float, clip: float) -> Tensor:
+    _require_cuda(dloss, logits, target)
+    logits = logits.contiguous().float()
+    B, C = logits.shape
+    asym = _ce_asym((target, weight, pos_weight, gamma_pos, gamma_neg, clip), B, C, logits.device)
+    dlogits = torch.empty_like(logits)
+    lib.call("hyb_cross_entropy_asym_bwd", logits, *asym, dloss.contiguous().float().reshape(1), dlogits, B, C, _stream())
+    return dlogits
+
+
 def cross_entropy_fake(logits, target, *opts):
     return logits.new_empty((), dtype=torch.float32)
 
@@ -723,6 +803,20 @@ def cross_entropy_dense(logits, target, weight=None, pos_weight=None, kind=0, la
     probabilities, used as given; class weights [C] and label smoothing as in torch.nn.functional.cross_entropy); kind 1: binary cross-entropy
     with logits (weight and pos_weight [C]).  No gradient for the target or the weights."""
     return torch.ops.hybrid.cross_entropy_dense(logits, target, weight, pos_weight, int(kind), float(label_smoothing))
+
+
+def cross_entropy_focal(logits, target, weight=None, ignore_index=None, gamma=2.0):
+    """The mean focal loss on class indices [B]: cross_entropy_opts (class weights, an ignored index; no label smoothing) with every clip's
+    term times (1 - p_target) ** gamma.  gamma is 0 or >= 1.  No gradient for the class weights."""
+    return torch.ops.hybrid.cross_entropy_focal(logits, target, weight, 0 if ignore_index is None else int(ignore_index), ignore_index is not None,
+                                                _ce_gamma("gamma", gamma))
+
+
+def cross_entropy_asym(logits, target, weight=None, pos_weight=None, gamma_pos=0.0, gamma_neg=4.0, clip=0.05):
+    """The mean asymmetric loss on a dense target: a contiguous fp32 [B, C] on the logits' device (include/hybrid_hip.h).  Each exponent is 0
+    or >= 1, clip in [0, 1).  No gradient for the target or the weights."""
+    return torch.ops.hybrid.cross_entropy_asym(logits, target, weight, pos_weight, _ce_gamma("gamma_pos", gamma_pos),
+                                               _ce_gamma("gamma_neg", gamma_neg), float(clip))
 
 
 def eval_metrics_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
@@ -1305,13 +1399,16 @@ def prepare_ce_scratch(B, device, stream):
     return t
 
 
-def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, dense=()):
+def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, dense=(), focal=(),
+                  asym=()):
     """The temporal part, one body for the three operators.  ce (): hyb_temporal_fwd; ce = (target,): hyb_temporal_ce_fwd, the loss in the
     same launches; ce = (target, weight, ignore_index, has_ignore, label_smoothing): hyb_temporal_ce_opts_fwd, the same call with the loss
     options behind the target; ce = (target, target_b, lam, weight, ...): hyb_temporal_ce_mix_fwd, the second target and lam in front of the
     options.  dense = (target [B, classes] fp32, weight, pos_weight, kind, label_smoothing) with ce (): hyb_temporal_ce_dense_fwd.
+    focal = (target [B] int64, weight, ignore_index, has_ignore, gamma) with ce (): hyb_temporal_ce_focal_fwd; asym = (target [B, classes]
+    fp32, weight, pos_weight, gamma_pos, gamma_neg, clip) with ce (): hyb_temporal_ce_asym_fwd.
     -> (logits, feat, enc_saved, enc_out), behind the loss [] when there is one."""
-    _require_cuda(h, token_w, head_w, *ce[:1], *dense[:1], *enc_params)
+    _require_cuda(h, token_w, head_w, *ce[:1], *dense[:1], *focal[:1], *asym[:1], *enc_params)
     _check_h_dtype(h, dt)
     h = h.contiguous()
     N, Hh, Ww, Cp = h.shape
@@ -1320,8 +1417,9 @@ def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, 
     classes = head_w.shape[0]
     _check_attention_limits(S, D, H)
     dev, tdt = h.device, _TORCH_DTYPE[dt & 0xff]
-    if ce and (ce[0].dim() != 1 or ce[0].shape[0] != B):
-        raise ValueError(f"expected class indices [B={B}], got {tuple(ce[0].shape)}")
+    for t in (*ce[:1], *focal[:1]):
+        if t.dim() != 1 or t.shape[0] != B:
+            raise ValueError(f"expected class indices [B={B}], got {tuple(t.shape)}")
     feat = torch.empty(N, Cp, dtype=tdt, device=dev)
     tok = torch.empty(B, S, D, dtype=tdt, device=dev)
     enc_out = torch.empty(B, S, D, dtype=tdt, device=dev)
@@ -1339,15 +1437,24 @@ def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, 
         name = "hyb_temporal_ce_dense_fwd"
         loss_in = _ce_dense(dense, B, classes, dev)
         loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
+    elif focal:
+        name = "hyb_temporal_ce_focal_fwd"
+        loss_in = (focal[0].contiguous().to(torch.int64), *_ce_focal(focal[1:], classes, dev))
+        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
+    elif asym:
+        name = "hyb_temporal_ce_asym_fwd"
+        loss_in = _ce_asym(asym, B, classes, dev)
+        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
     lib.call(name, dt, h, token_w.contiguous(), token_b.contiguous(), ps, head_w.contiguous(), head_b.contiguous(), mask, *loss_in, feat, tok, saved,
              enc_out, logits, *loss_out, B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, _stream())
     return (*loss_out[:1], logits, feat, saved, enc_out)
 
 
-def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, dense=()):
+def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, dense=(),
+                  focal=(), asym=()):
     """ce (): dout is dlogits, hyb_temporal_bwd; ce = (logits, target) + what follows the target in _temporal_fwd's ce, if anything: dout is
     dloss, hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd / hyb_temporal_ce_mix_bwd.  dense = (logits,) + _temporal_fwd's dense, with ce ():
-    dout is dloss, hyb_temporal_ce_dense_bwd.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
+    dout is dloss, hyb_temporal_ce_dense_bwd; focal / asym = (logits,) + _temporal_fwd's, likewise.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
     _require_cuda(dout, *ce[:1], feat)
     B, S, D = enc_out.shape
     N, Cp = feat.shape
@@ -1375,6 +1482,16 @@ def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_
         name = "hyb_temporal_ce_dense_bwd"
         dout = dout.reshape(1)
         loss_in = (dense[0].contiguous(), *_ce_dense(dense[1:], B, classes, dev))
+    elif focal:
+        _require_cuda(focal[0], focal[1])
+        name = "hyb_temporal_ce_focal_bwd"
+        dout = dout.reshape(1)
+        loss_in = (focal[0].contiguous(), focal[1].contiguous().to(torch.int64), *_ce_focal(focal[2:], classes, dev))
+    elif asym:
+        _require_cuda(asym[0])
+        name = "hyb_temporal_ce_asym_bwd"
+        dout = dout.reshape(1)
+        loss_in = (asym[0].contiguous(), *_ce_asym(asym[1:], B, classes, dev))
     lib.call(name, dt, dout, *loss_in, token_w.contiguous(), ps, head_w.contiguous(), mask, feat, saved, enc_out, dtw, dtb, grads, dhw, dhb, dh,
              B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, ws, ws.numel(), _stream())
     return [dh, dtw, dtb, dhw, dhb] + grads
@@ -1421,6 +1538,24 @@ def temporal_ce_dense_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params
                          dense=(target, weight, pos_weight, kind, label_smoothing))
 
 
+def temporal_ce_focal_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
+                         mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, gamma: float,
+                         B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
+                         seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """hybrid::temporal + hybrid::cross_entropy_focal in the same launches (hyb_temporal_ce_focal_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
+    return _temporal_fwd((), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
+                         focal=(target, weight, ignore_index, has_ignore, gamma))
+
+
+def temporal_ce_asym_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
+                        mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float,
+                        gamma_neg: float, clip: float, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
+                        seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """hybrid::temporal + hybrid::cross_entropy_asym in the same launches (hyb_temporal_ce_asym_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
+    return _temporal_fwd((), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
+                         asym=(target, weight, pos_weight, gamma_pos, gamma_neg, clip))
+
+
 def temporal_bwd_op(dlogits: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
                     saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
                     seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
@@ -1461,6 +1596,24 @@ def temporal_ce_dense_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weig
     """hybrid::cross_entropy_dense_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
     return _temporal_bwd((), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
                          dense=(logits, target, weight, pos_weight, kind, label_smoothing))
+
+
+def temporal_ce_focal_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
+                             gamma: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
+                             saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
+                             seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
+    """hybrid::cross_entropy_focal_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
+    return _temporal_bwd((), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
+                         focal=(logits, target, weight, ignore_index, has_ignore, gamma))
+
+
+def temporal_ce_asym_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float,
+                            gamma_neg: float, clip: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor],
+                            feat: Tensor, saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float,
+                            layer_p: float, seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
+    """hybrid::cross_entropy_asym_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
+    return _temporal_bwd((), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
+                         asym=(logits, target, weight, pos_weight, gamma_pos, gamma_neg, clip))
 
 
 def _temporal_fake(n_loss, h, token_w, token_b, enc_params, head_w, head_b, mask, *rest, seed_inc=None):
@@ -1522,6 +1675,27 @@ def temporal_ce_dense(h, token_w, token_b, enc_params, head_w, head_b, mask, tar
     r = torch.ops.hybrid.temporal_ce_dense(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
                                            pos_weight, int(kind), float(label_smoothing), B, dt, hid, L, H, float(attn_p), float(layer_p), seed,
                                            step_counter())
+    return r[0], r[1]
+
+
+def temporal_ce_focal(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, gamma, B, dt, hid, L, H, attn_p, layer_p,
+                      seed):
+    """-> (loss, logits): the temporal part and the focal loss on class indices (cross_entropy_focal) as one operator: the same launches."""
+    S = h.shape[0] // B
+    r = torch.ops.hybrid.temporal_ce_focal(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
+                                           0 if ignore_index is None else int(ignore_index), ignore_index is not None, _ce_gamma("gamma", gamma), B,
+                                           dt, hid, L, H, float(attn_p), float(layer_p), seed, step_counter())
+    return r[0], r[1]
+
+
+def temporal_ce_asym(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, pos_weight, gamma_pos, gamma_neg, clip, B, dt, hid, L, H,
+                     attn_p, layer_p, seed):
+    """-> (loss, logits): the temporal part and the asymmetric loss on a dense fp32 target [B, classes] (cross_entropy_asym) as one operator:
+    the same launches; the target, weight and pos_weight are read on the device when the kernels run."""
+    S = h.shape[0] // B
+    r = torch.ops.hybrid.temporal_ce_asym(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
+                                          pos_weight, _ce_gamma("gamma_pos", gamma_pos), _ce_gamma("gamma_neg", gamma_neg), float(clip), B, dt, hid,
+                                          L, H, float(attn_p), float(layer_p), seed, step_counter())
     return r[0], r[1]
 
 
@@ -1726,6 +1900,40 @@ class _CrossEntropyDenseFn(torch.autograd.Function):
         return (dlogits,) + (None,) * 5        # (no gradient for the target or the weights)
 
 
+class _CrossEntropyFocalFn(torch.autograd.Function):
+    """hybrid::cross_entropy_focal."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, has_ignore, gamma):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(logits, target, weight)
+        ctx.cfg = (ignore_index, has_ignore, gamma)
+        with _below_autograd():
+            return torch.ops.hybrid.cross_entropy_focal(logits, target, weight, ignore_index, has_ignore, gamma)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, target, weight = ctx.saved_tensors
+        return (torch.ops.hybrid.cross_entropy_focal_bwd(dloss, logits, target, weight, *ctx.cfg),) + (None,) * 5
+
+
+class _CrossEntropyAsymFn(torch.autograd.Function):
+    """hybrid::cross_entropy_asym."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, pos_weight, gamma_pos, gamma_neg, clip):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(logits, target, weight, pos_weight)
+        ctx.cfg = (gamma_pos, gamma_neg, clip)
+        with _below_autograd():
+            return torch.ops.hybrid.cross_entropy_asym(logits, target, weight, pos_weight, gamma_pos, gamma_neg, clip)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, target, weight, pos_weight = ctx.saved_tensors
+        return (torch.ops.hybrid.cross_entropy_asym_bwd(dloss, logits, target, weight, pos_weight, *ctx.cfg),) + (None,) * 6
+
+
 class _BackboneFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, S, training, momentum, eps, dt, *tensors):
@@ -1838,6 +2046,44 @@ class _TemporalDenseFn(torch.autograd.Function):
         return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 15 + tuple(g[5:])
 
 
+class _TemporalFocalFn(torch.autograd.Function):
+    """hybrid::temporal_ce_focal (pos_weight is None, scalars = (ignore_index, has_ignore, gamma)) and hybrid::temporal_ce_asym (scalars =
+    (gamma_pos, gamma_neg, clip)): the loss arguments are (target, weight[, pos_weight], three scalars) either way."""
+
+    @staticmethod
+    def forward(ctx, asym, h, token_w, token_b, head_w, head_b, mask, target, weight, pos_weight, s0, s1, s2, B, dt, hid, L, H, attn_p, layer_p, seed,
+                seed_inc, *enc_params):
+        ctx.set_materialize_grads(False)
+        tail = (B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+        with _below_autograd():
+            if asym:
+                out = torch.ops.hybrid.temporal_ce_asym(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, pos_weight, s0, s1, s2, *tail)
+            else:
+                out = torch.ops.hybrid.temporal_ce_focal(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, s0, s1, s2, *tail)
+        feat, saved, enc_out = out[-3:]
+        ctx.seed_inc = seed_inc
+        opt = [t for t in (weight, pos_weight, mask) if t is not None]
+        ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, out[1], target, *opt, *enc_params)
+        ctx.cfg = (asym, weight is not None, pos_weight is not None, mask is not None, (s0, s1, s2), h.shape[1], h.shape[2], dt, hid, L, H, attn_p,
+                   layer_p, seed)
+        ctx.mark_non_differentiable(*out[1:])
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, dout, *unused):
+        asym, has_weight, has_pw, has_mask, scalars, *tail = ctx.cfg
+        token_w, head_w, feat, saved, enc_out, logits, target, *rest = ctx.saved_tensors
+        weight = rest.pop(0) if has_weight else None
+        pos_weight = rest.pop(0) if has_pw else None
+        mask = rest.pop(0) if has_mask else None
+        tail = (token_w, rest, head_w, mask, feat, saved, enc_out, *tail, ctx.seed_inc)
+        if asym:
+            g = torch.ops.hybrid.temporal_ce_asym_bwd(dout, logits, target, weight, pos_weight, *scalars, *tail)
+        else:
+            g = torch.ops.hybrid.temporal_ce_focal_bwd(dout, logits, target, weight, *scalars, *tail)
+        return (None, g[0], g[1], g[2], g[3], g[4]) + (None,) * 16 + tuple(g[5:])
+
+
 _define("nchw_to_nhwc", "(Tensor x, int dt, int cp) -> Tensor", nchw_to_nhwc_op, nchw_to_nhwc_fake, _NchwToNhwcFn.apply)
 _define("nhwc_to_nchw", "(Tensor x, int dt, int C) -> Tensor", nhwc_to_nchw_op, nhwc_to_nchw_fake, _NhwcToNchwFn.apply)
 _define("cast", "(Tensor x, int dt, bool to_t) -> Tensor", cast_op, cast_fake, _CastFn.apply)
@@ -1878,6 +2124,14 @@ _define("cross_entropy_dense", "(Tensor logits, Tensor target, Tensor? weight, T
         cross_entropy_dense_op, cross_entropy_fake, _CrossEntropyDenseFn.apply)
 _define("cross_entropy_dense_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing) "
         "-> Tensor", cross_entropy_dense_bwd_op, cross_entropy_bwd_fake)
+_define("cross_entropy_focal", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float gamma) -> Tensor",
+        cross_entropy_focal_op, cross_entropy_fake, _CrossEntropyFocalFn.apply)
+_define("cross_entropy_focal_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float gamma) "
+        "-> Tensor", cross_entropy_focal_bwd_op, cross_entropy_bwd_fake)
+_define("cross_entropy_asym", "(Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, float clip) "
+        "-> Tensor", cross_entropy_asym_op, cross_entropy_fake, _CrossEntropyAsymFn.apply)
+_define("cross_entropy_asym_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, "
+        "float clip) -> Tensor", cross_entropy_asym_bwd_op, cross_entropy_bwd_fake)
 _define("eval_metrics_", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int topk, int views, "
         "Tensor(a!) sums, Tensor(b!) counts, Tensor(c!)? confusion) -> (Tensor, Tensor)", eval_metrics_op, eval_metrics_fake)
 _LIB.impl("eval_metrics_", _inference_only("eval_metrics_"), "Autograd")
@@ -1964,6 +2218,27 @@ _define("temporal_ce_dense_bwd", "(Tensor dloss, Tensor logits, Tensor target, T
         "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
         "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_dense_bwd_op,
         functools.partial(_temporal_bwd_fake, 6))
+_define("temporal_ce_focal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
+        "Tensor? weight, int ignore_index, bool has_ignore, float gamma, int B, int dt, int hid, int L, int H, float attn_p, float layer_p, "
+        "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_focal_op, functools.partial(_temporal_fake, 5),
+        lambda h, tw, tb, ps, hw, hb, mask, target, weight, ignore_index, has_ignore, gamma, B, dt, hid, L, H, attn_p, layer_p, seed,
+        seed_inc=None: _TemporalFocalFn.apply(False, h, tw, tb, hw, hb, mask, target, weight, None, ignore_index, has_ignore, gamma, B, dt, hid, L, H,
+                                               attn_p, layer_p, seed, seed_inc, *ps))
+_define("temporal_ce_focal_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float gamma, "
+        "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
+        "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_focal_bwd_op,
+        functools.partial(_temporal_bwd_fake, 6))
+_define("temporal_ce_asym", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
+        "Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, float clip, int B, int dt, int hid, int L, int H, float attn_p, "
+        "float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_asym_op,
+        functools.partial(_temporal_fake, 6),
+        lambda h, tw, tb, ps, hw, hb, mask, target, weight, pos_weight, gamma_pos, gamma_neg, clip, B, dt, hid, L, H, attn_p, layer_p, seed,
+        seed_inc=None: _TemporalFocalFn.apply(True, h, tw, tb, hw, hb, mask, target, weight, pos_weight, gamma_pos, gamma_neg, clip, B, dt, hid, L, H,
+                                               attn_p, layer_p, seed, seed_inc, *ps))
+_define("temporal_ce_asym_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, "
+        "float clip, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, "
+        "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_asym_bwd_op,
+        functools.partial(_temporal_bwd_fake, 7))
 
 
 # ---------------------------------------------------------------------------------------------
