@@ -82,8 +82,11 @@ dist.all_gather(others, flat)
 same = all(torch.equal(o, flat) for o in others)
 # and the state dict still carries the reference's key names under DDP's "module." prefix
 keys_ok = all(k.startswith("module.") for k in md.state_dict()) and [k[7:] for k in md.state_dict()] == list(ml.state_dict())
-print(f"DDPW rank {rank}: {len(names)} tensors ({nonzero} non-zero); DDP vs hand-averaged {e_ddp_mean:.2e}; DDP vs GradAllReducer {e_ddp_red:.2e}; "
-      f"ranks equal after AdamW {same}; state-dict keys {keys_ok}", flush=True)
+# (one write of the whole line, newline included: both ranks get here together and share the launcher's stdout, where print()'s separate
+# write of the line end can land behind the other rank's line when the stream is unbuffered -- the test reads one line per rank)
+sys.stdout.write(f"DDPW rank {rank}: {len(names)} tensors ({nonzero} non-zero); DDP vs hand-averaged {e_ddp_mean:.2e}; DDP vs GradAllReducer "
+                 f"{e_ddp_red:.2e}; ranks equal after AdamW {same}; state-dict keys {keys_ok}\n")
+sys.stdout.flush()
 ok = e_ddp_mean <= 1e-6 and e_ddp_red <= 1e-6 and same and keys_ok and nonzero == len(names)
 dist.destroy_process_group()
 sys.exit(0 if ok else 1)

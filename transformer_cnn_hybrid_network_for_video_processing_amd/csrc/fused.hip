@@ -258,17 +258,19 @@ extern "C" size_t hyb_temporal_bwd_workspace(int dtype, int B, int S, int HW, in
 }
 
 // The tail of the temporal part runs as ONE launch each way when the shapes allow (hyb_temporal_tail_ok): forward = the last layer's second
-// LayerNorm + head (+ cross-entropy when a target is given), backward = (cross-entropy backward +) head backward + that LayerNorm's
-// backward.  HYB_TEMPORAL_TAIL=0: the separate launches (A/B; same results up to the order of two fixed-order sums).
+// LayerNorm + head (+ the loss when one is described), backward = (the loss backward +) head backward + that LayerNorm's backward.
+// HYB_TEMPORAL_TAIL=0: the separate launches (A/B; same results up to the order of two fixed-order sums).  l: the loss (hyb_internal.h,
+// HybLoss), in the tail's launch or -- shapes the tail does not take -- as hyb_loss_fwd / hyb_loss_bwd behind / in front of the head;
+// nullptr: logits only / the caller's dlogits.
 static int tail_enabled() { static const int env = hyb_env_int("HYB_TEMPORAL_TAIL", 1); return env; }
 
 static int temporal_fwd_impl(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
                              const float* head_w, const float* head_b, const float* mask, void* feat, void* tok, void* enc_saved,
                              void* enc_out, float* logits, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes,
-                             float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc, const long long* target,
-                             float* loss, float* ce_scratch, void* stream, const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr,
-                             const HybCeDense* dense = nullptr, const HybCeFocal* focal = nullptr) {
+                             float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc, float* loss,
+                             float* ce_scratch, void* stream, const HybLoss* l) {
     HYB_CHECK_ARG(h && token_w && enc_params && head_w && feat && tok && enc_saved && enc_out && logits && B > 0 && S > 0 && HW > 0);
+    HYB_CHECK_ARG(!l || (loss && ce_scratch && hyb_loss_ok(*l)));
     const int N = B * S;
     const bool h16 = (dtype & HYB_H_BF16) != 0;                 // the pooled map is bf16, everything from the frame features on is fp32
     dtype &= 0xff;
@@ -285,35 +287,29 @@ static int temporal_fwd_impl(int dtype, const void* h, const float* token_w, con
                                  tail ? &t : nullptr));
     if (tail)
         return hyb_temporal_tail_fwd(dtype, t.f, t.x1, t.gamma, t.beta, enc_out, t.st2, B, S, D, t.eps, t.out_scale, t.p_drop, t.seed, seed_inc, head_w,
-                                     head_b, logits, classes, target, loss, ce_scratch, (hipStream_t)stream, ce, mix, dense, focal);
+                                     head_b, logits, classes, loss, ce_scratch, (hipStream_t)stream, l);
     HYB_TRY(hyb_head_fwd(dtype, enc_out, head_w, head_b, logits, B, S, D, classes, stream));
-    if (focal && dense) HYB_TRY(hyb_cross_entropy_asym_fwd(logits, dense->target, ce->weight, dense->pos_weight, focal->gamma, focal->gamma_neg, focal->clip,
-                                                           loss, B, classes, stream));
-    else if (focal) HYB_TRY(hyb_cross_entropy_focal_fwd(logits, target, ce->weight, ce->ignore_index, ce->has_ignore, focal->gamma, loss, B, classes, stream));
-    else if (dense) HYB_TRY(hyb_cross_entropy_dense_fwd(logits, dense->target, ce->weight, dense->pos_weight, dense->kind, ce->label_smoothing, loss, B, classes,
-                                                   stream));
-    else if (mix) HYB_TRY(hyb_cross_entropy_mix_fwd(logits, target, mix->target_b, mix->lam, ce->weight, ce->ignore_index, ce->has_ignore, ce->label_smoothing, loss, B,
-                                               classes, stream));
-    else if (ce) HYB_TRY(hyb_cross_entropy_opts_fwd(logits, target, ce->weight, ce->ignore_index, ce->has_ignore, ce->label_smoothing, loss, B, classes, stream));
-    else if (target) HYB_TRY(hyb_cross_entropy_fwd(logits, target, loss, B, classes, stream));
+    if (l) HYB_TRY(hyb_loss_fwd(*l, logits, loss, B, classes, (hipStream_t)stream));
     return 0;
 }
 
+// The seven forward entry points differ in the loss they describe and in nothing else: what they all hand on is named once.
+#define HYB_TEMPORAL_FWD_COMMON                                                                                                            \
+    dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D, Hid, L, H, classes, \
+        attn_p, layer_p, seed, seed_inc
 extern "C" int hyb_temporal_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
                                 const float* head_w, const float* head_b, const float* mask, void* feat, void* tok, void* enc_saved,
                                 void* enc_out, float* logits, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes,
                                 float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc, void* stream) {
-    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
-                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, nullptr, nullptr, nullptr, stream);
+    return temporal_fwd_impl(HYB_TEMPORAL_FWD_COMMON, nullptr, nullptr, stream, nullptr);
 }
 extern "C" int hyb_temporal_ce_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
                                    const float* head_w, const float* head_b, const float* mask, const long long* target, void* feat, void* tok,
                                    void* enc_saved, void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp,
                                    int D, int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
                                    const unsigned long long* seed_inc, void* stream) {
-    HYB_CHECK_ARG(target && loss && ce_scratch);
-    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
-                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, target, loss, ce_scratch, stream);
+    const HybLoss l = hyb_loss_plain(target);
+    return temporal_fwd_impl(HYB_TEMPORAL_FWD_COMMON, loss, ce_scratch, stream, &l);
 }
 extern "C" int hyb_temporal_ce_opts_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
                                         const float* head_w, const float* head_b, const float* mask, const long long* target, const float* weight,
@@ -321,21 +317,54 @@ extern "C" int hyb_temporal_ce_opts_fwd(int dtype, const void* h, const float* t
                                         void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D, int Hid,
                                         int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
                                         const unsigned long long* seed_inc, void* stream) {
-    const HybCeOpts ce{weight, ignore_index, has_ignore, label_smoothing};
-    HYB_CHECK_ARG(target && loss && ce_scratch && hyb_ce_opts_ok(ce));
-    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
-                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, target, loss, ce_scratch, stream, &ce);
+    const HybLoss l = hyb_loss_opts(target, weight, ignore_index, has_ignore, label_smoothing);
+    return temporal_fwd_impl(HYB_TEMPORAL_FWD_COMMON, loss, ce_scratch, stream, &l);
 }
+extern "C" int hyb_temporal_ce_mix_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                                       const float* head_w, const float* head_b, const float* mask, const long long* target, const long long* target_b,
+                                       const float* lam, const float* weight, long long ignore_index, int has_ignore, float label_smoothing, void* feat,
+                                       void* tok, void* enc_saved, void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C,
+                                       int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
+                                       const unsigned long long* seed_inc, void* stream) {
+    const HybLoss l = hyb_loss_mix(target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing);
+    return temporal_fwd_impl(HYB_TEMPORAL_FWD_COMMON, loss, ce_scratch, stream, &l);
+}
+extern "C" int hyb_temporal_ce_dense_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                                         const float* head_w, const float* head_b, const float* mask, const float* target, const float* weight,
+                                         const float* pos_weight, int kind, float label_smoothing, void* feat, void* tok, void* enc_saved,
+                                         void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D,
+                                         int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
+                                         const unsigned long long* seed_inc, void* stream) {
+    const HybLoss l = hyb_loss_dense(target, weight, pos_weight, kind, label_smoothing);
+    return temporal_fwd_impl(HYB_TEMPORAL_FWD_COMMON, loss, ce_scratch, stream, &l);
+}
+extern "C" int hyb_temporal_ce_focal_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                                         const float* head_w, const float* head_b, const float* mask, const long long* target, const float* weight,
+                                         long long ignore_index, int has_ignore, float gamma, void* feat, void* tok, void* enc_saved, void* enc_out,
+                                         float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
+                                         int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
+                                         void* stream) {
+    const HybLoss l = hyb_loss_focal(target, weight, ignore_index, has_ignore, gamma);
+    return temporal_fwd_impl(HYB_TEMPORAL_FWD_COMMON, loss, ce_scratch, stream, &l);
+}
+extern "C" int hyb_temporal_ce_asym_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
+                                        const float* head_w, const float* head_b, const float* mask, const float* target, const float* weight,
+                                        const float* pos_weight, float gamma_pos, float gamma_neg, float clip, void* feat, void* tok, void* enc_saved,
+                                        void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D,
+                                        int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
+                                        const unsigned long long* seed_inc, void* stream) {
+    const HybLoss l = hyb_loss_asym(target, weight, pos_weight, gamma_pos, gamma_neg, clip);
+    return temporal_fwd_impl(HYB_TEMPORAL_FWD_COMMON, loss, ce_scratch, stream, &l);
+}
+#undef HYB_TEMPORAL_FWD_COMMON
 
-static int temporal_bwd_impl(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* token_w,
+static int temporal_bwd_impl(int dtype, const float* dlogits, const float* logits, const float* dloss, const HybLoss* l, const float* token_w,
                              const float* const* enc_params, const float* head_w, const float* mask, const void* feat, const void* enc_saved,
                              const void* enc_out, float* dtoken_w, float* dtoken_b, float* const* enc_grads, float* dhead_w, float* dhead_b, void* dh,
                              int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
-                             unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes, void* stream,
-                             const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr,
-                             const HybCeFocal* focal = nullptr) {
-    HYB_CHECK_ARG((dlogits || (logits && (target || dense) && dloss)) && token_w && enc_params && head_w && feat && enc_saved && enc_out && dtoken_w && enc_grads &&
-                  dhead_w && dh && workspace);
+                             unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes, void* stream) {
+    HYB_CHECK_ARG(l ? !dlogits && logits && dloss && hyb_loss_ok(*l) : dlogits != nullptr);
+    HYB_CHECK_ARG(token_w && enc_params && head_w && feat && enc_saved && enc_out && dtoken_w && enc_grads && dhead_w && dh && workspace);
     const bool h16 = (dtype & HYB_H_BF16) != 0;                 // dh is written as bf16
     dtype &= 0xff;
     HYB_CHECK_ARG(!h16 || dtype == HYB_F32);
@@ -353,8 +382,8 @@ static int temporal_bwd_impl(int dtype, const float* dlogits, const float* logit
     const bool tail = tail_enabled() && dhead_b && hyb_temporal_tail_ok(B, S, D, classes, hyb_ln_bwd_rows(N)) && (ride || L <= 2);
     if (tail) {
         const HybEncBwdTail t = hyb_encoder_bwd_tail(dtype, enc_params, enc_saved, enc_ws, B, S, D, Hid, L, H, layer_p, seed);
-        HYB_TRY(hyb_temporal_tail_bwd(dtype, dlogits, logits, target, dloss, head_w, enc_out, t.f, t.gamma, t.stats, t.dx, t.dskip, t.ln_part, t.ln_rows,
-                                      head_part, B, S, D, classes, t.out_scale, t.p_drop, t.seed, seed_inc, (hipStream_t)stream, ce, mix, dense, focal));
+        HYB_TRY(hyb_temporal_tail_bwd(dtype, dlogits, logits, dloss, head_w, enc_out, t.f, t.gamma, t.stats, t.dx, t.dskip, t.ln_part, t.ln_rows,
+                                      head_part, B, S, D, classes, t.out_scale, t.p_drop, t.seed, seed_inc, (hipStream_t)stream, l));
         const long long cd = (long long)classes * D;
         const HybDwRider hr{head_part, dhead_w, dhead_b, B, cd + classes, cd};
         HYB_TRY(hyb_encoder_bwd_impl(dtype, nullptr, mask, enc_params, enc_grads, enc_saved, dtok, B, S, D, Hid, L, H, attn_p, layer_p, seed, seed_inc, enc_ws,
@@ -363,17 +392,7 @@ static int temporal_bwd_impl(int dtype, const float* dlogits, const float* logit
         const float* dl = dlogits;
         if (!dl) {      // cross-entropy backward as its own launch, into the head of the (not yet used) dfeat scratch
             HYB_CHECK_ARG((size_t)B * classes * sizeof(float) <= lay.dfeat_bytes);
-            if (focal && dense) HYB_TRY(hyb_cross_entropy_asym_bwd(logits, dense->target, ce->weight, dense->pos_weight, focal->gamma, focal->gamma_neg,
-                                                                   focal->clip, dloss, (float*)dfeat, B, classes, stream));
-            else if (focal) HYB_TRY(hyb_cross_entropy_focal_bwd(logits, target, ce->weight, ce->ignore_index, ce->has_ignore, focal->gamma, dloss,
-                                                                (float*)dfeat, B, classes, stream));
-            else if (dense) HYB_TRY(hyb_cross_entropy_dense_bwd(logits, dense->target, ce->weight, dense->pos_weight, dense->kind, ce->label_smoothing, dloss,
-                                                           (float*)dfeat, B, classes, stream));
-            else if (mix) HYB_TRY(hyb_cross_entropy_mix_bwd(logits, target, mix->target_b, mix->lam, ce->weight, ce->ignore_index, ce->has_ignore, ce->label_smoothing,
-                                                       dloss, (float*)dfeat, B, classes, stream));
-            else if (ce) HYB_TRY(hyb_cross_entropy_opts_bwd(logits, target, ce->weight, ce->ignore_index, ce->has_ignore, ce->label_smoothing, dloss, (float*)dfeat, B,
-                                                       classes, stream));
-            else HYB_TRY(hyb_cross_entropy_bwd(logits, target, dloss, (float*)dfeat, B, classes, stream));
+            HYB_TRY(hyb_loss_bwd(*l, logits, dloss, (float*)dfeat, B, classes, (hipStream_t)stream));
             dl = (const float*)dfeat;
         }
         HYB_TRY(hyb_head_bwd(dtype, enc_out, head_w, dl, denc, dhead_w, dhead_b, B, S, D, classes, stream));
@@ -388,15 +407,16 @@ static int temporal_bwd_impl(int dtype, const float* dlogits, const float* logit
     return 0;
 }
 
+// ... and the seven backward ones
+#define HYB_TEMPORAL_BWD_COMMON                                                                                                            \
+    token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b, enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, \
+        classes, attn_p, layer_p, seed, seed_inc, workspace, workspace_bytes, stream
 extern "C" int hyb_temporal_bwd(int dtype, const float* dlogits, const float* token_w, const float* const* enc_params, const float* head_w,
                                 const float* mask, const void* feat, const void* enc_saved, const void* enc_out, float* dtoken_w,
                                 float* dtoken_b, float* const* enc_grads, float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C,
                                 int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
                                 const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes, void* stream) {
-    HYB_CHECK_ARG(dlogits);
-    return temporal_bwd_impl(dtype, dlogits, nullptr, nullptr, nullptr, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
-                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
-                             workspace_bytes, stream);
+    return temporal_bwd_impl(dtype, dlogits, nullptr, nullptr, nullptr, HYB_TEMPORAL_BWD_COMMON);
 }
 extern "C" int hyb_temporal_ce_bwd(int dtype, const float* dloss, const float* logits, const long long* target, const float* token_w,
                                    const float* const* enc_params, const float* head_w, const float* mask, const void* feat, const void* enc_saved,
@@ -404,10 +424,8 @@ extern "C" int hyb_temporal_ce_bwd(int dtype, const float* dloss, const float* l
                                    void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p,
                                    float layer_p, unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-    HYB_CHECK_ARG(dloss && logits && target);
-    return temporal_bwd_impl(dtype, nullptr, logits, target, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
-                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
-                             workspace_bytes, stream);
+    const HybLoss l = hyb_loss_plain(target);
+    return temporal_bwd_impl(dtype, nullptr, logits, dloss, &l, HYB_TEMPORAL_BWD_COMMON);
 }
 extern "C" int hyb_temporal_ce_opts_bwd(int dtype, const float* dloss, const float* logits, const long long* target, const float* weight,
                                         long long ignore_index, int has_ignore, float label_smoothing, const float* token_w,
@@ -416,24 +434,8 @@ extern "C" int hyb_temporal_ce_opts_bwd(int dtype, const float* dloss, const flo
                                         void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p,
                                         float layer_p, unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes,
                                         void* stream) {
-    const HybCeOpts ce{weight, ignore_index, has_ignore, label_smoothing};
-    HYB_CHECK_ARG(dloss && logits && target && hyb_ce_opts_ok(ce));
-    return temporal_bwd_impl(dtype, nullptr, logits, target, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
-                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
-                             workspace_bytes, stream, &ce);
-}
-
-extern "C" int hyb_temporal_ce_mix_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
-                                       const float* head_w, const float* head_b, const float* mask, const long long* target, const long long* target_b,
-                                       const float* lam, const float* weight, long long ignore_index, int has_ignore, float label_smoothing, void* feat,
-                                       void* tok, void* enc_saved, void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C,
-                                       int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
-                                       const unsigned long long* seed_inc, void* stream) {
-    const HybCeOpts ce{weight, ignore_index, has_ignore, label_smoothing};
-    const HybCeMix mix{target_b, lam};
-    HYB_CHECK_ARG(target && target_b && lam && loss && ce_scratch && hyb_ce_opts_ok(ce));
-    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
-                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, target, loss, ce_scratch, stream, &ce, &mix);
+    const HybLoss l = hyb_loss_opts(target, weight, ignore_index, has_ignore, label_smoothing);
+    return temporal_bwd_impl(dtype, nullptr, logits, dloss, &l, HYB_TEMPORAL_BWD_COMMON);
 }
 extern "C" int hyb_temporal_ce_mix_bwd(int dtype, const float* dloss, const float* logits, const long long* target, const long long* target_b,
                                        const float* lam, const float* weight, long long ignore_index, int has_ignore, float label_smoothing,
@@ -442,25 +444,8 @@ extern "C" int hyb_temporal_ce_mix_bwd(int dtype, const float* dloss, const floa
                                        float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
                                        int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-    const HybCeOpts ce{weight, ignore_index, has_ignore, label_smoothing};
-    const HybCeMix mix{target_b, lam};
-    HYB_CHECK_ARG(dloss && logits && target && target_b && lam && hyb_ce_opts_ok(ce));
-    return temporal_bwd_impl(dtype, nullptr, logits, target, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
-                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
-                             workspace_bytes, stream, &ce, &mix);
-}
-
-extern "C" int hyb_temporal_ce_dense_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
-                                         const float* head_w, const float* head_b, const float* mask, const float* target, const float* weight,
-                                         const float* pos_weight, int kind, float label_smoothing, void* feat, void* tok, void* enc_saved,
-                                         void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D,
-                                         int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
-                                         const unsigned long long* seed_inc, void* stream) {
-    const HybCeOpts ce{weight, 0, 0, label_smoothing};
-    const HybCeDense dense{target, pos_weight, kind};
-    HYB_CHECK_ARG(loss && ce_scratch && hyb_ce_dense_ok(ce, dense));
-    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
-                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, nullptr, loss, ce_scratch, stream, &ce, nullptr, &dense);
+    const HybLoss l = hyb_loss_mix(target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing);
+    return temporal_bwd_impl(dtype, nullptr, logits, dloss, &l, HYB_TEMPORAL_BWD_COMMON);
 }
 extern "C" int hyb_temporal_ce_dense_bwd(int dtype, const float* dloss, const float* logits, const float* target, const float* weight,
                                          const float* pos_weight, int kind, float label_smoothing, const float* token_w,
@@ -469,27 +454,8 @@ extern "C" int hyb_temporal_ce_dense_bwd(int dtype, const float* dloss, const fl
                                          float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
                                          int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
                                          void* workspace, size_t workspace_bytes, void* stream) {
-    const HybCeOpts ce{weight, 0, 0, label_smoothing};
-    const HybCeDense dense{target, pos_weight, kind};
-    HYB_CHECK_ARG(dloss && logits && hyb_ce_dense_ok(ce, dense));
-    return temporal_bwd_impl(dtype, nullptr, logits, nullptr, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
-                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
-                             workspace_bytes, stream, &ce, nullptr, &dense);
-}
-
-// index focal and the asymmetric loss in the temporal part's own launches (include/hybrid_hip.h); shapes the tail does not take run the
-// stand-alone launches behind the same entry points
-extern "C" int hyb_temporal_ce_focal_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
-                                         const float* head_w, const float* head_b, const float* mask, const long long* target, const float* weight,
-                                         long long ignore_index, int has_ignore, float gamma, void* feat, void* tok, void* enc_saved, void* enc_out,
-                                         float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
-                                         int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
-                                         void* stream) {
-    const HybCeOpts ce{weight, ignore_index, has_ignore, 0.f};
-    const HybCeFocal focal{gamma, 0.f, 0.f};
-    HYB_CHECK_ARG(target && loss && ce_scratch && hyb_ce_focal_ok(ce, focal, nullptr));
-    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
-                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, target, loss, ce_scratch, stream, &ce, nullptr, nullptr, &focal);
+    const HybLoss l = hyb_loss_dense(target, weight, pos_weight, kind, label_smoothing);
+    return temporal_bwd_impl(dtype, nullptr, logits, dloss, &l, HYB_TEMPORAL_BWD_COMMON);
 }
 extern "C" int hyb_temporal_ce_focal_bwd(int dtype, const float* dloss, const float* logits, const long long* target, const float* weight,
                                          long long ignore_index, int has_ignore, float gamma, const float* token_w, const float* const* enc_params,
@@ -498,25 +464,8 @@ extern "C" int hyb_temporal_ce_focal_bwd(int dtype, const float* dloss, const fl
                                          int HW, int C, int Cp, int D, int Hid, int L, int H, int classes, float attn_p, float layer_p,
                                          unsigned long long seed, const unsigned long long* seed_inc, void* workspace, size_t workspace_bytes,
                                          void* stream) {
-    const HybCeOpts ce{weight, ignore_index, has_ignore, 0.f};
-    const HybCeFocal focal{gamma, 0.f, 0.f};
-    HYB_CHECK_ARG(dloss && logits && target && hyb_ce_focal_ok(ce, focal, nullptr));
-    return temporal_bwd_impl(dtype, nullptr, logits, target, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
-                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
-                             workspace_bytes, stream, &ce, nullptr, nullptr, &focal);
-}
-extern "C" int hyb_temporal_ce_asym_fwd(int dtype, const void* h, const float* token_w, const float* token_b, const float* const* enc_params,
-                                        const float* head_w, const float* head_b, const float* mask, const float* target, const float* weight,
-                                        const float* pos_weight, float gamma_pos, float gamma_neg, float clip, void* feat, void* tok, void* enc_saved,
-                                        void* enc_out, float* logits, float* loss, float* ce_scratch, int B, int S, int HW, int C, int Cp, int D,
-                                        int Hid, int L, int H, int classes, float attn_p, float layer_p, unsigned long long seed,
-                                        const unsigned long long* seed_inc, void* stream) {
-    const HybCeOpts ce{weight, 0, 0, 0.f};
-    const HybCeDense dense{target, pos_weight, 1};
-    const HybCeFocal focal{gamma_pos, gamma_neg, clip};
-    HYB_CHECK_ARG(loss && ce_scratch && hyb_ce_focal_ok(ce, focal, &dense));
-    return temporal_fwd_impl(dtype, h, token_w, token_b, enc_params, head_w, head_b, mask, feat, tok, enc_saved, enc_out, logits, B, S, HW, C, Cp, D,
-                             Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, nullptr, loss, ce_scratch, stream, &ce, nullptr, &dense, &focal);
+    const HybLoss l = hyb_loss_focal(target, weight, ignore_index, has_ignore, gamma);
+    return temporal_bwd_impl(dtype, nullptr, logits, dloss, &l, HYB_TEMPORAL_BWD_COMMON);
 }
 extern "C" int hyb_temporal_ce_asym_bwd(int dtype, const float* dloss, const float* logits, const float* target, const float* weight,
                                         const float* pos_weight, float gamma_pos, float gamma_neg, float clip, const float* token_w,
@@ -525,11 +474,7 @@ extern "C" int hyb_temporal_ce_asym_bwd(int dtype, const float* dloss, const flo
                                         float* dhead_w, float* dhead_b, void* dh, int B, int S, int HW, int C, int Cp, int D, int Hid, int L, int H,
                                         int classes, float attn_p, float layer_p, unsigned long long seed, const unsigned long long* seed_inc,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-    const HybCeOpts ce{weight, 0, 0, 0.f};
-    const HybCeDense dense{target, pos_weight, 1};
-    const HybCeFocal focal{gamma_pos, gamma_neg, clip};
-    HYB_CHECK_ARG(dloss && logits && hyb_ce_focal_ok(ce, focal, &dense));
-    return temporal_bwd_impl(dtype, nullptr, logits, nullptr, dloss, token_w, enc_params, head_w, mask, feat, enc_saved, enc_out, dtoken_w, dtoken_b,
-                             enc_grads, dhead_w, dhead_b, dh, B, S, HW, C, Cp, D, Hid, L, H, classes, attn_p, layer_p, seed, seed_inc, workspace,
-                             workspace_bytes, stream, &ce, nullptr, &dense, &focal);
+    const HybLoss l = hyb_loss_asym(target, weight, pos_weight, gamma_pos, gamma_neg, clip);
+    return temporal_bwd_impl(dtype, nullptr, logits, dloss, &l, HYB_TEMPORAL_BWD_COMMON);
 }
+#undef HYB_TEMPORAL_BWD_COMMON

@@ -88,30 +88,54 @@ int hyb_ln_rows_reduce(const float* part, int rows, int D, float* dgamma, float*
 int hyb_temporal_tail_ok(int B, int S, int D, int C, int ln_rows);
 // the cross-entropy loss's options as the *_opts_* entry points and kernels carry them (weight: [C] device floats, or nullptr = all ones)
 struct HybCeOpts { const float* weight; long long ignore_index; int has_ignore; float label_smoothing; };
-int hyb_ce_opts_ok(const HybCeOpts& o);
+int hyb_ce_opts_ok(const HybCeOpts& o);                    // (the evaluation meter's check too)
 // the second target and the mixing weight of every clip as the *_mix_* entry points and kernels carry them ([B] each, device memory)
 struct HybCeMix { const long long* target_b; const float* lam; };
 // a dense target as the *_dense_* entry points and kernels carry it: target [B][C] fp32 rows; kind 0: class probabilities (soft-target
 // cross-entropy), kind 1: per-class binary targets (BCE with logits; pos_weight [C] or nullptr = all ones).  label_smoothing and weight
 // travel in HybCeOpts (whose ignore fields are unused).
 struct HybCeDense { const float* target; const float* pos_weight; int kind; };
-int hyb_ce_dense_ok(const HybCeOpts& o, const HybCeDense& d);
 // the focusing scalars as the *_focal_* / *_asym_* entry points and kernels carry them, by value.  Index focal: gamma (gamma_neg and clip
 // are 0), beside HybCeOpts (no label smoothing).  Asymmetric: gamma is the positives' exponent, gamma_neg the negatives', clip the
 // probability shift m in [0, 1), beside HybCeOpts (weight only) and a HybCeDense of kind 1 (target, pos_weight).
 struct HybCeFocal { float gamma; float gamma_neg; float clip; };
-int hyb_ce_focal_ok(const HybCeOpts& o, const HybCeFocal& f, const HybCeDense* d);
-// ce != nullptr (a target is given): the loss with options, in the same one launch; mix != nullptr (needs ce): two targets per clip;
-// dense != nullptr (needs ce, target == nullptr, no mix): the dense-target loss; focal != nullptr (needs ce, no mix): index focal with a
-// target, the asymmetric loss with dense (kind 1)
+// One loss, described once from the entry point to the kernel launch.  mode == the MODE template argument of temporal_tail_{fwd,bwd}_body
+// (layernorm.hip); the members a mode does not read stay zero.  target: class indices [B] (PLAIN, OPTS, MIX, FOCAL); the dense modes
+// (SOFT = HybCeDense kind 0, BCE = kind 1, ASYM) carry theirs in d.  hyb_loss_*(): the members each family of entry points fills.
+enum HybLossMode { HYB_LOSS_PLAIN = 0, HYB_LOSS_OPTS, HYB_LOSS_MIX, HYB_LOSS_SOFT, HYB_LOSS_BCE, HYB_LOSS_FOCAL, HYB_LOSS_ASYM };
+struct HybLoss { int mode; const long long* target; HybCeOpts o; HybCeMix m; HybCeDense d; HybCeFocal f; };
+inline bool hyb_loss_is_dense(int mode) { return mode == HYB_LOSS_SOFT || mode == HYB_LOSS_BCE || mode == HYB_LOSS_ASYM; }
+inline HybLoss hyb_loss_plain(const long long* target) { return {HYB_LOSS_PLAIN, target}; }
+inline HybLoss hyb_loss_opts(const long long* target, const float* weight, long long ignore_index, int has_ignore, float label_smoothing) {
+    return {HYB_LOSS_OPTS, target, {weight, ignore_index, has_ignore, label_smoothing}};
+}
+inline HybLoss hyb_loss_mix(const long long* target, const long long* target_b, const float* lam, const float* weight, long long ignore_index,
+                            int has_ignore, float label_smoothing) {
+    return {HYB_LOSS_MIX, target, {weight, ignore_index, has_ignore, label_smoothing}, {target_b, lam}};
+}
+inline HybLoss hyb_loss_dense(const float* target, const float* weight, const float* pos_weight, int kind, float label_smoothing) {
+    return {kind == 1 ? HYB_LOSS_BCE : HYB_LOSS_SOFT, nullptr, {weight, 0, 0, label_smoothing}, {}, {target, pos_weight, kind}};
+}
+inline HybLoss hyb_loss_focal(const long long* target, const float* weight, long long ignore_index, int has_ignore, float gamma) {
+    return {HYB_LOSS_FOCAL, target, {weight, ignore_index, has_ignore, 0.f}, {}, {}, {gamma, 0.f, 0.f}};
+}
+inline HybLoss hyb_loss_asym(const float* target, const float* weight, const float* pos_weight, float gamma_pos, float gamma_neg, float clip) {
+    return {HYB_LOSS_ASYM, nullptr, {weight, 0, 0, 0.f}, {}, {target, pos_weight, 1}, {gamma_pos, gamma_neg, clip}};
+}
+// the one validity rule: the mode's target is there, and its members are in the ranges include/hybrid_hip.h states
+int hyb_loss_ok(const HybLoss& l);
+// the stand-alone launches (ce_*_kernel) of any mode: what the hyb_cross_entropy*_{fwd,bwd} entry points are, and what the temporal part
+// runs behind the head where the tail kernels do not take the shape
+int hyb_loss_fwd(const HybLoss& l, const float* logits, float* loss, int B, int C, hipStream_t st);
+int hyb_loss_bwd(const HybLoss& l, const float* logits, const float* dloss, float* dlogits, int B, int C, hipStream_t st);
+// l != nullptr: the loss in the same one launch (forward: into loss, with ce_scratch; backward: from the saved logits and dloss);
+// l == nullptr: logits only / the caller's dlogits
 int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float* gamma, const float* beta, void* enc_out, float* stats, int B, int S, int D,
                           float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const float* W, const float* bias,
-                          float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st, const HybCeOpts* ce = nullptr,
-                          const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr, const HybCeFocal* focal = nullptr);
-int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* W, const void* enc_out,
-                          const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part, int ln_rows, float* head_part, int B, int S,
-                          int D, int C, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, hipStream_t st,
-                          const HybCeOpts* ce = nullptr, const HybCeMix* mix = nullptr, const HybCeDense* dense = nullptr, const HybCeFocal* focal = nullptr);
+                          float* logits, int C, float* loss, float* ce_scratch, hipStream_t st, const HybLoss* l);
+int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const float* dloss, const float* W, const void* enc_out, const void* f,
+                          const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part, int ln_rows, float* head_part, int B, int S, int D, int C,
+                          float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, hipStream_t st, const HybLoss* l);
 // linear.hip
 int hyb_linear_bwd_wt(int dtype, const void* x, int ldx, const float* W, const void* Wt, const void* y, const void* dy, void* dx, int accumulate_dx, float* dW,
                       float* db, int M, int N, int K, int relu, void* ws, size_t ws_bytes, hipStream_t st);

@@ -1383,71 +1383,52 @@ int hyb_ln_rows_reduce(const float* part, int rows, int D, float* dgamma, float*
 int hyb_temporal_tail_ok(int B, int S, int D, int C, int ln_rows) {
     return B >= 1 && B <= ln_rows && S >= 1 && D % 8 == 0 && D <= 1536 && C >= 1 && C <= 64;       // (D: 64 KB of LDS in the backward)
 }
+// l: the loss in the same launch, or nullptr.  One kernel wrapper per HybLossMode (`launch`, T = float / bf16): the arguments every wrapper
+// takes, then the mode's own.  LDS behind the common part: [64] class weights for every mode with options, [64] + [64] target row and
+// pos_weight more for the dense ones.
 int hyb_temporal_tail_fwd(int dtype, const void* f, const void* x1, const float* gamma, const float* beta, void* enc_out, float* stats, int B, int S,
                           int D, float eps, float out_scale, float p_drop, unsigned long long seed, const unsigned long long* seed_inc, const float* W,
-                          const float* bias, float* logits, int C, const long long* target, float* loss, float* ce_scratch, hipStream_t st,
-                          const HybCeOpts* ce, const HybCeMix* mix, const HybCeDense* dense, const HybCeFocal* focal) {
-    HYB_CHECK_ARG(f && x1 && gamma && beta && enc_out && stats && W && logits && (!target || (loss && ce_scratch)) && (!ce || target || dense));
-    HYB_CHECK_ARG(!mix || (ce && mix->target_b && mix->lam));
-    HYB_CHECK_ARG(!dense || (ce && !target && !mix && loss && ce_scratch && hyb_ce_dense_ok(*ce, *dense)));
-    HYB_CHECK_ARG(!focal || (ce && !mix && (dense || target) && hyb_ce_focal_ok(*ce, *focal, dense)));
+                          const float* bias, float* logits, int C, float* loss, float* ce_scratch, hipStream_t st, const HybLoss* l) {
+    HYB_CHECK_ARG(f && x1 && gamma && beta && enc_out && stats && W && logits && (!l || (loss && ce_scratch && hyb_loss_ok(*l))));
+    HYB_CHECK_ARG(dtype == HYB_F32 || dtype == HYB_BF16);
+    const int mode = l ? l->mode : HYB_LOSS_PLAIN;
     const size_t es = dtype == HYB_F32 ? 4 : 2;
-    const size_t base = ((size_t)D + 64 + 256 + (ce ? 64 : 0) + (dense ? 128 : 0)) * sizeof(float);
+    const size_t base = ((size_t)D + 64 + 256 + (mode != HYB_LOSS_PLAIN ? 64 : 0) + (hyb_loss_is_dense(mode) ? 128 : 0)) * sizeof(float);
     const int rows_in_lds = base + (size_t)S * D * es <= 60 * 1024;
     const size_t lds = base + (rows_in_lds ? (size_t)S * D * es : 0);
     const int threads = S >= 8 ? 512 : 256;             // (1024 threads leave 128 registers per lane: the LayerNorm row spills -- measured 13 -> 24 us)
-#define HYB_TAIL_FWD_FOCAL(T)                                                                                                                        \
-    do {                                                                                                                                            \
-        if (dense)                                                                                                                                  \
-            hipLaunchKernelGGL(temporal_tail_fwd_asym_kernel<T>, dim3(B), dim3(threads), lds, st, (const T*)f, (const T*)x1, gamma, beta, (T*)enc_out, stats, B, \
-                               S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, loss, ce_scratch, rows_in_lds, *ce, *dense, *focal); \
-        else                                                                                                                                        \
-            hipLaunchKernelGGL(temporal_tail_fwd_focal_kernel<T>, dim3(B), dim3(threads), lds, st, (const T*)f, (const T*)x1, gamma, beta, (T*)enc_out, stats, B, \
-                               S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce, *focal); \
-    } while (0)
-    if (focal && dtype == HYB_F32) HYB_TAIL_FWD_FOCAL(float);
-    else if (focal && dtype == HYB_BF16) HYB_TAIL_FWD_FOCAL(bf16);
-    else
-#undef HYB_TAIL_FWD_FOCAL
-#define HYB_TAIL_FWD_DENSE(T, KIND)                                                                                                                  \
-    hipLaunchKernelGGL((temporal_tail_fwd_dense_kernel<T, KIND>), dim3(B), dim3(threads), lds, st, (const T*)f, (const T*)x1, gamma, beta, (T*)enc_out, stats, \
-                       B, S, D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, loss, ce_scratch, rows_in_lds, *ce, *dense)
-    if (dense && dtype == HYB_F32) { if (dense->kind == 1) HYB_TAIL_FWD_DENSE(float, 1); else HYB_TAIL_FWD_DENSE(float, 0); }
-    else if (dense && dtype == HYB_BF16) { if (dense->kind == 1) HYB_TAIL_FWD_DENSE(bf16, 1); else HYB_TAIL_FWD_DENSE(bf16, 0); }
-#undef HYB_TAIL_FWD_DENSE
-    else if (mix && dtype == HYB_F32)
-        hipLaunchKernelGGL(temporal_tail_fwd_mix_kernel<float>, dim3(B), dim3(threads), lds, st, (const float*)f, (const float*)x1, gamma, beta, (float*)enc_out, stats, B, S,
-                           D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce, *mix);
-    else if (mix && dtype == HYB_BF16)
-        hipLaunchKernelGGL(temporal_tail_fwd_mix_kernel<bf16>, dim3(B), dim3(threads), lds, st, (const bf16*)f, (const bf16*)x1, gamma, beta, (bf16*)enc_out, stats, B, S,
-                           D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce, *mix);
-    else if (ce && dtype == HYB_F32)
-        hipLaunchKernelGGL(temporal_tail_fwd_opts_kernel<float>, dim3(B), dim3(threads), lds, st, (const float*)f, (const float*)x1, gamma, beta, (float*)enc_out, stats, B, S,
-                           D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce);
-    else if (ce && dtype == HYB_BF16)
-        hipLaunchKernelGGL(temporal_tail_fwd_opts_kernel<bf16>, dim3(B), dim3(threads), lds, st, (const bf16*)f, (const bf16*)x1, gamma, beta, (bf16*)enc_out, stats, B, S,
-                           D, eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds, *ce);
-    else if (dtype == HYB_F32)
-        hipLaunchKernelGGL(temporal_tail_fwd_kernel<float>, dim3(B), dim3(threads), lds, st, (const float*)f, (const float*)x1, gamma, beta, (float*)enc_out, stats, B, S, D,
-                           eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds);
-    else if (dtype == HYB_BF16)
-        hipLaunchKernelGGL(temporal_tail_fwd_kernel<bf16>, dim3(B), dim3(threads), lds, st, (const bf16*)f, (const bf16*)x1, gamma, beta, (bf16*)enc_out, stats, B, S, D,
-                           eps, out_scale, p_drop, seed, seed_inc, W, bias, logits, C, target, loss, ce_scratch, rows_in_lds);
-    else return HYB_E_ARG;
+    auto launch = [&](auto t) {
+        using T = decltype(t);
+#define HYB_TAIL_FWD(kernel, ...)                                                                                                                 \
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(threads), lds, st, (const T*)f, (const T*)x1, gamma, beta, (T*)enc_out, stats, B, S, D, eps, out_scale, \
+                       p_drop, seed, seed_inc, W, bias, logits, C, __VA_ARGS__)
+        switch (mode) {
+        case HYB_LOSS_PLAIN: HYB_TAIL_FWD(temporal_tail_fwd_kernel<T>, l ? l->target : nullptr, loss, ce_scratch, rows_in_lds); break;
+        case HYB_LOSS_OPTS: HYB_TAIL_FWD(temporal_tail_fwd_opts_kernel<T>, l->target, loss, ce_scratch, rows_in_lds, l->o); break;
+        case HYB_LOSS_MIX: HYB_TAIL_FWD(temporal_tail_fwd_mix_kernel<T>, l->target, loss, ce_scratch, rows_in_lds, l->o, l->m); break;
+        case HYB_LOSS_SOFT: HYB_TAIL_FWD((temporal_tail_fwd_dense_kernel<T, 0>), loss, ce_scratch, rows_in_lds, l->o, l->d); break;
+        case HYB_LOSS_BCE: HYB_TAIL_FWD((temporal_tail_fwd_dense_kernel<T, 1>), loss, ce_scratch, rows_in_lds, l->o, l->d); break;
+        case HYB_LOSS_FOCAL: HYB_TAIL_FWD(temporal_tail_fwd_focal_kernel<T>, l->target, loss, ce_scratch, rows_in_lds, l->o, l->f); break;
+        case HYB_LOSS_ASYM: HYB_TAIL_FWD(temporal_tail_fwd_asym_kernel<T>, loss, ce_scratch, rows_in_lds, l->o, l->d, l->f); break;
+        }
+#undef HYB_TAIL_FWD
+    };
+    if (dtype == HYB_F32) launch(float{});
+    else launch(bf16{});
     HYB_LAUNCH_CHECK();
     return 0;
 }
-int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const long long* target, const float* dloss, const float* W,
-                          const void* enc_out, const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part,
-                          int ln_rows, float* head_part, int B, int S, int D, int C, float out_scale, float p_drop, unsigned long long seed,
-                          const unsigned long long* seed_inc, hipStream_t st, const HybCeOpts* ce, const HybCeMix* mix, const HybCeDense* dense,
-                          const HybCeFocal* focal) {
-    HYB_CHECK_ARG((dlogits || (logits && (target || dense) && dloss)) && W && enc_out && f && gamma && stats && dx && dskip && ln_part && head_part);
-    HYB_CHECK_ARG(!ce || (!dlogits && logits && (target || dense) && dloss));
-    HYB_CHECK_ARG(!mix || (ce && mix->target_b && mix->lam));
-    HYB_CHECK_ARG(!dense || (ce && !target && !mix && hyb_ce_dense_ok(*ce, *dense)));
-    HYB_CHECK_ARG(!focal || (ce && !mix && (dense || target) && hyb_ce_focal_ok(*ce, *focal, dense)));
-    const size_t lds = (64 + 9 * (size_t)D + (dense ? 3 * 64 : ce ? 64 + 256 : 0)) * sizeof(float);
+// l: the loss backward from the saved logits and dloss in the same launch; nullptr: the caller's dlogits.  LDS behind the common part: [64]
+// class weights, target row and pos_weight for the dense modes, [64] class weights and the [256] den tree for the others with options.
+int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, const float* dloss, const float* W, const void* enc_out,
+                          const void* f, const float* gamma, const float* stats, void* dx, void* dskip, float* ln_part, int ln_rows,
+                          float* head_part, int B, int S, int D, int C, float out_scale, float p_drop, unsigned long long seed,
+                          const unsigned long long* seed_inc, hipStream_t st, const HybLoss* l) {
+    HYB_CHECK_ARG((l ? !dlogits && logits && dloss && hyb_loss_ok(*l) : dlogits != nullptr) && W && enc_out && f && gamma && stats && dx && dskip && ln_part &&
+                  head_part);
+    HYB_CHECK_ARG(dtype == HYB_F32 || dtype == HYB_BF16);
+    const int mode = l ? l->mode : HYB_LOSS_PLAIN;
+    const size_t lds = (64 + 9 * (size_t)D + (hyb_loss_is_dense(mode) ? 3 * 64 : mode != HYB_LOSS_PLAIN ? 64 + 256 : 0)) * sizeof(float);
     // row blocks per clip: as many as the ln_rows partial rows allow (>= 1: hyb_temporal_tail_ok), four-row granules
     int nsb = hyb_cdiv(S, 4);
     if (nsb > ln_rows / B) nsb = ln_rows / B;
@@ -1455,44 +1436,26 @@ int hyb_temporal_tail_bwd(int dtype, const float* dlogits, const float* logits, 
     nsb = hyb_cdiv(S, rpw);
     const dim3 grid(nsb, B);
     if (lds > 64 * 1024) return HYB_E_ARG;
-#define HYB_TAIL_BWD_FOCAL(T)                                                                                                                        \
-    do {                                                                                                                                            \
-        if (dense)                                                                                                                                  \
-            hipLaunchKernelGGL(temporal_tail_bwd_asym_kernel<T>, grid, dim3(256), lds, st, logits, dloss, W, (const T*)enc_out, (const T*)f, gamma, stats,       \
-                               (T*)dx, (T*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *dense, *focal); \
-        else                                                                                                                                        \
-            hipLaunchKernelGGL(temporal_tail_bwd_focal_kernel<T>, grid, dim3(256), lds, st, logits, target, dloss, W, (const T*)enc_out, (const T*)f, gamma,     \
-                               stats, (T*)dx, (T*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *focal); \
-    } while (0)
-    if (focal && dtype == HYB_F32) HYB_TAIL_BWD_FOCAL(float);
-    else if (focal && dtype == HYB_BF16) HYB_TAIL_BWD_FOCAL(bf16);
-    else
-#undef HYB_TAIL_BWD_FOCAL
-#define HYB_TAIL_BWD_DENSE(T, KIND)                                                                                                                  \
-    hipLaunchKernelGGL((temporal_tail_bwd_dense_kernel<T, KIND>), grid, dim3(256), lds, st, logits, dloss, W, (const T*)enc_out, (const T*)f, gamma, stats,    \
-                       (T*)dx, (T*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *dense)
-    if (dense && dtype == HYB_F32) { if (dense->kind == 1) HYB_TAIL_BWD_DENSE(float, 1); else HYB_TAIL_BWD_DENSE(float, 0); }
-    else if (dense && dtype == HYB_BF16) { if (dense->kind == 1) HYB_TAIL_BWD_DENSE(bf16, 1); else HYB_TAIL_BWD_DENSE(bf16, 0); }
-#undef HYB_TAIL_BWD_DENSE
-    else if (mix && dtype == HYB_F32)
-        hipLaunchKernelGGL(temporal_tail_bwd_mix_kernel<float>, grid, dim3(256), lds, st, logits, target, dloss, W, (const float*)enc_out, (const float*)f, gamma, stats,
-                           (float*)dx, (float*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *mix);
-    else if (mix && dtype == HYB_BF16)
-        hipLaunchKernelGGL(temporal_tail_bwd_mix_kernel<bf16>, grid, dim3(256), lds, st, logits, target, dloss, W, (const bf16*)enc_out, (const bf16*)f, gamma, stats,
-                           (bf16*)dx, (bf16*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce, *mix);
-    else if (ce && dtype == HYB_F32)
-        hipLaunchKernelGGL(temporal_tail_bwd_opts_kernel<float>, grid, dim3(256), lds, st, logits, target, dloss, W, (const float*)enc_out, (const float*)f, gamma, stats,
-                           (float*)dx, (float*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce);
-    else if (ce && dtype == HYB_BF16)
-        hipLaunchKernelGGL(temporal_tail_bwd_opts_kernel<bf16>, grid, dim3(256), lds, st, logits, target, dloss, W, (const bf16*)enc_out, (const bf16*)f, gamma, stats,
-                           (bf16*)dx, (bf16*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc, *ce);
-    else if (dtype == HYB_F32)
-        hipLaunchKernelGGL(temporal_tail_bwd_kernel<float>, grid, dim3(256), lds, st, dlogits, logits, target, dloss, W, (const float*)enc_out, (const float*)f, gamma,
-                           stats, (float*)dx, (float*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc);
-    else if (dtype == HYB_BF16)
-        hipLaunchKernelGGL(temporal_tail_bwd_kernel<bf16>, grid, dim3(256), lds, st, dlogits, logits, target, dloss, W, (const bf16*)enc_out, (const bf16*)f, gamma,
-                           stats, (bf16*)dx, (bf16*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, seed_inc);
-    else return HYB_E_ARG;
+    auto launch = [&](auto t) {
+        using T = decltype(t);
+#define HYB_TAIL_BWD(kernel, ...) hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, __VA_ARGS__)
+#define HYB_TAIL_BWD_COMMON                                                                                                                      \
+    dloss, W, (const T*)enc_out, (const T*)f, gamma, stats, (T*)dx, (T*)dskip, ln_part, ln_rows, head_part, B, S, D, C, rpw, out_scale, p_drop, seed, \
+        seed_inc
+        switch (mode) {
+        case HYB_LOSS_PLAIN: HYB_TAIL_BWD(temporal_tail_bwd_kernel<T>, dlogits, logits, l ? l->target : nullptr, HYB_TAIL_BWD_COMMON); break;
+        case HYB_LOSS_OPTS: HYB_TAIL_BWD(temporal_tail_bwd_opts_kernel<T>, logits, l->target, HYB_TAIL_BWD_COMMON, l->o); break;
+        case HYB_LOSS_MIX: HYB_TAIL_BWD(temporal_tail_bwd_mix_kernel<T>, logits, l->target, HYB_TAIL_BWD_COMMON, l->o, l->m); break;
+        case HYB_LOSS_SOFT: HYB_TAIL_BWD((temporal_tail_bwd_dense_kernel<T, 0>), logits, HYB_TAIL_BWD_COMMON, l->o, l->d); break;
+        case HYB_LOSS_BCE: HYB_TAIL_BWD((temporal_tail_bwd_dense_kernel<T, 1>), logits, HYB_TAIL_BWD_COMMON, l->o, l->d); break;
+        case HYB_LOSS_FOCAL: HYB_TAIL_BWD(temporal_tail_bwd_focal_kernel<T>, logits, l->target, HYB_TAIL_BWD_COMMON, l->o, l->f); break;
+        case HYB_LOSS_ASYM: HYB_TAIL_BWD(temporal_tail_bwd_asym_kernel<T>, logits, HYB_TAIL_BWD_COMMON, l->o, l->d, l->f); break;
+        }
+#undef HYB_TAIL_BWD_COMMON
+#undef HYB_TAIL_BWD
+    };
+    if (dtype == HYB_F32) launch(float{});
+    else launch(bf16{});
     HYB_LAUNCH_CHECK();
     return 0;
 }
@@ -1527,135 +1490,107 @@ extern "C" int hyb_head_bwd(int dtype, const void* x, const float* W, const floa
     return 0;
 }
 
-extern "C" int hyb_cross_entropy_fwd(const float* logits, const long long* target, float* loss, int B, int C, void* stream) {
-    HYB_CHECK_ARG(logits && target && loss && B > 0 && C > 0);
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, B, C);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int hyb_cross_entropy_bwd(const float* logits, const long long* target, const float* dloss, float* dlogits, int B, int C, void* stream) {
-    HYB_CHECK_ARG(logits && target && dloss && dlogits && B > 0 && C > 0);
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3(hyb_cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-// The loss with options (ce_opts_*_kernel).  hyb_ce_opts_ok: what every *_opts_* entry point asks of them.
+// The loss by itself (ce_*_kernel; include/hybrid_hip.h states every definition).  hyb_loss_ok: what every entry point that carries a loss asks
+// of it beyond its own non-null pointers.  hyb_ce_opts_ok: the options' ranges.  An exponent is 0 or >= 1: between, the derivative of
+// base^g is singular at base == 0, which clipped negatives reach exactly.
 int hyb_ce_opts_ok(const HybCeOpts& o) {
     return (o.has_ignore == 0 || o.has_ignore == 1) && o.label_smoothing >= 0.f && o.label_smoothing <= 1.f;
 }
-extern "C" int hyb_cross_entropy_opts_fwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
-                                          float label_smoothing, float* loss, int B, int C, void* stream) {
-    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
-    HYB_CHECK_ARG(logits && target && loss && B > 0 && C > 0 && hyb_ce_opts_ok(o));
-    hipLaunchKernelGGL(ce_opts_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, B, C, o);
+static int ce_gamma_ok(float g) { return g == 0.f || (g >= 1.f && g <= 3.0e38f); }
+int hyb_loss_ok(const HybLoss& l) {
+    if (hyb_loss_is_dense(l.mode) ? !l.d.target : !l.target) return 0;
+    const float ls = l.o.label_smoothing;
+    switch (l.mode) {
+    case HYB_LOSS_PLAIN: return 1;
+    case HYB_LOSS_OPTS: return hyb_ce_opts_ok(l.o);
+    case HYB_LOSS_MIX: return l.m.target_b && l.m.lam && hyb_ce_opts_ok(l.o);
+    case HYB_LOSS_SOFT: return l.d.kind == 0 && !l.d.pos_weight && ls >= 0.f && ls <= 1.f;
+    case HYB_LOSS_BCE: return l.d.kind == 1 && ls == 0.f;
+    case HYB_LOSS_FOCAL: return ls == 0.f && ce_gamma_ok(l.f.gamma) && l.f.gamma_neg == 0.f && l.f.clip == 0.f;
+    case HYB_LOSS_ASYM: return l.d.kind == 1 && ls == 0.f && ce_gamma_ok(l.f.gamma) && ce_gamma_ok(l.f.gamma_neg) && l.f.clip >= 0.f && l.f.clip < 1.f;
+    }
+    return 0;
+}
+// forward: one workgroup; backward: a thread per clip
+int hyb_loss_fwd(const HybLoss& l, const float* logits, float* loss, int B, int C, hipStream_t st) {
+    HYB_CHECK_ARG(logits && loss && B > 0 && C > 0 && hyb_loss_ok(l));
+    const dim3 grid(1), block(256);
+    switch (l.mode) {
+    case HYB_LOSS_PLAIN: hipLaunchKernelGGL(ce_fwd_kernel, grid, block, 0, st, logits, l.target, loss, B, C); break;
+    case HYB_LOSS_OPTS: hipLaunchKernelGGL(ce_opts_fwd_kernel, grid, block, 0, st, logits, l.target, loss, B, C, l.o); break;
+    case HYB_LOSS_MIX: hipLaunchKernelGGL(ce_mix_fwd_kernel, grid, block, 0, st, logits, l.target, loss, B, C, l.o, l.m); break;
+    case HYB_LOSS_SOFT:
+    case HYB_LOSS_BCE: hipLaunchKernelGGL(ce_dense_fwd_kernel, grid, block, 0, st, logits, loss, B, C, l.o, l.d); break;
+    case HYB_LOSS_FOCAL: hipLaunchKernelGGL(ce_focal_fwd_kernel, grid, block, 0, st, logits, l.target, loss, B, C, l.o, l.f); break;
+    case HYB_LOSS_ASYM: hipLaunchKernelGGL(ce_asym_fwd_kernel, grid, block, 0, st, logits, loss, B, C, l.o, l.d, l.f); break;
+    }
     HYB_LAUNCH_CHECK();
     return 0;
 }
-extern "C" int hyb_cross_entropy_opts_bwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
-                                          float label_smoothing, const float* dloss, float* dlogits, int B, int C, void* stream) {
-    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
-    HYB_CHECK_ARG(logits && target && dloss && dlogits && B > 0 && C > 0 && hyb_ce_opts_ok(o));
-    hipLaunchKernelGGL(ce_opts_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o);
+int hyb_loss_bwd(const HybLoss& l, const float* logits, const float* dloss, float* dlogits, int B, int C, hipStream_t st) {
+    HYB_CHECK_ARG(logits && dloss && dlogits && B > 0 && C > 0 && hyb_loss_ok(l));
+    const dim3 grid(hyb_cdiv(B, 256)), block(256);
+    switch (l.mode) {
+    case HYB_LOSS_PLAIN: hipLaunchKernelGGL(ce_bwd_kernel, dim3(hyb_cdiv(B, 64)), dim3(64), 0, st, logits, l.target, dloss, dlogits, B, C); break;
+    case HYB_LOSS_OPTS: hipLaunchKernelGGL(ce_opts_bwd_kernel, grid, block, 0, st, logits, l.target, dloss, dlogits, B, C, l.o); break;
+    case HYB_LOSS_MIX: hipLaunchKernelGGL(ce_mix_bwd_kernel, grid, block, 0, st, logits, l.target, dloss, dlogits, B, C, l.o, l.m); break;
+    case HYB_LOSS_SOFT:
+    case HYB_LOSS_BCE: hipLaunchKernelGGL(ce_dense_bwd_kernel, grid, block, 0, st, logits, dloss, dlogits, B, C, l.o, l.d); break;
+    case HYB_LOSS_FOCAL: hipLaunchKernelGGL(ce_focal_bwd_kernel, grid, block, 0, st, logits, l.target, dloss, dlogits, B, C, l.o, l.f); break;
+    case HYB_LOSS_ASYM: hipLaunchKernelGGL(ce_asym_bwd_kernel, grid, block, 0, st, logits, dloss, dlogits, B, C, l.o, l.d, l.f); break;
+    }
     HYB_LAUNCH_CHECK();
     return 0;
 }
 
-// The loss with options and two targets per clip (ce_mix_*_kernel; include/hybrid_hip.h states the definition)
+// The twelve entry points: each fills a HybLoss with its own arguments (hyb_internal.h) and runs the pair above.
+extern "C" int hyb_cross_entropy_fwd(const float* logits, const long long* target, float* loss, int B, int C, void* stream) {
+    return hyb_loss_fwd(hyb_loss_plain(target), logits, loss, B, C, (hipStream_t)stream);
+}
+extern "C" int hyb_cross_entropy_bwd(const float* logits, const long long* target, const float* dloss, float* dlogits, int B, int C, void* stream) {
+    return hyb_loss_bwd(hyb_loss_plain(target), logits, dloss, dlogits, B, C, (hipStream_t)stream);
+}
+extern "C" int hyb_cross_entropy_opts_fwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                          float label_smoothing, float* loss, int B, int C, void* stream) {
+    return hyb_loss_fwd(hyb_loss_opts(target, weight, ignore_index, has_ignore, label_smoothing), logits, loss, B, C, (hipStream_t)stream);
+}
+extern "C" int hyb_cross_entropy_opts_bwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                          float label_smoothing, const float* dloss, float* dlogits, int B, int C, void* stream) {
+    return hyb_loss_bwd(hyb_loss_opts(target, weight, ignore_index, has_ignore, label_smoothing), logits, dloss, dlogits, B, C, (hipStream_t)stream);
+}
 extern "C" int hyb_cross_entropy_mix_fwd(const float* logits, const long long* target, const long long* target_b, const float* lam, const float* weight,
                                          long long ignore_index, int has_ignore, float label_smoothing, float* loss, int B, int C, void* stream) {
-    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
-    HYB_CHECK_ARG(logits && target && target_b && lam && loss && B > 0 && C > 0 && hyb_ce_opts_ok(o));
-    hipLaunchKernelGGL(ce_mix_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, B, C, o, HybCeMix{target_b, lam});
-    HYB_LAUNCH_CHECK();
-    return 0;
+    return hyb_loss_fwd(hyb_loss_mix(target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing), logits, loss, B, C, (hipStream_t)stream);
 }
 extern "C" int hyb_cross_entropy_mix_bwd(const float* logits, const long long* target, const long long* target_b, const float* lam, const float* weight,
                                          long long ignore_index, int has_ignore, float label_smoothing, const float* dloss, float* dlogits, int B, int C,
                                          void* stream) {
-    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
-    HYB_CHECK_ARG(logits && target && target_b && lam && dloss && dlogits && B > 0 && C > 0 && hyb_ce_opts_ok(o));
-    hipLaunchKernelGGL(ce_mix_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o,
-                       HybCeMix{target_b, lam});
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-// The loss on dense targets (ce_dense_*_kernel; include/hybrid_hip.h states the two definitions).  hyb_ce_dense_ok: what every *_dense_* entry
-// point asks of the options beyond non-null pointers.
-int hyb_ce_dense_ok(const HybCeOpts& o, const HybCeDense& d) {
-    if (!d.target || (d.kind != 0 && d.kind != 1)) return 0;
-    if (!(o.label_smoothing >= 0.f && o.label_smoothing <= 1.f)) return 0;
-    if (d.kind == 1 && o.label_smoothing != 0.f) return 0;
-    if (d.kind == 0 && d.pos_weight) return 0;
-    return 1;
+    return hyb_loss_bwd(hyb_loss_mix(target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing), logits, dloss, dlogits, B, C,
+                        (hipStream_t)stream);
 }
 extern "C" int hyb_cross_entropy_dense_fwd(const float* logits, const float* target, const float* weight, const float* pos_weight, int kind,
                                            float label_smoothing, float* loss, int B, int C, void* stream) {
-    const HybCeOpts o{weight, 0, 0, label_smoothing};
-    const HybCeDense d{target, pos_weight, kind};
-    HYB_CHECK_ARG(logits && loss && B > 0 && C > 0 && hyb_ce_dense_ok(o, d));
-    hipLaunchKernelGGL(ce_dense_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, loss, B, C, o, d);
-    HYB_LAUNCH_CHECK();
-    return 0;
+    return hyb_loss_fwd(hyb_loss_dense(target, weight, pos_weight, kind, label_smoothing), logits, loss, B, C, (hipStream_t)stream);
 }
 extern "C" int hyb_cross_entropy_dense_bwd(const float* logits, const float* target, const float* weight, const float* pos_weight, int kind,
                                            float label_smoothing, const float* dloss, float* dlogits, int B, int C, void* stream) {
-    const HybCeOpts o{weight, 0, 0, label_smoothing};
-    const HybCeDense d{target, pos_weight, kind};
-    HYB_CHECK_ARG(logits && dloss && dlogits && B > 0 && C > 0 && hyb_ce_dense_ok(o, d));
-    hipLaunchKernelGGL(ce_dense_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, dloss, dlogits, B, C, o, d);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-// The focal and asymmetric losses (ce_focal_*_kernel, ce_asym_*_kernel; include/hybrid_hip.h states the definitions).  hyb_ce_focal_ok: what
-// every *_focal_* (d == nullptr) and *_asym_* (d: the dense target, kind 1) entry point asks beyond non-null pointers: each exponent 0 or
-// >= 1 (between, the derivative of base^g is singular at base == 0, which clipped negatives reach exactly), clip in [0, 1), no label
-// smoothing.
-static int ce_gamma_ok(float g) { return g == 0.f || (g >= 1.f && g <= 3.0e38f); }
-int hyb_ce_focal_ok(const HybCeOpts& o, const HybCeFocal& f, const HybCeDense* d) {
-    if (o.label_smoothing != 0.f || !ce_gamma_ok(f.gamma)) return 0;
-    if (!d) return f.gamma_neg == 0.f && f.clip == 0.f;
-    return d->target && d->kind == 1 && ce_gamma_ok(f.gamma_neg) && f.clip >= 0.f && f.clip < 1.f;
+    return hyb_loss_bwd(hyb_loss_dense(target, weight, pos_weight, kind, label_smoothing), logits, dloss, dlogits, B, C, (hipStream_t)stream);
 }
 extern "C" int hyb_cross_entropy_focal_fwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
                                            float gamma, float* loss, int B, int C, void* stream) {
-    const HybCeOpts o{weight, ignore_index, has_ignore, 0.f};
-    const HybCeFocal f{gamma, 0.f, 0.f};
-    HYB_CHECK_ARG(logits && target && loss && B > 0 && C > 0 && hyb_ce_focal_ok(o, f, nullptr));
-    hipLaunchKernelGGL(ce_focal_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, loss, B, C, o, f);
-    HYB_LAUNCH_CHECK();
-    return 0;
+    return hyb_loss_fwd(hyb_loss_focal(target, weight, ignore_index, has_ignore, gamma), logits, loss, B, C, (hipStream_t)stream);
 }
 extern "C" int hyb_cross_entropy_focal_bwd(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
                                            float gamma, const float* dloss, float* dlogits, int B, int C, void* stream) {
-    const HybCeOpts o{weight, ignore_index, has_ignore, 0.f};
-    const HybCeFocal f{gamma, 0.f, 0.f};
-    HYB_CHECK_ARG(logits && target && dloss && dlogits && B > 0 && C > 0 && hyb_ce_focal_ok(o, f, nullptr));
-    hipLaunchKernelGGL(ce_focal_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, target, dloss, dlogits, B, C, o, f);
-    HYB_LAUNCH_CHECK();
-    return 0;
+    return hyb_loss_bwd(hyb_loss_focal(target, weight, ignore_index, has_ignore, gamma), logits, dloss, dlogits, B, C, (hipStream_t)stream);
 }
 extern "C" int hyb_cross_entropy_asym_fwd(const float* logits, const float* target, const float* weight, const float* pos_weight, float gamma_pos,
                                           float gamma_neg, float clip, float* loss, int B, int C, void* stream) {
-    const HybCeOpts o{weight, 0, 0, 0.f};
-    const HybCeDense d{target, pos_weight, 1};
-    const HybCeFocal f{gamma_pos, gamma_neg, clip};
-    HYB_CHECK_ARG(logits && loss && B > 0 && C > 0 && hyb_ce_focal_ok(o, f, &d));
-    hipLaunchKernelGGL(ce_asym_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, loss, B, C, o, d, f);
-    HYB_LAUNCH_CHECK();
-    return 0;
+    return hyb_loss_fwd(hyb_loss_asym(target, weight, pos_weight, gamma_pos, gamma_neg, clip), logits, loss, B, C, (hipStream_t)stream);
 }
 extern "C" int hyb_cross_entropy_asym_bwd(const float* logits, const float* target, const float* weight, const float* pos_weight, float gamma_pos,
                                           float gamma_neg, float clip, const float* dloss, float* dlogits, int B, int C, void* stream) {
-    const HybCeOpts o{weight, 0, 0, 0.f};
-    const HybCeDense d{target, pos_weight, 1};
-    const HybCeFocal f{gamma_pos, gamma_neg, clip};
-    HYB_CHECK_ARG(logits && dloss && dlogits && B > 0 && C > 0 && hyb_ce_focal_ok(o, f, &d));
-    hipLaunchKernelGGL(ce_asym_bwd_kernel, dim3(hyb_cdiv(B, 256)), dim3(256), 0, (hipStream_t)stream, logits, dloss, dlogits, B, C, o, d, f);
-    HYB_LAUNCH_CHECK();
-    return 0;
+    return hyb_loss_bwd(hyb_loss_asym(target, weight, pos_weight, gamma_pos, gamma_neg, clip), logits, dloss, dlogits, B, C, (hipStream_t)stream);
 }
 
 // The classification meter's update (eval_metrics_kernel): one launch of one workgroup that ADDS into sums / counts / confusion.

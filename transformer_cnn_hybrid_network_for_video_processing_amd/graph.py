@@ -227,18 +227,10 @@ class GraphedTrainStep:
         return [(g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"], g.get("max_grad_norm") is not None) for g in self.optimizer.param_groups]
 
     def _loss_opts_now(self):
-        """What a HybridCrossEntropyLoss's launches carry by value or by address: (ignore_index, label_smoothing, the weight buffer's address)."""
-        c = self.criterion
-        from .modules import HybridAsymmetricLoss, HybridBCEWithLogitsLoss, HybridFocalLoss
-        if type(c) is HybridBCEWithLogitsLoss:                      # nothing by value, two buffers by address
-            return (None, 0.0, tuple(None if t is None else t.data_ptr() for t in (c.weight, c.pos_weight)))
-        if type(c) is HybridFocalLoss:                              # (ignore_index, gamma in label_smoothing's place, the weight buffer)
-            return (c.ignore_index, c.gamma, c.weight.data_ptr() if c.weight is not None else None)
-        if type(c) is HybridAsymmetricLoss:                         # the three scalars by value, two buffers by address
-            return ((c.gamma_pos, c.gamma_neg, c.clip), 0.0, tuple(None if t is None else t.data_ptr() for t in (c.weight, c.pos_weight)))
-        if not hasattr(c, "has_options"):
-            return None
-        return (c.ignore_index, c.label_smoothing, c.weight.data_ptr() if c.weight is not None else None)
+        """[(name, value)]: what the criterion's captured launches carry by value and the addresses of the buffers they read, as the criterion
+        itself lists them (modules._Criterion._captured); None for a criterion that is not one of this package's."""
+        captured = getattr(self.criterion, "_captured", None)
+        return captured() if captured is not None else None
 
     def _check_hyper(self):
         """In front of every replay.  Device path: upload what changed.  Plain path: a few comparisons per group (the host is the step's pacemaker
@@ -251,11 +243,7 @@ class GraphedTrainStep:
                                "one launch over all parameter groups -- set it on the optimizer before constructing GraphedTrainStep")
         now = self._loss_opts_now()
         if now != self._captured_loss_opts:
-            from .modules import HybridAsymmetricLoss, HybridFocalLoss
-            first, second = (("gamma_pos / gamma_neg / clip", "label_smoothing") if type(self.criterion) is HybridAsymmetricLoss else
-                             ("ignore_index", "gamma") if type(self.criterion) is HybridFocalLoss else ("ignore_index", "label_smoothing"))
-            what = [n for n, a, b in zip((first, second, "the weight buffer (replaced, not updated in place)"), now,
-                                         self._captured_loss_opts) if a != b]
+            what = [name for (name, a), (_, b) in zip(now, self._captured_loss_opts) if a != b]
             raise RuntimeError(f"GraphedTrainStep: the criterion's {', '.join(what)} changed after capture, but the captured loss launch carries "
                                "the old value -- construct a new GraphedTrainStep (an in-place update of criterion.weight needs none: the "
                                "buffer is read at replay time)")

@@ -196,11 +196,14 @@ def _class_vector(name, v):
     return v.detach().clone()
 
 
-def _check_dense(logits, target):
+def _check_dense(target, B, C, logits=None):
+    """logits: the stand-alone criterion's; None: the fused loss, whose logits [B, C] do not exist yet."""
     if target.dtype != torch.float32:
         raise TypeError(f"a dense target must be float32, got {target.dtype}")
-    if logits.dim() != 2 or target.dim() != 2 or target.shape != logits.shape:
+    if logits is not None and (logits.dim() != 2 or target.dim() != 2 or target.shape != logits.shape):
         raise ValueError(f"a dense target has the shape of the logits [B,C]: got logits {tuple(logits.shape)} and target {tuple(target.shape)}")
+    if target.dim() != 2 or tuple(target.shape) != (B, C):
+        raise ValueError(f"a dense target has the shape of the logits [B={B},C={C}]: got {tuple(target.shape)}")
 
 
 def dense_target(y, num_classes, label_smoothing=0.0):
@@ -226,7 +229,26 @@ def dense_target(y, num_classes, label_smoothing=0.0):
     return t.contiguous()
 
 
-class HybridCrossEntropyLoss(nn.Module):
+def _address(name, t):
+    """A criterion's buffer as a captured launch holds it, by address: an in-place update is read, a replaced buffer is not."""
+    return _BUFFER_NAME[name], None if t is None else t.data_ptr()
+
+
+_BUFFER_NAME = {n: f"the {n} buffer (replaced, not updated in place)" for n in ("weight", "pos_weight")}
+
+
+class _Criterion(nn.Module):
+    """What the four criteria share.  Each describes its own call: ``_loss_call(target, B, C, device, logits=None)`` checks the target and
+    the per-class vectors against logits [B, C] on ``device`` (``logits`` themselves where they exist: the stand-alone call) and returns
+    (family, loss_args) -- the ops.LOSS_FAMILIES row that computes the criterion on that target and the arguments the row's schema lists.
+    forward() hands them to the stand-alone operator, forward_temporal_loss to the fused one.  ``_captured()`` -> [(name, value)]: what a
+    captured launch carries by value, and the addresses of the buffers it reads."""
+
+    def forward(self, logits, target):
+        return ops.cross_entropy_loss(logits, *self._loss_call(target, logits.shape[0], logits.shape[-1], logits.device, logits))
+
+
+class HybridCrossEntropyLoss(_Criterion):
     """Mean cross-entropy over the batch (the composite's own loss), one HIP kernel each way.
 
     ``weight`` (one fp32 entry >= 0 per class), ``ignore_index`` and ``label_smoothing`` mean what they mean in ``nn.CrossEntropyLoss``
@@ -275,25 +297,28 @@ class HybridCrossEntropyLoss(nn.Module):
         if self.ignore_index is not None:
             raise ValueError("ignore_index is not supported with a dense (class-probability) target")
 
-    def forward(self, logits, target):
+    def _loss_call(self, target, B, C, device, logits=None):
+        """A dense target: soft-target cross-entropy (dense, kind 0); a MixTarget: mix; class indices: opts, or -- no options -- the plain
+        operators it always used."""
         if _is_dense(target):
             self._refuse_ignore_index()
-            _check_dense(logits, target)
-            self._check_weight(logits.shape[-1])
-            return ops.cross_entropy_dense(logits, target, self.weight, None, 0, self.label_smoothing)
-        if isinstance(target, MixTarget):
-            self._check_weight(logits.shape[-1])
-            return ops.cross_entropy_mix(logits, target.y_a, target.y_b, target.lam, self.weight, self.ignore_index, self.label_smoothing)
-        if not self.has_options():
-            return ops.cross_entropy(logits, target)
-        self._check_weight(logits.shape[-1])
-        return ops.cross_entropy_opts(logits, target, self.weight, self.ignore_index, self.label_smoothing)
+            _check_dense(target, B, C, logits)
+            self._check_weight(C)
+            return "dense", (target, self.weight, None, 0, float(self.label_smoothing))
+        if not isinstance(target, MixTarget) and not self.has_options():
+            return "plain", (target,)
+        self._check_weight(C)
+        opts = (self.weight, *ops.ignore_args(self.ignore_index), float(self.label_smoothing))
+        return ("mix", (*target, *opts)) if isinstance(target, MixTarget) else ("opts", (target, *opts))
+
+    def _captured(self):
+        return [("ignore_index", self.ignore_index), ("label_smoothing", self.label_smoothing), _address("weight", self.weight)]
 
     def extra_repr(self):
         return f"ignore_index={self.ignore_index}, label_smoothing={self.label_smoothing}"
 
 
-class HybridBCEWithLogitsLoss(nn.Module):
+class HybridBCEWithLogitsLoss(_Criterion):
     """Mean binary cross-entropy with logits over all B x C entries, ``nn.BCEWithLogitsLoss(weight, pos_weight)`` with per-class vectors, one
     HIP kernel each way (include/hybrid_hip.h, hyb_cross_entropy_dense_*, kind 1; the overflow-safe form).  ``target`` is fp32 [B, C],
     contiguous, on the logits' device: multi-label clips, or ``dense_target(y, C)`` of a mixing ClipPipeline's labels.
@@ -312,12 +337,16 @@ class HybridBCEWithLogitsLoss(nn.Module):
             if v is not None and v.shape[0] != C:
                 raise ValueError(f"{name} has {v.shape[0]} entries but the logits have {C} classes")
 
-    def forward(self, logits, target):
+    def _loss_call(self, target, B, C, device, logits=None):
+        """Always the dense family, kind 1."""
         if not _is_dense(target):
             raise TypeError("HybridBCEWithLogitsLoss takes a floating target [B,C] (dense_target() makes one from class indices or a MixTarget)")
-        _check_dense(logits, target)
-        self._check_weight(logits.shape[-1])
-        return ops.cross_entropy_dense(logits, target, self.weight, self.pos_weight, 1, 0.0)
+        _check_dense(target, B, C, logits)
+        self._check_weight(C)
+        return "dense", (target, self.weight, self.pos_weight, 1, 0.0)
+
+    def _captured(self):
+        return [_address("weight", self.weight), _address("pos_weight", self.pos_weight)]
 
 
 def _gamma(name, g):
@@ -330,7 +359,7 @@ def _gamma(name, g):
     return g
 
 
-class HybridFocalLoss(nn.Module):
+class HybridFocalLoss(_Criterion):
     """Mean focal loss on class indices int64 [B] (Lin et al. 2017, the softmax form), one HIP kernel each way (include/hybrid_hip.h,
     hyb_cross_entropy_focal_*): every kept clip's cross-entropy term times ``(1 - p_target) ** gamma``, summed and divided by the kept
     clips' target weights -- ``HybridCrossEntropyLoss(weight, ignore_index)``'s rules throughout (an ignored clip adds nothing, all ignored
@@ -357,16 +386,19 @@ class HybridFocalLoss(nn.Module):
         if isinstance(target, MixTarget) or _is_dense(target):
             raise TypeError("HybridFocalLoss takes class indices int64 [B] (no MixTarget, no dense target)")
 
-    def forward(self, logits, target):
+    def _loss_call(self, target, B, C, device, logits=None):
         self._check_target(target)
-        self._check_weight(logits.shape[-1])
-        return ops.cross_entropy_focal(logits, target, self.weight, self.ignore_index, _gamma("gamma", self.gamma))
+        self._check_weight(C)
+        return "focal", (target, self.weight, *ops.ignore_args(self.ignore_index), _gamma("gamma", self.gamma))
+
+    def _captured(self):
+        return [("ignore_index", self.ignore_index), ("gamma", self.gamma), _address("weight", self.weight)]
 
     def extra_repr(self):
         return f"gamma={self.gamma}, ignore_index={self.ignore_index}"
 
 
-class HybridAsymmetricLoss(nn.Module):
+class HybridAsymmetricLoss(_Criterion):
     """Mean asymmetric loss over all B x C entries (Ridnik et al. 2021) on a floating target [B, C], one HIP kernel each way
     (include/hybrid_hip.h, hyb_cross_entropy_asym_*): positives are focused with ``gamma_pos``, negatives with ``gamma_neg`` after their
     probability is shifted down by ``clip`` (a negative below it adds nothing); the gradient includes the focusing factor.  Each exponent
@@ -415,15 +447,23 @@ class HybridAsymmetricLoss(nn.Module):
             if v is not None and v.shape[0] != C:
                 raise ValueError(f"{name} has {v.shape[0]} entries but the logits have {C} classes")
 
-    def forward(self, logits, target):
+    def _loss_call(self, target, B, C, device, logits=None):
+        """(sigmoid_focal's two vectors are made here, on ``device``)"""
         if not _is_dense(target):
             raise TypeError("HybridAsymmetricLoss takes a floating target [B,C] (dense_target() makes one from class indices or a MixTarget)")
-        _check_dense(logits, target)
-        self._check_weight(logits.shape[-1], logits.device)
-        return ops.cross_entropy_asym(logits, target, self.weight, self.pos_weight, *self._scalars())
+        _check_dense(target, B, C, logits)
+        self._check_weight(C, device)
+        return "asym", (target, self.weight, self.pos_weight, *self._scalars())
+
+    def _captured(self):
+        return [("gamma_pos / gamma_neg / clip", (self.gamma_pos, self.gamma_neg, self.clip)), _address("weight", self.weight),
+                _address("pos_weight", self.pos_weight)]
 
     def extra_repr(self):
         return f"gamma_neg={self.gamma_neg}, gamma_pos={self.gamma_pos}, clip={self.clip}"
+
+
+_DEFAULT_CRITERION = HybridCrossEntropyLoss()          # forward_temporal_loss(criterion=None)
 
 
 class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
@@ -529,82 +569,19 @@ class TransformerCNNHybrid(nn.Module, _ComputeDtypeMixin):
         target: hybrid::temporal_ce_dense, the same launches, as soft-target cross-entropy under a HybridCrossEntropyLoss (or None) and as
         binary cross-entropy under a HybridBCEWithLogitsLoss, which takes nothing else.  Models ``_fused()`` rejects run the criterion behind
         forward_temporal.  A HybridFocalLoss (class indices) and a HybridAsymmetricLoss (a dense target) ride the same way:
-        hybrid::temporal_ce_focal / hybrid::temporal_ce_asym."""
-        enc = self.encoder
-        if criterion is not None and type(criterion) not in (HybridCrossEntropyLoss, HybridBCEWithLogitsLoss, HybridFocalLoss, HybridAsymmetricLoss):
+        hybrid::temporal_ce_focal / hybrid::temporal_ce_asym.  Which operator, and its loss arguments: the criterion's ``_loss_call``."""
+        criterion = _DEFAULT_CRITERION if criterion is None else criterion
+        if type(criterion) not in (HybridCrossEntropyLoss, HybridBCEWithLogitsLoss, HybridFocalLoss, HybridAsymmetricLoss):
             raise TypeError("forward_temporal_loss fuses HybridCrossEntropyLoss, HybridBCEWithLogitsLoss, HybridFocalLoss and HybridAsymmetricLoss only")
-        if type(criterion) in (HybridFocalLoss, HybridAsymmetricLoss):
-            asym = type(criterion) is HybridAsymmetricLoss
-            if asym and not _is_dense(target):
-                raise TypeError("HybridAsymmetricLoss takes a floating target [B,C] (dense_target() makes one from class indices or a MixTarget)")
-            if not asym:
-                criterion._check_target(target)
-            if not self._fused():
-                logits = self.forward_temporal(h, B, mask)
-                return criterion(logits, target), logits
-            classes = self.head.weight.shape[0]
-            tdt = self._temporal_dt()
-            front = (h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias, enc._flat_params(),
-                     self.head.weight, self.head.bias, mask)
-            back = (B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout), ops.next_seed())
-            if asym:
-                if target.dtype != torch.float32:
-                    raise TypeError(f"a dense target must be float32, got {target.dtype}")
-                if target.dim() != 2 or tuple(target.shape) != (B, classes):
-                    raise ValueError(f"a dense target has the shape of the logits [B={B},C={classes}]: got {tuple(target.shape)}")
-                criterion._check_weight(classes, h.device)
-                return ops.temporal_ce_asym(*front, target, criterion.weight, criterion.pos_weight, *criterion._scalars(), *back)
-            criterion._check_weight(classes)
-            return ops.temporal_ce_focal(*front, target, criterion.weight, criterion.ignore_index, _gamma("gamma", criterion.gamma), *back)
-        bce = type(criterion) is HybridBCEWithLogitsLoss
-        if bce or _is_dense(target):
-            if not _is_dense(target):
-                raise TypeError("HybridBCEWithLogitsLoss takes a floating target [B,C] (dense_target() makes one from class indices or a MixTarget)")
-            if not self._fused():
-                logits = self.forward_temporal(h, B, mask)
-                return (criterion or HybridCrossEntropyLoss())(logits, target), logits
-            classes = self.head.weight.shape[0]
-            if not bce and criterion is not None:
-                criterion._refuse_ignore_index()
-            if target.dtype != torch.float32:
-                raise TypeError(f"a dense target must be float32, got {target.dtype}")
-            if target.dim() != 2 or tuple(target.shape) != (B, classes):
-                raise ValueError(f"a dense target has the shape of the logits [B={B},C={classes}]: got {tuple(target.shape)}")
-            if criterion is not None:
-                criterion._check_weight(classes)
-            weight = criterion.weight if criterion is not None else None
-            tdt = self._temporal_dt()
-            return ops.temporal_ce_dense(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias,
-                                         enc._flat_params(), self.head.weight, self.head.bias, mask, target, weight,
-                                         criterion.pos_weight if bce else None, 1 if bce else 0,
-                                         0.0 if bce or criterion is None else criterion.label_smoothing, B, tdt, enc.hidden_dim, enc.num_layers,
-                                         enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout), ops.next_seed())
-        opts = criterion is not None and criterion.has_options()
-        mixed = isinstance(target, MixTarget)
-        if not self._fused():
+        family, loss_args = criterion._loss_call(target, B, self.head.weight.shape[0], h.device)
+        if not self._fused():              # (the call above then only refused a bad target early; the criterion makes its own behind the logits)
             logits = self.forward_temporal(h, B, mask)
-            if mixed:
-                return (criterion or HybridCrossEntropyLoss())(logits, target), logits
-            return (criterion(logits, target) if opts else ops.cross_entropy(logits, target)), logits
-        tdt = self._temporal_dt()
-        if mixed:
-            weight, ignore_index, label_smoothing = criterion.options() if criterion is not None else (None, None, 0.0)
-            if criterion is not None:
-                criterion._check_weight(self.head.weight.shape[0])
-            return ops.temporal_ce_mix(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias,
-                                       enc._flat_params(), self.head.weight, self.head.bias, mask, target.y_a, target.y_b, target.lam, weight,
-                                       ignore_index, label_smoothing, B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads,
-                                       enc.attention_layers[0]._attn_p(), float(enc.dropout), ops.next_seed())
-        if opts:
-            criterion._check_weight(self.head.weight.shape[0])
-            weight, ignore_index, label_smoothing = criterion.options()
-            return ops.temporal_ce_opts(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias,
-                                        enc._flat_params(), self.head.weight, self.head.bias, mask, target, weight, ignore_index, label_smoothing, B, tdt,
-                                        enc.hidden_dim, enc.num_layers, enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout),
-                                        ops.next_seed())
-        return ops.temporal_ce(h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias, enc._flat_params(),
-                               self.head.weight, self.head.bias, mask, target, B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout),
-                               ops.next_seed())
+            return criterion(logits, target), logits
+        enc, tdt = self.encoder, self._temporal_dt()
+        front = (h if tdt & ops.HYB_H_BF16 else self._to_temporal(h), self.token_proj.weight, self.token_proj.bias, enc._flat_params(),
+                 self.head.weight, self.head.bias, mask)
+        back = (B, tdt, enc.hidden_dim, enc.num_layers, enc.num_heads, enc.attention_layers[0]._attn_p(), float(enc.dropout), ops.next_seed())
+        return ops.temporal_loss(front, family, loss_args, back)
 
     # ---- inference ------------------------------------------------------------------------------------------------------------------
     def _infer_fused(self):

@@ -41,7 +41,7 @@ fake kernel and an autograd kernel per operator.
 import ctypes
 import functools
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -628,149 +628,72 @@ def _ce_focal(focal, C, device):
     return (_ce_weight(focal[0], C, device), int(focal[1]), int(focal[2]), _ce_gamma("gamma", focal[3]))
 
 
-def _ce_name(stem, opts, mix, way):
-    return f"hyb_{stem}_mix_{way}" if mix else f"hyb_{stem}_opts_{way}" if opts else f"hyb_{stem}_{way}"
+def _ce_index(target, B):
+    """Class indices as the entry points of the index families read them: int64 [B], contiguous."""
+    if target.dim() != 1 or target.shape[0] != B:
+        raise ValueError(f"expected class indices [B={B}], got {tuple(target.shape)}")
+    return target.contiguous().to(torch.int64)
 
 
-def _cross_entropy_fwd(logits, target, opts, mix=()):
-    """opts (): hyb_cross_entropy_fwd; opts = (weight, ignore_index, has_ignore, label_smoothing): hyb_cross_entropy_opts_fwd, the same call
-    with the loss options behind the target; mix = (target_b, lam), with opts: hyb_cross_entropy_mix_fwd, the two in front of the options."""
-    _require_cuda(logits, target)
-    if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
-        raise ValueError(f"expected logits [B,C] and class indices [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
-    logits = logits.contiguous().float()
-    target = target.contiguous().to(torch.int64)
+class _LossFamily(NamedTuple):
+    """One row per way of describing the loss: the four operators hybrid::cross_entropy{sfx}[_bwd] and hybrid::temporal_ce{sfx}[_bwd] over the C
+    entry points hyb_cross_entropy{sfx}_{fwd,bwd} and hyb_temporal_ce{sfx}_{fwd,bwd} are built from it (_define_loss_family)."""
+    sfx: str            # operator suffix and C symbol stem
+    schema: str         # the loss arguments as the operator schemas spell them: the tensors first, `Tensor?` the optional ones
+    dense: bool         # the target is a dense fp32 [B, C], not class indices [B]
+    check: Callable     # (the schema's arguments, B, C, device) -> the same as the C entry points take them
+    n_args: int         # (from the schema, _loss_family) how many arguments it lists ...
+    n_tensors: int      # ... and how many of them, the leading ones, are tensors: saved for backward; the scalars behind are kept by value
+
+    def op(self, stem, way=""):
+        """torch.ops.hybrid.cross_entropy{sfx}{way} / temporal_ce{sfx}{way}"""
+        return getattr(torch.ops.hybrid, stem + self.sfx + way)
+
+
+def _loss_family(sfx, schema, dense, check):
+    types = [a.split()[0] for a in schema.split(", ")]
+    nt = sum(t in ("Tensor", "Tensor?") for t in types)
+    assert all(t in ("Tensor", "Tensor?") for t in types[:nt]) and all(t in ("int", "bool", "float") for t in types[nt:]), schema
+    return _LossFamily(sfx, schema, dense, check, len(types), nt)
+
+
+_OPTS_SCHEMA = "Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing"
+LOSS_FAMILIES = {
+    "plain": _loss_family("", "Tensor target", False, lambda a, B, C, dev: (_ce_index(a[0], B),)),
+    "opts": _loss_family("_opts", "Tensor target, " + _OPTS_SCHEMA, False, lambda a, B, C, dev: (_ce_index(a[0], B), *_ce_opts(a[1:], C, dev))),
+    "mix": _loss_family("_mix", "Tensor target, Tensor target_b, Tensor lam, " + _OPTS_SCHEMA, False,
+                        lambda a, B, C, dev: (_ce_index(a[0], B), *_ce_mix(a[1:3], B, dev), *_ce_opts(a[3:], C, dev))),
+    "dense": _loss_family("_dense", "Tensor target, Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing", True, _ce_dense),
+    "focal": _loss_family("_focal", "Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float gamma", False,
+                          lambda a, B, C, dev: (_ce_index(a[0], B), *_ce_focal(a[1:], C, dev))),
+    "asym": _loss_family("_asym", "Tensor target, Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, float clip", True, _ce_asym),
+}
+
+
+def _ce_logits(fam, logits, target):
+    if logits.dim() != 2 or not (fam.dense or (target.dim() == 1 and target.shape[0] == logits.shape[0])):
+        raise ValueError(f"expected logits [B,C], got {tuple(logits.shape)}" if fam.dense else
+                         f"expected logits [B,C] and class indices [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
+    return logits.contiguous().float()
+
+
+def _cross_entropy_fwd(fam, logits, args):
+    """hybrid::cross_entropy{sfx}: the mean loss of the family (include/hybrid_hip.h states each definition) -> loss []."""
+    _require_cuda(logits, args[0])
+    logits = _ce_logits(fam, logits, args[0])
     B, C = logits.shape
-    opts = _ce_opts(opts, C, logits.device)
-    mix = _ce_mix(mix, B, logits.device)
     loss = torch.empty((), dtype=torch.float32, device=logits.device)
-    lib.call(_ce_name("cross_entropy", opts, mix, "fwd"), logits, target, *mix, *opts, loss, B, C, _stream())
+    lib.call(f"hyb_cross_entropy{fam.sfx}_fwd", logits, *fam.check(args, B, C, logits.device), loss, B, C, _stream())
     return loss
 
 
-def _cross_entropy_bwd(dloss, logits, target, opts, mix=()):
-    _require_cuda(dloss, logits)
-    logits = logits.contiguous().float()
-    target = target.contiguous().to(torch.int64)
-    B, C = logits.shape
-    opts = _ce_opts(opts, C, logits.device)
-    mix = _ce_mix(mix, B, logits.device)
-    dl = dloss.contiguous().float().reshape(1)
-    dlogits = torch.empty_like(logits)
-    lib.call(_ce_name("cross_entropy", opts, mix, "bwd"), logits, target, *mix, *opts, dl, dlogits, B, C, _stream())
-    return dlogits
-
-
-def cross_entropy_op(logits: Tensor, target: Tensor) -> Tensor:
-    return _cross_entropy_fwd(logits, target, ())
-
-
-def cross_entropy_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor) -> Tensor:
-    return _cross_entropy_bwd(dloss, logits, target, ())
-
-
-def cross_entropy_opts_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
-                          label_smoothing: float) -> Tensor:
-    """Mean cross-entropy with class weights, label smoothing and an ignored class index (hyb_cross_entropy_opts_fwd): the sum of the kept
-    clips' terms over the sum of their target weights, torch.nn.functional.cross_entropy's "mean"."""
-    return _cross_entropy_fwd(logits, target, (weight, ignore_index, has_ignore, label_smoothing))
-
-
-def cross_entropy_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
-                              label_smoothing: float) -> Tensor:
-    return _cross_entropy_bwd(dloss, logits, target, (weight, ignore_index, has_ignore, label_smoothing))
-
-
-def cross_entropy_mix_op(logits: Tensor, target: Tensor, target_b: Tensor, lam: Tensor, weight: Optional[Tensor], ignore_index: int,
-                         has_ignore: bool, label_smoothing: float) -> Tensor:
-    """hybrid::cross_entropy_opts with two targets per clip (hyb_cross_entropy_mix_fwd): sum_b [lam_b term(b, target_b) + (1 - lam_b)
-    term(b, target_b_b)] over the same mix of the target weights -- the loss of a Mixup / CutMix batch."""
-    return _cross_entropy_fwd(logits, target, (weight, ignore_index, has_ignore, label_smoothing), (target_b, lam))
-
-
-def cross_entropy_mix_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, target_b: Tensor, lam: Tensor, weight: Optional[Tensor],
-                             ignore_index: int, has_ignore: bool, label_smoothing: float) -> Tensor:
-    return _cross_entropy_bwd(dloss, logits, target, (weight, ignore_index, has_ignore, label_smoothing), (target_b, lam))
-
-
-def cross_entropy_dense_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], kind: int,
-                           label_smoothing: float) -> Tensor:
-    """The mean loss on a dense fp32 target [B, C] (hyb_cross_entropy_dense_fwd).  kind 0: torch.nn.functional.cross_entropy with class
-    probabilities (weight, label_smoothing; the divisor is B); kind 1: binary_cross_entropy_with_logits (weight, pos_weight; the divisor is
-    B C)."""
-    _require_cuda(logits, target)
-    if logits.dim() != 2:
-        raise ValueError(f"expected logits [B,C], got {tuple(logits.shape)}")
-    logits = logits.contiguous().float()
-    B, C = logits.shape
-    dense = _ce_dense((target, weight, pos_weight, kind, label_smoothing), B, C, logits.device)
-    loss = torch.empty((), dtype=torch.float32, device=logits.device)
-    lib.call("hyb_cross_entropy_dense_fwd", logits, *dense, loss, B, C, _stream())
-    return loss
-
-
-def cross_entropy_dense_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], kind: int,
-                               label_smoothing: float) -> Tensor:
-    _require_cuda(dloss, logits, target)
-    logits = logits.contiguous().float()
-    B, C = logits.shape
-    dense = _ce_dense((target, weight, pos_weight, kind, label_smoothing), B, C, logits.device)
-    dl = dloss.contiguous().float().reshape(1)
-    dlogits = torch.empty_like(logits)
-    lib.call("hyb_cross_entropy_dense_bwd", logits, *dense, dl, dlogits, B, C, _stream())
-    return dlogits
-
-
-def _ce_index_checked(logits, target):
-    _require_cuda(logits, target)
-    if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
-        raise ValueError(f"expected logits [B,C] and class indices [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
-    return logits.contiguous().float(), target.contiguous().to(torch.int64)
-
-
-def cross_entropy_focal_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, gamma: float) -> Tensor:
-    """Mean focal loss on class indices (hyb_cross_entropy_focal_fwd): hybrid::cross_entropy_opts' terms, each times u ** gamma with u the
-    softmax mass of the other classes; the same den.  gamma == 0: cross_entropy_opts' bits."""
-    logits, target = _ce_index_checked(logits, target)
-    B, C = logits.shape
-    loss = torch.empty((), dtype=torch.float32, device=logits.device)
-    lib.call("hyb_cross_entropy_focal_fwd", logits, target, *_ce_focal((weight, ignore_index, has_ignore, gamma), C, logits.device), loss, B, C, _stream())
-    return loss
-
-
-def cross_entropy_focal_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
-                               gamma: float) -> Tensor:
-    _require_cuda(dloss)
-    logits, target = _ce_index_checked(logits, target)
+def _cross_entropy_bwd(fam, dloss, logits, args):
+    _require_cuda(dloss, logits, args[0])
+    logits = _ce_logits(fam, logits, args[0])
     B, C = logits.shape
     dlogits = torch.empty_like(logits)
-    lib.call("hyb_cross_entropy_focal_bwd", logits, target, *_ce_focal((weight, ignore_index, has_ignore, gamma), C, logits.device),
-             dloss.contiguous().float().reshape(1), dlogits, B, C, _stream())
-    return dlogits
-
-
-def cross_entropy_asym_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float, gamma_neg: float,
-                          clip: float) -> Tensor:
-    """Mean asymmetric loss on a dense fp32 target [B, C] (hyb_cross_entropy_asym_fwd); the divisor is B C."""
-    _require_cuda(logits, target)
-    if logits.dim() != 2:
-        raise ValueError(f"expected logits [B,C], got {tuple(logits.shape)}")
-    logits = logits.contiguous().float()
-    B, C = logits.shape
-    asym = _ce_asym((target, weight, pos_weight, gamma_pos, gamma_neg, clip), B, C, logits.device)
-    loss = torch.empty((), dtype=torch.float32, device=logits.device)
-    lib.call("hyb_cross_entropy_asym_fwd", logits, *asym, loss, B, C, _stream())
-    return loss
-
-
-def cross_entropy_asym_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float,
-                              gamma_neg: float, clip: float) -> Tensor:
-    _require_cuda(dloss, logits, target)
-    logits = logits.contiguous().float()
-    B, C = logits.shape
-    asym = _ce_asym((target, weight, pos_weight, gamma_pos, gamma_neg, clip), B, C, logits.device)
-    dlogits = torch.empty_like(logits)
-    lib.call("hyb_cross_entropy_asym_bwd", logits, *asym, dloss.contiguous().float().reshape(1), dlogits, B, C, _stream())
+    lib.call(f"hyb_cross_entropy{fam.sfx}_bwd", logits, *fam.check(args, B, C, logits.device), dloss.contiguous().float().reshape(1), dlogits, B, C,
+             _stream())
     return dlogits
 
 
@@ -782,39 +705,48 @@ def cross_entropy_bwd_fake(dloss, logits, target, *opts):
     return logits.new_empty(logits.shape, dtype=torch.float32)
 
 
+def ignore_args(ignore_index):
+    """ignore_index or None as the schemas carry it: (int ignore_index, bool has_ignore)"""
+    return (0 if ignore_index is None else int(ignore_index), ignore_index is not None)
+
+
+def cross_entropy_loss(logits, family, loss_args):
+    """The stand-alone loss of one LOSS_FAMILIES row, loss_args as its schema lists them (what a criterion's _loss_call returns)."""
+    return LOSS_FAMILIES[family].op("cross_entropy")(logits, *loss_args)
+
+
 def cross_entropy(logits, target):
     return torch.ops.hybrid.cross_entropy(logits, target)
 
 
 def cross_entropy_opts(logits, target, weight=None, ignore_index=None, label_smoothing=0.0):
-    return torch.ops.hybrid.cross_entropy_opts(logits, target, weight, 0 if ignore_index is None else int(ignore_index), ignore_index is not None,
-                                               float(label_smoothing))
+    """Mean cross-entropy with class weights, label smoothing and an ignored class index: the sum of the kept clips' terms over the sum of
+    their target weights, torch.nn.functional.cross_entropy's "mean"."""
+    return torch.ops.hybrid.cross_entropy_opts(logits, target, weight, *ignore_args(ignore_index), float(label_smoothing))
 
 
 def cross_entropy_mix(logits, target, target_b, lam, weight=None, ignore_index=None, label_smoothing=0.0):
     """The mean cross-entropy of a Mixup / CutMix batch: class indices target / target_b [B] and fp32 lam [B] (the weight of ``target``), all
     on the device; the options as in cross_entropy_opts.  No gradient for lam, the targets or the class weights."""
-    return torch.ops.hybrid.cross_entropy_mix(logits, target, target_b, lam, weight, 0 if ignore_index is None else int(ignore_index),
-                                              ignore_index is not None, float(label_smoothing))
+    return torch.ops.hybrid.cross_entropy_mix(logits, target, target_b, lam, weight, *ignore_args(ignore_index), float(label_smoothing))
 
 
 def cross_entropy_dense(logits, target, weight=None, pos_weight=None, kind=0, label_smoothing=0.0):
     """The mean loss on a dense target: a contiguous fp32 [B, C] on the logits' device.  kind 0: soft-target cross-entropy (rows are class
-    probabilities, used as given; class weights [C] and label smoothing as in torch.nn.functional.cross_entropy); kind 1: binary cross-entropy
-    with logits (weight and pos_weight [C]).  No gradient for the target or the weights."""
+    probabilities, used as given; class weights [C] and label smoothing as in torch.nn.functional.cross_entropy; the divisor is B); kind 1:
+    binary cross-entropy with logits (weight and pos_weight [C]; the divisor is B C).  No gradient for the target or the weights."""
     return torch.ops.hybrid.cross_entropy_dense(logits, target, weight, pos_weight, int(kind), float(label_smoothing))
 
 
 def cross_entropy_focal(logits, target, weight=None, ignore_index=None, gamma=2.0):
     """The mean focal loss on class indices [B]: cross_entropy_opts (class weights, an ignored index; no label smoothing) with every clip's
-    term times (1 - p_target) ** gamma.  gamma is 0 or >= 1.  No gradient for the class weights."""
-    return torch.ops.hybrid.cross_entropy_focal(logits, target, weight, 0 if ignore_index is None else int(ignore_index), ignore_index is not None,
-                                                _ce_gamma("gamma", gamma))
+    term times (1 - p_target) ** gamma; gamma == 0: cross_entropy_opts' bits.  gamma is 0 or >= 1.  No gradient for the class weights."""
+    return torch.ops.hybrid.cross_entropy_focal(logits, target, weight, *ignore_args(ignore_index), _ce_gamma("gamma", gamma))
 
 
 def cross_entropy_asym(logits, target, weight=None, pos_weight=None, gamma_pos=0.0, gamma_neg=4.0, clip=0.05):
-    """The mean asymmetric loss on a dense target: a contiguous fp32 [B, C] on the logits' device (include/hybrid_hip.h).  Each exponent is 0
-    or >= 1, clip in [0, 1).  No gradient for the target or the weights."""
+    """The mean asymmetric loss on a dense target: a contiguous fp32 [B, C] on the logits' device (include/hybrid_hip.h); the divisor is B C.
+    Each exponent is 0 or >= 1, clip in [0, 1).  No gradient for the target or the weights."""
     return torch.ops.hybrid.cross_entropy_asym(logits, target, weight, pos_weight, _ce_gamma("gamma_pos", gamma_pos),
                                                _ce_gamma("gamma_neg", gamma_neg), float(clip))
 
@@ -1399,16 +1331,10 @@ def prepare_ce_scratch(B, device, stream):
     return t
 
 
-def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, dense=(), focal=(),
-                  asym=()):
-    """The temporal part, one body for the three operators.  ce (): hyb_temporal_fwd; ce = (target,): hyb_temporal_ce_fwd, the loss in the
-    same launches; ce = (target, weight, ignore_index, has_ignore, label_smoothing): hyb_temporal_ce_opts_fwd, the same call with the loss
-    options behind the target; ce = (target, target_b, lam, weight, ...): hyb_temporal_ce_mix_fwd, the second target and lam in front of the
-    options.  dense = (target [B, classes] fp32, weight, pos_weight, kind, label_smoothing) with ce (): hyb_temporal_ce_dense_fwd.
-    focal = (target [B] int64, weight, ignore_index, has_ignore, gamma) with ce (): hyb_temporal_ce_focal_fwd; asym = (target [B, classes]
-    fp32, weight, pos_weight, gamma_pos, gamma_neg, clip) with ce (): hyb_temporal_ce_asym_fwd.
-    -> (logits, feat, enc_saved, enc_out), behind the loss [] when there is one."""
-    _require_cuda(h, token_w, head_w, *ce[:1], *dense[:1], *focal[:1], *asym[:1], *enc_params)
+def _temporal_fwd(loss, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
+    """The temporal part, one body for every forward operator.  loss None: hyb_temporal_fwd; loss = (family, the arguments its schema lists):
+    hyb_temporal_ce{sfx}_fwd, the loss in the same launches.  -> (logits, feat, enc_saved, enc_out), behind the loss [] when there is one."""
+    _require_cuda(h, token_w, head_w, *(loss[1][:1] if loss else ()), *enc_params)
     _check_h_dtype(h, dt)
     h = h.contiguous()
     N, Hh, Ww, Cp = h.shape
@@ -1417,51 +1343,37 @@ def _temporal_fwd(ce, h, token_w, token_b, enc_params, head_w, head_b, mask, B, 
     classes = head_w.shape[0]
     _check_attention_limits(S, D, H)
     dev, tdt = h.device, _TORCH_DTYPE[dt & 0xff]
-    for t in (*ce[:1], *focal[:1]):
-        if t.dim() != 1 or t.shape[0] != B:
-            raise ValueError(f"expected class indices [B={B}], got {tuple(t.shape)}")
+    name, loss_in, loss_out = "hyb_temporal_fwd", (), ()
+    if loss:
+        name = f"hyb_temporal_ce{loss[0].sfx}_fwd"
+        loss_in = loss[0].check(loss[1], B, classes, dev)
+        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
     feat = torch.empty(N, Cp, dtype=tdt, device=dev)
     tok = torch.empty(B, S, D, dtype=tdt, device=dev)
     enc_out = torch.empty(B, S, D, dtype=tdt, device=dev)
     saved = _ws(_query("hyb_encoder_saved_bytes", dt & 0xff, B, S, D, hid, L, H), dev)
     logits = torch.empty(B, classes, dtype=torch.float32, device=dev)
     ps = [p.contiguous() for p in enc_params]
-    name, loss_in, loss_out = "hyb_temporal_fwd", (), ()
-    if ce:
-        mix = ce[1:3] if len(ce) == 7 else ()
-        opts = ce[3:] if mix else ce[1:]
-        name = _ce_name("temporal_ce", opts, mix, "fwd")
-        loss_in = (ce[0].contiguous().to(torch.int64), *_ce_mix(mix, B, dev), *_ce_opts(opts, classes, dev))
-        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
-    elif dense:
-        name = "hyb_temporal_ce_dense_fwd"
-        loss_in = _ce_dense(dense, B, classes, dev)
-        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
-    elif focal:
-        name = "hyb_temporal_ce_focal_fwd"
-        loss_in = (focal[0].contiguous().to(torch.int64), *_ce_focal(focal[1:], classes, dev))
-        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
-    elif asym:
-        name = "hyb_temporal_ce_asym_fwd"
-        loss_in = _ce_asym(asym, B, classes, dev)
-        loss_out = (torch.empty((), dtype=torch.float32, device=dev), _ce_scratch(B, dev))
     lib.call(name, dt, h, token_w.contiguous(), token_b.contiguous(), ps, head_w.contiguous(), head_b.contiguous(), mask, *loss_in, feat, tok, saved,
              enc_out, logits, *loss_out, B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, _stream())
     return (*loss_out[:1], logits, feat, saved, enc_out)
 
 
-def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, dense=(),
-                  focal=(), asym=()):
-    """ce (): dout is dlogits, hyb_temporal_bwd; ce = (logits, target) + what follows the target in _temporal_fwd's ce, if anything: dout is
-    dloss, hyb_temporal_ce_bwd / hyb_temporal_ce_opts_bwd / hyb_temporal_ce_mix_bwd.  dense = (logits,) + _temporal_fwd's dense, with ce ():
-    dout is dloss, hyb_temporal_ce_dense_bwd; focal / asym = (logits,) + _temporal_fwd's, likewise.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
-    _require_cuda(dout, *ce[:1], feat)
+def _temporal_bwd(loss, dout, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None):
+    """loss None: dout is dlogits, hyb_temporal_bwd; loss = (family, logits, the arguments its schema lists): dout is dloss,
+    hyb_temporal_ce{sfx}_bwd.  -> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
+    _require_cuda(dout, *(loss[1:2] + loss[2][:1] if loss else ()), feat)
     B, S, D = enc_out.shape
     N, Cp = feat.shape
     C = token_w.shape[1]
     classes = head_w.shape[0]
     dev, tdt = feat.device, _TORCH_DTYPE[dt & 0xff]
     dout = dout.contiguous().float()
+    name, loss_in = "hyb_temporal_bwd", ()
+    if loss:
+        name = f"hyb_temporal_ce{loss[0].sfx}_bwd"
+        dout = dout.reshape(1)
+        loss_in = (loss[1].contiguous(), *loss[0].check(loss[2], B, classes, dev))
     ps = [p.contiguous() for p in enc_params]
     grads = [torch.empty_like(p) for p in ps]
     dh = torch.empty(N, Hh, Ww, Cp, dtype=torch.bfloat16 if dt & HYB_H_BF16 else tdt, device=dev)
@@ -1470,28 +1382,6 @@ def _temporal_bwd(ce, dout, token_w, enc_params, head_w, mask, feat, saved, enc_
     dhw = torch.empty_like(head_w, memory_format=torch.contiguous_format)
     dhb = torch.empty(classes, dtype=torch.float32, device=dev)
     ws = _ws(_query("hyb_temporal_bwd_workspace", dt & 0xff, B, S, Hh * Ww, Cp, D, hid, L, H), dev)
-    name, loss_in = "hyb_temporal_bwd", ()
-    if ce:
-        mix = ce[2:4] if len(ce) == 8 else ()
-        opts = ce[4:] if mix else ce[2:]
-        name = _ce_name("temporal_ce", opts, mix, "bwd")
-        dout = dout.reshape(1)
-        loss_in = (ce[0].contiguous(), ce[1].contiguous(), *_ce_mix(mix, B, dev), *_ce_opts(opts, classes, dev))
-    elif dense:
-        _require_cuda(dense[0])
-        name = "hyb_temporal_ce_dense_bwd"
-        dout = dout.reshape(1)
-        loss_in = (dense[0].contiguous(), *_ce_dense(dense[1:], B, classes, dev))
-    elif focal:
-        _require_cuda(focal[0], focal[1])
-        name = "hyb_temporal_ce_focal_bwd"
-        dout = dout.reshape(1)
-        loss_in = (focal[0].contiguous(), focal[1].contiguous().to(torch.int64), *_ce_focal(focal[2:], classes, dev))
-    elif asym:
-        _require_cuda(asym[0])
-        name = "hyb_temporal_ce_asym_bwd"
-        dout = dout.reshape(1)
-        loss_in = (asym[0].contiguous(), *_ce_asym(asym[1:], B, classes, dev))
     lib.call(name, dt, dout, *loss_in, token_w.contiguous(), ps, head_w.contiguous(), mask, feat, saved, enc_out, dtw, dtb, grads, dhw, dhb, dh,
              B, S, Hh * Ww, C, Cp, D, hid, L, H, classes, float(attn_p), float(layer_p), seed, seed_inc, ws, ws.numel(), _stream())
     return [dh, dtw, dtb, dhw, dhb] + grads
@@ -1501,123 +1391,18 @@ def temporal_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequenc
                 B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
                 seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """h [B*S, Hh, Ww, Cp] T (last pooled map) -> (logits [B, classes] fp32, feat, enc_saved, enc_out); the last three are saved for backward."""
-    return _temporal_fwd((), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def temporal_ce_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor, mask: Optional[Tensor],
-                   target: Tensor, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                   seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """hybrid::temporal + hybrid::cross_entropy in the same launches (hyb_temporal_ce_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
-    return _temporal_fwd((target,), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def temporal_ce_opts_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
-                        mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
-                        B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                        seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """hybrid::temporal + hybrid::cross_entropy_opts in the same launches (hyb_temporal_ce_opts_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
-    return _temporal_fwd((target, weight, ignore_index, has_ignore, label_smoothing), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt,
-                         hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def temporal_ce_mix_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
-                       mask: Optional[Tensor], target: Tensor, target_b: Tensor, lam: Tensor, weight: Optional[Tensor], ignore_index: int,
-                       has_ignore: bool, label_smoothing: float, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                       seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """hybrid::temporal + hybrid::cross_entropy_mix in the same launches (hyb_temporal_ce_mix_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
-    return _temporal_fwd((target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing), h, token_w, token_b, enc_params, head_w, head_b,
-                         mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def temporal_ce_dense_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
-                         mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], kind: int,
-                         label_smoothing: float, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                         seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """hybrid::temporal + hybrid::cross_entropy_dense in the same launches (hyb_temporal_ce_dense_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
-    return _temporal_fwd((), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
-                         dense=(target, weight, pos_weight, kind, label_smoothing))
-
-
-def temporal_ce_focal_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
-                         mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, gamma: float,
-                         B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                         seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """hybrid::temporal + hybrid::cross_entropy_focal in the same launches (hyb_temporal_ce_focal_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
-    return _temporal_fwd((), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
-                         focal=(target, weight, ignore_index, has_ignore, gamma))
-
-
-def temporal_ce_asym_op(h: Tensor, token_w: Tensor, token_b: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, head_b: Tensor,
-                        mask: Optional[Tensor], target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float,
-                        gamma_neg: float, clip: float, B: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float, seed: int,
-                        seed_inc: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """hybrid::temporal + hybrid::cross_entropy_asym in the same launches (hyb_temporal_ce_asym_fwd): -> (loss [], logits, feat, enc_saved, enc_out)."""
-    return _temporal_fwd((), h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
-                         asym=(target, weight, pos_weight, gamma_pos, gamma_neg, clip))
+    return _temporal_fwd(None, h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
 
 
 def temporal_bwd_op(dlogits: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
                     saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
                     seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
     """-> [dh, dtoken_w, dtoken_b, dhead_w, dhead_b, denc_param_0, ...]"""
-    return _temporal_bwd((), dlogits, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def temporal_ce_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor,
-                       mask: Optional[Tensor], feat: Tensor, saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int,
-                       attn_p: float, layer_p: float, seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """hybrid::cross_entropy_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
-    return _temporal_bwd((logits, target), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p,
-                         seed, seed_inc)
-
-
-def temporal_ce_opts_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
-                            label_smoothing: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
-                            saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
-                            seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """hybrid::cross_entropy_opts_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
-    return _temporal_bwd((logits, target, weight, ignore_index, has_ignore, label_smoothing), dloss, token_w, enc_params, head_w, mask, feat, saved,
-                         enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def temporal_ce_mix_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, target_b: Tensor, lam: Tensor, weight: Optional[Tensor],
-                           ignore_index: int, has_ignore: bool, label_smoothing: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor,
-                           mask: Optional[Tensor], feat: Tensor, saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int,
-                           attn_p: float, layer_p: float, seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """hybrid::cross_entropy_mix_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
-    return _temporal_bwd((logits, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing), dloss, token_w, enc_params, head_w, mask,
-                         feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-
-
-def temporal_ce_dense_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], kind: int,
-                             label_smoothing: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
-                             saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
-                             seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """hybrid::cross_entropy_dense_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
-    return _temporal_bwd((), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
-                         dense=(logits, target, weight, pos_weight, kind, label_smoothing))
-
-
-def temporal_ce_focal_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool,
-                             gamma: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor], feat: Tensor,
-                             saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float, layer_p: float,
-                             seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """hybrid::cross_entropy_focal_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
-    return _temporal_bwd((), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
-                         focal=(logits, target, weight, ignore_index, has_ignore, gamma))
-
-
-def temporal_ce_asym_bwd_op(dloss: Tensor, logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float,
-                            gamma_neg: float, clip: float, token_w: Tensor, enc_params: Sequence[Tensor], head_w: Tensor, mask: Optional[Tensor],
-                            feat: Tensor, saved: Tensor, enc_out: Tensor, Hh: int, Ww: int, dt: int, hid: int, L: int, H: int, attn_p: float,
-                            layer_p: float, seed: int, seed_inc: Optional[Tensor] = None) -> List[Tensor]:
-    """hybrid::cross_entropy_asym_bwd + hybrid::temporal_bwd in the same launches: same outputs."""
-    return _temporal_bwd((), dloss, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc,
-                         asym=(logits, target, weight, pos_weight, gamma_pos, gamma_neg, clip))
+    return _temporal_bwd(None, dlogits, token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
 
 
 def _temporal_fake(n_loss, h, token_w, token_b, enc_params, head_w, head_b, mask, *rest, seed_inc=None):
-    """Fake of the four forward operators: rest = the n_loss loss arguments of the schema (0, 1, 5 or 7), then B, dt, hid, L, H, ..."""
+    """Fake of the forward operators: rest = the n_loss loss arguments of the schema, then B, dt, hid, L, H, ..."""
     B, dt, hid, L, H = rest[n_loss:n_loss + 5]
     N, Hh, Ww, Cp = h.shape
     S, D = N // B, token_w.shape[0]
@@ -1628,7 +1413,7 @@ def _temporal_fake(n_loss, h, token_w, token_b, enc_params, head_w, head_b, mask
 
 
 def _temporal_bwd_fake(n_loss, dout, *rest, seed_inc=None):
-    """Fake of the four backward operators: rest = the n_loss loss arguments of the schema (0, 2, 6 or 8), then token_w, enc_params, ..."""
+    """Fake of the backward operators: rest = the n_loss loss arguments of the schema (the logits and the forward's), then token_w, enc_params, ..."""
     token_w, enc_params, head_w, mask, feat, saved, enc_out, Hh, Ww, dt = rest[n_loss:n_loss + 10]
     N, Cp = feat.shape
     c = lambda t: torch.empty_like(t, memory_format=torch.contiguous_format)
@@ -1636,67 +1421,57 @@ def _temporal_bwd_fake(n_loss, dout, *rest, seed_inc=None):
             feat.new_empty((token_w.shape[0],), dtype=torch.float32), c(head_w), feat.new_empty((head_w.shape[0],), dtype=torch.float32)] + [c(p) for p in enc_params]
 
 
-def temporal_ce(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed):
-    """-> (loss, logits): the temporal part and the mean cross-entropy loss as one operator (the loss rides in the temporal part's last launch,
-    its backward in the backward's first)."""
-    S = h.shape[0] // B
-    r = torch.ops.hybrid.temporal_ce(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, B, dt, hid, L, H,
-                                     float(attn_p), float(layer_p), seed, step_counter())
+def temporal_loss(front, family, loss_args, back):
+    """-> (loss, logits): the temporal part and the loss of one LOSS_FAMILIES row as one operator (the loss rides in the temporal part's last
+    launch, its backward in the backward's first; what the loss reads on the device -- targets, lam, weight, pos_weight -- is read when the
+    kernels run).  front = (h, token_w, token_b, enc_params, head_w, head_b, mask), loss_args as the row's schema lists them, back = (B, dt,
+    hid, L, H, attn_p, layer_p, seed)."""
+    h, token_w, token_b, enc_params, head_w, head_b, mask = front
+    B, dt, hid, L, H, attn_p, layer_p, seed = back
+    r = LOSS_FAMILIES[family].op("temporal_ce")(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, h.shape[0] // B, h.device),
+                                                *loss_args, B, dt, hid, L, H, float(attn_p), float(layer_p), seed, step_counter())
     return r[0], r[1]
+
+
+def temporal_ce(h, token_w, token_b, enc_params, head_w, head_b, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed):
+    """-> (loss, logits): the temporal part and the mean cross-entropy loss as one operator."""
+    return temporal_loss((h, token_w, token_b, enc_params, head_w, head_b, mask), "plain", (target,), (B, dt, hid, L, H, attn_p, layer_p, seed))
 
 
 def temporal_ce_opts(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, label_smoothing, B, dt, hid, L, H, attn_p,
                      layer_p, seed):
-    """-> (loss, logits): temporal_ce with class weights [classes] (or None), an ignored class index (or None) and label smoothing: the same
-    launches, the options ride in them."""
-    S = h.shape[0] // B
-    r = torch.ops.hybrid.temporal_ce_opts(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
-                                          0 if ignore_index is None else int(ignore_index), ignore_index is not None, float(label_smoothing), B, dt, hid,
-                                          L, H, float(attn_p), float(layer_p), seed, step_counter())
-    return r[0], r[1]
+    """-> (loss, logits): temporal_ce with class weights [classes] (or None), an ignored class index (or None) and label smoothing."""
+    return temporal_loss((h, token_w, token_b, enc_params, head_w, head_b, mask), "opts", (target, weight, *ignore_args(ignore_index), float(label_smoothing)),
+                         (B, dt, hid, L, H, attn_p, layer_p, seed))
 
 
 def temporal_ce_mix(h, token_w, token_b, enc_params, head_w, head_b, mask, target, target_b, lam, weight, ignore_index, label_smoothing, B, dt, hid,
                     L, H, attn_p, layer_p, seed):
-    """-> (loss, logits): temporal_ce_opts with two targets per clip and their mixing weight lam [B] (cross_entropy_mix): the same launches; the
-    targets and lam are read on the device when the kernels run."""
-    S = h.shape[0] // B
-    r = torch.ops.hybrid.temporal_ce_mix(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, target_b, lam,
-                                         weight, 0 if ignore_index is None else int(ignore_index), ignore_index is not None, float(label_smoothing), B,
-                                         dt, hid, L, H, float(attn_p), float(layer_p), seed, step_counter())
-    return r[0], r[1]
+    """-> (loss, logits): temporal_ce_opts with two targets per clip and their mixing weight lam [B] (cross_entropy_mix)."""
+    return temporal_loss((h, token_w, token_b, enc_params, head_w, head_b, mask), "mix",
+                         (target, target_b, lam, weight, *ignore_args(ignore_index), float(label_smoothing)), (B, dt, hid, L, H, attn_p, layer_p, seed))
 
 
 def temporal_ce_dense(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, pos_weight, kind, label_smoothing, B, dt, hid, L, H,
                       attn_p, layer_p, seed):
-    """-> (loss, logits): the temporal part and the loss on a dense fp32 target [B, classes] (cross_entropy_dense) as one operator: the same
-    launches; the target, weight and pos_weight are read on the device when the kernels run."""
-    S = h.shape[0] // B
-    r = torch.ops.hybrid.temporal_ce_dense(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
-                                           pos_weight, int(kind), float(label_smoothing), B, dt, hid, L, H, float(attn_p), float(layer_p), seed,
-                                           step_counter())
-    return r[0], r[1]
+    """-> (loss, logits): the temporal part and the loss on a dense fp32 target [B, classes] (cross_entropy_dense) as one operator."""
+    return temporal_loss((h, token_w, token_b, enc_params, head_w, head_b, mask), "dense", (target, weight, pos_weight, int(kind), float(label_smoothing)),
+                         (B, dt, hid, L, H, attn_p, layer_p, seed))
 
 
 def temporal_ce_focal(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, gamma, B, dt, hid, L, H, attn_p, layer_p,
                       seed):
-    """-> (loss, logits): the temporal part and the focal loss on class indices (cross_entropy_focal) as one operator: the same launches."""
-    S = h.shape[0] // B
-    r = torch.ops.hybrid.temporal_ce_focal(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
-                                           0 if ignore_index is None else int(ignore_index), ignore_index is not None, _ce_gamma("gamma", gamma), B,
-                                           dt, hid, L, H, float(attn_p), float(layer_p), seed, step_counter())
-    return r[0], r[1]
+    """-> (loss, logits): the temporal part and the focal loss on class indices (cross_entropy_focal) as one operator."""
+    return temporal_loss((h, token_w, token_b, enc_params, head_w, head_b, mask), "focal",
+                         (target, weight, *ignore_args(ignore_index), _ce_gamma("gamma", gamma)), (B, dt, hid, L, H, attn_p, layer_p, seed))
 
 
 def temporal_ce_asym(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, pos_weight, gamma_pos, gamma_neg, clip, B, dt, hid, L, H,
                      attn_p, layer_p, seed):
-    """-> (loss, logits): the temporal part and the asymmetric loss on a dense fp32 target [B, classes] (cross_entropy_asym) as one operator:
-    the same launches; the target, weight and pos_weight are read on the device when the kernels run."""
-    S = h.shape[0] // B
-    r = torch.ops.hybrid.temporal_ce_asym(h, token_w, token_b, list(enc_params), head_w, head_b, check_mask(mask, B, S, h.device), target, weight,
-                                          pos_weight, _ce_gamma("gamma_pos", gamma_pos), _ce_gamma("gamma_neg", gamma_neg), float(clip), B, dt, hid,
-                                          L, H, float(attn_p), float(layer_p), seed, step_counter())
-    return r[0], r[1]
+    """-> (loss, logits): the temporal part and the asymmetric loss on a dense fp32 target [B, classes] (cross_entropy_asym) as one operator."""
+    return temporal_loss((h, token_w, token_b, enc_params, head_w, head_b, mask), "asym",
+                         (target, weight, pos_weight, _ce_gamma("gamma_pos", gamma_pos), _ce_gamma("gamma_neg", gamma_neg), float(clip)),
+                         (B, dt, hid, L, H, attn_p, layer_p, seed))
 
 
 def temporal(h, token_w, token_b, enc_params, head_w, head_b, mask, B, dt, hid, L, H, attn_p, layer_p, seed):
@@ -1855,83 +1630,20 @@ class _HeadFn(torch.autograd.Function):
 
 
 class _CrossEntropyFn(torch.autograd.Function):
-    """hybrid::cross_entropy (has_ignore None: no loss options), hybrid::cross_entropy_opts and (target_b, lam given) hybrid::cross_entropy_mix."""
+    """hybrid::cross_entropy{sfx} of any _LossFamily: the family's tensors are saved, its scalars kept in ctx.cfg; no gradient for any of them."""
 
     @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, has_ignore, label_smoothing, target_b=None, lam=None):
+    def forward(ctx, fam, logits, *args):
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(logits, target, weight, target_b, lam)
-        ctx.cfg = None if has_ignore is None else (ignore_index, has_ignore, label_smoothing)
+        ctx.save_for_backward(logits, *args[:fam.n_tensors])
+        ctx.cfg = (fam, args[fam.n_tensors:])
         with _below_autograd():
-            if ctx.cfg is None:
-                return torch.ops.hybrid.cross_entropy(logits, target)
-            if target_b is not None:
-                return torch.ops.hybrid.cross_entropy_mix(logits, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing)
-            return torch.ops.hybrid.cross_entropy_opts(logits, target, weight, ignore_index, has_ignore, label_smoothing)
+            return fam.op("cross_entropy")(logits, *args)
 
     @staticmethod
     def backward(ctx, dloss):
-        logits, target, weight, target_b, lam = ctx.saved_tensors
-        if ctx.cfg is None:
-            dlogits = torch.ops.hybrid.cross_entropy_bwd(dloss, logits, target)
-        elif target_b is not None:
-            dlogits = torch.ops.hybrid.cross_entropy_mix_bwd(dloss, logits, target, target_b, lam, weight, *ctx.cfg)
-            return (dlogits,) + (None,) * 7    # (no gradient for lam, the second target or the class weights)
-        else:
-            dlogits = torch.ops.hybrid.cross_entropy_opts_bwd(dloss, logits, target, weight, *ctx.cfg)
-        return (dlogits,) + (None,) * 5        # (no gradient for the class weights)
-
-
-class _CrossEntropyDenseFn(torch.autograd.Function):
-    """hybrid::cross_entropy_dense."""
-
-    @staticmethod
-    def forward(ctx, logits, target, weight, pos_weight, kind, label_smoothing):
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(logits, target, weight, pos_weight)
-        ctx.cfg = (kind, label_smoothing)
-        with _below_autograd():
-            return torch.ops.hybrid.cross_entropy_dense(logits, target, weight, pos_weight, kind, label_smoothing)
-
-    @staticmethod
-    def backward(ctx, dloss):
-        logits, target, weight, pos_weight = ctx.saved_tensors
-        dlogits = torch.ops.hybrid.cross_entropy_dense_bwd(dloss, logits, target, weight, pos_weight, *ctx.cfg)
-        return (dlogits,) + (None,) * 5        # (no gradient for the target or the weights)
-
-
-class _CrossEntropyFocalFn(torch.autograd.Function):
-    """hybrid::cross_entropy_focal."""
-
-    @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, has_ignore, gamma):
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(logits, target, weight)
-        ctx.cfg = (ignore_index, has_ignore, gamma)
-        with _below_autograd():
-            return torch.ops.hybrid.cross_entropy_focal(logits, target, weight, ignore_index, has_ignore, gamma)
-
-    @staticmethod
-    def backward(ctx, dloss):
-        logits, target, weight = ctx.saved_tensors
-        return (torch.ops.hybrid.cross_entropy_focal_bwd(dloss, logits, target, weight, *ctx.cfg),) + (None,) * 5
-
-
-class _CrossEntropyAsymFn(torch.autograd.Function):
-    """hybrid::cross_entropy_asym."""
-
-    @staticmethod
-    def forward(ctx, logits, target, weight, pos_weight, gamma_pos, gamma_neg, clip):
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(logits, target, weight, pos_weight)
-        ctx.cfg = (gamma_pos, gamma_neg, clip)
-        with _below_autograd():
-            return torch.ops.hybrid.cross_entropy_asym(logits, target, weight, pos_weight, gamma_pos, gamma_neg, clip)
-
-    @staticmethod
-    def backward(ctx, dloss):
-        logits, target, weight, pos_weight = ctx.saved_tensors
-        return (torch.ops.hybrid.cross_entropy_asym_bwd(dloss, logits, target, weight, pos_weight, *ctx.cfg),) + (None,) * 6
+        fam, scalars = ctx.cfg
+        return (None, fam.op("cross_entropy", "_bwd")(dloss, *ctx.saved_tensors, *scalars)) + (None,) * fam.n_args
 
 
 class _BackboneFn(torch.autograd.Function):
@@ -1966,122 +1678,32 @@ class _BackboneFn(torch.autograd.Function):
 
 
 class _TemporalFn(torch.autograd.Function):
-    """hybrid::temporal (target None), hybrid::temporal_ce (has_ignore None: no loss options), hybrid::temporal_ce_opts and (target_b and lam
-    given) hybrid::temporal_ce_mix."""
+    """hybrid::temporal (fam None) and hybrid::temporal_ce{sfx} of any _LossFamily.  rest = the family's loss arguments, then (B, dt, hid, L, H,
+    attn_p, layer_p, seed, seed_inc), then the encoder's parameters."""
 
     @staticmethod
-    def forward(ctx, h, token_w, token_b, head_w, head_b, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
-                layer_p, seed, seed_inc, target_b, lam, *enc_params):
+    def forward(ctx, fam, h, token_w, token_b, head_w, head_b, mask, *rest):
         ctx.set_materialize_grads(False)
-        tail = (B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
+        n, nt = (fam.n_args, fam.n_tensors) if fam else (0, 0)
+        loss_args, tail, enc_params = rest[:n], rest[n:n + 9], rest[n + 9:]
         with _below_autograd():
-            if target is None:
-                out = torch.ops.hybrid.temporal(h, token_w, token_b, enc_params, head_w, head_b, mask, *tail)
-            elif has_ignore is None:
-                out = torch.ops.hybrid.temporal_ce(h, token_w, token_b, enc_params, head_w, head_b, mask, target, *tail)
-            elif target_b is not None:
-                out = torch.ops.hybrid.temporal_ce_mix(h, token_w, token_b, enc_params, head_w, head_b, mask, target, target_b, lam, weight, ignore_index,
-                                                       has_ignore, label_smoothing, *tail)
-            else:
-                out = torch.ops.hybrid.temporal_ce_opts(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, ignore_index, has_ignore,
-                                                        label_smoothing, *tail)
+            op = fam.op("temporal_ce") if fam else torch.ops.hybrid.temporal
+            out = op(h, token_w, token_b, enc_params, head_w, head_b, mask, *loss_args, *tail)
         feat, saved, enc_out = out[-3:]
-        ctx.seed_inc = seed_inc
-        opt = [t for t in (None if target is None else out[1], target, target_b, lam, weight, mask) if t is not None]      # (out[1]: the logits behind the loss)
-        ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, *opt, *enc_params)
-        ctx.cfg = (target is not None, target_b is not None, weight is not None, mask is not None, None if has_ignore is None else (ignore_index, has_ignore, label_smoothing),
-                   h.shape[1], h.shape[2], dt, hid, L, H, attn_p, layer_p, seed)
+        ctx.seed_inc = tail[8]                      # an int64 counter, not part of the autograd graph
+        ctx.save_for_backward(token_w, head_w, mask, feat, saved, enc_out, *out[1:2 if fam else 1], *loss_args[:nt], *enc_params)      # (out[1]: the logits behind the loss)
+        ctx.cfg = (fam, n, nt, loss_args[nt:], h.shape[1], h.shape[2], *tail[1:8])
         ctx.mark_non_differentiable(*out[1:])          # (with a loss, logits too: an output for the caller's metrics; the objective is the loss)
         return tuple(out)
 
     @staticmethod
     def backward(ctx, dout, *unused):
-        has_target, has_mix, has_weight, has_mask, opts, *tail = ctx.cfg
-        token_w, head_w, feat, saved, enc_out, *rest = ctx.saved_tensors
-        logits = rest.pop(0) if has_target else None
-        target = rest.pop(0) if has_target else None
-        mix = (rest.pop(0), rest.pop(0)) if has_mix else None
-        weight = rest.pop(0) if has_weight else None
-        mask = rest.pop(0) if has_mask else None
-        tail = (token_w, rest, head_w, mask, feat, saved, enc_out, *tail, ctx.seed_inc)
-        if not has_target:
-            g = torch.ops.hybrid.temporal_bwd(dout, *tail)
-        elif opts is None:
-            g = torch.ops.hybrid.temporal_ce_bwd(dout, logits, target, *tail)
-        elif has_mix:
-            g = torch.ops.hybrid.temporal_ce_mix_bwd(dout, logits, target, *mix, weight, *opts, *tail)
-        else:
-            g = torch.ops.hybrid.temporal_ce_opts_bwd(dout, logits, target, weight, *opts, *tail)
-        return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 17 + tuple(g[5:])
-
-
-class _TemporalDenseFn(torch.autograd.Function):
-    """hybrid::temporal_ce_dense."""
-
-    @staticmethod
-    def forward(ctx, h, token_w, token_b, head_w, head_b, mask, target, weight, pos_weight, kind, label_smoothing, B, dt, hid, L, H, attn_p, layer_p,
-                seed, seed_inc, *enc_params):
-        ctx.set_materialize_grads(False)
-        with _below_autograd():
-            out = torch.ops.hybrid.temporal_ce_dense(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, pos_weight, kind,
-                                                     label_smoothing, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-        feat, saved, enc_out = out[-3:]
-        ctx.seed_inc = seed_inc
-        opt = [t for t in (weight, pos_weight, mask) if t is not None]
-        ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, out[1], target, *opt, *enc_params)
-        ctx.cfg = (weight is not None, pos_weight is not None, mask is not None, kind, label_smoothing, h.shape[1], h.shape[2], dt, hid, L, H, attn_p,
-                   layer_p, seed)
-        ctx.mark_non_differentiable(*out[1:])
-        return tuple(out)
-
-    @staticmethod
-    def backward(ctx, dout, *unused):
-        has_weight, has_pw, has_mask, kind, label_smoothing, *tail = ctx.cfg
-        token_w, head_w, feat, saved, enc_out, logits, target, *rest = ctx.saved_tensors
-        weight = rest.pop(0) if has_weight else None
-        pos_weight = rest.pop(0) if has_pw else None
-        mask = rest.pop(0) if has_mask else None
-        g = torch.ops.hybrid.temporal_ce_dense_bwd(dout, logits, target, weight, pos_weight, kind, label_smoothing, token_w, rest, head_w, mask, feat,
-                                                   saved, enc_out, *tail, ctx.seed_inc)
-        return (g[0], g[1], g[2], g[3], g[4]) + (None,) * 15 + tuple(g[5:])
-
-
-class _TemporalFocalFn(torch.autograd.Function):
-    """hybrid::temporal_ce_focal (pos_weight is None, scalars = (ignore_index, has_ignore, gamma)) and hybrid::temporal_ce_asym (scalars =
-    (gamma_pos, gamma_neg, clip)): the loss arguments are (target, weight[, pos_weight], three scalars) either way."""
-
-    @staticmethod
-    def forward(ctx, asym, h, token_w, token_b, head_w, head_b, mask, target, weight, pos_weight, s0, s1, s2, B, dt, hid, L, H, attn_p, layer_p, seed,
-                seed_inc, *enc_params):
-        ctx.set_materialize_grads(False)
-        tail = (B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc)
-        with _below_autograd():
-            if asym:
-                out = torch.ops.hybrid.temporal_ce_asym(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, pos_weight, s0, s1, s2, *tail)
-            else:
-                out = torch.ops.hybrid.temporal_ce_focal(h, token_w, token_b, enc_params, head_w, head_b, mask, target, weight, s0, s1, s2, *tail)
-        feat, saved, enc_out = out[-3:]
-        ctx.seed_inc = seed_inc
-        opt = [t for t in (weight, pos_weight, mask) if t is not None]
-        ctx.save_for_backward(token_w, head_w, feat, saved, enc_out, out[1], target, *opt, *enc_params)
-        ctx.cfg = (asym, weight is not None, pos_weight is not None, mask is not None, (s0, s1, s2), h.shape[1], h.shape[2], dt, hid, L, H, attn_p,
-                   layer_p, seed)
-        ctx.mark_non_differentiable(*out[1:])
-        return tuple(out)
-
-    @staticmethod
-    def backward(ctx, dout, *unused):
-        asym, has_weight, has_pw, has_mask, scalars, *tail = ctx.cfg
-        token_w, head_w, feat, saved, enc_out, logits, target, *rest = ctx.saved_tensors
-        weight = rest.pop(0) if has_weight else None
-        pos_weight = rest.pop(0) if has_pw else None
-        mask = rest.pop(0) if has_mask else None
-        tail = (token_w, rest, head_w, mask, feat, saved, enc_out, *tail, ctx.seed_inc)
-        if asym:
-            g = torch.ops.hybrid.temporal_ce_asym_bwd(dout, logits, target, weight, pos_weight, *scalars, *tail)
-        else:
-            g = torch.ops.hybrid.temporal_ce_focal_bwd(dout, logits, target, weight, *scalars, *tail)
-        return (None, g[0], g[1], g[2], g[3], g[4]) + (None,) * 16 + tuple(g[5:])
+        fam, n, nt, scalars, *tail = ctx.cfg
+        token_w, head_w, mask, feat, saved, enc_out, *rest = ctx.saved_tensors
+        k = 1 + nt if fam else 0                       # the logits and the family's tensors, in front of the encoder's parameters
+        op = fam.op("temporal_ce", "_bwd") if fam else torch.ops.hybrid.temporal_bwd
+        g = op(dout, *rest[:k], *scalars, token_w, rest[k:], head_w, mask, feat, saved, enc_out, *tail, ctx.seed_inc)
+        return (None, g[0], g[1], g[2], g[3], g[4], None) + (None,) * (n + 9) + tuple(g[5:])
 
 
 _define("nchw_to_nhwc", "(Tensor x, int dt, int cp) -> Tensor", nchw_to_nhwc_op, nchw_to_nhwc_fake, _NchwToNhwcFn.apply)
@@ -2107,31 +1729,6 @@ _define("mha_bwd", "(Tensor dout, Tensor q_in, Tensor k_in, Tensor v_in, Tensor?
         "int dt, int H, float p_drop, int seed) -> Tensor[]", mha_bwd_op, mha_bwd_fake)
 _define("head", "(Tensor x, Tensor weight, Tensor? bias, int dt) -> Tensor", head_op, head_fake, _HeadFn.apply)
 _define("head_bwd", "(Tensor dlogits, Tensor x, Tensor weight, bool has_bias, int dt) -> (Tensor, Tensor, Tensor)", head_bwd_op, head_bwd_fake)
-_define("cross_entropy", "(Tensor logits, Tensor target) -> Tensor", cross_entropy_op, cross_entropy_fake,
-        lambda logits, target: _CrossEntropyFn.apply(logits, target, None, None, None, None))
-_define("cross_entropy_bwd", "(Tensor dloss, Tensor logits, Tensor target) -> Tensor", cross_entropy_bwd_op, cross_entropy_bwd_fake)
-_define("cross_entropy_opts", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing) -> Tensor",
-        cross_entropy_opts_op, cross_entropy_fake, _CrossEntropyFn.apply)
-_define("cross_entropy_opts_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, "
-        "float label_smoothing) -> Tensor", cross_entropy_opts_bwd_op, cross_entropy_bwd_fake)
-_define("cross_entropy_mix", "(Tensor logits, Tensor target, Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, bool has_ignore, "
-        "float label_smoothing) -> Tensor", cross_entropy_mix_op, cross_entropy_fake,
-        lambda logits, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing: _CrossEntropyFn.apply(
-            logits, target, weight, ignore_index, has_ignore, label_smoothing, target_b, lam))
-_define("cross_entropy_mix_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, "
-        "bool has_ignore, float label_smoothing) -> Tensor", cross_entropy_mix_bwd_op, cross_entropy_bwd_fake)
-_define("cross_entropy_dense", "(Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing) -> Tensor",
-        cross_entropy_dense_op, cross_entropy_fake, _CrossEntropyDenseFn.apply)
-_define("cross_entropy_dense_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing) "
-        "-> Tensor", cross_entropy_dense_bwd_op, cross_entropy_bwd_fake)
-_define("cross_entropy_focal", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float gamma) -> Tensor",
-        cross_entropy_focal_op, cross_entropy_fake, _CrossEntropyFocalFn.apply)
-_define("cross_entropy_focal_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float gamma) "
-        "-> Tensor", cross_entropy_focal_bwd_op, cross_entropy_bwd_fake)
-_define("cross_entropy_asym", "(Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, float clip) "
-        "-> Tensor", cross_entropy_asym_op, cross_entropy_fake, _CrossEntropyAsymFn.apply)
-_define("cross_entropy_asym_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, "
-        "float clip) -> Tensor", cross_entropy_asym_bwd_op, cross_entropy_bwd_fake)
 _define("eval_metrics_", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int topk, int views, "
         "Tensor(a!) sums, Tensor(b!) counts, Tensor(c!)? confusion) -> (Tensor, Tensor)", eval_metrics_op, eval_metrics_fake)
 _LIB.impl("eval_metrics_", _inference_only("eval_metrics_"), "Autograd")
@@ -2171,74 +1768,47 @@ _define("clip_transform_aa", "(Tensor src, Tensor params, Tensor? mean_invstd, i
 _LIB.impl("clip_transform_aa", _inference_only("clip_transform_aa"), "Autograd")
 _define("clip_luma_sums", "(Tensor src, Tensor params, int Tout) -> Tensor", clip_luma_sums_op, clip_luma_sums_fake)
 _LIB.impl("clip_luma_sums", _inference_only("clip_luma_sums"), "Autograd")
-_define("temporal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, int B, int dt, "
-        "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor)", temporal_op,
-        functools.partial(_temporal_fake, 0),
-        lambda h, tw, tb, ps, hw, hb, mask, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None: _TemporalFn.apply(
-            h, tw, tb, hw, hb, mask, None, None, None, None, None, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, None, None, *ps))
-_define("temporal_bwd", "(Tensor dlogits, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, "
-        "Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]",
-        temporal_bwd_op, functools.partial(_temporal_bwd_fake, 0))
-_define("temporal_ce", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, int B, "
-        "int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
-        temporal_ce_op, functools.partial(_temporal_fake, 1),
-        lambda h, tw, tb, ps, hw, hb, mask, target, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc=None: _TemporalFn.apply(
-            h, tw, tb, hw, hb, mask, target, None, None, None, None, B, dt, hid, L, H, attn_p, layer_p, seed, seed_inc, None, None, *ps))
-_define("temporal_ce_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, "
-        "Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) "
-        "-> Tensor[]", temporal_ce_bwd_op, functools.partial(_temporal_bwd_fake, 2))
-_define("temporal_ce_opts", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
-        "Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int B, int dt, int hid, int L, int H, float attn_p, float layer_p, "
-        "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_opts_op, functools.partial(_temporal_fake, 5),
-        lambda h, tw, tb, ps, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p, layer_p, seed,
-        seed_inc=None: _TemporalFn.apply(h, tw, tb, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p,
-                                          layer_p, seed, seed_inc, None, None, *ps))
-_define("temporal_ce_opts_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, "
-        "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
-        "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_opts_bwd_op,
-        functools.partial(_temporal_bwd_fake, 6))
-_define("temporal_ce_mix", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
-        "Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, bool has_ignore, float label_smoothing, int B, int dt, int hid, int L, int H, "
-        "float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_mix_op,
-        functools.partial(_temporal_fake, 7),
-        lambda h, tw, tb, ps, hw, hb, mask, target, target_b, lam, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H, attn_p, layer_p,
-        seed, seed_inc=None: _TemporalFn.apply(h, tw, tb, hw, hb, mask, target, weight, ignore_index, has_ignore, label_smoothing, B, dt, hid, L, H,
-                                               attn_p, layer_p, seed, seed_inc, target_b, lam, *ps))
-_define("temporal_ce_mix_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor target_b, Tensor lam, Tensor? weight, int ignore_index, "
-        "bool has_ignore, float label_smoothing, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, "
-        "Tensor enc_out, int Hh, int Ww, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]",
-        temporal_ce_mix_bwd_op, functools.partial(_temporal_bwd_fake, 8))
-_define("temporal_ce_dense", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
-        "Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing, int B, int dt, int hid, int L, int H, float attn_p, float layer_p, "
-        "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_dense_op, functools.partial(_temporal_fake, 5),
-        lambda h, tw, tb, ps, hw, hb, mask, target, weight, pos_weight, kind, label_smoothing, B, dt, hid, L, H, attn_p, layer_p, seed,
-        seed_inc=None: _TemporalDenseFn.apply(h, tw, tb, hw, hb, mask, target, weight, pos_weight, kind, label_smoothing, B, dt, hid, L, H, attn_p,
-                                               layer_p, seed, seed_inc, *ps))
-_define("temporal_ce_dense_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, int kind, float label_smoothing, "
-        "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
-        "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_dense_bwd_op,
-        functools.partial(_temporal_bwd_fake, 6))
-_define("temporal_ce_focal", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
-        "Tensor? weight, int ignore_index, bool has_ignore, float gamma, int B, int dt, int hid, int L, int H, float attn_p, float layer_p, "
-        "int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_focal_op, functools.partial(_temporal_fake, 5),
-        lambda h, tw, tb, ps, hw, hb, mask, target, weight, ignore_index, has_ignore, gamma, B, dt, hid, L, H, attn_p, layer_p, seed,
-        seed_inc=None: _TemporalFocalFn.apply(False, h, tw, tb, hw, hb, mask, target, weight, None, ignore_index, has_ignore, gamma, B, dt, hid, L, H,
-                                               attn_p, layer_p, seed, seed_inc, *ps))
-_define("temporal_ce_focal_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float gamma, "
-        "Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, int hid, "
-        "int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_focal_bwd_op,
-        functools.partial(_temporal_bwd_fake, 6))
-_define("temporal_ce_asym", "(Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask, Tensor target, "
-        "Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, float clip, int B, int dt, int hid, int L, int H, float attn_p, "
-        "float layer_p, int seed, Tensor? seed_inc=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor)", temporal_ce_asym_op,
-        functools.partial(_temporal_fake, 6),
-        lambda h, tw, tb, ps, hw, hb, mask, target, weight, pos_weight, gamma_pos, gamma_neg, clip, B, dt, hid, L, H, attn_p, layer_p, seed,
-        seed_inc=None: _TemporalFocalFn.apply(True, h, tw, tb, hw, hb, mask, target, weight, pos_weight, gamma_pos, gamma_neg, clip, B, dt, hid, L, H,
-                                               attn_p, layer_p, seed, seed_inc, *ps))
-_define("temporal_ce_asym_bwd", "(Tensor dloss, Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, "
-        "float clip, Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, "
-        "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None) -> Tensor[]", temporal_ce_asym_bwd_op,
-        functools.partial(_temporal_bwd_fake, 7))
+_TEMPORAL_FRONT = "Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask"
+_TEMPORAL_BACK = "int B, int dt, int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None"
+_TEMPORAL_BWD_BACK = ("Tensor token_w, Tensor[] enc_params, Tensor head_w, Tensor? mask, Tensor feat, Tensor saved, Tensor enc_out, int Hh, int Ww, int dt, "
+                      "int hid, int L, int H, float attn_p, float layer_p, int seed, Tensor? seed_inc=None")
+
+
+def _temporal_autograd(fam):
+    """Autograd-key kernel of hybrid::temporal / hybrid::temporal_ce{sfx}: the encoder's parameter list goes last, flattened (a Function sees tensors
+    only as direct arguments).  (The dispatcher leaves a defaulted seed_inc out.)"""
+    n = (fam.n_args if fam else 0) + 9
+
+    def kernel(h, token_w, token_b, enc_params, head_w, head_b, mask, *rest, seed_inc=None):
+        return _TemporalFn.apply(fam, h, token_w, token_b, head_w, head_b, mask, *(*rest, seed_inc)[:n], *enc_params)
+    return kernel
+
+
+_define("temporal", f"({_TEMPORAL_FRONT}, {_TEMPORAL_BACK}) -> (Tensor, Tensor, Tensor, Tensor)", temporal_op, functools.partial(_temporal_fake, 0),
+        _temporal_autograd(None))
+_define("temporal_bwd", f"(Tensor dlogits, {_TEMPORAL_BWD_BACK}) -> Tensor[]", temporal_bwd_op, functools.partial(_temporal_bwd_fake, 0))
+
+
+def _define_loss_family(fam):
+    """The four operators of one LOSS_FAMILIES row: backend kernels over _cross_entropy_* / _temporal_*, the fake kernels, the two Functions."""
+    n = fam.n_args
+    _define("cross_entropy" + fam.sfx, f"(Tensor logits, {fam.schema}) -> Tensor", lambda logits, *a: _cross_entropy_fwd(fam, logits, a),
+            cross_entropy_fake, lambda logits, *a: _CrossEntropyFn.apply(fam, logits, *a))
+    _define("cross_entropy" + fam.sfx + "_bwd", f"(Tensor dloss, Tensor logits, {fam.schema}) -> Tensor",
+            lambda dloss, logits, *a: _cross_entropy_bwd(fam, dloss, logits, a), cross_entropy_bwd_fake)
+    _define("temporal_ce" + fam.sfx, f"({_TEMPORAL_FRONT}, {fam.schema}, {_TEMPORAL_BACK}) -> (Tensor, Tensor, Tensor, Tensor, Tensor)",
+            lambda h, token_w, token_b, enc_params, head_w, head_b, mask, *r, **kw: _temporal_fwd((fam, r[:n]), h, token_w, token_b, enc_params, head_w,
+                                                                                                    head_b, mask, *r[n:], **kw),
+            functools.partial(_temporal_fake, n), _temporal_autograd(fam))
+    _define("temporal_ce" + fam.sfx + "_bwd", f"(Tensor dloss, Tensor logits, {fam.schema}, {_TEMPORAL_BWD_BACK}) -> Tensor[]",
+            lambda dloss, logits, *r, **kw: _temporal_bwd((fam, logits, r[:n]), dloss, *r[n:], **kw), functools.partial(_temporal_bwd_fake, n + 1))
+
+
+for _fam in LOSS_FAMILIES.values():
+    _define_loss_family(_fam)
+    # what the two Functions slice by: the parsed schema lists logits, then the row's n_tensors tensors, then its scalars
+    _args = _fam.op("cross_entropy").default._schema.arguments[1:]
+    assert [isinstance(a.real_type, (torch.TensorType, torch.OptionalType)) for a in _args] == [True] * _fam.n_tensors + [False] * (_fam.n_args - _fam.n_tensors)
 
 
 # ---------------------------------------------------------------------------------------------
