@@ -869,7 +869,9 @@ int hyb_dropout2d(const float* x, float* y, int N, long long HW, int C, float p,
  * finish does it), so the replayed step needs no separate "counter += 1" launch.  advance_ticket is a DEVICE pointer to one 32-bit word
  * owned by the caller, zero at rest, used by this counter's advancing launches only (the launch counts its finished workgroups there and
  * leaves it zero): advancing calls on different counters -- two optimizers on two streams -- each bring their own word and never
- * interfere; two advancing calls on the SAME counter must be stream-ordered, as any two steps of one optimizer are. */
+ * interfere; two advancing calls on the SAME counter must be stream-ordered, as any two steps of one optimizer are.
+ * -1 with nothing launched for a NULL array or entry or a numel[i] <= 0 ANYWHERE in the table (also past the 80 tensors of the first
+ * launch), and, as every optimizer call below, for a table of 2^31 or more 4096-element chunks. */
 int hyb_adamw_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                    const long long* numel, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,
                    long long* step_inc, unsigned int* advance_ticket, void* stream);
@@ -929,7 +931,8 @@ int hyb_adamw_step_dev_ema(int count, float* const* params, const float* const* 
  *
  * hyb_grad_accumulate: acc[i][e] = acc[i][e] + grads[i][e] for every tensor of the table in one launch (80 tensors per launch, more
  * tensors = more launches); 4096-element chunks, 16-byte accesses where both pointers are aligned; grads is only read.  3 x 4 bytes
- * per parameter.  -1 for a NULL array or entry, acc[i] == grads[i], numel[i] <= 0, count <= 0. */
+ * per parameter.  -1 for a NULL array or entry, acc[i] == grads[i], numel[i] <= 0, count <= 0, or a table of 2^31 or more chunks in all,
+ * decided before the first launch. */
 int hyb_grad_accumulate(int count, float* const* acc, const float* const* grads, const long long* numel, void* stream);
 /* hyb_grad_norm_acc: hyb_grad_norm over G -- the same workspace (hyb_grad_norm_workspace), the same summation order, the same final
  * launch, so the norm equals hyb_grad_norm over a materialised G bit for bit.  acc and grads are only read. */

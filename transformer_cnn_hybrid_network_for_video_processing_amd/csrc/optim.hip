@@ -14,6 +14,7 @@
 // Parameter groups: hyb_adamw_step_dev_groups serves the tensors of ALL groups from one launch -- the table carries one byte per tensor, its
 // group, and thread 0 of a workgroup forms its scalars from that group's row of the device blocks hyper[groups, 6] / ema_hyper[groups, 2];
 // hyb_adamw_hyper_set_groups writes the rows of several groups in one launch.
+#include <algorithm>
 #include <type_traits>
 
 #include "hyb_common.h"
@@ -573,42 +574,6 @@ __global__ __launch_bounds__(256) void hyper_set_groups_kernel(HyperSetArgs a) {
     for (int i = threadIdx.x; i < a.ema_n * 2; i += 256) a.ema_hyper[2 * (int)a.ema_group[i / 2] + i % 2] = a.ema_v[i];
 }
 
-// hyb_adamw_step_dev (ema == NULL) and hyb_adamw_step_dev_ema: the tensor table in launches of at most the variant's capacity, the last
-// of which advances the counter.  GROUPS (hyb_adamw_step_dev_groups): the grouped table and kernel; group[i] is tensor i's parameter group,
-// hyper / ema_hyper the bases of the blocks.
-template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false, bool GROUPS = false>
-int adamw_dev_launch(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                     float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
-                     long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream, float* const* acc = nullptr, long long k = 1, const long long* guard = nullptr,
-                     const unsigned char* group = nullptr) {
-    constexpr int MAX = GROUPS ? AdamGroupArgs<EMA, ACC != GRAD_PLAIN>::MAX
-                               : ACC != GRAD_PLAIN ? (EMA ? ADAM_EMA_ACC_MAX : ADAM_ACC_MAX) : (EMA ? ADAM_EMA_MAX : ADAM_MAX);
-    for (int first = 0; first < count; first += MAX) {
-        AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS> a{};
-        const int n = count - first < MAX ? count - first : MAX;
-        int chunks = 0;
-        for (int i = 0; i < n; ++i) {
-            a.t[i] = AdamTensor{params[first + i], ACC == GRAD_ACC ? nullptr : grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
-            if constexpr (EMA) a.e[i] = ema[first + i];
-            if constexpr (ACC != GRAD_PLAIN) a.acc[i] = acc[first + i];
-            if constexpr (GROUPS) a.group[i] = group[first + i];
-            a.chunk_begin[i] = chunks;
-            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
-        }
-        a.chunk_begin[n] = chunks;
-        a.count = n;
-        a.hyper = hyper; a.step_inc = step_inc; a.step = step; a.clip = clip;
-        if constexpr (EMA) a.ema_hyper = ema_hyper;
-        if constexpr (ACC != GRAD_PLAIN) { a.k = k; a.inv_k = (float)(1.0 / (double)k); }
-        if constexpr (GUARD) a.guard = guard;
-        a.advance = (advance_ticket && first + MAX >= count) ? step_inc : nullptr;            // the last launch of the call advances the counter
-        a.ticket = advance_ticket;
-        hipLaunchKernelGGL((adamw_dev_kernel<EMA, ACC, GUARD, GROUPS>), dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
-        HYB_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
 // ---- gradient accumulation ----------------------------------------------------------------------------------------------------------------
 // acc += g over the whole tensor table in one launch: what ends micro-batches 1 .. k - 1 of an accumulated step.  The chunk -> tensor -> thread
 // mapping of adamw_dev_kernel; a full aligned chunk issues its eight 16-byte loads before the first add.
@@ -654,126 +619,227 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(AccumArgs a) {
     }
 }
 
-// the one-workgroup launch that ends a norm call; guard != NULL: the variant that also takes the skip decision
-int grad_norm_final_launch(const float* partials, long long total, const double* hyper, float* norm_out, long long* guard, void* stream) {
-    if (guard) hipLaunchKernelGGL(grad_norm_final_guard_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int)total, hyper, norm_out, guard);
-    else hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int)total, hyper, norm_out);
+// ---- host side ----------------------------------------------------------------------------------------------------------------------------
+// Every entry point below works on a table of `count` tensors.  Three helpers are all of them share: table_ok (the table is sound),
+// for_each_slice (the table in launches of at most a kernel's capacity) and, for the device-path steps, one descriptor (AdamStep) with one
+// validity rule (adam_step_ok) and one dispatch (adam_step_launch).  Nothing is launched before the whole call has been checked.
+
+// count > 0, numel and every listed array given, no NULL entry, every numel positive, and the chunks of the whole table fit an int (the
+// kernels index them with one)
+template <typename... T> bool table_ok(int count, const long long* numel, const T* const*... arrays) {
+    if (count <= 0 || !numel || !(arrays && ...)) return false;
+    long long chunks = 0;
+    for (int i = 0; i < count; ++i) {                                // (the sum in long long, tested as it grows: no tensor can wrap it)
+        if (numel[i] <= 0 || !(arrays[i] && ...) || (chunks += (numel[i] - 1) / ADAM_CHUNK + 1) >= (1ll << 31)) return false;
+    }
+    return true;
+}
+
+// The table in slices of at most `capacity` tensors: launch(first, n, chunk_begin, last) gets tensors [first, first + n), chunk_begin[0 .. n]
+// (tensor first + i owns the workgroups chunk_begin[i] .. chunk_begin[i + 1] of the slice's launch) and whether this is the call's last slice
+// (the one that advances a counter).  Stops at the first non-zero status.
+template <typename Launch> int for_each_slice(int count, const long long* numel, int capacity, Launch&& launch) {
+    for (int first = 0; first < count; first += capacity) {
+        const int n = count - first < capacity ? count - first : capacity;
+        int chunk_begin[ADAM_MAX + 1] = {};
+        for (int i = 0; i < n; ++i) chunk_begin[i + 1] = chunk_begin[i] + hyb_cdiv(numel[first + i], ADAM_CHUNK);
+        const int rc = launch(first, n, chunk_begin, first + capacity >= count);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
+template <typename Kernel, typename Args> int launch_chunks(Kernel kernel, const Args& a, void* stream) {
+    hipLaunchKernelGGL(kernel, dim3(a.chunk_begin[a.count]), dim3(256), 0, (hipStream_t)stream, a);
     HYB_LAUNCH_CHECK();
     return 0;
 }
 
-// hyb_grad_norm (guard == NULL) and hyb_grad_norm_guard: the same chunk launches, the same final sum
-int grad_norm_call(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper, float* norm_out,
-                   long long* guard, void* stream) {
-    HYB_CHECK_ARG(count > 0 && grads && numel && partials && hyper && norm_out);
-    long long total = 0;
-    for (int i = 0; i < count; ++i) {
-        HYB_CHECK_ARG(grads[i] && numel[i] > 0);
-        total += hyb_cdiv(numel[i], ADAM_CHUNK);
-    }
-    HYB_CHECK_ARG(total < (1ll << 31));
-    int offset = 0;
-    for (int first = 0; first < count; first += ADAM_MAX) {
-        GradNormArgs a{};
-        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
-        int chunks = 0;
-        for (int i = 0; i < n; ++i) {
-            a.g[i] = grads[first + i]; a.n[i] = numel[first + i];
-            a.chunk_begin[i] = chunks;
-            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
-        }
-        a.chunk_begin[n] = chunks;
-        a.count = n;
-        a.chunk_offset = offset;
-        a.partials = partials;
-        hipLaunchKernelGGL(grad_norm_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
-        HYB_LAUNCH_CHECK();
-        offset += chunks;
-    }
-    return grad_norm_final_launch(partials, total, hyper, norm_out, guard, stream);
+// What any device-path step call is, in the order of hyb_adamw_step_dev_groups' parameters.  NULL where a call has no such thing: grads (the
+// accumulators hold the whole sum), acc (k == 1), ema and ema_hyper (no average), group (one group: hyper / ema_hyper are its rows, not the
+// blocks' bases), ticket (the counter does not advance), clip, guard.
+struct AdamStep {
+    int count;
+    float* const* params; const float* const* grads; float* const* exp_avg; float* const* exp_avg_sq; float* const* acc; float* const* ema;
+    const long long* numel;
+    const unsigned char* group; int groups;
+    const double* hyper; const double* ema_hyper;
+    long long k, step; long long* step_inc; unsigned int* ticket;
+    const float* clip; const long long* guard;
+};
+
+// the one rule; an entry point adds only what its own prototype promises (hyb_adamw_step_dev: grads, ...)
+bool adam_step_ok(const AdamStep& s) {
+    if (!table_ok(s.count, s.numel, s.params, s.exp_avg, s.exp_avg_sq) || !s.hyper || s.step < 1 || s.k < 1 || !(s.acc || (s.k == 1 && s.grads)) ||
+        (s.ema != nullptr) != (s.ema_hyper != nullptr) || (s.ticket && !s.step_inc) || (s.guard && !s.clip)) return false;
+    for (int i = 0; i < s.count; ++i)
+        if ((s.grads && !s.grads[i]) || (s.acc && (!s.acc[i] || s.acc[i] == s.params[i])) || (s.ema && (!s.ema[i] || s.ema[i] == s.params[i])) ||
+            (s.group && (int)s.group[i] >= s.groups)) return false;
+    return true;
 }
 
-// hyb_grad_norm_acc (guard == NULL) and hyb_grad_norm_acc_guard
-int grad_norm_acc_call(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k, float* partials,
-                       const double* hyper, float* norm_out, long long* guard, void* stream) {
-    HYB_CHECK_ARG(count > 0 && acc && numel && k >= 1 && partials && hyper && norm_out);
-    long long total = 0;
-    for (int i = 0; i < count; ++i) {
-        HYB_CHECK_ARG(acc[i] && (!grads || grads[i]) && numel[i] > 0);
-        total += hyb_cdiv(numel[i], ADAM_CHUNK);
-    }
-    HYB_CHECK_ARG(total < (1ll << 31));
-    int offset = 0;
-    for (int first = 0; first < count; first += ADAM_MAX) {
-        GradNormAccArgs a{};
-        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
-        int chunks = 0;
+// one instantiation of adamw_dev_kernel over the whole table; the last launch of the call advances the counter
+template <bool EMA, int ACC, bool GUARD, bool GROUPS> int adamw_dev_launch(const AdamStep& s, void* stream) {
+    using Args = AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS>;
+    return for_each_slice(s.count, s.numel, (int)(sizeof(Args::t) / sizeof(AdamTensor)), [&](int first, int n, const int* chunk_begin, bool last) {
+        Args a{};
         for (int i = 0; i < n; ++i) {
-            a.acc[i] = acc[first + i]; a.g[i] = grads ? grads[first + i] : nullptr; a.n[i] = numel[first + i];
-            a.chunk_begin[i] = chunks;
-            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
+            a.t[i] = AdamTensor{s.params[first + i], ACC == GRAD_ACC ? nullptr : s.grads[first + i], s.exp_avg[first + i], s.exp_avg_sq[first + i], s.numel[first + i]};
+            if constexpr (EMA) a.e[i] = s.ema[first + i];
+            if constexpr (ACC != GRAD_PLAIN) a.acc[i] = s.acc[first + i];
+            if constexpr (GROUPS) a.group[i] = s.group[first + i];
         }
-        a.chunk_begin[n] = chunks;
+        std::copy(chunk_begin, chunk_begin + n + 1, a.chunk_begin);
         a.count = n;
-        a.chunk_offset = offset;
+        a.hyper = s.hyper; a.step_inc = s.step_inc; a.step = s.step; a.clip = s.clip;
+        if constexpr (EMA) a.ema_hyper = s.ema_hyper;
+        if constexpr (ACC != GRAD_PLAIN) { a.k = s.k; a.inv_k = (float)(1.0 / (double)s.k); }
+        if constexpr (GUARD) a.guard = s.guard;
+        a.advance = (s.ticket && last) ? s.step_inc : nullptr;
+        a.ticket = s.ticket;
+        return launch_chunks(adamw_dev_kernel<EMA, ACC, GUARD, GROUPS>, a, stream);
+    });
+}
+
+// (ema, acc and grads, guard, group) given or not -> the 2 x 3 x 2 x 2 instantiations
+template <typename F> int with_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+int adam_step_launch(const AdamStep& s, void* stream) {
+    return with_flag(s.ema != nullptr, [&](auto ema) { return with_flag(s.guard != nullptr, [&](auto guard) { return with_flag(s.group != nullptr, [&](auto groups) {
+        constexpr bool EMA = decltype(ema)::value, GUARD = decltype(guard)::value, GROUPS = decltype(groups)::value;
+        if (!s.acc) return adamw_dev_launch<EMA, GRAD_PLAIN, GUARD, GROUPS>(s, stream);
+        if (s.grads) return adamw_dev_launch<EMA, GRAD_ACC_G, GUARD, GROUPS>(s, stream);
+        return adamw_dev_launch<EMA, GRAD_ACC, GUARD, GROUPS>(s, stream);
+    }); }); });
+}
+
+int adam_step(const AdamStep& s, void* stream) {
+    HYB_CHECK_ARG(adam_step_ok(s));
+    return adam_step_launch(s, stream);
+}
+
+// The four norm entry points: acc == NULL is the plain norm of grads (k == 1), acc given the norm of (acc + grads) / k, or of acc / k without
+// grads; guard given: the final launch that also takes the skip decision.  The same chunk launches, the same final sum.
+int grad_norm_call(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k, float* partials,
+                   const double* hyper, float* norm_out, long long* guard, void* stream) {
+    HYB_CHECK_ARG((!acc ? table_ok(count, numel, grads) : grads ? table_ok(count, numel, acc, grads) : table_ok(count, numel, acc)) && k >= 1 &&
+                  partials && hyper && norm_out);
+    int total = 0;
+    const int rc = for_each_slice(count, numel, ADAM_MAX, [&](int first, int n, const int* chunk_begin, bool) {
+        GradNormAccArgs a{};
+        for (int i = 0; i < n; ++i) {
+            a.g[i] = grads ? grads[first + i] : nullptr; a.n[i] = numel[first + i];
+            if (acc) a.acc[i] = acc[first + i];
+        }
+        std::copy(chunk_begin, chunk_begin + n + 1, a.chunk_begin);
+        a.count = n;
+        a.chunk_offset = total;
         a.partials = partials;
         a.inv_k = (float)(1.0 / (double)k);
-        if (grads) hipLaunchKernelGGL(grad_norm_acc_kernel<GRAD_ACC_G>, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(grad_norm_acc_kernel<GRAD_ACC>, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
-        HYB_LAUNCH_CHECK();
-        offset += chunks;
-    }
-    return grad_norm_final_launch(partials, total, hyper, norm_out, guard, stream);
+        total += chunk_begin[n];
+        if (!acc) return launch_chunks(grad_norm_kernel, static_cast<const GradNormArgs&>(a), stream);
+        return grads ? launch_chunks(grad_norm_acc_kernel<GRAD_ACC_G>, a, stream) : launch_chunks(grad_norm_acc_kernel<GRAD_ACC>, a, stream);
+    });
+    if (rc != 0) return rc;
+    if (guard) hipLaunchKernelGGL(grad_norm_final_guard_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, total, hyper, norm_out, guard);
+    else hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, total, hyper, norm_out);
+    HYB_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace
 
-extern "C" int hyb_grad_accumulate(int count, float* const* acc, const float* const* grads, const long long* numel, void* stream) {
-    HYB_CHECK_ARG(count > 0 && acc && grads && numel);
-    for (int i = 0; i < count; ++i) HYB_CHECK_ARG(acc[i] && grads[i] && acc[i] != grads[i] && numel[i] > 0);
-    for (int first = 0; first < count; first += ADAM_MAX) {
-        AccumArgs a{};
-        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
-        long long chunks = 0;
-        for (int i = 0; i < n; ++i) {
-            a.acc[i] = acc[first + i]; a.g[i] = grads[first + i]; a.n[i] = numel[first + i];
-            a.chunk_begin[i] = (int)chunks;
-            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
-            HYB_CHECK_ARG(chunks < (1ll << 31));
-        }
-        a.chunk_begin[n] = (int)chunks;
+// The by-value step.  The WHOLE table is checked before the first launch -- a NULL entry or a numel <= 0 in a later slice (past the 80th
+// tensor) is refused with nothing stepped -- and so is a table whose chunks do not fit an int, as by every entry point of this file.
+extern "C" int hyb_adamw_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                              const long long* numel, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,
+                              long long* step_inc, unsigned int* advance_ticket, void* stream) {
+    HYB_CHECK_ARG(table_ok(count, numel, params, grads, exp_avg, exp_avg_sq) && step >= 1 && lr >= 0.0 && (!advance_ticket || step_inc));
+    // every scalar is formed in double from the caller's doubles and rounded once, as torch does with its Python floats
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    AdamArgs scalars{};
+    scalars.decay = (float)(1.0 - lr * weight_decay);
+    scalars.omb1 = (float)(1.0 - beta1); scalars.beta2 = (float)beta2; scalars.omb2 = (float)(1.0 - beta2); scalars.eps = (float)eps;
+    scalars.step_size = (float)(lr / bc1);
+    scalars.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    scalars.step_inc = step_inc; scalars.step = step; scalars.lr = lr; scalars.beta1d = beta1; scalars.beta2d = beta2;
+    scalars.ticket = advance_ticket;
+    return for_each_slice(count, numel, ADAM_MAX, [&](int first, int n, const int* chunk_begin, bool last) {
+        AdamArgs a = scalars;
+        for (int i = 0; i < n; ++i) a.t[i] = AdamTensor{params[first + i], grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
+        std::copy(chunk_begin, chunk_begin + n + 1, a.chunk_begin);
         a.count = n;
-        hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, a);
-        HYB_LAUNCH_CHECK();
+        a.advance = (advance_ticket && last) ? step_inc : nullptr;            // the last launch of the call advances the counter
+        return launch_chunks(adamw_kernel, a, stream);
+    });
+}
+
+// acc += grads.  The chunks of the WHOLE table must fit an int, checked before the first launch (not slice by slice, after earlier slices
+// have been added).
+extern "C" int hyb_grad_accumulate(int count, float* const* acc, const float* const* grads, const long long* numel, void* stream) {
+    HYB_CHECK_ARG(table_ok(count, numel, acc, grads));
+    for (int i = 0; i < count; ++i) HYB_CHECK_ARG(acc[i] != grads[i]);
+    return for_each_slice(count, numel, ADAM_MAX, [&](int first, int n, const int* chunk_begin, bool) {
+        AccumArgs a{};
+        for (int i = 0; i < n; ++i) { a.acc[i] = acc[first + i]; a.g[i] = grads[first + i]; a.n[i] = numel[first + i]; }
+        std::copy(chunk_begin, chunk_begin + n + 1, a.chunk_begin);
+        a.count = n;
+        return launch_chunks(grad_accumulate_kernel, a, stream);
+    });
+}
+
+extern "C" size_t hyb_grad_norm_workspace(int count, const long long* numel) {
+    if (count <= 0 || !numel) return 0;
+    size_t chunks = 0;
+    for (int i = 0; i < count; ++i) {
+        if (numel[i] <= 0) return 0;
+        chunks += (size_t)hyb_cdiv(numel[i], ADAM_CHUNK);
     }
-    return 0;
+    return chunks;
+}
+
+extern "C" int hyb_grad_norm(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
+                             float* norm_out, void* stream) {
+    return grad_norm_call(count, nullptr, grads, numel, 1, partials, hyper, norm_out, nullptr, stream);
+}
+
+extern "C" int hyb_grad_norm_guard(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
+                                   float* norm_out, long long* guard, void* stream) {
+    HYB_CHECK_ARG(guard);
+    return grad_norm_call(count, nullptr, grads, numel, 1, partials, hyper, norm_out, guard, stream);
 }
 
 extern "C" int hyb_grad_norm_acc(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k, float* partials,
                                  const double* hyper, float* norm_out, void* stream) {
-    return grad_norm_acc_call(count, acc, grads, numel, k, partials, hyper, norm_out, nullptr, stream);
+    HYB_CHECK_ARG(acc);
+    return grad_norm_call(count, acc, grads, numel, k, partials, hyper, norm_out, nullptr, stream);
 }
 
 extern "C" int hyb_grad_norm_acc_guard(int count, const float* const* acc, const float* const* grads, const long long* numel, long long k,
                                        float* partials, const double* hyper, float* norm_out, long long* guard, void* stream) {
-    HYB_CHECK_ARG(guard);
-    return grad_norm_acc_call(count, acc, grads, numel, k, partials, hyper, norm_out, guard, stream);
+    HYB_CHECK_ARG(acc && guard);
+    return grad_norm_call(count, acc, grads, numel, k, partials, hyper, norm_out, guard, stream);
+}
+
+// ---- the five device-path steps: each states what its own prototype requires, fills the descriptor and forwards -------------------------------
+extern "C" int hyb_adamw_step_dev(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                  const long long* numel, const double* hyper, long long step, long long* step_inc,
+                                  unsigned int* advance_ticket, const float* clip, void* stream) {
+    HYB_CHECK_ARG(grads);
+    return adam_step({count, params, grads, exp_avg, exp_avg_sq, nullptr, nullptr, numel, nullptr, 0, hyper, nullptr, 1, step, step_inc, advance_ticket, clip, nullptr}, stream);
+}
+
+extern "C" int hyb_adamw_step_dev_ema(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                      float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
+                                      long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream) {
+    HYB_CHECK_ARG(grads && ema && ema_hyper);
+    return adam_step({count, params, grads, exp_avg, exp_avg_sq, nullptr, ema, numel, nullptr, 0, hyper, ema_hyper, 1, step, step_inc, advance_ticket, clip, nullptr}, stream);
 }
 
 extern "C" int hyb_adamw_step_dev_acc(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                                       float* const* acc, float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper,
                                       long long k, long long step, long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream) {
-    HYB_CHECK_ARG(count > 0 && params && exp_avg && exp_avg_sq && acc && numel && hyper && k >= 1 && step >= 1 && (!advance_ticket || step_inc) &&
-                  (ema != nullptr) == (ema_hyper != nullptr));
-    for (int i = 0; i < count; ++i)
-        HYB_CHECK_ARG(params[i] && (!grads || grads[i]) && exp_avg[i] && exp_avg_sq[i] && acc[i] && acc[i] != params[i] &&
-                      (!ema || (ema[i] && ema[i] != params[i])) && numel[i] > 0);
-    if (ema) {
-        if (grads) return adamw_dev_launch<true, GRAD_ACC_G>(count, params, grads, exp_avg, exp_avg_sq, ema, numel, hyper, ema_hyper, step, step_inc, advance_ticket, clip, stream, acc, k);
-        return adamw_dev_launch<true, GRAD_ACC>(count, params, nullptr, exp_avg, exp_avg_sq, ema, numel, hyper, ema_hyper, step, step_inc, advance_ticket, clip, stream, acc, k);
-    }
-    if (grads) return adamw_dev_launch<false, GRAD_ACC_G>(count, params, grads, exp_avg, exp_avg_sq, nullptr, numel, hyper, nullptr, step, step_inc, advance_ticket, clip, stream, acc, k);
-    return adamw_dev_launch<false, GRAD_ACC>(count, params, nullptr, exp_avg, exp_avg_sq, nullptr, numel, hyper, nullptr, step, step_inc, advance_ticket, clip, stream, acc, k);
+    HYB_CHECK_ARG(acc);
+    return adam_step({count, params, grads, exp_avg, exp_avg_sq, acc, ema, numel, nullptr, 0, hyper, ema_hyper, k, step, step_inc, advance_ticket, clip, nullptr}, stream);
 }
 
 // every variant of the device-path step behind one entry point: acc == NULL (k == 1) is the plain step, with or without the average
@@ -781,17 +847,8 @@ extern "C" int hyb_adamw_step_dev_guard(int count, float* const* params, const f
                                         float* const* acc, float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper,
                                         long long k, long long step, long long* step_inc, unsigned int* advance_ticket, const float* clip,
                                         const long long* guard, void* stream) {
-    HYB_CHECK_ARG(count > 0 && params && exp_avg && exp_avg_sq && numel && hyper && k >= 1 && step >= 1 && (!advance_ticket || step_inc) &&
-                  (ema != nullptr) == (ema_hyper != nullptr) && guard && clip && (acc || (k == 1 && grads)));
-    for (int i = 0; i < count; ++i)
-        HYB_CHECK_ARG(params[i] && (!grads || grads[i]) && exp_avg[i] && exp_avg_sq[i] && (!acc || (acc[i] && acc[i] != params[i])) &&
-                      (!ema || (ema[i] && ema[i] != params[i])) && numel[i] > 0);
-#define HYB_GUARDED(EMA, ACC, G, E, EH) \
-    adamw_dev_launch<EMA, ACC, true>(count, params, G, exp_avg, exp_avg_sq, E, numel, hyper, EH, step, step_inc, advance_ticket, clip, stream, acc, k, guard)
-    if (!acc) return ema ? HYB_GUARDED(true, GRAD_PLAIN, grads, ema, ema_hyper) : HYB_GUARDED(false, GRAD_PLAIN, grads, nullptr, nullptr);
-    if (ema) return grads ? HYB_GUARDED(true, GRAD_ACC_G, grads, ema, ema_hyper) : HYB_GUARDED(true, GRAD_ACC, nullptr, ema, ema_hyper);
-    return grads ? HYB_GUARDED(false, GRAD_ACC_G, grads, nullptr, nullptr) : HYB_GUARDED(false, GRAD_ACC, nullptr, nullptr, nullptr);
-#undef HYB_GUARDED
+    HYB_CHECK_ARG(guard && clip);
+    return adam_step({count, params, grads, exp_avg, exp_avg_sq, acc, ema, numel, nullptr, 0, hyper, ema_hyper, k, step, step_inc, advance_ticket, clip, guard}, stream);
 }
 
 // the same variants over the tensors of several parameter groups: hyper / ema_hyper are the bases of the blocks, group[i] picks tensor i's row
@@ -799,24 +856,26 @@ extern "C" int hyb_adamw_step_dev_groups(int count, float* const* params, const 
                                          float* const* acc, float* const* ema, const long long* numel, const unsigned char* group, int groups,
                                          const double* hyper, const double* ema_hyper, long long k, long long step, long long* step_inc,
                                          unsigned int* advance_ticket, const float* clip, const long long* guard, void* stream) {
-    HYB_CHECK_ARG(count > 0 && params && exp_avg && exp_avg_sq && numel && group && groups >= 1 && groups <= ADAM_GROUPS_MAX && hyper && k >= 1 &&
-                  step >= 1 && (!advance_ticket || step_inc) && (ema != nullptr) == (ema_hyper != nullptr) && (!guard || clip) &&
-                  (acc || (k == 1 && grads)));
-    long long chunks = 0;
-    for (int i = 0; i < count; ++i) {
-        HYB_CHECK_ARG(params[i] && (!grads || grads[i]) && exp_avg[i] && exp_avg_sq[i] && (!acc || (acc[i] && acc[i] != params[i])) &&
-                      (!ema || (ema[i] && ema[i] != params[i])) && numel[i] > 0 && (int)group[i] < groups);
-        chunks += hyb_cdiv(numel[i], ADAM_CHUNK);
-    }
-    HYB_CHECK_ARG(chunks < (1ll << 31));
-#define HYB_GROUPED(EMA, ACC, GUARD, G, E, EH) \
-    adamw_dev_launch<EMA, ACC, GUARD, true>(count, params, G, exp_avg, exp_avg_sq, E, numel, hyper, EH, step, step_inc, advance_ticket, clip, stream, acc, k, guard, group)
-#define HYB_GROUPED_ACC(EMA, GUARD, E, EH) \
-    (!acc ? HYB_GROUPED(EMA, GRAD_PLAIN, GUARD, grads, E, EH) : grads ? HYB_GROUPED(EMA, GRAD_ACC_G, GUARD, grads, E, EH) : HYB_GROUPED(EMA, GRAD_ACC, GUARD, nullptr, E, EH))
-    if (guard) return ema ? HYB_GROUPED_ACC(true, true, ema, ema_hyper) : HYB_GROUPED_ACC(false, true, nullptr, nullptr);
-    return ema ? HYB_GROUPED_ACC(true, false, ema, ema_hyper) : HYB_GROUPED_ACC(false, false, nullptr, nullptr);
-#undef HYB_GROUPED_ACC
-#undef HYB_GROUPED
+    HYB_CHECK_ARG(group && groups >= 1 && groups <= ADAM_GROUPS_MAX);
+    return adam_step({count, params, grads, exp_avg, exp_avg_sq, acc, ema, numel, group, groups, hyper, ema_hyper, k, step, step_inc, advance_ticket, clip, guard}, stream);
+}
+
+// ---- the uploads of the device blocks -----------------------------------------------------------------------------------------------------------
+extern "C" int hyb_adamw_hyper_set(double* hyper, double lr, double beta1, double beta2, double eps, double weight_decay, double max_grad_norm,
+                                   void* stream) {
+    HYB_CHECK_ARG(hyper && lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0 &&
+                  max_grad_norm == max_grad_norm);
+    const HyperVals h{{lr, beta1, beta2, eps, weight_decay, max_grad_norm}};
+    hipLaunchKernelGGL(hyper_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, h);
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int hyb_adamw_ema_set(double* ema_hyper, double decay, double warmup, void* stream) {
+    HYB_CHECK_ARG(ema_hyper && decay >= 0.0 && decay < 1.0 && (warmup == 0.0 || warmup == 1.0));
+    hipLaunchKernelGGL(ema_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ema_hyper, decay, warmup);
+    HYB_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int hyb_adamw_hyper_set_groups(double* hyper, double* ema_hyper, int groups, int count, const unsigned char* group, const double* values,
@@ -854,89 +913,3 @@ extern "C" int hyb_adamw_hyper_set_groups(double* hyper, double* ema_hyper, int 
     return 0;
 }
 
-extern "C" int hyb_adamw_hyper_set(double* hyper, double lr, double beta1, double beta2, double eps, double weight_decay, double max_grad_norm,
-                                   void* stream) {
-    HYB_CHECK_ARG(hyper && lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0 &&
-                  max_grad_norm == max_grad_norm);
-    const HyperVals h{{lr, beta1, beta2, eps, weight_decay, max_grad_norm}};
-    hipLaunchKernelGGL(hyper_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, h);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" size_t hyb_grad_norm_workspace(int count, const long long* numel) {
-    if (count <= 0 || !numel) return 0;
-    size_t chunks = 0;
-    for (int i = 0; i < count; ++i) {
-        if (numel[i] <= 0) return 0;
-        chunks += (size_t)hyb_cdiv(numel[i], ADAM_CHUNK);
-    }
-    return chunks;
-}
-
-extern "C" int hyb_grad_norm(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
-                             float* norm_out, void* stream) {
-    return grad_norm_call(count, grads, numel, partials, hyper, norm_out, nullptr, stream);
-}
-
-extern "C" int hyb_grad_norm_guard(int count, const float* const* grads, const long long* numel, float* partials, const double* hyper,
-                                   float* norm_out, long long* guard, void* stream) {
-    HYB_CHECK_ARG(guard);
-    return grad_norm_call(count, grads, numel, partials, hyper, norm_out, guard, stream);
-}
-
-extern "C" int hyb_adamw_step_dev(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                                  const long long* numel, const double* hyper, long long step, long long* step_inc,
-                                  unsigned int* advance_ticket, const float* clip, void* stream) {
-    HYB_CHECK_ARG(count > 0 && params && grads && exp_avg && exp_avg_sq && numel && hyper && step >= 1 && (!advance_ticket || step_inc));
-    for (int i = 0; i < count; ++i) HYB_CHECK_ARG(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && numel[i] > 0);
-    return adamw_dev_launch<false>(count, params, grads, exp_avg, exp_avg_sq, nullptr, numel, hyper, nullptr, step, step_inc, advance_ticket, clip, stream);
-}
-
-extern "C" int hyb_adamw_ema_set(double* ema_hyper, double decay, double warmup, void* stream) {
-    HYB_CHECK_ARG(ema_hyper && decay >= 0.0 && decay < 1.0 && (warmup == 0.0 || warmup == 1.0));
-    hipLaunchKernelGGL(ema_set_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ema_hyper, decay, warmup);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int hyb_adamw_step_dev_ema(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                                      float* const* ema, const long long* numel, const double* hyper, const double* ema_hyper, long long step,
-                                      long long* step_inc, unsigned int* advance_ticket, const float* clip, void* stream) {
-    HYB_CHECK_ARG(count > 0 && params && grads && exp_avg && exp_avg_sq && ema && numel && hyper && ema_hyper && step >= 1 &&
-                  (!advance_ticket || step_inc));
-    for (int i = 0; i < count; ++i)
-        HYB_CHECK_ARG(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && ema[i] && ema[i] != params[i] && numel[i] > 0);
-    return adamw_dev_launch<true>(count, params, grads, exp_avg, exp_avg_sq, ema, numel, hyper, ema_hyper, step, step_inc, advance_ticket, clip, stream);
-}
-
-extern "C" int hyb_adamw_step(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                              const long long* numel, double lr, double beta1, double beta2, double eps, double weight_decay, long long step,
-                              long long* step_inc, unsigned int* advance_ticket, void* stream) {
-    HYB_CHECK_ARG(count > 0 && params && grads && exp_avg && exp_avg_sq && numel && step >= 1 && lr >= 0.0 && (!advance_ticket || step_inc));
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    for (int first = 0; first < count; first += ADAM_MAX) {
-        AdamArgs a{};
-        const int n = count - first < ADAM_MAX ? count - first : ADAM_MAX;
-        int chunks = 0;
-        for (int i = 0; i < n; ++i) {
-            HYB_CHECK_ARG(params[first + i] && grads[first + i] && exp_avg[first + i] && exp_avg_sq[first + i] && numel[first + i] > 0);
-            a.t[i] = AdamTensor{params[first + i], grads[first + i], exp_avg[first + i], exp_avg_sq[first + i], numel[first + i]};
-            a.chunk_begin[i] = chunks;
-            chunks += hyb_cdiv(numel[first + i], ADAM_CHUNK);
-        }
-        a.chunk_begin[n] = chunks;
-        a.count = n;
-        // every scalar is formed in double from the caller's doubles and rounded once, as torch does with its Python floats
-        a.decay = (float)(1.0 - lr * weight_decay);
-        a.omb1 = (float)(1.0 - beta1); a.beta2 = (float)beta2; a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
-        a.step_size = (float)(lr / bc1);
-        a.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-        a.step_inc = step_inc; a.step = step; a.lr = lr; a.beta1d = beta1; a.beta2d = beta2;
-        a.advance = (advance_ticket && first + ADAM_MAX >= count) ? step_inc : nullptr;       // the last launch of the call advances the counter
-        a.ticket = advance_ticket;
-        hipLaunchKernelGGL(adamw_kernel, dim3(chunks), dim3(256), 0, (hipStream_t)stream, a);
-        HYB_LAUNCH_CHECK();
-    }
-    return 0;
-}

@@ -61,14 +61,12 @@ Gradient accumulation (accumulation_steps = k > 1): one optimizer step over k ca
     DistributedDataParallel.no_sync() -- and graph C steps on bucket / k with no gradient tensors, which leaves the buckets zeroed.
     Limitation: fwd_bwd() is refused with k > 1 and world > 1 (graphs A and B no longer fill the buckets by themselves).
 """
-import ctypes
 import os
 
 import torch
 import torch.distributed as dist
 
 from . import ops
-from ._lib import lib, ptr_array
 from .meter import MultiLabelMeter
 
 
@@ -152,8 +150,7 @@ class GraphedTrainStep:
         self._advancing = (sum(1 for g in optimizer.param_groups if any(p.requires_grad for p in g["params"])) == 1
                            or (hasattr(optimizer, "merges_groups") and optimizer.merges_groups()))
         optimizer.set_step_counter(self.counter, advance=self._advancing)
-        self._acc_tabs = {}                                    # world > 1, k > 1: the pointer tables of the two eager accumulate launches
-        self._captured = False
+        self._captured = False                                 # (world > 1, k > 1: the eager accumulate launches' tables are kept from then on)
         if self.world > 1 and k == 1:
             for p, v in zip(self.t_params + self.b_params, self.t_views + self.b_views):
                 p.grad = v                                     # AdamW reads the (all-reduced) buckets in place
@@ -340,16 +337,9 @@ class GraphedTrainStep:
         """World > 1 with accumulation: one eager hyb_grad_accumulate, bucket views += the gradients graph A (or B) has just written."""
         if self.world == 1 or self._k == 1:
             return
-        tab = self._acc_tabs.get(which)
-        if tab is None:
-            params, views = (self.t_params, self.t_views) if which == "t" else (self.b_params, self.b_views)
-            if not params:
-                return
-            tab = (len(params), ptr_array([v.data_ptr() for v in views]), ptr_array([p.grad.data_ptr() for p in params]),
-                   (ctypes.c_longlong * len(params))(*[p.numel() for p in params]), [p.grad for p in params])
-            if self._captured:                                 # the captured gradient tensors stay where they are (and tab[4] keeps them alive)
-                self._acc_tabs[which] = tab
-        lib.call("hyb_grad_accumulate", tab[0], tab[1], tab[2], tab[3], ops._stream())
+        params, views = (self.t_params, self.t_views) if which == "t" else (self.b_params, self.b_views)
+        if params:                                             # (the optimizer keeps the table only once the captures are done)
+            self.optimizer._accumulate_into(("bucket", which), params, views, keep=self._captured)
 
     def _reduce(self, bucket):
         if self.world == 1:

@@ -4,50 +4,102 @@
 weight_decay 1e-2, amsgrad/maximize off); state-dict keys (`step`, `exp_avg`, `exp_avg_sq`) follow torch's so checkpoints
 interchange.  CUDA fp32 parameters only -- there is no CPU fallback.
 
-Two things a training run needs on top of that, both built on hyper-parameters that live in DEVICE memory (`double hyper[6]` per group):
-  * `max_grad_norm=c`: `torch.nn.utils.clip_grad_norm_(params, c)` fused into the step -- one launch forms the global L2 norm of all
-    gradients and the clip coefficient (`hyb_grad_norm`, bit-reproducible), the AdamW launch scales every gradient element by it;
-  * `set_dynamic_hyper(True)`: the AdamW launch reads lr / betas / eps / weight_decay from the device block (`hyb_adamw_step_dev`), so a
-    launch captured into a hipGraph follows `param_groups[i]["lr"] = ...` -- i.e. any `torch.optim.lr_scheduler` -- after a
-    `sync_hyper()`, which `step()` (eager) and `GraphedTrainStep.step()` (before the replay) call;
-  * `ema_decay=d`: an exponential moving average of the weights (timm's ModelEma, swa_utils.AveragedModel) kept by the AdamW launch itself
-    (`hyb_adamw_step_dev_ema`): `state[p]["ema"] <- d * ema + (1 - d) * p_new` where the launch holds `p_new` in a register -- no second
-    pass over the weights, no extra launch.  `ema_warmup=True` uses `min(d, (1 + n) / (10 + n))` after n earlier steps.  Both live in a device
-    block (`double [groups, 2]`), so a captured step follows a decay changed between replays.  `ema_model(model)` gives a twin module whose
+What a training run needs on top of that, all built on hyper-parameters that live in DEVICE memory (`double hyper[groups, 6]`; the C side
+of each is described in include/hybrid_hip.h):
+  * `max_grad_norm=c`: `torch.nn.utils.clip_grad_norm_(params, c)` fused into the step -- one bit-reproducible launch forms the global L2
+    norm of all gradients and the clip coefficient, the AdamW launch scales every gradient element by it;
+  * `set_dynamic_hyper(True)`: the AdamW launch reads lr / betas / eps / weight_decay from the device block, so a launch captured into a
+    hipGraph follows `param_groups[i]["lr"] = ...` -- i.e. any `torch.optim.lr_scheduler` -- after a `sync_hyper()`, which `step()`
+    (eager) and `GraphedTrainStep.step()` (before the replay) call;
+  * `ema_decay=d`: an exponential moving average of the weights (timm's ModelEma, swa_utils.AveragedModel) kept by the AdamW launch itself:
+    `state[p]["ema"] <- d * ema + (1 - d) * p_new` where the launch holds `p_new` in a register -- no second pass over the weights, no
+    extra launch.  `ema_warmup=True` uses `min(d, (1 + n) / (10 + n))` after n earlier steps.  Both live in a device block
+    (`double [groups, 2]`), so a captured step follows a decay changed between replays.  `ema_model(model)` gives a twin module whose
     parameters ARE the averages, for `predict` / `GraphedPredict`.  The average follows only parameters that are stepped: a parameter
     without a gradient keeps its old average.
   * `accumulation_steps=k`: one optimizer step over k micro-batches.  After each of the first k - 1 backward passes `accumulate()` adds
-    every `.grad` into an fp32 accumulator (`hyb_grad_accumulate`, one launch per group); `step()` after the k-th steps on
-    `(acc + grad) * (1 / k)` and leaves the accumulators zeroed, all inside the AdamW launch (`hyb_adamw_step_dev_acc`; the norm of a
-    clipped step is taken over the same mean, `hyb_grad_norm_acc`): no separate sum, scale or memset pass.  The accumulators are zero at
-    every optimizer-step boundary, so they are neither state nor part of the state dict.
+    every `.grad` into an fp32 accumulator; `step()` after the k-th steps on `(acc + grad) * (1 / k)` and leaves the accumulators zeroed,
+    all inside the AdamW launch (the norm of a clipped step is taken over the same mean): no separate sum, scale or memset pass.  The
+    accumulators are zero at every optimizer-step boundary, so they are neither state nor part of the state dict.
   * `skip_nonfinite=True`: an optimizer step whose global gradient norm is not finite -- a NaN or infinite gradient element, or finite ones
     whose sum of squares overflows fp32 (a single 1e20: deliberate) -- leaves parameters, both moments and the weight average exactly as
-    they were, and is counted, all on the device: the norm launch's final workgroup writes `{skip_now, skipped_total}` into a device block
-    (`hyb_grad_norm_guard` / `hyb_grad_norm_acc_guard`), the AdamW launch reads it and, on a skip, makes no store to the model
-    (`hyb_adamw_step_dev_guard`); it still zeroes the accumulators and advances the device step counter.  What GradScaler.step does, with
-    no host read: it works inside a replayed hipGraph.  Bias correction and the average's warm-up go by the number of APPLIED updates, so
-    the run continues as if the batch had never been seen.  With max_grad_norm the norm is taken anyway and the guard adds no launch;
-    without, the guard runs the norm launches for its decision (coefficient 1).  With finite gradients every step is bit-identical to the
-    unguarded one.  `skipped_steps` / `last_step_skipped` are device scalars; on a skipped step `grad_norm` holds the non-finite norm and
-    `clip_coef` is unspecified.  In eager use `state[p]["step"]` counts ATTEMPTED steps until `fold_skipped()` (one host read; `state_dict()`
-    calls it) subtracts the device count, so saved steps are applied-update counts.  Out of scope: BatchNorm running statistics are
-    updated by the forward pass and are not rolled back (an inf activation reaches them, as in torch), and a learning-rate scheduler
-    stepped by the host is not held back on a skipped step (as with GradScaler).
-  * `merge_groups=True` (the default): on the device path ONE AdamW launch serves the tensors of all parameter groups
-    (`hyb_adamw_step_dev_groups`: the tensor table carries each tensor's group, and a workgroup reads that group's row of the device
-    blocks), `accumulate()` is one launch and `sync_hyper()` uploads all changed groups with one (`hyb_adamw_hyper_set_groups`) -- so
-    no-decay groups and a per-layer learning rate (`TransformerCNNHybrid.param_groups`) cost no launch per group, and an advancing step
-    counter works with them.  Bit for bit the per-group launches' result.  It applies when more than one group has gradients, all of
-    them keep a weight average or none does, they share the step number and there are at most 255 groups; otherwise, and on the plain
-    by-value path, every group is a launch of its own as before.  An attribute like `skip_nonfinite`, neither a group key nor state."""
+    they were, and is counted, all on the device: the norm launch's final workgroup writes `{skip_now, skipped_total}` into a device block,
+    the AdamW launch reads it and, on a skip, makes no store to the model; it still zeroes the accumulators and advances the device step
+    counter.  What GradScaler.step does, with no host read: it works inside a replayed hipGraph.  Bias correction and the average's
+    warm-up go by the number of APPLIED updates, so the run continues as if the batch had never been seen.  With max_grad_norm the norm
+    is taken anyway and the guard adds no launch; without, the guard runs the norm launches for its decision (coefficient 1).  With finite
+    gradients every step is bit-identical to the unguarded one.  `skipped_steps` / `last_step_skipped` are device scalars; on a skipped
+    step `grad_norm` holds the non-finite norm and `clip_coef` is unspecified.  In eager use `state[p]["step"]` counts ATTEMPTED steps
+    until `fold_skipped()` (one host read; `state_dict()` calls it) subtracts the device count, so saved steps are applied-update
+    counts.  Out of scope: BatchNorm running statistics are updated by the forward pass and are not rolled back (an inf activation
+    reaches them, as in torch), and a learning-rate scheduler stepped by the host is not held back on a skipped step (as with GradScaler).
+  * `merge_groups=True` (the default): on the device path ONE AdamW launch serves the tensors of all parameter groups (the tensor table
+    carries each tensor's group, and a workgroup reads that group's row of the device blocks), `accumulate()` is one launch and
+    `sync_hyper()` uploads all changed groups with one -- so no-decay groups and a per-layer learning rate
+    (`TransformerCNNHybrid.param_groups`) cost no launch per group, and an advancing step counter works with them.  Bit for bit the
+    per-group launches' result.  It applies when more than one group has gradients, all of them keep a weight average or none does, they
+    share the step number and there are at most 255 groups; otherwise, and on the plain by-value path, every group is a launch of its
+    own as before.  An attribute like `skip_nonfinite`, neither a group key nor state.
+
+How a step is put together.  `_plan` decides once per call which groups are live and whether one call serves them all; each resulting
+launch unit is a `_Unit` record -- the pointer tables of its tensors, built (and cached while no tensor moves) by `_unit`, the one builder
+behind `step()`, `accumulate()` and GraphedTrainStep's eager accumulate.  `step()` is then `_prepare` (state, tables, step numbers),
+`_norm` (one call, named by `_norm_symbol`) and `_launch` (one call per unit: `_step_symbol` names the entry point, `_STEP_ARGS` lists its
+arguments by the names of the record's fields)."""
 import copy
 import ctypes
+from typing import NamedTuple
 
 import torch
 
 from ._lib import lib, ptr_array
 from .ops import _stream
+
+
+class _Unit(NamedTuple):
+    """A launch unit: the tensors ONE library call serves -- the stepped parameters of one group (key: its index) or of all live groups
+    (key "all") -- as the host arrays the call takes.  A column the unit does not carry is None."""
+    key: object          # where the unit is cached
+    first: int           # index of the unit's first group (whose hyper row an ungrouped call reads)
+    params: list
+    layout: list         # the group index of every tensor (None: accumulate() does not care)
+    addrs: list          # per tensor, the addresses of its columns: the unit is valid while they and the layout stay
+    n: int
+    numel: object        # long long [n]
+    p: object            # the pointer arrays: parameters, exp_avg, exp_avg_sq, ...
+    m: object
+    v: object
+    ema: object          # ... the weight averages, the accumulators, ...
+    acc: object
+    group: object        # ... and unsigned char [n], the layout as a merged call takes it (None: a call for one group)
+
+
+# the arguments of each device-path step entry point, in order (the stream follows): fields of the unit, or names _launch defines
+_STEP_ARGS = {
+    "hyb_adamw_step_dev": "n p grads m v numel hyper step counter ticket clip",
+    "hyb_adamw_step_dev_ema": "n p grads m v ema numel hyper ema_hyper step counter ticket clip",
+    "hyb_adamw_step_dev_acc": "n p grads m v acc ema numel hyper ema_hyper k step counter ticket clip",
+    "hyb_adamw_step_dev_guard": "n p grads m v acc ema numel hyper ema_hyper k step counter ticket clip guard",
+    "hyb_adamw_step_dev_groups": "n p grads m v acc ema numel group groups hyper ema_hyper k step counter ticket clip guard",
+}
+_STEP_ARGS = {name: tuple(fields.split()) for name, fields in _STEP_ARGS.items()}
+
+
+def _step_symbol(merged, guard, accum, ema):
+    """The entry point of a device-path step: the first of merged / guarded / accumulating / averaging that holds names it (each of the
+    earlier ones takes all the later ones' arguments)."""
+    return "hyb_adamw_step_dev" + ("_groups" if merged else "_guard" if guard else "_acc" if accum else "_ema" if ema else "")
+
+
+def _norm_symbol(guard, accum):
+    return "hyb_grad_norm" + ("_acc" if accum else "") + ("_guard" if guard else "")
+
+
+def _no_capture(what, remedy, why=""):
+    """Device memory that must be zero (or hold a value) before its first captured use is created eagerly: a buffer born while its stream
+    captures is written only by that one graph (a replay of another graph would meet whatever it held before), so that is refused."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"HybridAdamW: {what} does not exist yet and cannot be created under stream capture {why}-- {remedy}")
 
 
 class HybridAdamW(torch.optim.Optimizer):
@@ -59,16 +111,17 @@ class HybridAdamW(torch.optim.Optimizer):
             raise ValueError("max_grad_norm must be None (no clipping) or > 0")
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("ema_decay must be None (no average) or in [0, 1)")
-        # (checked before the base class touches anything; neither a param-group key nor state: the accumulators are zero between steps)
-        self._accum_k = self._check_accumulation(accumulation_steps)
-        self._skip_nonfinite = self._check_skip_nonfinite(skip_nonfinite)    # (handled the same way: a constructor argument and an attribute)
-        self._merge_groups = self._check_merge_groups(merge_groups)          # (and this one: which launches serve the groups, not what they compute)
+        # three constructor arguments that are attributes -- neither a param-group key nor state (the accumulators are zero between steps;
+        # merge_groups says which launches serve the groups, not what they compute); checked before the base class touches anything
+        self._accum_k = self._checked("accumulation_steps", accumulation_steps)
+        self._skip_nonfinite = self._checked("skip_nonfinite", skip_nonfinite)
+        self._merge_groups = self._checked("merge_groups", merge_groups)
         self._guard = None           # device int64 [2]: skip_now (the last guarded step was skipped), skipped_total (since the last fold)
         # max_grad_norm sits in the groups only so that it travels in the state dict: clipping is global, every group carries the same value;
         # ema_decay / ema_warmup are per group (None: that group takes the launch without the average)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
                                       ema_decay=ema_decay, ema_warmup=bool(ema_warmup)))
-        self._tables = {}            # per group: cached pointer tables of the tensors whose addresses never change
+        self._tables = {}            # unit key -> the _Unit of step(), cached while the tensors' addresses stay
         self._step_counter = None    # device int64 [1]: the kernel uses step + counter (captured launches, graph.GraphedTrainStep)
         self._advance = False
         self._ticket = None          # device uint32 [1], this optimizer's own: the advancing launch counts its finished workgroups there
@@ -81,85 +134,70 @@ class HybridAdamW(torch.optim.Optimizer):
         self._ema_sent = {}          # per group: the (decay, warmup) last uploaded
         self._acc = {}               # parameter -> its fp32 gradient accumulator (16-byte aligned; zero at every optimizer-step boundary)
         self._acc_flat = []          # the flat buffers the accumulators created here are views of
-        self._acc_tables = {}        # per group: cached pointer tables of accumulate()
+        self._acc_tables = {}        # unit key -> the _Unit (parameters and accumulators only) of accumulate()
         self._acc_only = False       # _bind_accumulators(no_grad=True): the accumulators hold the whole sum, step() passes no gradients
 
     @staticmethod
-    def _check_accumulation(k):
-        if not isinstance(k, int) or isinstance(k, bool) or k < 1:
-            raise ValueError("accumulation_steps must be an int >= 1")
-        return k
+    def _checked(name, value):
+        """accumulation_steps: an int >= 1; skip_nonfinite, merge_groups: a bool."""
+        if name == "accumulation_steps":
+            if not isinstance(value, int) or isinstance(value, bool) or value < 1:
+                raise ValueError("accumulation_steps must be an int >= 1")
+        elif not isinstance(value, bool):
+            raise ValueError(f"{name} must be a bool")
+        return value
+
+    accumulation_steps = property(lambda self: self._accum_k)
+    skip_nonfinite = property(lambda self: self._skip_nonfinite)
+    merge_groups = property(lambda self: self._merge_groups)
 
     def set_accumulation(self, k):
         """Micro-batches per optimizer step from now on (1: plain steps).  Change it only at an optimizer-step boundary: step() divides
         whatever the accumulators hold, plus the current gradients, by the k in force when it runs."""
-        self._accum_k = self._check_accumulation(k)
-
-    @property
-    def accumulation_steps(self):
-        return self._accum_k
-
-    @staticmethod
-    def _check_skip_nonfinite(flag):
-        if not isinstance(flag, bool):
-            raise ValueError("skip_nonfinite must be a bool")
-        return flag
-
-    @property
-    def skip_nonfinite(self):
-        return self._skip_nonfinite
+        self._accum_k = self._checked("accumulation_steps", k)
 
     def set_skip_nonfinite(self, flag):
         """Switch the non-finite guard on or off between steps.  Switching folds the device's count of skipped steps first (fold_skipped():
         one host read), since only guarded launches subtract it from the step number."""
-        flag = self._check_skip_nonfinite(flag)
-        if flag != self._skip_nonfinite:
+        if self._checked("skip_nonfinite", flag) != self._skip_nonfinite:
             self.fold_skipped()
             self._skip_nonfinite = flag
 
-    @staticmethod
-    def _check_merge_groups(flag):
-        if not isinstance(flag, bool):
-            raise ValueError("merge_groups must be a bool")
-        return flag
-
-    @property
-    def merge_groups(self):
-        return self._merge_groups
-
     def set_merge_groups(self, flag):
         """Switch the one-launch step over all parameter groups on or off between steps (the cached pointer tables go with it)."""
-        flag = self._check_merge_groups(flag)
-        if flag != self._merge_groups:
+        if self._checked("merge_groups", flag) != self._merge_groups:
             self._merge_groups = flag
             self._tables.clear()
             self._acc_tables.clear()
 
-    def _merged(self, stepped):
-        """Whether ONE hyb_adamw_step_dev_groups call serves every live group -- a group with a parameter for which stepped(p) holds: the
-        device path, more than one live group, all of them with the average or all without, one step number, at most 255 groups."""
-        if not self._merge_groups or len(self.param_groups) > 255 or not self.uses_device_hyper():
-            return False
-        live = [g for g in self.param_groups if any(stepped(p) for p in g["params"])]
-        if len(live) < 2 or len({self._group_ema(g) is not None for g in live}) != 1:
-            return False
-        return len({int(self.state.get(p, {}).get("step", 0)) for g in live for p in g["params"] if stepped(p)}) == 1
+    def _plan(self, stepped):
+        """(merged, units) for the parameters for which stepped(p) holds.  A group with one is live; units lists what each library call
+        serves as (table key, indices of its groups).  merged: ONE hyb_adamw_step_dev_groups call serves every live group (key "all") -- the
+        device path, more than one live group, all of them with the average or all without, one step number, at most 255 groups;
+        otherwise one call per live group (key: its index)."""
+        groups = self.param_groups
+        live = [gi for gi, g in enumerate(groups) if any(stepped(p) for p in g["params"])]
+        merged = (self._merge_groups and len(groups) <= 255 and self.uses_device_hyper() and len(live) > 1
+                  and len({self._group_ema(groups[gi]) is not None for gi in live}) == 1
+                  and len({int(self.state.get(p, {}).get("step", 0)) for gi in live for p in groups[gi]["params"] if stepped(p)}) == 1)
+        return merged, ([("all", live)] if merged else [(gi, [gi]) for gi in live])
 
     def merges_groups(self):
         """Whether step() will serve all parameter groups from one AdamW launch, judged by requires_grad (for a caller that captures
         step() before any gradient exists, GraphedTrainStep): an advancing step counter is then allowed with several groups."""
-        return self._merged(lambda p: p.requires_grad)
+        return self._plan(lambda p: p.requires_grad)[0]
+
+    def _device(self):
+        dev = self.param_groups[0]["params"][0].device
+        if dev.type != "cuda":
+            raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
+        return dev
 
     def _guard_block(self):
-        """The guard block, created and zeroed EAGERLY, for the reason _device_buffers gives."""
+        """The guard block, created and zeroed eagerly (_no_capture)."""
         if self._guard is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("HybridAdamW: the non-finite guard's device block does not exist yet and cannot be created under stream "
-                                   "capture -- call sync_hyper() (or take one eager step()) with skip_nonfinite on before capturing")
-            dev = self.param_groups[0]["params"][0].device
-            if dev.type != "cuda":
-                raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
-            self._guard = torch.zeros(2, dtype=torch.int64, device=dev)
+            _no_capture("the non-finite guard's device block", "call sync_hyper() (or take one eager step()) with skip_nonfinite on before capturing")
+            self._guard = torch.zeros(2, dtype=torch.int64, device=self._device())
         return self._guard
 
     @property
@@ -236,15 +274,10 @@ class HybridAdamW(torch.optim.Optimizer):
         return c
 
     def _device_buffers(self):
-        """The hyper blocks and norm_out: created and zeroed EAGERLY.  A buffer born while its stream captures is
-        zeroed only by that one graph (a replay of another graph would meet whatever the block held before), so that is refused."""
+        """The hyper blocks and norm_out, created and zeroed eagerly (_no_capture)."""
         if self._hyper is None or self._hyper.shape[0] != len(self.param_groups):
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("HybridAdamW: the device hyper-parameter block does not exist yet and cannot be created under stream "
-                                   "capture -- call sync_hyper() (or take one eager step()) before capturing")
-            dev = self.param_groups[0]["params"][0].device
-            if dev.type != "cuda":
-                raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
+            _no_capture("the device hyper-parameter block", "call sync_hyper() (or take one eager step()) before capturing")
+            dev = self._device()
             self._hyper = torch.zeros(len(self.param_groups), 6, dtype=torch.float64, device=dev)
             self._hyper_sent = {}
             self._ema_hyper = torch.zeros(len(self.param_groups), 2, dtype=torch.float64, device=dev)
@@ -266,32 +299,26 @@ class HybridAdamW(torch.optim.Optimizer):
         the per-group calls where a single group changed, merge_groups is off or there are more than 255; the host never waits).  Must NOT be captured: the
         values travel as kernel arguments, a captured upload would put the capture-time values back at every replay."""
         hyper = self._device_buffers()
-        changed = [(gi, vals) for gi, vals in enumerate(map(self._group_hyper, self.param_groups)) if self._hyper_sent.get(gi) != vals]
-        ema_changed = [(gi, ema) for gi, ema in enumerate(map(self._group_ema, self.param_groups)) if ema is not None and self._ema_sent.get(gi) != ema]
-        if self._merge_groups and len({gi for gi, _ in changed + ema_changed}) > 1 and len(self.param_groups) <= 255:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
-            lib.call("hyb_adamw_hyper_set_groups", hyper, self._ema_hyper, len(self.param_groups),
-                     len(changed), (ctypes.c_ubyte * len(changed))(*[gi for gi, _ in changed]),
-                     (ctypes.c_double * (6 * len(changed)))(*[v for _, vals in changed for v in vals]),
-                     len(ema_changed), (ctypes.c_ubyte * len(ema_changed))(*[gi for gi, _ in ema_changed]),
-                     (ctypes.c_double * (2 * len(ema_changed)))(*[v for _, ema in ema_changed for v in ema]), _stream())
-            self._hyper_sent.update(changed)
-            self._ema_sent.update(ema_changed)
+        changed = {gi: vals for gi, vals in enumerate(map(self._group_hyper, self.param_groups)) if self._hyper_sent.get(gi) != vals}
+        ema_changed = {gi: ema for gi, ema in enumerate(map(self._group_ema, self.param_groups)) if ema is not None and self._ema_sent.get(gi) != ema}
+        rows = sorted(changed.keys() | ema_changed.keys())
+        if not rows:
             return
-        for gi, group in enumerate(self.param_groups):
-            vals = self._group_hyper(group)
-            if self._hyper_sent.get(gi) != vals:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
-                lib.call("hyb_adamw_hyper_set", hyper[gi], *vals, _stream())
-                self._hyper_sent[gi] = vals
-            ema = self._group_ema(group)
-            if ema is not None and self._ema_sent.get(gi) != ema:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
-                lib.call("hyb_adamw_ema_set", self._ema_hyper[gi], *ema, _stream())
-                self._ema_sent[gi] = ema
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("HybridAdamW.sync_hyper() under stream capture: upload the hyper-parameters before capturing")
+        if self._merge_groups and len(rows) > 1 and len(self.param_groups) <= 255:
+            lib.call("hyb_adamw_hyper_set_groups", hyper, self._ema_hyper, len(self.param_groups),
+                     len(changed), (ctypes.c_ubyte * len(changed))(*changed), (ctypes.c_double * (6 * len(changed)))(*[v for vals in changed.values() for v in vals]),
+                     len(ema_changed), (ctypes.c_ubyte * len(ema_changed))(*ema_changed),
+                     (ctypes.c_double * (2 * len(ema_changed)))(*[v for ema in ema_changed.values() for v in ema]), _stream())
+        else:
+            for gi in rows:
+                if gi in changed:
+                    lib.call("hyb_adamw_hyper_set", hyper[gi], *changed[gi], _stream())
+                if gi in ema_changed:
+                    lib.call("hyb_adamw_ema_set", self._ema_hyper[gi], *ema_changed[gi], _stream())
+        self._hyper_sent.update(changed)
+        self._ema_sent.update(ema_changed)
 
     @property
     def grad_norm(self):
@@ -319,9 +346,8 @@ class HybridAdamW(torch.optim.Optimizer):
                 st["step"] = int(st["step"].item())
 
     def _new_ema(self, p):
-        if p.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("HybridAdamW: a parameter's weight average does not exist yet and cannot be created under stream capture -- "
-                               "call ema_init() (or take one eager step()) before capturing")
+        if p.is_cuda:
+            _no_capture("a parameter's weight average", "call ema_init() (or take one eager step()) before capturing")
         return p.detach().clone()
 
     @torch.no_grad()
@@ -369,15 +395,31 @@ class HybridAdamW(torch.optim.Optimizer):
             self._tables.clear()
             self._acc_tables.clear()
 
+    # ---- launch units -------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _unit(cache, key, first, params, layout=None, merged=False, **columns):
+        """The _Unit of `params` with the given columns (p, m, v, ema, acc: one tensor per parameter, or None), from cache[key] if it is
+        still valid -- every tensor of every column is where it was (load_state_dict() / a rollback replaces the moments and the averages
+        with new allocations, the old ones may already be freed) and in the group it was in -- else built and cached (cache None: not kept)."""
+        addrs = list(zip(*[[t.data_ptr() for t in col] for col in columns.values() if col is not None]))
+        u = None if cache is None else cache.get(key)
+        if u is None or u.addrs != addrs or u.layout != layout:
+            arrays = dict.fromkeys(("p", "m", "v", "ema", "acc"))
+            arrays.update((name, ptr_array([t.data_ptr() for t in col])) for name, col in columns.items() if col is not None)
+            u = _Unit(key, first, params, layout, addrs, len(params), (ctypes.c_longlong * len(params))(*[p.numel() for p in params]),
+                      group=(ctypes.c_ubyte * len(params))(*layout) if merged else None, **arrays)
+            if cache is not None:
+                cache[key] = u
+        return u
+
     # ---- gradient accumulation --------------------------------------------------------------------------------------------------------
     def _new_accumulators(self, params):
         """Zeroed accumulators for `params`, views of ONE flat buffer, each starting on a multiple of 4 elements (16 bytes)."""
         if not params:
             return
-        if params[0].is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("HybridAdamW: a parameter's gradient accumulator does not exist yet and cannot be created under stream capture "
-                               "(it must be zero before the first micro-batch, and a buffer born in a capture is zeroed by that graph only) -- "
-                               "call accum_init() before capturing")
+        if params[0].is_cuda:
+            _no_capture("a parameter's gradient accumulator", "call accum_init() before capturing",
+                        "(it must be zero before the first micro-batch, and a buffer born in a capture is zeroed by that graph only) ")
         for p in params:
             if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
                 raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
@@ -413,6 +455,11 @@ class HybridAdamW(torch.optim.Optimizer):
         self._tables.clear()
         self._acc_tables.clear()
 
+    def _accumulate_into(self, key, params, accs, keep=True):
+        """accs[i] += params[i].grad in one hyb_grad_accumulate call, its table cached under `key` (keep=False: built for this call only)."""
+        u = self._unit(self._acc_tables if keep else None, key, None, params, p=params, acc=accs)
+        lib.call("hyb_grad_accumulate", u.n, u.acc, self._float_grads(params), u.numel, _stream())
+
     @torch.no_grad()
     def accumulate(self):
         """End one of the micro-batches 1 .. k - 1: acc += grad for every parameter with a gradient, one hyb_grad_accumulate launch per
@@ -421,20 +468,9 @@ class HybridAdamW(torch.optim.Optimizer):
             raise RuntimeError("HybridAdamW.accumulate() needs accumulation_steps > 1 (with 1, step() does not read the accumulators)")
         if self._acc_only:
             raise RuntimeError("HybridAdamW.accumulate(): the accumulators are bound to external buffers whose owner adds the gradients itself")
-        # where step() serves all groups from one launch, so does this: the tensors of every live group in one table (key "all")
-        merged = self._merged(lambda p: p.grad is not None)
-        tables = [("all", [p for group in self.param_groups for p in group["params"]])] if merged else \
-            [(gi, group["params"]) for gi, group in enumerate(self.param_groups)]
-        for gi, params in tables:
-            ps = [p for p in params if p.grad is not None]
-            if not ps:
-                continue
-            accs = self._accumulators(ps)
-            addrs = [(p.data_ptr(), a.data_ptr()) for p, a in zip(ps, accs)]
-            tab = self._acc_tables.get(gi)
-            if tab is None or tab[0] != addrs:
-                tab = self._acc_tables[gi] = (addrs, ptr_array([a[1] for a in addrs]), (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps]))
-            lib.call("hyb_grad_accumulate", len(ps), tab[1], self._float_grads(ps), tab[2], _stream())
+        for key, unit in self._plan(lambda p: p.grad is not None)[1]:
+            ps = [p for gi in unit for p in self.param_groups[gi]["params"] if p.grad is not None]
+            self._accumulate_into(key, ps, self._accumulators(ps))
 
     @staticmethod
     def _float_grads(ps):
@@ -446,128 +482,102 @@ class HybridAdamW(torch.optim.Optimizer):
             grads.append(g)
         return grads
 
+    # ---- the step -----------------------------------------------------------------------------------------------------------------------
+    def _prepare(self, key, unit, merged):
+        """One launch unit of step(): create what its parameters lack (accumulators, averages, moments), count the step, and return
+        (its _Unit, its gradients or None, the step number the call takes, whether it keeps averages)."""
+        ps, layout, ema = [], [], None
+        for gi in unit:
+            group = self.param_groups[gi]
+            gps = [p for p in group["params"] if p.grad is not None]
+            ema = self._group_ema(group)            # (merged: every group of the unit has one, or none has)
+            ps += gps
+            layout += [gi] * len(gps)
+        accs = self._accumulators(ps) if self._accum_k > 1 else None     # (first: a refusal under capture leaves the step counts untouched)
+        for p in ps:
+            if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
+            st = self.state[p]
+            if ema is not None and "ema" not in st:
+                st["ema"] = self._new_ema(p)         # the value before this step
+            if "exp_avg" not in st:                  # (ema_init() may have left a state that holds the average only)
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if self._step_counter is None:
+                st["step"] += 1
+        # with a device counter the Python-side step stays put and the kernel uses (step + 1) + counter
+        steps = {int(self.state[p]["step"]) + (1 if self._step_counter is not None else 0) for p in ps}
+        if len(steps) != 1:
+            raise RuntimeError("HybridAdamW: parameters of one group must share the step count")
+        states = [self.state[p] for p in ps]
+        u = self._unit(self._tables, key, unit[0], ps, layout, merged, p=ps, m=[st["exp_avg"] for st in states], v=[st["exp_avg_sq"] for st in states],
+                       ema=None if ema is None else [st["ema"] for st in states], acc=accs)
+        return u, None if accs is not None and self._acc_only else self._float_grads(ps), steps.pop(), ema is not None
+
+    def _norm(self, work, hyper, guard):
+        """ONE norm over the gradients of all units, as clip_grad_norm_(model.parameters()) -- in an accumulated step over the mean of the k
+        micro-batches' gradients; the guard takes its decision from it, so it runs without clipping too (hyper[5] == 0: coefficient 1)."""
+        accum = self._accum_k > 1
+        grads = None if accum and self._acc_only else [g for _, gs, _ in work for g in gs]
+        numels = tuple(n for u, _, _ in work for n in u.numel)
+        if self._partials is None or self._partials[0] != numels:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("HybridAdamW: the gradient-norm workspace cannot be created under stream capture -- take one eager "
+                                   "step() with the same gradients first")
+            arr = (ctypes.c_longlong * len(numels))(*numels)
+            chunks = lib.query("hyb_grad_norm_workspace", len(numels), arr)
+            self._partials = (numels, torch.zeros(chunks, dtype=torch.float32, device=hyper.device), arr)
+        _, partials, numel = self._partials
+        args = (ptr_array([a[-1] for u, _, _ in work for a in u.addrs]), grads, numel, self._accum_k) if accum else (grads, numel)
+        lib.call(_norm_symbol(guard is not None, accum), len(numels), *args, partials, hyper[work[0][0].first], self._norm_out,
+                 *(() if guard is None else (guard,)), _stream())
+        return self._norm_out
+
+    def _launch(self, u, grads, step, hyper, clip, guard):
+        """The one AdamW call of a unit on the device path.  A merged call takes the blocks' bases, any other its group's rows."""
+        name = _step_symbol(u.group is not None, guard is not None, self._accum_k > 1, u.ema is not None)
+        ema_hyper = None if u.ema is None else self._ema_hyper
+        vals = u._asdict()
+        vals.update(grads=grads, groups=len(self.param_groups), k=self._accum_k, step=step, counter=self._step_counter,
+                    ticket=self._ticket if self._advance else None, clip=clip, guard=guard, hyper=hyper if u.group is not None else hyper[u.first],
+                    ema_hyper=ema_hyper if u.group is not None or ema_hyper is None else ema_hyper[u.first])
+        lib.call(name, *[vals[f] for f in _STEP_ARGS[name]], _stream())
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        live = [gi for gi, group in enumerate(self.param_groups) if any(p.grad is not None for p in group["params"])]
-        # one hyb_adamw_step_dev_groups call over the tensors of all live groups (device path only): one call ends the step, so the counter
-        # may advance with several groups
-        merged = self._merged(lambda p: p.grad is not None)
-        if self._advance and len(live) != 1 and not merged:
+        # merged: one call ends the step, so the counter may advance with several groups
+        merged, units = self._plan(lambda p: p.grad is not None)
+        if self._advance and len(units) != 1:
             raise RuntimeError("HybridAdamW: an advancing step counter needs exactly one parameter group with gradients")
-        dev_path = self.uses_device_hyper()
-        accum = self._accum_k > 1
         guard = self._guard_block() if self._skip_nonfinite else None     # (first: a refusal under capture leaves the step counts untouched)
-        work = []                                   # per launch unit: (first group index, tensor count, tables, gradients, step number)
-        ema_groups = []                             # the live groups that keep an average
-        # a launch unit: the live groups one AdamW call serves -- all of them (merged; table key "all"), or one each (key: the group's index)
-        for key, unit in ([("all", live)] if merged else [(gi, [gi]) for gi in live]):
-            ps, layout, ema = [], [], None
-            for gi in unit:
-                group = self.param_groups[gi]
-                gps = [p for p in group["params"] if p.grad is not None]
-                ema = self._group_ema(group)        # (merged: every group of the unit has one, or none has)
-                if ema is not None:
-                    ema_groups.append(gi)
-                ps += gps
-                layout += [gi] * len(gps)
-            accs = self._accumulators(ps) if accum else None     # (first: a refusal under capture leaves the step counts untouched)
-            for p in ps:
-                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                    raise RuntimeError("HybridAdamW: contiguous fp32 CUDA parameters only (no CPU fallback)")
-                st = self.state[p]
-                if ema is not None and "ema" not in st:
-                    st["ema"] = self._new_ema(p)         # the value before this step
-                if "exp_avg" not in st:                  # (ema_init() may have left a state that holds the average only)
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                if self._step_counter is None:
-                    st["step"] += 1
-            # with a device counter the Python-side step stays put and the kernel uses (step + 1) + counter
-            steps = {int(self.state[p]["step"]) + (1 if self._step_counter is not None else 0) for p in ps}
-            if len(steps) != 1:
-                raise RuntimeError("HybridAdamW: parameters of one group must share the step count")
-            # the cached pointer tables are valid only while every parameter AND both of its moment tensors stay where they are:
-            # load_state_dict() / a rollback replaces the moments (and the averages) with new allocations (the old ones may already be freed)
-            if ema is None:
-                addrs = [(p.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for p in ps]
-            else:
-                addrs = [(p.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(), self.state[p]["ema"].data_ptr())
-                         for p in ps]
-            if accum:                               # ... and, in an accumulated step, the accumulators (the key's last entry)
-                addrs = [a + (acc.data_ptr(),) for a, acc in zip(addrs, accs)]
-            tab = self._tables.get(key)
-            if tab is None or tab[1] != addrs or tab[9] != layout:      # (merged: ... and while every tensor stays in its group)
-                tab = (None, addrs, ptr_array([a[0] for a in addrs]), ptr_array([a[1] for a in addrs]), ptr_array([a[2] for a in addrs]),
-                       (ctypes.c_longlong * len(ps))(*[p.numel() for p in ps]), None if ema is None else ptr_array([a[3] for a in addrs]),
-                       ptr_array([a[-1] for a in addrs]) if accum else None, (ctypes.c_ubyte * len(ps))(*layout) if merged else None, layout)
-                self._tables[key] = tab
-            grads = None if accum and self._acc_only else self._float_grads(ps)
-            work.append((unit[0], len(ps), tab, grads, steps.pop()))
-        counter = self._step_counter
-        ticket = self._ticket if self._advance else None
-        if not dev_path:
-            for gi, n, tab, grads, step in work:
-                group = self.param_groups[gi]
-                b1, b2 = group["betas"]
-                lib.call("hyb_adamw_step", n, tab[2], grads, tab[3], tab[4], tab[5], float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                         float(group["weight_decay"]), step, counter, ticket, _stream())
+        work, ema_groups = [], []
+        for key, unit in units:
+            u, grads, step, ema = self._prepare(key, unit, merged)
+            work.append((u, grads, step))
+            ema_groups += unit if ema else []
+        if not self.uses_device_hyper():
+            for u, grads, step in work:
+                lr, b1, b2, eps, wd, _ = self._group_hyper(self.param_groups[u.first])
+                lib.call("hyb_adamw_step", u.n, u.p, grads, u.m, u.v, u.numel, lr, b1, b2, eps, wd, step, self._step_counter,
+                         self._ticket if self._advance else None, _stream())
             return loss
         # ---- device path: hyper-parameters (and the clip coefficient) are read from device memory by the launches themselves ----
         clip = self._clip_value()
         hyper = self._device_buffers()
         if torch.cuda.is_current_stream_capturing():
-            # only hyb_grad_norm and hyb_adamw_step_dev are recorded; the upload is the replaying caller's (GraphedTrainStep.step)
+            # only the norm and the AdamW calls are recorded; the upload is the replaying caller's (GraphedTrainStep.step)
             if len(self._hyper_sent) != len(self.param_groups) or any(gi not in self._ema_sent for gi in ema_groups):
                 raise RuntimeError("HybridAdamW: hyper-parameters were never uploaded -- call sync_hyper() before capturing step()")
         else:
             self.sync_hyper()
         if not work:
             return loss
-        clip_coef = None
-        # ONE norm over the gradients of all groups, as clip_grad_norm_(model.parameters()); the guard takes its decision from it, so it runs
-        # the norm launches without clipping too (hyper[5] == 0: coefficient 1)
-        if clip is not None or guard is not None:
-            all_grads = None if accum and self._acc_only else [g for w in work for g in w[3]]
-            numels = tuple(n for w in work for n in w[2][5])
-            if self._partials is None or self._partials[0] != numels:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("HybridAdamW: the gradient-norm workspace cannot be created under stream capture -- take one eager "
-                                       "step() with the same gradients first")
-                arr = (ctypes.c_longlong * len(numels))(*numels)
-                chunks = lib.query("hyb_grad_norm_workspace", len(numels), arr)
-                self._partials = (numels, torch.zeros(chunks, dtype=torch.float32, device=hyper.device), arr)
-            if accum:                               # ... here over the mean of the k micro-batches' gradients
-                all_accs = ptr_array([a[-1] for w in work for a in w[2][1]])
-                if guard is None:
-                    lib.call("hyb_grad_norm_acc", len(numels), all_accs, all_grads, self._partials[2], self._accum_k, self._partials[1],
-                             hyper[work[0][0]], self._norm_out, _stream())
-                else:
-                    lib.call("hyb_grad_norm_acc_guard", len(numels), all_accs, all_grads, self._partials[2], self._accum_k, self._partials[1],
-                             hyper[work[0][0]], self._norm_out, guard, _stream())
-            elif guard is None:
-                lib.call("hyb_grad_norm", len(all_grads), all_grads, self._partials[2], self._partials[1], hyper[work[0][0]], self._norm_out, _stream())
-            else:
-                lib.call("hyb_grad_norm_guard", len(all_grads), all_grads, self._partials[2], self._partials[1], hyper[work[0][0]], self._norm_out,
-                         guard, _stream())
-            clip_coef = self._norm_out
-        for gi, n, tab, grads, step in work:
-            if merged:                              # every variant below, for all groups: the blocks' bases, and each tensor's group
-                lib.call("hyb_adamw_step_dev_groups", n, tab[2], grads, tab[3], tab[4], tab[7], tab[6], tab[5], tab[8], len(self.param_groups), hyper,
-                         None if tab[6] is None else self._ema_hyper, self._accum_k, step, counter, ticket, clip_coef, guard, _stream())
-            elif guard is not None:                 # every variant below behind one entry point, which reads the decision when it runs
-                lib.call("hyb_adamw_step_dev_guard", n, tab[2], grads, tab[3], tab[4], tab[7], tab[6], tab[5], hyper[gi],
-                         None if tab[6] is None else self._ema_hyper[gi], self._accum_k, step, counter, ticket, clip_coef, guard, _stream())
-            elif accum:                               # the same launch on (acc + g) / k, which leaves the accumulators zeroed
-                lib.call("hyb_adamw_step_dev_acc", n, tab[2], grads, tab[3], tab[4], tab[7], tab[6], tab[5], hyper[gi],
-                         None if tab[6] is None else self._ema_hyper[gi], self._accum_k, step, counter, ticket, clip_coef, _stream())
-            elif tab[6] is None:
-                lib.call("hyb_adamw_step_dev", n, tab[2], grads, tab[3], tab[4], tab[5], hyper[gi], step, counter, ticket, clip_coef, _stream())
-            else:                                   # the same launch, which also moves the averages
-                lib.call("hyb_adamw_step_dev_ema", n, tab[2], grads, tab[3], tab[4], tab[6], tab[5], hyper[gi], self._ema_hyper[gi], step, counter,
-                         ticket, clip_coef, _stream())
+        clip_coef = self._norm(work, hyper, guard) if clip is not None or guard is not None else None
+        for u, grads, step in work:
+            self._launch(u, grads, step, hyper, clip_coef, guard)
         return loss
