@@ -464,6 +464,54 @@ int hyb_eval_multilabel(const float* logits /* [B*V, C] */, const float* target 
                         unsigned char* pred /* [B, C] or NULL */, float* scores /* [B, C] */,
                         int B, int C, void* stream);
 
+/* hyb_eval_metrics_focal / hyb_eval_metrics_soft / hyb_eval_multilabel_asym: the two meters' updates under the other criteria the library
+ *   trains with (new symbols, hyb_abi_version() stays 9).  Each is the launch of hyb_eval_metrics / hyb_eval_multilabel with another loss
+ *   term: ONE 256-thread workgroup, thread t owns videos t, t + 256, .., fp32 terms summed in double over the fixed 256-leaf tree, one thread
+ *   makes the final add (no floating-point atomic), the launch ADDS into the caller's state and never synchronises.  Scores, predictions,
+ *   ranks, every counter, confusion, the tp / fp / fn cells and the bank are computed exactly as stated above -- the same statements of the
+ *   same kernel body, instantiated per criterion.  Only the loss term and the form of the target differ:
+ *   FOCAL (hyb_eval_metrics_focal; class indices y [B], the options and gamma of hyb_cross_entropy_focal_*):
+ *     V == 1: term_b is that criterion's per-clip function, keep_b w[y] u_b^gamma (lse_b - z_by), and the den share is w[y_b]: sums[0] /
+ *             sums[1] is its arithmetic.  keep, out-of-range targets and NaN scores follow the rules of hyb_eval_metrics.
+ *     V > 1:  with pbar the mean softmax written to scores[b]:  ubar = sum_{c != y} pbar_c, summed in class order, not formed as 1 - pbar_y;
+ *             term_b = keep_b w[y] ubar^gamma (-log pbar_y), x^0 taken as 1 (x^1 as x, x^2 as x x); the same den share.
+ *     gamma == 0 gives hyb_eval_metrics with the same weight and ignore_index (label_smoothing 0), both sums bit for bit, for every V.
+ *   SOFT (hyb_eval_metrics_soft; one fp32 row of class probabilities t_b [C] per video, weight and label_smoothing e of
+ *   hyb_cross_entropy_dense_* kind 0; q_c = (1 - e) t_c + e / C):
+ *     V == 1: term_b = sum_c w_c q_c (lse_b - z_bc), that criterion's per-clip function.
+ *     V > 1:  term_b = sum_c w_c q_c (-log pbar_c), in class order from 0.f, one fma per class.
+ *     Every video is kept and adds exactly 1.0 to sums[1]: the criterion's divisor is B, there is no ignore_index.  Rows are used as given.
+ *     The label for top-1 / top-k / confusion is the LOWEST index among the maxima of t_b (found with a strict >, as pred is).  A row
+ *     that holds a NaN has no label: the video counts as kept, is wrong for both accuracies, has no confusion entry, and its loss term
+ *     is what the arithmetic gives.
+ *   ASYMMETRIC (hyb_eval_multilabel_asym; weight, pos_weight, gamma_pos, gamma_neg, clip of hyb_cross_entropy_asym_*):
+ *     V == 1: term_b = sum_c cell_bc, that criterion's per-clip function on (z_b, t_b), where hyb_eval_multilabel has the BCE term; the
+ *             meter reports sums[0] / (videos C) as it does for BCE.
+ *     V > 1:  with s_c the mean sigmoid (the score) and qbar_c = (1 / V) sum_v sg(-z_vc), its own mean in view order, never 1 - s_c:
+ *             the criterion's cell with p -> s_c, q -> qbar_c and
+ *               logp = max(log s_c, -100),   logn = max(log qbar_c, -100) if clip == 0, else log(min(qbar_c + clip, 1));
+ *             r = max(s_c - clip, 0), base, g_t and L as there, the clip's term the same fma(-(w_c L), base^g_t (t logp + (1 - t) logn), sum)
+ *             chain over c.  It is formed in the class loop that forms the scores: no further walk over the row.  All views at
+ *             z = +-100 give a finite term.
+ *   HYB_E_ARG, before any HIP call: everything hyb_eval_metrics / hyb_eval_multilabel refuse; an exponent that is neither 0 nor >= 1 (NaN
+ *   and infinity included); clip outside [0, 1); label_smoothing outside [0, 1]. */
+int hyb_eval_metrics_focal(const float* logits /* [B*V, C] */, const long long* target /* [B] */, const float* weight /* [C] or NULL */,
+                           long long ignore_index, int has_ignore, float gamma, int topk, int views,
+                           double* sums /* [2] */, long long* counts /* [5] */, long long* confusion /* [C*C] or NULL */,
+                           long long* pred /* [B] or NULL */, float* scores /* [B, C] or NULL */, int B, int C, void* stream);
+int hyb_eval_metrics_soft(const float* logits /* [B*V, C] */, const float* target /* [B, C] */, const float* weight /* [C] or NULL */,
+                          float label_smoothing, int topk, int views,
+                          double* sums /* [2] */, long long* counts /* [5] */, long long* confusion /* [C*C] or NULL */,
+                          long long* pred /* [B] or NULL */, float* scores /* [B, C] or NULL */, int B, int C, void* stream);
+int hyb_eval_multilabel_asym(const float* logits /* [B*V, C] */, const float* target /* [B, C] */,
+                             const float* weight /* [C] or NULL */, const float* pos_weight /* [C] or NULL */,
+                             float gamma_pos, float gamma_neg, float clip, const float* threshold /* [C] */, int views,
+                             double* sums /* [1] */, long long* counts /* [5] */, long long* cells /* [C, 3] */,
+                             float* bank_scores /* [capacity, C] or NULL */, unsigned char* bank_labels /* [capacity, C] or NULL */,
+                             long long capacity,
+                             unsigned char* pred /* [B, C] or NULL */, float* scores /* [B, C] */,
+                             int B, int C, void* stream);
+
 /* ---- model-level entry points: whole CNN backbone / whole temporal part in ONE call each way ---------------------------
  * They chain the stage-level entry points above on the caller's stream; their purpose is host time (a training step is three
  * operator calls each way), not different arithmetic: results are bit-identical to calling the stages one by one.

@@ -100,7 +100,7 @@ struct HybCeDense { const float* target; const float* pos_weight; int kind; };
 // probability shift m in [0, 1), beside HybCeOpts (weight only) and a HybCeDense of kind 1 (target, pos_weight).
 struct HybCeFocal { float gamma; float gamma_neg; float clip; };
 // One loss, described once from the entry point to the kernel launch.  mode == the MODE template argument of temporal_tail_{fwd,bwd}_body
-// (layernorm.hip); the members a mode does not read stay zero.  target: class indices [B] (PLAIN, OPTS, MIX, FOCAL); the dense modes
+// and of the two meter kernels eval_metrics_kernel / eval_multilabel_kernel (layernorm.hip); the members a mode does not read stay zero.  target: class indices [B] (PLAIN, OPTS, MIX, FOCAL); the dense modes
 // (SOFT = HybCeDense kind 0, BCE = kind 1, ASYM) carry theirs in d.  hyb_loss_*(): the members each family of entry points fills.
 enum HybLossMode { HYB_LOSS_PLAIN = 0, HYB_LOSS_OPTS, HYB_LOSS_MIX, HYB_LOSS_SOFT, HYB_LOSS_BCE, HYB_LOSS_FOCAL, HYB_LOSS_ASYM };
 struct HybLoss { int mode; const long long* target; HybCeOpts o; HybCeMix m; HybCeDense d; HybCeFocal f; };

@@ -1138,6 +1138,10 @@ __global__ __launch_bounds__(256) void temporal_tail_bwd_asym_kernel(const float
 // V == 1: the scores are the logits and the loss term is ce_clip_loss_opts / ce_clip_den themselves (a validation loss is the training
 // criterion's arithmetic).  V > 1: the scores are the mean of the views' softmax rows, formed in fp32 in the video's own `scores` row (the
 // owning thread's scratch), and the term is the criterion's formula with -log(pbar_c) where it has lse - z_c.
+// ONE body for every criterion the meter knows, templated on the loss mode as the temporal tail is: HYB_LOSS_OPTS (hyb_eval_metrics),
+// HYB_LOSS_FOCAL (hyb_eval_metrics_focal) and HYB_LOSS_SOFT (hyb_eval_metrics_soft; the target is the dense row l.d.target[b], its label the
+// lowest index among the row's maxima).  Only the loss term, the den share and the form of the target differ: scores, pred, ranks,
+// counters and confusion are the same statements in every instantiation.
 struct HybEvalArgs {
     const float* logits; const long long* target; double* sums; long long* counts; long long* confusion; long long* pred; float* scores;
     int B, C, V, topk;
@@ -1153,14 +1157,51 @@ __device__ __forceinline__ float eval_clip_loss_probs(const float* p, const floa
     }
     return r;
 }
-__global__ __launch_bounds__(256) void eval_metrics_kernel(HybEvalArgs a, HybCeOpts o) {
+// V > 1, focal: ubar = sum_{c != y} pbar_c in class order (not 1 - pbar_y); gm == 0 returns eval_clip_loss_probs' bits at label smoothing 0
+__device__ __forceinline__ float eval_clip_loss_probs_focal(const float* p, const float* w, long long t, int C, const HybCeOpts& o, float gm) {
+    if (!ce_keep(t, o)) return 0.f;
+    if (!(t >= 0 && t < C)) return NAN;
+    const float r = ce_w(w, (int)t) * -logf(p[(int)t]);
+    if (gm == 0.f) return r;
+    float u = 0.f;
+    for (int c = 0; c < C; ++c)
+        if (c != (int)t) u += p[c];
+    return ce_pow(u, gm) * r;
+}
+// V > 1, soft targets: ce_clip_loss_soft's chain with -log(pbar_c) where it has lse - z_c
+__device__ __forceinline__ float eval_clip_loss_probs_soft(const float* p, const float* w, const float* t, int C, float e) {
+    float r = 0.f;
+    for (int c = 0; c < C; ++c) r = fmaf(ce_w(w, c) * ce_soft_q(t[c], e, C), -logf(p[c]), r);
+    return r;
+}
+// a soft row's label for top-1 / top-k / confusion: the lowest index among its maxima (strict >, as pred); a row holding a NaN has none
+__device__ __forceinline__ long long eval_soft_label(const float* t, int C) {
+    bool has_nan = false;
+    int y = 0;
+    float best = t[0];
+    for (int c = 0; c < C; ++c) {
+        const float v = t[c];
+        has_nan |= v != v;
+        if (v > best) { best = v; y = c; }
+    }
+    return has_nan ? -1 : y;
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void eval_metrics_kernel(HybEvalArgs a, HybLoss l) {
+    static_assert(MODE == HYB_LOSS_OPTS || MODE == HYB_LOSS_FOCAL || MODE == HYB_LOSS_SOFT, "the classification meter's criteria");
+    const HybCeOpts& o = l.o;
     __shared__ double partd[2][256];
     __shared__ int parti[4][256];
     const int C = a.C, V = a.V;
     double num = 0.0, den = 0.0;
     int kept = 0, top1 = 0, topk = 0, nans = 0;
     for (int b = threadIdx.x; b < a.B; b += 256) {
-        const long long t = a.target[b];
+        const float* tl = nullptr;                                              // SOFT: the video's target row
+        long long t;
+        if constexpr (MODE == HYB_LOSS_SOFT) {
+            tl = l.d.target + (long long)b * C;
+            t = eval_soft_label(tl, C);                                         // -1: no label -- kept, wrong, no confusion entry
+        } else t = a.target[b];
         const float* s = a.logits + (long long)b * V * C;                       // V == 1: the scores are the logits
         float term;
         if (V > 1) {
@@ -1178,9 +1219,13 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(HybEvalArgs a, HybCeO
             }
             for (int c = 0; c < C; ++c) sc[c] = sc[c] / (float)V;
             s = sc;
-            term = eval_clip_loss_probs(sc, o.weight, t, C, o);
+            if constexpr (MODE == HYB_LOSS_FOCAL) term = eval_clip_loss_probs_focal(sc, o.weight, t, C, o, l.f.gamma);
+            else if constexpr (MODE == HYB_LOSS_SOFT) term = eval_clip_loss_probs_soft(sc, o.weight, tl, C, o.label_smoothing);
+            else term = eval_clip_loss_probs(sc, o.weight, t, C, o);
         } else {
-            term = ce_clip_loss_opts(s, o.weight, t, C, o);
+            if constexpr (MODE == HYB_LOSS_FOCAL) term = ce_clip_loss_focal(s, o.weight, t, C, o, l.f.gamma);
+            else if constexpr (MODE == HYB_LOSS_SOFT) term = ce_clip_loss_soft(s, o.weight, tl, C, o.label_smoothing);
+            else term = ce_clip_loss_opts(s, o.weight, t, C, o);
             if (a.scores)
                 for (int c = 0; c < C; ++c) a.scores[(long long)b * C + c] = s[c];
         }
@@ -1196,7 +1241,8 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(HybEvalArgs a, HybCeO
         if (a.pred) a.pred[b] = pred;
         if (!ce_keep(t, o)) continue;                                           // ignored: seen, and nothing else
         num += (double)term;
-        den += (double)ce_clip_den(o.weight, t, C, o);
+        if constexpr (MODE == HYB_LOSS_SOFT) den += 1.0;                        // the criterion's divisor is B
+        else den += (double)ce_clip_den(o.weight, t, C, o);
         ++kept;
         if (has_nan) { ++nans; continue; }                                      // wrong for both accuracies, no confusion entry
         if (!(t >= 0 && t < C)) continue;                                       // kept and wrong; the sums went NaN above
@@ -1232,6 +1278,9 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(HybEvalArgs a, HybCeO
 // thread makes the final add.  V == 1: the term is ce_clip_loss_bce itself, the criterion's function.  The score bank is appended without a
 // hand-off: every thread reads the cursor counts[3] before the first barrier, video b owns row cursor + b, and thread 0 moves the cursor
 // after the last barrier, when nobody reads it any more.
+// ONE body for both criteria, templated on the loss mode: HYB_LOSS_BCE (hyb_eval_multilabel) and HYB_LOSS_ASYM (hyb_eval_multilabel_asym,
+// `fo`).  V == 1: ce_clip_loss_asym stands where ce_clip_loss_bce does; V > 1: the asymmetric cell on the mean scores is formed in the
+// class loop that forms them, so neither instantiation walks a row a fourth time.
 struct HybEvalMlArgs {
     const float* logits; const float* target; const float* weight; const float* pos_weight; const float* threshold;
     double* sums; long long* counts; long long* cells; float* bank_scores; unsigned char* bank_labels; long long capacity;
@@ -1243,7 +1292,20 @@ __device__ __forceinline__ float eval_sigmoid(float z) {                        
     return (z >= 0.f ? 1.f : ez) / (1.f + ez);
 }
 __device__ __forceinline__ float eval_log_floor(float l) { return l < -100.f ? -100.f : l; }      // torch's clamp: a NaN passes through
-__global__ __launch_bounds__(256) void eval_multilabel_kernel(HybEvalMlArgs a) {
+// V > 1, asymmetric: ce_asym_factors with p -> s (the mean sigmoid), q -> qb (the mean of sigmoid(-z), its own sum) and the logs floored
+__device__ __forceinline__ void eval_asym_factors(float s, float qb, float t, float w, float pw, const HybCeFocal& fo, float& a, float& e) {
+    const float logp = eval_log_floor(logf(s));
+    const float logn = fo.clip == 0.f ? eval_log_floor(logf(qb)) : logf(fminf(qb + fo.clip, 1.f));
+    const float r = fmaxf(s - fo.clip, 0.f);
+    const float base = fmaf(t, qb, (1.f - t) * r);
+    const float gt = fmaf(fo.gamma, t, fo.gamma_neg * (1.f - t));
+    const float L = fmaf(pw - 1.f, t, 1.f);
+    a = -(w * L);
+    e = ce_pow(base, gt) * fmaf(t, logp, (1.f - t) * logn);
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void eval_multilabel_kernel(HybEvalMlArgs a, HybCeFocal fo) {
+    static_assert(MODE == HYB_LOSS_BCE || MODE == HYB_LOSS_ASYM, "the multi-label meter's criteria");
     __shared__ double partd[256];
     __shared__ int parti[2][256];
     const int C = a.C, V = a.V;
@@ -1266,14 +1328,32 @@ __global__ __launch_bounds__(256) void eval_multilabel_kernel(HybEvalMlArgs a) {
         // video's NaN flag, which every prediction below needs, comes from a pass of loads alone
         bool has_nan = false;
         for (int i = 0; i < V * C; ++i) has_nan |= z[i] != z[i];
-        float term = V == 1 ? ce_clip_loss_bce(z, weight, pos_weight, t, C) : 0.f;
+        float term = 0.f;
+        if (V == 1) {
+            if constexpr (MODE == HYB_LOSS_ASYM) term = ce_clip_loss_asym(z, weight, pos_weight, t, C, fo);
+            else term = ce_clip_loss_bce(z, weight, pos_weight, t, C);
+        }
         const long long r = cursor + b;
         const bool store = bank && r >= 0 && r < a.capacity;                    // nothing at or beyond capacity, whatever the cursor holds
         bool match = !has_nan;
         for (int c = 0; c < C; ++c) {
             float s = eval_sigmoid(z[c]);
             const float tc = t[c];
-            if (V > 1) {
+            if constexpr (MODE == HYB_LOSS_ASYM) {
+                if (V > 1) {
+                    float qb = eval_sigmoid(-z[c]);
+                    for (int v = 1; v < V; ++v) {
+                        const float zv = z[(long long)v * C + c];
+                        s += eval_sigmoid(zv);
+                        qb += eval_sigmoid(-zv);
+                    }
+                    s = s / (float)V;
+                    qb = qb / (float)V;
+                    float fa, fe;
+                    eval_asym_factors(s, qb, tc, ce_w(weight, c), ce_w(pos_weight, c), fo, fa, fe);
+                    term = fmaf(fa, fe, term);
+                }
+            } else if (V > 1) {
                 for (int v = 1; v < V; ++v) s += eval_sigmoid(z[(long long)v * C + c]);
                 s = s / (float)V;
                 term = fmaf(ce_w(weight, c), fmaf(ce_w(pos_weight, c) * tc, -eval_log_floor(logf(s)), (1.f - tc) * -eval_log_floor(log1pf(-s))), term);
@@ -1593,31 +1673,71 @@ extern "C" int hyb_cross_entropy_asym_bwd(const float* logits, const float* targ
     return hyb_loss_bwd(hyb_loss_asym(target, weight, pos_weight, gamma_pos, gamma_neg, clip), logits, dloss, dlogits, B, C, (hipStream_t)stream);
 }
 
-// The classification meter's update (eval_metrics_kernel): one launch of one workgroup that ADDS into sums / counts / confusion.
-extern "C" int hyb_eval_metrics(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
-                                float label_smoothing, int topk, int views, double* sums, long long* counts, long long* confusion,
-                                long long* pred, float* scores, int B, int C, void* stream) {
-    const HybCeOpts o{weight, ignore_index, has_ignore, label_smoothing};
-    HYB_CHECK_ARG(logits && target && sums && counts && B >= 1 && C >= 1 && views >= 1 && topk >= 1 && topk <= C && hyb_ce_opts_ok(o));
+// The classification meter's update (eval_metrics_kernel<mode>): one launch of one workgroup that ADDS into sums / counts / confusion.  The
+// three entry points describe their criterion as a HybLoss (hyb_internal.h) and meet here: one set of checks, hyb_loss_ok included, one launch.
+static int eval_metrics_launch(const HybLoss& l, const float* logits, int topk, int views, double* sums, long long* counts, long long* confusion,
+                               long long* pred, float* scores, int B, int C, void* stream) {
+    HYB_CHECK_ARG(logits && sums && counts && B >= 1 && C >= 1 && views >= 1 && topk >= 1 && topk <= C && hyb_ce_opts_ok(l.o) && hyb_loss_ok(l));
     HYB_CHECK_ARG(views == 1 || scores);
     HYB_CHECK_ARG((long long)B * views <= 0x7fffffffll);
-    const HybEvalArgs a{logits, target, sums, counts, confusion, pred, scores, B, C, views, topk};
-    hipLaunchKernelGGL(eval_metrics_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, o);
+    const HybEvalArgs a{logits, l.target, sums, counts, confusion, pred, scores, B, C, views, topk};
+    switch (l.mode) {
+    case HYB_LOSS_OPTS: hipLaunchKernelGGL(eval_metrics_kernel<HYB_LOSS_OPTS>, dim3(1), dim3(256), 0, (hipStream_t)stream, a, l); break;
+    case HYB_LOSS_FOCAL: hipLaunchKernelGGL(eval_metrics_kernel<HYB_LOSS_FOCAL>, dim3(1), dim3(256), 0, (hipStream_t)stream, a, l); break;
+    case HYB_LOSS_SOFT: hipLaunchKernelGGL(eval_metrics_kernel<HYB_LOSS_SOFT>, dim3(1), dim3(256), 0, (hipStream_t)stream, a, l); break;
+    default: return HYB_E_ARG;
+    }
     HYB_LAUNCH_CHECK();
     return 0;
 }
+extern "C" int hyb_eval_metrics(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                float label_smoothing, int topk, int views, double* sums, long long* counts, long long* confusion,
+                                long long* pred, float* scores, int B, int C, void* stream) {
+    return eval_metrics_launch(hyb_loss_opts(target, weight, ignore_index, has_ignore, label_smoothing), logits, topk, views, sums, counts, confusion,
+                               pred, scores, B, C, stream);
+}
+extern "C" int hyb_eval_metrics_focal(const float* logits, const long long* target, const float* weight, long long ignore_index, int has_ignore,
+                                      float gamma, int topk, int views, double* sums, long long* counts, long long* confusion, long long* pred,
+                                      float* scores, int B, int C, void* stream) {
+    return eval_metrics_launch(hyb_loss_focal(target, weight, ignore_index, has_ignore, gamma), logits, topk, views, sums, counts, confusion, pred,
+                               scores, B, C, stream);
+}
+extern "C" int hyb_eval_metrics_soft(const float* logits, const float* target, const float* weight, float label_smoothing, int topk, int views,
+                                     double* sums, long long* counts, long long* confusion, long long* pred, float* scores, int B, int C,
+                                     void* stream) {
+    return eval_metrics_launch(hyb_loss_dense(target, weight, nullptr, 0, label_smoothing), logits, topk, views, sums, counts, confusion, pred, scores,
+                               B, C, stream);
+}
 
-// The multi-label meter's update (eval_multilabel_kernel): one launch of one workgroup that ADDS into sums / counts / cells and appends to the bank.
+// The multi-label meter's update (eval_multilabel_kernel<mode>): one launch of one workgroup that ADDS into sums / counts / cells and appends
+// to the bank.  Both entry points describe their criterion as a HybLoss and meet here.
+static int eval_multilabel_launch(const HybLoss& l, const float* logits, const float* threshold, int views, double* sums, long long* counts,
+                                  long long* cells, float* bank_scores, unsigned char* bank_labels, long long capacity, unsigned char* pred,
+                                  float* scores, int B, int C, void* stream) {
+    HYB_CHECK_ARG(logits && threshold && sums && counts && cells && scores && B >= 1 && C >= 1 && views >= 1 && capacity >= 0 && hyb_loss_ok(l));
+    HYB_CHECK_ARG((bank_scores != nullptr) == (bank_labels != nullptr) && (!bank_scores || capacity > 0));
+    HYB_CHECK_ARG((long long)B * views <= 0x7fffffffll && (long long)views * C <= 0x7fffffffll);
+    const HybEvalMlArgs a{logits, l.d.target, l.o.weight, l.d.pos_weight, threshold, sums, counts, cells, bank_scores, bank_labels, capacity, pred,
+                          scores, B, C, views};
+    switch (l.mode) {
+    case HYB_LOSS_BCE: hipLaunchKernelGGL(eval_multilabel_kernel<HYB_LOSS_BCE>, dim3(1), dim3(256), 0, (hipStream_t)stream, a, l.f); break;
+    case HYB_LOSS_ASYM: hipLaunchKernelGGL(eval_multilabel_kernel<HYB_LOSS_ASYM>, dim3(1), dim3(256), 0, (hipStream_t)stream, a, l.f); break;
+    default: return HYB_E_ARG;
+    }
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
 extern "C" int hyb_eval_multilabel(const float* logits, const float* target, const float* weight, const float* pos_weight, const float* threshold,
                                    int views, double* sums, long long* counts, long long* cells, float* bank_scores,
                                    unsigned char* bank_labels, long long capacity, unsigned char* pred, float* scores, int B, int C,
                                    void* stream) {
-    HYB_CHECK_ARG(logits && target && threshold && sums && counts && cells && scores && B >= 1 && C >= 1 && views >= 1 && capacity >= 0);
-    HYB_CHECK_ARG((bank_scores != nullptr) == (bank_labels != nullptr) && (!bank_scores || capacity > 0));
-    HYB_CHECK_ARG((long long)B * views <= 0x7fffffffll && (long long)views * C <= 0x7fffffffll);
-    const HybEvalMlArgs a{logits, target, weight, pos_weight, threshold, sums, counts, cells, bank_scores, bank_labels, capacity, pred, scores,
-                          B, C, views};
-    hipLaunchKernelGGL(eval_multilabel_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
-    HYB_LAUNCH_CHECK();
-    return 0;
+    return eval_multilabel_launch(hyb_loss_dense(target, weight, pos_weight, 1, 0.f), logits, threshold, views, sums, counts, cells, bank_scores,
+                                  bank_labels, capacity, pred, scores, B, C, stream);
+}
+extern "C" int hyb_eval_multilabel_asym(const float* logits, const float* target, const float* weight, const float* pos_weight, float gamma_pos,
+                                        float gamma_neg, float clip, const float* threshold, int views, double* sums, long long* counts,
+                                        long long* cells, float* bank_scores, unsigned char* bank_labels, long long capacity,
+                                        unsigned char* pred, float* scores, int B, int C, void* stream) {
+    return eval_multilabel_launch(hyb_loss_asym(target, weight, pos_weight, gamma_pos, gamma_neg, clip), logits, threshold, views, sums, counts, cells,
+                                  bank_scores, bank_labels, capacity, pred, scores, B, C, stream);
 }

@@ -68,6 +68,7 @@ import torch.distributed as dist
 
 from . import ops
 from .meter import MultiLabelMeter
+from .modules import HybridAsymmetricLoss, HybridFocalLoss
 
 
 class GraphedTrainStep:
@@ -539,7 +540,11 @@ class GraphedEval:
     With a ``meter.MultiLabelMeter`` the captured launch is hyb_eval_multilabel and the static ``y`` is fp32 [B, C].  Nothing travels by
     value: the criterion's ``weight`` and ``pos_weight`` buffers and the meter's ``threshold`` buffer are captured by address, so an in-place
     update of any of them reaches the next replay and a REPLACED buffer is refused.  The reset after the warm-up zeroes the bank's cursor
-    too: a freshly built GraphedEval leaves an empty bank, and every replay appends behind the cursor on the device."""
+    too: a freshly built GraphedEval leaves an empty bank, and every replay appends behind the cursor on the device.
+    The other criteria need no further argument: a meter with a HybridFocalLoss captures hyb_eval_metrics_focal, a floating ``y`` [B, C]
+    (soft targets; the static ``y`` is fp32 [B, C]) hyb_eval_metrics_soft, a MultiLabelMeter with a HybridAsymmetricLoss
+    hyb_eval_multilabel_asym.  ``gamma``, ``gamma_pos``, ``gamma_neg``, ``clip`` and ``label_smoothing`` travel by value in the captured launch
+    and a change after capture is refused by name, like ``ignore_index``; the buffers are captured by address as above."""
 
     def __init__(self, model, x, y, meter, mask=None, views=1, warmup=3):
         if not hasattr(model, "evaluate"):
@@ -551,6 +556,8 @@ class GraphedEval:
         self.x = x.detach().float().clone()                   # static inputs
         self._multilabel = isinstance(meter, MultiLabelMeter)
         self.y = y.detach().float().clone() if self._multilabel else y.detach().clone()     # multi-label: the static y is fp32 [B, C]
+        self._soft = not self._multilabel and self.y.is_floating_point()                   # soft targets: the static y is fp32 [B, C] too
+        self._by_name = self._soft or isinstance(meter.criterion, (HybridFocalLoss, HybridAsymmetricLoss))
         self.mask = mask.detach().clone() if mask is not None else None
         self._captured_loss_opts = self._loss_opts_now()
         side = torch.cuda.Stream(device=dev)
@@ -571,14 +578,34 @@ class GraphedEval:
         """What the captured meter launch carries by value or by address: (ignore_index, label_smoothing, the weight buffer's address); with
         a MultiLabelMeter the addresses of the criterion's weight and pos_weight buffers and of the meter's threshold buffer."""
         c = self.meter.criterion
+        if self._by_name:
+            return self._loss_opts_by_name(c)
         if self._multilabel:
             return tuple(None if t is None else t.data_ptr() for t in (*self.meter.loss_options(), self.meter.threshold))
         if c is None:
             return None
         return (c.ignore_index, c.label_smoothing, c.weight.data_ptr() if c.weight is not None else None)
 
+    def _loss_opts_by_name(self, c):
+        """The focal, soft-target and asymmetric launches: ((name, value), ..) of every scalar the captured launch carries by value and of
+        every buffer it reads by address."""
+        def address(t):
+            return None if t is None else t.data_ptr()
+        if self._multilabel:
+            return (("gamma_pos", c.gamma_pos), ("gamma_neg", c.gamma_neg), ("clip", c.clip), ("weight buffer", address(c.weight)),
+                    ("pos_weight buffer", address(c.pos_weight)), ("meter's threshold buffer", address(self.meter.threshold)))
+        if c is None:
+            return ()
+        scalar = ("label_smoothing", c.label_smoothing) if self._soft else ("gamma", c.gamma)
+        return (("ignore_index", c.ignore_index), scalar, ("weight buffer", address(c.weight)))
+
     def _check_loss_opts(self):
         now = self._loss_opts_now()
+        if now != self._captured_loss_opts and self._by_name:
+            what = [n for (n, a), (_, b) in zip(now, self._captured_loss_opts) if a != b] or ["criterion itself"]
+            raise RuntimeError(f"GraphedEval: {', '.join(what)} changed after capture, but the captured meter launch carries the old value (a "
+                               "scalar) or reads the old address (a buffer that was replaced, not updated in place) -- construct a new "
+                               "GraphedEval (an in-place update of a buffer needs none: it is read at replay time)")
         if now != self._captured_loss_opts and self._multilabel:
             what = [n for n, a, b in zip(("criterion's weight buffer", "criterion's pos_weight buffer", "meter's threshold buffer"), now,
                                          self._captured_loss_opts) if a != b]

@@ -7,6 +7,9 @@ include/hybrid_hip.h).  It never synchronises and can be captured into a predict
 once, in ``compute()``.  The loss is the arithmetic of HybridCrossEntropyLoss -- the same device functions, the same class weights,
 ``ignore_index`` and label smoothing -- so a validation loss compares exactly with the training loss.  With ``views = V > 1`` a video's
 score is the mean of the softmax of its V views (temporal clips x spatial crops), the standard multi-view protocol.
+The same holds for every criterion the library trains with: a HybridFocalLoss gives the focal validation loss (``hybrid::eval_metrics_focal_``),
+a floating [B, C] target the soft-target cross-entropy (``hybrid::eval_metrics_soft_``), and MultiLabelMeter takes a HybridAsymmetricLoss
+(``hybrid::eval_multilabel_asym_``).  Each is the same launch with another loss term; everything but the loss sums is computed alike.
 
 Ties are settled by the library's own rule: the prediction is the lowest index among the maxima, and the target's rank counts the classes
 that score higher plus the lower-indexed classes that score the same.
@@ -17,7 +20,7 @@ that score higher plus the lower-indexed classes that score the same.
 import torch
 
 from . import ops
-from .modules import HybridCrossEntropyLoss
+from .modules import HybridAsymmetricLoss, HybridBCEWithLogitsLoss, HybridCrossEntropyLoss, HybridFocalLoss, MixTarget, _gamma, _is_dense
 
 
 class ClassificationMeter:
@@ -26,8 +29,8 @@ class ClassificationMeter:
             raise ValueError(f"num_classes must be an int >= 1, got {num_classes!r}")
         if isinstance(topk, bool) or not isinstance(topk, int) or not 1 <= topk <= num_classes:
             raise ValueError(f"topk must be an int in [1, num_classes = {num_classes}], got {topk!r}")
-        if criterion is not None and not isinstance(criterion, HybridCrossEntropyLoss):
-            raise TypeError(f"criterion must be a HybridCrossEntropyLoss or None, got {type(criterion).__name__}")
+        if criterion is not None and not isinstance(criterion, (HybridCrossEntropyLoss, HybridFocalLoss)):
+            raise TypeError(f"criterion must be a HybridCrossEntropyLoss, a HybridFocalLoss or None, got {type(criterion).__name__}")
         if criterion is not None and criterion.weight is not None and criterion.weight.shape[0] != num_classes:
             raise ValueError(f"the criterion's weight has {criterion.weight.shape[0]} entries but the meter has {num_classes} classes")
         device = torch.device(device)
@@ -45,24 +48,49 @@ class ClassificationMeter:
 
     def loss_options(self):
         """(weight buffer or None, ignore_index, has_ignore, label_smoothing) as the update launch takes them: the weight by address (read
-        when the launch runs), the other two by value."""
+        when the launch runs), the other two by value.  Under a HybridFocalLoss the fourth entry is its gamma."""
         c = self.criterion
         if c is None:
             return None, 0, False, 0.0
+        if isinstance(c, HybridFocalLoss):                                          # (its fourth scalar is gamma: it has no label smoothing)
+            return c.weight, *ops.ignore_args(c.ignore_index), _gamma("gamma", c.gamma)
         return c.weight, 0 if c.ignore_index is None else int(c.ignore_index), c.ignore_index is not None, float(c.label_smoothing)
+
+    def _operator(self, target):
+        """Which update launch this target takes under this criterion, after the refusals the criteria themselves make: a floating [B, C]
+        target is a row of class probabilities per video (None or a HybridCrossEntropyLoss without ignore_index), class indices go to the
+        criterion's own launch.  The scalars are read from the criterion here, at every update, and validated as its own call does."""
+        c = self.criterion
+        if isinstance(target, MixTarget):
+            raise TypeError("ClassificationMeter.update takes class indices int64 [B] or a soft target fp32 [B, C], not a MixTarget: "
+                            "validation batches are not mixed")
+        if _is_dense(target):
+            if isinstance(c, HybridFocalLoss):
+                c._check_target(target)                                            # TypeError: focal takes class indices
+            if c is not None:
+                c._refuse_ignore_index()                                           # ValueError, as the criterion itself
+            weight, _, _, smoothing = self.loss_options()
+            if not 0.0 <= smoothing <= 1.0:
+                raise ValueError(f"label_smoothing must be in [0, 1], got {smoothing}")
+            return torch.ops.hybrid.eval_metrics_soft_, (weight, smoothing)
+        op = torch.ops.hybrid.eval_metrics_focal_ if isinstance(c, HybridFocalLoss) else torch.ops.hybrid.eval_metrics_
+        return op, self.loss_options()
 
     def update(self, logits, target, views=1):
         """Add one batch: logits fp32 [B * views, C] contiguous (the views of one video adjacent: row b * views + v), target int64 [B], both on
         the meter's device.  One launch, no synchronisation.  Returns pred (int64 [B]; -1 for a video whose scores hold a NaN), or
-        (pred, scores) when views > 1 (scores fp32 [B, C]: the mean of the views' softmax)."""
+        (pred, scores) when views > 1 (scores fp32 [B, C]: the mean of the views' softmax).
+        A floating target fp32 [B, C] is a row of class probabilities per video (a teacher's soft targets): the loss is the criterion's
+        soft-target cross-entropy (criterion None or a HybridCrossEntropyLoss; an ``ignore_index`` raises ValueError as the criterion does, a
+        HybridFocalLoss raises TypeError), every video is kept, and its label for the accuracies and the confusion matrix is the lowest
+        index among its row's maxima.  A MixTarget raises TypeError: validation batches are not mixed."""
         if isinstance(views, bool) or not isinstance(views, int) or views < 1:
             raise ValueError(f"views must be an int >= 1, got {views!r}")
+        op, loss_args = self._operator(target)
         ops._require_cuda(logits, target, *self._state())
         if logits.dim() != 2 or logits.shape[1] != self.num_classes:
             raise ValueError(f"expected logits [B * views, {self.num_classes}], got {tuple(logits.shape)}")
-        weight, ignore_index, has_ignore, smoothing = self.loss_options()
-        pred, scores = torch.ops.hybrid.eval_metrics_(logits, target, weight, ignore_index, has_ignore, smoothing, self.topk, views, self.sums,
-                                                      self.counts, self.confusion)
+        pred, scores = op(logits, target, *loss_args, self.topk, views, self.sums, self.counts, self.confusion)
         return (pred, scores) if views > 1 else pred
 
     def reset(self):
@@ -151,17 +179,19 @@ class MultiLabelMeter:
     ``target`` is fp32 [B, C], a label is t >= 0.5; a score is the sigmoid of the logit (the mean over the views' sigmoids with views > 1)
     and a class is predicted when its score reaches its threshold.  ``threshold``: a float or C of them in (0, 1), kept as an fp32 [C]
     device buffer that the launch reads when it runs (an in-place update reaches the next update and the next replay).  ``criterion``: None
-    or a HybridBCEWithLogitsLoss, whose ``weight`` and ``pos_weight`` buffers are read the same way; the loss is that criterion's arithmetic.
+    a HybridBCEWithLogitsLoss or a HybridAsymmetricLoss (``sigmoid_focal(...)`` included), whose ``weight`` and ``pos_weight`` buffers are
+    read the same way; the loss is that criterion's arithmetic.  The asymmetric loss's exponents and ``clip`` are read at every update.
     ``capacity``: the videos whose scores are kept; 0 = no bank and no AP.  Videos beyond it are counted as dropped, and AP is then NaN."""
 
     def __init__(self, num_classes, threshold=0.5, criterion=None, capacity=0, device="cuda"):
-        from .modules import HybridBCEWithLogitsLoss
         if isinstance(num_classes, bool) or not isinstance(num_classes, int) or num_classes < 1:
             raise ValueError(f"num_classes must be an int >= 1, got {num_classes!r}")
         if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0:
             raise ValueError(f"capacity must be an int >= 0, got {capacity!r}")
-        if criterion is not None and not isinstance(criterion, HybridBCEWithLogitsLoss):
-            raise TypeError(f"criterion must be a HybridBCEWithLogitsLoss or None, got {type(criterion).__name__}")
+        if criterion is not None and not isinstance(criterion, (HybridBCEWithLogitsLoss, HybridAsymmetricLoss)):
+            raise TypeError(f"criterion must be a HybridBCEWithLogitsLoss, a HybridAsymmetricLoss or None, got {type(criterion).__name__}")
+        if isinstance(criterion, HybridAsymmetricLoss) and criterion.weight is None and criterion.pos_weight is None:
+            criterion._check_weight(num_classes, torch.device(device))             # sigmoid_focal: its two vectors, now that the class count is known
         for name in ("weight", "pos_weight"):
             v = None if criterion is None else getattr(criterion, name)
             if v is not None and v.shape[0] != num_classes:
@@ -201,10 +231,15 @@ class MultiLabelMeter:
         on the meter's device.  One launch, no synchronisation.  Returns (pred uint8 [B, C], scores fp32 [B, C])."""
         if isinstance(views, bool) or not isinstance(views, int) or views < 1:
             raise ValueError(f"views must be an int >= 1, got {views!r}")
+        # the asymmetric loss's exponents and clip: read from the criterion at every update and validated as its own call validates them
+        scalars = self.criterion._scalars() if isinstance(self.criterion, HybridAsymmetricLoss) else None
         ops._require_cuda(logits, target, *self._state())
         if logits.dim() != 2 or logits.shape[1] != self.num_classes:
             raise ValueError(f"expected logits [B * views, {self.num_classes}], got {tuple(logits.shape)}")
         weight, pos_weight = self.loss_options()
+        if scalars is not None:
+            return torch.ops.hybrid.eval_multilabel_asym_(logits, target, weight, pos_weight, *scalars, self.threshold, views, self.sums,
+                                                          self.counts, self.cells, self.bank_scores, self.bank_labels)
         return torch.ops.hybrid.eval_multilabel_(logits, target, weight, pos_weight, self.threshold, views, self.sums, self.counts, self.cells,
                                                  self.bank_scores, self.bank_labels)
 

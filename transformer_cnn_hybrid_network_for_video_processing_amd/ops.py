@@ -37,6 +37,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::clip_transform_aa    clip_transform_views with the antialiased resize (torchvision's Resize(antialias=True)): a separable triangle filter
     hybrid::eval_metrics_    one launch behind the logits that adds loss, top-1 / top-k, confusion matrix into a meter's state (no autograd formula)
     hybrid::eval_multilabel_ the multi-label twin: BCE loss, per-class tp / fp / fn, exact matches, and the scores appended to a bank for exact mAP
+    hybrid::eval_metrics_focal_, hybrid::eval_metrics_soft_, hybrid::eval_multilabel_asym_   the same launches with the focal, soft-target and asymmetric loss terms
 """
 import ctypes
 import functools
@@ -751,12 +752,20 @@ def cross_entropy_asym(logits, target, weight=None, pos_weight=None, gamma_pos=0
                                                _ce_gamma("gamma_neg", gamma_neg), float(clip))
 
 
-def eval_metrics_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
-                    topk: int, views: int, sums: Tensor, counts: Tensor, confusion: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
-    """The classification meter's update (hyb_eval_metrics): ONE launch that ADDS this batch into sums (float64 [2]: loss numerator and
-    denominator), counts (int64 [5]: videos seen, kept, top-1 correct, top-k correct, NaN rows) and confusion (int64 [C, C], row = target,
-    or None) -> (pred int64 [B], scores fp32 [B, C]: the views' mean softmax, empty [0, C] when views == 1).  logits [B * views, C] fp32
-    contiguous, the views of one video adjacent; the loss options as hybrid::cross_entropy_opts takes them.  Never synchronises."""
+def _eval_dense_target(target, views, logits):
+    """A meter's dense target under _check_dense's rules (fp32, one row of C numbers per video), contiguous: it is read in place."""
+    if target.dtype != torch.float32:
+        raise TypeError(f"a dense target must be float32, got {target.dtype}")
+    if target.dim() != 2 or target.shape[1] != logits.shape[1] or target.shape[0] * views != logits.shape[0]:
+        raise ValueError(f"a dense target has one row per video [B, C] with logits [B * views, C]: got {tuple(target.shape)}, "
+                         f"logits {tuple(logits.shape)}, views {views}")
+    if not target.is_contiguous():
+        raise ValueError("a dense target must be contiguous (it is read in place when the kernels run)")
+
+
+def _eval_metrics(symbol, dense, loss_args, logits, target, topk, views, sums, counts, confusion):
+    """What the classification meter's operators share: the tensor checks, the outputs and the one call.  dense: the target is a fp32 row
+    per video, not a class index; loss_args(C, device) -> the entry point's arguments between the target and topk."""
     _require_cuda(logits, target, sums, counts, confusion)
     if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
         raise ValueError(f"logits must be a contiguous float32 [B * views, C] tensor, got {logits.dtype} {tuple(logits.shape)}"
@@ -764,7 +773,9 @@ def eval_metrics_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ig
     if views < 1:
         raise ValueError(f"views must be >= 1, got {views}")
     C = logits.shape[1]
-    if target.dim() != 1 or target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] * views != logits.shape[0]:
+    if dense:
+        _eval_dense_target(target, views, logits)
+    elif target.dim() != 1 or target.dtype != torch.int64 or not target.is_contiguous() or target.shape[0] * views != logits.shape[0]:
         raise ValueError(f"expected int64 class indices [B] with logits [B * views, C]: got {target.dtype} {tuple(target.shape)}, "
                          f"logits {tuple(logits.shape)}, views {views}")
     B = target.shape[0]
@@ -777,27 +788,58 @@ def eval_metrics_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ig
             raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {logits.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
     if target.device != logits.device:
         raise RuntimeError(f"target is on {target.device} but the logits are on {logits.device}")
-    weight = _ce_weight(weight, C, logits.device)
+    loss_args = loss_args(C, logits.device)
     pred = torch.empty(B, dtype=torch.int64, device=logits.device)
     scores = torch.empty((B if views > 1 else 0, C), dtype=torch.float32, device=logits.device)
-    lib.call("hyb_eval_metrics", logits, target, weight, int(ignore_index), int(has_ignore), float(label_smoothing), int(topk), int(views),
-             sums, counts, confusion, pred, scores if views > 1 else None, B, C, _stream())
+    lib.call(symbol, logits, target, *loss_args, int(topk), int(views), sums, counts, confusion, pred, scores if views > 1 else None, B, C,
+             _stream())
     return pred, scores
 
 
+def eval_metrics_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, label_smoothing: float,
+                    topk: int, views: int, sums: Tensor, counts: Tensor, confusion: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """The classification meter's update (hyb_eval_metrics): ONE launch that ADDS this batch into sums (float64 [2]: loss numerator and
+    denominator), counts (int64 [5]: videos seen, kept, top-1 correct, top-k correct, NaN rows) and confusion (int64 [C, C], row = target,
+    or None) -> (pred int64 [B], scores fp32 [B, C]: the views' mean softmax, empty [0, C] when views == 1).  logits [B * views, C] fp32
+    contiguous, the views of one video adjacent; the loss options as hybrid::cross_entropy_opts takes them.  Never synchronises."""
+    return _eval_metrics("hyb_eval_metrics", False,
+                         lambda C, dev: (_ce_weight(weight, C, dev), int(ignore_index), int(has_ignore), float(label_smoothing)),
+                         logits, target, topk, views, sums, counts, confusion)
+
+
+def eval_metrics_focal_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], ignore_index: int, has_ignore: bool, gamma: float,
+                          topk: int, views: int, sums: Tensor, counts: Tensor, confusion: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """eval_metrics_ with the focal loss's term (hyb_eval_metrics_focal): the options as hybrid::cross_entropy_focal takes them, gamma 0 or
+    >= 1.  Everything but the two loss sums is eval_metrics_'s."""
+    gamma = _ce_gamma("gamma", gamma)
+    return _eval_metrics("hyb_eval_metrics_focal", False, lambda C, dev: (_ce_weight(weight, C, dev), int(ignore_index), int(has_ignore), gamma),
+                         logits, target, topk, views, sums, counts, confusion)
+
+
+def eval_metrics_soft_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], label_smoothing: float, topk: int, views: int,
+                         sums: Tensor, counts: Tensor, confusion: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """eval_metrics_ on soft targets (hyb_eval_metrics_soft): target fp32 [B, C] contiguous, one row of class probabilities per video, the
+    loss hybrid::cross_entropy_dense's kind 0 (every video kept, the denominator counts them); a video's label for the accuracies and the
+    confusion matrix is the lowest index among its row's maxima."""
+    label_smoothing = float(label_smoothing)
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+    return _eval_metrics("hyb_eval_metrics_soft", True, lambda C, dev: (_ce_weight(weight, C, dev), label_smoothing),
+                         logits, target, topk, views, sums, counts, confusion)
+
+
 def eval_metrics_fake(logits, target, weight, ignore_index, has_ignore, label_smoothing, topk, views, sums, counts, confusion):
-    return (target.new_empty(target.shape, dtype=torch.int64),
+    return (target.new_empty(target.shape[:1], dtype=torch.int64),
             logits.new_empty((target.shape[0] if views > 1 else 0, logits.shape[1]), dtype=torch.float32))
 
 
-def eval_multilabel_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], threshold: Tensor, views: int,
-                       sums: Tensor, counts: Tensor, cells: Tensor, bank_scores: Optional[Tensor],
-                       bank_labels: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
-    """The multi-label meter's update (hyb_eval_multilabel): ONE launch that ADDS this batch into sums (float64 [1]: the BCE loss numerator),
-    counts (int64 [5]: videos seen, NaN videos, exact matches, rows stored in the bank, rows dropped) and cells (int64 [C, 3]: tp, fp, fn per
-    class) and appends the scores and labels to the bank (fp32 / uint8 [capacity, C], or both None) behind the cursor counts[3]
-    -> (pred uint8 [B, C], scores fp32 [B, C]: the views' mean sigmoid).  logits [B * views, C] fp32 contiguous, the views of one video
-    adjacent; target fp32 [B, C]; weight / pos_weight [C] or None; threshold fp32 [C].  Never synchronises."""
+def eval_metrics_soft_fake(logits, target, weight, label_smoothing, topk, views, sums, counts, confusion):
+    return eval_metrics_fake(logits, target, weight, 0, False, label_smoothing, topk, views, sums, counts, confusion)
+
+
+def _eval_multilabel(symbol, scalars, logits, target, weight, pos_weight, threshold, views, sums, counts, cells, bank_scores, bank_labels):
+    """What the multi-label meter's operators share: the tensor checks, the outputs and the one call.  scalars: the entry point's arguments
+    between pos_weight and threshold."""
     _require_cuda(logits, target, weight, pos_weight, threshold, sums, counts, cells, bank_scores, bank_labels)
     if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
         raise ValueError(f"logits must be a contiguous float32 [B * views, C] tensor, got {logits.dtype} {tuple(logits.shape)}"
@@ -827,13 +869,42 @@ def eval_multilabel_op(logits: Tensor, target: Tensor, weight: Optional[Tensor],
     weight, pos_weight = _ce_weight(weight, C, logits.device), _ce_weight(pos_weight, C, logits.device)
     pred = torch.empty((B, C), dtype=torch.uint8, device=logits.device)
     scores = torch.empty((B, C), dtype=torch.float32, device=logits.device)
-    lib.call("hyb_eval_multilabel", logits, target, weight, pos_weight, threshold, int(views), sums, counts, cells, bank_scores, bank_labels,
+    lib.call(symbol, logits, target, weight, pos_weight, *scalars, threshold, int(views), sums, counts, cells, bank_scores, bank_labels,
              capacity, pred, scores, B, C, _stream())
     return pred, scores
 
 
+def eval_multilabel_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], threshold: Tensor, views: int,
+                       sums: Tensor, counts: Tensor, cells: Tensor, bank_scores: Optional[Tensor],
+                       bank_labels: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """The multi-label meter's update (hyb_eval_multilabel): ONE launch that ADDS this batch into sums (float64 [1]: the BCE loss numerator),
+    counts (int64 [5]: videos seen, NaN videos, exact matches, rows stored in the bank, rows dropped) and cells (int64 [C, 3]: tp, fp, fn per
+    class) and appends the scores and labels to the bank (fp32 / uint8 [capacity, C], or both None) behind the cursor counts[3]
+    -> (pred uint8 [B, C], scores fp32 [B, C]: the views' mean sigmoid).  logits [B * views, C] fp32 contiguous, the views of one video
+    adjacent; target fp32 [B, C]; weight / pos_weight [C] or None; threshold fp32 [C].  Never synchronises."""
+    return _eval_multilabel("hyb_eval_multilabel", (), logits, target, weight, pos_weight, threshold, views, sums, counts, cells, bank_scores,
+                            bank_labels)
+
+
+def eval_multilabel_asym_op(logits: Tensor, target: Tensor, weight: Optional[Tensor], pos_weight: Optional[Tensor], gamma_pos: float,
+                            gamma_neg: float, clip: float, threshold: Tensor, views: int, sums: Tensor, counts: Tensor, cells: Tensor,
+                            bank_scores: Optional[Tensor], bank_labels: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+    """eval_multilabel_ with the asymmetric loss's term (hyb_eval_multilabel_asym): the scalars as hybrid::cross_entropy_asym takes them, each
+    exponent 0 or >= 1, clip in [0, 1).  Everything but the loss sum is eval_multilabel_'s."""
+    clip = float(clip)
+    if not 0.0 <= clip < 1.0:
+        raise ValueError(f"clip must be in [0, 1), got {clip}")
+    return _eval_multilabel("hyb_eval_multilabel_asym", (_ce_gamma("gamma_pos", gamma_pos), _ce_gamma("gamma_neg", gamma_neg), clip), logits,
+                            target, weight, pos_weight, threshold, views, sums, counts, cells, bank_scores, bank_labels)
+
+
 def eval_multilabel_fake(logits, target, weight, pos_weight, threshold, views, sums, counts, cells, bank_scores, bank_labels):
     return (target.new_empty(target.shape, dtype=torch.uint8), target.new_empty(target.shape, dtype=torch.float32))
+
+
+def eval_multilabel_asym_fake(logits, target, weight, pos_weight, gamma_pos, gamma_neg, clip, threshold, views, sums, counts, cells, bank_scores,
+                              bank_labels):
+    return eval_multilabel_fake(logits, target, weight, pos_weight, threshold, views, sums, counts, cells, bank_scores, bank_labels)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1736,6 +1807,16 @@ _define("eval_multilabel_", "(Tensor logits, Tensor target, Tensor? weight, Tens
         "Tensor(b!) counts, Tensor(c!) cells, Tensor(d!)? bank_scores, Tensor(e!)? bank_labels) -> (Tensor, Tensor)", eval_multilabel_op,
         eval_multilabel_fake)
 _LIB.impl("eval_multilabel_", _inference_only("eval_multilabel_"), "Autograd")
+_define("eval_metrics_focal_", "(Tensor logits, Tensor target, Tensor? weight, int ignore_index, bool has_ignore, float gamma, int topk, int views, "
+        "Tensor(a!) sums, Tensor(b!) counts, Tensor(c!)? confusion) -> (Tensor, Tensor)", eval_metrics_focal_op, eval_metrics_fake)
+_LIB.impl("eval_metrics_focal_", _inference_only("eval_metrics_focal_"), "Autograd")
+_define("eval_metrics_soft_", "(Tensor logits, Tensor target, Tensor? weight, float label_smoothing, int topk, int views, Tensor(a!) sums, "
+        "Tensor(b!) counts, Tensor(c!)? confusion) -> (Tensor, Tensor)", eval_metrics_soft_op, eval_metrics_soft_fake)
+_LIB.impl("eval_metrics_soft_", _inference_only("eval_metrics_soft_"), "Autograd")
+_define("eval_multilabel_asym_", "(Tensor logits, Tensor target, Tensor? weight, Tensor? pos_weight, float gamma_pos, float gamma_neg, float clip, "
+        "Tensor threshold, int views, Tensor(a!) sums, Tensor(b!) counts, Tensor(c!) cells, Tensor(d!)? bank_scores, Tensor(e!)? bank_labels) "
+        "-> (Tensor, Tensor)", eval_multilabel_asym_op, eval_multilabel_asym_fake)
+_LIB.impl("eval_multilabel_asym_", _inference_only("eval_multilabel_asym_"), "Autograd")
 _define("backbone", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, bool training, "
         "float momentum, float eps, int dt) -> Tensor[]", backbone_op, backbone_fake,
         lambda x, ws, gs, bs, rms, rvs, training, momentum, eps, dt: list(_BackboneFn.apply(x, len(ws), training, momentum, eps, dt, *ws, *gs, *bs,
