@@ -1053,6 +1053,41 @@ int hyb_adamw_hyper_set_groups(double* hyper /* [groups, 6] */, double* ema_hype
                                const unsigned char* group, const double* values /* [count, 6] */, int ema_count,
                                const unsigned char* ema_group, const double* ema_values /* [ema_count, 2] */, void* stream);
 
+/* ---- LAMB: layer-wise trust ratios in the fused step (You et al. 2020; timm's Lamb, apex FusedLAMB without nvlamb) -------------------------
+ * (New symbols only; hyb_abi_version() stays 9.)  Per tensor, at applied step t, with G the effective gradient exactly as the AdamW launch
+ * forms it (acc / grads / k as in hyb_adamw_step_dev_acc, times clip[1] when clip is given):
+ *     m' = m + (1 - b1)(G - m)      v' = b2 v + (1 - b2) G^2                                      (the step's own expressions)
+ *     q  = (m' / (1 - b1^t)) / (sqrt(v') / sqrt(1 - b2^t) + eps)        u = q + wd p
+ *     r  = |p| / |u|  if (wd != 0 or always_adapt) and |p| > 0 and |u| > 0, else 1                 (L2 norms over the tensor)
+ *     p <- p - lr r u
+ * which is the AdamW step of that tensor at the rate r lr: one read-only pass forms the ratios, then the AdamW launch runs with them.
+ *
+ * hyb_lamb_trust: the pass.  The table, group / groups / hyper, k, step, step_inc, clip and guard are those of the hyb_lamb_step_dev call
+ * that follows (grads / acc / group / clip / guard may be NULL as there; group == NULL: hyper is the one row).  It stores nothing to
+ * params, the moments or acc.  fp32 per element, contraction off:
+ *     u = fmaf((float)wd, p, (float)(1 / (1 - b1^t)) * (m' / fmaf(sqrtf(v'), (float)(1 / sqrt(1 - b2^t)), (float)eps)))
+ * then p^2 and u^2 summed like hyb_grad_norm sums g^2 -- 4096-element chunks in a fixed order, two fp32 partials per chunk, a tensor's
+ * partials in double in a fixed order by a second launch (one workgroup per tensor) -- so the ratios are bit-identical from run to run.
+ * trust_out: DEVICE float [count, 3], row i = {|p_i|, |u_i|, r_i} over the WHOLE table (more than 80 tensors, 72 with acc: more launches);
+ * r = (float)((double)|p| / (double)|u|).  wd is read from the tensor's row of hyper when the launch runs, always_adapt (0 or 1) travels by
+ * value.  With guard, the step number is less skipped_total as in the guarded step; on a skipped step trust_out is unspecified (and unread).
+ * partials: hyb_lamb_trust_workspace(count, numel) floats (2 per chunk; 0 for bad arguments), no state kept in it between calls.
+ * 4 x 4 bytes read per parameter, 5 x 4 with acc and grads. */
+size_t hyb_lamb_trust_workspace(int count, const long long* numel);
+int hyb_lamb_trust(int count, float* const* params, const float* const* grads /* or NULL */, float* const* exp_avg, float* const* exp_avg_sq,
+                   float* const* acc /* or NULL */, const long long* numel, const unsigned char* group /* or NULL */, int groups,
+                   const double* hyper, long long k, long long step, long long* step_inc, const float* clip /* or NULL */,
+                   const long long* guard /* [2], or NULL */, int always_adapt, float* partials, float* trust_out /* [count, 3] */, void* stream);
+/* hyb_lamb_step_dev: hyb_adamw_step_dev_groups -- every variant behind it, the average, accumulation, the guard, the advancing counter -- in
+ * which thread 0 of a workgroup forms its tensor's decay and step size from r lr, r = trust[3 i + 2], in double, rounded once: r == 1 gives
+ * the AdamW step bit for bit.  group may be NULL here (hyper / ema_hyper are then the one group's rows, groups is not read).  trust: the
+ * trust_out of the hyb_lamb_trust call of this step (never NULL); on a guarded skip it is not read. */
+int hyb_lamb_step_dev(int count, float* const* params, const float* const* grads /* or NULL */, float* const* exp_avg,
+                      float* const* exp_avg_sq, float* const* acc /* or NULL */, float* const* ema /* or NULL */, const long long* numel,
+                      const unsigned char* group /* or NULL */, int groups, const double* hyper, const double* ema_hyper /* or NULL */,
+                      long long k, long long step, long long* step_inc, unsigned int* advance_ticket, const float* clip /* or NULL */,
+                      const long long* guard /* [2], or NULL */, const float* trust /* [count, 3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@
 // Parameter groups: hyb_adamw_step_dev_groups serves the tensors of ALL groups from one launch -- the table carries one byte per tensor, its
 // group, and thread 0 of a workgroup forms its scalars from that group's row of the device blocks hyper[groups, 6] / ema_hyper[groups, 2];
 // hyb_adamw_hyper_set_groups writes the rows of several groups in one launch.
+// LAMB: hyb_lamb_trust forms every tensor's trust ratio r = |p| / |u| on the device (a read-only chunk pass and a one-workgroup-per-tensor
+// final launch, 4 x 4 bytes read per parameter), hyb_lamb_step_dev is the AdamW launch at the rate r * lr per tensor (LAMB, below).
 #include <algorithm>
 #include <type_traits>
 
@@ -377,9 +379,11 @@ template <bool ACCUM, typename Args> __device__ __forceinline__ long long adam_s
 }
 
 // (hyper: the six values of the tensor's parameter group -- a.hyper itself, or in a grouped launch the group's row of the block)
-template <bool ACCUM = false, typename Args> __device__ __forceinline__ void adam_dev_scalars(const Args& a, const double* hyper, float* out /* [8] */, long long skipped = 0ll) {
+// LAMB: the tensor's trust ratio r scales the rate -- decay and step_size are formed from r * lr, still in double and rounded once; every
+// other instantiation reads hyper[0] as it always did (r is not looked at), and r == 1.0 gives AdamW's doubles.
+template <bool ACCUM = false, bool LAMB = false, typename Args> __device__ __forceinline__ void adam_dev_scalars(const Args& a, const double* hyper, float* out /* [8] */, long long skipped = 0ll, double r = 1.0) {
 #pragma clang fp contract(off)                                    // 1.0 - lr * wd: a product rounded, then a difference, as on the host (no fma)
-    const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
+    const double lr = LAMB ? r * hyper[0] : hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
     const double tt = (double)adam_step_number<ACCUM>(a, skipped);
     const double prod = lr * wd;
     out[0] = (float)(1.0 - prod);
@@ -409,8 +413,19 @@ template <bool ACCUM = false, typename Args> __device__ __forceinline__ void ada
 
 template <bool EMA, int ACC> using AdamDevTableArgs =
     std::conditional_t<ACC != GRAD_PLAIN, std::conditional_t<EMA, AdamEmaAccArgs, AdamAccArgs>, std::conditional_t<EMA, AdamEmaArgs, AdamDevArgs>>;
-template <bool EMA, int ACC, bool GUARD = false, bool GROUPS = false> using AdamDevKernelArgs =
+template <bool EMA, int ACC, bool GUARD = false, bool GROUPS = false> using AdamwDevKernelArgs =
     std::conditional_t<GROUPS, AdamGroupArgs<EMA, ACC != GRAD_PLAIN>, std::conditional_t<GUARD, AdamGuarded<AdamDevTableArgs<EMA, ACC>>, AdamDevTableArgs<EMA, ACC>>>;
+// The LAMB launches (hyb_lamb_step_dev): any of the tables above with the trust block of hyb_lamb_trust -- float [3] per tensor of the WHOLE
+// call, {|p|, |u|, r} -- and the index of the slice's first tensor in it.  Types of their own once more: every table above stays as it is.
+template <typename Base> struct AdamLamb : Base { const float* trust; int first; };
+static_assert(sizeof(AdamLamb<AdamDevArgs>) <= 4096 && sizeof(AdamLamb<AdamEmaArgs>) <= 4096 && sizeof(AdamLamb<AdamAccArgs>) <= 4096 &&
+              sizeof(AdamLamb<AdamEmaAccArgs>) <= 4096 && sizeof(AdamLamb<AdamGuarded<AdamDevArgs>>) <= 4096 && sizeof(AdamLamb<AdamGuarded<AdamEmaArgs>>) <= 4096 &&
+              sizeof(AdamLamb<AdamGuarded<AdamAccArgs>>) <= 4096 && sizeof(AdamLamb<AdamGuarded<AdamEmaAccArgs>>) <= 4096 &&
+              sizeof(AdamLamb<AdamGroupArgs<false, false>>) <= 4096 && sizeof(AdamLamb<AdamGroupArgs<true, false>>) <= 4096 &&
+              sizeof(AdamLamb<AdamGroupArgs<false, true>>) <= 4096 && sizeof(AdamLamb<AdamGroupArgs<true, true>>) <= 4096,
+              "the tensor table travels in the kernel arguments");
+template <bool EMA, int ACC, bool GUARD = false, bool GROUPS = false, bool LAMB = false> using AdamDevKernelArgs =
+    std::conditional_t<LAMB, AdamLamb<AdamwDevKernelArgs<EMA, ACC, GUARD, GROUPS>>, AdamwDevKernelArgs<EMA, ACC, GUARD, GROUPS>>;
 
 // the counter's one read (thread 0, in front of the barrier) is complete in every workgroup that has taken a ticket: see adamw_kernel
 template <typename Args> __device__ __forceinline__ void adam_dev_advance(const Args& a) {
@@ -434,8 +449,12 @@ template <typename Args> __device__ __forceinline__ void adam_dev_advance(const 
 // GROUPS: hyb_adamw_step_dev_groups -- the table holds the tensors of several parameter groups, and thread 0 reads the hyper-parameters from
 // the row of ITS tensor's group (a.group[ti]) where the other launches read the one row they were given.  Nothing else differs: every
 // element comes out as the launch over its group alone gives it.
-template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false, bool GROUPS = false> __global__ __launch_bounds__(256)
-void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS> a) {
+// LAMB: hyb_lamb_step_dev -- thread 0 also reads its tensor's trust ratio r = trust[3 (first + ti) + 2], which hyb_lamb_trust has formed for
+// this very step, and forms decay and step_size from r * lr (adam_dev_scalars): p - lr r u = p (1 - (r lr) wd) - (r lr / (1 - b1^t)) m' /
+// (sqrt(v') / sqrt(1 - b2^t) + eps), so the element loop is AdamW's, and r == 1.0f gives AdamW's step bit for bit.  On a guarded skip the trust
+// block is not read.
+template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false, bool GROUPS = false, bool LAMB = false> __global__ __launch_bounds__(256)
+void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS, LAMB> a) {
     constexpr bool ACCUM = ACC != GRAD_PLAIN, HAS_G = ACC != GRAD_ACC;
     __shared__ float s_sc[EMA ? 10 : 8];
     __shared__ int s_skip;
@@ -471,7 +490,8 @@ void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS> a) {
         if (!skip) {
             const double* hyper = a.hyper;
             if constexpr (GROUPS) hyper += HYPER_N * (int)a.group[ti];
-            adam_dev_scalars<ACCUM>(a, hyper, s_sc, skipped);
+            if constexpr (LAMB) adam_dev_scalars<ACCUM, true>(a, hyper, s_sc, skipped, (double)a.trust[3ll * (a.first + ti) + 2]);
+            else adam_dev_scalars<ACCUM>(a, hyper, s_sc, skipped);
             if constexpr (EMA) {
                 const double* ema_hyper = a.ema_hyper;
                 if constexpr (GROUPS) ema_hyper += 2 * (int)a.group[ti];
@@ -549,6 +569,151 @@ void adamw_dev_kernel(AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS> a) {
         }
     }
     adam_dev_advance(a);
+}
+
+// ---- LAMB: layer-wise trust ratios (hyb_lamb_trust / hyb_lamb_step_dev; You et al. 2020, as timm's Lamb and apex's FusedLAMB without nvlamb) ------
+// Per tensor r = |p| / |u| with u = q + wd p, q the bias-corrected Adam direction of THIS step, so the ratio needs m' and v' before the step
+// stores them.  lamb_trust_kernel is a read-only chunk pass that forms them exactly as the step will -- the scalars of adam_dev_scalars at
+// the same step number, the expressions of adam_dev_one -- and then, in fp32 with contraction off,
+//     q = m' / fmaf(sqrtf(v'), inv_sqrt_bc2, eps)            (adam_dev_one's q)
+//     u = fmaf(wd32, p, inv_bc1 * q)                          wd32 = (float)wd, inv_bc1 = (float)(1.0 / (1.0 - pow(b1, t))), both rounded once
+// and sums p^2 and u^2 as grad_chunk_sumsq sums g^2: a thread's 16 elements in index order with fmaf (the mapping of adamw_dev_kernel, whether
+// the tensor is 16-byte aligned or not), wave_sum, the four wave totals pairwise -> partials[2 chunk], partials[2 chunk + 1].  That form of u
+// is the contract: the ratios are bit-identical from run to run and independent of how the table is cut into launches.
+// lamb_trust_final_kernel, one workgroup per tensor in a launch of its own (the hand-off: see the note on grad_norm above), adds the
+// tensor's partials in double in grad_norm_finish's order and writes trust_out[i] = {|p|, |u|, r}.  No floating-point atomics anywhere.
+template <bool ACCUM> struct LambTrustArgs : AdamDevTable<ACCUM ? 72 : ADAM_MAX> {      // (advance and ticket stay NULL: nothing is stepped)
+    static constexpr int MAX = ACCUM ? 72 : ADAM_MAX;
+    unsigned char group[MAX];
+    const float* acc[ACCUM ? MAX : 1];
+    long long k;
+    float inv_k;
+    const long long* guard;      // NULL, or the guard block: the step number is less skipped_total, as in the guarded step
+    int chunk_offset;            // index of this launch's first chunk among all chunks of the call
+    float* partials;
+};
+static_assert(sizeof(LambTrustArgs<false>) <= 4096 && sizeof(LambTrustArgs<true>) <= 4096, "the tensor table travels in the kernel arguments");
+
+__device__ __forceinline__ void lamb_trust_one(float p, float g, float m, float v, const AdamScalars& a, float inv_bc1, float wd32, float& sp, float& su) {
+#pragma clang fp contract(off)
+    g = g * a.clip;
+    m = __builtin_fmaf(a.omb1, g - m, m);
+    v = __builtin_fmaf(a.beta2, v, (a.omb2 * g) * g);
+    const float q = m / __builtin_fmaf(sqrtf(v), a.inv_sqrt_bc2, a.eps);
+    const float u = __builtin_fmaf(wd32, p, inv_bc1 * q);
+    sp = __builtin_fmaf(p, p, sp);
+    su = __builtin_fmaf(u, u, su);
+}
+
+template <int ACC, bool GROUPS> __global__ __launch_bounds__(256) void lamb_trust_kernel(LambTrustArgs<ACC != GRAD_PLAIN> a) {
+    constexpr bool ACCUM = ACC != GRAD_PLAIN, HAS_G = ACC != GRAD_ACC;
+    __shared__ float s_sc[10];
+    __shared__ float s_wave[8];
+    __shared__ int s_skip;
+    int ti = 0;
+    for (int i = 1; i < a.count; ++i)
+        if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
+    const AdamTensor t = a.t[ti];
+    const float* ta = nullptr;
+    float inv_k = 1.f;
+    if constexpr (ACCUM) { ta = a.acc[ti]; inv_k = a.inv_k; }
+    const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
+    const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v | (uintptr_t)ta) & 15) == 0);
+    constexpr int NK = ADAM_CHUNK / (256 * 4);
+    const bool full = vec && base + ADAM_CHUNK <= t.n;            // as in adamw_dev_kernel: a full chunk's loads go out before the scalar work
+    f32x4 p[NK], m[NK], v[NK], g[HAS_G ? NK : 1], ac[ACCUM ? NK : 1];
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            p[k] = *reinterpret_cast<const f32x4*>(t.p + i); m[k] = *reinterpret_cast<const f32x4*>(t.m + i);
+            v[k] = *reinterpret_cast<const f32x4*>(t.v + i);
+            if constexpr (HAS_G) g[k] = *reinterpret_cast<const f32x4*>(t.g + i);
+            if constexpr (ACCUM) ac[k] = *reinterpret_cast<const f32x4*>(ta + i);
+        }
+    }
+    if (threadIdx.x == 0) {
+        long long skipped = 0ll;
+        bool skip = false;
+        if (a.guard) { skip = a.guard[0] != 0ll; skipped = a.guard[1]; }
+        s_skip = skip ? 1 : 0;
+        if (!skip) {
+#pragma clang fp contract(off)
+            const double* hyper = a.hyper;
+            if constexpr (GROUPS) hyper += HYPER_N * (int)a.group[ti];
+            adam_dev_scalars<ACCUM>(a, hyper, s_sc, skipped);
+            s_sc[8] = (float)(1.0 / (1.0 - pow(hyper[1], (double)adam_step_number<ACCUM>(a, skipped))));
+            s_sc[9] = (float)hyper[4];
+        }
+    }
+    __syncthreads();
+    float* out = a.partials + 2ll * (a.chunk_offset + (int)blockIdx.x);
+    if (s_skip) {                                                  // a skipped step reads no trust value: zeros (r = 1), and no pass over poison
+        if (threadIdx.x == 0) { out[0] = 0.f; out[1] = 0.f; }
+        return;
+    }
+    const AdamScalars sc{s_sc[0], s_sc[1], s_sc[2], s_sc[3], s_sc[4], s_sc[5], s_sc[6], s_sc[7]};
+    const float inv_bc1 = s_sc[8], wd32 = s_sc[9];
+    float sp = 0.f, su = 0.f;
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                lamb_trust_one(p[k][j], eff_grad<ACC>(ACCUM ? ac[k][j] : 0.f, HAS_G ? g[k][j] : 0.f, inv_k), m[k][j], v[k][j], sc, inv_bc1, wd32, sp, su);
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            for (long long e = i; e < i + 4 && e < t.n; ++e)
+                lamb_trust_one(t.p[e], eff_grad<ACC>(ACCUM ? ta[e] : 0.f, HAS_G ? t.g[e] : 0.f, inv_k), t.m[e], t.v[e], sc, inv_bc1, wd32, sp, su);
+        }
+    }
+    sp = wave_sum(sp);
+    su = wave_sum(su);
+    if ((threadIdx.x & 63) == 0) { s_wave[threadIdx.x >> 6] = sp; s_wave[4 + (threadIdx.x >> 6)] = su; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[0] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+        out[1] = (s_wave[4] + s_wave[5]) + (s_wave[6] + s_wave[7]);
+    }
+}
+
+// The final launch serves up to 760 tensors: an int and a byte per tensor in the kernel arguments.
+constexpr int LAMB_FINAL_MAX = 760;
+struct LambFinalArgs {
+    int chunk_begin[LAMB_FINAL_MAX + 1];      // tensor first + i owns the chunks chunk_begin[i] .. chunk_begin[i + 1] of the whole call
+    unsigned char group[LAMB_FINAL_MAX];      // its row of hyper (all zero: hyper is the one row)
+    int first;
+    int always_adapt;
+    const float* partials;
+    const double* hyper;
+    float* trust_out;
+};
+static_assert(sizeof(LambFinalArgs) <= 4096, "the tensor table travels in the kernel arguments");
+
+__global__ __launch_bounds__(256) void lamb_trust_final_kernel(LambFinalArgs a) {
+    __shared__ double s_sum[2][256];
+    const int c0 = a.chunk_begin[blockIdx.x], c1 = a.chunk_begin[blockIdx.x + 1];
+    double sp = 0.0, su = 0.0;
+    for (int c = c0 + (int)threadIdx.x; c < c1; c += 256) {         // thread t takes t, t + 256, ... ascending
+        sp += (double)a.partials[2ll * c];
+        su += (double)a.partials[2ll * c + 1];
+    }
+    s_sum[0][threadIdx.x] = sp;
+    s_sum[1][threadIdx.x] = su;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tp = 0.0, tu = 0.0;
+        for (int i = 0; i < 256; ++i) { tp += s_sum[0][i]; tu += s_sum[1][i]; }      // the 256 thread sums in ascending order
+        const float w_norm = (float)sqrt(tp), u_norm = (float)sqrt(tu);
+        const double wd = a.hyper[HYPER_N * (int)a.group[blockIdx.x] + 4];
+        const bool adapt = (wd != 0.0 || a.always_adapt != 0) && w_norm > 0.f && u_norm > 0.f;
+        float* out = a.trust_out + 3ll * (a.first + (int)blockIdx.x);
+        out[0] = w_norm;
+        out[1] = u_norm;
+        out[2] = adapt ? (float)((double)w_norm / (double)u_norm) : 1.0f;
+    }
 }
 
 __global__ __launch_bounds__(64) void ema_set_kernel(double* ema_hyper, double decay, double warmup) {
@@ -666,12 +831,14 @@ struct AdamStep {
     const double* hyper; const double* ema_hyper;
     long long k, step; long long* step_inc; unsigned int* ticket;
     const float* clip; const long long* guard;
+    const float* trust;          // NULL: AdamW.  The trust block of hyb_lamb_trust, float [count, 3]: the LAMB step (hyb_lamb_step_dev)
 };
 
 // the one rule; an entry point adds only what its own prototype promises (hyb_adamw_step_dev: grads, ...)
 bool adam_step_ok(const AdamStep& s) {
     if (!table_ok(s.count, s.numel, s.params, s.exp_avg, s.exp_avg_sq) || !s.hyper || s.step < 1 || s.k < 1 || !(s.acc || (s.k == 1 && s.grads)) ||
-        (s.ema != nullptr) != (s.ema_hyper != nullptr) || (s.ticket && !s.step_inc) || (s.guard && !s.clip)) return false;
+        (s.ema != nullptr) != (s.ema_hyper != nullptr) || (s.ticket && !s.step_inc) || (s.guard && !s.clip) ||
+        (s.group && (s.groups < 1 || s.groups > ADAM_GROUPS_MAX))) return false;     // (the LAMB calls take group or NULL: the range is the rule's)
     for (int i = 0; i < s.count; ++i)
         if ((s.grads && !s.grads[i]) || (s.acc && (!s.acc[i] || s.acc[i] == s.params[i])) || (s.ema && (!s.ema[i] || s.ema[i] == s.params[i])) ||
             (s.group && (int)s.group[i] >= s.groups)) return false;
@@ -679,8 +846,8 @@ bool adam_step_ok(const AdamStep& s) {
 }
 
 // one instantiation of adamw_dev_kernel over the whole table; the last launch of the call advances the counter
-template <bool EMA, int ACC, bool GUARD, bool GROUPS> int adamw_dev_launch(const AdamStep& s, void* stream) {
-    using Args = AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS>;
+template <bool EMA, int ACC, bool GUARD, bool GROUPS, bool LAMB> int adamw_dev_launch(const AdamStep& s, void* stream) {
+    using Args = AdamDevKernelArgs<EMA, ACC, GUARD, GROUPS, LAMB>;
     return for_each_slice(s.count, s.numel, (int)(sizeof(Args::t) / sizeof(AdamTensor)), [&](int first, int n, const int* chunk_begin, bool last) {
         Args a{};
         for (int i = 0; i < n; ++i) {
@@ -695,26 +862,78 @@ template <bool EMA, int ACC, bool GUARD, bool GROUPS> int adamw_dev_launch(const
         if constexpr (EMA) a.ema_hyper = s.ema_hyper;
         if constexpr (ACC != GRAD_PLAIN) { a.k = s.k; a.inv_k = (float)(1.0 / (double)s.k); }
         if constexpr (GUARD) a.guard = s.guard;
+        if constexpr (LAMB) { a.trust = s.trust; a.first = first; }
         a.advance = (s.ticket && last) ? s.step_inc : nullptr;
         a.ticket = s.ticket;
-        return launch_chunks(adamw_dev_kernel<EMA, ACC, GUARD, GROUPS>, a, stream);
+        return launch_chunks(adamw_dev_kernel<EMA, ACC, GUARD, GROUPS, LAMB>, a, stream);
     });
 }
 
-// (ema, acc and grads, guard, group) given or not -> the 2 x 3 x 2 x 2 instantiations
+// (ema, acc and grads, guard, group, trust) given or not -> the 2 x 3 x 2 x 2 x 2 instantiations
 template <typename F> int with_flag(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
 int adam_step_launch(const AdamStep& s, void* stream) {
     return with_flag(s.ema != nullptr, [&](auto ema) { return with_flag(s.guard != nullptr, [&](auto guard) { return with_flag(s.group != nullptr, [&](auto groups) {
-        constexpr bool EMA = decltype(ema)::value, GUARD = decltype(guard)::value, GROUPS = decltype(groups)::value;
-        if (!s.acc) return adamw_dev_launch<EMA, GRAD_PLAIN, GUARD, GROUPS>(s, stream);
-        if (s.grads) return adamw_dev_launch<EMA, GRAD_ACC_G, GUARD, GROUPS>(s, stream);
-        return adamw_dev_launch<EMA, GRAD_ACC, GUARD, GROUPS>(s, stream);
+        return with_flag(s.trust != nullptr, [&](auto lamb) {
+            constexpr bool EMA = decltype(ema)::value, GUARD = decltype(guard)::value, GROUPS = decltype(groups)::value, LAMB = decltype(lamb)::value;
+            if (!s.acc) return adamw_dev_launch<EMA, GRAD_PLAIN, GUARD, GROUPS, LAMB>(s, stream);
+            if (s.grads) return adamw_dev_launch<EMA, GRAD_ACC_G, GUARD, GROUPS, LAMB>(s, stream);
+            return adamw_dev_launch<EMA, GRAD_ACC, GUARD, GROUPS, LAMB>(s, stream);
+        });
     }); }); });
 }
 
 int adam_step(const AdamStep& s, void* stream) {
     HYB_CHECK_ARG(adam_step_ok(s));
     return adam_step_launch(s, stream);
+}
+
+// The trust pass of the step that `s` describes (no average, no ticket: nothing is stepped): the chunk launches over the table in slices,
+// then the final launches, one workgroup per tensor.
+template <int ACC, bool GROUPS> int lamb_trust_launch(const AdamStep& s, int always_adapt, float* partials, float* trust_out, void* stream) {
+    using Args = LambTrustArgs<ACC != GRAD_PLAIN>;
+    int total = 0;
+    const int rc = for_each_slice(s.count, s.numel, Args::MAX, [&](int first, int n, const int* chunk_begin, bool) {
+        Args a{};
+        for (int i = 0; i < n; ++i) {
+            a.t[i] = AdamTensor{s.params[first + i], ACC == GRAD_ACC ? nullptr : s.grads[first + i], s.exp_avg[first + i], s.exp_avg_sq[first + i], s.numel[first + i]};
+            if constexpr (ACC != GRAD_PLAIN) a.acc[i] = s.acc[first + i];
+            if constexpr (GROUPS) a.group[i] = s.group[first + i];
+        }
+        std::copy(chunk_begin, chunk_begin + n + 1, a.chunk_begin);
+        a.count = n;
+        a.hyper = s.hyper; a.step_inc = s.step_inc; a.step = s.step; a.clip = s.clip;
+        a.k = s.k; a.inv_k = (float)(1.0 / (double)s.k);
+        a.guard = s.guard;
+        a.chunk_offset = total;
+        a.partials = partials;
+        total += chunk_begin[n];
+        return launch_chunks(lamb_trust_kernel<ACC, GROUPS>, a, stream);
+    });
+    if (rc != 0) return rc;
+    for (int first = 0, chunk = 0; first < s.count; first += LAMB_FINAL_MAX) {
+        LambFinalArgs f{};
+        const int n = s.count - first < LAMB_FINAL_MAX ? s.count - first : LAMB_FINAL_MAX;
+        for (int i = 0; i < n; ++i) {
+            f.chunk_begin[i] = chunk;
+            chunk += hyb_cdiv(s.numel[first + i], ADAM_CHUNK);
+            if constexpr (GROUPS) f.group[i] = s.group[first + i];
+        }
+        f.chunk_begin[n] = chunk;
+        f.first = first; f.always_adapt = always_adapt; f.partials = partials; f.hyper = s.hyper; f.trust_out = trust_out;
+        hipLaunchKernelGGL(lamb_trust_final_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, f);
+        HYB_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+int lamb_trust_call(const AdamStep& s, int always_adapt, float* partials, float* trust_out, void* stream) {
+    HYB_CHECK_ARG(adam_step_ok(s) && !s.ema && !s.ticket && (always_adapt == 0 || always_adapt == 1) && partials && trust_out);
+    return with_flag(s.group != nullptr, [&](auto groups) {
+        constexpr bool GROUPS = decltype(groups)::value;
+        if (!s.acc) return lamb_trust_launch<GRAD_PLAIN, GROUPS>(s, always_adapt, partials, trust_out, stream);
+        if (s.grads) return lamb_trust_launch<GRAD_ACC_G, GROUPS>(s, always_adapt, partials, trust_out, stream);
+        return lamb_trust_launch<GRAD_ACC, GROUPS>(s, always_adapt, partials, trust_out, stream);
+    });
 }
 
 // The four norm entry points: acc == NULL is the plain norm of grads (k == 1), acc given the norm of (acc + grads) / k, or of acc / k without
@@ -858,6 +1077,25 @@ extern "C" int hyb_adamw_step_dev_groups(int count, float* const* params, const 
                                          unsigned int* advance_ticket, const float* clip, const long long* guard, void* stream) {
     HYB_CHECK_ARG(group && groups >= 1 && groups <= ADAM_GROUPS_MAX);
     return adam_step({count, params, grads, exp_avg, exp_avg_sq, acc, ema, numel, group, groups, hyper, ema_hyper, k, step, step_inc, advance_ticket, clip, guard}, stream);
+}
+
+// ---- LAMB: the trust pass, then the step that reads it -- the same descriptor, group or not ---------------------------------------------------
+extern "C" size_t hyb_lamb_trust_workspace(int count, const long long* numel) { return 2 * hyb_grad_norm_workspace(count, numel); }
+
+extern "C" int hyb_lamb_trust(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                              float* const* acc, const long long* numel, const unsigned char* group, int groups, const double* hyper, long long k,
+                              long long step, long long* step_inc, const float* clip, const long long* guard, int always_adapt, float* partials,
+                              float* trust_out, void* stream) {
+    return lamb_trust_call({count, params, grads, exp_avg, exp_avg_sq, acc, nullptr, numel, group, groups, hyper, nullptr, k, step, step_inc, nullptr, clip, guard, nullptr},
+                           always_adapt, partials, trust_out, stream);
+}
+
+extern "C" int hyb_lamb_step_dev(int count, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                 float* const* acc, float* const* ema, const long long* numel, const unsigned char* group, int groups,
+                                 const double* hyper, const double* ema_hyper, long long k, long long step, long long* step_inc,
+                                 unsigned int* advance_ticket, const float* clip, const long long* guard, const float* trust, void* stream) {
+    HYB_CHECK_ARG(trust);
+    return adam_step({count, params, grads, exp_avg, exp_avg_sq, acc, ema, numel, group, groups, hyper, ema_hyper, k, step, step_inc, advance_ticket, clip, guard, trust}, stream);
 }
 
 // ---- the uploads of the device blocks -----------------------------------------------------------------------------------------------------------

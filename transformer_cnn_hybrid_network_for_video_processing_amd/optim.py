@@ -45,7 +45,10 @@ How a step is put together.  `_plan` decides once per call which groups are live
 launch unit is a `_Unit` record -- the pointer tables of its tensors, built (and cached while no tensor moves) by `_unit`, the one builder
 behind `step()`, `accumulate()` and GraphedTrainStep's eager accumulate.  `step()` is then `_prepare` (state, tables, step numbers),
 `_norm` (one call, named by `_norm_symbol`) and `_launch` (one call per unit: `_step_symbol` names the entry point, `_STEP_ARGS` lists its
-arguments by the names of the record's fields)."""
+arguments by the names of the record's fields).
+
+`HybridLAMB` (at the end of the file) is the same optimizer with layer-wise trust ratios: its `_launch` is two calls per unit, the trust
+pass and the step that reads it."""
 import copy
 import ctypes
 from typing import NamedTuple
@@ -81,6 +84,8 @@ _STEP_ARGS = {
     "hyb_adamw_step_dev_acc": "n p grads m v acc ema numel hyper ema_hyper k step counter ticket clip",
     "hyb_adamw_step_dev_guard": "n p grads m v acc ema numel hyper ema_hyper k step counter ticket clip guard",
     "hyb_adamw_step_dev_groups": "n p grads m v acc ema numel group groups hyper ema_hyper k step counter ticket clip guard",
+    "hyb_lamb_step_dev": "n p grads m v acc ema numel group groups hyper ema_hyper k step counter ticket clip guard trust",
+    "hyb_lamb_trust": "n p grads m v acc numel group groups hyper k step counter clip guard always_adapt partials trust",
 }
 _STEP_ARGS = {name: tuple(fields.split()) for name, fields in _STEP_ARGS.items()}
 
@@ -534,14 +539,20 @@ class HybridAdamW(torch.optim.Optimizer):
                  *(() if guard is None else (guard,)), _stream())
         return self._norm_out
 
-    def _launch(self, u, grads, step, hyper, clip, guard):
-        """The one AdamW call of a unit on the device path.  A merged call takes the blocks' bases, any other its group's rows."""
-        name = _step_symbol(u.group is not None, guard is not None, self._accum_k > 1, u.ema is not None)
+    def _step_values(self, u, grads, step, hyper, clip, guard):
+        """Every argument a device-path step call of the unit can take, by the names of _STEP_ARGS.  A merged call takes the blocks' bases,
+        any other its group's rows."""
         ema_hyper = None if u.ema is None else self._ema_hyper
         vals = u._asdict()
         vals.update(grads=grads, groups=len(self.param_groups), k=self._accum_k, step=step, counter=self._step_counter,
                     ticket=self._ticket if self._advance else None, clip=clip, guard=guard, hyper=hyper if u.group is not None else hyper[u.first],
                     ema_hyper=ema_hyper if u.group is not None or ema_hyper is None else ema_hyper[u.first])
+        return vals
+
+    def _launch(self, u, grads, step, hyper, clip, guard):
+        """The one AdamW call of a unit on the device path."""
+        name = _step_symbol(u.group is not None, guard is not None, self._accum_k > 1, u.ema is not None)
+        vals = self._step_values(u, grads, step, hyper, clip, guard)
         lib.call(name, *[vals[f] for f in _STEP_ARGS[name]], _stream())
 
     @torch.no_grad()
@@ -581,3 +592,60 @@ class HybridAdamW(torch.optim.Optimizer):
         for u, grads, step in work:
             self._launch(u, grads, step, hyper, clip_coef, guard)
         return loss
+
+
+class HybridLAMB(HybridAdamW):
+    """LAMB (You et al., 2020; timm's Lamb, apex's FusedLAMB without nvlamb) on HybridAdamW's device path: per tensor the Adam update
+    u = m_hat / (sqrt(v_hat) + eps) + weight_decay * p is scaled by the trust ratio r = |p| / |u| (1 where either norm is zero, and for a
+    tensor whose group has weight_decay == 0 unless always_adapt), p <- p - lr * r * u.  That is the AdamW step of the tensor at the rate
+    r * lr, so a step is the existing norm call (when clipping or guarding), ONE read-only launch pair that forms every tensor's ratio on
+    the device (hyb_lamb_trust: the moments as the step will form them, bit-reproducible sums) and the AdamW launch reading the ratios
+    (hyb_lamb_step_dev) -- per launch unit, whatever the number of tensors, with no host read: it works under GraphedTrainStep with
+    everything HybridAdamW offers there (clipping, schedules, the average, accumulation, the guard, merged groups, data parallelism).
+
+    Defaults as timm: eps 1e-6, weight_decay 1e-2, max_grad_norm 1.0 (None: no clipping).  State-dict keys are HybridAdamW's, so
+    checkpoints interchange with it and with torch.optim.AdamW.  always_adapt is an attribute fixed at construction (it travels by value
+    in the captured launch).  `trust_ratios()` gives the last step's {|p|, |u|, r} per parameter as device tensors.  weight_decay is read
+    on the device: setting a group's weight_decay to 0 between replays stops adapting its tensors without a recapture."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=1e-2, always_adapt=False, max_grad_norm=1.0, ema_decay=None,
+                 ema_warmup=False, accumulation_steps=1, skip_nonfinite=False, merge_groups=True):
+        if not isinstance(always_adapt, bool):
+            raise ValueError("always_adapt must be a bool")
+        self._always_adapt = always_adapt
+        self._trust = {}             # unit key -> (numels, device fp32 [2 * chunks], device fp32 [n, 3], the unit's parameters)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay,
+                         ema_warmup=ema_warmup, accumulation_steps=accumulation_steps, skip_nonfinite=skip_nonfinite, merge_groups=merge_groups)
+
+    always_adapt = property(lambda self: self._always_adapt)
+
+    def uses_device_hyper(self):
+        """Always: the ratios are formed and read on the device (there is no by-value LAMB)."""
+        return True
+
+    def _trust_workspace(self, u):
+        """The unit's partial sums and trust block, created eagerly (_no_capture) and kept while the unit serves the same tensor sizes."""
+        numels = tuple(u.numel)
+        w = self._trust.get(u.key)
+        if w is None or w[0] != numels:
+            _no_capture("the trust-ratio workspace", "take one eager step() with the same gradients first")
+            dev = self._device()
+            floats = lib.query("hyb_lamb_trust_workspace", u.n, u.numel)
+            w = self._trust[u.key] = (numels, torch.zeros(floats, dtype=torch.float32, device=dev), torch.ones(u.n, 3, dtype=torch.float32, device=dev),
+                                      u.params)
+        elif w[3] is not u.params:                  # (the same sizes behind other tensors: the rows now speak of these)
+            w = self._trust[u.key] = w[:3] + (u.params,)
+        return w[1], w[2]
+
+    def trust_ratios(self):
+        """{parameter: device fp32 tensor [3] = (|p|, |u|, r)} of the last step, for every parameter that step served: views of the blocks
+        the launches write, no host read.  After a step the guard skipped, the contents are unspecified."""
+        return {p: block[i] for _, _, block, params in self._trust.values() for i, p in enumerate(params)}
+
+    def _launch(self, u, grads, step, hyper, clip, guard):
+        """The trust pass and the step that reads it: two calls per unit."""
+        partials, trust = self._trust_workspace(u)
+        vals = self._step_values(u, grads, step, hyper, clip, guard)
+        vals.update(always_adapt=int(self._always_adapt), partials=partials, trust=trust)
+        for name in ("hyb_lamb_trust", "hyb_lamb_step_dev"):
+            lib.call(name, *[vals[f] for f in _STEP_ARGS[name]], _stream())
