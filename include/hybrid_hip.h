@@ -204,6 +204,12 @@ int hyb_conv3x3_fwd_variant(int dtype, int N, int H, int W, int Cip, int Cop);
  * walks ceil(tiles / grid) consecutive tiles -- without (stats = 0: stats_partials == NULL) or with (stats = 1) partial statistics; 0 for the
  * first-generation kernel (one tile per workgroup) and for bad arguments */
 int hyb_conv3x3_fwd_run(int dtype, int stats, int N, int H, int W, int Cip, int Cop);
+/* pure host query (new symbol, hyb_abi_version() stays 9): the stage-1 twin of hyb_conv3x3_fwd_run.  Every first-stage kernel is persistent; pass =
+ * 0 statistics, 1 apply + pool, 2 Gram, 3 backward of hyb_convstage_fwd / hyb_convstage_bwd(first = 1).  > 0: the 8x16-pixel blocks in a WAVE's run
+ * (a wave-private kernel serves the pass: wave k of the grid walks blocks [k run, (k + 1) run), row-major inside an image; waves past the last block
+ * are idle); < 0: minus the 8x32-pixel tiles in a workgroup's run (the block-level kernel); 0: the pass does not run for this dtype / shape / mode,
+ * or an argument is bad.  Assumes 16-byte-aligned tensors; the HYB_S1_* switches as the process reads them. */
+int hyb_stage1_run(int dtype, int pass, int training, int N, int H, int W, int Ci, int Cop);
 /* pure host query: the non-first weight-gradient kernel of this shape (fused = hyb_convstage_bwd's form), 100 * generation (1, 2, 3) + input channels per workgroup (32, 64) */
 int hyb_conv3x3_wgrad_variant(int dtype, int fused, int N, int H, int W, int Cip, int Cop);
 size_t hyb_convstage_infer_workspace(int dtype, int first, int N, int H, int W, int Cip, int Cop);

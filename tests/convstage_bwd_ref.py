@@ -93,7 +93,8 @@ def channel_constants(Co, gen):
         beta[sl] = torch.maximum(torch.minimum(beta[sl], lim), -lim)
     gamma[0], beta[0] = 1.0, -4.0
     gamma[1] = -gamma[1].abs()
-    gamma[8] = 0.0
+    if Co > 8:                                     # (the first stage's 8-channel row of tests/stage1_run_shapes.py has one octet only)
+        gamma[8] = 0.0
     return gamma, beta, mean, invstd
 
 

@@ -601,11 +601,68 @@ long long hyb_stage1_route_elems(int dtype, int N, int H, int W, int Cop) {
     return (long long)N * (H / 2) * (W / 2) * Cop / 4;          // bytes / 2
 }
 
-static int s1_grid(long long numTiles) {
+// ---- the grid rule of stage 1: the one place a pass's workgroup count is decided ---------------------------------------------------------
+// Every stage-1 kernel is persistent.  A workgroup of the block-level kernels (this file) walks ceil(tiles / wgs) consecutive 8x32-pixel
+// tiles; a WAVE of the wave-private kernels (conv_first_wave.hip) walks ceil(blocks / (4 wgs)) consecutive 8x16-pixel blocks, and waves or
+// whole workgroups past the last block have none (their partial rows are zeros, which the fixed-order row sums then add).
+//   pass 0  statistics    min(tiles, HYB_S1_FWD_WGS = 1024), at most S1_MAXPART partial rows; training only, and not when the Gram pass serves
+//   pass 1  apply + pool  min(tiles, HYB_S1_APPLY_WGS = 2048; <= 0: the statistics pass's count): it keeps no partial rows, so its grid is
+//                         free -- 2048 workgroups (shorter runs, 166 VGPRs = 3 workgroups per CU resident) measured +1 % of the step over 1024
+//   pass 2  Gram          HYB_S1_GRAM_WGS = 512 (1024 measured 0.5 % slower), at most S1_BWD_PART partial rows; training with gram_fwd only
+//   pass 3  backward      min(tiles, HYB_S1_BWD_WGS = 512; 768 = three workgroups per CU for the kernel without G measured 1 % slower), at
+//                         most S1_BWD_PART partial rows
+// and a wave-private kernel never gets more workgroups than ceil(blocks / 4).  hyb_stage1_run (below) reports `run`; stage1_fwd_t and
+// stage1_bwd_t launch `wgs` workgroups and sum `wgs` partial rows.
+enum { S1_PASS_STATS = 0, S1_PASS_APPLY = 1, S1_PASS_GRAM = 2, S1_PASS_BWD = 3 };
+struct S1Grid {
+    int wgs;      // workgroups launched (= partial rows written); 0: the pass does not run
+    int run;      // > 0: blocks per wave (wave-private kernel); < 0: -(tiles per workgroup) (block-level kernel); 0: the pass does not run
+};
+static S1Grid s1_grid_rule(int pass, const S1Paths& p, int training, int N, int H, int W) {
     static const int fwd_wgs = hyb_env_int("HYB_S1_FWD_WGS", S1_FWD_WGS);
-    long long g = numTiles < fwd_wgs ? numTiles : fwd_wgs;
-    if (g > S1_MAXPART) g = S1_MAXPART;
-    return (int)(g < 1 ? 1 : g);
+    static const int apply_wgs = hyb_env_int("HYB_S1_APPLY_WGS", 2048);
+    static const int gram_wgs = hyb_env_int("HYB_S1_GRAM_WGS", 512);
+    static const int bwd_wgs = hyb_env_int("HYB_S1_BWD_WGS", 0);
+    const long long tiles = (long long)N * hyb_cdiv(W, S1_TW) * hyb_cdiv(H, S1_TH);
+    const long long blocks = (long long)N * hyb_cdiv(W, 16) * hyb_cdiv(H, 8);
+    if (tiles < 1 || tiles >= (1ll << 31)) return S1Grid{0, 0};
+    long long stat = tiles < fwd_wgs ? tiles : fwd_wgs;
+    if (stat > S1_MAXPART) stat = S1_MAXPART;
+    if (stat < 1) stat = 1;
+    long long want = 0;
+    bool wave = false;
+    if (pass == S1_PASS_STATS) {
+        if (!training || p.gram_fwd) return S1Grid{0, 0};
+        want = stat; wave = p.fwd_wave;
+    } else if (pass == S1_PASS_APPLY) {
+        want = apply_wgs > 0 ? apply_wgs : stat; wave = p.fwd_wave;
+        if (want > tiles) want = tiles;
+    } else if (pass == S1_PASS_GRAM) {
+        if (!training || !p.gram_fwd) return S1Grid{0, 0};
+        want = gram_wgs < 1 ? 1 : (gram_wgs > S1_BWD_PART ? S1_BWD_PART : gram_wgs); wave = true;
+    } else if (pass == S1_PASS_BWD) {
+        want = bwd_wgs > 0 ? bwd_wgs : S1_BWD_WGS; wave = p.bwd_wave;
+        if (want > S1_BWD_PART) want = S1_BWD_PART;
+        if (want > tiles) want = tiles;
+    } else {
+        return S1Grid{0, 0};
+    }
+    if (wave) {
+        if (blocks >= (1ll << 30)) return S1Grid{0, 0};          // (block counters are ints; never reached: a wave-private path needs 32-bit offsets)
+        if (want * 4 > blocks) want = (blocks + 3) / 4;
+        return S1Grid{(int)want, (int)((blocks + 4 * want - 1) / (4 * want))};
+    }
+    return S1Grid{(int)want, -(int)((tiles + want - 1) / want)};
+}
+
+// Pure host query: the run of a stage-1 pass (pass: 0 statistics, 1 apply + pool, 2 Gram, 3 backward) as hyb_convstage_fwd / _bwd with
+// first = 1 launch it for 16-byte-aligned tensors, under the HYB_S1_* switches as this process reads them.  > 0: blocks (8x16 pixels) per
+// wave of the wave-private kernel; < 0: -(tiles (8x32 pixels) per workgroup) of the block-level kernel; 0: the pass does not run for this
+// dtype / shape / mode, or an argument is bad.
+extern "C" int hyb_stage1_run(int dtype, int pass, int training, int N, int H, int W, int Ci, int Cop) {
+    if ((dtype != HYB_F32 && dtype != HYB_BF16) || pass < 0 || pass > 3 || N < 1 || H < 2 || W < 2 || Ci < 1 || Ci > 4 || Cop < 32 || Cop % 32 != 0) return 0;
+    const S1Paths p = s1_paths(dtype == HYB_F32 ? 4 : 2, nullptr, nullptr, N, H, W, Ci, Cop, training != 0, true);
+    return s1_grid_rule(pass, p, training != 0, N, H, W).run;
 }
 
 template <typename T>
@@ -650,9 +707,7 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
     a.route = (route && wave_private && paths.route) ? (unsigned*)route : nullptr;
     const long long numTiles = (long long)N * a.tilesX * a.tilesY;
     a.numTiles = (int)numTiles;
-    const int gx = s1_grid(numTiles);
     int rc;
-    int gx_rows = gx;                                      // partial statistics rows actually written
     if (packed_out && !infer) {
         // defined contents for the whole saved buffer (its size is counted in 2-byte elements: twice the need with fp32 storage): the
         // Gram slot's padding always, the slot itself when this path does not produce it
@@ -661,8 +716,8 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
         if (!(training && use_gram)) { if (hipError_t e = hipMemsetAsync(gram, 0, tail, st)) return (int)e; }
     }
     if (training && use_gram) {
-        static const int gram_wgs = hyb_env_int("HYB_S1_GRAM_WGS", 512);          // 1024 measured 0.5 % slower
-        int grows = gram_wgs < 1 ? 1 : (gram_wgs > S1_BWD_PART ? S1_BWD_PART : gram_wgs);
+        const int grows = s1_grid_rule(S1_PASS_GRAM, paths, training, N, H, W).wgs;
+        if (grows < 1) return HYB_E_ARG;
         rc = hyb_stage1w_gram(dtype, a, grows, st);
         if (rc) return rc;
         hipLaunchKernelGGL(s1_rows_sum_kernel, dim3(hyb_cdiv(2304, 32)), dim3(256), 0, st, part, gram, grows, 2304ll);
@@ -672,9 +727,11 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
         HYB_LAUNCH_CHECK();
         rc = 0;
     } else if (training) {
-        rc = wave_private ? hyb_stage1w_pass(dtype, 0, a, gx_rows, st) : s1_dispatch<T, 0>(a, gx, st);
+        const int gx = s1_grid_rule(S1_PASS_STATS, paths, training, N, H, W).wgs;      // = partial statistics rows written
+        if (gx < 1) return HYB_E_ARG;
+        rc = wave_private ? hyb_stage1w_pass(dtype, 0, a, gx, st) : s1_dispatch<T, 0>(a, gx, st);
         if (rc) return rc;
-        rc = hyb_bn_stats_finalize(part, gx_rows, gamma, beta, running_mean, running_var, nbt, momentum, eps, (long long)N * H * W, Co, Cop,
+        rc = hyb_bn_stats_finalize(part, gx, gamma, beta, running_mean, running_var, nbt, momentum, eps, (long long)N * H * W, Co, Cop,
                                    scale_shift, mean_invstd, running_out, (void*)st);
     } else if (infer) {
         rc = 0;
@@ -683,11 +740,8 @@ static int stage1_fwd_t(int dtype, const float* x, const float* weight, const fl
                              scale_shift, mean_invstd, nullptr, (void*)st);
     }
     if (rc) return rc;
-    // the apply+pool pass keeps no partial rows, so its grid is free: 2048 workgroups (shorter tile runs, 166 VGPRs = 3 workgroups
-    // per CU resident) measured +1 % of the step over 1024.  HYB_S1_APPLY_WGS overrides (A/B).
-    static const int apply_wgs = hyb_env_int("HYB_S1_APPLY_WGS", 2048);
-    int gx1 = apply_wgs > 0 ? apply_wgs : gx;
-    if (gx1 > numTiles) gx1 = (int)numTiles;
+    const int gx1 = s1_grid_rule(S1_PASS_APPLY, paths, training, N, H, W).wgs;
+    if (gx1 < 1) return HYB_E_ARG;
     return wave_private ? hyb_stage1w_pass(dtype, 1, a, gx1, st) : s1_dispatch<T, 1>(a, gx1, st);
 }
 
@@ -725,12 +779,8 @@ static int stage1_bwd_t(const void* dpooled, const float* x, const float* weight
     const long long numTiles = (long long)N * a.tilesX * a.tilesY;
     a.numTiles = (int)numTiles;
     // one pass over x and dpooled (MODE 4), a fixed-order sum of the partial rows, and a finalize on tiny matrices
-    static const int bwd_wgs = hyb_env_int("HYB_S1_BWD_WGS", 0);                // 0: 512 (768 = three workgroups per CU for the kernel without G measured 1 % slower)
-    // (saved_g is decided below from the same inputs; the grid only needs the bound)
-    int want = bwd_wgs > 0 ? bwd_wgs : S1_BWD_WGS;
-    if (want > S1_BWD_PART) want = S1_BWD_PART;
-    int gx = (int)(numTiles < want ? numTiles : want);
-    if (gx < 1) gx = 1;
+    const int gx = s1_grid_rule(S1_PASS_BWD, paths, training, N, H, W).wgs;      // = partial rows written
+    if (gx < 1) return HYB_E_ARG;
     const long long roww = (long long)Cop * 48 + 2304;
     // the forward pass of a training step left the Gram matrix behind the packed weights: accumulate S1 only
     const bool saved_g = paths.gram_saved;

@@ -1088,12 +1088,11 @@ int s1w_launch(S1Args a, int grid_x, hipStream_t st) {
 }
 // the wave-private forward passes work on 8x8 blocks: tilesX/tilesY/numTiles of `a` are re-derived for that block size
 template <typename T, int MODE>
-int s1w_dispatch(S1Args a, int& grid_x /* in: wanted workgroups; out: launched (= partial rows of MODE 0) */, hipStream_t st) {
+int s1w_dispatch(S1Args a, int grid_x /* workgroups, from s1_grid_rule (conv_first.hip); = partial rows of MODE 0 */, hipStream_t st) {
     a.tilesX = hyb_cdiv(a.W, S1W_BW); a.tilesY = hyb_cdiv(a.H, 8);
     const long long nb = (long long)a.N * a.tilesX * a.tilesY;
     if (nb >= (1ll << 30)) return HYB_E_ARG;
     a.numTiles = (int)nb;
-    if ((long long)grid_x * 4 > nb) grid_x = (int)((nb + 3) / 4);
     if (a.Cop % 64 == 0) return s1w_launch<T, 4, MODE>(a, grid_x, st);
     return s1w_launch<T, 2, MODE>(a, grid_x, st);
 }
@@ -1112,13 +1111,12 @@ int hyb_stage1w_pack(int dtype, const float* weight, void* wp2, int Co, int Ci, 
 
 // backward pass over 8x16 blocks; `a` as for the block-level MODE 4 launch (wp2 set); bf16 only (the transposing LDS read is a 16-bit
 // instruction): fp32 parity mode keeps the block-level kernel
-int hyb_stage1w_bwd(int dtype, S1Args a, int with_g, int& grid_x, hipStream_t st) {
+int hyb_stage1w_bwd(int dtype, S1Args a, int with_g, int grid_x, hipStream_t st) {
     if (dtype != HYB_BF16 && !(HYB_X3 && dtype == HYB_F32 && with_g)) return HYB_E_ARG;
     a.tilesX = hyb_cdiv(a.W, S1W_BW); a.tilesY = hyb_cdiv(a.H, 8);
     const long long nb = (long long)a.N * a.tilesX * a.tilesY;
     if (nb >= (1ll << 30)) return HYB_E_ARG;
     a.numTiles = (int)nb;
-    if ((long long)grid_x * 4 > nb) grid_x = (int)((nb + 3) / 4);
 #ifdef HYB_F32_X3
     if (dtype == HYB_F32) return a.Cop % 64 == 0 ? s1x_bwd_launch<4>(a, grid_x, st) : s1x_bwd_launch<2>(a, grid_x, st);
 #endif
@@ -1126,14 +1124,14 @@ int hyb_stage1w_bwd(int dtype, S1Args a, int with_g, int& grid_x, hipStream_t st
     return with_g ? s1w_bwd_launch<bf16, 2, true>(a, grid_x, st) : s1w_bwd_launch<bf16, 2, false>(a, grid_x, st);
 }
 
-// Gram pass over 8x16 blocks (no ragged blocks: H % 8 == 0, W % 16 == 0); writes grid_x partial rows of 2304 floats to a.part
-int hyb_stage1w_gram(int dtype, S1Args a, int& grid_x, hipStream_t st) {
+// Gram pass over 8x16 blocks (no ragged blocks: H % 8 == 0, W % 16 == 0); writes grid_x partial rows of 2304 floats to a.part.
+// grid_x here and in the two launchers around it comes from s1_grid_rule (conv_first.hip): at most ceil(blocks / 4) workgroups
+int hyb_stage1w_gram(int dtype, S1Args a, int grid_x, hipStream_t st) {
     if (dtype != HYB_BF16) return HYB_E_ARG;
     a.tilesX = hyb_cdiv(a.W, S1W_BW); a.tilesY = hyb_cdiv(a.H, 8);
     const long long nb = (long long)a.N * a.tilesX * a.tilesY;
     if (nb >= (1ll << 30)) return HYB_E_ARG;
     a.numTiles = (int)nb;
-    if ((long long)grid_x * 4 > nb) grid_x = (int)((nb + 3) / 4);
     size_t lds = (size_t)4 * (S1W_IMG + S1B_CT) * sizeof(bf16);
     if (lds < (size_t)4 * 2304 * sizeof(float)) lds = (size_t)4 * 2304 * sizeof(float);
     lds += 64;
@@ -1143,7 +1141,7 @@ int hyb_stage1w_gram(int dtype, S1Args a, int& grid_x, hipStream_t st) {
     return 0;
 }
 
-int hyb_stage1w_pass(int dtype, int mode, const S1Args& a, int& grid_x, hipStream_t st) {
+int hyb_stage1w_pass(int dtype, int mode, const S1Args& a, int grid_x, hipStream_t st) {
     if (dtype == HYB_F32) return mode == 0 ? s1w_dispatch<float, 0>(a, grid_x, st) : s1w_dispatch<float, 1>(a, grid_x, st);
     if (dtype == HYB_BF16) return mode == 0 ? s1w_dispatch<bf16, 0>(a, grid_x, st) : s1w_dispatch<bf16, 1>(a, grid_x, st);
     return HYB_E_ARG;
