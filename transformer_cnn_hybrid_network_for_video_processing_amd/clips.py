@@ -33,6 +33,7 @@ import torch
 
 from ._lib import lib
 from .modules import MixTarget
+from .ops import clip_transform_into
 
 
 class ClipCSVDataset(torch.utils.data.Dataset):
@@ -204,7 +205,7 @@ class ClipPipeline:
                 lib.call("hyb_frames_u8hwc_to_f32chw", s["dev_u8"], s["x"], B * T, H, W, C, self.stream.cuda_stream)
             else:
                 s["dev_p"].copy_(s["host_p"], non_blocking=True)
-                Tout, Ho, Wo = s["x"].shape[1], s["x"].shape[3], s["x"].shape[4]
+                Tout = s["x"].shape[1]
                 if mixing:
                     s["dev_m"].copy_(s["host_m"], non_blocking=True)
                 if mixing and not dense:
@@ -214,20 +215,9 @@ class ClipPipeline:
                     s["dev_ph"].copy_(s["host_ph"], non_blocking=True)
                     if "luma" in s:
                         lib.call("hyb_clips_u8_luma_sums", s["dev_u8"], s["dev_p"], s["luma"], B, T, H, W, C, Tout, self.stream.cuda_stream)
-                    lib.call("hyb_clips_u8_transform_photo", s["dev_u8"], s["dev_p"], s["dev_m"] if mixing else None, s["dev_ph"], s.get("luma"),
-                             self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho, Wo, self.stream.cuda_stream)
-                elif self.transform.antialias:
-                    lib.call("hyb_clips_u8_transform_aa", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, views, T, H, W, C, Tout, Ho, Wo,
-                             self.stream.cuda_stream)
-                elif views > 1:
-                    lib.call("hyb_clips_u8_transform_views", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, views, T, H, W, C, Tout, Ho, Wo,
-                             self.stream.cuda_stream)
-                elif mixing:
-                    lib.call("hyb_clips_u8_transform_mix", s["dev_u8"], s["dev_p"], s["dev_m"], self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho,
-                             Wo, self.stream.cuda_stream)
-                else:
-                    lib.call("hyb_clips_u8_transform", s["dev_u8"], s["dev_p"], self._mean_invstd, s["x"], B, T, H, W, C, Tout, Ho, Wo,
-                             self.stream.cuda_stream)
+                # the one transform call: which kernel is ClipTransform.kernel()'s answer, how it is called is the operators' (ops.CLIP_OPS)
+                clip_transform_into(self.transform.kernel(), s["x"], s["dev_u8"], s["dev_p"], self._mean_invstd, views, self.stream.cuda_stream,
+                                    mix=s.get("dev_m"), photo=s.get("dev_ph"), luma_sums=s.get("luma"))
             s["ready"].record(self.stream)
 
     def __iter__(self):
@@ -297,7 +287,7 @@ class ClipTransform:
                   An axis without slack gives coinciding views (S = 3 of a square source at eval_crop = 1: three times the same crop); that is
                   allowed.  All three are for train=False: a non-default value with train=True raises
     antialias     True: the resize is torchvision's ``Resize(antialias=True)`` -- ``F.interpolate(..., antialias=True)``'s triangle filter, whose
-                  support grows with the down-scale -- for training rows and evaluation views alike (hyb_clips_u8_transform_aa); what to use
+                  support grows with the down-scale -- for training rows and evaluation views alike (``kernel()`` is then "aa"); what to use
                   when the source is more than about 2 x the output ("resize 256, crop 224" from a 720-line decoder).  The rows do not change:
                   ``sample`` / ``sample_views`` of a seed are the same with it on and off.  Not provided together with mixing or the photometric
                   options (raises).  False, the default: the kernels, draws and bits are what they were
@@ -379,7 +369,7 @@ class ClipTransform:
     ERASE_MODES = ("zero", "black", "pixel")
 
     def photometric(self):
-        """Whether this transform jitters, grays, adds noise or erases (ClipPipeline then calls hyb_clips_u8_transform_photo)."""
+        """Whether this transform jitters, grays, adds noise or erases (``kernel()`` says what ClipPipeline then calls)."""
         return self.train and (self.brightness > 0 or self.contrast > 0 or self.saturation > 0 or self.grayscale > 0 or self.noise_std[1] > 0
                                or self.erase_prob > 0)
 
@@ -426,6 +416,22 @@ class ClipTransform:
             if self.erase_prob > 0 and g.random() < self.erase_prob:
                 rows[b, 8:12] = self._erase_box(Ho, Wo)
         return rows
+
+    def kernel(self):
+        """Which device transform ClipPipeline runs for this transform: a key of ops.CLIP_OPS.  The first that applies of
+          "photo"  hyb_clips_u8_transform_photo  a photometric option is on (``photometric()``), with mixing or without
+          "aa"     hyb_clips_u8_transform_aa     antialias=True, for the training rows (V = 1) and the evaluation views alike
+          "views"  hyb_clips_u8_transform_views  more than one evaluation view per clip (``views`` > 1)
+          "mix"    hyb_clips_u8_transform_mix    Mixup / CutMix (``mixing()``)
+          "plain"  hyb_clips_u8_transform        everything else: train=False switches mixing and the photometric options off
+        This is the only statement of the rule."""
+        if self.photometric():
+            return "photo"
+        if self.antialias:
+            return "aa"
+        if self.views > 1:
+            return "views"
+        return "mix" if self.mixing() else "plain"
 
     @property
     def views(self):
@@ -536,7 +542,7 @@ class ClipTransform:
         return rows
 
     def mixing(self):
-        """Whether this transform mixes clips (ClipPipeline then calls the mix kernel and yields MixTargets)."""
+        """Whether this transform mixes clips (ClipPipeline then yields MixTargets; ``kernel()`` says what it calls)."""
         return self.train and (self.mixup_alpha > 0 or self.cutmix_alpha > 0)
 
     def _mix_draw(self, Ho, Wo):

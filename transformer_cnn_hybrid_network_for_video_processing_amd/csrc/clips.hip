@@ -14,11 +14,15 @@
 // source rows, which the vector L1 serves; no LDS, no barrier.  blockIdx.x walks the (row, quad) positions of a frame, blockIdx.y the
 // output frames, so the clip index, its parameter row and the clamps are wave-uniform.
 //
-// Four launches share the rule: the plain kernel, the mix kernel (Mixup / CutMix), the photo kernel (colour jitter, noise, erasing) and the
+// Four kernels share the rule: the plain kernel, the mix kernel (Mixup / CutMix), the photo kernel (colour jitter, noise, erasing) and the
 // views kernel (V evaluation views of every source clip, hyb_clips_u8_transform_views).  The plain, mix, photo and luma kernels are to keep
 // their instruction schedules: a new variant is a new kernel built from clip_row / clip_taps / clip_pixel, not a change to one of them.
-// The antialiased resize (hyb_clips_u8_transform_aa, at the end of the file) has a rule and an access pattern of its own: a separable triangle
-// filter through LDS, with barriers.
+// The antialiased resize (hyb_clips_u8_transform_aa, the last kernel of the file) has a rule and an access pattern of its own: a separable
+// triangle filter through LDS, with barriers.
+//
+// The host side is at the end of the file and is written once for the five transforms: an entry point fills a HybClipJob (kind, pointers,
+// extents), hyb_clip_ok is the one validity rule -- a shared body and a table row per kind -- and hyb_clip_launch the one launch rule: frames,
+// the 16-byte store condition, the grid and one switch over the kinds.  A new variant is a kind, a row in the check and a case in the launch.
 #include "hyb_common.h"
 
 namespace {
@@ -542,100 +546,6 @@ __global__ __launch_bounds__(256) void clips_u8_luma_sums_kernel(const unsigned 
 }
 }  // namespace
 
-extern "C" int hyb_clips_u8_transform(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int Tin, int Hin,
-                                      int Win, int C, int Tout, int Ho, int Wo, void* stream) {
-    HYB_CHECK_ARG(src && params && dst && B > 0 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Ho > 0 && Wo > 0);
-    HYB_CHECK_ARG(C <= 4 && Hin <= 16384 && Win <= 16384 && Ho <= 16384 && Wo <= 16384);      // the rule's integer products stay below 2^31
-    const long long frames = (long long)B * Tout;
-    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
-    const bool vec = Wo % 4 == 0 && ((unsigned long long)dst & 15) == 0;
-    const int per_frame = Ho * (vec ? Wo / 4 : Wo);
-    const dim3 grid(hyb_cdiv(per_frame, 256), gy);
-    if (vec)
-        hipLaunchKernelGGL(clips_u8_transform_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, Tin, Hin, Win,
-                           C, Tout, Ho, Wo);
-    else
-        hipLaunchKernelGGL(clips_u8_transform_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, Tin, Hin, Win,
-                           C, Tout, Ho, Wo);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int hyb_clips_u8_transform_mix(const unsigned char* src, const int* params, const int* mix, const float* mean_invstd, float* dst, int B, int Tin,
-                                          int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream) {
-    HYB_CHECK_ARG(src && params && mix && dst && B > 0 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Ho > 0 && Wo > 0);
-    HYB_CHECK_ARG(C <= 4 && Hin <= 16384 && Win <= 16384 && Ho <= 16384 && Wo <= 16384);
-    const long long frames = (long long)B * Tout;
-    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
-    const bool vec = Wo % 4 == 0 && ((unsigned long long)dst & 15) == 0;
-    const int per_frame = Ho * (vec ? Wo / 4 : Wo);
-    const dim3 grid(hyb_cdiv(per_frame, 256), gy);
-    if (vec)
-        hipLaunchKernelGGL(clips_u8_transform_mix_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mix, mean_invstd, dst, frames, B, Tin,
-                           Hin, Win, C, Tout, Ho, Wo);
-    else
-        hipLaunchKernelGGL(clips_u8_transform_mix_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mix, mean_invstd, dst, frames, B, Tin,
-                           Hin, Win, C, Tout, Ho, Wo);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int hyb_clips_u8_transform_views(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int V, int Tin,
-                                            int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream) {
-    HYB_CHECK_ARG(src && params && dst && B > 0 && V >= 1 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Ho > 0 && Wo > 0);
-    HYB_CHECK_ARG(C <= 4 && Hin <= 16384 && Win <= 16384 && Ho <= 16384 && Wo <= 16384);
-    HYB_CHECK_ARG((long long)B * V <= 2147483647LL);                  // the output clips are counted in int like the plain kernel's
-    const long long frames = (long long)B * V * Tout;
-    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
-    const bool vec = Wo % 4 == 0 && ((unsigned long long)dst & 15) == 0;
-    const int per_frame = Ho * (vec ? Wo / 4 : Wo);
-    const dim3 grid(hyb_cdiv(per_frame, 256), gy);
-    if (vec)
-        hipLaunchKernelGGL(clips_u8_transform_views_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, V, Tin,
-                           Hin, Win, C, Tout, Ho, Wo);
-    else
-        hipLaunchKernelGGL(clips_u8_transform_views_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, V, Tin,
-                           Hin, Win, C, Tout, Ho, Wo);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int hyb_clips_u8_transform_photo(const unsigned char* src, const int* params, const int* mix, const int* photo, const long long* luma_sums,
-                                            const float* mean_invstd, float* dst, int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo,
-                                            void* stream) {
-    HYB_CHECK_ARG(src && params && photo && dst && B > 0 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Ho > 0 && Wo > 0);
-    HYB_CHECK_ARG((C == 1 || C == 3) && Hin <= 16384 && Win <= 16384 && Ho <= 16384 && Wo <= 16384);      // the luma is defined for grey and RGB
-    const long long frames = (long long)B * Tout;
-    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
-    const bool vec = Wo % 4 == 0 && ((unsigned long long)dst & 15) == 0;
-    const int per_frame = Ho * (vec ? Wo / 4 : Wo);
-    const dim3 grid(hyb_cdiv(per_frame, 256), gy);
-    if (vec)
-        hipLaunchKernelGGL(clips_u8_transform_photo_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mix, photo, luma_sums, mean_invstd,
-                           dst, frames, B, Tin, Hin, Win, C, Tout, Ho, Wo);
-    else
-        hipLaunchKernelGGL(clips_u8_transform_photo_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mix, photo, luma_sums, mean_invstd,
-                           dst, frames, B, Tin, Hin, Win, C, Tout, Ho, Wo);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int hyb_clips_u8_luma_sums(const unsigned char* src, const int* params, long long* sums, int B, int Tin, int Hin, int Win, int C, int Tout,
-                                      void* stream) {
-    HYB_CHECK_ARG(src && params && sums && B > 0 && Tin > 0 && Hin > 0 && Win > 0 && Tout > 0);
-    HYB_CHECK_ARG((C == 1 || C == 3) && Hin <= 16384 && Win <= 16384);
-    const long long frames = (long long)B * Tout;
-    // the workgroups of a frame meet in sums[f] through integer atomics: zeroed here, on the same stream, in every call
-    const hipError_t e = hipMemsetAsync(sums, 0, (size_t)frames * sizeof(long long), (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
-    const dim3 grid(hyb_cdiv(Hin, LUMA_SPLIT_ROWS), gy);
-    hipLaunchKernelGGL(clips_u8_luma_sums_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, params, reinterpret_cast<unsigned long long*>(sums), frames,
-                       Tin, Hin, Win, C, Tout);
-    HYB_LAUNCH_CHECK();
-    return 0;
-}
-
 // ---- Antialiased resize (hyb_clips_u8_transform_aa; include/hybrid_hip.h has the rule in full): torchvision's Resize(antialias=True), i.e.
 // F.interpolate(bilinear, align_corners=False, antialias=True).  The kernels above stay as they were written; this one takes clip_row (the clamps,
 // the temporal index, the flip) and the views kernel's frame walk from them and nothing else.  Per axis, n crop positions -> m output positions:
@@ -837,22 +747,119 @@ __global__ __launch_bounds__(256) void clips_u8_transform_aa_kernel(const unsign
 }
 }  // namespace
 
+// ---- The host side: one job, one check, one launch rule.  Every transform entry point fills a HybClipJob and hands it to hyb_clip_ok and
+// hyb_clip_launch; nothing below them restates a limit, the 16-byte rule or a grid.  A new variant is a kind, a row in CLIP_KINDS and a case in
+// hyb_clip_launch's switch.
+namespace {
+enum HybClipKind { HYB_CLIP_PLAIN, HYB_CLIP_MIX, HYB_CLIP_VIEWS, HYB_CLIP_PHOTO, HYB_CLIP_AA };
+struct HybClipJob {
+    int kind;
+    const unsigned char* src; const int* params; const int* mix; const int* photo; const long long* luma_sums; const float* mean_invstd; float* dst;
+    int B, V, Tin, Hin, Win, C, Tout, Ho, Wo;
+};
+constexpr int CLIP_MAX_EXTENT = 16384;       // Hin, Win, Ho, Wo: the rule's integer products stay below 2^31
+// What a kind asks beyond the shared rule: the row pointers it cannot do without, whether it takes V rows per source clip (else V is 1), and
+// whether it needs a luma (defined for grey and RGB: C == 1 or C == 3; else C <= 4).  luma_sums and mean_invstd are optional everywhere.
+struct ClipKindRule { bool needs_mix, needs_photo, has_views, luma; };
+constexpr ClipKindRule CLIP_KINDS[] = {
+    /* HYB_CLIP_PLAIN */ {false, false, false, false},
+    /* HYB_CLIP_MIX   */ {true, false, false, false},
+    /* HYB_CLIP_VIEWS */ {false, false, true, false},
+    /* HYB_CLIP_PHOTO */ {false, true, false, true},       // (mix is optional here)
+    /* HYB_CLIP_AA    */ {false, false, true, false},
+};
+
+// The source side of the rule, which hyb_clips_u8_luma_sums shares: the bytes, the parameter rows, their extents and the channel count
+bool clip_src_ok(const unsigned char* src, const int* params, int B, int Tin, int Hin, int Win, int C, int Tout, bool luma) {
+    return src && params && B > 0 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Hin <= CLIP_MAX_EXTENT && Win <= CLIP_MAX_EXTENT &&
+           (luma ? C == 1 || C == 3 : C <= 4);
+}
+
+// The one validity rule; nothing here touches the device, so a refused job has made no HIP call
+int hyb_clip_ok(const HybClipJob& j) {
+    const ClipKindRule& k = CLIP_KINDS[j.kind];
+    HYB_CHECK_ARG(clip_src_ok(j.src, j.params, j.B, j.Tin, j.Hin, j.Win, j.C, j.Tout, k.luma));
+    HYB_CHECK_ARG(j.dst && j.Ho > 0 && j.Wo > 0 && j.Ho <= CLIP_MAX_EXTENT && j.Wo <= CLIP_MAX_EXTENT);
+    HYB_CHECK_ARG((j.mix || !k.needs_mix) && (j.photo || !k.needs_photo));
+    // the output clips are counted in int
+    HYB_CHECK_ARG(k.has_views ? j.V >= 1 && (long long)j.B * j.V <= 2147483647LL : j.V == 1);
+    return 0;
+}
+
+// The one launch rule.  blockIdx.y walks the B * V * Tout output frames, at most 65535 at a time; a lane owns VEC = 4 output pixels when the rows
+// of dst can be written as 16-byte stores; blockIdx.x walks a frame's (row, quad) positions, or its tiles for the antialiased kernel.
+int hyb_clip_launch(const HybClipJob& j, hipStream_t st) {
+    const long long frames = (long long)j.B * j.V * j.Tout;
+    const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
+    const bool vec = j.Wo % 4 == 0 && ((unsigned long long)j.dst & 15) == 0;
+    const int lane_w = vec ? 4 : 1;
+    const int gx = j.kind == HYB_CLIP_AA ? hyb_cdiv(j.Ho, AA_TH) * hyb_cdiv(j.Wo, AA_QW * lane_w)       // <= 512 * 2048 tiles
+                                         : hyb_cdiv(j.Ho * (j.Wo / lane_w), 256);
+    const dim3 grid(gx, gy);
+#define CLIP_CASE(KIND, KERNEL, ...)                                                                  \
+    case KIND:                                                                                        \
+        if (vec) hipLaunchKernelGGL(KERNEL<4>, grid, dim3(256), 0, st, __VA_ARGS__);                  \
+        else hipLaunchKernelGGL(KERNEL<1>, grid, dim3(256), 0, st, __VA_ARGS__);                      \
+        break
+#define CLIP_EXTENTS j.Tin, j.Hin, j.Win, j.C, j.Tout, j.Ho, j.Wo
+    switch (j.kind) {
+        CLIP_CASE(HYB_CLIP_PLAIN, clips_u8_transform_kernel, j.src, j.params, j.mean_invstd, j.dst, frames, CLIP_EXTENTS);
+        CLIP_CASE(HYB_CLIP_MIX, clips_u8_transform_mix_kernel, j.src, j.params, j.mix, j.mean_invstd, j.dst, frames, j.B, CLIP_EXTENTS);
+        CLIP_CASE(HYB_CLIP_VIEWS, clips_u8_transform_views_kernel, j.src, j.params, j.mean_invstd, j.dst, frames, j.V, CLIP_EXTENTS);
+        CLIP_CASE(HYB_CLIP_PHOTO, clips_u8_transform_photo_kernel, j.src, j.params, j.mix, j.photo, j.luma_sums, j.mean_invstd, j.dst, frames, j.B,
+                  CLIP_EXTENTS);
+        CLIP_CASE(HYB_CLIP_AA, clips_u8_transform_aa_kernel, j.src, j.params, j.mean_invstd, j.dst, frames, j.V, CLIP_EXTENTS);
+    }
+#undef CLIP_EXTENTS
+#undef CLIP_CASE
+    HYB_LAUNCH_CHECK();
+    return 0;
+}
+
+int hyb_clip_run(const HybClipJob& j, void* stream) {
+    const int rc = hyb_clip_ok(j);
+    return rc ? rc : hyb_clip_launch(j, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int hyb_clips_u8_transform(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int Tin, int Hin,
+                                      int Win, int C, int Tout, int Ho, int Wo, void* stream) {
+    return hyb_clip_run({HYB_CLIP_PLAIN, src, params, nullptr, nullptr, nullptr, mean_invstd, dst, B, 1, Tin, Hin, Win, C, Tout, Ho, Wo}, stream);
+}
+
+extern "C" int hyb_clips_u8_transform_mix(const unsigned char* src, const int* params, const int* mix, const float* mean_invstd, float* dst, int B, int Tin,
+                                          int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream) {
+    return hyb_clip_run({HYB_CLIP_MIX, src, params, mix, nullptr, nullptr, mean_invstd, dst, B, 1, Tin, Hin, Win, C, Tout, Ho, Wo}, stream);
+}
+
+extern "C" int hyb_clips_u8_transform_views(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int V, int Tin,
+                                            int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream) {
+    return hyb_clip_run({HYB_CLIP_VIEWS, src, params, nullptr, nullptr, nullptr, mean_invstd, dst, B, V, Tin, Hin, Win, C, Tout, Ho, Wo}, stream);
+}
+
+extern "C" int hyb_clips_u8_transform_photo(const unsigned char* src, const int* params, const int* mix, const int* photo, const long long* luma_sums,
+                                            const float* mean_invstd, float* dst, int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo,
+                                            void* stream) {
+    return hyb_clip_run({HYB_CLIP_PHOTO, src, params, mix, photo, luma_sums, mean_invstd, dst, B, 1, Tin, Hin, Win, C, Tout, Ho, Wo}, stream);
+}
+
 extern "C" int hyb_clips_u8_transform_aa(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int V, int Tin, int Hin,
                                          int Win, int C, int Tout, int Ho, int Wo, void* stream) {
-    HYB_CHECK_ARG(src && params && dst && B > 0 && V >= 1 && Tin > 0 && Hin > 0 && Win > 0 && C > 0 && Tout > 0 && Ho > 0 && Wo > 0);
-    HYB_CHECK_ARG(C <= 4 && Hin <= 16384 && Win <= 16384 && Ho <= 16384 && Wo <= 16384);      // the rule's integer products stay below 2^31
-    HYB_CHECK_ARG((long long)B * V <= 2147483647LL);
-    const long long frames = (long long)B * V * Tout;
+    return hyb_clip_run({HYB_CLIP_AA, src, params, nullptr, nullptr, nullptr, mean_invstd, dst, B, V, Tin, Hin, Win, C, Tout, Ho, Wo}, stream);
+}
+
+// No job: no dst, a memset in front and a grid over the crop rows.  The source side of the check is the jobs'.
+extern "C" int hyb_clips_u8_luma_sums(const unsigned char* src, const int* params, long long* sums, int B, int Tin, int Hin, int Win, int C, int Tout,
+                                      void* stream) {
+    HYB_CHECK_ARG(sums && clip_src_ok(src, params, B, Tin, Hin, Win, C, Tout, true));
+    const long long frames = (long long)B * Tout;
+    // the workgroups of a frame meet in sums[f] through integer atomics: zeroed here, on the same stream, in every call
+    const hipError_t e = hipMemsetAsync(sums, 0, (size_t)frames * sizeof(long long), (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
     const unsigned gy = (unsigned)(frames < 65535 ? frames : 65535);
-    const bool vec = Wo % 4 == 0 && ((unsigned long long)dst & 15) == 0;
-    const int tw = AA_QW * (vec ? 4 : 1);
-    const dim3 grid(hyb_cdiv(Ho, AA_TH) * hyb_cdiv(Wo, tw), gy);                                  // <= 512 * 2048 tiles
-    if (vec)
-        hipLaunchKernelGGL(clips_u8_transform_aa_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, V, Tin, Hin,
-                           Win, C, Tout, Ho, Wo);
-    else
-        hipLaunchKernelGGL(clips_u8_transform_aa_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, src, params, mean_invstd, dst, frames, V, Tin, Hin,
-                           Win, C, Tout, Ho, Wo);
+    const dim3 grid(hyb_cdiv(Hin, LUMA_SPLIT_ROWS), gy);
+    hipLaunchKernelGGL(clips_u8_luma_sums_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, params, reinterpret_cast<unsigned long long*>(sums), frames,
+                       Tin, Hin, Win, C, Tout);
     HYB_LAUNCH_CHECK();
     return 0;
 }

@@ -1162,122 +1162,125 @@ def backbone_infer(x, stages, dt):
                                            [bn.running_mean for bn in bns], [bn.running_var for bn in bns], float(bns[0].eps), int(dt))
 
 
-def _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo):
-    if src.dim() != 5 or src.dtype != torch.uint8:
-        raise TypeError("hybrid::clip_transform reads uint8 clips [B,Tin,Hin,Win,C]")
-    B, Tin, Hin, Win, C = src.shape
-    if params.dtype != torch.int32 or tuple(params.shape) != (B, 8):
-        raise TypeError(f"params must be int32 [{B},8]: one row {{y0, x0, ch, cw, flip, t0, tstride, 0}} per clip")
-    if mean_invstd is not None and (mean_invstd.dtype != torch.float32 or tuple(mean_invstd.shape) != (2, C)):
-        raise TypeError(f"mean_invstd must be float32 [2,{C}]: mean, then 1/std")
-    if C > 4 or max(Hin, Win, Ho, Wo) > 16384 or min(B, Tin, Hin, Win, C, Tout, Ho, Wo) <= 0:
-        raise ValueError("hybrid::clip_transform needs C <= 4, extents > 0 and Hin, Win, Ho, Wo <= 16384")
-    return B, Tin, Hin, Win, C
+_CLIP_ROW = "{y0, x0, ch, cw, flip, t0, tstride, 0}"
 
 
-def clip_transform_op(src: Tensor, params: Tensor, mean_invstd: Optional[Tensor], Tout: int, Ho: int, Wo: int) -> Tensor:
-    """uint8 [B,Tin,Hin,Win,C] -> fp32 [B,Tout,C,Ho,Wo]: crop, bilinear resize, flip, temporal sub-sampling, / 255, normalise, one parameter
-    row per clip (hyb_clips_u8_transform in include/hybrid_hip.h has the sampling rule)."""
-    _require_cuda(src, params, mean_invstd)
-    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
-    out = torch.empty(B, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
-    lib.call("hyb_clips_u8_transform", src.contiguous(), params.contiguous(), None if mean_invstd is None else mean_invstd.contiguous(), out,
-             B, Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
-    return out
-
-
-def _clip_mix_rows(mix, B):
-    if mix.dtype != torch.int32 or tuple(mix.shape) != (B, 8):
-        raise TypeError(f"mix must be int32 [{B},8]: one row {{partner, kind, by0, bx0, bh, bw, lam_bits, 0}} per clip")
-
-
-def clip_transform_mix_op(src: Tensor, params: Tensor, mix: Tensor, mean_invstd: Optional[Tensor], Tout: int, Ho: int, Wo: int) -> Tensor:
-    """hybrid::clip_transform with Mixup / CutMix in the same pass (hyb_clips_u8_transform_mix in include/hybrid_hip.h has the rules): one more
-    int32 row per clip names the partner clip, the kind and the box or lam."""
-    _require_cuda(src, params, mix, mean_invstd)
-    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
-    _clip_mix_rows(mix, B)
-    out = torch.empty(B, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
-    lib.call("hyb_clips_u8_transform_mix", src.contiguous(), params.contiguous(), mix.contiguous(),
-             None if mean_invstd is None else mean_invstd.contiguous(), out, B, Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
-    return out
-
-
-def clip_transform_mix_fake(src, params, mix, mean_invstd, Tout, Ho, Wo):
-    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
-    _clip_mix_rows(mix, B)
-    return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
-
-
-def clip_transform_fake(src, params, mean_invstd, Tout, Ho, Wo):
-    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
-    return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
-
-
-def _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo, op="clip_transform_views"):
+def _clip_dims(op, src, params, mean_invstd, V, Tout, Ho=None, Wo=None):
+    """The one shape / dtype rule of hybrid::{op}: -> (B, Tin, Hin, Win, C) of src.  V None: one parameter row per clip, else V adjacent rows per
+    source clip.  Ho None (clip_luma_sums): no output extents, and the luma's C == 1 or C == 3 in place of C <= 4."""
     if src.dim() != 5 or src.dtype != torch.uint8:
         raise TypeError(f"hybrid::{op} reads uint8 clips [B,Tin,Hin,Win,C]")
     B, Tin, Hin, Win, C = src.shape
-    if V < 1 or B * V > 2 ** 31 - 1:
+    if V is not None and (V < 1 or B * V > 2 ** 31 - 1):
         raise ValueError(f"hybrid::{op} needs V >= 1 and B * V within int32, got V = {V} for {B} clips")
-    if params.dtype != torch.int32 or tuple(params.shape) != (B * V, 8):
-        raise TypeError(f"params must be int32 [{B * V},8]: V = {V} adjacent rows {{y0, x0, ch, cw, flip, t0, tstride, 0}} per source clip")
+    nrows = B if V is None else B * V
+    if params.dtype != torch.int32 or tuple(params.shape) != (nrows, 8):
+        raise TypeError(f"params must be int32 [{nrows},8]: " + (f"one row {_CLIP_ROW} per clip" if V is None else
+                                                                 f"V = {V} adjacent rows {_CLIP_ROW} per source clip"))
     if mean_invstd is not None and (mean_invstd.dtype != torch.float32 or tuple(mean_invstd.shape) != (2, C)):
         raise TypeError(f"mean_invstd must be float32 [2,{C}]: mean, then 1/std")
-    if C > 4 or max(Hin, Win, Ho, Wo) > 16384 or min(B, Tin, Hin, Win, C, Tout, Ho, Wo) <= 0:
+    if Ho is None:
+        if C not in (1, 3) or max(Hin, Win) > 16384 or min(B, Tin, Hin, Win, Tout) <= 0:
+            raise ValueError(f"hybrid::{op} needs C == 1 or C == 3, extents > 0 and Hin, Win <= 16384")
+    elif C > 4 or max(Hin, Win, Ho, Wo) > 16384 or min(B, Tin, Hin, Win, C, Tout, Ho, Wo) <= 0:
         raise ValueError(f"hybrid::{op} needs C <= 4, extents > 0 and Hin, Win, Ho, Wo <= 16384")
     return B, Tin, Hin, Win, C
 
 
-def clip_transform_views_op(src: Tensor, params: Tensor, mean_invstd: Optional[Tensor], V: int, Tout: int, Ho: int, Wo: int) -> Tensor:
-    """uint8 [B,Tin,Hin,Win,C] -> fp32 [B*V,Tout,C,Ho,Wo]: output clip b*V + v is hybrid::clip_transform's for row b*V + v applied to source
-    clip b, bit for bit (hyb_clips_u8_transform_views in include/hybrid_hip.h) -- the row order ClassificationMeter's views=V scores."""
-    _require_cuda(src, params, mean_invstd)
-    B, Tin, Hin, Win, C = _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo)
-    out = torch.empty(B * V, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
-    lib.call("hyb_clips_u8_transform_views", src.contiguous(), params.contiguous(), None if mean_invstd is None else mean_invstd.contiguous(), out,
-             B, int(V), Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
+# The per-clip row tensors a transform may take beside params: dtype, columns (None: Tout) and what the refusal says behind "must be ... [B,n]: "
+_CLIP_ROWS = {
+    "mix": (torch.int32, 8, "one row {partner, kind, by0, bx0, bh, bw, lam_bits, 0} per clip"),
+    "photo": (torch.int32, 16, "one row {brightness, contrast, saturation bits, order, gray, sigma bits, seed lo, seed hi, ey0, ex0, eh, ew, mode, "
+                               "0, 0, 0} per clip"),
+    "luma_sums": (torch.int64, None, "hybrid::clip_luma_sums of the same src, params and Tout"),
+}
+
+
+class _ClipOp(NamedTuple):
+    """One row per clip transform: the operator hybrid::{name} over the C entry point {symbol} (include/hybrid_hip.h has each rule).  Its backend
+    kernel, its fake kernel and ClipPipeline's call are built from the row (_clip_run, _clip_fake, clip_transform_into): uint8 [B,Tin,Hin,Win,C]
+    -> fp32 [B*V,Tout,C,Ho,Wo]."""
+    name: str
+    symbol: str
+    schema: str
+    rows: tuple         # (from the schema) the row tensors between params and mean_invstd, in the C order: (name in _CLIP_ROWS, optional)
+    views: bool         # (from the schema) takes V: V adjacent parameter rows per source clip, B * V output clips
+    luma: bool          # forms a luma: C == 1 or C == 3
+    says: str           # the operator the shared rule's messages name
+
+
+def _clip_op(name, symbol, schema, luma=False, says=None):
+    args = schema[1:schema.index(") ->")].split(", ")
+    at = args.index("Tensor? mean_invstd")
+    assert args[:2] == ["Tensor src", "Tensor params"] and args[at + 1:][-3:] == ["int Tout", "int Ho", "int Wo"], schema
+    return _ClipOp(name, symbol, schema, tuple((a.split()[1], a.startswith("Tensor? ")) for a in args[2:at]), args[at + 1] == "int V", luma, says or name)
+
+
+# Keyed by what ClipTransform.kernel() answers.  (hybrid::clip_transform_mix and _photo refuse through clip_transform's rule, under its name.)
+CLIP_OPS = {
+    "plain": _clip_op("clip_transform", "hyb_clips_u8_transform", "(Tensor src, Tensor params, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor"),
+    "mix": _clip_op("clip_transform_mix", "hyb_clips_u8_transform_mix",
+                    "(Tensor src, Tensor params, Tensor mix, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor", says="clip_transform"),
+    "photo": _clip_op("clip_transform_photo", "hyb_clips_u8_transform_photo",
+                      "(Tensor src, Tensor params, Tensor? mix, Tensor photo, Tensor? luma_sums, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor",
+                      luma=True, says="clip_transform"),
+    "views": _clip_op("clip_transform_views", "hyb_clips_u8_transform_views",
+                      "(Tensor src, Tensor params, Tensor? mean_invstd, int V, int Tout, int Ho, int Wo) -> Tensor"),
+    "aa": _clip_op("clip_transform_aa", "hyb_clips_u8_transform_aa", "(Tensor src, Tensor params, Tensor? mean_invstd, int V, int Tout, int Ho, int Wo) -> Tensor"),
+}
+
+
+def _clip_check(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo):
+    dims = _clip_dims(op.says, src, params, mean_invstd, V if op.views else None, Tout, Ho, Wo)
+    if op.luma and dims[4] not in (1, 3):
+        raise ValueError(f"hybrid::{op.name} needs C == 1 or C == 3 (the luma is defined for grey and RGB clips)")
+    for (name, optional), t in zip(op.rows, rows):
+        dtype, cols, what = _CLIP_ROWS[name]
+        shape = (dims[0], Tout if cols is None else cols)
+        if t is None and optional:
+            continue
+        if t is None or t.dtype != dtype or tuple(t.shape) != shape:
+            raise TypeError(f"{name} must be {str(dtype)[6:]} [{shape[0]},{shape[1]}]: {what}")
+    return dims
+
+
+def _clip_args(op, a):
+    """The operator's arguments behind params, as its schema lists them -> (rows, mean_invstd, V, Tout, Ho, Wo)"""
+    n = len(op.rows)
+    return (a[:n], *a[n:]) if op.views else (a[:n], a[n], 1, *a[n + 1:])
+
+
+def _clip_run(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo, out=None, stream=None):
+    """The one body of the five transforms: check, allocate [B*V,Tout,C,Ho,Wo] (or take `out`), one call of the row's entry point."""
+    _require_cuda(src, params, *rows, mean_invstd, out)
+    V, Tout, Ho, Wo = int(V), int(Tout), int(Ho), int(Wo)
+    B, Tin, Hin, Win, C = _clip_check(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo)
+    shape = (B * V, Tout, C, Ho, Wo)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise TypeError(f"hybrid::{op.name} writes contiguous float32 {list(shape)}")
+    lib.call(op.symbol, src.contiguous(), params.contiguous(), *[None if t is None else t.contiguous() for t in (*rows, mean_invstd)], out,
+             B, *((V,) if op.views else ()), Tin, Hin, Win, C, Tout, Ho, Wo, _stream() if stream is None else stream)
     return out
 
 
-def clip_transform_views_fake(src, params, mean_invstd, V, Tout, Ho, Wo):
-    B, Tin, Hin, Win, C = _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo)
+def _clip_fake(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo):
+    B, Tin, Hin, Win, C = _clip_check(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo)
     return src.new_empty((B * V, Tout, C, Ho, Wo), dtype=torch.float32)
 
 
-def clip_transform_views(src, params, mean_invstd, V, Tout, Ho, Wo):
-    """V evaluation views of every source clip in one launch: src uint8 [B,Tin,Hin,Win,C], params int32 [B*V,8] (ClipTransform.sample_views: V
-    adjacent rows per clip), mean_invstd fp32 [2,C] or None -> fp32 [B*V,Tout,C,Ho,Wo], equal to clip_transform on src.repeat_interleave(V, 0)
-    without that copy: what model.evaluate(x, y, meter, views=V) takes beside labels [B]."""
-    return torch.ops.hybrid.clip_transform_views(src, params, mean_invstd, int(V), int(Tout), int(Ho), int(Wo))
-
-
-def clip_transform_aa_op(src: Tensor, params: Tensor, mean_invstd: Optional[Tensor], V: int, Tout: int, Ho: int, Wo: int) -> Tensor:
-    """uint8 [B,Tin,Hin,Win,C] -> fp32 [B*V,Tout,C,Ho,Wo] like hybrid::clip_transform_views, resampled with the antialias filter of
-    F.interpolate(bilinear, align_corners=False, antialias=True) (hyb_clips_u8_transform_aa in include/hybrid_hip.h has the rule)."""
-    _require_cuda(src, params, mean_invstd)
-    B, Tin, Hin, Win, C = _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo, "clip_transform_aa")
-    out = torch.empty(B * V, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
-    lib.call("hyb_clips_u8_transform_aa", src.contiguous(), params.contiguous(), None if mean_invstd is None else mean_invstd.contiguous(), out,
-             B, int(V), Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
-    return out
-
-
-def clip_transform_aa_fake(src, params, mean_invstd, V, Tout, Ho, Wo):
-    B, Tin, Hin, Win, C = _clip_views_dims(src, params, mean_invstd, V, Tout, Ho, Wo, "clip_transform_aa")
-    return src.new_empty((B * V, Tout, C, Ho, Wo), dtype=torch.float32)
-
-
-def clip_transform_aa(src, params, mean_invstd, V, Tout, Ho, Wo):
-    """clip_transform_views with the antialiased resize (ClipTransform(antialias=True)): src uint8 [B,Tin,Hin,Win,C], params int32 [B*V,8] (V adjacent
-    rows per clip from ClipTransform.sample_views, or V = 1 and the rows of ClipTransform.sample), mean_invstd fp32 [2,C] or None -> fp32
-    [B*V,Tout,C,Ho,Wo].  Rows with ch == Ho and cw == Wo give clip_transform's bits."""
-    return torch.ops.hybrid.clip_transform_aa(src, params, mean_invstd, int(V), int(Tout), int(Ho), int(Wo))
+def clip_transform_into(kind, out, src, params, mean_invstd=None, V=1, stream=None, **rows):
+    """The transform ClipTransform.kernel() names, written into a tensor the caller keeps (ClipPipeline's slots) on `stream`: the operator's
+    checks and the operator's call.  rows: mix= / photo= / luma_sums=, of which the kind takes its own."""
+    op = CLIP_OPS[kind]
+    return _clip_run(op, src, params, [rows.get(name) for name, _ in op.rows], mean_invstd, V, out.shape[1], out.shape[3], out.shape[4], out, stream)
 
 
 def clip_transform(src, params, mean_invstd, Tout, Ho, Wo):
     """The device leg of ClipTransform on its own: src uint8 [B,Tin,Hin,Win,C], params int32 [B,8] (ClipTransform.sample), mean_invstd fp32
-    [2,C] or None -> fp32 [B,Tout,C,Ho,Wo] on the current stream (hybrid::clip_transform checks devices, dtypes and shapes)."""
+    [2,C] or None -> fp32 [B,Tout,C,Ho,Wo] on the current stream (hybrid::clip_transform checks devices, dtypes and shapes): crop, bilinear
+    resize, flip, temporal sub-sampling, / 255, normalise."""
     return torch.ops.hybrid.clip_transform(src, params, mean_invstd, int(Tout), int(Ho), int(Wo))
 
 
@@ -1287,66 +1290,18 @@ def clip_transform_mix(src, params, mix, mean_invstd, Tout, Ho, Wo):
     return torch.ops.hybrid.clip_transform_mix(src, params, mix, mean_invstd, int(Tout), int(Ho), int(Wo))
 
 
-def _clip_photo_rows(photo, B):
-    if photo.dtype != torch.int32 or tuple(photo.shape) != (B, 16):
-        raise TypeError(f"photo must be int32 [{B},16]: one row {{brightness, contrast, saturation bits, order, gray, sigma bits, seed lo, seed hi, "
-                        "ey0, ex0, eh, ew, mode, 0, 0, 0} per clip")
+def clip_transform_views(src, params, mean_invstd, V, Tout, Ho, Wo):
+    """V evaluation views of every source clip in one launch: src uint8 [B,Tin,Hin,Win,C], params int32 [B*V,8] (ClipTransform.sample_views: V
+    adjacent rows per clip), mean_invstd fp32 [2,C] or None -> fp32 [B*V,Tout,C,Ho,Wo], equal to clip_transform on src.repeat_interleave(V, 0)
+    without that copy, bit for bit: what model.evaluate(x, y, meter, views=V) takes beside labels [B]."""
+    return torch.ops.hybrid.clip_transform_views(src, params, mean_invstd, int(V), int(Tout), int(Ho), int(Wo))
 
 
-def _clip_photo_dims(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo):
-    B, Tin, Hin, Win, C = _clip_transform_dims(src, params, mean_invstd, Tout, Ho, Wo)
-    if C not in (1, 3):
-        raise ValueError("hybrid::clip_transform_photo needs C == 1 or C == 3 (the luma is defined for grey and RGB clips)")
-    if mix is not None:
-        _clip_mix_rows(mix, B)
-    _clip_photo_rows(photo, B)
-    if luma_sums is not None and (luma_sums.dtype != torch.int64 or tuple(luma_sums.shape) != (B, Tout)):
-        raise TypeError(f"luma_sums must be int64 [{B},{Tout}]: hybrid::clip_luma_sums of the same src, params and Tout")
-    return B, Tin, Hin, Win, C
-
-
-def clip_transform_photo_op(src: Tensor, params: Tensor, mix: Optional[Tensor], photo: Tensor, luma_sums: Optional[Tensor],
-                            mean_invstd: Optional[Tensor], Tout: int, Ho: int, Wo: int) -> Tensor:
-    """hybrid::clip_transform / _mix with colour jitter, grayscale, Gaussian noise and random erasing in the same pass
-    (hyb_clips_u8_transform_photo in include/hybrid_hip.h has the rule): one int32 row of 16 per clip."""
-    _require_cuda(src, params, mix, photo, luma_sums, mean_invstd)
-    B, Tin, Hin, Win, C = _clip_photo_dims(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo)
-    out = torch.empty(B, Tout, C, Ho, Wo, dtype=torch.float32, device=src.device)
-    lib.call("hyb_clips_u8_transform_photo", src.contiguous(), params.contiguous(), None if mix is None else mix.contiguous(), photo.contiguous(),
-             None if luma_sums is None else luma_sums.contiguous(), None if mean_invstd is None else mean_invstd.contiguous(), out,
-             B, Tin, Hin, Win, C, int(Tout), int(Ho), int(Wo), _stream())
-    return out
-
-
-def clip_transform_photo_fake(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo):
-    B, Tin, Hin, Win, C = _clip_photo_dims(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo)
-    return src.new_empty((B, Tout, C, Ho, Wo), dtype=torch.float32)
-
-
-def _clip_luma_dims(src, params, Tout):
-    if src.dim() != 5 or src.dtype != torch.uint8:
-        raise TypeError("hybrid::clip_luma_sums reads uint8 clips [B,Tin,Hin,Win,C]")
-    B, Tin, Hin, Win, C = src.shape
-    if params.dtype != torch.int32 or tuple(params.shape) != (B, 8):
-        raise TypeError(f"params must be int32 [{B},8]: one row {{y0, x0, ch, cw, flip, t0, tstride, 0}} per clip")
-    if C not in (1, 3) or max(Hin, Win) > 16384 or min(B, Tin, Hin, Win, Tout) <= 0:
-        raise ValueError("hybrid::clip_luma_sums needs C == 1 or C == 3, extents > 0 and Hin, Win <= 16384")
-    return B, Tin, Hin, Win, C
-
-
-def clip_luma_sums_op(src: Tensor, params: Tensor, Tout: int) -> Tensor:
-    """int64 [B,Tout]: the integer luma sum (2989 R + 5870 G + 1140 B; grey: 10000 * value) over the crop of every output frame's source frame
-    (hyb_clips_u8_luma_sums in include/hybrid_hip.h), from which hybrid::clip_transform_photo forms its contrast pivot."""
-    _require_cuda(src, params)
-    B, Tin, Hin, Win, C = _clip_luma_dims(src, params, Tout)
-    out = torch.empty(B, Tout, dtype=torch.int64, device=src.device)
-    lib.call("hyb_clips_u8_luma_sums", src.contiguous(), params.contiguous(), out, B, Tin, Hin, Win, C, int(Tout), _stream())
-    return out
-
-
-def clip_luma_sums_fake(src, params, Tout):
-    B = _clip_luma_dims(src, params, Tout)[0]
-    return src.new_empty((B, Tout), dtype=torch.int64)
+def clip_transform_aa(src, params, mean_invstd, V, Tout, Ho, Wo):
+    """clip_transform_views with the antialiased resize (ClipTransform(antialias=True)): src uint8 [B,Tin,Hin,Win,C], params int32 [B*V,8] (V adjacent
+    rows per clip from ClipTransform.sample_views, or V = 1 and the rows of ClipTransform.sample), mean_invstd fp32 [2,C] or None -> fp32
+    [B*V,Tout,C,Ho,Wo].  Rows with ch == Ho and cw == Wo give clip_transform's bits."""
+    return torch.ops.hybrid.clip_transform_aa(src, params, mean_invstd, int(V), int(Tout), int(Ho), int(Wo))
 
 
 def clip_transform_photo(src, params, mix, photo, luma_sums, mean_invstd, Tout, Ho, Wo):
@@ -1354,6 +1309,21 @@ def clip_transform_photo(src, params, mix, photo, luma_sums, mean_invstd, Tout, 
     the same pass.  mix: rows of clip_transform_mix or None; luma_sums: clip_luma_sums(src, params, Tout), needed when a contrast factor may
     differ from 1, else None."""
     return torch.ops.hybrid.clip_transform_photo(src, params, mix, photo, luma_sums, mean_invstd, int(Tout), int(Ho), int(Wo))
+
+
+def clip_luma_sums_op(src: Tensor, params: Tensor, Tout: int) -> Tensor:
+    """int64 [B,Tout]: the integer luma sum (2989 R + 5870 G + 1140 B; grey: 10000 * value) over the crop of every output frame's source frame
+    (hyb_clips_u8_luma_sums in include/hybrid_hip.h), from which hybrid::clip_transform_photo forms its contrast pivot."""
+    _require_cuda(src, params)
+    B, Tin, Hin, Win, C = _clip_dims("clip_luma_sums", src, params, None, None, Tout)
+    out = torch.empty(B, Tout, dtype=torch.int64, device=src.device)
+    lib.call("hyb_clips_u8_luma_sums", src.contiguous(), params.contiguous(), out, B, Tin, Hin, Win, C, int(Tout), _stream())
+    return out
+
+
+def clip_luma_sums_fake(src, params, Tout):
+    B = _clip_dims("clip_luma_sums", src, params, None, None, Tout)[0]
+    return src.new_empty((B, Tout), dtype=torch.int64)
 
 
 def clip_luma_sums(src, params, Tout):
@@ -1833,20 +1803,15 @@ _LIB.impl("convstage_infer", _inference_only("convstage_infer"), "Autograd")
 _define("backbone_infer", "(Tensor x, Tensor[] weights, Tensor[] gammas, Tensor[] betas, Tensor[] running_means, Tensor[] running_vars, float eps, "
         "int dt) -> Tensor", backbone_infer_op, backbone_infer_fake)
 _LIB.impl("backbone_infer", _inference_only("backbone_infer"), "Autograd")
-_define("clip_transform", "(Tensor src, Tensor params, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor", clip_transform_op, clip_transform_fake)
-_LIB.impl("clip_transform", _inference_only("clip_transform"), "Autograd")
-_define("clip_transform_mix", "(Tensor src, Tensor params, Tensor mix, Tensor? mean_invstd, int Tout, int Ho, int Wo) -> Tensor", clip_transform_mix_op,
-        clip_transform_mix_fake)
-_LIB.impl("clip_transform_mix", _inference_only("clip_transform_mix"), "Autograd")
-_define("clip_transform_photo", "(Tensor src, Tensor params, Tensor? mix, Tensor photo, Tensor? luma_sums, Tensor? mean_invstd, int Tout, int Ho, int Wo) "
-        "-> Tensor", clip_transform_photo_op, clip_transform_photo_fake)
-_LIB.impl("clip_transform_photo", _inference_only("clip_transform_photo"), "Autograd")
-_define("clip_transform_views", "(Tensor src, Tensor params, Tensor? mean_invstd, int V, int Tout, int Ho, int Wo) -> Tensor", clip_transform_views_op,
-        clip_transform_views_fake)
-_LIB.impl("clip_transform_views", _inference_only("clip_transform_views"), "Autograd")
-_define("clip_transform_aa", "(Tensor src, Tensor params, Tensor? mean_invstd, int V, int Tout, int Ho, int Wo) -> Tensor", clip_transform_aa_op,
-        clip_transform_aa_fake)
-_LIB.impl("clip_transform_aa", _inference_only("clip_transform_aa"), "Autograd")
+def _define_clip_op(op):
+    """The operator of one CLIP_OPS row: backend and fake kernel over _clip_run / _clip_fake, inference only."""
+    _define(op.name, op.schema, lambda src, params, *a: _clip_run(op, src, params, *_clip_args(op, a)),
+            lambda src, params, *a: _clip_fake(op, src, params, *_clip_args(op, a)))
+    _LIB.impl(op.name, _inference_only(op.name), "Autograd")
+
+
+for _op in CLIP_OPS.values():
+    _define_clip_op(_op)
 _define("clip_luma_sums", "(Tensor src, Tensor params, int Tout) -> Tensor", clip_luma_sums_op, clip_luma_sums_fake)
 _LIB.impl("clip_luma_sums", _inference_only("clip_luma_sums"), "Autograd")
 _TEMPORAL_FRONT = "Tensor h, Tensor token_w, Tensor token_b, Tensor[] enc_params, Tensor head_w, Tensor head_b, Tensor? mask"
