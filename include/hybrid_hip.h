@@ -1094,6 +1094,58 @@ int hyb_lamb_step_dev(int count, float* const* params, const float* const* grads
                       long long k, long long step, long long* step_inc, unsigned int* advance_ticket, const float* clip /* or NULL */,
                       const long long* guard /* [2], or NULL */, const float* trust /* [count, 3] */, void* stream);
 
+/* ---- SGD with momentum, and LARS, in the fused step (torch.optim.SGD's rule; timm's Lars with trust_clip = False) ----------------------------
+ * (New symbols only; hyb_abi_version() stays 9.)  One state tensor per parameter, the momentum buffer: the launch moves 5 x 4 bytes per
+ * parameter (it reads p, g, buf and writes p, buf) where the AdamW launch moves 7 x 4.  The device block `double hyper[groups, 6]` is read
+ * as {lr, momentum, dampening, lars_eps, weight_decay, max_grad_norm}: hyb_adamw_hyper_set, hyb_adamw_hyper_set_groups, hyb_adamw_ema_set,
+ * the four hyb_grad_norm* and hyb_grad_accumulate serve SGD unchanged (their range checks -- columns 1 and 2 in [0, 1), column 3 >= 0 -- are
+ * the ranges wanted here).
+ *
+ * The rule.  Per element of a tensor at applied step t -- t = step + *step_inc (/ k when accumulating) - skipped_total, the step number of
+ * the AdamW launch -- with the effective gradient exactly as the AdamW launch forms it (acc / grads / k as in hyb_adamw_step_dev_acc, then
+ * times clip[1] when clip is given), in fp32 with contraction off and every fused multiply-add written out:
+ *     G    = eff_grad(acc, g, 1 / k) * clip
+ *     d    = fmaf(wd32, p, G)                      coupled L2 decay, torch.optim.SGD's
+ *     d    = r * d                                 LARS only (trust != NULL); r = trust[3 i + 2], the tensor's trust ratio
+ *     buf' = (t == 1) ? d : fmaf(mu32, buf, omt32 * d)
+ *     s    = nesterov ? fmaf(mu32, buf', d) : (mu32 == 0) ? d : buf'
+ *     p'   = fmaf(-lr32, s, p)
+ *     e'   = fmaf(d32, e, omd32 * p')              where the call keeps the average (ema, ema_hyper: as hyb_adamw_step_dev_ema)
+ * mu32 = (float)momentum, omt32 = (float)(1.0 - dampening), wd32 = (float)weight_decay, lr32 = (float)lr: each rounded once from the doubles
+ * of the tensor's row of hyper, by thread 0 of the workgroup when the launch runs.  At t == 1 the old buffer value does not reach the
+ * result (a select, not a product with 0): a buffer full of NaNs gives buf' = d.  With momentum == 0 torch.optim.SGD keeps no buffer and
+ * steps on d itself, whatever the dampening: so does this rule (s = d, again a select); the buffer is still written and never read back into p.
+ *
+ * hyb_sgd_step_dev: every variant behind one entry point, the arguments of hyb_adamw_step_dev_groups with ONE state table (momentum_buf),
+ * `nesterov` (0 or 1, by value) and `trust` (NULL: plain SGD; else the trust_out of this step's hyb_lars_trust call, not read on a guarded
+ * skip).  NULL where a call has no such thing, under the rule of the AdamW steps: grads (acc holds the whole sum), acc (then k == 1 and
+ * grads != NULL), ema together with ema_hyper, group (hyper / ema_hyper are then the one group's rows, groups is not read), step_inc,
+ * advance_ticket (needs step_inc), clip, guard (needs clip).  A guarded skip stores nothing to p / buf / e, stores +0.0f over the
+ * accumulators and takes its ticket; the accumulators are left +0.0f by every step; the last launch of the call advances the counter.
+ * 80 tensors per launch, 72 with acc and ema together.  -1 as hyb_adamw_step_dev_groups, and for a nesterov other than 0 or 1. */
+int hyb_sgd_step_dev(int count, float* const* params, const float* const* grads /* or NULL */, float* const* momentum_buf,
+                     float* const* acc /* or NULL */, float* const* ema /* or NULL */, const long long* numel,
+                     const unsigned char* group /* or NULL */, int groups, const double* hyper, const double* ema_hyper /* or NULL */,
+                     long long k, long long step, long long* step_inc, unsigned int* advance_ticket, const float* clip /* or NULL */,
+                     const long long* guard /* [2], or NULL */, int nesterov, const float* trust /* [count, 3], or NULL */, void* stream);
+/* hyb_lars_trust: LARS's layer-wise ratios for the hyb_sgd_step_dev call that follows (the same params / grads / acc / numel / group /
+ * groups / hyper / k / clip / guard).  Per tensor, wn = |p| and gn = |G| (L2 norms, G the effective, clipped gradient above):
+ *     r = trust_coeff wn / (gn + wn wd + eps)      in double from the fp32 norms, rounded once
+ *     r = 1  where wn == 0 or gn == 0, and for every tensor of a group with weight_decay == 0 unless always_adapt
+ * wd and eps (columns 4 and 3) are read from the tensor's row of hyper when the launch runs; trust_coeff (> 0, finite) and always_adapt
+ * (0 or 1) travel by value.  A read-only pass (2 x 4 bytes per parameter, 3 x 4 with acc and grads): p^2 and G^2 summed like hyb_grad_norm
+ * sums g^2 -- 4096-element chunks in a fixed order, two fp32 partials per chunk, a tensor's partials in double in a fixed order by a
+ * second launch (one workgroup per tensor) -- so the ratios are bit-identical from run to run and independent of how the table is cut
+ * into launches.  trust_out: DEVICE float [count, 3], row i = {wn_i, gn_i, r_i}.  On a step the guard skips, trust_out is unspecified (and
+ * unread).  partials: hyb_lars_trust_workspace(count, numel) floats (2 per chunk; 0 for bad arguments), no state kept between calls.
+ * -1 under the rule of the step (acc with k, guard needs clip, the group range), for trust_coeff or always_adapt out of range, and for
+ * partials or trust_out NULL. */
+size_t hyb_lars_trust_workspace(int count, const long long* numel);
+int hyb_lars_trust(int count, float* const* params, const float* const* grads /* or NULL */, float* const* acc /* or NULL */,
+                   const long long* numel, const unsigned char* group /* or NULL */, int groups, const double* hyper, long long k,
+                   const float* clip /* or NULL */, const long long* guard /* [2], or NULL */, double trust_coeff, int always_adapt,
+                   float* partials, float* trust_out /* [count, 3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,8 @@
 // hyb_adamw_hyper_set_groups writes the rows of several groups in one launch.
 // LAMB: hyb_lamb_trust forms every tensor's trust ratio r = |p| / |u| on the device (a read-only chunk pass and a one-workgroup-per-tensor
 // final launch, 4 x 4 bytes read per parameter), hyb_lamb_step_dev is the AdamW launch at the rate r * lr per tensor (LAMB, below).
+// SGD: hyb_sgd_step_dev is torch.optim.SGD's rule (momentum, dampening, Nesterov, coupled weight decay) in a launch of the same shape with one
+// state tensor, 5 x 4 bytes per parameter; hyb_lars_trust forms LARS's layer-wise ratios for it (SGD with momentum, and LARS, below).
 #include <algorithm>
 #include <type_traits>
 
@@ -784,6 +786,320 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(AccumArgs a) {
     }
 }
 
+// ---- SGD with momentum, and LARS (hyb_sgd_step_dev / hyb_lars_trust; torch.optim.SGD's rule, timm's Lars without trust clipping) ---------------
+// One state tensor per parameter, the momentum buffer: 5 x 4 bytes per parameter where AdamW moves 7 x 4.  The hyper row is the same block,
+// read as {lr, momentum, dampening, lars_eps, weight_decay, max_grad_norm}; thread 0 rounds mu32 = (float)momentum, omt32 = (float)(1.0 -
+// dampening), wd32 and lr32 once each from its doubles.  Per element at applied step t (adam_step_number), fp32, contraction off, every fused
+// multiply-add written out:
+//     G    = eff_grad(acc, g, inv_k) * clip
+//     d    = fmaf(wd32, p, G)                      coupled L2 decay
+//     d    = r * d                                 LARS: r is the tensor's trust ratio (r == 1.0f: the SGD step bit for bit)
+//     buf' = t == 1 ? d : fmaf(mu32, buf, omt32 * d)            a select: whatever the buffer held before the first step never reaches buf'
+//     s    = nesterov ? fmaf(mu32, buf', d) : mu32 == 0 ? d : buf'      (without momentum torch.optim.SGD steps on d: dampening is not applied)
+//     p'   = fmaf(-lr32, s, p)
+//     e'   = adam_ema_one(e, p', d32, omd32)
+// The table is one type per (EMA, ACCUM) with every optional member in it (group, guard, trust are read by the instantiations that have
+// them): 80 tensors per launch, 72 with the average and the accumulators.
+struct SgdTensor { float* p; const float* g; float* b; long long n; };
+template <bool EMA, bool ACCUM> struct SgdArgs {
+    static constexpr int MAX = EMA && ACCUM ? 72 : ADAM_MAX;
+    SgdTensor t[MAX];
+    int chunk_begin[MAX + 1];
+    int count;
+    const double* hyper;
+    const long long* step_inc;
+    long long* advance;
+    unsigned int* ticket;
+    long long step;
+    const float* clip;
+    unsigned char group[MAX];
+    float* e[EMA ? MAX : 1];
+    const double* ema_hyper;
+    float* acc[ACCUM ? MAX : 1];
+    long long k;
+    float inv_k;
+    int nesterov;                // 0 or 1, by value: uniform over the launch
+    const long long* guard;
+    const float* trust;          // LARS: the trust block of hyb_lars_trust, float [3] per tensor of the WHOLE call, and the index of the
+    int first;                   // slice's first tensor in it
+};
+static_assert(sizeof(SgdArgs<false, false>) <= 4096 && sizeof(SgdArgs<true, false>) <= 4096 && sizeof(SgdArgs<false, true>) <= 4096 &&
+              sizeof(SgdArgs<true, true>) <= 4096, "the tensor table travels in the kernel arguments");
+
+struct SgdScalars { float mu, omt, wd, lr, clip, r; bool first, nesterov, plain; };      // plain: mu32 == 0, the step is d itself
+
+template <bool LARS> __device__ __forceinline__ void sgd_dev_one(float& p, float g, float& b, const SgdScalars& a) {
+#pragma clang fp contract(off)
+    g = g * a.clip;
+    float d = __builtin_fmaf(a.wd, p, g);
+    if constexpr (LARS) d = a.r * d;
+    const float nb = a.first ? d : __builtin_fmaf(a.mu, b, a.omt * d);
+    const float s = a.nesterov ? __builtin_fmaf(a.mu, nb, d) : a.plain ? d : nb;
+    b = nb;
+    p = __builtin_fmaf(-a.lr, s, p);
+}
+
+// adamw_dev_kernel's frame around sgd_dev_one: the chunk -> tensor -> thread mapping, a full chunk's 16-byte loads in front of the scalar
+// phase, the 16-byte path with its 4-element and element-wise remainders, the accumulator stored +0.0f, the guard's skip (no store to
+// p / buf / e, accumulators zeroed, ticket taken) and adam_dev_advance on the call's last launch.
+template <bool EMA, int ACC = GRAD_PLAIN, bool GUARD = false, bool GROUPS = false, bool LARS = false> __global__ __launch_bounds__(256)
+void sgd_dev_kernel(SgdArgs<EMA, ACC != GRAD_PLAIN> a) {
+    constexpr bool ACCUM = ACC != GRAD_PLAIN, HAS_G = ACC != GRAD_ACC;
+    __shared__ float s_sc[8];
+    __shared__ int s_flag[2];                                      // skip, t == 1
+    int ti = 0;
+    for (int i = 1; i < a.count; ++i)
+        if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
+    const SgdTensor t = a.t[ti];
+    float* te = nullptr;
+    if constexpr (EMA) te = a.e[ti];
+    float* ta = nullptr;
+    float inv_k = 1.f;
+    if constexpr (ACCUM) { ta = a.acc[ti]; inv_k = a.inv_k; }
+    const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
+    const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.b | (uintptr_t)te | (uintptr_t)ta) & 15) == 0);
+    constexpr int NK = ADAM_CHUNK / (256 * 4);
+    const bool full = vec && base + ADAM_CHUNK <= t.n;
+    f32x4 p[NK], b[NK], g[HAS_G ? NK : 1], ea[EMA ? NK : 1], ac[ACCUM ? NK : 1];
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            p[k] = *reinterpret_cast<const f32x4*>(t.p + i); b[k] = *reinterpret_cast<const f32x4*>(t.b + i);
+            if constexpr (HAS_G) g[k] = *reinterpret_cast<const f32x4*>(t.g + i);
+            if constexpr (EMA) ea[k] = *reinterpret_cast<const f32x4*>(te + i);
+            if constexpr (ACCUM) ac[k] = *reinterpret_cast<const f32x4*>(ta + i);
+        }
+    }
+    if (threadIdx.x == 0) {
+        long long skipped = 0ll;
+        bool skip = false;
+        if constexpr (GUARD) { skip = a.guard[0] != 0ll; skipped = a.guard[1]; }
+        s_flag[0] = skip ? 1 : 0;
+        if (!skip) {
+#pragma clang fp contract(off)
+            const double* hyper = a.hyper;
+            if constexpr (GROUPS) hyper += HYPER_N * (int)a.group[ti];
+            s_sc[0] = (float)hyper[1];
+            s_sc[1] = (float)(1.0 - hyper[2]);
+            s_sc[2] = (float)hyper[4];
+            s_sc[3] = (float)hyper[0];
+            s_sc[4] = a.clip ? a.clip[1] : 1.0f;
+            s_sc[5] = 1.0f;
+            if constexpr (LARS) s_sc[5] = a.trust[3ll * (a.first + ti) + 2];
+            s_flag[1] = adam_step_number<ACCUM>(a, skipped) == 1ll ? 1 : 0;
+            if constexpr (EMA) {
+                const double* ema_hyper = a.ema_hyper;
+                if constexpr (GROUPS) ema_hyper += 2 * (int)a.group[ti];
+                adam_ema_scalars<ACCUM>(a, ema_hyper, s_sc + 6, skipped);
+            }
+        }
+    }
+    __syncthreads();
+    if constexpr (GUARD) {
+        if (s_flag[0]) {                                           // uniform over the workgroup (and over the launch)
+            if constexpr (ACCUM) {
+#pragma unroll 1
+                for (int k = 0; k < NK; ++k) {
+                    const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+                    if (i >= t.n) break;
+                    if (vec && i + 4 <= t.n) *reinterpret_cast<f32x4*>(ta + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+                    else for (long long e = i; e < i + 4 && e < t.n; ++e) ta[e] = 0.f;
+                }
+            }
+            adam_dev_advance(a);
+            return;
+        }
+    }
+    const SgdScalars sc{s_sc[0], s_sc[1], s_sc[2], s_sc[3], s_sc[4], s_sc[5], s_flag[1] != 0, a.nesterov != 0, s_sc[0] == 0.f};
+    float d32 = 0.f, omd32 = 0.f;
+    if constexpr (EMA) { d32 = s_sc[6]; omd32 = s_sc[7]; }
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float pj = p[k][j], bj = b[k][j];
+                sgd_dev_one<LARS>(pj, eff_grad<ACC>(ACCUM ? ac[k][j] : 0.f, HAS_G ? g[k][j] : 0.f, inv_k), bj, sc);
+                p[k][j] = pj; b[k][j] = bj;
+                if constexpr (EMA) ea[k][j] = adam_ema_one(ea[k][j], pj, d32, omd32);
+            }
+            *reinterpret_cast<f32x4*>(t.p + i) = p[k]; *reinterpret_cast<f32x4*>(t.b + i) = b[k];
+            if constexpr (EMA) *reinterpret_cast<f32x4*>(te + i) = ea[k];
+            if constexpr (ACCUM) *reinterpret_cast<f32x4*>(ta + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            if (i >= t.n) break;
+            if (vec && i + 4 <= t.n) {
+                f32x4 pp = *reinterpret_cast<f32x4*>(t.p + i), bb = *reinterpret_cast<f32x4*>(t.b + i);
+                f32x4 gg{}, ee{}, aa{};
+                if constexpr (HAS_G) gg = *reinterpret_cast<const f32x4*>(t.g + i);
+                if constexpr (EMA) ee = *reinterpret_cast<const f32x4*>(te + i);
+                if constexpr (ACCUM) aa = *reinterpret_cast<const f32x4*>(ta + i);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float pj = pp[j], bj = bb[j];
+                    sgd_dev_one<LARS>(pj, eff_grad<ACC>(aa[j], gg[j], inv_k), bj, sc);
+                    pp[j] = pj; bb[j] = bj;
+                    if constexpr (EMA) ee[j] = adam_ema_one(ee[j], pj, d32, omd32);
+                }
+                *reinterpret_cast<f32x4*>(t.p + i) = pp; *reinterpret_cast<f32x4*>(t.b + i) = bb;
+                if constexpr (EMA) *reinterpret_cast<f32x4*>(te + i) = ee;
+                if constexpr (ACCUM) *reinterpret_cast<f32x4*>(ta + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+            } else {
+                for (long long e = i; e < i + 4 && e < t.n; ++e) {
+                    float ge = 0.f, ae = 0.f;
+                    if constexpr (HAS_G) ge = t.g[e];
+                    if constexpr (ACCUM) { ae = ta[e]; ta[e] = 0.f; }
+                    sgd_dev_one<LARS>(t.p[e], eff_grad<ACC>(ae, ge, inv_k), t.b[e], sc);
+                    if constexpr (EMA) te[e] = adam_ema_one(te[e], t.p[e], d32, omd32);
+                }
+            }
+        }
+    }
+    adam_dev_advance(a);
+}
+
+// LARS: per tensor r = trust_coeff |p| / (|G| + wd |p| + eps), G the effective, clipped gradient of THIS step.  lars_trust_kernel is a
+// read-only chunk pass over p and G (2 x 4 bytes per parameter, 3 x 4 when accumulating) that sums p^2 and G^2 as grad_chunk_sumsq sums g^2:
+// a thread's 16 elements in index order with fmaf (the mapping of sgd_dev_kernel, aligned or not), wave_sum, the four wave totals pairwise
+// -> partials[2 chunk], partials[2 chunk + 1]; it needs no hyper-parameter, only the clip coefficient and the guard's decision.
+// lars_trust_final_kernel, one workgroup per tensor in a launch of its own (the hand-off: see the note on grad_norm above), adds the
+// tensor's partials in double in lamb_trust_final_kernel's order and writes trust_out[i] = {|p|, |G|, r}; weight_decay and lars_eps are
+// read from the tensor's row of hyper there.  Bit-identical from run to run, independent of how the table is sliced.
+struct LarsTrustArgs {
+    const float* p[ADAM_MAX];
+    const float* g[ADAM_MAX];
+    const float* acc[ADAM_MAX];
+    long long n[ADAM_MAX];
+    int chunk_begin[ADAM_MAX + 1];
+    int count;
+    float inv_k;
+    const float* clip;
+    const long long* guard;      // NULL, or the guard block: a skipped step reads no trust value
+    int chunk_offset;            // index of this launch's first chunk among all chunks of the call
+    float* partials;
+};
+static_assert(sizeof(LarsTrustArgs) <= 4096, "the tensor table travels in the kernel arguments");
+
+__device__ __forceinline__ void lars_trust_one(float p, float g, float clip, float& sp, float& sg) {
+#pragma clang fp contract(off)
+    g = g * clip;
+    sp = __builtin_fmaf(p, p, sp);
+    sg = __builtin_fmaf(g, g, sg);
+}
+
+template <int ACC> __global__ __launch_bounds__(256) void lars_trust_kernel(LarsTrustArgs a) {
+    constexpr bool ACCUM = ACC != GRAD_PLAIN, HAS_G = ACC != GRAD_ACC;
+    __shared__ float s_clip;
+    __shared__ float s_wave[8];
+    __shared__ int s_skip;
+    int ti = 0;
+    for (int i = 1; i < a.count; ++i)
+        if ((int)blockIdx.x >= a.chunk_begin[i]) ti = i;
+    const float* __restrict__ tp = a.p[ti];
+    const float* __restrict__ tg = a.g[ti];
+    const float* __restrict__ ta = a.acc[ti];
+    const long long n = a.n[ti];
+    const float inv_k = a.inv_k;
+    const long long base = (long long)(blockIdx.x - a.chunk_begin[ti]) * ADAM_CHUNK;
+    const bool vec = ((((uintptr_t)tp | (uintptr_t)tg | (uintptr_t)ta) & 15) == 0);
+    constexpr int NK = ADAM_CHUNK / (256 * 4);
+    const bool full = vec && base + ADAM_CHUNK <= n;
+    f32x4 p[NK], g[HAS_G ? NK : 1], ac[ACCUM ? NK : 1];
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            p[k] = *reinterpret_cast<const f32x4*>(tp + i);
+            if constexpr (HAS_G) g[k] = *reinterpret_cast<const f32x4*>(tg + i);
+            if constexpr (ACCUM) ac[k] = *reinterpret_cast<const f32x4*>(ta + i);
+        }
+    }
+    if (threadIdx.x == 0) {
+        const bool skip = a.guard && a.guard[0] != 0ll;
+        s_skip = skip ? 1 : 0;
+        s_clip = !skip && a.clip ? a.clip[1] : 1.0f;
+    }
+    __syncthreads();
+    float* out = a.partials + 2ll * (a.chunk_offset + (int)blockIdx.x);
+    if (s_skip) {                                                  // zeros (r = 1), and no pass over poison
+        if (threadIdx.x == 0) { out[0] = 0.f; out[1] = 0.f; }
+        return;
+    }
+    const float clip = s_clip;
+    float sp = 0.f, sg = 0.f;
+    if (full) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                lars_trust_one(p[k][j], eff_grad<ACC>(ACCUM ? ac[k][j] : 0.f, HAS_G ? g[k][j] : 0.f, inv_k), clip, sp, sg);
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < NK; ++k) {
+            const long long i = base + ((long long)k * 256 + threadIdx.x) * 4;
+            for (long long e = i; e < i + 4 && e < n; ++e) {
+                float ge = 0.f, ae = 0.f;
+                if constexpr (HAS_G) ge = tg[e];
+                if constexpr (ACCUM) ae = ta[e];
+                lars_trust_one(tp[e], eff_grad<ACC>(ae, ge, inv_k), clip, sp, sg);
+            }
+        }
+    }
+    sp = wave_sum(sp);
+    sg = wave_sum(sg);
+    if ((threadIdx.x & 63) == 0) { s_wave[threadIdx.x >> 6] = sp; s_wave[4 + (threadIdx.x >> 6)] = sg; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[0] = (s_wave[0] + s_wave[1]) + (s_wave[2] + s_wave[3]);
+        out[1] = (s_wave[4] + s_wave[5]) + (s_wave[6] + s_wave[7]);
+    }
+}
+
+struct LarsFinalArgs {
+    int chunk_begin[LAMB_FINAL_MAX + 1];      // tensor first + i owns the chunks chunk_begin[i] .. chunk_begin[i + 1] of the whole call
+    unsigned char group[LAMB_FINAL_MAX];      // its row of hyper (all zero: hyper is the one row)
+    int first;
+    int always_adapt;
+    double trust_coeff;
+    const float* partials;
+    const double* hyper;
+    float* trust_out;
+};
+static_assert(sizeof(LarsFinalArgs) <= 4096, "the tensor table travels in the kernel arguments");
+
+__global__ __launch_bounds__(256) void lars_trust_final_kernel(LarsFinalArgs a) {
+    __shared__ double s_sum[2][256];
+    const int c0 = a.chunk_begin[blockIdx.x], c1 = a.chunk_begin[blockIdx.x + 1];
+    double sp = 0.0, sg = 0.0;
+    for (int c = c0 + (int)threadIdx.x; c < c1; c += 256) {         // thread t takes t, t + 256, ... ascending
+        sp += (double)a.partials[2ll * c];
+        sg += (double)a.partials[2ll * c + 1];
+    }
+    s_sum[0][threadIdx.x] = sp;
+    s_sum[1][threadIdx.x] = sg;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+        double tp = 0.0, tg = 0.0;
+        for (int i = 0; i < 256; ++i) { tp += s_sum[0][i]; tg += s_sum[1][i]; }      // the 256 thread sums in ascending order
+        const float w_norm = (float)sqrt(tp), g_norm = (float)sqrt(tg);
+        const double* hyper = a.hyper + HYPER_N * (int)a.group[blockIdx.x];
+        const double eps = hyper[3], wd = hyper[4];
+        const bool adapt = (wd != 0.0 || a.always_adapt != 0) && w_norm > 0.f && g_norm > 0.f;
+        const double decayed = (double)w_norm * wd;
+        float* out = a.trust_out + 3ll * (a.first + (int)blockIdx.x);
+        out[0] = w_norm;
+        out[1] = g_norm;
+        out[2] = adapt ? (float)(a.trust_coeff * (double)w_norm / (((double)g_norm + decayed) + eps)) : 1.0f;
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
 // Every entry point below works on a table of `count` tensors.  Three helpers are all of them share: table_ok (the table is sound),
 // for_each_slice (the table in launches of at most a kernel's capacity) and, for the device-path steps, one descriptor (AdamStep) with one
@@ -832,11 +1148,18 @@ struct AdamStep {
     long long k, step; long long* step_inc; unsigned int* ticket;
     const float* clip; const long long* guard;
     const float* trust;          // NULL: AdamW.  The trust block of hyb_lamb_trust, float [count, 3]: the LAMB step (hyb_lamb_step_dev)
+    // The SGD calls (hyb_sgd_step_dev, hyb_lars_trust) are the same descriptor: exp_avg is the momentum buffer, exp_avg_sq stays NULL, trust
+    // is hyb_lars_trust's block.  RULE_LARS_PASS: the read-only pass, which takes no state table at all.
+    int rule;
+    int nesterov;
 };
+constexpr int RULE_ADAM = 0, RULE_SGD = 1, RULE_LARS_PASS = 2;
 
 // the one rule; an entry point adds only what its own prototype promises (hyb_adamw_step_dev: grads, ...)
 bool adam_step_ok(const AdamStep& s) {
-    if (!table_ok(s.count, s.numel, s.params, s.exp_avg, s.exp_avg_sq) || !s.hyper || s.step < 1 || s.k < 1 || !(s.acc || (s.k == 1 && s.grads)) ||
+    const bool tables = s.rule == RULE_ADAM ? table_ok(s.count, s.numel, s.params, s.exp_avg, s.exp_avg_sq)
+                      : s.rule == RULE_SGD  ? table_ok(s.count, s.numel, s.params, s.exp_avg) : table_ok(s.count, s.numel, s.params);
+    if (!tables || !s.hyper || s.step < 1 || s.k < 1 || !(s.acc || (s.k == 1 && s.grads)) || (s.nesterov != 0 && s.nesterov != 1) ||
         (s.ema != nullptr) != (s.ema_hyper != nullptr) || (s.ticket && !s.step_inc) || (s.guard && !s.clip) ||
         (s.group && (s.groups < 1 || s.groups > ADAM_GROUPS_MAX))) return false;     // (the LAMB calls take group or NULL: the range is the rule's)
     for (int i = 0; i < s.count; ++i)
@@ -934,6 +1257,81 @@ int lamb_trust_call(const AdamStep& s, int always_adapt, float* partials, float*
         if (s.grads) return lamb_trust_launch<GRAD_ACC_G, GROUPS>(s, always_adapt, partials, trust_out, stream);
         return lamb_trust_launch<GRAD_ACC, GROUPS>(s, always_adapt, partials, trust_out, stream);
     });
+}
+
+// one instantiation of sgd_dev_kernel over the whole table; the last launch of the call advances the counter
+template <bool EMA, int ACC, bool GUARD, bool GROUPS, bool LARS> int sgd_dev_launch(const AdamStep& s, void* stream) {
+    using Args = SgdArgs<EMA, ACC != GRAD_PLAIN>;
+    return for_each_slice(s.count, s.numel, Args::MAX, [&](int first, int n, const int* chunk_begin, bool last) {
+        Args a{};
+        for (int i = 0; i < n; ++i) {
+            a.t[i] = SgdTensor{s.params[first + i], ACC == GRAD_ACC ? nullptr : s.grads[first + i], s.exp_avg[first + i], s.numel[first + i]};
+            if constexpr (EMA) a.e[i] = s.ema[first + i];
+            if constexpr (ACC != GRAD_PLAIN) a.acc[i] = s.acc[first + i];
+            if constexpr (GROUPS) a.group[i] = s.group[first + i];
+        }
+        std::copy(chunk_begin, chunk_begin + n + 1, a.chunk_begin);
+        a.count = n;
+        a.hyper = s.hyper; a.step_inc = s.step_inc; a.step = s.step; a.clip = s.clip; a.ema_hyper = s.ema_hyper;
+        a.k = s.k; a.inv_k = (float)(1.0 / (double)s.k);
+        a.nesterov = s.nesterov; a.guard = s.guard; a.trust = s.trust; a.first = first;
+        a.advance = (s.ticket && last) ? s.step_inc : nullptr;
+        a.ticket = s.ticket;
+        return launch_chunks(sgd_dev_kernel<EMA, ACC, GUARD, GROUPS, LARS>, a, stream);
+    });
+}
+
+// (ema, acc and grads, guard, group, trust) given or not -> the 2 x 3 x 2 x 2 x 2 instantiations; nesterov is an argument
+int sgd_step(const AdamStep& s, void* stream) {
+    HYB_CHECK_ARG(s.rule == RULE_SGD && adam_step_ok(s));
+    return with_flag(s.ema != nullptr, [&](auto ema) { return with_flag(s.guard != nullptr, [&](auto guard) { return with_flag(s.group != nullptr, [&](auto groups) {
+        return with_flag(s.trust != nullptr, [&](auto lars) {
+            constexpr bool EMA = decltype(ema)::value, GUARD = decltype(guard)::value, GROUPS = decltype(groups)::value, LARS = decltype(lars)::value;
+            if (!s.acc) return sgd_dev_launch<EMA, GRAD_PLAIN, GUARD, GROUPS, LARS>(s, stream);
+            if (s.grads) return sgd_dev_launch<EMA, GRAD_ACC_G, GUARD, GROUPS, LARS>(s, stream);
+            return sgd_dev_launch<EMA, GRAD_ACC, GUARD, GROUPS, LARS>(s, stream);
+        });
+    }); }); });
+}
+
+// The trust pass of the SGD step that `s` describes: the chunk launches over the table in slices, then the final launches, one workgroup
+// per tensor.
+int lars_trust_call(const AdamStep& s, double trust_coeff, int always_adapt, float* partials, float* trust_out, void* stream) {
+    HYB_CHECK_ARG(s.rule == RULE_LARS_PASS && adam_step_ok(s) && trust_coeff > 0.0 && trust_coeff < (double)INFINITY &&
+                  (always_adapt == 0 || always_adapt == 1) && partials && trust_out);
+    int total = 0;
+    const int rc = for_each_slice(s.count, s.numel, ADAM_MAX, [&](int first, int n, const int* chunk_begin, bool) {
+        LarsTrustArgs a{};
+        for (int i = 0; i < n; ++i) {
+            a.p[i] = s.params[first + i]; a.n[i] = s.numel[first + i];
+            a.g[i] = s.grads ? s.grads[first + i] : nullptr;
+            a.acc[i] = s.acc ? s.acc[first + i] : nullptr;
+        }
+        std::copy(chunk_begin, chunk_begin + n + 1, a.chunk_begin);
+        a.count = n;
+        a.inv_k = (float)(1.0 / (double)s.k);
+        a.clip = s.clip; a.guard = s.guard;
+        a.chunk_offset = total;
+        a.partials = partials;
+        total += chunk_begin[n];
+        if (!s.acc) return launch_chunks(lars_trust_kernel<GRAD_PLAIN>, a, stream);
+        return s.grads ? launch_chunks(lars_trust_kernel<GRAD_ACC_G>, a, stream) : launch_chunks(lars_trust_kernel<GRAD_ACC>, a, stream);
+    });
+    if (rc != 0) return rc;
+    for (int first = 0, chunk = 0; first < s.count; first += LAMB_FINAL_MAX) {
+        LarsFinalArgs f{};
+        const int n = s.count - first < LAMB_FINAL_MAX ? s.count - first : LAMB_FINAL_MAX;
+        for (int i = 0; i < n; ++i) {
+            f.chunk_begin[i] = chunk;
+            chunk += hyb_cdiv(s.numel[first + i], ADAM_CHUNK);
+            if (s.group) f.group[i] = s.group[first + i];
+        }
+        f.chunk_begin[n] = chunk;
+        f.first = first; f.always_adapt = always_adapt; f.trust_coeff = trust_coeff; f.partials = partials; f.hyper = s.hyper; f.trust_out = trust_out;
+        hipLaunchKernelGGL(lars_trust_final_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, f);
+        HYB_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 // The four norm entry points: acc == NULL is the plain norm of grads (k == 1), acc given the norm of (acc + grads) / k, or of acc / k without
@@ -1096,6 +1494,24 @@ extern "C" int hyb_lamb_step_dev(int count, float* const* params, const float* c
                                  unsigned int* advance_ticket, const float* clip, const long long* guard, const float* trust, void* stream) {
     HYB_CHECK_ARG(trust);
     return adam_step({count, params, grads, exp_avg, exp_avg_sq, acc, ema, numel, group, groups, hyper, ema_hyper, k, step, step_inc, advance_ticket, clip, guard, trust}, stream);
+}
+
+// ---- SGD and LARS: the same descriptor with one state table, checked by the same rule -----------------------------------------------------------
+extern "C" int hyb_sgd_step_dev(int count, float* const* params, const float* const* grads, float* const* momentum_buf, float* const* acc,
+                                float* const* ema, const long long* numel, const unsigned char* group, int groups, const double* hyper,
+                                const double* ema_hyper, long long k, long long step, long long* step_inc, unsigned int* advance_ticket,
+                                const float* clip, const long long* guard, int nesterov, const float* trust, void* stream) {
+    return sgd_step({count, params, grads, momentum_buf, nullptr, acc, ema, numel, group, groups, hyper, ema_hyper, k, step, step_inc, advance_ticket, clip, guard,
+                     trust, RULE_SGD, nesterov}, stream);
+}
+
+extern "C" size_t hyb_lars_trust_workspace(int count, const long long* numel) { return 2 * hyb_grad_norm_workspace(count, numel); }
+
+extern "C" int hyb_lars_trust(int count, float* const* params, const float* const* grads, float* const* acc, const long long* numel,
+                              const unsigned char* group, int groups, const double* hyper, long long k, const float* clip, const long long* guard,
+                              double trust_coeff, int always_adapt, float* partials, float* trust_out, void* stream) {
+    return lars_trust_call({count, params, grads, nullptr, nullptr, acc, nullptr, numel, group, groups, hyper, nullptr, k, 1, nullptr, nullptr, clip, guard, nullptr,
+                            RULE_LARS_PASS, 0}, trust_coeff, always_adapt, partials, trust_out, stream);
 }
 
 // ---- the uploads of the device blocks -----------------------------------------------------------------------------------------------------------

@@ -222,7 +222,10 @@ class GraphedTrainStep:
         # the captures above did not execute: the state is still "after the warm-up steps"
 
     def _hyper_now(self):
-        return [(g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"], g.get("max_grad_norm") is not None) for g in self.optimizer.param_groups]
+        """Per group, as the optimizer itself states it: (the row of its device block less the clip value, whether it clips, what its launch
+        carries by value besides)."""
+        opt = self.optimizer
+        return [(opt._group_hyper(g)[:5], g.get("max_grad_norm") is not None, opt._by_value(g)) for g in opt.param_groups]
 
     def _loss_opts_now(self):
         """[(name, value)]: what the criterion's captured launches carry by value and the addresses of the buffers they read, as the criterion
@@ -248,6 +251,13 @@ class GraphedTrainStep:
         if [g.get("ema_decay") is not None for g in self.optimizer.param_groups] != self._ema_on:
             raise RuntimeError("GraphedTrainStep: ema_decay was switched on or off after capture; the captured AdamW launch does (not) keep the "
                                "average -- set it on the optimizer before constructing GraphedTrainStep (its value may change at any time)")
+        if self._captured_hyper[0][2]:                         # (an optimizer whose launch carries something by value: HybridSGD's nesterov)
+            for g, c in zip(self.optimizer.param_groups, self._captured_hyper):
+                now = self.optimizer._by_value(g)
+                if now != c[2]:
+                    what = [name for (name, a), (_, b) in zip(now, c[2]) if a != b]
+                    raise RuntimeError(f"GraphedTrainStep: the optimizer's {', '.join(what)} changed after capture, but it travels by value in the "
+                                       "captured step launch -- construct a new GraphedTrainStep")
         if self._dev_hyper:
             if any((g.get("max_grad_norm") is not None) != self._clipping for g in self.optimizer.param_groups):
                 raise RuntimeError("GraphedTrainStep: max_grad_norm was switched on or off after capture; the norm launch is (not) part of the "
@@ -255,7 +265,7 @@ class GraphedTrainStep:
             self.optimizer.sync_hyper()                        # on the current stream, in front of the replay; uploads only what changed
             return
         for g, c in zip(self.optimizer.param_groups, self._captured_hyper):
-            if g["lr"] != c[0] or tuple(g["betas"]) != c[1] or g["eps"] != c[2] or g["weight_decay"] != c[3] or (g.get("max_grad_norm") is not None) != c[4]:
+            if self.optimizer._group_hyper(g)[:5] != c[0] or (g.get("max_grad_norm") is not None) != c[1]:
                 raise RuntimeError("GraphedTrainStep: an optimizer hyper-parameter (lr, betas, eps, weight_decay, max_grad_norm) changed after "
                                    "capture, but the captured AdamW launch carries the old value -- construct with dynamic_hyper=True to use "
                                    "schedulers (and set max_grad_norm before constructing)")

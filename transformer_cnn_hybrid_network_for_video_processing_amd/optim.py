@@ -48,7 +48,8 @@ behind `step()`, `accumulate()` and GraphedTrainStep's eager accumulate.  `step(
 arguments by the names of the record's fields).
 
 `HybridLAMB` (at the end of the file) is the same optimizer with layer-wise trust ratios: its `_launch` is two calls per unit, the trust
-pass and the step that reads it."""
+pass and the step that reads it.  `HybridSGD` and `HybridLARS` (after it) are the same optimizer again with torch.optim.SGD's rule: one
+state tensor (`_STATE`), a hyper row of their own (`_group_hyper`) and a `_launch` that calls hyb_sgd_step_dev."""
 import copy
 import ctypes
 from typing import NamedTuple
@@ -86,6 +87,8 @@ _STEP_ARGS = {
     "hyb_adamw_step_dev_groups": "n p grads m v acc ema numel group groups hyper ema_hyper k step counter ticket clip guard",
     "hyb_lamb_step_dev": "n p grads m v acc ema numel group groups hyper ema_hyper k step counter ticket clip guard trust",
     "hyb_lamb_trust": "n p grads m v acc numel group groups hyper k step counter clip guard always_adapt partials trust",
+    "hyb_sgd_step_dev": "n p grads m acc ema numel group groups hyper ema_hyper k step counter ticket clip guard nesterov trust",
+    "hyb_lars_trust": "n p grads acc numel group groups hyper k clip guard trust_coeff always_adapt partials trust",
 }
 _STEP_ARGS = {name: tuple(fields.split()) for name, fields in _STEP_ARGS.items()}
 
@@ -108,10 +111,17 @@ def _no_capture(what, remedy, why=""):
 
 
 class HybridAdamW(torch.optim.Optimizer):
+    _STATE = ("exp_avg", "exp_avg_sq")     # the state tensors of the update rule, in the order of the unit's columns m, v (HybridSGD: one)
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None, ema_decay=None, ema_warmup=False,
                  accumulation_steps=1, skip_nonfinite=False, merge_groups=True):
         if lr < 0.0 or eps < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 or weight_decay < 0.0:
             raise ValueError("invalid AdamW hyper-parameter")
+        self._setup(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm, ema_decay, ema_warmup, accumulation_steps,
+                    skip_nonfinite, merge_groups)
+
+    def _setup(self, params, rule, max_grad_norm, ema_decay, ema_warmup, accumulation_steps, skip_nonfinite, merge_groups):
+        """Everything of the constructor that does not depend on the update rule; `rule`: the rule's own (checked) group defaults."""
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError("max_grad_norm must be None (no clipping) or > 0")
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
@@ -124,8 +134,7 @@ class HybridAdamW(torch.optim.Optimizer):
         self._guard = None           # device int64 [2]: skip_now (the last guarded step was skipped), skipped_total (since the last fold)
         # max_grad_norm sits in the groups only so that it travels in the state dict: clipping is global, every group carries the same value;
         # ema_decay / ema_warmup are per group (None: that group takes the launch without the average)
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                                      ema_decay=ema_decay, ema_warmup=bool(ema_warmup)))
+        super().__init__(params, dict(rule, max_grad_norm=max_grad_norm, ema_decay=ema_decay, ema_warmup=bool(ema_warmup)))
         self._tables = {}            # unit key -> the _Unit of step(), cached while the tensors' addresses stay
         self._step_counter = None    # device int64 [1]: the kernel uses step + counter (captured launches, graph.GraphedTrainStep)
         self._advance = False
@@ -298,6 +307,11 @@ class HybridAdamW(torch.optim.Optimizer):
         c = group.get("max_grad_norm")             # (groups loaded from a torch.optim.AdamW state dict lack the key)
         return (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), 0.0 if c is None else float(c))
 
+    def _by_value(self, group):
+        """((name, value), ...): what a captured step launch of this group carries by value besides its hyper-parameters -- a change after
+        capture cannot be followed, and GraphedTrainStep refuses it by name.  Nothing here (HybridSGD: nesterov)."""
+        return ()
+
     def sync_hyper(self):
         """Upload every group's (lr, betas, eps, weight_decay, max_grad_norm), and (ema_decay, ema_warmup) where the group keeps an average,
         that differs from what the device holds (one tiny launch on the current stream for all changed groups, hyb_adamw_hyper_set_groups;
@@ -344,8 +358,8 @@ class HybridAdamW(torch.optim.Optimizer):
         if self._guard is not None:                 # loaded `step` values are applied-update counts: nothing is left to subtract
             self._guard[1:].zero_()
         for st in self.state.values():              # torch casts loaded state to the parameter's dtype/device; keep the layout the kernel needs
-            for k in ("exp_avg", "exp_avg_sq", "ema"):
-                if k in st:
+            for k in self._STATE + ("ema",):
+                if st.get(k) is not None:
                     st[k] = st[k].to(torch.float32).contiguous()
             if "step" in st and torch.is_tensor(st["step"]):
                 st["step"] = int(st["step"].item())
@@ -505,10 +519,10 @@ class HybridAdamW(torch.optim.Optimizer):
             st = self.state[p]
             if ema is not None and "ema" not in st:
                 st["ema"] = self._new_ema(p)         # the value before this step
-            if "exp_avg" not in st:                  # (ema_init() may have left a state that holds the average only)
+            if self._STATE[0] not in st:             # (ema_init() may have left a state that holds the average only)
                 st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                for name in self._STATE:
+                    st[name] = torch.zeros_like(p, memory_format=torch.preserve_format)
             if self._step_counter is None:
                 st["step"] += 1
         # with a device counter the Python-side step stays put and the kernel uses (step + 1) + counter
@@ -516,7 +530,8 @@ class HybridAdamW(torch.optim.Optimizer):
         if len(steps) != 1:
             raise RuntimeError("HybridAdamW: parameters of one group must share the step count")
         states = [self.state[p] for p in ps]
-        u = self._unit(self._tables, key, unit[0], ps, layout, merged, p=ps, m=[st["exp_avg"] for st in states], v=[st["exp_avg_sq"] for st in states],
+        m, v = ([st[name] for st in states] for name in self._STATE) if len(self._STATE) == 2 else ([st[self._STATE[0]] for st in states], None)
+        u = self._unit(self._tables, key, unit[0], ps, layout, merged, p=ps, m=m, v=v,
                        ema=None if ema is None else [st["ema"] for st in states], acc=accs)
         return u, None if accs is not None and self._acc_only else self._float_grads(ps), steps.pop(), ema is not None
 
@@ -618,6 +633,7 @@ class HybridLAMB(HybridAdamW):
                          ema_warmup=ema_warmup, accumulation_steps=accumulation_steps, skip_nonfinite=skip_nonfinite, merge_groups=merge_groups)
 
     always_adapt = property(lambda self: self._always_adapt)
+    _TRUST_WORKSPACE = "hyb_lamb_trust_workspace"
 
     def uses_device_hyper(self):
         """Always: the ratios are formed and read on the device (there is no by-value LAMB)."""
@@ -630,7 +646,7 @@ class HybridLAMB(HybridAdamW):
         if w is None or w[0] != numels:
             _no_capture("the trust-ratio workspace", "take one eager step() with the same gradients first")
             dev = self._device()
-            floats = lib.query("hyb_lamb_trust_workspace", u.n, u.numel)
+            floats = lib.query(self._TRUST_WORKSPACE, u.n, u.numel)
             w = self._trust[u.key] = (numels, torch.zeros(floats, dtype=torch.float32, device=dev), torch.ones(u.n, 3, dtype=torch.float32, device=dev),
                                       u.params)
         elif w[3] is not u.params:                  # (the same sizes behind other tensors: the rows now speak of these)
@@ -648,4 +664,112 @@ class HybridLAMB(HybridAdamW):
         vals = self._step_values(u, grads, step, hyper, clip, guard)
         vals.update(always_adapt=int(self._always_adapt), partials=partials, trust=trust)
         for name in ("hyb_lamb_trust", "hyb_lamb_step_dev"):
+            lib.call(name, *[vals[f] for f in _STEP_ARGS[name]], _stream())
+
+
+class HybridSGD(HybridAdamW):
+    """SGD with momentum -- torch.optim.SGD's rule: coupled L2 weight decay, dampening, Nesterov; maximize off -- on HybridAdamW's device
+    path (hyb_sgd_step_dev): per element d = g + weight_decay * p, buf <- d at the first step and momentum * buf + (1 - dampening) * d
+    after it, p <- p - lr * (d + momentum * buf if nesterov else buf).  One launch per unit with one state tensor per parameter: 5 x 4
+    bytes per parameter where the AdamW launch moves 7 x 4.  It always takes the device path (there is no by-value SGD launch), so it
+    works under GraphedTrainStep with everything HybridAdamW offers there: clipping, schedules of lr / momentum / dampening / weight_decay
+    between replays, the weight average, accumulation, the non-finite guard, merged groups, data parallelism.
+
+    State keys are torch's `momentum_buffer` plus `step` (which says whether the buffer has been started), so checkpoints interchange with
+    torch.optim.SGD: a loaded state with a buffer and no `step` gets step = 1, so that the buffer is used.  With momentum == 0 the buffer
+    is still kept (torch keeps none): it is harmless -- it holds (1 - dampening) * d and never reaches p, the step is on d itself as
+    in torch -- and the parameter values are torch's.  `nesterov` is a group key so that it travels in the state dict, and like max_grad_norm it must be equal in all groups: it
+    travels by value in the captured launch, and GraphedTrainStep refuses a change after capture."""
+    _STATE = ("momentum_buffer",)
+
+    def __init__(self, params, lr, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False, max_grad_norm=None, ema_decay=None,
+                 ema_warmup=False, accumulation_steps=1, skip_nonfinite=False, merge_groups=True):
+        self._setup(params, self._sgd_rule(lr, momentum, dampening, weight_decay, nesterov), max_grad_norm, ema_decay, ema_warmup,
+                    accumulation_steps, skip_nonfinite, merge_groups)
+
+    @staticmethod
+    def _sgd_rule(lr, momentum, dampening, weight_decay, nesterov):
+        if lr < 0.0 or not 0.0 <= momentum < 1.0 or not 0.0 <= dampening < 1.0 or weight_decay < 0.0:
+            raise ValueError("invalid SGD hyper-parameter")
+        if not isinstance(nesterov, bool):
+            raise ValueError("nesterov must be a bool")
+        if nesterov and (momentum <= 0.0 or dampening != 0.0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        return dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
+
+    def uses_device_hyper(self):
+        """Always: there is no by-value SGD launch."""
+        return True
+
+    def _group_hyper(self, group):
+        """The group's row of the device block: {lr, momentum, dampening, lars_eps, weight_decay, max_grad_norm}."""
+        c = group.get("max_grad_norm")             # (groups loaded from a torch.optim.SGD state dict lack the key)
+        return (float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group.get("eps", 0.0)), float(group["weight_decay"]),
+                0.0 if c is None else float(c))
+
+    def _by_value(self, group):
+        return (("nesterov", bool(group.get("nesterov", False))),)
+
+    def _nesterov_value(self):
+        vals = {bool(g.get("nesterov", False)) for g in self.param_groups}
+        if len(vals) != 1:
+            raise RuntimeError("HybridSGD: nesterov travels by value in the launch -- every param group must carry the same nesterov")
+        nesterov = vals.pop()
+        if nesterov and any(float(g["momentum"]) <= 0.0 or float(g["dampening"]) != 0.0 for g in self.param_groups):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        return nesterov
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            if st.get("momentum_buffer") is None:
+                st.pop("momentum_buffer", None)     # (as after ema_init(): the buffer is created, and started, by the next step)
+            elif "step" not in st:
+                st["step"] = 1                       # torch.optim.SGD's state: the buffer has been started
+
+    def _sgd_values(self, u, grads, step, hyper, clip, guard):
+        vals = self._step_values(u, grads, step, hyper, clip, guard)
+        vals.update(nesterov=int(self._nesterov_value()), trust=None)
+        return vals
+
+    def _launch(self, u, grads, step, hyper, clip, guard):
+        """The one SGD call of a unit."""
+        vals = self._sgd_values(u, grads, step, hyper, clip, guard)
+        lib.call("hyb_sgd_step_dev", *[vals[f] for f in _STEP_ARGS["hyb_sgd_step_dev"]], _stream())
+
+
+class HybridLARS(HybridSGD):
+    """LARS (You et al., 2017; timm's Lars with trust_clip=False) on HybridSGD's launch: per tensor the decayed gradient d = g + weight_decay * p
+    is scaled by the trust ratio r = trust_coeff * |p| / (|g| + weight_decay * |p| + eps) -- 1 where either norm is zero, and for a tensor
+    whose group has weight_decay == 0 unless always_adapt -- and then takes HybridSGD's momentum step.  g is the effective gradient: the
+    mean over an accumulated step, after clipping.  A step is the existing norm call (when clipping or guarding), ONE read-only launch pair
+    that forms every tensor's ratio on the device (hyb_lars_trust, bit-reproducible sums) and the SGD launch reading the ratios, per launch
+    unit, with no host read: everything HybridSGD offers under GraphedTrainStep holds.  weight_decay and eps are read on the device;
+    trust_coeff and always_adapt are attributes fixed at construction (they travel by value in the captured launch).  `trust_ratios()`
+    gives the last step's (|p|, |g|, r) per parameter as device tensors.  With weight_decay == 0 everywhere (and always_adapt off) every
+    ratio is 1 and the step is HybridSGD's bit for bit."""
+    _TRUST_WORKSPACE = "hyb_lars_trust_workspace"
+
+    def __init__(self, params, lr, momentum=0.9, weight_decay=1e-4, nesterov=False, trust_coeff=1e-3, eps=1e-8, always_adapt=False, dampening=0.0,
+                 max_grad_norm=None, ema_decay=None, ema_warmup=False, accumulation_steps=1, skip_nonfinite=False, merge_groups=True):
+        if not isinstance(always_adapt, bool):
+            raise ValueError("always_adapt must be a bool")
+        if isinstance(trust_coeff, bool) or not 0.0 < float(trust_coeff) < float("inf") or eps < 0.0:
+            raise ValueError("invalid LARS hyper-parameter")
+        self._always_adapt, self._trust_coeff = always_adapt, float(trust_coeff)
+        self._trust = {}             # unit key -> (numels, device fp32 [2 * chunks], device fp32 [n, 3], the unit's parameters)
+        self._setup(params, dict(self._sgd_rule(lr, momentum, dampening, weight_decay, nesterov), eps=eps), max_grad_norm, ema_decay, ema_warmup,
+                    accumulation_steps, skip_nonfinite, merge_groups)
+
+    always_adapt = property(lambda self: self._always_adapt)
+    trust_coeff = property(lambda self: self._trust_coeff)
+    _trust_workspace = HybridLAMB._trust_workspace
+    trust_ratios = HybridLAMB.trust_ratios
+
+    def _launch(self, u, grads, step, hyper, clip, guard):
+        """The trust pass and the step that reads it: two calls per unit."""
+        partials, trust = self._trust_workspace(u)
+        vals = self._sgd_values(u, grads, step, hyper, clip, guard)
+        vals.update(trust_coeff=self._trust_coeff, always_adapt=int(self._always_adapt), partials=partials, trust=trust)
+        for name in ("hyb_lars_trust", "hyb_sgd_step_dev"):
             lib.call(name, *[vals[f] for f in _STEP_ARGS[name]], _stream())
