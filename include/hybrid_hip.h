@@ -879,6 +879,65 @@ int hyb_clips_u8_luma_sums(const unsigned char* src /* [B][Tin][Hin][Win][C] uin
                            long long* sums          /* device, [B][Tout] int64 */,
                            int B, int Tin, int Hin, int Win, int C, int Tout, void* stream);
 
+/* hyb_clip_aug_u8_transform: hyb_clips_u8_transform_photo with RandAugment's ops and a hue shift in the same pass (new symbol,
+ * hyb_abi_version() stays 9; the name stands outside the hyb_clips_u8_* family, whose six members tests/test_clip_job_cpu.py lists as a closed
+ * set).  `aug`: one more int32 row of 32 per clip, in device memory; all frames of a clip share it:
+ *   [0]        flags: bit 0 switches the geometry on
+ *   [1]        n, the length of the program, clamped into 0..8
+ *   [2..17]    (op, arg) x 8: the program's steps in order; only the first n are read; an op outside 0..8 counts as 0 (Identity)
+ *   [18..23]   M = (a, b, c, d, e, f) as fp32 bits; a value that is not finite switches the geometry off
+ *   [24..26]   fill[3] as fp32 bits, on the [0,1] scale: !(v >= 0) (NaN included) counts as 0, values above 1 as 1; C == 1 reads fill[0]
+ *   [27..31]   reserved, not read
+ * The pixel chain of hyb_clips_u8_transform_photo becomes
+ *   1.  resample, with the geometry when it is on
+ *   1a. the program: its n steps on the [0,1] value, in order
+ *   2-6 jitter, gray, noise, normalise, erase, as hyb_clips_u8_transform_photo states them (photo == NULL: identity photo rows)
+ *   7.  mix: the partner's pixel goes through the PARTNER's params, aug and photo rows.
+ * Geometry.  M maps an output pixel to a point of the un-augmented output frame, in PIL's Image.AFFINE convention; pixel (i, j) = (oy, ox)
+ * has the centre (j + 1/2, i + 1/2), everything in fp32:
+ *   x = fma(a, j + 0.5f, fma(b, i + 0.5f, c));      y = fma(d, j + 0.5f, fma(e, i + 0.5f, f))
+ *   !(0 <= x < Wo && 0 <= y < Ho) (a NaN is outside): the value is fill[c]; it then goes through 1a-7 like any other pixel.  Otherwise
+ *   x  = Wo - x when the clip is flipped
+ *   sx = (x * float(cw)) / float(Wo) - 0.5f;        sy = (y * float(ch)) / float(Ho) - 0.5f          (rounded product, quotient, difference)
+ *   ix = floor(sx), fx = sx - ix;  iy = floor(sy), fy = sy - iy;    the taps ix, ix + 1 clamped into [0, cw-1], iy, iy + 1 into [0, ch-1]
+ *   top = fma(fx, a01 - a00, a00);  bot = fma(fx, a11 - a10, a10);  v = fma(fy, bot - top, top) / 255.0f
+ * ONE resampling of the source crop through the composite map (output pixel -> un-augmented output frame -> crop), not a second resampling of
+ * the resized frame; with ch == Ho, cw == Wo and no flip it is PIL's Image.transform(AFFINE, BILINEAR, fillcolor) of the crop.  A row without the
+ * geometry takes the integer taps of hyb_clips_u8_transform: with n == 0 (or only Identity steps) on top and identity photo rows (or NULL), the
+ * bits of hyb_clips_u8_transform_photo, and so of hyb_clips_u8_transform and hyb_clips_u8_transform_mix.
+ * The program.  q = floor(255 v + 1/2) is the byte of a value; factors are read like the photo row's (!(f >= 0) is 1, above 16 is 16) and
+ * integer arguments are clamped into their ranges.  L(v) = 0.2989 r + 0.587 g + 0.114 b.
+ *   0 Identity
+ *   1 Invert                  v = 1 - v
+ *   2 Brightness   f bits     v = clamp01(f v)
+ *   3 Contrast     f bits     v = clamp01(f v + (1-f) m).  m starts as the clip's mean luma mu0 = (sum_t luma_sums[b][t]) / (10000*255*ch*cw*Tout)
+ *                             (double, rounded to fp32 once) and moves with the steps in front of this one: a Brightness step makes it
+ *                             min(f m, 1), an Invert step 1 - m, nothing else moves it.  luma_sums == NULL: the factor counts as 1
+ *   4 Color        f bits     v = clamp01(f v + (1-f) L(v));  nothing happens at C == 1
+ *   5 Posterize    bits 0..8  v = float(q & ~(2^(8-bits) - 1)) / 255.0f
+ *   6 Solarize     thr 0..256 q >= thr: v = 1 - v
+ *   7 SolarizeAdd  add 0..255 q < 128: v = min(1, v + float(add) / 255.0f)
+ *   8 Hue          h bits     a NaN is 0, then clamped into [-1/2, 1/2]; torchvision's adjust_hue on floats; nothing happens at C == 1 or h == 0:
+ *        mx = max(r,g,b); mn = min(r,g,b); cr = mx - mn; eq = (mx == mn); s = cr / (eq ? 1 : mx); d = eq ? 1 : cr
+ *        rc = (mx-r)/d; gc = (mx-g)/d; bc = (mx-b)/d
+ *        hh = mx == r ? bc - gc : (mx == g ? 2 + rc - bc : 4 + gc - rc);   hh = fmod(hh/6 + 1, 1);   hh = hh + h;  hh = hh - floor(hh)
+ *        i = floor(6 hh); f = 6 hh - i; i = i mod 6
+ *        p = clamp01(mx (1 - s)); q' = clamp01(mx (1 - s f)); t = clamp01(mx (1 - s (1 - f)))
+ *        (r,g,b) = i == 0 ? (mx,t,p) : 1 ? (q',mx,p) : 2 ? (p,mx,t) : 3 ? (p,q',mx) : 4 ? (t,p,mx) : (mx,p,q')       every operation rounded, none fused
+ * On values that are bytes / 255 Invert, Posterize, Solarize and SolarizeAdd give the bytes of PIL's ImageOps.invert / posterize / solarize and
+ * of timm's solarize_add.  The jitter of step 2 keeps its pivot rule on the untouched mu0.
+ * No row value reads outside src.  mix, photo, luma_sums and mean_invstd may be NULL.  C must be 1 or 3; otherwise the limits of
+ * hyb_clips_u8_transform. */
+int hyb_clip_aug_u8_transform(const unsigned char* src /* [B][Tin][Hin][Win][C] uint8 */,
+                              const int* params        /* device, [B][8] int32, one row per CLIP */,
+                              const int* mix           /* device, [B][8] int32, one row per CLIP; or NULL = nothing mixes */,
+                              const int* photo         /* device, [B][16] int32, one row per CLIP; or NULL = identity rows */,
+                              const int* aug           /* device, [B][32] int32, one row per CLIP */,
+                              const long long* luma_sums /* device, [B][Tout] int64 from hyb_clips_u8_luma_sums; or NULL */,
+                              const float* mean_invstd /* device, [2][C]: mean then 1/std; or NULL = no normalisation */,
+                              float* dst               /* [B][Tout][C][Ho][Wo] fp32 */,
+                              int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo, void* stream);
+
 /* ---- ResNet-bottleneck backbone `Encoder_32K` (only bytecode of it ships with the reference:
  * __pycache__/AE_256_32K.cpython-38.pyc, read as data -- `Bottleneck` src L21-53, `Encoder_32K` src L58-137).  NHWC fp32 with the
  * true channel counts, exact-fp32 arithmetic like the FCT entry points above, which these generalise.

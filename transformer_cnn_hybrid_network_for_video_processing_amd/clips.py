@@ -24,6 +24,9 @@ every clip come out of ONE launch (``hyb_clips_u8_transform_views``) that reads 
 cross PCIe once, and the rows are in the order ``ClassificationMeter.update(..., views=V)`` scores.
 The antialiased resize (``ClipTransform(antialias=True)``, ``hyb_clips_u8_transform_aa``): the same rows, training or evaluation, resampled with
 torchvision's ``Resize(antialias=True)`` filter -- a separable triangle filter through LDS instead of two taps per axis.
+RandAugment and hue jitter (``ClipTransform(randaugment="rand-m7-n4-mstd0.5", hue=0.1)``, ``hyb_clip_aug_u8_transform``): a fourth int32 row per clip
+carries the drawn geometric ops folded into ONE affine map, which the kernel composes with the crop's resampling (one gather, not a second
+resampling), and the drawn photometric ops as a program of pointwise steps in front of the jitter.
 """
 import csv
 import os
@@ -107,7 +110,10 @@ class ClipPipeline:
     HybridBCEWithLogitsLoss, GraphedTrainStep (dense target) and MultiLabelMeter take.  With a mixing transform the yielded row is
     lam_b y_b + (1 - lam_b) y_partner(b), formed on the host in fp32, in place of a MixTarget.  The first batch decides which kind a pipeline carries.
     A transform with ``antialias=True``: hyb_clips_u8_transform_aa is the one kernel, for the training rows (V = 1) and the evaluation views alike;
-    the rows and what is yielded do not change."""
+    the rows and what is yielded do not change.
+    A transform with ``randaugment=`` or ``hue=`` (``transform.augmenting()``): an aug row int32 [B,32] per clip (``transform.sample_aug``) travels in the
+    slots' ``host_aug`` / ``dev_aug`` beside the other rows and hyb_clip_aug_u8_transform is the one kernel, with the mix rows and the photo rows or
+    without; hyb_clips_u8_luma_sums runs in front of it when a Contrast step or a contrast factor can be drawn.  What is yielded does not change."""
 
     def __init__(self, source, device="cuda", depth=2, transform=None):
         self.source, self.depth, self.transform = source, max(1, int(depth)), transform
@@ -156,8 +162,11 @@ class ClipPipeline:
                 if self.transform.photometric():
                     s["host_ph"] = torch.empty(B, 16, dtype=torch.int32).pin_memory()
                     s["dev_ph"] = torch.empty(B, 16, dtype=torch.int32, device=self.device)
-                    if self.transform.needs_luma():
-                        s["luma"] = torch.empty(B, xshape[1], dtype=torch.int64, device=self.device)
+                if self.transform.augmenting():
+                    s["host_aug"] = torch.empty(B, 32, dtype=torch.int32).pin_memory()
+                    s["dev_aug"] = torch.empty(B, 32, dtype=torch.int32, device=self.device)
+                if self.transform.needs_luma():           # (photometric or augmenting: a contrast factor or a Contrast step can be drawn)
+                    s["luma"] = torch.empty(B, xshape[1], dtype=torch.int64, device=self.device)
             self.stream.wait_stream(torch.cuda.current_stream(self.device))      # mean_invstd was uploaded on the consumer's stream
 
     def _issue(self, slot, batch):
@@ -198,6 +207,9 @@ class ClipPipeline:
         photo = self.transform is not None and self.transform.photometric()
         if photo:
             s["host_ph"].numpy()[...] = self.transform.sample_photo(B, self.transform.out_frames(T), *self.transform.size)
+        augmenting = self.transform is not None and self.transform.augmenting()
+        if augmenting:
+            s["host_aug"].numpy()[...] = self.transform.sample_aug(B, *self.transform.size)
         with torch.cuda.stream(self.stream):
             s["dev_u8"].copy_(s["host"], non_blocking=True)
             s["y"].copy_(s["host_y"], non_blocking=True)
@@ -213,11 +225,14 @@ class ClipPipeline:
                     s["lam"].copy_(s["host_lam"], non_blocking=True)
                 if photo:
                     s["dev_ph"].copy_(s["host_ph"], non_blocking=True)
-                    if "luma" in s:
-                        lib.call("hyb_clips_u8_luma_sums", s["dev_u8"], s["dev_p"], s["luma"], B, T, H, W, C, Tout, self.stream.cuda_stream)
-                # the one transform call: which kernel is ClipTransform.kernel()'s answer, how it is called is the operators' (ops.CLIP_OPS)
+                if augmenting:
+                    s["dev_aug"].copy_(s["host_aug"], non_blocking=True)
+                if "luma" in s:
+                    lib.call("hyb_clips_u8_luma_sums", s["dev_u8"], s["dev_p"], s["luma"], B, T, H, W, C, Tout, self.stream.cuda_stream)
+                # the one transform call: which kernel is ClipTransform.kernel()'s answer, how it is called is the operators' (ops.CLIP_OPS and
+                # ops.CLIP_OPS_EXT)
                 clip_transform_into(self.transform.kernel(), s["x"], s["dev_u8"], s["dev_p"], self._mean_invstd, views, self.stream.cuda_stream,
-                                    mix=s.get("dev_m"), photo=s.get("dev_ph"), luma_sums=s.get("luma"))
+                                    mix=s.get("dev_m"), photo=s.get("dev_ph"), luma_sums=s.get("luma"), aug=s.get("dev_aug"))
             s["ready"].record(self.stream)
 
     def __iter__(self):
@@ -270,7 +285,7 @@ class ClipTransform:
     brightness, contrast, saturation   strength s >= 0 of torchvision's ColorJitter: the factor is drawn from U[max(0, 1-s), 1+s] per CLIP and
                   the three ops run in a uniformly drawn order; jitter_prob: probability that a clip is jittered at all.  The contrast pivot is
                   the mean luma of the clip's untouched source crops (one affine map for all frames of a clip), not torchvision's per-frame
-                  mean of the jittered image; there is no hue jitter
+                  mean of the jittered image; the hue jitter is ``hue`` below
     grayscale     probability that a clip becomes its luma in every channel (after the jitter)
     noise_std     sigma of additive Gaussian noise on the [0,1] scale, a float or a (lo, hi) range to draw it from; noise_prob: per clip
     erase_prob, erase_scale, erase_ratio   torchvision's RandomErasing: one box per clip in output coordinates, the same for all its frames;
@@ -291,12 +306,32 @@ class ClipTransform:
                   when the source is more than about 2 x the output ("resize 256, crop 224" from a 720-line decoder).  The rows do not change:
                   ``sample`` / ``sample_views`` of a seed are the same with it on and off.  Not provided together with mixing or the photometric
                   options (raises).  False, the default: the kernels, draws and bits are what they were
+    randaugment   None, (n, m) or timm's string form "rand-m7-n4-mstd0.5" (m, n, mstd and inc1 are read; the increasing set is always used; any
+                  other field is refused by name): RandAugment per CLIP.  n ops are drawn uniformly WITH replacement from ``ra_ops``, each is applied
+                  with probability ``ra_prob`` at the magnitude clip(N(m, mstd), 0, 10); with L = magnitude / 10 the levels are timm's increasing
+                  ones: Rotate +-30 L degrees, ShearX / ShearY +-0.3 L, TranslateX / TranslateY +-0.45 L of Wo / Ho, Brightness / Contrast / Color
+                  max(0.1, 1 +- 0.9 L), Posterize 4 - int(4 L) bits, Solarize threshold 256 - int(256 L), SolarizeAdd int(110 L); a signed level
+                  flips its sign with probability 1/2.  The geometric ops are folded on the host into ONE affine map (timm's PIL matrices, output ->
+                  input, Rotate about the frame's centre, op 1 then op 2 = M1 o M2) that the kernel composes with the crop's resampling; the
+                  photometric ops run in drawn order as a program of pointwise steps between the resampling and the colour jitter.  All frames of a
+                  clip share the row; with Mixup / CutMix the partner goes through its own
+    ra_ops        the names to draw from; None: timm's increasing set without AutoContrast, Equalize and Sharpness (``RA_OPS``)
+    ra_prob       probability that a drawn op is applied
+    fill          the value, on the [0, 1] scale, of pixels the affine map takes from outside the frame: a number or one per channel; None: ``mean``
+                  when there is one, else 0.5.  A filled pixel goes through the program, the jitter and the normalisation like any other
+    hue           h in [0, 1/2]: a shift from U[-h, h] per clip (torchvision's adjust_hue), drawn under ``jitter_prob`` by a draw of its own and
+                  appended as the program's LAST step: it runs in front of the brightness / contrast / saturation steps, not inside their random
+                  order as torchvision's ColorJitter would place it
+                  These draws come from ``sample_aug`` and a FOURTH Generator derived from ``seed``: the crop, mix and photo rows of a seed do not move.
+                  ``kernel()`` is then "aug" (hyb_clip_aug_u8_transform).  With the defaults (or train=False) nothing changes: the same kernels, draws
+                  and bits.  Not provided: AutoContrast, Equalize, Sharpness, bicubic interpolation, per-frame programs, the new options together with
+                  antialias=True (raises) or on evaluation views
     """
 
     def __init__(self, size, scale=(0.35, 1.0), ratio=(3 / 4, 4 / 3), hflip=0.5, mean=None, std=None, frames=None, frame_stride=(1, 1), seed=0,
                  train=True, mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, switch_prob=0.5, mix_mode="batch", brightness=0.0, contrast=0.0, saturation=0.0, jitter_prob=1.0,
                  grayscale=0.0, noise_std=0.0, noise_prob=1.0, erase_prob=0.0, erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), erase_mode="zero",
-                 eval_views=(1, 1), eval_crop=1.0, eval_flip=False, antialias=False):
+                 eval_views=(1, 1), eval_crop=1.0, eval_flip=False, antialias=False, randaugment=None, ra_ops=None, ra_prob=0.5, fill=None, hue=0.0):
         self.size = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
         if min(self.size) <= 0:
             raise ValueError(f"size must be positive, got {size!r}")
@@ -365,8 +400,134 @@ class ClipTransform:
         if self.antialias and (self.mixing() or self.photometric()):
             raise ValueError("antialias=True together with Mixup / CutMix or the photometric options is not provided: the antialiased resize has "
                              "no mix or photo kernel")
+        self.randaugment = None if randaugment is None else self._parse_randaugment(randaugment)
+        self.ra_ops = tuple(self.RA_OPS if ra_ops is None else ra_ops)
+        unknown = [o for o in self.ra_ops if o not in self.RA_OPS]
+        if unknown or not self.ra_ops:
+            raise ValueError(f"ra_ops must be a non-empty selection of {self.RA_OPS}, got {unknown or ra_ops!r}")
+        self.ra_prob, self.hue = float(ra_prob), float(hue)
+        if not 0.0 <= self.ra_prob <= 1.0:
+            raise ValueError("ra_prob is a probability")
+        if not 0.0 <= self.hue <= 0.5:
+            raise ValueError(f"hue is a range h in [0, 1/2] of the shift U[-h, h], got {hue!r}")
+        if self.randaugment is not None and self.randaugment[0] + (self.hue > 0) > 8:
+            raise ValueError("an aug row's program holds 8 steps: randaugment's n (plus one for hue) must not exceed it")
+        if fill is None:
+            # the default never refuses: the first three entries of any mean (the aug kernel takes C == 1 or 3), on the [0, 1] scale the row carries
+            f = np.clip(self.mean[:3], 0, 1) if self.mean is not None else np.full(1, 0.5, dtype=np.float32)
+        else:
+            f = np.atleast_1d(np.asarray(fill, dtype=np.float32))
+            if f.ndim != 1 or len(f) > 3 or not np.all((f >= 0) & (f <= 1)):
+                raise ValueError(f"fill is a value in [0, 1] or one per channel, got {fill!r}")
+        self.fill = np.concatenate([f, np.repeat(f[-1:], 3 - len(f))]).astype(np.float32)      # three entries, as the row carries them
+        self.aug_rng = np.random.default_rng([self.seed, 0x617567])          # a fourth stream: the crop, mix and photo rows do not move
+        if self.antialias and self.augmenting():
+            raise ValueError("antialias=True together with randaugment= or hue= is not provided: the antialiased resize has no aug kernel")
 
     ERASE_MODES = ("zero", "black", "pixel")
+    AUG_OPS = ("Identity", "Invert", "Brightness", "Contrast", "Color", "Posterize", "Solarize", "SolarizeAdd", "Hue")      # a program step's op code
+    RA_GEOMETRIC = ("Rotate", "ShearX", "ShearY", "TranslateX", "TranslateY")
+    # timm's increasing set (rand-...-inc1) without AutoContrast, Equalize and Sharpness
+    RA_OPS = ("Invert", "Rotate", "Posterize", "Solarize", "SolarizeAdd", "Color", "Contrast", "Brightness", "ShearX", "ShearY", "TranslateX", "TranslateY")
+
+    @staticmethod
+    def _parse_randaugment(spec):
+        """(n, m) or timm's "rand-m7-n4-mstd0.5[-inc1]" -> (n, m, mstd).  timm's defaults for a field left out: m 10, n 2, mstd 0."""
+        if isinstance(spec, str):
+            parts = spec.split("-")
+            if parts[0] != "rand":
+                raise ValueError(f"randaugment: {spec!r} does not start with 'rand'")
+            n, m, mstd = 2, 10.0, 0.0
+            for part in parts[1:]:
+                key = part.rstrip("0123456789.")
+                val = part[len(key):]
+                try:
+                    if key not in ("m", "n", "mstd", "inc") or not val:
+                        raise ValueError
+                    if key == "n":
+                        n = int(val)
+                    elif key == "m":
+                        m = float(val)
+                    elif key == "mstd":
+                        mstd = float(val)
+                    elif int(val) != 1:
+                        raise ValueError
+                except ValueError:
+                    raise ValueError(f"randaugment: the field {part!r} of {spec!r} is not provided (m, n, mstd and inc1 are)") from None
+        else:
+            (n, m), mstd = spec, 0.0
+            n, m = int(n), float(m)
+        if not (0 <= n <= 8 and 0.0 <= m <= 10.0 and 0.0 <= mstd < float("inf")):
+            raise ValueError(f"randaugment needs 0 <= n <= 8, 0 <= m <= 10 and a finite mstd >= 0, got n = {n}, m = {m}, mstd = {mstd}")
+        return n, m, mstd
+
+    def augmenting(self):
+        """Whether this transform draws RandAugment ops or a hue shift (``kernel()`` is then "aug" and ClipPipeline carries aug rows)."""
+        return self.train and (self.randaugment is not None or self.hue > 0)
+
+    @staticmethod
+    def _affine(name, level, Ho, Wo):
+        """timm's PIL matrix (a, b, c, d, e, f) of one geometric op at a signed level, output -> input, as a 3 x 3 float64 matrix."""
+        M = np.eye(3)
+        if name == "Rotate":                                # PIL's Image.rotate(level degrees) about (Wo / 2, Ho / 2)
+            a = -np.deg2rad(level)
+            M[0, :2], M[1, :2] = (np.cos(a), np.sin(a)), (-np.sin(a), np.cos(a))
+            cx, cy = Wo / 2.0, Ho / 2.0
+            M[0, 2] = M[0, 0] * -cx + M[0, 1] * -cy + cx
+            M[1, 2] = M[1, 0] * -cx + M[1, 1] * -cy + cy
+        elif name == "ShearX":
+            M[0, 1] = level
+        elif name == "ShearY":
+            M[1, 0] = level
+        elif name == "TranslateX":
+            M[0, 2] = level * Wo
+        else:
+            M[1, 2] = level * Ho
+        return M
+
+    def sample_aug(self, B, Ho, Wo):
+        """-> int32 [B,32]: one aug row {flags, n, (op, arg) x 8, M[6] as fp32 bits, fill[3] as fp32 bits, 0 x 5} per clip for
+        hyb_clip_aug_u8_transform.  A clip that draws nothing gets the identity row: no geometry, an empty program.  Per drawn op four draws
+        are made whatever comes of them (the op, applied or not, the magnitude's normal deviate, the sign), then two for the hue."""
+        rows = np.zeros((B, 32), dtype=np.int32)
+        rows[:, 18:24] = np.asarray([1, 0, 0, 0, 1, 0], dtype=np.float32).view(np.int32)
+        rows[:, 24:27] = self.fill.view(np.int32)
+        if not self.augmenting():
+            return rows
+        g = self.aug_rng
+        n, m, mstd = self.randaugment if self.randaugment is not None else (0, 0.0, 0.0)
+        for b in range(B):
+            M, geo, prog = np.eye(3), False, []
+            for _ in range(n):
+                name = self.ra_ops[int(g.integers(0, len(self.ra_ops)))]
+                applied, z, negative = g.random() < self.ra_prob, g.standard_normal(), g.random() < 0.5
+                if not applied:
+                    continue
+                L = min(max(m + mstd * z, 0.0), 10.0) / 10.0
+                sign = -1.0 if negative else 1.0
+                if name in self.RA_GEOMETRIC:
+                    level = sign * L * {"Rotate": 30.0, "ShearX": 0.3, "ShearY": 0.3, "TranslateX": 0.45, "TranslateY": 0.45}[name]
+                    M, geo = M @ self._affine(name, level, Ho, Wo), True      # op 1 then op 2: M1 o M2
+                elif name in ("Brightness", "Contrast", "Color"):
+                    prog.append((self.AUG_OPS.index(name), int(np.float32(max(0.1, 1.0 + sign * 0.9 * L)).view(np.int32))))
+                elif name == "Posterize":
+                    prog.append((5, 4 - int(4 * L)))
+                elif name == "Solarize":
+                    prog.append((6, 256 - int(256 * L)))
+                elif name == "SolarizeAdd":
+                    prog.append((7, int(110 * L)))
+                else:
+                    prog.append((1, 0))
+            if self.hue > 0:
+                jitter, u = g.random() < self.jitter_prob, g.uniform(-self.hue, self.hue)
+                if jitter:
+                    prog.append((8, int(np.float32(u).view(np.int32))))
+            rows[b, 0], rows[b, 1] = int(geo), len(prog)
+            for i, (op, arg) in enumerate(prog):
+                rows[b, 2 + 2 * i], rows[b, 3 + 2 * i] = op, arg
+            if geo:
+                rows[b, 18:24] = M[:2].reshape(6).astype(np.float32).view(np.int32)
+        return rows
 
     def photometric(self):
         """Whether this transform jitters, grays, adds noise or erases (``kernel()`` says what ClipPipeline then calls)."""
@@ -374,8 +535,9 @@ class ClipTransform:
                                or self.erase_prob > 0)
 
     def needs_luma(self):
-        """Whether a contrast factor other than 1 may be drawn: the kernel then needs hyb_clips_u8_luma_sums for its pivot."""
-        return self.train and self.contrast > 0
+        """Whether a contrast factor other than 1 may be drawn, by the jitter or as a RandAugment Contrast step: the kernel then needs
+        hyb_clips_u8_luma_sums for its pivot."""
+        return self.train and (self.contrast > 0 or (self.randaugment is not None and self.randaugment[0] > 0 and "Contrast" in self.ra_ops))
 
     def _erase_box(self, Ho, Wo):
         """torchvision's RandomErasing.get_params: up to 10 tries of area x log-uniform ratio that fit strictly inside, else no box."""
@@ -418,13 +580,17 @@ class ClipTransform:
         return rows
 
     def kernel(self):
-        """Which device transform ClipPipeline runs for this transform: a key of ops.CLIP_OPS.  The first that applies of
+        """Which device transform ClipPipeline runs for this transform: a key of ops.CLIP_OPS (or, for "aug", ops.CLIP_OPS_EXT).  The first that
+        applies of
+          "aug"    hyb_clip_aug_u8_transform     randaugment= or hue= is on (``augmenting()``), with mixing and the photometric options or without
           "photo"  hyb_clips_u8_transform_photo  a photometric option is on (``photometric()``), with mixing or without
           "aa"     hyb_clips_u8_transform_aa     antialias=True, for the training rows (V = 1) and the evaluation views alike
           "views"  hyb_clips_u8_transform_views  more than one evaluation view per clip (``views`` > 1)
           "mix"    hyb_clips_u8_transform_mix    Mixup / CutMix (``mixing()``)
           "plain"  hyb_clips_u8_transform        everything else: train=False switches mixing and the photometric options off
         This is the only statement of the rule."""
+        if self.augmenting():
+            return "aug"
         if self.photometric():
             return "photo"
         if self.antialias:

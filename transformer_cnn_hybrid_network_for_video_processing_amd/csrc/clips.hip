@@ -15,12 +15,13 @@
 // output frames, so the clip index, its parameter row and the clamps are wave-uniform.
 //
 // Four kernels share the rule: the plain kernel, the mix kernel (Mixup / CutMix), the photo kernel (colour jitter, noise, erasing) and the
-// views kernel (V evaluation views of every source clip, hyb_clips_u8_transform_views).  The plain, mix, photo and luma kernels are to keep
+// views kernel (V evaluation views of every source clip, hyb_clips_u8_transform_views); a fifth, the aug kernel (RandAugment's ops and a hue
+// shift, hyb_clip_aug_u8_transform), puts an affine map in front of the rule and a program of pointwise steps behind it.  The plain, mix, photo and luma kernels are to keep
 // their instruction schedules: a new variant is a new kernel built from clip_row / clip_taps / clip_pixel, not a change to one of them.
 // The antialiased resize (hyb_clips_u8_transform_aa, the last kernel of the file) has a rule and an access pattern of its own: a separable
 // triangle filter through LDS, with barriers.
 //
-// The host side is at the end of the file and is written once for the five transforms: an entry point fills a HybClipJob (kind, pointers,
+// The host side is at the end of the file and is written once for the six transforms: an entry point fills a HybClipJob (kind, pointers,
 // extents), hyb_clip_ok is the one validity rule -- a shared body and a table row per kind -- and hyb_clip_launch the one launch rule: frames,
 // the 16-byte store condition, the grid and one switch over the kinds.  A new variant is a kind, a row in the check and a case in the launch.
 #include "hyb_common.h"
@@ -482,6 +483,345 @@ __global__ __launch_bounds__(256) void clips_u8_transform_photo_kernel(const uns
     }
 }
 
+// ---- RandAugment's ops and a hue shift (hyb_clip_aug_u8_transform; include/hybrid_hip.h has the rule in full): one more int32 row of 32 per clip,
+// {flags, n, (op, arg) x 8, M[6], fill[3], 0 x 5}.  The kernels above stay as they were written, so photo_values is not touched: aug_photo_tail
+// below is its steps 2-6 once more -- a further copy of that arithmetic, see the note above clips_u8_transform_kernel: change all or none.
+// tests/test_gpu_randaug.py (identity aug rows against the photo kernel with torch.equal) is what catches a copy that was forgotten.
+// The identity photo row, for photo == NULL
+__device__ __forceinline__ PhotoRow photo_identity() {
+    PhotoRow h;
+    h.fb = h.fc = h.fs = 1.f; h.mu = 0.f; h.sigma = 0.f; h.steps = 0x24; h.gray = false; h.seed = 0ull;
+    h.ey0 = h.ex0 = h.eh = h.ew = 0; h.mode = 0;
+    return h;
+}
+__device__ __forceinline__ bool aug_finite(int bits) { return (bits & 0x7f800000) != 0x7f800000; }
+// The geometry of one aug row: on only with the flag and a finite M.  Wave-uniform.
+struct AugGeo { bool on; float m[6], fill[3]; };
+__device__ __forceinline__ AugGeo aug_geo(const int* __restrict__ a) {
+    AugGeo g;
+    g.on = (a[0] & 1) != 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        g.on = g.on && aug_finite(a[18 + i]);
+        g.m[i] = __int_as_float(a[18 + i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float f = __int_as_float(a[24 + i]);
+        g.fill[i] = !(f >= 0.f) ? 0.f : (f > 1.f ? 1.f : f);
+    }
+    return g;
+}
+// Step 1 with the geometry: output pixel -> point of the un-augmented output frame -> point of the crop, ONE bilinear gather there.  The
+// coordinates are per lane and per pixel: the VEC pixels of a lane share neither row taps nor the in / out test.  Every operation is rounded as
+// written (tests/randaug_ref.py restates them one by one in fp32); the fused ones are written as fmaf.
+template <int VEC>
+__device__ __forceinline__ void aug_resample(float (&v)[3][VEC], const ClipRow& r, const AugGeo& g, int oy, int ox0, int Win, int C, int Ho, int Wo) {
+#pragma clang fp contract(off)
+    const float yc = (float)oy + 0.5f;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        const float xc = (float)(ox0 + j) + 0.5f;
+        float x = fmaf(g.m[0], xc, fmaf(g.m[1], yc, g.m[2]));
+        const float y = fmaf(g.m[3], xc, fmaf(g.m[4], yc, g.m[5]));
+        if (!(x >= 0.f && x < (float)Wo && y >= 0.f && y < (float)Ho)) {      // a NaN is outside
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][j] = g.fill[c];
+            continue;
+        }
+        if (r.flip) x = (float)Wo - x;
+        const float sx = (x * (float)r.cw) / (float)Wo - 0.5f, sy = (y * (float)r.ch) / (float)Ho - 0.5f;      // in [-1/2, cw - 1/2] and [-1/2, ch - 1/2)
+        const float flx = floorf(sx), fly = floorf(sy);
+        const float fx = sx - flx, fy = sy - fly;
+        // the taps are clamped into the crop whatever the coordinates were: no value reads outside src
+        const int ix = clampi((int)flx, -1, r.cw), iy = clampi((int)fly, -1, r.ch);
+        const int ix0 = clampi(ix, 0, r.cw - 1), ix1 = clampi(ix + 1, 0, r.cw - 1);
+        const int iy0 = clampi(iy, 0, r.ch - 1), iy1 = clampi(iy + 1, 0, r.ch - 1);
+        const unsigned row0 = (unsigned)(((r.y0 + iy0) * Win + r.x0) * C), row1 = (unsigned)(((r.y0 + iy1) * Win + r.x0) * C);      // < 2^30, as in clip_taps
+        const unsigned c0 = (unsigned)(ix0 * C), c1 = (unsigned)(ix1 * C);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+            v[c][j] = clip_unit(r.fb, row0, row1, c0, c1, fx, fy, c);
+        }
+    }
+}
+// The byte of a value in [0, 1]: floor(255 v + 1/2)
+__device__ __forceinline__ int aug_byte(float v) { return (int)floorf(255.f * v + 0.5f); }
+// torchvision's adjust_hue on one pixel (_rgb2hsv, h <- (h + shift) mod 1, _hsv2rgb), every operation rounded, none fused
+__device__ __forceinline__ void aug_hue(float& r, float& g, float& b, float shift) {
+#pragma clang fp contract(off)
+    const float mx = fmaxf(fmaxf(r, g), b), mn = fminf(fminf(r, g), b);
+    const float cr = mx - mn;
+    const bool eq = mx == mn;
+    const float s = cr / (eq ? 1.f : mx), d = eq ? 1.f : cr;
+    const float rc = (mx - r) / d, gc = (mx - g) / d, bc = (mx - b) / d;
+    float hh = mx == r ? bc - gc : (mx == g ? 2.f + rc - bc : 4.f + gc - rc);
+    hh = hh / 6.f + 1.f;
+    hh = hh - floorf(hh);
+    hh = hh + shift;
+    hh = hh - floorf(hh);
+    const float h6 = hh * 6.f, fl = floorf(h6), f = h6 - fl;
+    int i = (int)fl;
+    i = i >= 6 ? i - 6 : i;
+    const float p = clamp01(mx * (1.f - s)), q = clamp01(mx * (1.f - s * f)), t = clamp01(mx * (1.f - s * (1.f - f)));
+    r = i == 0 ? mx : (i == 1 ? q : (i == 2 ? p : (i == 3 ? p : (i == 4 ? t : mx))));
+    g = i == 0 ? t : (i == 1 ? mx : (i == 2 ? mx : (i == 3 ? q : p)));
+    b = i == 0 ? p : (i == 1 ? p : (i == 2 ? t : (i == 3 ? mx : (i == 4 ? mx : q))));
+}
+// Step 1a: the row's program on a lane's VEC pixels.  The steps are read from the row as they are run (scalar loads, scalar branches).
+template <int VEC>
+__device__ __forceinline__ void aug_program(float (&v)[3][VEC], const int* __restrict__ a, const long long* __restrict__ luma_sums, long long b,
+                                            const ClipRow& r, int C, int Tout) {
+    const int n = clampi(a[1], 0, 8);
+    bool need_mu = false;
+    for (int s = 0; s < n; ++s) need_mu |= a[2 + 2 * s] == 3 && luma_sums && photo_factor(a[3 + 2 * s]) != 1.f;
+    float mu = 0.f;
+    if (need_mu) {
+        // the clip's mean luma as photo_row forms it
+        long long sum = 0;
+        for (int t = 0; t < Tout; ++t) sum += luma_sums[b * Tout + t];
+        mu = (float)((double)sum / (10000.0 * 255.0 * (double)r.ch * (double)r.cw * (double)Tout));
+    }
+#pragma unroll 1
+    for (int s = 0; s < n; ++s) {
+        const int op = a[2 + 2 * s], arg = a[3 + 2 * s];
+        if (op == 1) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c >= C) break;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) v[c][j] = 1.f - v[c][j];
+            }
+            mu = 1.f - mu;
+        } else if (op == 2) {
+            const float f = photo_factor(arg);
+            if (f != 1.f) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c >= C) break;
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) v[c][j] = clamp01(f * v[c][j]);
+                }
+            }
+            mu = fminf(f * mu, 1.f);
+        } else if (op == 3) {
+            const float f = luma_sums ? photo_factor(arg) : 1.f;
+            if (f != 1.f) {
+                const float add = (1.f - f) * mu;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c >= C) break;
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) v[c][j] = clamp01(f * v[c][j] + add);
+                }
+            }
+        } else if (op == 4) {
+            const float f = photo_factor(arg);
+            if (f != 1.f && C == 3) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    const float add = (1.f - f) * photo_luma(v[0][j], v[1][j], v[2][j]);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) v[c][j] = clamp01(f * v[c][j] + add);
+                }
+            }
+        } else if (op == 5) {
+            const int mask = ~((1 << (8 - clampi(arg, 0, 8))) - 1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c >= C) break;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) v[c][j] = (float)(aug_byte(v[c][j]) & mask) / 255.0f;
+            }
+        } else if (op == 6) {
+            const int thr = clampi(arg, 0, 256);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c >= C) break;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) v[c][j] = aug_byte(v[c][j]) >= thr ? 1.f - v[c][j] : v[c][j];
+            }
+        } else if (op == 7) {
+            const float add = (float)clampi(arg, 0, 255) / 255.0f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c >= C) break;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) v[c][j] = aug_byte(v[c][j]) < 128 ? fminf(1.f, v[c][j] + add) : v[c][j];
+            }
+        } else if (op == 8) {
+            float h = __int_as_float(arg);
+            h = !(h == h) ? 0.f : fminf(fmaxf(h, -0.5f), 0.5f);
+            if (h != 0.f && C == 3) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) aug_hue(v[0][j], v[1][j], v[2][j], h);
+            }
+        }
+    }
+}
+// Steps 2-6 of the photo rule on values that are already resampled: photo_values from its first jitter step on, expression for expression
+template <int VEC>
+__device__ __forceinline__ void aug_photo_tail(float (&v)[3][VEC], const PhotoRow& h, int t, int oy, int ox0, int C, int Tout, int Ho, int Wo,
+                                               const float* __restrict__ mean_invstd) {
+#pragma unroll
+    for (int step = 0; step < 3; ++step) {
+        const int op = h.steps >> (2 * step) & 3;
+        if (op == 0) {
+            if (h.fb != 1.f) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c >= C) break;
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) v[c][j] = clamp01(h.fb * v[c][j]);
+                }
+            }
+        } else if (op == 1) {
+            if (h.fc != 1.f) {
+                const float add = (1.f - h.fc) * h.mu;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c >= C) break;
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) v[c][j] = clamp01(h.fc * v[c][j] + add);
+                }
+            }
+        } else if (h.fs != 1.f && C == 3) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                const float add = (1.f - h.fs) * photo_luma(v[0][j], v[1][j], v[2][j]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][j] = clamp01(h.fs * v[c][j] + add);
+            }
+        }
+    }
+    if (h.gray && C == 3) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) v[0][j] = v[1][j] = v[2][j] = photo_luma(v[0][j], v[1][j], v[2][j]);
+    }
+    const unsigned long long plane = (unsigned long long)Ho * Wo;
+    if (h.sigma != 0.f) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+            const unsigned long long e0 = ((unsigned long long)(t * C + c) * Ho + oy) * Wo + ox0;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) v[c][j] = clamp01(v[c][j] + h.sigma * photo_normal(h.seed, e0 + j));
+        }
+    }
+    if (mean_invstd) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) v[c][j] = (v[c][j] - mean_invstd[c]) * mean_invstd[C + c];
+        }
+    }
+    if (oy >= h.ey0 && oy < h.ey0 + h.eh && h.ew > 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+            const unsigned long long e0 = ((unsigned long long)(t * C + c) * Ho + oy) * Wo + ox0 + (unsigned long long)Tout * C * plane;
+            const float black = mean_invstd ? (0.f - mean_invstd[c]) * mean_invstd[C + c] : 0.f;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                if (ox0 + j >= h.ex0 && ox0 + j < h.ex0 + h.ew) v[c][j] = h.mode == 0 ? 0.f : (h.mode == 1 ? black : photo_normal(h.seed, e0 + j));
+            }
+        }
+    }
+}
+
+// The photo kernel's grid, its stores and its two-sided mix loop; the clip, its four rows, the program and M are wave-uniform, the program's steps
+// and "geometry or integer taps" are scalar branches, and only the coordinates and the in / out test of the geometry vary per lane.
+template <int VEC>
+__global__ __launch_bounds__(256) void clips_u8_transform_aug_kernel(const unsigned char* __restrict__ src, const int* __restrict__ params,
+                                                                     const int* __restrict__ mix, const int* __restrict__ photo,
+                                                                     const int* __restrict__ aug, const long long* __restrict__ luma_sums,
+                                                                     const float* __restrict__ mean_invstd, float* __restrict__ dst, long long frames,
+                                                                     int B, int Tin, int Hin, int Win, int C, int Tout, int Ho, int Wo) {
+    const int Wq = Wo / VEC;
+    const unsigned pos = blockIdx.x * 256u + threadIdx.x;
+    if (pos >= (unsigned)(Ho * Wq)) return;
+    const int oy = (int)(pos / (unsigned)Wq), ox0 = ((int)pos - oy * Wq) * VEC;
+    const long long frame_bytes = (long long)Hin * Win * C;
+    for (long long f = blockIdx.y; f < frames; f += gridDim.y) {
+        const long long b = f / Tout;
+        const int t = (int)(f - b * Tout);
+        int kind = 0;
+        const int* m = mix ? mix + b * 8 : nullptr;
+        if (m) kind = m[1];
+        if (kind < 0 || kind > 2) kind = 0;
+        float lam = 1.f;
+        bool own_needed = true, oth_needed = false, in[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) in[j] = false;
+        if (kind == 1) {
+            lam = __int_as_float(m[6]);
+            lam = !(lam <= 1.f) ? 1.f : (lam < 0.f ? 0.f : lam);        // into [0, 1]; a NaN counts as 1
+            oth_needed = true;
+        } else if (kind == 2) {
+            const int by0 = clampi(m[2], 0, Ho), bx0 = clampi(m[3], 0, Wo);
+            const int bh = clampi(m[4], 0, Ho - by0), bw = clampi(m[5], 0, Wo - bx0);
+            const bool inrow = oy >= by0 && oy < by0 + bh;
+            own_needed = false;
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                in[j] = inrow && ox0 + j >= bx0 && ox0 + j < bx0 + bw;
+                oth_needed |= in[j];
+                own_needed |= !in[j];
+            }
+        }
+        // (the photo kernel's loop: one copy of the chain's instructions serves the clip and its partner)
+        float res[3][VEC];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) res[c][j] = 0.f;
+        }
+#pragma unroll 1
+        for (int side = 0; side < 2; ++side) {
+            if (!(side == 0 ? own_needed : oth_needed)) continue;
+            const long long sb = side == 0 ? b : (long long)clampi(m[0], 0, B - 1);      // the partner's own params, aug and photo rows
+            const ClipRow r = clip_row(src, params, sb, t, Tin, Hin, Win, frame_bytes);
+            const PhotoRow h = photo ? photo_row(photo, luma_sums, sb, r, Tout, Ho, Wo) : photo_identity();
+            const int* a = aug + sb * 32;
+            const AugGeo g = aug_geo(a);
+            float cur[3][VEC];
+            if (g.on) {
+                aug_resample<VEC>(cur, r, g, oy, ox0, Win, C, Ho, Wo);
+            } else {
+                const ClipTaps<VEC> k = clip_taps<VEC>(r, oy, ox0, Win, C, Ho, Wo);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    if (c >= C) break;
+#pragma unroll
+                    for (int j = 0; j < VEC; ++j) cur[c][j] = clip_unit(r.fb, k.row0, k.row1, k.c0[j], k.c1[j], k.fx[j], k.fy, c);
+                }
+            }
+            aug_program<VEC>(cur, a, luma_sums, sb, r, C, Tout);
+            aug_photo_tail<VEC>(cur, h, t, oy, ox0, C, Tout, Ho, Wo, mean_invstd);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (c >= C) break;
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) {
+                    if (side == 0) res[c][j] = cur[c][j];
+                    else if (kind == 1) res[c][j] = mixup_blend(lam, res[c][j], cur[c][j]);
+                    else if (in[j]) res[c][j] = cur[c][j];
+                }
+            }
+        }
+        float* out = dst + (f * C * Ho + oy) * (long long)Wo + ox0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= C) break;
+            float* oc = out + (long long)c * Ho * Wo;
+            if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(oc) = f32x4{res[c][0], res[c][1], res[c][2], res[c][3]};
+            else oc[0] = res[c][0];
+        }
+    }
+}
+
 // ---- hyb_clips_u8_luma_sums: the integer luma sum of every output frame's source crop, for the contrast pivot.  blockIdx.y is the output
 // frame, the blockIdx.x workgroups of a frame take its crop rows in turn.  A row is a run of cw * C consecutive bytes: its 16-byte aligned
 // middle is read as 16-byte loads, one per lane, the up to 15 bytes in front of and behind it one byte per lane.  For C == 3 a chunk's bytes are
@@ -751,22 +1091,24 @@ __global__ __launch_bounds__(256) void clips_u8_transform_aa_kernel(const unsign
 // hyb_clip_launch; nothing below them restates a limit, the 16-byte rule or a grid.  A new variant is a kind, a row in CLIP_KINDS and a case in
 // hyb_clip_launch's switch.
 namespace {
-enum HybClipKind { HYB_CLIP_PLAIN, HYB_CLIP_MIX, HYB_CLIP_VIEWS, HYB_CLIP_PHOTO, HYB_CLIP_AA };
+enum HybClipKind { HYB_CLIP_PLAIN, HYB_CLIP_MIX, HYB_CLIP_VIEWS, HYB_CLIP_PHOTO, HYB_CLIP_AA, HYB_CLIP_AUG };
 struct HybClipJob {
     int kind;
     const unsigned char* src; const int* params; const int* mix; const int* photo; const long long* luma_sums; const float* mean_invstd; float* dst;
     int B, V, Tin, Hin, Win, C, Tout, Ho, Wo;
+    const int* aug = nullptr;          // the aug rows, behind the extents: the five older jobs are written without them
 };
 constexpr int CLIP_MAX_EXTENT = 16384;       // Hin, Win, Ho, Wo: the rule's integer products stay below 2^31
 // What a kind asks beyond the shared rule: the row pointers it cannot do without, whether it takes V rows per source clip (else V is 1), and
 // whether it needs a luma (defined for grey and RGB: C == 1 or C == 3; else C <= 4).  luma_sums and mean_invstd are optional everywhere.
-struct ClipKindRule { bool needs_mix, needs_photo, has_views, luma; };
+struct ClipKindRule { bool needs_mix, needs_photo, has_views, luma, needs_aug; };
 constexpr ClipKindRule CLIP_KINDS[] = {
-    /* HYB_CLIP_PLAIN */ {false, false, false, false},
-    /* HYB_CLIP_MIX   */ {true, false, false, false},
-    /* HYB_CLIP_VIEWS */ {false, false, true, false},
-    /* HYB_CLIP_PHOTO */ {false, true, false, true},       // (mix is optional here)
-    /* HYB_CLIP_AA    */ {false, false, true, false},
+    /* HYB_CLIP_PLAIN */ {false, false, false, false, false},
+    /* HYB_CLIP_MIX   */ {true, false, false, false, false},
+    /* HYB_CLIP_VIEWS */ {false, false, true, false, false},
+    /* HYB_CLIP_PHOTO */ {false, true, false, true, false},       // (mix is optional here)
+    /* HYB_CLIP_AA    */ {false, false, true, false, false},
+    /* HYB_CLIP_AUG   */ {false, false, false, true, true},       // (mix and photo are optional here)
 };
 
 // The source side of the rule, which hyb_clips_u8_luma_sums shares: the bytes, the parameter rows, their extents and the channel count
@@ -780,7 +1122,7 @@ int hyb_clip_ok(const HybClipJob& j) {
     const ClipKindRule& k = CLIP_KINDS[j.kind];
     HYB_CHECK_ARG(clip_src_ok(j.src, j.params, j.B, j.Tin, j.Hin, j.Win, j.C, j.Tout, k.luma));
     HYB_CHECK_ARG(j.dst && j.Ho > 0 && j.Wo > 0 && j.Ho <= CLIP_MAX_EXTENT && j.Wo <= CLIP_MAX_EXTENT);
-    HYB_CHECK_ARG((j.mix || !k.needs_mix) && (j.photo || !k.needs_photo));
+    HYB_CHECK_ARG((j.mix || !k.needs_mix) && (j.photo || !k.needs_photo) && (j.aug || !k.needs_aug));
     // the output clips are counted in int
     HYB_CHECK_ARG(k.has_views ? j.V >= 1 && (long long)j.B * j.V <= 2147483647LL : j.V == 1);
     return 0;
@@ -809,6 +1151,8 @@ int hyb_clip_launch(const HybClipJob& j, hipStream_t st) {
         CLIP_CASE(HYB_CLIP_PHOTO, clips_u8_transform_photo_kernel, j.src, j.params, j.mix, j.photo, j.luma_sums, j.mean_invstd, j.dst, frames, j.B,
                   CLIP_EXTENTS);
         CLIP_CASE(HYB_CLIP_AA, clips_u8_transform_aa_kernel, j.src, j.params, j.mean_invstd, j.dst, frames, j.V, CLIP_EXTENTS);
+        CLIP_CASE(HYB_CLIP_AUG, clips_u8_transform_aug_kernel, j.src, j.params, j.mix, j.photo, j.aug, j.luma_sums, j.mean_invstd, j.dst, frames, j.B,
+                  CLIP_EXTENTS);
     }
 #undef CLIP_EXTENTS
 #undef CLIP_CASE
@@ -846,6 +1190,12 @@ extern "C" int hyb_clips_u8_transform_photo(const unsigned char* src, const int*
 extern "C" int hyb_clips_u8_transform_aa(const unsigned char* src, const int* params, const float* mean_invstd, float* dst, int B, int V, int Tin, int Hin,
                                          int Win, int C, int Tout, int Ho, int Wo, void* stream) {
     return hyb_clip_run({HYB_CLIP_AA, src, params, nullptr, nullptr, nullptr, mean_invstd, dst, B, V, Tin, Hin, Win, C, Tout, Ho, Wo}, stream);
+}
+
+extern "C" int hyb_clip_aug_u8_transform(const unsigned char* src, const int* params, const int* mix, const int* photo, const int* aug,
+                                         const long long* luma_sums, const float* mean_invstd, float* dst, int B, int Tin, int Hin, int Win, int C, int Tout,
+                                         int Ho, int Wo, void* stream) {
+    return hyb_clip_run({HYB_CLIP_AUG, src, params, mix, photo, luma_sums, mean_invstd, dst, B, 1, Tin, Hin, Win, C, Tout, Ho, Wo, aug}, stream);
 }
 
 // No job: no dst, a memset in front and a grid over the crop rows.  The source side of the check is the jobs'.

@@ -33,6 +33,7 @@ fake kernel and an autograd kernel per operator.
     hybrid::clip_transform_mix   ... with Mixup / CutMix against a partner clip in the same pass   (one more int32 row per clip)
     hybrid::clip_transform_photo ... with colour jitter, grayscale, Gaussian noise and random erasing too   (one int32 row of 16 per clip)
     hybrid::clip_luma_sums       integer luma sums of the source crops: the contrast pivot of clip_transform_photo
+    hybrid::clip_transform_aug   ... with RandAugment's ops (an affine map in the resampling, a program of pointwise steps) and a hue shift too
     hybrid::clip_transform_views V evaluation views (windows x crops) of every source clip in one launch: V rows per clip, the source read in place
     hybrid::clip_transform_aa    clip_transform_views with the antialiased resize (torchvision's Resize(antialias=True)): a separable triangle filter
     hybrid::eval_metrics_    one launch behind the logits that adds loss, top-1 / top-k, confusion matrix into a meter's state (no autograd formula)
@@ -1193,6 +1194,7 @@ _CLIP_ROWS = {
     "photo": (torch.int32, 16, "one row {brightness, contrast, saturation bits, order, gray, sigma bits, seed lo, seed hi, ey0, ex0, eh, ew, mode, "
                                "0, 0, 0} per clip"),
     "luma_sums": (torch.int64, None, "hybrid::clip_luma_sums of the same src, params and Tout"),
+    "aug": (torch.int32, 32, "one row {flags, n, (op, arg) x 8, M[6] bits, fill[3] bits, 0 x 5} per clip"),
 }
 
 
@@ -1230,6 +1232,15 @@ CLIP_OPS = {
 }
 
 
+# The transforms added behind the five above, keyed the same way; clip_transform_into looks here as well.  (CLIP_OPS keeps its five keys: they are
+# the answers ClipTransform.kernel() has over the older options.)
+CLIP_OPS_EXT = {
+    "aug": _clip_op("clip_transform_aug", "hyb_clip_aug_u8_transform",
+                    "(Tensor src, Tensor params, Tensor? mix, Tensor? photo, Tensor aug, Tensor? luma_sums, Tensor? mean_invstd, int Tout, int Ho, int Wo) "
+                    "-> Tensor", luma=True, says="clip_transform"),
+}
+
+
 def _clip_check(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo):
     dims = _clip_dims(op.says, src, params, mean_invstd, V if op.views else None, Tout, Ho, Wo)
     if op.luma and dims[4] not in (1, 3):
@@ -1251,7 +1262,7 @@ def _clip_args(op, a):
 
 
 def _clip_run(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo, out=None, stream=None):
-    """The one body of the five transforms: check, allocate [B*V,Tout,C,Ho,Wo] (or take `out`), one call of the row's entry point."""
+    """The one body of the transforms: check, allocate [B*V,Tout,C,Ho,Wo] (or take `out`), one call of the row's entry point."""
     _require_cuda(src, params, *rows, mean_invstd, out)
     V, Tout, Ho, Wo = int(V), int(Tout), int(Ho), int(Wo)
     B, Tin, Hin, Win, C = _clip_check(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo)
@@ -1272,8 +1283,8 @@ def _clip_fake(op, src, params, rows, mean_invstd, V, Tout, Ho, Wo):
 
 def clip_transform_into(kind, out, src, params, mean_invstd=None, V=1, stream=None, **rows):
     """The transform ClipTransform.kernel() names, written into a tensor the caller keeps (ClipPipeline's slots) on `stream`: the operator's
-    checks and the operator's call.  rows: mix= / photo= / luma_sums=, of which the kind takes its own."""
-    op = CLIP_OPS[kind]
+    checks and the operator's call.  rows: mix= / photo= / luma_sums= / aug=, of which the kind takes its own."""
+    op = CLIP_OPS[kind] if kind in CLIP_OPS else CLIP_OPS_EXT[kind]
     return _clip_run(op, src, params, [rows.get(name) for name, _ in op.rows], mean_invstd, V, out.shape[1], out.shape[3], out.shape[4], out, stream)
 
 
@@ -1309,6 +1320,14 @@ def clip_transform_photo(src, params, mix, photo, luma_sums, mean_invstd, Tout, 
     the same pass.  mix: rows of clip_transform_mix or None; luma_sums: clip_luma_sums(src, params, Tout), needed when a contrast factor may
     differ from 1, else None."""
     return torch.ops.hybrid.clip_transform_photo(src, params, mix, photo, luma_sums, mean_invstd, int(Tout), int(Ho), int(Wo))
+
+
+def clip_transform_aug(src, params, mix, photo, aug, luma_sums, mean_invstd, Tout, Ho, Wo):
+    """clip_transform_photo with aug rows int32 [B,32] (ClipTransform.sample_aug): RandAugment's geometric ops folded into one affine map inside
+    the resampling, its photometric ops and a hue shift as a program of up to 8 pointwise steps in front of the jitter.  mix, photo: rows of
+    clip_transform_mix / clip_transform_photo or None (None: nothing mixes / identity photo rows); luma_sums: clip_luma_sums(src, params, Tout),
+    needed when a Contrast step or a contrast factor may occur, else None."""
+    return torch.ops.hybrid.clip_transform_aug(src, params, mix, photo, aug, luma_sums, mean_invstd, int(Tout), int(Ho), int(Wo))
 
 
 def clip_luma_sums_op(src: Tensor, params: Tensor, Tout: int) -> Tensor:
@@ -1810,7 +1829,7 @@ def _define_clip_op(op):
     _LIB.impl(op.name, _inference_only(op.name), "Autograd")
 
 
-for _op in CLIP_OPS.values():
+for _op in (*CLIP_OPS.values(), *CLIP_OPS_EXT.values()):
     _define_clip_op(_op)
 _define("clip_luma_sums", "(Tensor src, Tensor params, int Tout) -> Tensor", clip_luma_sums_op, clip_luma_sums_fake)
 _LIB.impl("clip_luma_sums", _inference_only("clip_luma_sums"), "Autograd")
